@@ -17,11 +17,11 @@ env.step of every env = one launch of step_kernel.  Envs shard across ranks with
 (weak scaling: 65 536 envs per GPU); the episode-boundary trajectory all-gather of config 4 is timed as a
 separate, clearly labelled leg and is NOT part of `value`.
 
-The step loop is captured into ONE HIP graph of lcm(--steps, 1250) env steps - a whole number of --steps regions AND of box sequences, with
-the setpoint switches inside the graph - so that neither host launch overhead nor graph seams nor per-replay setpoint copies sit between
-the kernels (round 3; tools/graph_chunk_sweep.py measures what they cost).  Exactly --warmup steps run untimed first.  The timed region is
-exactly --steps env steps, repeated `repeats` times back to back (reported; a multiple of the graph's own repeat count, chosen so that the
-region lasts >= 10 ms); ms_per_step = time / (steps x repeats).
+Exactly --warmup steps run untimed first.  The timed region is exactly --steps env steps, captured into HIP graphs with the setpoint
+switches inside them (one graph of the --steps steps; past 7 500 steps a graph of whole box sequences replayed several times and one of
+the rest) so that no host launch overhead sits between the kernels (tools/graph_chunk_sweep.py measures what it costs); ms_per_step =
+time of the timed region / --steps.  --dump-outputs DIR writes what the last timed step returned (obs, reward, done) as .npy files; the
+inputs (start poses, actions) are seeded, the same from run to run.
 """
 import argparse
 import json
@@ -42,7 +42,7 @@ PER_ENV_BYTES_MOVED = 177 + 4 + 128                # what the kernel's layout mo
 HBM_PEAK_GBPS = 8000.0                             # MI355X_MICROARCH.md: 8.0 TB/s spec
 ALGO_FLOPS_PER_ENV_STEP = 20 * 80 + 400            # ~80 flop per plant sub-step (semi-implicit Euler, 20 x 10 ms) + ~400 decode / trig / reward
 VALU_PEAK_TFLOPS = 157.3                           # MI355X_MICROARCH.md: peak fp32 vector
-MIN_TIMED_MS = 10.0
+DUMP_LIMIT = 64 << 20                              # bytes --dump-outputs may write in all
 # algorithmic bytes per env-step of the other measured kernels (each stated where it is used)
 ROLLOUT_BYTES_MOVED = 28 + 36 + 4 + 1              # dpenv_rollout: action row in; obs row, reward, done out (state stays in registers)
 POLICY_ROWS_BYTES_F32 = 36 + 28 + 4 + 4 + 4 + 4 + 1      # dpenv_policy_rollout: obs 36 | act 28 | rew | val | logp | boot | done written, nothing read
@@ -154,10 +154,13 @@ def parse():
     ap.add_argument('--no-fused', action='store_true', help='skip the fused-rollout leg')
     ap.add_argument('--cpu-seconds', type=float, default=14.0, help='budget of the CPU baseline leg (half 1 thread, half all cores)')
     ap.add_argument('--policy-form', default='auto', choices=['auto', 'one_wave', 'two_wave'], help='launch form of the closed-loop legs')
-    ap.add_argument('--graph-steps', type=int, default=0, help='profiling form: capture ONE graph of this many env steps (from sequence position '
-                                                                 '--warmup) and replay it; the box sequence then does not advance between replays '
-                                                                 '(default 0: one graph of lcm(steps, 1250) steps, the whole sequence)')
-    ap.add_argument('--repeats', type=int, default=0, help='repeats of the timed --steps region (0 = enough for %g ms)' % MIN_TIMED_MS)
+    ap.add_argument('--graph-steps', type=int, default=0, help='profiling form: capture graphs of this many env steps (from sequence position '
+                                                                 '--warmup) and replay them; the box sequence then restarts with every replay '
+                                                                 '(default 0: one graph of the --steps steps)')
+    ap.add_argument('--repeats', type=int, default=1, help='run the timed --steps region this many times back to back (default 1); a profiling run '
+                                                          'of a short region needs enough repeats for a steady state (tools/profile_round.sh)')
+    ap.add_argument('--dump-outputs', default='', metavar='DIR', help='write what the last timed step returned - obs, reward, done - to DIR/<name>.npy '
+                                                                     '(float32; a fixed sample of the envs past %d MB)' % (DUMP_LIMIT >> 20))
     ap.add_argument('--gather', type=int, default=-1, help='time the config-4 trajectory all-gather (default: on if gpus > 1)')
     ap.add_argument('--hold-plant', action='store_true', help='diagnostic: skip the plant sub-steps (INVALID as a result)')
     ap.add_argument('--backend', default='nccl', help="'nccl' (= RCCL; default) or 'gloo' (rehearsal only)")
@@ -878,6 +881,25 @@ def eager_record(env, actions, dev):
             'bound': 'gpu' if h_c < ev else 'host'}
 
 
+def dump_outputs(out_dir, arrays, rank, world):
+    """--dump-outputs: the arrays {name: tensor [n, ...]} as out_dir/<name>.npy in float32 (rank r of several: r<r>_<name>.npy), at most
+    DUMP_LIMIT bytes over all ranks.  Past that, the same seeded sample of env rows from every array, its indices in env_index.npy."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    host = {k: v.detach().float().cpu().numpy() for k, v in arrays.items()}
+    n = next(iter(host.values())).shape[0]
+    row_bytes = sum(a[0].nbytes for a in host.values())
+    limit = DUMP_LIMIT // world
+    if n * row_bytes > limit:
+        m = (limit - 64 * 1024) // (row_bytes + 8)
+        idx = np.sort(np.random.RandomState(0).choice(n, m, replace=False))
+        host = {k: a[idx] for k, a in host.items()}
+        host['env_index'] = idx.astype(np.float64)
+    pre = 'r%d_' % rank if world > 1 else ''
+    for k, a in host.items():
+        np.save(os.path.join(out_dir, pre + k + '.npy'), np.ascontiguousarray(a))
+
+
 def main():
     args = parse()
     pool_environment()                                  # the same on the torchrun-launched and on the self-launched path, before `import torch`
@@ -969,28 +991,27 @@ def main():
     def step_at(t):
         env.step(actions[t % NA], new_ref=ref_for(t), out=(obs, rew, done))
 
-    # Launch form of the timed region.  One HIP graph holds G = lcm(K, 1250) env steps = G / K back-to-back repeats of the K-step region,
-    # with the setpoint switches INSIDE the graph (new_ref at the switch steps): every replay then starts at the same point of the box
-    # sequence, the host issues nothing between the kernels, and the seam between two graph replays - 0.1-0.6 us per step for graphs of
-    # 10-50 steps plus a setpoint copy before every replay (tools/graph_chunk_sweep.py: 5.29 us per step for 50-step graphs with the copy,
-    # 5.10 for >= 250-step graphs without) - is host launch overhead, not env.step.  For a K whose lcm with 1250 is too long, or with
-    # --no-graph, the steps are launched one by one (slower: the host is then in the loop).
-    from math import gcd
-    G = K * SEQ // gcd(K, SEQ)
-    aligned = G <= 7500
-    if not aligned:
-        # an awkward --steps: the graph holds the smallest whole number of K-step regions that covers one box sequence, and the sequence
-        # restarts with every replay (its last leg - back at the start pose - is up to K - 1 steps longer); said in config.launch
-        G = K * (-(-SEQ // K))
+    # Launch form of the timed region: exactly K env steps from sequence position W, the setpoint switches of the box sequence at their
+    # own steps.  They are captured into HIP graphs so that no host launch overhead sits between the kernels: one graph of the K steps,
+    # or, for K > GRAPH_CAP, a graph of C steps (a whole number of box sequences, so that every replay starts at the same point of the
+    # sequence) replayed K // C times and a graph of the K % C steps that remain.  With --no-graph the steps are launched one by one (the
+    # host is then in the loop); --graph-steps S (profiling form) captures S-step graphs and the sequence restarts with every replay.
+    GRAPH_CAP = 6 * SEQ
     if args.graph_steps > 0:
-        G = K * max(1, args.graph_steps // K)           # a whole number of --steps regions; --steps > --graph-steps: one region per graph
-        aligned = False
+        C = min(K, args.graph_steps)
+    else:
+        C = K if K <= GRAPH_CAP else GRAPH_CAP
+    Q, REM = K // C, K % C
     use_graph = not args.no_graph
-    pos = {'t': 0}
-    for t in range(W):                                 # exactly W untimed warm-up steps, eager
-        step_at(t)
-    pos['t'] = W
-    graph = None
+
+    def begin():
+        """the start pose, then exactly W untimed warm-up steps, eager: the state every timed region starts from"""
+        env.reset(init=init, new_ref=start.clone())
+        for t in range(W):
+            step_at(t)
+
+    begin()
+    graphs = []
     if use_graph:
         s_ = torch.cuda.Stream(device=dev)
         s_.wait_stream(torch.cuda.current_stream(dev))
@@ -998,48 +1019,36 @@ def main():
             step_at(W)                                # warm the launch path before capture (one extra untimed step, state only)
         torch.cuda.current_stream(dev).wait_stream(s_)
         torch.cuda.synchronize(dev)
-        env.reset(init=init, new_ref=start.clone())   # back to the start pose: the graph is captured from sequence position W
-        for t in range(W):
-            step_at(t)
-        graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(graph):
-            for s_i in range(G):
-                step_at(W + s_i)
+        for m, reps in ((C, Q), (REM, 1)):
+            if m and reps:
+                gr = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(gr):
+                    for s_i in range(m):
+                        step_at(W + s_i)
+                graphs.append((gr, reps))
+        for gr, _ in graphs:                          # one untimed replay each: the first replay of a graph also uploads it
+            gr.replay()
+        torch.cuda.synchronize(dev)
+        begin()                                       # back to the state after the W warm-up steps
 
     def run_region():
-        """G env steps (= G / K repeats of the K-step region) from sequence position W (mod 1250)"""
-        if graph is not None:
-            graph.replay()
+        """the K timed env steps from sequence position W (mod 1250)"""
+        if use_graph:
+            for gr, reps in graphs:
+                for _ in range(reps):
+                    gr.replay()
         else:
-            for s_i in range(G):
-                step_at(pos['t'] + s_i)
-        pos['t'] += G
+            for s_i in range(K):
+                step_at(W + s_i)
 
-    # how often to replay so that the timed region lasts >= MIN_TIMED_MS: from one untimed pass (also a warm-up of the graph)
-    cal0, cal1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    torch.cuda.synchronize(dev)
-    cal0.record()
-    run_region()
-    cal1.record()
-    torch.cuda.synchronize(dev)
-    per_region = G // K                                 # repeats of the K-step region inside one graph
-    if args.repeats > 0:
-        RG = max(1, -(-args.repeats // per_region))
-    else:
-        RG = max(1, int(-(-MIN_TIMED_MS // max(cal0.elapsed_time(cal1), 1e-3))))
-    if world > 1:
-        rt = torch.tensor([RG], device=dev, dtype=torch.int64)
-        dist.all_reduce(rt, op=dist.ReduceOp.MAX)      # every rank times the same amount of work
-        RG = int(rt[0])
-    R = RG * per_region
-    C = G
+    R = max(1, args.repeats)                           # 1 unless asked for: the region runs R times back to back, the state carrying on
     ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     if world > 1:
         dist.barrier()
     torch.cuda.synchronize(dev)
     t0 = time.perf_counter()
     ev0.record()
-    for _ in range(RG):
+    for _ in range(R):
         run_region()
     ev1.record()
     torch.cuda.synchronize(dev)
@@ -1059,6 +1068,8 @@ def main():
         per_rank_ev = [ev_ms * 1e-3]
     wall = float(tt[0])
     KR = K * R                                          # env steps inside the timed region
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {'obs': obs, 'reward': rew, 'done': done}, rank, world)
     assert bool(torch.isfinite(obs).all()) and bool(torch.isfinite(rew).all()), 'non-finite outputs'
     # the other legs run whole 50-step launches: at least 1 250 steps each (25 launches: a 5-launch leg is dominated by launch latency
     # and clock ramp), more when --steps asks for more
@@ -1085,10 +1096,10 @@ def main():
         except Exception:
             pass
         valu_tflops = ALGO_FLOPS_PER_ENV_STEP * n / kern_s / 1e12
-        launch = ('one launch per step from the host (no graph)' if graph is None else
-                  'hipGraph replay, %d env steps per graph (%d repeats of the %d-step region%s)' % (
-                      G, per_region, K, ', box-sequence switches inside the graph' if aligned else
-                      '; PROFILING FORM: the sequence does not advance' if args.graph_steps > 0 else '; the sequence restarts with every replay'))
+        launch = ('one launch per step from the host (no graph)' if not use_graph else
+                  'hipGraph replay: %s; box-sequence switches inside the graph%s' % (
+                      ' + '.join('%d x %d env steps' % (reps, gr_steps) for gr_steps, reps in ((C, Q), (REM, 1)) if gr_steps and reps),
+                      '; PROFILING FORM: the sequence restarts with every replay' if args.graph_steps > 0 and C < K else ''))
         res = {
             'metric': 'env-steps/sec at 65536 parallel envs' + (' [DIAGNOSTIC hold_plant: INVALID]' if args.hold_plant else ''), 'value': total_envs * KR / wall, 'unit': 'env-steps/s',
             'n_gpus': world, 'steps': K, 'warmup': W, 'repeats': R, 'ms_per_step': wall / KR * 1e3, 'higher_is_better': True,
@@ -1097,7 +1108,7 @@ def main():
                                    'setpoint sequence (switch steps 50/300/550/700/950 of 1250), terminate off, fp32' % n,
                        'envs_per_gpu': n, 'total_envs': total_envs, 'integrator': 'semi-implicit Euler 20 x 10 ms',
                        'launch': launch,
-                       'timed_region': '%d steps x %d repeats back to back = %d graph replay(s) (%.1f ms)' % (K, R, RG, wall * 1e3),
+                       'timed_region': '%d steps x %d repeat(s) back to back (%.3f ms)' % (K, R, wall * 1e3),
                        'sharding': 'independent env shards, no data-path collective',
                        'backend': args.backend if world > 1 else None},
             'roofline': {'bound': 'hbm', 'achieved': achieved, 'peak': HBM_PEAK_GBPS, 'unit': 'GB/s',

@@ -2,6 +2,7 @@
 """Fixture that pins the network GRAPH to the reference's own file.
 
     python3 -B tests/golden/gen_final_graph.py            (build container only: needs /root/reference)
+    python3 -B tests/golden/gen_final_graph.py --check    (the same: checks the committed fixtures against the reference's files)
 
 Reads src/rl/windows_workspace/data/finalmodel/finconttothighbowder_s0/tf1_save/saved_model.pb - the GraphDef that
 tf.saved_model.simple_save wrote for the thesis' final policy (spinup/utils/logx.py:161-228) - with ml4ca_amd/tf_graph.py (no
@@ -89,5 +90,31 @@ def main():
     print('hidden activation', rec['hidden_activation'], 'constants', {k: v for k, v in consts.items() if k.startswith('pi/')})
 
 
+def check():
+    """The committed fixtures against the reference's own files, without writing anything: the checkpoint's variables are those of
+    final_policy.npz, the graph's forward nodes those of final_graph.json, and ActorCritic.from_saved_model loads the fixture's weights."""
+    from ml4ca_amd import tf_graph as G
+    from ml4ca_amd.policy import ActorCritic
+    from ml4ca_amd.tf_checkpoint import read_bundle
+    d = np.load(os.path.join(OUT, 'final_policy.npz'))
+    t = {k.replace('.', '/'): d[k] for k in d.files if '.' in k}
+    assert sum(v.size for v in t.values()) == 28175
+    b = read_bundle(os.path.join(MODEL, 'variables', 'variables'))
+    assert sum(v.size for v in b.values()) == 84529          # SURVEY section 2 row 18: 28 175 parameters + Adam slots
+    for k, v in t.items():
+        assert np.array_equal(b[k], v), k
+    rec = json.load(open(os.path.join(OUT, 'final_graph.json')))
+    g = G.read_saved_model(os.path.join(MODEL, 'saved_model.pb'))
+    assert len(g.order) == rec['nodes_in_file'] and G.ancestors(g, rec['fetches']) == rec['order']
+    for n in rec['order']:
+        nd = rec['forward_nodes'][n]
+        assert g.nodes[n]['op'] == nd['op'] and g.nodes[n]['inputs'] == nd['inputs'], n
+    ac = ActorCritic.from_saved_model(MODEL)
+    assert (ac.obs_dim, ac.act_dim, ac.hidden_sizes, ac.activation) == (9, 7, (80, 80, 80), 'leaky') and np.float32(ac.leak) == np.float32(0.2)
+    for k, v in ac.state_dict().items():
+        assert np.array_equal(v, t[k]), k
+    print('final_policy.npz and final_graph.json match the reference\'s checkpoint and saved graph')
+
+
 if __name__ == '__main__':
-    main()
+    check() if '--check' in sys.argv[1:] else main()

@@ -233,7 +233,7 @@ def test_two_wave_policy_rollout_full_size_soak():
     assert int(c1[1].min()) >= 1                    # every env went through at least one in-kernel reset
 
 
-def test_bench_line_with_every_record_at_reduced_size():
+def test_bench_line_with_every_record_at_reduced_size(tmp_path):
     """bench.py end to end on one GPU at reduced size: the ONE stdout line (contract keys, roofline, compact cpu_baseline; under 4 KB, and
     stdout + stderr together under the 8 KB tail the driver keeps) and the side records in bench_side.json: cpu_baseline with its legs and the
     per-quantity error ledger, the side legs, the config-4 record (every leg present, no error) and the vessel-class record.  The N > 1 runs of the driver
@@ -243,7 +243,7 @@ def test_bench_line_with_every_record_at_reduced_size():
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    side_path = os.path.join(root, 'gpurun_out', 'bench_side_test.json') if os.path.isdir(os.path.join(root, 'gpurun_out')) else '/tmp/bench_side_test.json'
+    side_path = str(tmp_path / 'bench_side_test.json')
     p = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--envs', '8192', '--steps', '100', '--warmup', '50', '--cpu-seconds', '1.5',
                         '--config4', '1', '--config4-envs', '4096', '--classes', '3', '--side-json', side_path], capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stderr[-3000:]
@@ -288,7 +288,7 @@ def test_bench_line_with_every_record_at_reduced_size():
     assert {'classes_1', 'classes_3', 'classes_16'} <= set(vc) and vc['classes_3']['step_us'] > 0
 
 
-def test_bench_two_ranks_started_by_bench_itself_on_one_gpu():
+def test_bench_two_ranks_started_by_bench_itself_on_one_gpu(tmp_path):
     """The N > 1 bench line end to end, as far as one GPU allows: `python bench.py --gpus 2` with no launcher around it starts its two
     ranks as a child process, both use this GPU (--same-device) and talk over gloo; the line must carry the headline (2 x envs), the
     process-group record (2 ranks, their pids) and every leg of the config-4 record, collectives included.  What the driver's N > 1 runs
@@ -301,7 +301,7 @@ def test_bench_two_ranks_started_by_bench_itself_on_one_gpu():
     env = dict(os.environ)
     for k in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK'):
         env.pop(k, None)
-    side_path = os.path.join(root, 'gpurun_out', 'bench_side_test2.json') if os.path.isdir(os.path.join(root, 'gpurun_out')) else '/tmp/bench_side_test2.json'
+    side_path = str(tmp_path / 'bench_side_test2.json')
     p = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', '2', '--backend', 'gloo', '--same-device', '--envs', '4096',
                         '--steps', '20', '--warmup', '5', '--config4-envs', '1024', '--side-json', side_path], capture_output=True, text=True, timeout=900, env=env)
     assert p.returncode == 0, p.stderr[-3000:]
@@ -326,7 +326,7 @@ def test_bench_two_ranks_started_by_bench_itself_on_one_gpu():
     assert {'chunks_1', 'chunks_4', 'chunks_8'} <= set(c4['exchange_compact'])
 
 
-def test_bench_side_records_cannot_cost_the_headline_line():
+def test_bench_side_records_cannot_cost_the_headline_line(tmp_path):
     """bench.py --side-timeout: a per-rank watchdog ends a run whose side records do not finish (a hung collective of the config-4 record on a node
     it was never run on) with the exit code of a successful run - the ONE stdout line is already out, stderr says what happened."""
     import json
@@ -335,8 +335,47 @@ def test_bench_side_records_cannot_cost_the_headline_line():
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     p = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--envs', '8192', '--steps', '20', '--warmup', '5', '--cpu-seconds', '0.6',
-                        '--side-timeout', '0.2', '--side-json', '/tmp/bench_side_watchdog.json'], capture_output=True, text=True, timeout=300)
+                        '--side-timeout', '0.2', '--side-json', str(tmp_path / 'bench_side_watchdog.json')], capture_output=True, text=True, timeout=300)
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [l for l in p.stdout.splitlines() if l.startswith('{')]
     assert len(lines) == 1 and 'roofline' in json.loads(lines[0]) and 'cpu_baseline' in json.loads(lines[0])
     assert 'side records still running after' in p.stderr and 'exit code 0' in p.stderr
+
+
+def test_bench_dump_outputs_are_the_last_timed_step(tmp_path):
+    """bench.py --dump-outputs DIR: after exactly --steps timed steps the arrays the last one returned (obs, reward, done) are in DIR as
+    float32 .npy files; the graph-replayed timed region writes what the same steps launched one by one write, bit for bit - across a
+    setpoint switch (steps 5-64), past one graph's length (7 600 steps: a 7 500-step graph and a 100-step one) and with the region run
+    twice back to back (--repeats 2: the state carries on, the setpoints of the same steps are applied again)."""
+    import json
+    import os
+    import subprocess
+    import sys
+    import numpy as np
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    n = 8192
+
+    def run(tag, steps, *extra, repeats=1):
+        d = tmp_path / tag
+        p = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--envs', str(n), '--steps', str(steps), '--warmup', '5',
+                            '--no-cpu-baseline', '--side-legs', '0', '--eager-loop', '0', '--multi-handle', '0', '--config4', '0', '--side-json', '',
+                            '--repeats', str(repeats), '--dump-outputs', str(d)] + list(extra), capture_output=True, text=True, timeout=300)
+        assert p.returncode == 0, p.stderr[-3000:]
+        lines = [l for l in p.stdout.splitlines() if l.startswith('{')]
+        assert len(lines) == 1, p.stdout[-2000:]
+        r = json.loads(lines[0])
+        assert r['steps'] == steps and r['repeats'] == repeats and r['ms_per_step'] > 0
+        out = {k: np.load(str(d / (k + '.npy'))) for k in ('obs', 'reward', 'done')}
+        assert sorted(os.listdir(str(d))) == ['done.npy', 'obs.npy', 'reward.npy']
+        assert out['obs'].shape == (n, 9) and out['reward'].shape == (n,) and out['done'].shape == (n,)
+        assert all(a.dtype == np.float32 for a in out.values()) and np.isfinite(out['obs']).all()
+        return out
+
+    got = {}
+    for steps, repeats in ((60, 1), (7600, 1), (60, 2)):
+        g = run('graph_%d_%d' % (steps, repeats), steps, repeats=repeats)
+        e = run('eager_%d_%d' % (steps, repeats), steps, '--no-graph', repeats=repeats)
+        for k in g:
+            assert np.array_equal(g[k], e[k]), (steps, repeats, k)
+        got[steps, repeats] = g
+    assert not np.array_equal(got[60, 1]['obs'], got[60, 2]['obs'])   # the second repeat stepped on from where the first ended

@@ -564,3 +564,33 @@ def test_dynpos_fit_preset_against_every_recorded_pin():
     # with the thrust loss on top: the surge pins of the second set as before, yaw under losses still near the recorded 0.52
     m = F.manoeuvres(both.astype(np.float64))
     assert abs(m['surge_ahead'] - 1.40) < 0.01 and abs(m['surge_astern'] + 1.10) < 0.01 and abs(m['yaw'] - 0.52) < 0.035
+
+
+def test_bench_dump_outputs_samples_past_the_limit(tmp_path, monkeypatch):
+    """bench.dump_outputs past DUMP_LIMIT: every array keeps the same seeded sample of env rows, the indices go to env_index.npy
+    (float64, exact), the files of all ranks together stay under the limit; under it the arrays are written whole, without an index."""
+    import torch
+    import bench
+    n = 20000
+    g = torch.Generator().manual_seed(0)
+    arrays = {'obs': torch.randn((n, 9), generator=g), 'reward': torch.randn(n, generator=g),
+              'done': torch.randint(0, 4, (n,), generator=g, dtype=torch.uint8)}
+    bench.dump_outputs(str(tmp_path / 'whole'), arrays, 0, 1)
+    assert sorted(os.listdir(str(tmp_path / 'whole'))) == ['done.npy', 'obs.npy', 'reward.npy']
+    assert np.array_equal(np.load(str(tmp_path / 'whole' / 'obs.npy')), arrays['obs'].numpy())
+    monkeypatch.setattr(bench, 'DUMP_LIMIT', 1 << 20)
+    world = 2
+    for rank in range(world):
+        bench.dump_outputs(str(tmp_path / 'sampled'), arrays, rank, world)
+    d = tmp_path / 'sampled'
+    files = sorted(os.listdir(str(d)))
+    assert files == sorted('r%d_%s.npy' % (r, k) for r in range(world) for k in ('done', 'env_index', 'obs', 'reward'))
+    assert sum(os.path.getsize(str(d / f)) for f in files) <= 1 << 20
+    for rank in range(world):
+        idx = np.load(str(d / ('r%d_env_index.npy' % rank)))
+        assert idx.dtype == np.float64 and 0 < idx.size < n and np.all(np.diff(idx) > 0) and idx.max() < n
+        ii = idx.astype(np.int64)
+        for k, a in arrays.items():
+            got = np.load(str(d / ('r%d_%s.npy' % (rank, k))))
+            assert got.dtype == np.float32 and np.array_equal(got, a.float().numpy()[ii]), k
+    assert np.array_equal(np.load(str(d / 'r0_env_index.npy')), np.load(str(d / 'r1_env_index.npy')))

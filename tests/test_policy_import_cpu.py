@@ -2,6 +2,7 @@
 reference's variable names, fp32 torch forward pass against the committed float64 expectations of the shipped
 model, and the evaluation metrics."""
 import os
+import struct
 
 import numpy as np
 import pytest
@@ -10,7 +11,6 @@ G = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden')
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FIX = os.path.join(ROOT, 'tests', 'golden', 'final_policy.npz')
-REF_CKPT = '/root/reference/src/rl/windows_workspace/data/finalmodel/finconttothighbowder_s0/tf1_save/variables/variables'
 
 
 def fixture_tensors():
@@ -33,17 +33,6 @@ def test_bundle_roundtrip(tmp_path):
         (tmp_path / 'bad.index').write_bytes(b'\\x00' * 64)
         (tmp_path / 'bad.data-00000-of-00001').write_bytes(b'')
         read_bundle(str(tmp_path / 'bad'))
-
-
-@pytest.mark.skipif(not os.path.exists(REF_CKPT + '.index'), reason='reference tree only exists in the build container')
-def test_reader_on_the_reference_checkpoint_matches_fixture():
-    from ml4ca_amd.tf_checkpoint import read_bundle
-    b = read_bundle(REF_CKPT)
-    assert sum(v.size for v in b.values()) == 84529          # 28 175 parameters + Adam slots
-    t, _ = fixture_tensors()
-    assert sum(v.size for v in t.values()) == 28175
-    for k, v in t.items():
-        assert np.array_equal(b[k], v), k
 
 
 def test_actor_critic_from_reference_names_and_forward():
@@ -216,9 +205,6 @@ def test_policy_yardstick_reproduces_the_checkpoint_fixture():
 
 
 # ---- the network GRAPH pinned to the reference's own saved_model.pb (tests/golden/gen_final_graph.py) -----------------------------
-REF_MODEL = '/root/reference/src/rl/windows_workspace/data/finalmodel/finconttothighbowder_s0/tf1_save'
-
-
 def graph_fixture():
     import json
     rec = json.load(open(os.path.join(G, 'final_graph.json')))
@@ -302,17 +288,161 @@ def test_yardstick_and_torch_reference_against_an_execution_of_the_saved_graph()
         TG.evaluate(bad, ['extra'], {'Placeholder': obs}, t)
 
 
-@pytest.mark.skipif(not os.path.exists(os.path.join(REF_MODEL, 'saved_model.pb')), reason='reference tree only exists in the build container')
-def test_graph_reader_on_the_reference_file_matches_the_fixture():
+# ---- a SavedModel written from the committed graph fixture: read_saved_model and ActorCritic.from_saved_model in the suite -----------
+def _pb_varint(v):
+    out = bytearray()
+    while True:
+        b, v = v & 0x7f, v >> 7
+        out.append(b | (0x80 if v else 0))
+        if not v:
+            return bytes(out)
+
+
+def _pb(num, payload):
+    """one field: an int is a varint (wire type 0), bytes / str are length-delimited (wire type 2)"""
+    if isinstance(payload, int):
+        return _pb_varint(num << 3) + _pb_varint(payload)
+    if isinstance(payload, str):
+        payload = payload.encode()
+    return _pb_varint((num << 3) | 2) + _pb_varint(len(payload)) + payload
+
+
+def _pb_tensor(a):
+    """TensorProto the way TensorFlow writes constants: scalars in float_val / int_val (packed), larger tensors in tensor_content"""
+    enum = {np.dtype(np.float32): 1, np.dtype(np.int32): 3}[a.dtype]
+    shape = b''.join(_pb(2, _pb(1, int(s))) for s in a.shape)
+    body = _pb(1, enum) + _pb(2, shape)
+    if a.size == 1 and a.dtype == np.float32:
+        body += _pb(5, a.astype('<f4').tobytes())
+    elif a.size == 1:
+        body += _pb(7, b''.join(_pb_varint(int(x) & ((1 << 64) - 1)) for x in a.reshape(-1)))
+    else:
+        body += _pb(4, a.astype(a.dtype.newbyteorder('<')).tobytes())
+    return body
+
+
+def _pb_attr(v):
+    if isinstance(v, np.ndarray):
+        return _pb(8, _pb_tensor(v))
+    if isinstance(v, bool):
+        return _pb(5, int(v))
+    if isinstance(v, (list, tuple)) and len(v) == 2 and v[0] == 'dtype':
+        return _pb(6, int(v[1]))
+    if isinstance(v, (list, tuple)):
+        return _pb(1, _pb(3, b''.join(_pb_varint(int(x) & ((1 << 64) - 1)) for x in v)))
+    raise TypeError(v)
+
+
+def _saved_model_bytes(rec, nodes):
+    gd = b''
+    for i, name in enumerate(rec['order']):
+        nd = nodes[name]
+        body = _pb(1, name) + _pb(2, nd['op'])
+        for k, inp in enumerate(nd['inputs']):
+            body += _pb(3, inp if k % 2 == 0 else inp + ':0')           # ':0' names the same tensor; the reader strips it
+        if i == len(rec['order']) - 1 and i > 0:
+            body += _pb(3, '^' + rec['order'][0])                    # a control input: not a data input
+        for k in sorted(nd['attr']):
+            body += _pb(5, _pb(1, k) + _pb(2, _pb_attr(nd['attr'][k])))
+        gd += _pb(1, body)
+    sig = b''
+    for field, key in ((1, 'inputs'), (2, 'outputs')):
+        for k, t in sorted(rec['signature'][key].items()):
+            sig += _pb(field, _pb(1, k) + _pb(2, _pb(1, t)))
+    mg = _pb(2, gd) + _pb(5, _pb(1, 'serving_default') + _pb(2, sig))
+    return _pb(1, 1) + _pb(2, mg)
+
+
+def test_saved_model_reader_on_a_file_written_from_the_graph_fixture(tmp_path):
+    """tf_graph.read_saved_model and ActorCritic.from_saved_model on a SavedModel encoded here, field by field, from the committed
+    forward graph (final_graph.json) and weights (final_policy.npz): the nodes, their order, attributes and the signature come back as
+    the fixture holds them, and the model loads with the fixture's topology, activation, slope and weights."""
+    import torch
     from ml4ca_amd import tf_graph as TG
     from ml4ca_amd.policy import ActorCritic
-    rec, nodes, _ = graph_fixture()
-    g = TG.read_saved_model(os.path.join(REF_MODEL, 'saved_model.pb'))
-    assert len(g.order) == rec['nodes_in_file'] and TG.ancestors(g, rec['fetches']) == rec['order']
+    from ml4ca_amd.tf_checkpoint import write_bundle
+    rec, nodes, vec = graph_fixture()
+    (tmp_path / 'variables').mkdir()
+    (tmp_path / 'saved_model.pb').write_bytes(_saved_model_bytes(rec, nodes))
+    t, d = fixture_tensors()
+    write_bundle(str(tmp_path / 'variables' / 'variables'), t)
+    g = TG.read_saved_model(str(tmp_path / 'saved_model.pb'))
+    assert g.order == rec['order'] and g.signature == rec['signature']
     for n in rec['order']:
-        assert g.nodes[n]['op'] == nodes[n]['op'] and g.nodes[n]['inputs'] == nodes[n]['inputs'], n
-    ac = ActorCritic.from_saved_model(REF_MODEL)
+        got, want = g.nodes[n], nodes[n]
+        assert got['op'] == want['op'] and got['inputs'] == want['inputs'], n
+        assert sorted(got['attr']) == sorted(want['attr']), n
+        for k, v in want['attr'].items():
+            if isinstance(v, np.ndarray):
+                assert got['attr'][k].dtype == v.dtype and np.array_equal(got['attr'][k], v), (n, k)
+            else:
+                assert list(got['attr'][k]) == list(v) if isinstance(v, (list, tuple)) else got['attr'][k] == v, (n, k)
+    assert TG.ancestors(g, rec['fetches']) == rec['order']
+    ac = ActorCritic.from_saved_model(str(tmp_path))
     assert (ac.obs_dim, ac.act_dim, ac.hidden_sizes, ac.activation) == (9, 7, (80, 80, 80), 'leaky') and np.float32(ac.leak) == np.float32(0.2)
-    t, _ = fixture_tensors()
     for k, v in ac.state_dict().items():
         assert np.array_equal(v, t[k]), k
+    mu, v = ac.forward_ref(torch.tensor(vec['obs'], dtype=torch.float32))
+    assert np.abs(mu.numpy() - vec['mu_f64']).max() < 1e-5 * max(1.0, np.abs(vec['mu_f64']).max())
+
+
+def _sst_block(entries, restart_interval=16):
+    """a LevelDB table block as TensorFlow's table builder writes it: keys prefix-compressed against the previous key, a restart
+    point (full key) every `restart_interval` entries"""
+    body, restarts, prev = bytearray(), [], b''
+    for i, (k, v) in enumerate(entries):
+        shared = 0
+        if i % restart_interval:
+            while shared < min(len(k), len(prev)) and k[shared] == prev[shared]:
+                shared += 1
+        else:
+            restarts.append(len(body))
+        body += _pb_varint(shared) + _pb_varint(len(k) - shared) + _pb_varint(len(v)) + k[shared:] + v
+        prev = k
+    for r in restarts or [0]:
+        body += struct.pack('<I', r)
+    return bytes(body) + struct.pack('<I', len(restarts or [0]))
+
+
+def test_bundle_reader_on_a_prefix_compressed_multi_block_index(tmp_path):
+    """read_bundle on an index laid out as TensorFlow's writer lays it out and the project's own write_bundle does not: shared key
+    prefixes (pi/dense/bias, pi/dense/bias/Adam, pi/dense/bias/Adam_1 ...), restart points every 16 keys, several data blocks behind a
+    multi-entry index block, non-zero block CRCs, an int64 scalar (global_step) - the fixture's weights and Adam slots come back."""
+    import zlib
+    t, _ = fixture_tensors()
+    rng = np.random.RandomState(3)
+    tensors = dict(t)
+    for k, v in t.items():
+        tensors[k + '/Adam'] = rng.normal(size=v.shape).astype(np.float32)
+        tensors[k + '/Adam_1'] = rng.normal(size=v.shape).astype(np.float32)
+    tensors['beta1_power'] = np.float32(0.9).reshape(())
+    tensors['global_step'] = np.array(123456789012, np.int64).reshape(())
+    names = sorted(tensors)
+    data, entries = bytearray(), [(b'', _pb(1, 1) + _pb(3, _pb(1, 26)))]       # header: num_shards 1, version {producer 26}
+    for name in names:
+        a = np.array(tensors[name], order='C')                                  # keeps 0-d scalars 0-d
+        shape = b''.join(_pb(2, _pb(1, int(s))) for s in a.shape)
+        enum = {np.dtype(np.float32): 1, np.dtype(np.int64): 9}[a.dtype]
+        raw = a.astype(a.dtype.newbyteorder('<')).tobytes()
+        entries.append((name.encode(), _pb(1, enum) + _pb(2, shape) + _pb(4, len(data)) + _pb(5, len(raw)) +
+                        _pb_varint((6 << 3) | 5) + struct.pack('<I', zlib.crc32(raw))))
+        data += raw
+    out, index = bytearray(), []
+    for lo in range(0, len(entries), 7):                                          # 7 entries per data block
+        blk = _sst_block(entries[lo:lo + 7])
+        index.append((entries[min(lo + 6, len(entries) - 1)][0], _pb_varint(len(out)) + _pb_varint(len(blk))))
+        out += blk + b'\x00' + struct.pack('<I', zlib.crc32(blk) | 1)
+    meta_off, meta = len(out), _sst_block([])
+    out += meta + b'\x00' + struct.pack('<I', zlib.crc32(meta) | 1)
+    idx_off, idx = len(out), _sst_block(index, restart_interval=1)
+    out += idx + b'\x00' + struct.pack('<I', zlib.crc32(idx) | 1)
+    footer = _pb_varint(meta_off) + _pb_varint(len(meta)) + _pb_varint(idx_off) + _pb_varint(len(idx))
+    out += footer + b'\x00' * (40 - len(footer)) + struct.pack('<Q', 0xdb4775248b80fb57)
+    (tmp_path / 'variables.index').write_bytes(bytes(out))
+    (tmp_path / 'variables.data-00000-of-00001').write_bytes(bytes(data))
+    from ml4ca_amd.tf_checkpoint import read_bundle
+    b = read_bundle(str(tmp_path / 'variables'))
+    assert sorted(b) == names and len(index) > 2
+    for k in names:
+        assert b[k].dtype == np.asarray(tensors[k]).dtype and b[k].shape == np.asarray(tensors[k]).shape and np.array_equal(b[k], tensors[k]), k
+    assert int(b['global_step']) == 123456789012 and sum(v.size for v in b.values()) == 3 * 28175 + 2

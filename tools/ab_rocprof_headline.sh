@@ -7,7 +7,7 @@ for rep in 1 2; do
 for v in "$@"; do
   tag=$(basename $v .so)_$rep
   export DPENV_LIB=$GRAFT_REPO_ROOT/$v
-  rocprofv3 --kernel-trace --stats --output-format csv -d $O/$tag -- python3 bench.py --graph-steps 50 --steps 50 --warmup 50 --no-cpu-baseline --no-fused --side-legs 0 --eager-loop 0 > $O/$tag.json 2> $O/$tag.err
+  rocprofv3 --kernel-trace --stats --output-format csv -d $O/$tag -- python3 bench.py --graph-steps 50 --steps 50 --repeats 40 --warmup 50 --no-cpu-baseline --no-fused --side-legs 0 --eager-loop 0 > $O/$tag.json 2> $O/$tag.err
   python3 - $O/$tag $tag <<'PY'
 import csv, glob, sys, statistics, json
 f = glob.glob(sys.argv[1] + '/**/*kernel_trace.csv', recursive=True)

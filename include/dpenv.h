@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define DPENV_ABI_VERSION 5
+#define DPENV_ABI_VERSION 6
 
 typedef struct dpenv_s* dpenv_handle;
 typedef void* dpenv_stream; /* hipStream_t; NULL = the null stream */
@@ -460,6 +460,45 @@ int dpenv_adv_apply_stats(float* adv, int64_t count, const double* stats, double
 int dpenv_adv_sum(const float* adv, int64_t count, float* sum_out, dpenv_stream s);
 int dpenv_adv_sumsq(const float* adv, int64_t count, const float* mean, float* sumsq_out, dpenv_stream s);
 int dpenv_adv_apply(float* adv, int64_t count, const float* mean, const float* std, dpenv_stream s);
+
+/* ---- the deployed controller: the trained actor plus the ROS node's body-frame integral action ---------------------------------
+ * (rl_allocator.py:252-273 of the reference).  While it is on, the closed-loop launches apply it once per env step to the pose-error
+ * components e = obs[0:3] as the env forms them (make_obs, whatever wrap_mode the handle uses), with two per-env items of state, the
+ * integrator value I[3] and an int32 count c of control steps since the last (re)arrival, in this f32 order:
+ *     outside = |e0| > box0 || |e1| > box1 || |e2| > box2        (strict >: an error of exactly box is inside, as in the node)
+ *     if outside: I = 0, c = 0
+ *     else:       c = min(c + 1, D); if c >= D: I_j = fminf(fmaxf(I_j + step_s * (gain_j * e_j), -bound_j), bound_j)
+ *     policy input o[0:3] = e + I                                 (o[3:] unchanged)
+ * D is the smallest integer with D * dt > dwell_s (dt = n_substeps * substep_dt, computed in f64): the node's (now - time_arrival) > dwell
+ * test in control steps.  The update happens when the observation after a step is formed - a step that ends an episode updates on its
+ * last observation (what V of that observation, the bootstrap value, sees) and the reset then zeroes I and c: a new episode's first
+ * observation carries I = 0.  A launch's first policy input is rebuilt from the stored state and the stored I with NO update, so two
+ * launches of T/2 write the rows of one launch of T.  Reward, termination and the plant see the true state; only the policy input changes
+ * (the obs rows, last_obs, and the observations val and boot are computed from).
+ * Every reset zeroes I and c: dpenv_reset (for the envs it re-draws), auto-reset and reset_at_end.
+ * Supported: final variant with continuous angles (every arithmetic and launch form; shared hull, classes, per-env hulls, randomisation,
+ * the thrust-loss preset, randomised and drifting current, auto-reset, reset_at_end), limited and full variants (one-wave form); all with
+ * extended_state and a leaky-relu / relu network of hidden width <= 80.  Anything else: DPENV_EINVAL, with the set named.
+ * While it is on, dpenv_step, dpenv_step_ex and dpenv_rollout return DPENV_EINVAL (their observations would lack I): an eager deployment
+ * composes dpenv_step with the law on the host (ml4ca_amd.deploy.BatchedBodyFrameIntegrator). */
+typedef struct dpenv_integral_action {
+    uint32_t struct_size;
+    float gain[3];           /* (0.05, 0.05, 0.05) in the node */
+    float bound[3];          /* |I_j| <= bound_j: (0.5 m, 1.0 m, pi / 32) */
+    float box[3];            /* |e_j| > box_j on any axis resets I and c: (5 m, 5 m, 140 deg in rad) */
+    float dwell_s;           /* 5.0 s: I integrates once c * dt > dwell_s */
+    float step_s;            /* integration step; <= 0 = the control period n_substeps * substep_dt */
+} dpenv_integral_action;
+/* ia = NULL turns the action off (the closed loop runs its original kernels again).  Turning it on zeroes I and c of every env.  Refused:
+ * NaN, negative bounds or box, a negative dwell, and the simple variant (the node refuses it too, rl_allocator.py:126). */
+int dpenv_set_integral_action(dpenv_handle h, const dpenv_integral_action* ia, dpenv_stream s);
+/* The checkpoint path of the action's state, next to dpenv_get_state / dpenv_get_rng_counters: I_out / I_in device float[3][n_envs],
+ * count device int32[n_envs]; either pointer may be NULL.  DPENV_EINVAL while the action is off. */
+int dpenv_get_integral_state(dpenv_handle h, float* I_out, int32_t* count_out, dpenv_stream s);
+int dpenv_set_integral_state(dpenv_handle h, const float* I_in, const int32_t* count_in, dpenv_stream s);
+/* dpenv_policy_rollout with the action on (required), plus integ_out: device float[T][n][3], the I added to obs[t] (NULL = not written),
+ * so that obs[t][0:3] - integ_out[t] is the true error.  Plain dpenv_policy_rollout applies the action as well while it is on. */
+int dpenv_policy_rollout_integral(dpenv_handle h, const dpenv_policy_rollout_io* io, float* integ_out, dpenv_stream s);
 
 int dpenv_abi_version(void);
 

@@ -20,7 +20,7 @@ POLICY_F16, POLICY_F32, POLICY_F32_ACTOR = 0, 1, 2
 LAUNCH_AUTO, LAUNCH_ONE_WAVE, LAUNCH_TWO_WAVE = 0, 1, 2
 DONE_TERMINAL, DONE_TIMELIMIT, DONE_FAULT = 1, 2, 4
 NSTATE, NPARAM, NPARAM_USED, MAX_CLASSES = 15, 32, 32, 64
-ABI_VERSION = 5
+ABI_VERSION = 6
 VESSEL_KEEP_RANDOMISATION = 1          # dpenv_set_vessel_params_ex flag
 
 # canonical state rows (dpenv.h DPENV_S_*)
@@ -74,6 +74,11 @@ class PolicyDesc(C.Structure):
                 ('device_pointers', C.c_int32), ('reserved', C.c_int32)]
 
 
+class IntegralAction(C.Structure):
+    _fields_ = [('struct_size', C.c_uint32), ('gain', C.c_float * 3), ('bound', C.c_float * 3), ('box', C.c_float * 3),
+                ('dwell_s', C.c_float), ('step_s', C.c_float)]
+
+
 # every symbol include/dpenv.h declares: name -> (restype, argtypes)
 _VP, _I32, _I64, _F = C.c_void_p, C.c_int32, C.c_int64, C.c_float
 SYMBOLS = {
@@ -123,6 +128,10 @@ SYMBOLS = {
     'dpenv_adv_sum': (C.c_int, [_VP, _I64, _VP, _VP]),
     'dpenv_adv_sumsq': (C.c_int, [_VP, _I64, _VP, _VP, _VP]),
     'dpenv_adv_apply': (C.c_int, [_VP, _I64, _VP, _VP, _VP]),
+    'dpenv_set_integral_action': (C.c_int, [_VP, C.POINTER(IntegralAction), _VP]),
+    'dpenv_get_integral_state': (C.c_int, [_VP, _VP, _VP, _VP]),
+    'dpenv_set_integral_state': (C.c_int, [_VP, _VP, _VP, _VP]),
+    'dpenv_policy_rollout_integral': (C.c_int, [_VP, C.POINTER(PolicyRolloutIO), _VP, _VP]),
 }
 
 _lib = None

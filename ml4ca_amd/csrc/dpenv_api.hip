@@ -73,6 +73,8 @@ struct dpenv_s {
     int pol_form;           // DPENV_LAUNCH_* requested
     bool has_policy;
     bool lag_valid;         // the state block was last written by a closed-loop launch (PolicyArgs.use_lag)
+    bool integ_on;          // dpenv_set_integral_action: the closed loop runs the *_integ kernels with `integ`
+    IntegArgs integ;        // its parameters and per-env state (float4 [n]: I | count), allocated by the first dpenv_set_integral_action
     int device;
     std::string err;
 };
@@ -334,6 +336,8 @@ extern "C" int dpenv_create(const dpenv_config* cfg, const float* vessel_params,
     h->pol_form = DPENV_LAUNCH_AUTO;
     h->has_policy = false;
     h->lag_valid = false;
+    h->integ_on = false;
+    std::memset(&h->integ, 0, sizeof h->integ);
     std::memset(&h->pol, 0, sizeof h->pol);
 
     VesselDev tab[MAX_CLASSES];
@@ -477,6 +481,7 @@ extern "C" int dpenv_destroy(dpenv_handle h)
     if (h->blob) (void)hipFree(h->blob);
     if (h->pol_buf) (void)hipFree(h->pol_buf);
     if (h->pol_raw) (void)hipFree(h->pol_raw);
+    if (h->integ.state) (void)hipFree(h->integ.state);
     for (int k = 0; k < 2; ++k) if (h->pol_read[k]) (void)hipEventDestroy(h->pol_read[k]);
     if (h->loss_ev) (void)hipEventDestroy(h->loss_ev);
     if (h->loss_host) (void)hipHostFree(h->loss_host);
@@ -744,17 +749,23 @@ extern "C" int dpenv_reset(dpenv_handle h, const uint8_t* mask, const float* ini
     bind_optional(h, a, (hipStream_t)s);
     a.obs = obs_out;
     HIP_TRY(h, dpenv_dev_launch_reset(&a, h->mode, h->cfg.extended_state, mask, init, ref, (hipStream_t)s));
+    if (h->integ_on) HIP_TRY(h, dpenv_dev_launch_integ_clear(h->integ.state, mask, h->cfg.n_envs, (hipStream_t)s));   // new episodes start with I = 0
     // the reset kernel writes the lagged thrust columns (S3) of the envs it re-draws: a full reset makes them valid everywhere, a
     // masked one leaves the validity of the other envs' columns as it was (it used to drop the lag of every env)
     if (!mask) h->lag_valid = true;
     return DPENV_OK;
 }
 
+#define INTEG_OPEN_LOOP_MSG                                                                                                         \
+    "%s: the integral action is on (dpenv_set_integral_action) and this launch's observations would lack I: run the closed loop "    \
+    "(dpenv_policy_rollout), compose the step with the law on the host, or turn the action off"
+
 extern "C" int dpenv_step_ex(dpenv_handle h, const dpenv_step_io* io, dpenv_stream s)
 {
     if (!h) return DPENV_EINVAL;
     DeviceGuard dev_guard(h->device);
     if (!io || io->struct_size != sizeof(dpenv_step_io)) return fail(h, DPENV_EINVAL, "dpenv_step_io ABI mismatch");
+    if (h->integ_on) return fail(h, DPENV_EINVAL, INTEG_OPEN_LOOP_MSG, "dpenv_step");
     if (!io->action || !io->obs || !io->reward || !io->done)
         return fail(h, DPENV_EINVAL, "action, obs, reward and done buffers are required");
     if (classes_missing(h))
@@ -796,6 +807,7 @@ extern "C" int dpenv_rollout(dpenv_handle h, const dpenv_rollout_io* io, dpenv_s
     if (!h) return DPENV_EINVAL;
     DeviceGuard dev_guard(h->device);
     if (!io || io->struct_size != sizeof(dpenv_rollout_io)) return fail(h, DPENV_EINVAL, "dpenv_rollout_io ABI mismatch");
+    if (h->integ_on) return fail(h, DPENV_EINVAL, INTEG_OPEN_LOOP_MSG, "dpenv_rollout");
     if (io->T <= 0 || !io->actions || !io->obs || !io->reward || !io->done)
         return fail(h, DPENV_EINVAL, "T > 0 and action, obs, reward, done blocks are required");
     if (io->n_switch < 0 || io->n_switch > DPENV_MAX_SWITCH || (io->n_switch > 0 && !io->refs))
@@ -1099,9 +1111,8 @@ extern "C" int dpenv_debug_pk_probe(dpenv_handle h, void* out, void* sink, int b
 }
 #endif
 
-extern "C" int dpenv_policy_rollout(dpenv_handle h, const dpenv_policy_rollout_io* io, dpenv_stream s)
+static int policy_rollout_impl(dpenv_handle h, const dpenv_policy_rollout_io* io, float* integ_out, dpenv_stream s)
 {
-    if (!h) return DPENV_EINVAL;
     DeviceGuard dev_guard(h->device);
     if (!h->has_policy) return fail(h, DPENV_EINVAL, "dpenv_set_policy has not been called");
     if (!io || io->struct_size != sizeof(dpenv_policy_rollout_io)) return fail(h, DPENV_EINVAL, "dpenv_policy_rollout_io ABI mismatch");
@@ -1138,11 +1149,101 @@ extern "C" int dpenv_policy_rollout(dpenv_handle h, const dpenv_policy_rollout_i
     const bool shipped = h->mode == MODE_FINAL_CONT && h->cfg.extended_state && pa.act == DPENV_ACT_LEAKY_RELU;
     if ((a.rand_tab || a.loss_on != LOSS_NONE || a.cur_nom) && pa.ws && !shipped) pa.ws = 0;
     // the one-wave kernels (and only they, after the line above) know the thrust loss through the table alone
+    if (h->integ_on) {
+        // the integral action's kernels: the final variant / continuous angles in every form, limited and full in the one-wave form
+        const bool final_cont = h->mode == MODE_FINAL_CONT;
+        if (!(final_cont || h->mode == MODE_LIMITED || h->mode == MODE_FULL) || !h->cfg.extended_state || pa.act != DPENV_ACT_LEAKY_RELU || pa.ks != 5)
+            return fail(h, DPENV_EINVAL, "the integral action runs with the final variant (continuous angles), limited or full, extended_state, and a "
+                                         "leaky-relu / relu network of hidden width <= 80");
+        if (!final_cont) pa.ws = 0;
+    }
     if (!pa.ws) bind_shared_loss_as_table(h, a);
-    if (pa.split) HIP_TRY(h, dpenv_dev_launch_policy_rollout_x(&a, &pa, h->mode, h->cfg.extended_state, (hipStream_t)s));
-    else HIP_TRY(h, dpenv_dev_launch_policy_rollout(&a, &pa, h->mode, h->cfg.extended_state, (hipStream_t)s));
+    if (h->integ_on) {
+        IntegArgs ia = h->integ;
+        ia.out = integ_out;
+        if (pa.split) HIP_TRY(h, dpenv_dev_launch_policy_rollout_x_integ(&a, &pa, &ia, h->mode, h->cfg.extended_state, (hipStream_t)s));
+        else HIP_TRY(h, dpenv_dev_launch_policy_rollout_integ(&a, &pa, &ia, h->mode, h->cfg.extended_state, (hipStream_t)s));
+    } else if (pa.split) {
+        HIP_TRY(h, dpenv_dev_launch_policy_rollout_x(&a, &pa, h->mode, h->cfg.extended_state, (hipStream_t)s));
+    } else {
+        HIP_TRY(h, dpenv_dev_launch_policy_rollout(&a, &pa, h->mode, h->cfg.extended_state, (hipStream_t)s));
+    }
     h->lag_valid = true;
     return mark_policy_read(h, s);
+}
+
+extern "C" int dpenv_policy_rollout(dpenv_handle h, const dpenv_policy_rollout_io* io, dpenv_stream s)
+{
+    if (!h) return DPENV_EINVAL;
+    return policy_rollout_impl(h, io, nullptr, s);
+}
+
+extern "C" int dpenv_policy_rollout_integral(dpenv_handle h, const dpenv_policy_rollout_io* io, float* integ_out, dpenv_stream s)
+{
+    if (!h) return DPENV_EINVAL;
+    if (!h->integ_on) return fail(h, DPENV_EINVAL, "dpenv_policy_rollout_integral: the integral action is off (dpenv_set_integral_action)");
+    return policy_rollout_impl(h, io, integ_out, s);
+}
+
+// ---- the deployed node's integral action (dpenv.h) -------------------------------------------------------------------------------
+extern "C" int dpenv_set_integral_action(dpenv_handle h, const dpenv_integral_action* ia, dpenv_stream s)
+{
+    if (!h) return DPENV_EINVAL;
+    if (!ia) {
+        h->integ_on = false;
+        return DPENV_OK;
+    }
+    if (ia->struct_size != sizeof(dpenv_integral_action)) return fail(h, DPENV_EINVAL, "dpenv_integral_action ABI mismatch");
+    if (h->mode == MODE_SIMPLE)
+        return fail(h, DPENV_EINVAL, "the integral action is not defined for the simple variant (the RL node refuses it, rl_allocator.py:126)");
+    for (int j = 0; j < 3; ++j) {
+        if (!std::isfinite(ia->gain[j])) return fail(h, DPENV_EINVAL, "integral action: gain[%d] must be finite", j);
+        if (std::isnan(ia->bound[j]) || ia->bound[j] < 0.0f) return fail(h, DPENV_EINVAL, "integral action: bound[%d] must be >= 0", j);
+        if (std::isnan(ia->box[j]) || ia->box[j] < 0.0f) return fail(h, DPENV_EINVAL, "integral action: box[%d] must be >= 0", j);
+    }
+    if (!std::isfinite(ia->dwell_s) || ia->dwell_s < 0.0f) return fail(h, DPENV_EINVAL, "integral action: dwell_s must be finite and >= 0");
+    if (!std::isfinite(ia->step_s)) return fail(h, DPENV_EINVAL, "integral action: step_s must be finite (<= 0: the control period)");
+    // D: the smallest count with D * dt > dwell_s, in f64 (the node's (now - time_arrival) > dwell test in control steps)
+    const double dt = (double)h->cfg.substep_dt * (double)h->cfg.n_substeps;
+    const double q = (double)ia->dwell_s / dt;
+    if (q > 1e9) return fail(h, DPENV_EINVAL, "integral action: dwell_s is more than 1e9 control periods");
+    int64_t D = (int64_t)std::floor(q);
+    while (D > 0 && (double)(D - 1) * dt > (double)ia->dwell_s) --D;
+    while (!((double)D * dt > (double)ia->dwell_s)) ++D;
+    DeviceGuard dev_guard(h->device);
+    if (!h->integ.state) {
+        void* p = nullptr;
+        if (hipMalloc(&p, sizeof(float4) * (size_t)h->cfg.n_envs) != hipSuccess) return fail(h, DPENV_ENOMEM, "hipMalloc of the integral state failed");
+        h->integ.state = (float4*)p;
+    }
+    IntegArgs& g = h->integ;
+    for (int j = 0; j < 3; ++j) { g.gain[j] = ia->gain[j]; g.bound[j] = ia->bound[j]; g.box[j] = ia->box[j]; }
+    g.step_s = ia->step_s > 0.0f ? ia->step_s : h->cfg.substep_dt * (float)h->cfg.n_substeps;
+    g.dwell = (int32_t)D;
+    g.out = nullptr;
+    HIP_TRY(h, dpenv_dev_launch_integ_clear(g.state, nullptr, h->cfg.n_envs, (hipStream_t)s));
+    h->integ_on = true;
+    return DPENV_OK;
+}
+
+extern "C" int dpenv_get_integral_state(dpenv_handle h, float* I_out, int32_t* count_out, dpenv_stream s)
+{
+    if (!h) return DPENV_EINVAL;
+    if (!h->integ_on) return fail(h, DPENV_EINVAL, "dpenv_get_integral_state: the integral action is off");
+    if (!I_out && !count_out) return fail(h, DPENV_EINVAL, "dpenv_get_integral_state: NULL argument");
+    DeviceGuard dev_guard(h->device);
+    HIP_TRY(h, dpenv_dev_launch_integ_state_io(h->integ.state, I_out, count_out, h->cfg.n_envs, 0, (hipStream_t)s));
+    return DPENV_OK;
+}
+
+extern "C" int dpenv_set_integral_state(dpenv_handle h, const float* I_in, const int32_t* count_in, dpenv_stream s)
+{
+    if (!h) return DPENV_EINVAL;
+    if (!h->integ_on) return fail(h, DPENV_EINVAL, "dpenv_set_integral_state: the integral action is off");
+    if (!I_in && !count_in) return fail(h, DPENV_EINVAL, "dpenv_set_integral_state: NULL argument");
+    DeviceGuard dev_guard(h->device);
+    HIP_TRY(h, dpenv_dev_launch_integ_state_io(h->integ.state, (float*)I_in, (int32_t*)count_in, h->cfg.n_envs, 1, (hipStream_t)s));
+    return DPENV_OK;
 }
 
 extern "C" int dpenv_get_state(dpenv_handle h, float* state_out, int32_t* counters_out, dpenv_stream s)

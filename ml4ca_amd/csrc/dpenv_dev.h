@@ -189,6 +189,16 @@ struct PolicyArgs {
     uint32_t* dbg;            // diagnostic builds only (DPENV_WS_SELFCHECK): event records, NULL otherwise
 };
 
+// the deployed RL node's body-frame integral action in the closed loop (dpenv_set_integral_action; rl_allocator.py:252-273 of the
+// reference): a separate argument of the *_integ kernels only, so the kernels without it keep their argument block
+struct IntegArgs {
+    float4* state;            // [n] I[0..2] | count of control steps since the last (re)arrival (int32 bits)
+    float* out;               // [T][n][3] the I added to obs[t], or NULL
+    float gain[3], bound[3], box[3];
+    float step_s;
+    int32_t dwell;            // D: the smallest count with D * dt > dwell_s
+};
+
 // device-side weight packing (pack_policy_kernel): one dense network, DEVICE pointers
 struct PackNet {
     const float* W[5];        // W[l][in][out] row-major (tf.layers.dense kernel layout)
@@ -221,6 +231,20 @@ hipError_t dpenv_dev_launch_policy_rollout_xws_f32(const dpenv::StepArgs* a, con
                                                    hipStream_t s);
 hipError_t dpenv_dev_launch_policy_rollout_xws_f32_actor(const dpenv::StepArgs* a, const dpenv::PolicyArgs* pa, int mode, int ext,
                                                          hipStream_t s);
+// the closed loop with the integral action (IntegArgs): one-wave kernels of dpenv_policy.hip / dpenv_policy_x.hip, which hand pa->ws launches
+// to the two-wave kernels of their arithmetic's translation unit
+hipError_t dpenv_dev_launch_policy_rollout_integ(const dpenv::StepArgs* a, const dpenv::PolicyArgs* pa, const dpenv::IntegArgs* ia, int mode,
+                                                 int ext, hipStream_t s);
+hipError_t dpenv_dev_launch_policy_rollout_x_integ(const dpenv::StepArgs* a, const dpenv::PolicyArgs* pa, const dpenv::IntegArgs* ia, int mode,
+                                                   int ext, hipStream_t s);
+hipError_t dpenv_dev_launch_policy_rollout_ws_integ(const dpenv::StepArgs* a, const dpenv::PolicyArgs* pa, const dpenv::IntegArgs* ia, int mode,
+                                                    int ext, hipStream_t s);
+hipError_t dpenv_dev_launch_policy_rollout_xws_f32_integ(const dpenv::StepArgs* a, const dpenv::PolicyArgs* pa, const dpenv::IntegArgs* ia,
+                                                         int mode, int ext, hipStream_t s);
+hipError_t dpenv_dev_launch_policy_rollout_xws_f32_actor_integ(const dpenv::StepArgs* a, const dpenv::PolicyArgs* pa, const dpenv::IntegArgs* ia,
+                                                               int mode, int ext, hipStream_t s);
+hipError_t dpenv_dev_launch_integ_clear(float4* state, const uint8_t* mask, int n, hipStream_t s);
+hipError_t dpenv_dev_launch_integ_state_io(float4* state, float* I, int32_t* c, int n, int write, hipStream_t s);
 hipError_t dpenv_dev_launch_policy_forward(const dpenv::PolicyArgs* pa, int od, int adim, const float* obs, float* mu,
                                            float* v, int n, hipStream_t s);
 hipError_t dpenv_dev_launch_policy_rollout(const dpenv::StepArgs* a, const dpenv::PolicyArgs* pa, int mode, int ext,

@@ -61,155 +61,39 @@ __global__ __launch_bounds__(PBLOCK) void policy_forward_kernel(const PolicyArgs
 template <int MODE, bool EXT, int KA>
 __global__ __launch_bounds__(PBLOCK) void policy_rollout_kernel(const StepArgs a, const PolicyArgs pa)
 {
-    constexpr int A = ModeTraits<MODE>::A;
-    constexpr int OD = EXT ? 9 : 6;
-    extern __shared__ uint4 lds_dyn[];
-    uint4* lds_w = lds_dyn;
-    float* lds_io = (float*)lds_dyn + policy_lds_io_offset_floats(pa) + (threadIdx.x >> 6) * (64 * 9);
-    stage_weights(lds_w, pa);
-    const uint4* Wpi = lds_w;
-    const uint4* Wv = lds_w + pa.nent;
-    const float* Bpi = (const float*)(lds_dyn + 2 * pa.nent);
-    const float* Bv = Bpi + pa.nblk * 32;
-    const _Float16 leak = (_Float16)pa.leak;
+    constexpr bool INTEG = false;
+    const IntegArgs ia{};
+#include "dpenv_policy_rollout_body.inc"
+}
 
-    const int lane = threadIdx.x & 63;
-    const int n = a.n;
-    const int wave0 = blockIdx.x * PBLOCK + (threadIdx.x & ~63);
-    if (wave0 >= n) return;                                      // whole wave out of range (uniform)
-    const int i = wave0 + lane;
-    const bool live = i < n;
-    const int il = live ? i : n - 1;
+// INTEG: the deployed node's integral action (IntegArgs, dpenv_set_integral_action)
+template <int MODE, bool EXT, int KA>
+__global__ __launch_bounds__(PBLOCK) void policy_rollout_integ_kernel(const StepArgs a, const PolicyArgs pa, const IntegArgs ia)
+{
+    constexpr bool INTEG = true;
+#include "dpenv_policy_rollout_body.inc"
+}
 
-    Env s;
-    load_env(a, il, s);
-    sincos_lean(s.psi, s.sn, s.cs);
-    Current cur = {0.0f, 0.0f, 0.0f, 0.0f, 0u};
-    float vc0 = 0.0f, beta0 = 0.0f;
-    if (a.cur_vc) {
-        cur.vc = a.cur_vc[il]; cur.beta = a.cur_beta[il];
-        if (a.current_drift) { vc0 = a.cur_vc0[il]; beta0 = a.cur_beta0[il]; cur.ctr = a.drift_ctr[il]; }
-        current_components(cur);
-    }
-    // single class: SGPR-resident (the VGPRs are needed by the MLP); classes: per lane from the table, once per launch
-    Vessel ve = launch_vessel_plain(a, il);                      // re-drawn with the episode when the randomisation is on
-    uint32_t episode = a.auto_reset ? (uint32_t)a.episode[il] : 0u;
-    bool ep_dirty = false, rf_dirty = (MODE == MODE_FULL);
-    const PolicyConsts<A> pc = load_policy_consts<A>(pa);
-    const bool draw = pa.noise == nullptr && pa.sample != 0;
-    uint32_t nctr = draw ? a.noise_ctr[il] : 0u;
+// the explicit reset's side of the integral action (dpenv_reset): I = 0, count = 0 for the envs it re-draws
+__global__ __launch_bounds__(256) void integ_clear_kernel(float4* state, const uint8_t* mask, int n)
+{
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i < n && (mask == nullptr || mask[i] != 0)) state[i] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+}
 
-    const int64_t stride_a = (int64_t)n * A, stride_o = (int64_t)n * OD;
-    const int64_t w_a = (int64_t)wave0 * A, w_o = (int64_t)wave0 * OD;
-    const int64_t rem_a = stride_a - w_a, rem_o = stride_o - w_o;
-
-    // observation of the current state = policy input of step 0 (ENV:196-205), and its value
-    float o[9];
-    {
-        float sr_, cr_;
-        bool same_;
-        make_obs(s.N, s.E, s.psi, s.u, s.v, s.r, s.refN, s.refE, s.refPsi, s.pt, a.wrap_mode == WRAP_REFERENCE, o, sr_, cr_,
-                 same_);
-    }
-    if (EXT && pa.use_lag) {                                     // continue the episode with the observation the last launch ended with
-        const float4 lg = a.S3[il];
-        o[6] = lg.x; o[7] = lg.y; o[8] = lg.z;
-    }
-    half8 in0, in1;
-    obs_to_frags<OD>(o, in0, in1);
-    float vout[8], mu[8];
-    mlp_eval2<KA>(Wpi, Wv, Bpi, Bv, pa.n_hidden, in0, in1, leak, mu, vout);     // actor and critic of o_0
-    float v_t = vout[0];
-
-    float pre[A];
-    if (pa.noise) load_rows<A, 64>(pa.noise + w_a, rem_a, lane, pre);
-    int next_switch = 0;
-    for (int t = 0; t < pa.T; ++t) {
-        // ---- store the policy input row; the actor's mean for it is already there (joint evaluation) -------------
-        wave_store_rows<OD>(lds_io, pa.obs_out, (int64_t)t * stride_o + w_o, rem_o, o, lane, a.obs_bf16 != 0);
-        // ---- sample: a = mu + std * xi (core.py:85), log-likelihood (core.py:42-46) -----------
-        float act[A];
-        float logp;
-        if (pa.noise) {
-            float xi[A];
-            wave_rows_from_regs<A>(lds_io, pre, xi, lane);
-            if (t + 1 < pa.T) load_rows<A, 64>(pa.noise + (int64_t)(t + 1) * stride_a + w_a, rem_a, lane, pre);
-            logp = sample_action<A>(pc, mu, xi, act);
-        } else if (draw) {
-            float xi[A];
-            policy_noise<A>(a, a.env_id_base + i, nctr, xi);
-            ++nctr;
-            logp = sample_action<A>(pc, mu, xi, act);
-        } else {
-            logp = mean_action<A>(pc, mu, act);
-        }
-        wave_store_rows<A>(lds_io, pa.act_out, (int64_t)t * stride_a + w_a, rem_a, act, lane);
-
-        // ---- env.step ------------------------------------------------------------------------
-        bool has_ref = false;
-        float nrN = 0.0f, nrE = 0.0f, nrP = 0.0f;
-        if (next_switch < pa.n_switch && pa.switch_step[next_switch] == t) {
-            const float* rp = pa.refs + (int64_t)next_switch * 3 * n;
-            nrN = rp[il]; nrE = rp[(int64_t)n + il]; nrP = rp[2 * (int64_t)n + il];
-            has_ref = true; rf_dirty = true;
-            ++next_switch;
-        }
-        StepOut out;
-        env_step<MODE, EXT>(a, ve, s, act, has_ref, nrN, nrE, nrP, a.cur_vc != nullptr, cur.vcN, cur.vcE, out, il);
-        if (a.current_drift) current_drift_step(a, cur, vc0, beta0, a.env_id_base + i);
-
-#pragma unroll
-        for (int k = 0; k < 9; ++k) o[k] = out.o[k];
-        // ppo.py:305-322 with reset_at_end: after the LAST step of the block every env is cut and re-drawn, ended or not
-        const bool do_reset = ((a.auto_reset && out.d != 0u) || (pa.reset_at_end && t == pa.T - 1)) && live;
-        // ---- value of the observation this step produced, and the next policy input ------------------------------
-        // No env of the wave finished (the common case): the next policy input IS that observation, so one joint
-        // evaluation gives V(o') for the bootstrap and the actor's mean for the next step.  Otherwise the critic is
-        // run once more on the pre-reset observation of the wave before the finished envs are re-drawn.
-        float v_pre = 0.0f;
-        if (__ballot(do_reset) != 0ull) {                       // wave-uniform
-            // only a CUT episode (time limit) bootstraps with V of its last observation; a terminated one with 0 (ppo.py:311)
-            if (__ballot(do_reset && (out.d & DONE_TERMINAL) == 0u) != 0ull) {
-                obs_to_frags<OD>(o, in0, in1);
-                mlp_eval<KA>(Wv, Bv, pa.n_hidden, in0, in1, leak, vout);
-                v_pre = vout[0];
-            }
-            if (do_reset) {
-                env_auto_reset<MODE>(a, s, a.env_id_base + i, episode, o);
-                if (a.rand_tab) redraw_vessel_cold(a, i, episode, ve);    // domain randomisation: the new episode runs on a new hull
-                if (a.cur_nom) current_redraw(a, i, episode, cur, vc0, beta0);    // ... in a new current (stored with the final state)
-                ++episode; ep_dirty = true; rf_dirty = true;
-            }
-        }
-        obs_to_frags<OD>(o, in0, in1);
-        mlp_eval2<KA>(Wpi, Wv, Bpi, Bv, pa.n_hidden, in0, in1, leak, mu, vout);
-        const float v_next = do_reset ? v_pre : vout[0];
-        const float v_new = vout[0];
-        // bootstrap value at a path end (ppo.py:311): 0 if the env terminated, V(o) if only the time limit or the
-        // end of this launch cut the path
-        const bool terminal = (out.d & DONE_TERMINAL) != 0u;
-        const bool ended = (out.d != 0u) || (t == pa.T - 1);
-        const float boot = (ended && !terminal) ? v_next : 0.0f;
-
-        if (live) {
-            (pa.rew + (int64_t)t * n)[(unsigned)i] = out.reward;
-            (pa.done + (int64_t)t * n)[(unsigned)i] = (uint8_t)out.d;
-            (pa.val + (int64_t)t * n)[(unsigned)i] = v_t;
-            (pa.logp + (int64_t)t * n)[(unsigned)i] = logp;
-            (pa.boot + (int64_t)t * n)[(unsigned)i] = boot;
-        }
-        v_t = v_new;
-    }
-    // observation after the last step (policy input of the next launch) and final state
-    wave_store_rows<OD>(lds_io, pa.last_obs, w_o, rem_o, o, lane, a.obs_bf16 != 0);
-    if (live) {
-        pa.last_val[i] = v_t;
-        store_env(a, i, s, rf_dirty);
-        if (EXT) a.S3[i] = make_float4(o[6], o[7], o[8], 0.0f);
-        if (ep_dirty) a.episode[i] = (int)episode;
-        if (a.current_drift) { a.cur_vc[i] = cur.vc; a.cur_beta[i] = cur.beta; a.drift_ctr[i] = cur.ctr; }
-        if (a.cur_nom && ep_dirty) store_current(a, i, cur, vc0, beta0, true);
-        if (draw) a.noise_ctr[i] = nctr;
+// the checkpoint path (dpenv_get_integral_state / dpenv_set_integral_state): float4 [n] <-> I float[3][n] | count int32[n]; either may be NULL
+__global__ __launch_bounds__(256) void integ_state_io_kernel(float4* state, float* I, int32_t* c, int n, int write)
+{
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    float4 q = state[i];
+    if (write) {
+        if (I) { q.x = I[i]; q.y = I[(int64_t)n + i]; q.z = I[2 * (int64_t)n + i]; }
+        if (c) q.w = __int_as_float(c[i]);
+        state[i] = q;
+    } else {
+        if (I) { I[i] = q.x; I[(int64_t)n + i] = q.y; I[2 * (int64_t)n + i] = q.z; }
+        if (c) c[i] = __float_as_int(q.w);
     }
 }
 
@@ -399,4 +283,45 @@ extern "C" hipError_t dpenv_dev_launch_policy_rollout(const StepArgs* a, const P
     }
     return hipErrorInvalidValue;
 #endif
+}
+
+// the closed loop with the integral action: final variant / continuous angles, limited and full; extended state, leaky-relu, width <= 80
+// (dpenv_policy_rollout checks the shape and names the supported set)
+template <int MODE>
+static hipError_t launch_policy_rollout_integ_one(const StepArgs& a, const PolicyArgs& pa, const IntegArgs& ia, hipStream_t s)
+{
+    const dim3 grid((a.n + PBLOCK - 1) / PBLOCK), block(PBLOCK);
+    const size_t lds = policy_lds_bytes(pa);
+    hipError_t e = hipFuncSetAttribute((const void*)policy_rollout_integ_kernel<MODE, true, 5>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                       (int)lds);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL((policy_rollout_integ_kernel<MODE, true, 5>), grid, block, lds, s, a, pa, ia);
+    return hipGetLastError();
+}
+
+extern "C" hipError_t dpenv_dev_launch_policy_rollout_integ(const StepArgs* a, const PolicyArgs* pa, const IntegArgs* ia, int mode, int ext,
+                                                            hipStream_t s)
+{
+    if (!ext || pa->ks != 5 || pa->act != 0) return hipErrorInvalidValue;
+    if (pa->ws) return dpenv_dev_launch_policy_rollout_ws_integ(a, pa, ia, mode, ext, s);
+    switch (mode) {
+    case MODE_FINAL_CONT: return launch_policy_rollout_integ_one<MODE_FINAL_CONT>(*a, *pa, *ia, s);
+#ifndef DPENV_DEV_FAST
+    case MODE_LIMITED: return launch_policy_rollout_integ_one<MODE_LIMITED>(*a, *pa, *ia, s);
+    case MODE_FULL: return launch_policy_rollout_integ_one<MODE_FULL>(*a, *pa, *ia, s);
+#endif
+    }
+    return hipErrorInvalidValue;
+}
+
+extern "C" hipError_t dpenv_dev_launch_integ_clear(float4* state, const uint8_t* mask, int n, hipStream_t s)
+{
+    hipLaunchKernelGGL(integ_clear_kernel, dim3((n + 255) / 256), dim3(256), 0, s, state, mask, n);
+    return hipGetLastError();
+}
+
+extern "C" hipError_t dpenv_dev_launch_integ_state_io(float4* state, float* I, int32_t* c, int n, int write, hipStream_t s)
+{
+    hipLaunchKernelGGL(integ_state_io_kernel, dim3((n + 255) / 256), dim3(256), 0, s, state, I, c, n, write);
+    return hipGetLastError();
 }

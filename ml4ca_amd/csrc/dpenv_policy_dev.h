@@ -478,6 +478,53 @@ __device__ __forceinline__ float mean_action(const PolicyConsts<A>& c, const flo
     return logp;
 }
 
+// the integral action of the *_integ closed-loop kernels: one update per env step on e = o[0:3] as make_obs forms it, in this f32 order
+// (deploy.BatchedBodyFrameIntegrator is the host statement of it), then o[0:3] = e + I
+struct IntegState {
+    float I[3];
+    int c;
+};
+__device__ __forceinline__ IntegState integ_load(const IntegArgs& ia, int il)
+{
+    const float4 q = ia.state[il];
+    return IntegState{{q.x, q.y, q.z}, __float_as_int(q.w)};
+}
+__device__ __forceinline__ void integ_store(const IntegArgs& ia, int i, const IntegState& g)
+{
+    ia.state[i] = make_float4(g.I[0], g.I[1], g.I[2], __int_as_float(g.c));
+}
+__device__ __forceinline__ void integ_update(const IntegArgs& ia, IntegState& g, const float o[9])
+{
+    const bool outside = fabsf(o[0]) > ia.box[0] || fabsf(o[1]) > ia.box[1] || fabsf(o[2]) > ia.box[2];    // strict >, as the node
+    if (outside) {
+        g.I[0] = g.I[1] = g.I[2] = 0.0f;
+        g.c = 0;
+    } else {
+        g.c = min(g.c + 1, ia.dwell);
+        if (g.c >= ia.dwell) {
+#pragma unroll
+            for (int j = 0; j < 3; ++j) g.I[j] = fminf(fmaxf(g.I[j] + ia.step_s * (ia.gain[j] * o[j]), -ia.bound[j]), ia.bound[j]);
+        }
+    }
+}
+__device__ __forceinline__ void integ_clear(IntegState& g)
+{
+    g.I[0] = g.I[1] = g.I[2] = 0.0f;
+    g.c = 0;
+}
+__device__ __forceinline__ void integ_apply(const IntegState& g, float o[9])
+{
+#pragma unroll
+    for (int j = 0; j < 3; ++j) o[j] += g.I[j];
+}
+__device__ __forceinline__ void integ_row(const IntegArgs& ia, int t, int n, int i, bool live, const IntegState& g)
+{
+    if (ia.out && live) {
+        float* p = ia.out + ((int64_t)t * n + i) * 3;
+        p[0] = g.I[0]; p[1] = g.I[1]; p[2] = g.I[2];
+    }
+}
+
 // this lane's vessel: its own per-env block (dpenv_set_vessel_params / domain randomisation), its class block from the table in HBM,
 // or the single class of the kernel arguments - loaded once per launch; the T-step kernels' staging area is the register file
 __device__ __forceinline__ Vessel launch_vessel_plain(const StepArgs& a, int il)

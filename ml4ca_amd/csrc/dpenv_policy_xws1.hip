@@ -5,5 +5,11 @@
 
 extern "C" hipError_t dpenv_dev_launch_policy_rollout_xws_f32(const dpenv::StepArgs* a, const dpenv::PolicyArgs* pa, int mode, int ext, hipStream_t s)
 {
-    return dpenv_ws_launch::launch<dpenv::PREC_F32>(*a, *pa, mode, ext, s);
+    return dpenv_ws_launch::launch<dpenv::PREC_F32>(*a, *pa, nullptr, mode, ext, s);
+}
+
+extern "C" hipError_t dpenv_dev_launch_policy_rollout_xws_f32_integ(const dpenv::StepArgs* a, const dpenv::PolicyArgs* pa, const dpenv::IntegArgs* ia, int mode, int ext,
+                                                                    hipStream_t s)
+{
+    return dpenv_ws_launch::launch<dpenv::PREC_F32>(*a, *pa, ia, mode, ext, s);
 }

@@ -5,6 +5,8 @@ Host logic (NumPy, float64), not on the accelerated path: SURVEY section 8(f) ra
 trained on the batched env can be driven exactly the way the vessel's node drives it - state assembly with the radian
 wrap the node uses (unlike the training env, quirk Q1), network order -> ROS thruster order, default commands for the
 thrusters a variant does not control, the optional body-frame integral action, and the message fields published.
+BatchedBodyFrameIntegrator is the torch form of that integral action for a batch of envs (the law the closed-loop
+kernels apply while it is on, include/dpenv.h).
 
   network order  [n_bow, n_port, n_star, (a_bow,) a_port, a_star]       (customEnv.py:47-61)
   ROS order      [n_port, n_star, n_bow, a_port, a_star, a_bow]         (rl_allocator.py:92-106)
@@ -86,6 +88,60 @@ class BodyFrameIntegrator(object):
         elif (now - self.time_arrival) > 5.0:
             self.value = np.clip(self.value + step * self.GAIN * err, -self.BOUND, self.BOUND)
         return err + self.value
+
+
+def dwell_steps(dwell_s, dt):
+    """D: the smallest integer with D * dt > dwell_s, in float64 - the node's (now - time_arrival) > dwell_s in control steps."""
+    D = max(int(np.floor(float(dwell_s) / float(dt))), 0)
+    while D > 0 and (D - 1) * float(dt) > float(dwell_s):
+        D -= 1
+    while not D * float(dt) > float(dwell_s):
+        D += 1
+    return D
+
+
+class BatchedBodyFrameIntegrator(object):
+    """BodyFrameIntegrator for n envs at once, as torch tensors: the law the closed-loop kernels apply while
+    dpenv_set_integral_action is on (include/dpenv.h), in its operation order, so that in float32 it reproduces the
+    kernels' policy inputs bit for bit.  The dwell clock is a count of control steps (c, capped at D = dwell_steps):
+        outside = any |e_j| > box_j;  outside: I = 0, c = 0;  else c = min(c + 1, D) and, once c >= D,
+        I_j = min(max(I_j + step_s * (gain_j * e_j), -bound_j), bound_j)
+    update(e) applies it once (one control step) and returns e[:, :3] + I; reset(mask) zeroes I and c (a new episode).
+    With env.step / policy_forward it is the eager form of the deployed controller; the fused launch is
+    policy.policy_rollout with env.set_integral_action on."""
+    GAIN = (0.05, 0.05, 0.05)
+    BOUND = (0.5, 1.0, np.pi / 32)
+    BOX = (5.0, 5.0, float(np.deg2rad(140.0)))
+
+    def __init__(self, n, gain=GAIN, bound=BOUND, box=BOX, dwell_s=5.0, dt=0.2, step_s=None, dtype=None, device='cpu'):
+        import torch
+        self.dtype = torch.float32 if dtype is None else dtype
+        t = lambda v: torch.as_tensor(np.asarray(v, np.float64), dtype=self.dtype, device=device)
+        self.gain, self.bound, self.box = t(gain), t(bound), t(box)
+        self.step_s = t(dt if step_s is None else step_s)
+        self.dwell = dwell_steps(dwell_s, dt)
+        self.I = torch.zeros((n, 3), dtype=self.dtype, device=device)
+        self.count = torch.zeros(n, dtype=torch.int32, device=device)
+
+    def update(self, e):
+        """e: [n, >=3] (the observation's pose-error columns first).  Returns the policy input's first three columns."""
+        import torch
+        e = e[:, :3].to(self.dtype)
+        outside = (e.abs() > self.box).any(dim=1)
+        self.count = torch.where(outside, torch.zeros_like(self.count), torch.clamp(self.count + 1, max=self.dwell))
+        grow = (~outside) & (self.count >= self.dwell)
+        new = torch.minimum(torch.maximum(self.I + self.step_s * (self.gain * e), -self.bound), self.bound)
+        self.I = torch.where(outside[:, None], torch.zeros_like(self.I), torch.where(grow[:, None], new, self.I))
+        return e + self.I
+
+    def reset(self, mask=None):
+        """Zero I and c of the envs in mask (bool [n]; None = all)."""
+        if mask is None:
+            self.I.zero_()
+            self.count.zero_()
+        else:
+            self.I[mask] = 0
+            self.count[mask] = 0
 
 
 class RLAllocatorNode(object):

@@ -181,6 +181,7 @@ class BatchedRevoltEnv(object):
         self._ashape, self._oshape = tuple(self.action_shape), tuple(self.obs_shape)
         self._n1, self._r3, self._p4 = (n,), (3, n), (4, n)
         self._step_ex = self.lib.dpenv_step_ex
+        self.integral_action = None          # dict of the parameters while set_integral_action() has it on
 
     # -- plumbing -----------------------------------------------------------------------------
     # What a Python `for` over step() pays per call besides the launch is this plumbing (bench.py `eager_loop`): the stream handle and
@@ -291,8 +292,15 @@ class BatchedRevoltEnv(object):
         io.final_obs = chk(final_obs, self._oshape, self.obs_torch_dtype, 'final_obs').data_ptr() if final_obs is not None else None
         rc = self._step_ex(self._h, self._io_ref, self._stream())
         if rc:
+            self._refuse_open_loop('step')
             _lib.check(rc, self._h)
         return obs, rew, done, {'None': 0}
+
+    def _refuse_open_loop(self, what):
+        if self.integral_action is not None:
+            raise ValueError('%s(): the integral action is on (set_integral_action) and this launch\'s observations would lack I; fly the closed '
+                             'loop (policy.policy_rollout), compose step() with deploy.BatchedBodyFrameIntegrator after set_integral_action(None), '
+                             'or turn it off' % what)
 
     def rollout(self, actions, switch_steps=(), refs=None, out=None):
         """T env steps in one launch (dpenv_rollout): exactly T successive step() calls with actions[t], passing
@@ -300,6 +308,7 @@ class BatchedRevoltEnv(object):
         state kept in registers between steps.  actions: float32 [T, n, act_dim] (or [T, act_dim, n] for 'soa').
         Returns (obs [T, n, obs_dim], reward [T, n], done_bits [T, n]); obs[t] is what step t returned."""
         torch = _torch()
+        self._refuse_open_loop('rollout')
         T = int(actions.shape[0])
         n = self.n_envs
         self._chk(actions, (T,) + self.action_shape, torch.float32, 'actions')
@@ -344,6 +353,49 @@ class BatchedRevoltEnv(object):
         state = self._chk(state, (_lib.NSTATE, self.n_envs), torch.float32, 'state')
         counters = self._chk(counters, (2, self.n_envs), torch.int32, 'counters')
         _lib.check(self.lib.dpenv_set_state(self._h, self._ptr(state), self._ptr(counters), self._stream()), self._h)
+
+    # -- the deployed controller's integral action (dpenv.h dpenv_set_integral_action) ----------------------------------------------
+    @property
+    def control_period(self):
+        """The env's control period n_steps * 0.01 s in float32, as the library computes it (the integral action's default step_s)."""
+        return float(np.float32(self.cfg.substep_dt) * np.float32(self.cfg.n_substeps))
+
+    def set_integral_action(self, gain=(0.05, 0.05, 0.05), bound=(0.5, 1.0, math.pi / 32), box=(5.0, 5.0, 140.0 * math.pi / 180.0),
+                            dwell_s=5.0, step_s=None):
+        """The RL node's body-frame integral action (rl_allocator.py:252-273) in the closed-loop launches: the policy input becomes
+        o[0:3] = e + I (dpenv.h has the law).  Defaults are the node's.  step_s None = the control period.  off=True (or
+        turns it off.  Turning it on zeroes the integrator of every env.  While it is on, step() and rollout()
+        raise ValueError."""
+        if gain is None:
+            _lib.check(self.lib.dpenv_set_integral_action(self._h, None, self._stream()), self._h)
+            self.integral_action = None
+            return
+        ia = _lib.IntegralAction()
+        ia.struct_size = C.sizeof(_lib.IntegralAction)
+        for j in range(3):
+            ia.gain[j], ia.bound[j], ia.box[j] = float(gain[j]), float(bound[j]), float(box[j])
+        ia.dwell_s = float(dwell_s)
+        ia.step_s = 0.0 if step_s is None else float(step_s)
+        if step_s is not None and not step_s > 0:
+            raise ValueError('step_s must be > 0 (None = the control period)')
+        _lib.check(self.lib.dpenv_set_integral_action(self._h, C.byref(ia), self._stream()), self._h)
+        self.integral_action = dict(gain=tuple(ia.gain), bound=tuple(ia.bound), box=tuple(ia.box), dwell_s=ia.dwell_s,
+                                    step_s=self.control_period if step_s is None else float(np.float32(step_s)))
+
+    def get_integral_state(self):
+        """(I float32 [3, n], count int32 [n]): the integrator and the control steps since the last (re)arrival.  Checkpoint with
+        get_state() / get_rng_counters()."""
+        torch = _torch()
+        I = torch.empty((3, self.n_envs), dtype=torch.float32, device=self.device)
+        c = torch.empty(self.n_envs, dtype=torch.int32, device=self.device)
+        _lib.check(self.lib.dpenv_get_integral_state(self._h, self._ptr(I), self._ptr(c), self._stream()), self._h)
+        return I, c
+
+    def set_integral_state(self, I=None, count=None):
+        torch = _torch()
+        I = self._chk(I, (3, self.n_envs), torch.float32, 'I')
+        count = self._chk(count, (self.n_envs,), torch.int32, 'count')
+        _lib.check(self.lib.dpenv_set_integral_state(self._h, self._ptr(I), self._ptr(count), self._stream()), self._h)
 
     def get_rng_counters(self):
         """(noise_ctr, drift_ctr): int32 [n] draws made so far of the in-kernel exploration noise and of the current drift (uint32

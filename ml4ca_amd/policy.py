@@ -229,7 +229,9 @@ def policy_rollout(env, T, noise=None, switch_steps=(), refs=None, out=None, sam
     actions the env has sampled so far - like tf.random_normal inside the reference's graph, core.py:85, but reproducible and
     independent of the rank count); sample=False / None is the deterministic policy a = mu (test_policy.py:90).  Returns a dict of blocks: obs [T,n,od] (policy inputs), act [T,n,ad],
     rew, val, logp, boot [T,n], done [T,n] uint8, last_obs [n,od], last_val [n].  GAE: rollout.gae(rew, val, end=done, boot=boot).
-    reset_at_end: the reference's epoch boundary (ppo.py:305-322): every env is cut and re-drawn after step T-1 (dpenv.h)."""
+    reset_at_end: the reference's epoch boundary (ppo.py:305-322): every env is cut and re-drawn after step T-1 (dpenv.h).
+    With the integral action on (env.set_integral_action) the launch applies it and out['integ'] [T,n,3] holds the I added to obs[t]
+    (obs[..., :3] - integ is the true error)."""
     torch = _torch()
     n, od, ad = env.n_envs, env.num_states, env.num_actions
     dev = env.device
@@ -258,5 +260,11 @@ def policy_rollout(env, T, noise=None, switch_steps=(), refs=None, out=None, sam
     io.refs = refs.data_ptr() if k else None
     io.sample = 1 if (sample and noise is None) else 0
     io.reset_at_end = 1 if reset_at_end else 0
-    _lib.check(env.lib.dpenv_policy_rollout(env._h, C.byref(io), env._stream()), env._h)
+    if env.integral_action is not None:
+        if out.get('integ') is None:
+            out['integ'] = torch.empty((T, n, 3), dtype=f32, device=dev)
+        env._chk(out['integ'], (T, n, 3), f32, "out['integ']")
+        _lib.check(env.lib.dpenv_policy_rollout_integral(env._h, C.byref(io), out['integ'].data_ptr(), env._stream()), env._h)
+    else:
+        _lib.check(env.lib.dpenv_policy_rollout(env._h, C.byref(io), env._stream()), env._h)
     return out

@@ -18,6 +18,8 @@ def main():
     ap.add_argument('--reps', type=int, default=30)
     ap.add_argument('--warm', type=int, default=40, help='untimed launches first: the MFMA-heavy forms wobble by 10-30 %% for the first ~20 launches of a process (clock / power ramp)')
     ap.add_argument('--out', default='')
+    ap.add_argument('--integral', action='store_true', help='time every form with the deployed node\'s integral action (dpenv_set_integral_action, '
+                    'the node\'s parameters) off and on, alternating launch by launch in one process; prints the ratio on / off of the medians')
     ap.add_argument('--forms', default='f16:two_wave,f16:one_wave,f32_actor:two_wave,f32_actor:one_wave,f32:two_wave,f32:one_wave')
     args = ap.parse_args()
     import torch
@@ -38,6 +40,9 @@ def main():
                 print('%7d %-22s refused (%s)' % (n, spec, str(e)[:60]), flush=True)
                 continue
             env.reset()
+            if args.integral:
+                res['%d/%s' % (n, spec)] = time_integral(env, args, n, spec)
+                continue
             out = policy_rollout(env, args.steps, sample=True)
             for _ in range(args.warm):
                 policy_rollout(env, args.steps, sample=True, out=out)
@@ -57,6 +62,30 @@ def main():
     if args.out:
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
         json.dump(res, open(args.out, 'w'), indent=1)
+
+
+def time_integral(env, args, n, spec):
+    """us per env step with the integral action off and on, alternating launch by launch (same process, same state stream)."""
+    import torch
+    from ml4ca_amd.policy import policy_rollout
+    outs, ts = {}, {False: [], True: []}
+    for k in range(args.warm + args.reps):
+        for on in (False, True):
+            env.set_integral_action() if on else env.set_integral_action(None)
+            outs[on] = policy_rollout(env, args.steps, sample=True, out=outs.get(on))
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            policy_rollout(env, args.steps, sample=True, out=outs[on])
+            torch.cuda.synchronize()
+            if k >= args.warm:
+                ts[on].append((time.perf_counter() - t0) / args.steps * 1e6)
+    env.set_integral_action(None)
+    med = {on: sorted(v)[len(v) // 2] for on, v in ts.items()}
+    assert bool(torch.isfinite(outs[True]['integ']).all())
+    print('%7d %-22s off %7.2f  on %7.2f us/step (min %6.2f / %6.2f)  on/off %.3f' % (n, spec, med[False], med[True], min(ts[False]),
+                                                                                    min(ts[True]), med[True] / med[False]), flush=True)
+    return {'us_per_step_median_off': med[False], 'us_per_step_median_on': med[True], 'us_per_step_min_off': min(ts[False]),
+            'us_per_step_min_on': min(ts[True]), 'on_over_off': med[True] / med[False]}
 
 
 if __name__ == '__main__':

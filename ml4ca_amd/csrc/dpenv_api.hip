@@ -416,7 +416,7 @@ extern "C" int dpenv_create(const dpenv_config* cfg, const float* vessel_params,
     h->rand_tab = (float*)(b + o_rt);
     h->raw0_dev = (float*)(b + o_r0);
     h->cur_nom = (float*)(b + o_cn);
-    h->loss_flag = (uint32_t*)(b + o_et + npad * 16 * DRAW_GROUPS);     // = env_tab + DRAW_GROUPS * env_stride: where thrust_loss_on() looks (dpenv_env_dev.h)
+    h->loss_flag = (uint32_t*)(b + o_et + npad * 16 * DRAW_GROUPS);     // = env_tab + DRAW_GROUPS * env_stride: read back by resolve_loss; kernels see StepArgs.loss_on
     a.class_tab = (const float*)(b + o_ct);
     a.n_classes = n_classes;
     a.v0 = tab[0];
@@ -458,7 +458,7 @@ extern "C" int dpenv_create(const dpenv_config* cfg, const float* vessel_params,
         }
         e = hipMemcpy(h->raw0_dev, h->raw0, sizeof h->raw0, hipMemcpyHostToDevice);
         if (e == hipSuccess) {       // the table starts as the image of class 0 for every env (what the kernels without a shared form read)
-            e = dpenv_dev_launch_pack_env_vessels(h->raw0_dev, 1, 0, h->env_tab, nullptr, h->env_stride, cfg->n_envs, nullptr);
+            e = dev::launch_pack_env_vessels(h->raw0_dev, 1, 0, h->env_tab, nullptr, h->env_stride, cfg->n_envs, nullptr);
             if (e == hipSuccess) e = hipDeviceSynchronize();
         }
         if (e != hipSuccess) {
@@ -663,7 +663,7 @@ extern "C" int dpenv_set_vessel_params_ex(dpenv_handle h, const float* params, u
         // back to the classes / the single class; a single class WITH thrust-loss coefficients keeps them (kernel arguments), and the table
         // becomes the image of that hull again for the kernels that read it there
         if (h->per_env)
-            HIP_TRY(h, dpenv_dev_launch_pack_env_vessels(h->raw0_dev, 1, 0, h->env_tab, nullptr, h->env_stride, h->cfg.n_envs, (hipStream_t)s));
+            HIP_TRY(h, dev::launch_pack_env_vessels(h->raw0_dev, 1, 0, h->env_tab, nullptr, h->env_stride, h->cfg.n_envs, (hipStream_t)s));
         h->per_env = false;
         h->randomise = false;
         h->loss_pending = false;
@@ -674,7 +674,7 @@ extern "C" int dpenv_set_vessel_params_ex(dpenv_handle h, const float* params, u
     HIP_TRY(h, hipStreamIsCapturing((hipStream_t)s, &cap));
     // stream-ordered, no read-back: the packing kernel leaves "some env has a thrust-loss coefficient" in the word behind the table
     HIP_TRY(h, hipMemsetAsync(h->loss_flag, 0, sizeof(uint32_t), (hipStream_t)s));
-    HIP_TRY(h, dpenv_dev_launch_pack_env_vessels(params, (int64_t)h->cfg.n_envs, 1, h->env_tab, h->loss_flag, h->env_stride, h->cfg.n_envs, (hipStream_t)s));
+    HIP_TRY(h, dev::launch_pack_env_vessels(params, (int64_t)h->cfg.n_envs, 1, h->env_tab, h->loss_flag, h->env_stride, h->cfg.n_envs, (hipStream_t)s));
     // which kernels run from here on depends on that word (the general per-env form applies the loss, the plain one does not carry the code).
     // Outside a capture it also travels to a pinned host word behind an event: the next launch takes the answer from there (resolve_loss);
     // recorded into a graph the setter leaves the answer unknown: the general kernels then apply the table's coefficients whatever they are.
@@ -702,7 +702,7 @@ extern "C" int dpenv_get_vessel_params(dpenv_handle h, float* params_out, dpenv_
     if (!h->per_env && h->n_classes > 1)
         return fail(h, DPENV_EINVAL, "no per-env parameter blocks in force (dpenv_set_vessel_params / dpenv_set_vessel_randomisation)");
     DeviceGuard dev_guard(h->device);
-    HIP_TRY(h, dpenv_dev_launch_unpack_env_vessels(h->env_tab, h->env_stride, params_out, h->cfg.n_envs, (hipStream_t)s));
+    HIP_TRY(h, dev::launch_unpack_env_vessels(h->env_tab, h->env_stride, params_out, h->cfg.n_envs, (hipStream_t)s));
     return DPENV_OK;
 }
 
@@ -730,7 +730,7 @@ extern "C" int dpenv_set_vessel_randomisation(dpenv_handle h, const float* nomin
     }
     HIP_TRY(h, hipMemcpyAsync(h->rand_tab, h->rand_host, sizeof h->rand_host, hipMemcpyHostToDevice, (hipStream_t)s));
     // until its first reset every env runs on the nominal hull
-    HIP_TRY(h, dpenv_dev_launch_pack_env_vessels(h->rand_tab, 1, 0, h->env_tab, nullptr, h->env_stride, h->cfg.n_envs, (hipStream_t)s));
+    HIP_TRY(h, dev::launch_pack_env_vessels(h->rand_tab, 1, 0, h->env_tab, nullptr, h->env_stride, h->cfg.n_envs, (hipStream_t)s));
     h->per_env = true;
     h->randomise = true;
     h->rand_loss = false;                               // a draw scales the nominal value: no coefficient there, none in any hull
@@ -748,8 +748,8 @@ extern "C" int dpenv_reset(dpenv_handle h, const uint8_t* mask, const float* ini
     StepArgs a = h->args;
     bind_optional(h, a, (hipStream_t)s);
     a.obs = obs_out;
-    HIP_TRY(h, dpenv_dev_launch_reset(&a, h->mode, h->cfg.extended_state, mask, init, ref, (hipStream_t)s));
-    if (h->integ_on) HIP_TRY(h, dpenv_dev_launch_integ_clear(h->integ.state, mask, h->cfg.n_envs, (hipStream_t)s));   // new episodes start with I = 0
+    HIP_TRY(h, dev::launch_reset(&a, h->mode, h->cfg.extended_state, mask, init, ref, (hipStream_t)s));
+    if (h->integ_on) HIP_TRY(h, dev::launch_integ_clear(h->integ.state, mask, h->cfg.n_envs, (hipStream_t)s));   // new episodes start with I = 0
     // the reset kernel writes the lagged thrust columns (S3) of the envs it re-draws: a full reset makes them valid everywhere, a
     // masked one leaves the validity of the other envs' columns as it was (it used to drop the lag of every env)
     if (!mask) h->lag_valid = true;
@@ -787,7 +787,7 @@ extern "C" int dpenv_step_ex(dpenv_handle h, const dpenv_step_io* io, dpenv_stre
     // MI355X); beyond that the extra waves queue behind env waves and the one-wave kernel is faster (98 304 envs: 6.92 vs 7.19 us, 1 M:
     // 34.7 vs 39.2; profiles/r04_reset_wave.txt)
     const int reset_wave = (!h->cfg.step_one_wave && (int64_t)h->cfg.n_envs <= (int64_t)256 * h->n_cus) ? 1 : 0;
-    HIP_TRY(h, dpenv_dev_launch_step(&a, h->mode, h->cfg.extended_state, vessel_source(h), reset_wave, (hipStream_t)s));
+    HIP_TRY(h, dev::launch_step(&a, h->mode, h->cfg.extended_state, vessel_source(h), reset_wave, (hipStream_t)s));
     h->lag_valid = h->has_policy;
     return DPENV_OK;
 }
@@ -828,7 +828,7 @@ extern "C" int dpenv_rollout(dpenv_handle h, const dpenv_rollout_io* io, dpenv_s
     // above 10-15 % slower than one wave per 64 envs: profiles/r04_fused_two_wave.txt, r04_batch_sweep.txt)
     // (the randomisation's instantiation needs 201 VGPRs: two waves per SIMD, i.e. up to 256 envs per CU)
     const int two_wave = (!h->cfg.step_one_wave && (int64_t)h->cfg.n_envs <= (int64_t)(vessel_source(h) == VES_ENV_RND ? 256 : 384) * h->n_cus) ? 1 : 0;
-    HIP_TRY(h, dpenv_dev_launch_rollout(&a, &ra, h->mode, h->cfg.extended_state, vessel_source(h), two_wave, (hipStream_t)s));
+    HIP_TRY(h, dev::launch_rollout(&a, &ra, h->mode, h->cfg.extended_state, vessel_source(h), two_wave, (hipStream_t)s));
     // the rollout kernels leave the thrust columns of their last observation in S3 - with the extended state (without it no observation has
     // thrust columns and S3 is never written: the flag keeps what it was)
     if (h->cfg.extended_state) h->lag_valid = true;
@@ -978,7 +978,7 @@ extern "C" int dpenv_set_policy_desc(dpenv_handle h, const dpenv_policy_desc* d,
     char* base = (char*)h->pol_buf + (size_t)slot * (h->pol_buf_bytes / 2);
     float* bias = (float*)(base + bytes_frags);
     float* consts = (float*)(base + bytes_frags + bytes_bias);
-    HIP_TRY(h, dpenv_dev_launch_pack_policy(&pn[0], &pn[1], ls_dev, ad, ks, nent, nblk, split, base, bias, consts, (hipStream_t)s));
+    HIP_TRY(h, dev::launch_pack_policy(&pn[0], &pn[1], ls_dev, ad, ks, nent, nblk, split, base, bias, consts, (hipStream_t)s));
     PolicyArgs& pa = h->pol;
     std::memset(&pa, 0, sizeof pa);
     pa.frags = (const uint4*)base;
@@ -1062,15 +1062,17 @@ extern "C" int dpenv_get_policy_launch(dpenv_handle h, int32_t* two_wave_out, in
     return DPENV_OK;
 }
 
+static int policy_prec(const PolicyArgs& pa) { return !pa.split ? PREC_F16 : (pa.critic_f16 ? PREC_F32_ACTOR : PREC_F32); }
+
 extern "C" int dpenv_get_policy_launch_ex(dpenv_handle h, int32_t out[4])
 {
     if (!h || !out) return fail(h, DPENV_EINVAL, "dpenv_get_policy_launch_ex: NULL argument");
     if (!h->has_policy) return fail(h, DPENV_EINVAL, "dpenv_set_policy has not been called");
     const PolicyArgs& pa = h->pol;
-    const int prec = !pa.split ? PREC_F16 : (pa.critic_f16 ? PREC_F32_ACTOR : PREC_F32);
+    const int prec = policy_prec(pa);
     out[0] = pa.ws ? 1 : 0;
     out[1] = pa.ws ? 64 * pa.ws_groups : 256;
-    out[2] = !pa.ws ? 1 : ((pa.ws_groups == 2 && ((DPENV_WS_CRITIC_WAVE >> prec) & 1)) ? 3 : 2);      // waves per 64 envs (dpenv_policy_ws.h: go<>)
+    out[2] = pa.ws ? ws_roles(prec, pa.ws_groups) : 1;      // waves per 64 envs
     out[3] = prec;
     return DPENV_OK;
 }
@@ -1089,10 +1091,10 @@ extern "C" int dpenv_policy_forward(dpenv_handle h, const float* obs, float* mu_
     if (!h->has_policy) return fail(h, DPENV_EINVAL, "dpenv_set_policy has not been called");
     if (!obs || !mu_out || !v_out || n <= 0) return fail(h, DPENV_EINVAL, "dpenv_policy_forward: bad argument");
     if (h->pol.split)
-        HIP_TRY(h, dpenv_dev_launch_policy_forward_x(&h->pol, dpenv_obs_dim(&h->cfg), dpenv_act_dim(&h->cfg), obs, mu_out, v_out, n,
+        HIP_TRY(h, dev::launch_policy_forward_x(&h->pol, dpenv_obs_dim(&h->cfg), dpenv_act_dim(&h->cfg), obs, mu_out, v_out, n,
                                                      (hipStream_t)s));
     else
-        HIP_TRY(h, dpenv_dev_launch_policy_forward(&h->pol, dpenv_obs_dim(&h->cfg), dpenv_act_dim(&h->cfg), obs, mu_out, v_out, n,
+        HIP_TRY(h, dev::launch_policy_forward(&h->pol, dpenv_obs_dim(&h->cfg), dpenv_act_dim(&h->cfg), obs, mu_out, v_out, n,
                                                    (hipStream_t)s));
     return mark_policy_read(h, s);
 }
@@ -1110,6 +1112,31 @@ extern "C" int dpenv_debug_pk_probe(dpenv_handle h, void* out, void* sink, int b
     return DPENV_OK;
 }
 #endif
+
+// Which closed-loop kernel runs: the one place that decides.  The two-wave form runs where its launcher has the instantiation (the ws_*
+// predicates of dpenv_dev.h, the same ones it instantiates by); everything else runs the one-wave kernels - the same rows bit for bit, the
+// hull / current re-draw and the table's thrust loss a run-time switch there, which know the thrust loss through the table alone.
+static int launch_closed_loop(dpenv_handle h, StepArgs& a, PolicyArgs& pa, const IntegArgs* ia, hipStream_t s)
+{
+    const int mode = h->mode, ext = h->cfg.extended_state, ka = pa.ks + 16 * pa.act;
+    if (ia && !integ_one_wave(mode, ext, ka))
+        return fail(h, DPENV_EINVAL, "the integral action runs with the final variant (continuous angles), limited or full, extended_state, and a "
+                                     "leaky-relu / relu network of hidden width <= 80");
+    const bool general = a.rand_tab || a.loss_on != LOSS_NONE || a.cur_nom;       // hull / current re-draws, a thrust loss
+    if ((general && !ws_general(mode, ext, ka)) || (ia && !ws_integ(mode, ext, ka))) pa.ws = 0;
+    hipError_t e;
+    if (!pa.ws) {
+        bind_shared_loss_as_table(h, a);
+        e = pa.split ? dev::launch_policy_rollout_x(&a, &pa, ia, mode, ext, s) : dev::launch_policy_rollout(&a, &pa, ia, mode, ext, s);
+    } else if (!pa.split) {
+        e = dev::launch_policy_rollout_ws<PREC_F16>(&a, &pa, ia, mode, ext, s);
+    } else {
+        e = pa.critic_f16 ? dev::launch_policy_rollout_ws<PREC_F32_ACTOR>(&a, &pa, ia, mode, ext, s)
+                          : dev::launch_policy_rollout_ws<PREC_F32>(&a, &pa, ia, mode, ext, s);
+    }
+    if (e != hipSuccess) return fail(h, DPENV_EHIP, "closed-loop launch failed: %s", hipGetErrorString(e));
+    return DPENV_OK;
+}
 
 static int policy_rollout_impl(dpenv_handle h, const dpenv_policy_rollout_io* io, float* integ_out, dpenv_stream s)
 {
@@ -1143,31 +1170,10 @@ static int policy_rollout_impl(dpenv_handle h, const dpenv_policy_rollout_io* io
 #ifdef DPENV_WS_SELFCHECK
     pa.dbg = g_selfcheck_buf;
 #endif
-    // the two-wave kernels carry the randomisation's hull re-draw in an instantiation of their own, built for the shipped training configuration
-    // (final / continuous angles / extended state, leaky-relu or relu networks); everything else runs the one-wave kernels while the
-    // randomisation is on - the same rows bit for bit, the draw a run-time switch there
-    const bool shipped = h->mode == MODE_FINAL_CONT && h->cfg.extended_state && pa.act == DPENV_ACT_LEAKY_RELU;
-    if ((a.rand_tab || a.loss_on != LOSS_NONE || a.cur_nom) && pa.ws && !shipped) pa.ws = 0;
-    // the one-wave kernels (and only they, after the line above) know the thrust loss through the table alone
-    if (h->integ_on) {
-        // the integral action's kernels: the final variant / continuous angles in every form, limited and full in the one-wave form
-        const bool final_cont = h->mode == MODE_FINAL_CONT;
-        if (!(final_cont || h->mode == MODE_LIMITED || h->mode == MODE_FULL) || !h->cfg.extended_state || pa.act != DPENV_ACT_LEAKY_RELU || pa.ks != 5)
-            return fail(h, DPENV_EINVAL, "the integral action runs with the final variant (continuous angles), limited or full, extended_state, and a "
-                                         "leaky-relu / relu network of hidden width <= 80");
-        if (!final_cont) pa.ws = 0;
-    }
-    if (!pa.ws) bind_shared_loss_as_table(h, a);
-    if (h->integ_on) {
-        IntegArgs ia = h->integ;
-        ia.out = integ_out;
-        if (pa.split) HIP_TRY(h, dpenv_dev_launch_policy_rollout_x_integ(&a, &pa, &ia, h->mode, h->cfg.extended_state, (hipStream_t)s));
-        else HIP_TRY(h, dpenv_dev_launch_policy_rollout_integ(&a, &pa, &ia, h->mode, h->cfg.extended_state, (hipStream_t)s));
-    } else if (pa.split) {
-        HIP_TRY(h, dpenv_dev_launch_policy_rollout_x(&a, &pa, h->mode, h->cfg.extended_state, (hipStream_t)s));
-    } else {
-        HIP_TRY(h, dpenv_dev_launch_policy_rollout(&a, &pa, h->mode, h->cfg.extended_state, (hipStream_t)s));
-    }
+    IntegArgs ia = h->integ;
+    ia.out = integ_out;
+    const int rc = launch_closed_loop(h, a, pa, h->integ_on ? &ia : nullptr, (hipStream_t)s);
+    if (rc != DPENV_OK) return rc;
     h->lag_valid = true;
     return mark_policy_read(h, s);
 }
@@ -1221,7 +1227,7 @@ extern "C" int dpenv_set_integral_action(dpenv_handle h, const dpenv_integral_ac
     g.step_s = ia->step_s > 0.0f ? ia->step_s : h->cfg.substep_dt * (float)h->cfg.n_substeps;
     g.dwell = (int32_t)D;
     g.out = nullptr;
-    HIP_TRY(h, dpenv_dev_launch_integ_clear(g.state, nullptr, h->cfg.n_envs, (hipStream_t)s));
+    HIP_TRY(h, dev::launch_integ_clear(g.state, nullptr, h->cfg.n_envs, (hipStream_t)s));
     h->integ_on = true;
     return DPENV_OK;
 }
@@ -1232,7 +1238,7 @@ extern "C" int dpenv_get_integral_state(dpenv_handle h, float* I_out, int32_t* c
     if (!h->integ_on) return fail(h, DPENV_EINVAL, "dpenv_get_integral_state: the integral action is off");
     if (!I_out && !count_out) return fail(h, DPENV_EINVAL, "dpenv_get_integral_state: NULL argument");
     DeviceGuard dev_guard(h->device);
-    HIP_TRY(h, dpenv_dev_launch_integ_state_io(h->integ.state, I_out, count_out, h->cfg.n_envs, 0, (hipStream_t)s));
+    HIP_TRY(h, dev::launch_integ_state_io(h->integ.state, I_out, count_out, h->cfg.n_envs, 0, (hipStream_t)s));
     return DPENV_OK;
 }
 
@@ -1242,7 +1248,7 @@ extern "C" int dpenv_set_integral_state(dpenv_handle h, const float* I_in, const
     if (!h->integ_on) return fail(h, DPENV_EINVAL, "dpenv_set_integral_state: the integral action is off");
     if (!I_in && !count_in) return fail(h, DPENV_EINVAL, "dpenv_set_integral_state: NULL argument");
     DeviceGuard dev_guard(h->device);
-    HIP_TRY(h, dpenv_dev_launch_integ_state_io(h->integ.state, (float*)I_in, (int32_t*)count_in, h->cfg.n_envs, 1, (hipStream_t)s));
+    HIP_TRY(h, dev::launch_integ_state_io(h->integ.state, (float*)I_in, (int32_t*)count_in, h->cfg.n_envs, 1, (hipStream_t)s));
     return DPENV_OK;
 }
 
@@ -1250,7 +1256,7 @@ extern "C" int dpenv_get_state(dpenv_handle h, float* state_out, int32_t* counte
 {
     if (!h) return DPENV_EINVAL;
     DeviceGuard dev_guard(h->device);
-    HIP_TRY(h, dpenv_dev_launch_get_state(&h->args, state_out, counters_out, (hipStream_t)s));
+    HIP_TRY(h, dev::launch_get_state(&h->args, state_out, counters_out, (hipStream_t)s));
     return DPENV_OK;
 }
 
@@ -1258,7 +1264,7 @@ extern "C" int dpenv_set_state(dpenv_handle h, const float* state_in, const int3
 {
     if (!h) return DPENV_EINVAL;
     DeviceGuard dev_guard(h->device);
-    HIP_TRY(h, dpenv_dev_launch_set_state(&h->args, state_in, counters_in, (hipStream_t)s));
+    HIP_TRY(h, dev::launch_set_state(&h->args, state_in, counters_in, (hipStream_t)s));
     if (state_in) h->lag_valid = true;                     // the kernel wrote the columns a state-rebuilt observation carries (pt / 100)
     return DPENV_OK;
 }
@@ -1312,11 +1318,11 @@ extern "C" int dpenv_thrust_map(const float* params, const float* n_pct, const f
     VesselDev vd;
     std::string why;
     if (derive_vessel(params, &vd, &why, true) != DPENV_OK) return fail(nullptr, DPENV_EINVAL, "%s", why.c_str());
-    HIP_TRY(nullptr, dpenv_dev_launch_thrust_map(&vd, n_pct, alpha, tau_out, n, (hipStream_t)s));
+    HIP_TRY(nullptr, dev::launch_thrust_map(&vd, n_pct, alpha, tau_out, n, (hipStream_t)s));
     return DPENV_OK;
 }
 
-extern "C" int64_t dpenv_gae_workspace_bytes(int32_t n) { return n > 0 ? dpenv_dev_gae_workspace_bytes(n) : 0; }
+extern "C" int64_t dpenv_gae_workspace_bytes(int32_t n) { return n > 0 ? dev::gae_workspace_bytes(n) : 0; }
 
 extern "C" int dpenv_gae_stats(const float* rew, const float* val, const uint8_t* end, const float* boot, const float* last_val,
                                int32_t T, int32_t n, float gamma, float lam, float* adv_out, float* ret_out, void* workspace,
@@ -1325,7 +1331,7 @@ extern "C" int dpenv_gae_stats(const float* rew, const float* val, const uint8_t
     if (!rew || !val || !adv_out || !ret_out || T <= 0 || n <= 0)
         return fail(nullptr, DPENV_EINVAL, "dpenv_gae: bad argument");
     if (stats_out && !workspace) return fail(nullptr, DPENV_EINVAL, "dpenv_gae_stats: statistics need the workspace (dpenv_gae_workspace_bytes)");
-    HIP_TRY(nullptr, dpenv_dev_launch_gae(rew, val, end, boot, last_val, T, n, gamma, lam, adv_out, ret_out, (double*)workspace,
+    HIP_TRY(nullptr, dev::launch_gae(rew, val, end, boot, last_val, T, n, gamma, lam, adv_out, ret_out, (double*)workspace,
                                           stats_out, (hipStream_t)s));
     return DPENV_OK;
 }
@@ -1339,27 +1345,27 @@ extern "C" int dpenv_gae(const float* rew, const float* val, const uint8_t* end,
 extern "C" int dpenv_adv_sum(const float* adv, int64_t count, float* sum_out, dpenv_stream s)
 {
     if (!adv || !sum_out || count <= 0) return fail(nullptr, DPENV_EINVAL, "dpenv_adv_sum: bad argument");
-    HIP_TRY(nullptr, dpenv_dev_launch_sum(adv, count, nullptr, sum_out, (hipStream_t)s));
+    HIP_TRY(nullptr, dev::launch_sum(adv, count, nullptr, sum_out, (hipStream_t)s));
     return DPENV_OK;
 }
 
 extern "C" int dpenv_adv_sumsq(const float* adv, int64_t count, const float* mean, float* sumsq_out, dpenv_stream s)
 {
     if (!adv || !mean || !sumsq_out || count <= 0) return fail(nullptr, DPENV_EINVAL, "dpenv_adv_sumsq: bad argument");
-    HIP_TRY(nullptr, dpenv_dev_launch_sum(adv, count, mean, sumsq_out, (hipStream_t)s));
+    HIP_TRY(nullptr, dev::launch_sum(adv, count, mean, sumsq_out, (hipStream_t)s));
     return DPENV_OK;
 }
 
 extern "C" int dpenv_adv_apply(float* adv, int64_t count, const float* mean, const float* std, dpenv_stream s)
 {
     if (!adv || !mean || !std || count <= 0) return fail(nullptr, DPENV_EINVAL, "dpenv_adv_apply: bad argument");
-    HIP_TRY(nullptr, dpenv_dev_launch_adv_apply(adv, count, mean, std, nullptr, 0.0, (hipStream_t)s));
+    HIP_TRY(nullptr, dev::launch_adv_apply(adv, count, mean, std, nullptr, 0.0, (hipStream_t)s));
     return DPENV_OK;
 }
 
 extern "C" int dpenv_adv_apply_stats(float* adv, int64_t count, const double* stats, double total_count, dpenv_stream s)
 {
     if (!adv || !stats || count <= 0 || !(total_count >= 1.0)) return fail(nullptr, DPENV_EINVAL, "dpenv_adv_apply_stats: bad argument");
-    HIP_TRY(nullptr, dpenv_dev_launch_adv_apply(adv, count, nullptr, nullptr, stats, total_count, (hipStream_t)s));
+    HIP_TRY(nullptr, dev::launch_adv_apply(adv, count, nullptr, nullptr, stats, total_count, (hipStream_t)s));
     return DPENV_OK;
 }

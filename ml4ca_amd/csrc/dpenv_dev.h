@@ -5,6 +5,7 @@
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <type_traits>
 
 #ifndef DPENV_BLOCK
 #define DPENV_BLOCK 64    // threads per workgroup = one wave64; one lane per environment; LDS staging is wave-private
@@ -207,7 +208,7 @@ struct PackNet {
 };
 
 // which arithmetics get a critic wave of their own (ROLES = 3) in the 128-env geometry of the two-wave closed loop: bit 0 f16, bit 1 all
-// exact, bit 2 exact actor (dpenv_policy_ws.h has the measurements); here because dpenv_get_policy_launch_ex reports the resolved form
+// exact, bit 2 exact actor (dpenv_policy_ws.h has the measurements)
 #ifndef DPENV_WS_CRITIC_WAVE
 #define DPENV_WS_CRITIC_WAVE 6
 #endif
@@ -216,63 +217,157 @@ constexpr int POLICY_WS_MAILBOX_X_BYTES = 4 * (64 * 9 * 4 + 64 * 4 + 64) * 4; //
 constexpr int PREC_F16 = 0, PREC_F32 = 1, PREC_F32_ACTOR = 2;                 // = DPENV_POLICY_* of include/dpenv.h
 constexpr int POLICY_STAGING_BYTES = 4 * 64 * 9 * 4;                           // one-wave form: four wave-private row areas
 
-}  // namespace dpenv
+// =============================================================================================
+//  launch layer: run-time axes -> template instantiations
+// =============================================================================================
+// Each with_* helper calls f with a std::integral_constant of the run-time value; an unknown value is hipErrorInvalidValue.
+// -DDPENV_DEV_FAST (development builds only, never shipped) narrows the axes here and nowhere else: each helper then admits the
+// shipped value alone - final variant / continuous angles, extended state, hidden width <= 80 leaky-relu, obs 9 / act 7.
+template <int V> using Int = std::integral_constant<int, V>;
 
-extern "C" {
-hipError_t dpenv_dev_launch_pack_policy(const dpenv::PackNet* pi, const dpenv::PackNet* v, const float* log_std, int adim, int ks,
-                                        int nent, int nblk, int split, void* frags, float* bias, float* consts, hipStream_t s);
-hipError_t dpenv_dev_launch_policy_forward_x(const dpenv::PolicyArgs* pa, int od, int adim, const float* obs, float* mu,
-                                             float* v, int n, hipStream_t s);
-hipError_t dpenv_dev_launch_policy_rollout_x(const dpenv::StepArgs* a, const dpenv::PolicyArgs* pa, int mode, int ext,
-                                             hipStream_t s);
-hipError_t dpenv_dev_launch_policy_rollout_ws(const dpenv::StepArgs* a, const dpenv::PolicyArgs* pa, int mode, int ext, hipStream_t s);
-// two-wave form of the split arithmetics (dpenv_policy_xws1.hip: PREC_F32, dpenv_policy_xws2.hip: PREC_F32_ACTOR)
-hipError_t dpenv_dev_launch_policy_rollout_xws_f32(const dpenv::StepArgs* a, const dpenv::PolicyArgs* pa, int mode, int ext,
-                                                   hipStream_t s);
-hipError_t dpenv_dev_launch_policy_rollout_xws_f32_actor(const dpenv::StepArgs* a, const dpenv::PolicyArgs* pa, int mode, int ext,
-                                                         hipStream_t s);
-// the closed loop with the integral action (IntegArgs): one-wave kernels of dpenv_policy.hip / dpenv_policy_x.hip, which hand pa->ws launches
-// to the two-wave kernels of their arithmetic's translation unit
-hipError_t dpenv_dev_launch_policy_rollout_integ(const dpenv::StepArgs* a, const dpenv::PolicyArgs* pa, const dpenv::IntegArgs* ia, int mode,
-                                                 int ext, hipStream_t s);
-hipError_t dpenv_dev_launch_policy_rollout_x_integ(const dpenv::StepArgs* a, const dpenv::PolicyArgs* pa, const dpenv::IntegArgs* ia, int mode,
-                                                   int ext, hipStream_t s);
-hipError_t dpenv_dev_launch_policy_rollout_ws_integ(const dpenv::StepArgs* a, const dpenv::PolicyArgs* pa, const dpenv::IntegArgs* ia, int mode,
-                                                    int ext, hipStream_t s);
-hipError_t dpenv_dev_launch_policy_rollout_xws_f32_integ(const dpenv::StepArgs* a, const dpenv::PolicyArgs* pa, const dpenv::IntegArgs* ia,
-                                                         int mode, int ext, hipStream_t s);
-hipError_t dpenv_dev_launch_policy_rollout_xws_f32_actor_integ(const dpenv::StepArgs* a, const dpenv::PolicyArgs* pa, const dpenv::IntegArgs* ia,
-                                                               int mode, int ext, hipStream_t s);
-hipError_t dpenv_dev_launch_integ_clear(float4* state, const uint8_t* mask, int n, hipStream_t s);
-hipError_t dpenv_dev_launch_integ_state_io(float4* state, float* I, int32_t* c, int n, int write, hipStream_t s);
-hipError_t dpenv_dev_launch_policy_forward(const dpenv::PolicyArgs* pa, int od, int adim, const float* obs, float* mu,
-                                           float* v, int n, hipStream_t s);
-hipError_t dpenv_dev_launch_policy_rollout(const dpenv::StepArgs* a, const dpenv::PolicyArgs* pa, int mode, int ext,
-                                           hipStream_t s);
-hipError_t dpenv_dev_launch_rollout(const dpenv::StepArgs* a, const dpenv::RolloutArgs* ra, int mode, int ext, int ves, int two_wave,
-                                    hipStream_t s);
-// ves: VES_* (where the vessel of a lane comes from)
-hipError_t dpenv_dev_launch_step(const dpenv::StepArgs* a, int mode, int ext, int ves, int reset_wave, hipStream_t s);
+template <typename F> hipError_t with_mode(int mode, F&& f)
+{
+    switch (mode) {
+#ifndef DPENV_DEV_FAST
+    case MODE_FULL: return f(Int<MODE_FULL>{});
+    case MODE_SIMPLE: return f(Int<MODE_SIMPLE>{});
+    case MODE_LIMITED: return f(Int<MODE_LIMITED>{});
+    case MODE_FINAL_WRAP: return f(Int<MODE_FINAL_WRAP>{});
+#endif
+    case MODE_FINAL_CONT: return f(Int<MODE_FINAL_CONT>{});
+    }
+    return hipErrorInvalidValue;
+}
+
+template <typename F> hipError_t with_ext(int ext, F&& f)
+{
+    if (ext) return f(std::true_type{});
+#ifndef DPENV_DEV_FAST
+    return f(std::false_type{});
+#else
+    return hipErrorInvalidValue;
+#endif
+}
+
+template <typename F> hipError_t with_mode_ext(int mode, int ext, F&& f)
+{
+    return with_mode(mode, [&](auto M) { return with_ext(ext, [&](auto E) { return f(M, E); }); });
+}
+
+// KA = ks + 16 act: hidden width <= 80 (ks 5) or <= 96 (ks 6) x leaky-relu / relu (act 0) or tanh (act 1)
+template <typename F> hipError_t with_ka(const PolicyArgs& pa, F&& f)
+{
+    if ((pa.ks != 5 && pa.ks != 6) || (pa.act != 0 && pa.act != 1)) return hipErrorInvalidValue;
+    switch (pa.ks + 16 * pa.act) {
+    case 5: return f(Int<5>{});
+#ifndef DPENV_DEV_FAST
+    case 6: return f(Int<6>{});
+    case 21: return f(Int<21>{});
+    case 22: return f(Int<22>{});
+#endif
+    }
+    return hipErrorInvalidValue;
+}
+
+template <typename F> hipError_t with_mode_ext_ka(int mode, int ext, const PolicyArgs& pa, F&& f)
+{
+    return with_mode_ext(mode, ext, [&](auto M, auto E) { return with_ka(pa, [&](auto K) { return f(M, E, K); }); });
+}
+
+// the (obs dim, act dim) pairs of the env variants (dpenv_obs_dim / dpenv_act_dim): the standalone forward kernels' shapes
+template <typename F> hipError_t with_obs_act(int od, int adim, F&& f)
+{
+    if (od == 9 && adim == 7) return f(Int<9>{}, Int<7>{});
+#ifndef DPENV_DEV_FAST
+    if (od == 9 && adim == 5) return f(Int<9>{}, Int<5>{});
+    if (od == 9 && adim == 6) return f(Int<9>{}, Int<6>{});
+    if (od == 6 && adim == 7) return f(Int<6>{}, Int<7>{});
+    if (od == 6 && adim == 5) return f(Int<6>{}, Int<5>{});
+    if (od == 6 && adim == 6) return f(Int<6>{}, Int<6>{});
+    if (od == 6 && adim == 3) return f(Int<6>{}, Int<3>{});
+#endif
+    return hipErrorInvalidValue;
+}
+
+template <typename F> hipError_t with_ves(int ves, F&& f)
+{
+    switch (ves) {
+    case VES_ARGS: return f(Int<VES_ARGS>{});
+    case VES_CLASS_LDS: return f(Int<VES_CLASS_LDS>{});
+    case VES_ENV_VGPR: return f(Int<VES_ENV_VGPR>{});
+    case VES_ENV_LDS: return f(Int<VES_ENV_LDS>{});
+    case VES_ENV_RND: return f(Int<VES_ENV_RND>{});
+    case VES_ARGS_LOSS: return f(Int<VES_ARGS_LOSS>{});
+    }
+    return hipErrorInvalidValue;
+}
+
+// a launch with dynamic LDS above the default limit: raise the kernel's limit, then launch
+template <typename... P, typename... A>
+hipError_t launch_with_lds(void (*kernel)(P...), dim3 grid, dim3 block, size_t lds, hipStream_t s, const A&... args)
+{
+    hipError_t e = hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(kernel, grid, block, lds, s, args...);
+    return hipGetLastError();
+}
+
+// ---- the instantiation set of each kernel family, stated once: its launcher instantiates what these admit, and the host routes by them ----
+// step_kernel, rollout_kernel / rollout_ws_kernel, reset_kernel: every MODE x EXT (x VES), the vessel source mapped as follows
+constexpr int step_ves(int ves) { return ves == VES_ENV_LDS && BLOCK != 64 ? VES_ENV_VGPR : ves; }   // the LDS image is one wave's
+constexpr int rollout_ves(int ves) { return ves == VES_ENV_LDS ? VES_ENV_VGPR : ves; }   // a T-step kernel's staging area is the register file
+// one-wave closed loop (f16 and split arithmetics), standalone forward: every MODE x EXT x KA; with the integral action:
+constexpr bool integ_one_wave(int mode, bool ext, int ka)
+{
+    return (mode == MODE_FINAL_CONT || mode == MODE_LIMITED || mode == MODE_FULL) && ext && ka == 5;
+}
+// two-wave closed loop (every MODE x EXT): leaky-relu / relu in every arithmetic and geometry, tanh in f16 with four groups only
+constexpr bool ws_has(int ka, int prec, int groups) { return ka < 16 || (prec == PREC_F16 && groups == 4); }
+// its general per-env (RND) and shared training (SLOSS) forms: the shipped training configuration (train.py:47-54) with leaky-relu / relu
+constexpr bool ws_general(int mode, bool ext, int ka) { return mode == MODE_FINAL_CONT && ext && ka < 16; }
+// its integral action: the final variant / continuous angles, extended state, leaky-relu / relu of width <= 80
+constexpr bool ws_integ(int mode, bool ext, int ka) { return mode == MODE_FINAL_CONT && ext && ka == 5; }
+// waves per 64 envs of the two-wave form: an env and a network wave, plus a critic wave where DPENV_WS_CRITIC_WAVE gives one
+constexpr int ws_roles(int prec, int groups) { return (groups == 2 && ((DPENV_WS_CRITIC_WAVE >> prec) & 1)) ? 3 : 2; }
+
+// ---- launchers: called by dpenv_api.hip, defined by the translation unit that owns the kernels; not exported from libdpenv.so ----
+namespace __attribute__((visibility("hidden"))) dev {
+// dpenv_kernels.hip.  ves: VES_* (where the vessel of a lane comes from)
+hipError_t launch_step(const StepArgs* a, int mode, int ext, int ves, int reset_wave, hipStream_t s);
+hipError_t launch_rollout(const StepArgs* a, const RolloutArgs* ra, int mode, int ext, int ves, int two_wave, hipStream_t s);
+hipError_t launch_reset(const StepArgs* a, int mode, int ext, const uint8_t* mask, const float* init, const float* ref, hipStream_t s);
+hipError_t launch_get_state(const StepArgs* a, float* st, int32_t* ctr, hipStream_t s);
+hipError_t launch_set_state(const StepArgs* a, const float* st, const int32_t* ctr, hipStream_t s);
 // raw public parameters -> per-env blocks: raw[p * p_stride + i * i_stride] (SoA block: p_stride = n, i_stride = 1; one vector for every env:
 // p_stride = 1, i_stride = 0); and back (out[p * n + i])
 // tab: ET[DRAW_GROUPS][stride] (vessel block + thrust-loss rows); loss_flag (device word, may be NULL) is OR-ed with 1 if any env's
 // thrust-loss coefficient is non-zero
-hipError_t dpenv_dev_launch_pack_env_vessels(const float* raw, int64_t p_stride, int64_t i_stride, float4* tab, uint32_t* loss_flag,
-                                             int stride, int n, hipStream_t s);
-hipError_t dpenv_dev_launch_unpack_env_vessels(const float4* tab, int stride, float* out, int n, hipStream_t s);
-hipError_t dpenv_dev_launch_reset(const dpenv::StepArgs* a, int mode, int ext, const uint8_t* mask, const float* init,
-                                  const float* ref, hipStream_t s);
-hipError_t dpenv_dev_launch_get_state(const dpenv::StepArgs* a, float* st, int32_t* ctr, hipStream_t s);
-hipError_t dpenv_dev_launch_set_state(const dpenv::StepArgs* a, const float* st, const int32_t* ctr, hipStream_t s);
-hipError_t dpenv_dev_launch_thrust_map(const dpenv::VesselDev* vd, const float* n_pct, const float* alpha, float* tau,
-                                       int n, hipStream_t s);
-int64_t dpenv_dev_gae_workspace_bytes(int n);
-hipError_t dpenv_dev_launch_gae(const float* rew, const float* val, const uint8_t* end, const float* boot,
-                                const float* last_val, int T, int n, float gamma, float lam, float* adv, float* ret,
-                                double* workspace, double* stats, hipStream_t s);
-hipError_t dpenv_dev_launch_sum(const float* x, int64_t count, const float* mean, float* out, hipStream_t s);
-hipError_t dpenv_dev_launch_adv_apply(float* x, int64_t count, const float* mean, const float* std, const double* stats,
-                                      double total_count, hipStream_t s);
-}
+hipError_t launch_pack_env_vessels(const float* raw, int64_t p_stride, int64_t i_stride, float4* tab, uint32_t* loss_flag, int stride, int n,
+                                   hipStream_t s);
+hipError_t launch_unpack_env_vessels(const float4* tab, int stride, float* out, int n, hipStream_t s);
+hipError_t launch_thrust_map(const VesselDev* vd, const float* n_pct, const float* alpha, float* tau, int n, hipStream_t s);
+int64_t gae_workspace_bytes(int n);
+hipError_t launch_gae(const float* rew, const float* val, const uint8_t* end, const float* boot, const float* last_val, int T, int n,
+                      float gamma, float lam, float* adv, float* ret, double* workspace, double* stats, hipStream_t s);
+hipError_t launch_sum(const float* x, int64_t count, const float* mean, float* out, hipStream_t s);
+hipError_t launch_adv_apply(float* x, int64_t count, const float* mean, const float* std, const double* stats, double total_count,
+                            hipStream_t s);
+// dpenv_policy.hip (f16) and dpenv_policy_x.hip (split arithmetics): weight packing, standalone forward, one-wave closed loop;
+// ia != NULL: the closed loop with the integral action
+hipError_t launch_pack_policy(const PackNet* pi, const PackNet* v, const float* log_std, int adim, int ks, int nent, int nblk, int split,
+                              void* frags, float* bias, float* consts, hipStream_t s);
+hipError_t launch_policy_forward(const PolicyArgs* pa, int od, int adim, const float* obs, float* mu, float* v, int n, hipStream_t s);
+hipError_t launch_policy_forward_x(const PolicyArgs* pa, int od, int adim, const float* obs, float* mu, float* v, int n, hipStream_t s);
+hipError_t launch_policy_rollout(const StepArgs* a, const PolicyArgs* pa, const IntegArgs* ia, int mode, int ext, hipStream_t s);
+hipError_t launch_policy_rollout_x(const StepArgs* a, const PolicyArgs* pa, const IntegArgs* ia, int mode, int ext, hipStream_t s);
+hipError_t launch_integ_clear(float4* state, const uint8_t* mask, int n, hipStream_t s);
+hipError_t launch_integ_state_io(float4* state, float* I, int32_t* c, int n, int write, hipStream_t s);
+// two-wave closed loop, dpenv_policy_ws.h; one arithmetic per translation unit: dpenv_policy_ws.hip PREC_F16, dpenv_policy_xws1.hip
+// PREC_F32, dpenv_policy_xws2.hip PREC_F32_ACTOR
+template <int PREC>
+hipError_t launch_policy_rollout_ws(const StepArgs* a, const PolicyArgs* pa, const IntegArgs* ia, int mode, int ext, hipStream_t s);
+}  // namespace dev
+
+}  // namespace dpenv
 
 #endif

@@ -1110,39 +1110,9 @@ __device__ double g_sum_partials[2 * SUM_MAXGRID];
 }  // namespace dpenv
 
 // =============================================================================================
-//  launchers (called from dpenv_api.cpp through dpenv_dev.h)
+//  launchers (called from dpenv_api.hip through dpenv_dev.h)
 // =============================================================================================
 using namespace dpenv;
-
-template <int MODE, int VES>
-static hipError_t launch_step_ves(const StepArgs& a, bool ext, bool reset_wave, hipStream_t s)
-{
-    const dim3 grid((a.n + BLOCK - 1) / BLOCK), block(BLOCK);
-    if (a.auto_reset && BLOCK == 64 && reset_wave) {
-        // auto-reset on: a second wave per workgroup prepares the re-draws beside the plant loop (RESETW above)
-        const dim3 block2(2 * BLOCK);
-        if (ext) hipLaunchKernelGGL((step_kernel<MODE, true, VES, BLOCK == 64>), grid, block2, 0, s, a);
-        else hipLaunchKernelGGL((step_kernel<MODE, false, VES, BLOCK == 64>), grid, block2, 0, s, a);
-        return hipGetLastError();
-    }
-    if (ext) hipLaunchKernelGGL((step_kernel<MODE, true, VES>), grid, block, 0, s, a);
-    else hipLaunchKernelGGL((step_kernel<MODE, false, VES>), grid, block, 0, s, a);
-    return hipGetLastError();
-}
-
-template <int MODE>
-static hipError_t launch_step_mode(const StepArgs& a, bool ext, int ves, bool reset_wave, hipStream_t s)
-{
-    switch (ves) {
-    case VES_ARGS: return launch_step_ves<MODE, VES_ARGS>(a, ext, reset_wave, s);
-    case VES_CLASS_LDS: return launch_step_ves<MODE, VES_CLASS_LDS>(a, ext, reset_wave, s);
-    case VES_ENV_VGPR: return launch_step_ves<MODE, VES_ENV_VGPR>(a, ext, reset_wave, s);
-    case VES_ENV_LDS: return launch_step_ves<MODE, (BLOCK == 64 ? VES_ENV_LDS : VES_ENV_VGPR)>(a, ext, reset_wave, s);
-    case VES_ENV_RND: return launch_step_ves<MODE, VES_ENV_RND>(a, ext, reset_wave, s);
-    case VES_ARGS_LOSS: return launch_step_ves<MODE, VES_ARGS_LOSS>(a, ext, reset_wave, s);
-    }
-    return hipErrorInvalidValue;
-}
 
 #ifdef DPENV_STEP_TRACE
 extern "C" int dpenv_debug_set_step_trace(void* p)      // device buffer of STEP_TRACE_RING x workgroups x 4 dwords (or NULL)
@@ -1151,126 +1121,82 @@ extern "C" int dpenv_debug_set_step_trace(void* p)      // device buffer of STEP
 }
 #endif
 
-extern "C" hipError_t dpenv_dev_launch_step(const StepArgs* a, int mode, int ext, int ves, int reset_wave, hipStream_t s)
+// the vessel source must match the arguments: a per-env form needs the table, VES_ARGS_LOSS and only it reads StepArgs.kl
+static bool vessel_source_ok(const StepArgs& a, int ves)
 {
-    if (ves >= VES_ENV_VGPR && ves <= VES_ENV_RND && !a->env_tab) return hipErrorInvalidValue;
-    if ((ves == VES_ARGS_LOSS) != (a->loss_on == LOSS_SHARED)) return hipErrorInvalidValue;
-    switch (mode) {
-    case MODE_FULL: return launch_step_mode<MODE_FULL>(*a, ext, ves, reset_wave != 0, s);
-    case MODE_SIMPLE: return launch_step_mode<MODE_SIMPLE>(*a, ext, ves, reset_wave != 0, s);
-    case MODE_LIMITED: return launch_step_mode<MODE_LIMITED>(*a, ext, ves, reset_wave != 0, s);
-    case MODE_FINAL_WRAP: return launch_step_mode<MODE_FINAL_WRAP>(*a, ext, ves, reset_wave != 0, s);
-    case MODE_FINAL_CONT: return launch_step_mode<MODE_FINAL_CONT>(*a, ext, ves, reset_wave != 0, s);
-    }
-    return hipErrorInvalidValue;
+    return !(ves >= VES_ENV_VGPR && ves <= VES_ENV_RND && !a.env_tab) && (ves == VES_ARGS_LOSS) == (a.loss_on == LOSS_SHARED);
 }
 
-extern "C" hipError_t dpenv_dev_launch_pack_env_vessels(const float* raw, int64_t p_stride, int64_t i_stride, float4* tab, uint32_t* loss_flag,
-                                                        int stride, int n, hipStream_t s)
+hipError_t dev::launch_step(const StepArgs* a, int mode, int ext, int ves, int reset_wave, hipStream_t s)
+{
+    if (!vessel_source_ok(*a, ves)) return hipErrorInvalidValue;
+    const dim3 grid((a->n + BLOCK - 1) / BLOCK);
+    // auto-reset on: a second wave per workgroup prepares the re-draws beside the plant loop (RESETW above)
+    const bool two = a->auto_reset && BLOCK == 64 && reset_wave;
+    return with_mode_ext(mode, ext, [&](auto M, auto E) { return with_ves(ves, [&](auto V) {
+        if (two) hipLaunchKernelGGL((step_kernel<M, E, step_ves(V), BLOCK == 64>), grid, dim3(2 * BLOCK), 0, s, *a);
+        else hipLaunchKernelGGL((step_kernel<M, E, step_ves(V)>), grid, dim3(BLOCK), 0, s, *a);
+        return hipGetLastError();
+    }); });
+}
+
+hipError_t dev::launch_pack_env_vessels(const float* raw, int64_t p_stride, int64_t i_stride, float4* tab, uint32_t* loss_flag, int stride, int n,
+                                        hipStream_t s)
 {
     hipLaunchKernelGGL(pack_env_vessels_kernel, dim3((n + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, s, raw, p_stride, i_stride, tab, loss_flag, stride, n);
     return hipGetLastError();
 }
 
-extern "C" hipError_t dpenv_dev_launch_unpack_env_vessels(const float4* tab, int stride, float* out, int n, hipStream_t s)
+hipError_t dev::launch_unpack_env_vessels(const float4* tab, int stride, float* out, int n, hipStream_t s)
 {
     hipLaunchKernelGGL(unpack_env_vessels_kernel, dim3((n + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, s, tab, stride, out, n);
     return hipGetLastError();
 }
 
-template <int MODE, int VES>
-static hipError_t launch_rollout_ves(const StepArgs& a, const RolloutArgs& ra, bool ext, bool two_wave, hipStream_t s)
+hipError_t dev::launch_rollout(const StepArgs* a, const RolloutArgs* ra, int mode, int ext, int ves, int two_wave, hipStream_t s)
 {
-    const dim3 grid((a.n + RBLOCK - 1) / RBLOCK), block(RBLOCK);
-    if (two_wave) {
-        const dim3 block2(128);
-        if (ext) hipLaunchKernelGGL((rollout_ws_kernel<MODE, true, VES>), grid, block2, 0, s, a, ra);
-        else hipLaunchKernelGGL((rollout_ws_kernel<MODE, false, VES>), grid, block2, 0, s, a, ra);
+    if (!vessel_source_ok(*a, ves)) return hipErrorInvalidValue;
+    const dim3 grid((a->n + RBLOCK - 1) / RBLOCK);
+    return with_mode_ext(mode, ext, [&](auto M, auto E) { return with_ves(ves, [&](auto V) {
+        if (two_wave) hipLaunchKernelGGL((rollout_ws_kernel<M, E, rollout_ves(V)>), grid, dim3(128), 0, s, *a, *ra);
+        else hipLaunchKernelGGL((rollout_kernel<M, E, rollout_ves(V)>), grid, dim3(RBLOCK), 0, s, *a, *ra);
         return hipGetLastError();
-    }
-    if (ext) hipLaunchKernelGGL((rollout_kernel<MODE, true, VES>), grid, block, 0, s, a, ra);
-    else hipLaunchKernelGGL((rollout_kernel<MODE, false, VES>), grid, block, 0, s, a, ra);
-    return hipGetLastError();
+    }); });
 }
 
-template <int MODE>
-static hipError_t launch_rollout_mode(const StepArgs& a, const RolloutArgs& ra, bool ext, int ves, bool two_wave, hipStream_t s)
+hipError_t dev::launch_reset(const StepArgs* a, int mode, int ext, const uint8_t* mask, const float* init, const float* ref, hipStream_t s)
 {
-    switch (ves) {
-    case VES_ARGS: return launch_rollout_ves<MODE, VES_ARGS>(a, ra, ext, two_wave, s);
-    case VES_CLASS_LDS: return launch_rollout_ves<MODE, VES_CLASS_LDS>(a, ra, ext, two_wave, s);
-    case VES_ENV_VGPR: case VES_ENV_LDS: return launch_rollout_ves<MODE, VES_ENV_VGPR>(a, ra, ext, two_wave, s);   // a T-step kernel's staging area is the register file
-    case VES_ENV_RND: return launch_rollout_ves<MODE, VES_ENV_RND>(a, ra, ext, two_wave, s);
-    case VES_ARGS_LOSS: return launch_rollout_ves<MODE, VES_ARGS_LOSS>(a, ra, ext, two_wave, s);
-    }
-    return hipErrorInvalidValue;
+    return with_mode_ext(mode, ext, [&](auto M, auto E) {
+        hipLaunchKernelGGL((reset_kernel<M, E>), dim3((a->n + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, s, *a, mask, init, ref);
+        return hipGetLastError();
+    });
 }
 
-extern "C" hipError_t dpenv_dev_launch_rollout(const StepArgs* a, const RolloutArgs* ra, int mode, int ext, int ves, int two_wave,
-                                               hipStream_t s)
-{
-    if (ves >= VES_ENV_VGPR && ves <= VES_ENV_RND && !a->env_tab) return hipErrorInvalidValue;
-    if ((ves == VES_ARGS_LOSS) != (a->loss_on == LOSS_SHARED)) return hipErrorInvalidValue;
-    switch (mode) {
-    case MODE_FULL: return launch_rollout_mode<MODE_FULL>(*a, *ra, ext, ves, two_wave != 0, s);
-    case MODE_SIMPLE: return launch_rollout_mode<MODE_SIMPLE>(*a, *ra, ext, ves, two_wave != 0, s);
-    case MODE_LIMITED: return launch_rollout_mode<MODE_LIMITED>(*a, *ra, ext, ves, two_wave != 0, s);
-    case MODE_FINAL_WRAP: return launch_rollout_mode<MODE_FINAL_WRAP>(*a, *ra, ext, ves, two_wave != 0, s);
-    case MODE_FINAL_CONT: return launch_rollout_mode<MODE_FINAL_CONT>(*a, *ra, ext, ves, two_wave != 0, s);
-    }
-    return hipErrorInvalidValue;
-}
-
-template <int MODE>
-static hipError_t launch_reset_mode(const StepArgs& a, bool ext, const uint8_t* mask, const float* init, const float* ref,
-                                    hipStream_t s)
-{
-    const dim3 grid((a.n + BLOCK - 1) / BLOCK), block(BLOCK);
-    if (ext) hipLaunchKernelGGL((reset_kernel<MODE, true>), grid, block, 0, s, a, mask, init, ref);
-    else hipLaunchKernelGGL((reset_kernel<MODE, false>), grid, block, 0, s, a, mask, init, ref);
-    return hipGetLastError();
-}
-
-extern "C" hipError_t dpenv_dev_launch_reset(const StepArgs* a, int mode, int ext, const uint8_t* mask, const float* init,
-                                             const float* ref, hipStream_t s)
-{
-    switch (mode) {
-    case MODE_FULL: return launch_reset_mode<MODE_FULL>(*a, ext, mask, init, ref, s);
-    case MODE_SIMPLE: return launch_reset_mode<MODE_SIMPLE>(*a, ext, mask, init, ref, s);
-    case MODE_LIMITED: return launch_reset_mode<MODE_LIMITED>(*a, ext, mask, init, ref, s);
-    case MODE_FINAL_WRAP: return launch_reset_mode<MODE_FINAL_WRAP>(*a, ext, mask, init, ref, s);
-    case MODE_FINAL_CONT: return launch_reset_mode<MODE_FINAL_CONT>(*a, ext, mask, init, ref, s);
-    }
-    return hipErrorInvalidValue;
-}
-
-extern "C" hipError_t dpenv_dev_launch_get_state(const StepArgs* a, float* st, int32_t* ctr, hipStream_t s)
+hipError_t dev::launch_get_state(const StepArgs* a, float* st, int32_t* ctr, hipStream_t s)
 {
     hipLaunchKernelGGL(get_state_kernel, dim3((a->n + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, s, *a, st, ctr);
     return hipGetLastError();
 }
 
-extern "C" hipError_t dpenv_dev_launch_set_state(const StepArgs* a, const float* st, const int32_t* ctr, hipStream_t s)
+hipError_t dev::launch_set_state(const StepArgs* a, const float* st, const int32_t* ctr, hipStream_t s)
 {
     hipLaunchKernelGGL(set_state_kernel, dim3((a->n + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, s, *a, st, ctr);
     return hipGetLastError();
 }
 
-extern "C" hipError_t dpenv_dev_launch_thrust_map(const VesselDev* vd, const float* n_pct, const float* alpha, float* tau,
-                                                  int n, hipStream_t s)
+hipError_t dev::launch_thrust_map(const VesselDev* vd, const float* n_pct, const float* alpha, float* tau, int n, hipStream_t s)
 {
     hipLaunchKernelGGL(thrust_map_kernel, dim3((n + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, s, *vd, n_pct, alpha, tau, n);
     return hipGetLastError();
 }
 
-extern "C" int64_t dpenv_dev_gae_workspace_bytes(int n)
+int64_t dev::gae_workspace_bytes(int n)
 {
     return (((int64_t)n + 63) / 64) * 2 * (int64_t)sizeof(double);      // sized for the scalar form (one lane per column)
 }
 
-extern "C" hipError_t dpenv_dev_launch_gae(const float* rew, const float* val, const uint8_t* end, const float* boot,
-                                           const float* last_val, int T, int n, float gamma, float lam, float* adv,
-                                           float* ret, double* workspace, double* stats, hipStream_t s)
+hipError_t dev::launch_gae(const float* rew, const float* val, const uint8_t* end, const float* boot, const float* last_val, int T, int n,
+                           float gamma, float lam, float* adv, float* ret, double* workspace, double* stats, hipStream_t s)
 {
     // two columns per lane (8-byte rows) need n % 2 == 0 and 8-byte aligned bases (torch allocations are); anything else takes the
     // scalar form.  Measured at T = 400, n = 65 536 (tools/gae_bench.py; 21 B per env-step): two columns per lane with rows fetched
@@ -1299,7 +1225,7 @@ static int reduce_grid(int64_t count)
     return (int)g;
 }
 
-extern "C" hipError_t dpenv_dev_launch_sum(const float* x, int64_t count, const float* mean, float* out, hipStream_t s)
+hipError_t dev::launch_sum(const float* x, int64_t count, const float* mean, float* out, hipStream_t s)
 {
     double* parts = nullptr;
     hipError_t e = hipGetSymbolAddress((void**)&parts, HIP_SYMBOL(g_sum_partials));
@@ -1310,8 +1236,8 @@ extern "C" hipError_t dpenv_dev_launch_sum(const float* x, int64_t count, const 
     return hipGetLastError();
 }
 
-extern "C" hipError_t dpenv_dev_launch_adv_apply(float* x, int64_t count, const float* mean, const float* std,
-                                                 const double* stats, double total_count, hipStream_t s)
+hipError_t dev::launch_adv_apply(float* x, int64_t count, const float* mean, const float* std, const double* stats, double total_count,
+                                 hipStream_t s)
 {
     if (stats) hipLaunchKernelGGL(adv_apply_kernel<true>, dim3(reduce_grid(count)), dim3(SUMB), 0, s, x, count, mean, std, stats, total_count);
     else hipLaunchKernelGGL(adv_apply_kernel<false>, dim3(reduce_grid(count)), dim3(SUMB), 0, s, x, count, mean, std, stats, total_count);

@@ -1,6 +1,6 @@
 // dpenv_policy_ws.h - the closed-loop rollout with the work of every 64 envs split over two waves (an env wave and a network
-// wave per SIMD), for all three network arithmetics.  Included by dpenv_policy.hip (PREC_F16) and dpenv_policy_xws*.hip
-// (PREC_F32, PREC_F32_ACTOR: one translation unit each, they take minutes to compile).
+// wave per SIMD), for all three network arithmetics.  Included by dpenv_policy_ws.hip (PREC_F16) and dpenv_policy_xws*.hip
+// (PREC_F32, PREC_F32_ACTOR): one translation unit each, they take minutes to compile.
 #ifndef DPENV_POLICY_WS_H
 #define DPENV_POLICY_WS_H
 #include <type_traits>
@@ -69,7 +69,7 @@ __device__ __forceinline__ void ws_wait(int* p, int v)
 
 #define WS_EVAL(W_, B_, f0_, f1_) mlp_eval<KA>(W_, B_, pa.n_hidden, f0_, f1_, leak, outv)
 //  RND: the domain randomisation's hull re-draw compiled into the reset branch (instantiated for the shipped training configuration only -
-//  final variant, continuous angles, extended state, leaky-relu - see dpenv_ws_launch::pick and dpenv_env_dev.h redraw_vessel_cold).
+//  final variant, continuous angles, extended state, leaky-relu - see ws_general in dpenv_dev.h and dpenv_env_dev.h redraw_vessel_cold).
 //  SLOSS (round 6): the SHARED training form - the single class's thrust-loss coefficients from the kernel arguments (StepArgs.kl, LOSS_SHARED;
 //  zeros for a hull without a loss: the rows of the default kernels bit for bit) and the per-episode current re-draw: the thrust-loss preset and /
 //  or dpenv_set_current_randomisation on the shared hull, without per-env blocks; same configurations as RND.
@@ -93,104 +93,51 @@ __global__ __launch_bounds__(64 * GROUPS * ROLES) void policy_rollout_ws_integ_k
 
 }  // namespace dpenv
 
-// ---- host side: one launcher per arithmetic, instantiated by the translation unit that owns it -------------------------------
-// Two-wave launches exist for hidden activation leaky-relu / relu in every arithmetic; tanh only in PREC_F16 with four groups
-// (dpenv_set_policy_desc routes the others to the one-wave kernels).  -DDPENV_DEV_FAST (development builds only, never shipped)
-// instantiates the shipped configuration alone: final / continuous angles / extended state, width <= 80.
-namespace dpenv_ws_launch {
-using namespace dpenv;
+// ---- host side: one launcher per arithmetic, explicitly instantiated by the translation unit that owns it -------------------------
+// Which arithmetics get the critic wave (ws_roles, DPENV_WS_CRITIC_WAVE in dpenv_dev.h) in the 128-env geometry: measured (same call,
+// bit-identical rows, profiles/r04_critic_wave.txt; 32 768 / 8 192 envs): all exact 9.43 -> 7.85 / 9.24 -> 7.30 us per step, exact actor
+// 7.4-7.7 -> 7.3-7.45 / 7.23 -> 7.01; f16 5.20 -> 5.50 / 4.76 -> 5.03 with row staging (116 B of scratch at the 256 registers two waves on a
+// SIMD leave), 5.27 -> 5.33 / 4.79 -> 4.92 without it (no scratch): the f16 step is its chain already - so the two split arithmetics get the
+// critic wave, f16 keeps two roles.
+namespace dpenv {
 
-// which arithmetics get the critic wave (ROLES = 3) in the 128-env geometry: bit 0 f16, bit 1 all exact, bit 2 exact actor.  Measured
-// (same call, bit-identical rows, profiles/r04_critic_wave.txt; 32 768 / 8 192 envs): all exact 9.43 -> 7.85 / 9.24 -> 7.30 us per step, exact
-// actor 7.4-7.7 -> 7.3-7.45 / 7.23 -> 7.01; f16 5.20 -> 5.50 / 4.76 -> 5.03 with row staging (116 B of scratch at the 256 registers two waves
-// on a SIMD leave), 5.27 -> 5.33 / 4.79 -> 4.92 without it (no scratch): the f16 step is its chain already - so the two split arithmetics
-// get the critic wave, f16 keeps two roles.
-// (DPENV_WS_CRITIC_WAVE: dpenv_dev.h, default 6)
-// ia != NULL: the integral action's kernel, instantiated for the final variant / continuous angles / extended state, leaky-relu, width <= 80
-template <int MODE, bool EXT, int KA, int PREC, int GROUPS, bool RND = false, bool SLOSS = false>
-static hipError_t go(const StepArgs& a, const PolicyArgs& pa, const IntegArgs* ia, hipStream_t s)
+template <int MODE, bool EXT, int KA, int PREC, int GROUPS, bool RND, bool SLOSS>
+static hipError_t ws_go(const StepArgs& a, const PolicyArgs& pa, const IntegArgs* ia, hipStream_t s)
 {
-    constexpr int ROLES = (GROUPS == 2 && ((DPENV_WS_CRITIC_WAVE >> PREC) & 1)) ? 3 : 2;
-    const dim3 grid((a.n + 64 * GROUPS - 1) / (64 * GROUPS));
+    constexpr int ROLES = ws_roles(PREC, GROUPS);
+    const dim3 grid((a.n + 64 * GROUPS - 1) / (64 * GROUPS)), block(64 * GROUPS * ROLES);
     const size_t lds = (size_t)ws_images(PREC) * pa.nent * 16 + (size_t)2 * pa.nblk * 32 * 4 +
                        (size_t)GROUPS * ((((PREC == PREC_F16 && ROLES == 2)) ? WS_GROUP_FLOATS : WS_GROUP_FLOATS_X) +
                                          (ROLES == 3 ? 64 * 9 : 0)) * 4;
-    if (ia) {
-        if constexpr (MODE == MODE_FINAL_CONT && EXT && KA == 5) {
-            hipError_t e = hipFuncSetAttribute((const void*)policy_rollout_ws_integ_kernel<MODE, EXT, KA, ROLES, PREC, GROUPS, RND, SLOSS>,
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            if (e != hipSuccess) return e;
-            hipLaunchKernelGGL((policy_rollout_ws_integ_kernel<MODE, EXT, KA, ROLES, PREC, GROUPS, RND, SLOSS>), grid, dim3(64 * GROUPS * ROLES), lds, s,
-                               a, pa, *ia);
-            return hipGetLastError();
-        } else {
-            return hipErrorInvalidValue;
-        }
-    }
-    hipError_t e = hipFuncSetAttribute((const void*)policy_rollout_ws_kernel<MODE, EXT, KA, ROLES, PREC, GROUPS, RND, SLOSS>,
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((policy_rollout_ws_kernel<MODE, EXT, KA, ROLES, PREC, GROUPS, RND, SLOSS>), grid, dim3(64 * GROUPS * ROLES), lds, s, a, pa);
-    return hipGetLastError();
-}
-
-// the randomisation's instantiation exists for the shipped training configuration (train.py:47-54: final, continuous angles, extended
-// state) with leaky-relu / relu networks; dpenv_policy_rollout refuses the others while the randomisation is on (dpenv.h)
-template <int MODE, bool EXT, int KA, int PREC, int GROUPS>
-static hipError_t pick(const StepArgs& a, const PolicyArgs& pa, const IntegArgs* ia, hipStream_t s)
-{
-    if (a.loss_on == LOSS_SHARED) {                       // the single class's coefficients as kernel arguments
-        if (a.env_tab) return hipErrorInvalidValue;
-        if constexpr (MODE == MODE_FINAL_CONT && EXT && KA < 16) return go<MODE, EXT, KA, PREC, GROUPS, false, true>(a, pa, ia, s);
-        else return hipErrorNotSupported;
-    }
-    if (a.rand_tab || a.loss_on != LOSS_NONE || a.cur_nom) {   // the general per-env form: hull / current re-draws, the table's thrust loss
-        if constexpr (MODE == MODE_FINAL_CONT && EXT && KA < 16) return go<MODE, EXT, KA, PREC, GROUPS, true>(a, pa, ia, s);
-        else return hipErrorNotSupported;
-    }
-    return go<MODE, EXT, KA, PREC, GROUPS, false>(a, pa, ia, s);
-}
-
-template <int MODE, bool EXT, int PREC>
-static hipError_t by_shape(const StepArgs& a, const PolicyArgs& pa, const IntegArgs* ia, hipStream_t s)
-{
-    const int ka = pa.ks + 16 * pa.act;
-    const bool two = pa.ws_groups == 2;
-#ifdef DPENV_DEV_FAST
-    if (ka != 5) return hipErrorInvalidValue;
-    return two ? pick<MODE, EXT, 5, PREC, 2>(a, pa, ia, s) : pick<MODE, EXT, 5, PREC, 4>(a, pa, ia, s);
-#else
-    switch (ka) {
-    case 5: return two ? pick<MODE, EXT, 5, PREC, 2>(a, pa, ia, s) : pick<MODE, EXT, 5, PREC, 4>(a, pa, ia, s);
-    case 6: return two ? pick<MODE, EXT, 6, PREC, 2>(a, pa, ia, s) : pick<MODE, EXT, 6, PREC, 4>(a, pa, ia, s);
-    }
-    if constexpr (PREC == PREC_F16) {
-        if (two) return hipErrorInvalidValue;
-        if (ka == 21) return pick<MODE, EXT, 21, PREC, 4>(a, pa, ia, s);
-        if (ka == 22) return pick<MODE, EXT, 22, PREC, 4>(a, pa, ia, s);
-    }
+    if (!ia) return launch_with_lds(policy_rollout_ws_kernel<MODE, EXT, KA, ROLES, PREC, GROUPS, RND, SLOSS>, grid, block, lds, s, a, pa);
+    if constexpr (ws_integ(MODE, EXT, KA))
+        return launch_with_lds(policy_rollout_ws_integ_kernel<MODE, EXT, KA, ROLES, PREC, GROUPS, RND, SLOSS>, grid, block, lds, s, a, pa, *ia);
     return hipErrorInvalidValue;
-#endif
 }
 
+// the set the ws_* predicates of dpenv_dev.h admit; dpenv_api.hip routes everything else to the one-wave kernels
 template <int PREC>
-static hipError_t launch(const StepArgs& a, const PolicyArgs& pa, const IntegArgs* ia, int mode, int ext, hipStream_t s)
+hipError_t dev::launch_policy_rollout_ws(const StepArgs* a, const PolicyArgs* pa, const IntegArgs* ia, int mode, int ext, hipStream_t s)
 {
-    if ((pa.ks != 5 && pa.ks != 6) || (pa.act != 0 && pa.act != 1) || (pa.ws_groups != 2 && pa.ws_groups != 4)) return hipErrorInvalidValue;
-#ifdef DPENV_DEV_FAST
-    if (mode != MODE_FINAL_CONT || !ext) return hipErrorInvalidValue;
-    return by_shape<MODE_FINAL_CONT, true, PREC>(a, pa, ia, s);
-#else
-    switch (mode) {
-    case MODE_FULL: return ext ? by_shape<MODE_FULL, true, PREC>(a, pa, ia, s) : by_shape<MODE_FULL, false, PREC>(a, pa, ia, s);
-    case MODE_SIMPLE: return ext ? by_shape<MODE_SIMPLE, true, PREC>(a, pa, ia, s) : by_shape<MODE_SIMPLE, false, PREC>(a, pa, ia, s);
-    case MODE_LIMITED: return ext ? by_shape<MODE_LIMITED, true, PREC>(a, pa, ia, s) : by_shape<MODE_LIMITED, false, PREC>(a, pa, ia, s);
-    case MODE_FINAL_WRAP: return ext ? by_shape<MODE_FINAL_WRAP, true, PREC>(a, pa, ia, s) : by_shape<MODE_FINAL_WRAP, false, PREC>(a, pa, ia, s);
-    case MODE_FINAL_CONT: return ext ? by_shape<MODE_FINAL_CONT, true, PREC>(a, pa, ia, s) : by_shape<MODE_FINAL_CONT, false, PREC>(a, pa, ia, s);
-    }
-    return hipErrorInvalidValue;
-#endif
+    if (pa->ws_groups != 2 && pa->ws_groups != 4) return hipErrorInvalidValue;
+    const bool sloss = a->loss_on == LOSS_SHARED;                    // the single class's coefficients as kernel arguments
+    if (sloss && a->env_tab) return hipErrorInvalidValue;
+    const bool rnd = !sloss && (a->rand_tab || a->loss_on != LOSS_NONE || a->cur_nom);   // hull / current re-draws, the table's thrust loss
+    return with_mode_ext_ka(mode, ext, *pa, [&](auto M, auto E, auto K) {
+        auto groups = [&](auto G) -> hipError_t {
+            if constexpr (ws_has(K, PREC, G)) {
+                if constexpr (ws_general(M, E, K)) {
+                    if (sloss) return ws_go<M, E, K, PREC, G, false, true>(*a, *pa, ia, s);
+                    if (rnd) return ws_go<M, E, K, PREC, G, true, false>(*a, *pa, ia, s);
+                }
+                if (!sloss && !rnd) return ws_go<M, E, K, PREC, G, false, false>(*a, *pa, ia, s);
+            }
+            return hipErrorInvalidValue;
+        };
+        return pa->ws_groups == 2 ? groups(Int<2>{}) : groups(Int<4>{});
+    });
 }
-}  // namespace dpenv_ws_launch
+
+}  // namespace dpenv
 
 #endif

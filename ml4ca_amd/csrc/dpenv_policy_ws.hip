@@ -12,13 +12,6 @@ using namespace dpenv;
 #include "dpenv_diag.inc"
 #endif
 
-extern "C" hipError_t dpenv_dev_launch_policy_rollout_ws(const dpenv::StepArgs* a, const dpenv::PolicyArgs* pa, int mode, int ext, hipStream_t s)
-{
-    return dpenv_ws_launch::launch<dpenv::PREC_F16>(*a, *pa, nullptr, mode, ext, s);
-}
-
-extern "C" hipError_t dpenv_dev_launch_policy_rollout_ws_integ(const dpenv::StepArgs* a, const dpenv::PolicyArgs* pa, const dpenv::IntegArgs* ia, int mode, int ext,
-                                                               hipStream_t s)
-{
-    return dpenv_ws_launch::launch<dpenv::PREC_F16>(*a, *pa, ia, mode, ext, s);
+namespace dpenv {
+template hipError_t dev::launch_policy_rollout_ws<PREC_F16>(const StepArgs*, const PolicyArgs*, const IntegArgs*, int, int, hipStream_t);
 }

@@ -85,114 +85,24 @@ using namespace dpenv;
 
 static size_t lds_bytes_x(const PolicyArgs& pa) { return (size_t)4 * pa.nent * 16 + (size_t)2 * pa.nblk * 32 * 4; }
 
-extern "C" hipError_t dpenv_dev_launch_policy_forward_x(const PolicyArgs* pa, int od, int adim, const float* obs, float* mu, float* v,
-                                                        int n, hipStream_t s)
+hipError_t dev::launch_policy_forward_x(const PolicyArgs* pa, int od, int adim, const float* obs, float* mu, float* v, int n, hipStream_t s)
 {
+    if (!pa->split) return hipErrorInvalidValue;
     const dim3 grid((n + PBLOCK - 1) / PBLOCK), block(PBLOCK);
+    return with_obs_act(od, adim, [&](auto OD, auto A) { return with_ka(*pa, [&](auto K) {
+        return launch_with_lds(policy_forward_x_kernel<OD, A, K>, grid, block, lds_bytes_x(*pa), s, *pa, obs, mu, v, n);
+    }); });
+}
+
+// the one-wave closed loop in the split arithmetics; with the integral action (ia) the set integ_one_wave admits
+hipError_t dev::launch_policy_rollout_x(const StepArgs* a, const PolicyArgs* pa, const IntegArgs* ia, int mode, int ext, hipStream_t s)
+{
+    if (!pa->split) return hipErrorInvalidValue;
+    const dim3 grid((a->n + PBLOCK - 1) / PBLOCK), block(PBLOCK);
     const size_t lds = lds_bytes_x(*pa);
-#define FWD_K(OD_, A_, KS_)                                                                                              \
-    do {                                                                                                                 \
-        hipError_t e = hipFuncSetAttribute((const void*)policy_forward_x_kernel<OD_, A_, KS_>,                            \
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                        \
-        if (e != hipSuccess) return e;                                                                                   \
-        hipLaunchKernelGGL((policy_forward_x_kernel<OD_, A_, KS_>), grid, block, lds, s, *pa, obs, mu, v, n);             \
-        return hipGetLastError();                                                                                        \
-    } while (0)
-#define FWD(OD_, A_)                                                                                                     \
-    do {                                                                                                                 \
-        if (ka == 5) FWD_K(OD_, A_, 5);                                                                                  \
-        if (ka == 6) FWD_K(OD_, A_, 6);                                                                                  \
-        if (ka == 21) FWD_K(OD_, A_, 21);                                                                                \
-        FWD_K(OD_, A_, 22);                                                                                              \
-    } while (0)
-    if ((pa->ks != 5 && pa->ks != 6) || (pa->act != 0 && pa->act != 1) || !pa->split) return hipErrorInvalidValue;
-    const int ka = pa->ks + 16 * pa->act;
-#ifdef DPENV_DEV_FAST
-    if (od == 9 && adim == 7 && ka == 5) FWD_K(9, 7, 5);
-#else
-    if (od == 9 && adim == 7) FWD(9, 7);
-    if (od == 9 && adim == 5) FWD(9, 5);
-    if (od == 9 && adim == 6) FWD(9, 6);
-    if (od == 6 && adim == 7) FWD(6, 7);
-    if (od == 6 && adim == 5) FWD(6, 5);
-    if (od == 6 && adim == 6) FWD(6, 6);
-    if (od == 6 && adim == 3) FWD(6, 3);
-#endif
-#undef FWD_K
-#undef FWD
-    return hipErrorInvalidValue;
-}
-
-template <int MODE, bool EXT, int KA>
-static hipError_t launch_x_one(const StepArgs& a, const PolicyArgs& pa, hipStream_t s)
-{
-    const dim3 grid((a.n + PBLOCK - 1) / PBLOCK), block(PBLOCK);
-    const size_t lds = lds_bytes_x(pa);
-    hipError_t e = hipFuncSetAttribute((const void*)policy_rollout_x_kernel<MODE, EXT, KA>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((policy_rollout_x_kernel<MODE, EXT, KA>), grid, block, lds, s, a, pa);
-    return hipGetLastError();
-}
-
-template <int MODE>
-static hipError_t launch_x_mode(const StepArgs& a, const PolicyArgs& pa, bool ext, hipStream_t s)
-{
-    if ((pa.ks != 5 && pa.ks != 6) || (pa.act != 0 && pa.act != 1) || !pa.split) return hipErrorInvalidValue;
-#ifdef DPENV_DEV_FAST
-    if (pa.ks != 5 || pa.act != 0 || !ext) return hipErrorInvalidValue;
-    return launch_x_one<MODE, true, 5>(a, pa, s);
-#else
-    switch (pa.ks + 16 * pa.act) {
-    case 5: return ext ? launch_x_one<MODE, true, 5>(a, pa, s) : launch_x_one<MODE, false, 5>(a, pa, s);
-    case 6: return ext ? launch_x_one<MODE, true, 6>(a, pa, s) : launch_x_one<MODE, false, 6>(a, pa, s);
-    case 21: return ext ? launch_x_one<MODE, true, 21>(a, pa, s) : launch_x_one<MODE, false, 21>(a, pa, s);
-    default: return ext ? launch_x_one<MODE, true, 22>(a, pa, s) : launch_x_one<MODE, false, 22>(a, pa, s);
-    }
-#endif
-}
-
-extern "C" hipError_t dpenv_dev_launch_policy_rollout_x(const StepArgs* a, const PolicyArgs* pa, int mode, int ext, hipStream_t s)
-{
-    if (pa->ws) return pa->critic_f16 ? dpenv_dev_launch_policy_rollout_xws_f32_actor(a, pa, mode, ext, s)
-                                      : dpenv_dev_launch_policy_rollout_xws_f32(a, pa, mode, ext, s);
-#ifdef DPENV_DEV_FAST
-    return mode == MODE_FINAL_CONT ? launch_x_mode<MODE_FINAL_CONT>(*a, *pa, ext, s) : hipErrorInvalidValue;
-#else
-    switch (mode) {
-    case MODE_FULL: return launch_x_mode<MODE_FULL>(*a, *pa, ext, s);
-    case MODE_SIMPLE: return launch_x_mode<MODE_SIMPLE>(*a, *pa, ext, s);
-    case MODE_LIMITED: return launch_x_mode<MODE_LIMITED>(*a, *pa, ext, s);
-    case MODE_FINAL_WRAP: return launch_x_mode<MODE_FINAL_WRAP>(*a, *pa, ext, s);
-    case MODE_FINAL_CONT: return launch_x_mode<MODE_FINAL_CONT>(*a, *pa, ext, s);
-    }
-    return hipErrorInvalidValue;
-#endif
-}
-
-// the closed loop with the integral action in the split arithmetics (dpenv_policy.hip: dpenv_dev_launch_policy_rollout_integ has the supported set)
-template <int MODE>
-static hipError_t launch_x_integ_one(const StepArgs& a, const PolicyArgs& pa, const IntegArgs& ia, hipStream_t s)
-{
-    const dim3 grid((a.n + PBLOCK - 1) / PBLOCK), block(PBLOCK);
-    const size_t lds = lds_bytes_x(pa);
-    hipError_t e = hipFuncSetAttribute((const void*)policy_rollout_x_integ_kernel<MODE, true, 5>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((policy_rollout_x_integ_kernel<MODE, true, 5>), grid, block, lds, s, a, pa, ia);
-    return hipGetLastError();
-}
-
-extern "C" hipError_t dpenv_dev_launch_policy_rollout_x_integ(const StepArgs* a, const PolicyArgs* pa, const IntegArgs* ia, int mode, int ext,
-                                                              hipStream_t s)
-{
-    if (!ext || pa->ks != 5 || pa->act != 0 || !pa->split) return hipErrorInvalidValue;
-    if (pa->ws) return pa->critic_f16 ? dpenv_dev_launch_policy_rollout_xws_f32_actor_integ(a, pa, ia, mode, ext, s)
-                                      : dpenv_dev_launch_policy_rollout_xws_f32_integ(a, pa, ia, mode, ext, s);
-    switch (mode) {
-    case MODE_FINAL_CONT: return launch_x_integ_one<MODE_FINAL_CONT>(*a, *pa, *ia, s);
-#ifndef DPENV_DEV_FAST
-    case MODE_LIMITED: return launch_x_integ_one<MODE_LIMITED>(*a, *pa, *ia, s);
-    case MODE_FULL: return launch_x_integ_one<MODE_FULL>(*a, *pa, *ia, s);
-#endif
-    }
-    return hipErrorInvalidValue;
+    return with_mode_ext_ka(mode, ext, *pa, [&](auto M, auto E, auto K) -> hipError_t {
+        if (!ia) return launch_with_lds(policy_rollout_x_kernel<M, E, K>, grid, block, lds, s, *a, *pa);
+        if constexpr (integ_one_wave(M, E, K)) return launch_with_lds(policy_rollout_x_integ_kernel<M, E, K>, grid, block, lds, s, *a, *pa, *ia);
+        return hipErrorInvalidValue;
+    });
 }

@@ -3,13 +3,6 @@
 // Reference: rollout loop spinup/algos/tf1/ppo/ppo.py:289-322, fp32 networks core.py:29-33,80-107.
 #include "dpenv_policy_ws.h"
 
-extern "C" hipError_t dpenv_dev_launch_policy_rollout_xws_f32_actor(const dpenv::StepArgs* a, const dpenv::PolicyArgs* pa, int mode, int ext, hipStream_t s)
-{
-    return dpenv_ws_launch::launch<dpenv::PREC_F32_ACTOR>(*a, *pa, nullptr, mode, ext, s);
-}
-
-extern "C" hipError_t dpenv_dev_launch_policy_rollout_xws_f32_actor_integ(const dpenv::StepArgs* a, const dpenv::PolicyArgs* pa, const dpenv::IntegArgs* ia, int mode, int ext,
-                                                                          hipStream_t s)
-{
-    return dpenv_ws_launch::launch<dpenv::PREC_F32_ACTOR>(*a, *pa, ia, mode, ext, s);
+namespace dpenv {
+template hipError_t dev::launch_policy_rollout_ws<PREC_F32_ACTOR>(const StepArgs*, const PolicyArgs*, const IntegArgs*, int, int, hipStream_t);
 }

@@ -26,6 +26,11 @@ def test_library_exports_every_declared_symbol():
     assert len(declared) >= 20
     for name in declared:
         assert hasattr(lib, name), 'libdpenv.so does not export %s' % name
+    # and nothing else: the internal launchers between the translation units stay out of the dynamic symbol table
+    nm = subprocess.run(['nm', '-D', '--defined-only', _lib.LIB_PATH], check=True, capture_output=True, text=True).stdout
+    exported = sorted(f[2] for f in (ln.split() for ln in nm.splitlines()) if len(f) == 3 and f[1] == 'T' and f[2].startswith('dpenv_'))
+    assert exported == declared, 'exported but not declared: %s; declared but not exported: %s' % (
+        sorted(set(exported) - set(declared)), sorted(set(declared) - set(exported)))
     assert sorted(_lib.SYMBOLS) == declared, 'binding table and header drifted apart'
     assert lib.dpenv_abi_version() == _lib.ABI_VERSION
 

@@ -79,6 +79,10 @@ class IntegralAction(C.Structure):
                 ('dwell_s', C.c_float), ('step_s', C.c_float)]
 
 
+class ReferenceFilter(C.Structure):
+    _fields_ = [('struct_size', C.c_uint32), ('omega', C.c_float * 3), ('zeta', C.c_float * 3)]
+
+
 # every symbol include/dpenv.h declares: name -> (restype, argtypes)
 _VP, _I32, _I64, _F = C.c_void_p, C.c_int32, C.c_int64, C.c_float
 SYMBOLS = {
@@ -132,6 +136,11 @@ SYMBOLS = {
     'dpenv_get_integral_state': (C.c_int, [_VP, _VP, _VP, _VP]),
     'dpenv_set_integral_state': (C.c_int, [_VP, _VP, _VP, _VP]),
     'dpenv_policy_rollout_integral': (C.c_int, [_VP, C.POINTER(PolicyRolloutIO), _VP, _VP]),
+    'dpenv_set_reference_filter': (C.c_int, [_VP, C.POINTER(ReferenceFilter), _VP]),
+    'dpenv_get_reference_filter_state': (C.c_int, [_VP, _VP, _VP, _VP]),
+    'dpenv_set_reference_filter_state': (C.c_int, [_VP, _VP, _VP, _VP]),
+    'dpenv_reference_filter_coeffs': (C.c_int, [C.POINTER(ReferenceFilter), _F, C.POINTER(C.c_float * 9 * 3), C.POINTER(C.c_float * 3 * 3)]),
+    'dpenv_policy_rollout_deployed': (C.c_int, [_VP, C.POINTER(PolicyRolloutIO), _VP, _VP, _VP]),
 }
 
 _lib = None

@@ -75,6 +75,8 @@ struct dpenv_s {
     bool lag_valid;         // the state block was last written by a closed-loop launch (PolicyArgs.use_lag)
     bool integ_on;          // dpenv_set_integral_action: the closed loop runs the *_integ kernels with `integ`
     IntegArgs integ;        // its parameters and per-env state (float4 [n]: I | count), allocated by the first dpenv_set_integral_action
+    bool reff_on;           // dpenv_set_reference_filter: the closed loop runs the *_reff kernels with `reff`
+    FilterArgs reff;        // its f32 coefficients and per-env state (float4 [3][n]: pos | vel | acc | target), allocated on first use
     int device;
     std::string err;
 };
@@ -338,6 +340,8 @@ extern "C" int dpenv_create(const dpenv_config* cfg, const float* vessel_params,
     h->lag_valid = false;
     h->integ_on = false;
     std::memset(&h->integ, 0, sizeof h->integ);
+    h->reff_on = false;
+    std::memset(&h->reff, 0, sizeof h->reff);
     std::memset(&h->pol, 0, sizeof h->pol);
 
     VesselDev tab[MAX_CLASSES];
@@ -482,6 +486,7 @@ extern "C" int dpenv_destroy(dpenv_handle h)
     if (h->pol_buf) (void)hipFree(h->pol_buf);
     if (h->pol_raw) (void)hipFree(h->pol_raw);
     if (h->integ.state) (void)hipFree(h->integ.state);
+    if (h->reff.state) (void)hipFree(h->reff.state);
     for (int k = 0; k < 2; ++k) if (h->pol_read[k]) (void)hipEventDestroy(h->pol_read[k]);
     if (h->loss_ev) (void)hipEventDestroy(h->loss_ev);
     if (h->loss_host) (void)hipHostFree(h->loss_host);
@@ -750,6 +755,7 @@ extern "C" int dpenv_reset(dpenv_handle h, const uint8_t* mask, const float* ini
     a.obs = obs_out;
     HIP_TRY(h, dev::launch_reset(&a, h->mode, h->cfg.extended_state, mask, init, ref, (hipStream_t)s));
     if (h->integ_on) HIP_TRY(h, dev::launch_integ_clear(h->integ.state, mask, h->cfg.n_envs, (hipStream_t)s));   // new episodes start with I = 0
+    if (h->reff_on) HIP_TRY(h, dev::launch_reff_rest(a.RF, h->reff.state, mask, h->cfg.n_envs, (hipStream_t)s));   // ... the filter at rest
     // the reset kernel writes the lagged thrust columns (S3) of the envs it re-draws: a full reset makes them valid everywhere, a
     // masked one leaves the validity of the other envs' columns as it was (it used to drop the lag of every env)
     if (!mask) h->lag_valid = true;
@@ -759,6 +765,9 @@ extern "C" int dpenv_reset(dpenv_handle h, const uint8_t* mask, const float* ini
 #define INTEG_OPEN_LOOP_MSG                                                                                                         \
     "%s: the integral action is on (dpenv_set_integral_action) and this launch's observations would lack I: run the closed loop "    \
     "(dpenv_policy_rollout), compose the step with the law on the host, or turn the action off"
+#define REFF_OPEN_LOOP_MSG                                                                                                          \
+    "%s: the reference filter is on (dpenv_set_reference_filter) and would not see this launch: run the closed loop "               \
+    "(dpenv_policy_rollout), compose the step with the filter on the host (its position as new_ref), or turn the filter off"
 
 extern "C" int dpenv_step_ex(dpenv_handle h, const dpenv_step_io* io, dpenv_stream s)
 {
@@ -766,6 +775,7 @@ extern "C" int dpenv_step_ex(dpenv_handle h, const dpenv_step_io* io, dpenv_stre
     DeviceGuard dev_guard(h->device);
     if (!io || io->struct_size != sizeof(dpenv_step_io)) return fail(h, DPENV_EINVAL, "dpenv_step_io ABI mismatch");
     if (h->integ_on) return fail(h, DPENV_EINVAL, INTEG_OPEN_LOOP_MSG, "dpenv_step");
+    if (h->reff_on) return fail(h, DPENV_EINVAL, REFF_OPEN_LOOP_MSG, "dpenv_step");
     if (!io->action || !io->obs || !io->reward || !io->done)
         return fail(h, DPENV_EINVAL, "action, obs, reward and done buffers are required");
     if (classes_missing(h))
@@ -808,6 +818,7 @@ extern "C" int dpenv_rollout(dpenv_handle h, const dpenv_rollout_io* io, dpenv_s
     DeviceGuard dev_guard(h->device);
     if (!io || io->struct_size != sizeof(dpenv_rollout_io)) return fail(h, DPENV_EINVAL, "dpenv_rollout_io ABI mismatch");
     if (h->integ_on) return fail(h, DPENV_EINVAL, INTEG_OPEN_LOOP_MSG, "dpenv_rollout");
+    if (h->reff_on) return fail(h, DPENV_EINVAL, REFF_OPEN_LOOP_MSG, "dpenv_rollout");
     if (io->T <= 0 || !io->actions || !io->obs || !io->reward || !io->done)
         return fail(h, DPENV_EINVAL, "T > 0 and action, obs, reward, done blocks are required");
     if (io->n_switch < 0 || io->n_switch > DPENV_MAX_SWITCH || (io->n_switch > 0 && !io->refs))
@@ -1116,29 +1127,32 @@ extern "C" int dpenv_debug_pk_probe(dpenv_handle h, void* out, void* sink, int b
 // Which closed-loop kernel runs: the one place that decides.  The two-wave form runs where its launcher has the instantiation (the ws_*
 // predicates of dpenv_dev.h, the same ones it instantiates by); everything else runs the one-wave kernels - the same rows bit for bit, the
 // hull / current re-draw and the table's thrust loss a run-time switch there, which know the thrust loss through the table alone.
-static int launch_closed_loop(dpenv_handle h, StepArgs& a, PolicyArgs& pa, const IntegArgs* ia, hipStream_t s)
+static int launch_closed_loop(dpenv_handle h, StepArgs& a, PolicyArgs& pa, const IntegArgs* ia, const FilterArgs* fa, hipStream_t s)
 {
     const int mode = h->mode, ext = h->cfg.extended_state, ka = pa.ks + 16 * pa.act;
     if (ia && !integ_one_wave(mode, ext, ka))
         return fail(h, DPENV_EINVAL, "the integral action runs with the final variant (continuous angles), limited or full, extended_state, and a "
                                      "leaky-relu / relu network of hidden width <= 80");
+    if (fa && !reff_one_wave(mode, ext, ka))
+        return fail(h, DPENV_EINVAL, "the reference filter runs with the final variant (continuous angles), limited or full, extended_state, and a "
+                                     "leaky-relu / relu network of hidden width <= 80");
     const bool general = a.rand_tab || a.loss_on != LOSS_NONE || a.cur_nom;       // hull / current re-draws, a thrust loss
-    if ((general && !ws_general(mode, ext, ka)) || (ia && !ws_integ(mode, ext, ka))) pa.ws = 0;
+    if ((general && !ws_general(mode, ext, ka)) || (ia && !ws_integ(mode, ext, ka)) || (fa && !ws_reff(mode, ext, ka))) pa.ws = 0;
     hipError_t e;
     if (!pa.ws) {
         bind_shared_loss_as_table(h, a);
-        e = pa.split ? dev::launch_policy_rollout_x(&a, &pa, ia, mode, ext, s) : dev::launch_policy_rollout(&a, &pa, ia, mode, ext, s);
+        e = pa.split ? dev::launch_policy_rollout_x(&a, &pa, ia, fa, mode, ext, s) : dev::launch_policy_rollout(&a, &pa, ia, fa, mode, ext, s);
     } else if (!pa.split) {
-        e = dev::launch_policy_rollout_ws<PREC_F16>(&a, &pa, ia, mode, ext, s);
+        e = dev::launch_policy_rollout_ws<PREC_F16>(&a, &pa, ia, fa, mode, ext, s);
     } else {
-        e = pa.critic_f16 ? dev::launch_policy_rollout_ws<PREC_F32_ACTOR>(&a, &pa, ia, mode, ext, s)
-                          : dev::launch_policy_rollout_ws<PREC_F32>(&a, &pa, ia, mode, ext, s);
+        e = pa.critic_f16 ? dev::launch_policy_rollout_ws<PREC_F32_ACTOR>(&a, &pa, ia, fa, mode, ext, s)
+                          : dev::launch_policy_rollout_ws<PREC_F32>(&a, &pa, ia, fa, mode, ext, s);
     }
     if (e != hipSuccess) return fail(h, DPENV_EHIP, "closed-loop launch failed: %s", hipGetErrorString(e));
     return DPENV_OK;
 }
 
-static int policy_rollout_impl(dpenv_handle h, const dpenv_policy_rollout_io* io, float* integ_out, dpenv_stream s)
+static int policy_rollout_impl(dpenv_handle h, const dpenv_policy_rollout_io* io, float* integ_out, float* ref_out, dpenv_stream s)
 {
     DeviceGuard dev_guard(h->device);
     if (!h->has_policy) return fail(h, DPENV_EINVAL, "dpenv_set_policy has not been called");
@@ -1172,7 +1186,9 @@ static int policy_rollout_impl(dpenv_handle h, const dpenv_policy_rollout_io* io
 #endif
     IntegArgs ia = h->integ;
     ia.out = integ_out;
-    const int rc = launch_closed_loop(h, a, pa, h->integ_on ? &ia : nullptr, (hipStream_t)s);
+    FilterArgs fa = h->reff;
+    fa.out = ref_out;
+    const int rc = launch_closed_loop(h, a, pa, h->integ_on ? &ia : nullptr, h->reff_on ? &fa : nullptr, (hipStream_t)s);
     if (rc != DPENV_OK) return rc;
     h->lag_valid = true;
     return mark_policy_read(h, s);
@@ -1181,14 +1197,150 @@ static int policy_rollout_impl(dpenv_handle h, const dpenv_policy_rollout_io* io
 extern "C" int dpenv_policy_rollout(dpenv_handle h, const dpenv_policy_rollout_io* io, dpenv_stream s)
 {
     if (!h) return DPENV_EINVAL;
-    return policy_rollout_impl(h, io, nullptr, s);
+    return policy_rollout_impl(h, io, nullptr, nullptr, s);
 }
 
 extern "C" int dpenv_policy_rollout_integral(dpenv_handle h, const dpenv_policy_rollout_io* io, float* integ_out, dpenv_stream s)
 {
     if (!h) return DPENV_EINVAL;
     if (!h->integ_on) return fail(h, DPENV_EINVAL, "dpenv_policy_rollout_integral: the integral action is off (dpenv_set_integral_action)");
-    return policy_rollout_impl(h, io, integ_out, s);
+    return policy_rollout_impl(h, io, integ_out, nullptr, s);
+}
+
+extern "C" int dpenv_policy_rollout_deployed(dpenv_handle h, const dpenv_policy_rollout_io* io, float* ref_out, float* integ_out, dpenv_stream s)
+{
+    if (!h) return DPENV_EINVAL;
+    if (!h->reff_on) return fail(h, DPENV_EINVAL, "dpenv_policy_rollout_deployed: the reference filter is off (dpenv_set_reference_filter)");
+    if (integ_out && !h->integ_on)
+        return fail(h, DPENV_EINVAL, "dpenv_policy_rollout_deployed: integ_out needs the integral action on (dpenv_set_integral_action)");
+    return policy_rollout_impl(h, io, integ_out, ref_out, s);
+}
+
+// ---- the setpoint reference filter (dpenv.h) -------------------------------------------------------------------------------------
+// exp(M) of the 4x4 augmented system M = [[A, B], [0, 0]] dt of one axis, in f64: scaling and squaring of the degree-18 Taylor polynomial
+// (||M / 2^sq||_1 <= 1/2: truncation below 1e-22).  deploy.reference_filter_coeffs_f64 is the same recipe in NumPy.
+static void reff_coeffs_f64(double w, double z, double dt, double phi[9], double gam[3])
+{
+    const double c = 2.0 * z + 1.0;
+    double M[4][4] = {{0.0, 1.0, 0.0, 0.0}, {0.0, 0.0, 1.0, 0.0}, {-w * w * w, -c * w * w, -c * w, w * w * w}, {0.0, 0.0, 0.0, 0.0}};
+    double norm = 0.0;
+    for (int col = 0; col < 4; ++col) {
+        double sum = 0.0;
+        for (int r = 0; r < 4; ++r) { M[r][col] *= dt; sum += std::fabs(M[r][col]); }
+        norm = std::fmax(norm, sum);
+    }
+    int sq = 0;
+    while (norm > 0.5 && sq < 200) { norm *= 0.5; ++sq; }
+    const double scale = std::ldexp(1.0, -sq);
+    for (int r = 0; r < 4; ++r) for (int col = 0; col < 4; ++col) M[r][col] *= scale;
+    double E[4][4], T[4][4];                                     // E = sum_k M^k / k!, T = the running term
+    for (int r = 0; r < 4; ++r) for (int col = 0; col < 4; ++col) E[r][col] = T[r][col] = (r == col) ? 1.0 : 0.0;
+    for (int k = 1; k <= 18; ++k) {
+        double U[4][4];
+        for (int r = 0; r < 4; ++r) for (int col = 0; col < 4; ++col) {
+            double acc = 0.0;
+            for (int q = 0; q < 4; ++q) acc += T[r][q] * M[q][col];
+            U[r][col] = acc / (double)k;
+        }
+        for (int r = 0; r < 4; ++r) for (int col = 0; col < 4; ++col) { T[r][col] = U[r][col]; E[r][col] += U[r][col]; }
+    }
+    for (int k = 0; k < sq; ++k) {
+        double U[4][4];
+        for (int r = 0; r < 4; ++r) for (int col = 0; col < 4; ++col) {
+            double acc = 0.0;
+            for (int q = 0; q < 4; ++q) acc += E[r][q] * E[q][col];
+            U[r][col] = acc;
+        }
+        std::memcpy(E, U, sizeof E);
+    }
+    for (int r = 0; r < 3; ++r) {
+        for (int col = 0; col < 3; ++col) phi[3 * r + col] = E[r][col];
+        gam[r] = E[r][3];
+    }
+}
+
+static const char* reff_check(const dpenv_reference_filter* rf)
+{
+    if (rf->struct_size != sizeof(dpenv_reference_filter)) return "dpenv_reference_filter ABI mismatch";
+    for (int j = 0; j < 3; ++j) {
+        if (!std::isfinite(rf->omega[j]) || !(rf->omega[j] > 0.0f)) return "reference filter: omega must be finite and > 0 on every axis";
+        if (!std::isfinite(rf->zeta[j]) || !(rf->zeta[j] > 0.0f)) return "reference filter: zeta must be finite and > 0 on every axis";
+    }
+    return nullptr;
+}
+
+// the f32 coefficients, or an error message
+static const char* reff_coeffs_f32(const dpenv_reference_filter* rf, float dt, float phi[3][9], float gam[3][3])
+{
+    if (const char* why = reff_check(rf)) return why;
+    if (!std::isfinite(dt) || !(dt > 0.0f)) return "reference filter: dt must be finite and > 0";
+    for (int j = 0; j < 3; ++j) {
+        double p[9], g[3];
+        reff_coeffs_f64((double)rf->omega[j], (double)rf->zeta[j], (double)dt, p, g);
+        for (int k = 0; k < 9; ++k) phi[j][k] = (float)p[k];
+        for (int k = 0; k < 3; ++k) gam[j][k] = (float)g[k];
+        for (int k = 0; k < 9; ++k) if (!std::isfinite(phi[j][k])) return "reference filter: omega * dt too large (the coefficients overflow f32)";
+        for (int k = 0; k < 3; ++k) if (!std::isfinite(gam[j][k])) return "reference filter: omega * dt too large (the coefficients overflow f32)";
+    }
+    return nullptr;
+}
+
+extern "C" int dpenv_reference_filter_coeffs(const dpenv_reference_filter* rf, float dt, float phi_out[3][9], float gam_out[3][3])
+{
+    if (!rf || !phi_out || !gam_out) return fail(nullptr, DPENV_EINVAL, "dpenv_reference_filter_coeffs: NULL argument");
+    float phi[3][9], gam[3][3];
+    if (const char* why = reff_coeffs_f32(rf, dt, phi, gam)) return fail(nullptr, DPENV_EINVAL, "%s", why);
+    std::memcpy(phi_out, phi, sizeof phi);
+    std::memcpy(gam_out, gam, sizeof gam);
+    return DPENV_OK;
+}
+
+extern "C" int dpenv_set_reference_filter(dpenv_handle h, const dpenv_reference_filter* rf, dpenv_stream s)
+{
+    if (!h) return DPENV_EINVAL;
+    if (!rf) {
+        h->reff_on = false;
+        return DPENV_OK;
+    }
+    if (!((h->mode == MODE_FINAL_CONT || h->mode == MODE_LIMITED || h->mode == MODE_FULL) && h->cfg.extended_state))
+        return fail(h, DPENV_EINVAL, "the reference filter runs with the final variant (continuous angles), limited or full, extended_state, and a "
+                                     "leaky-relu / relu network of hidden width <= 80");
+    FilterArgs& f = h->reff;
+    float phi[3][9], gam[3][3];
+    if (const char* why = reff_coeffs_f32(rf, h->cfg.substep_dt * (float)h->cfg.n_substeps, phi, gam)) return fail(h, DPENV_EINVAL, "%s", why);
+    DeviceGuard dev_guard(h->device);
+    if (!f.state) {
+        void* p = nullptr;
+        if (hipMalloc(&p, sizeof(float4) * 3 * (size_t)h->cfg.n_envs) != hipSuccess)
+            return fail(h, DPENV_ENOMEM, "hipMalloc of the reference filter state failed");
+        f.state = (float4*)p;
+    }
+    std::memcpy(f.phi, phi, sizeof phi);
+    std::memcpy(f.gam, gam, sizeof gam);
+    f.out = nullptr;
+    HIP_TRY(h, dev::launch_reff_rest(h->args.RF, f.state, nullptr, h->cfg.n_envs, (hipStream_t)s));
+    h->reff_on = true;
+    return DPENV_OK;
+}
+
+extern "C" int dpenv_get_reference_filter_state(dpenv_handle h, float* x_out, float* r_out, dpenv_stream s)
+{
+    if (!h) return DPENV_EINVAL;
+    if (!h->reff_on) return fail(h, DPENV_EINVAL, "dpenv_get_reference_filter_state: the reference filter is off");
+    if (!x_out && !r_out) return fail(h, DPENV_EINVAL, "dpenv_get_reference_filter_state: NULL argument");
+    DeviceGuard dev_guard(h->device);
+    HIP_TRY(h, dev::launch_reff_state_io(h->reff.state, x_out, r_out, h->cfg.n_envs, 0, (hipStream_t)s));
+    return DPENV_OK;
+}
+
+extern "C" int dpenv_set_reference_filter_state(dpenv_handle h, const float* x_in, const float* r_in, dpenv_stream s)
+{
+    if (!h) return DPENV_EINVAL;
+    if (!h->reff_on) return fail(h, DPENV_EINVAL, "dpenv_set_reference_filter_state: the reference filter is off");
+    if (!x_in && !r_in) return fail(h, DPENV_EINVAL, "dpenv_set_reference_filter_state: NULL argument");
+    DeviceGuard dev_guard(h->device);
+    HIP_TRY(h, dev::launch_reff_state_io(h->reff.state, (float*)x_in, (float*)r_in, h->cfg.n_envs, 1, (hipStream_t)s));
+    return DPENV_OK;
 }
 
 // ---- the deployed node's integral action (dpenv.h) -------------------------------------------------------------------------------

@@ -200,6 +200,15 @@ struct IntegArgs {
     int32_t dwell;            // D: the smallest count with D * dt > dwell_s
 };
 
+// the setpoint reference filter of the deployed controller in the closed loop (dpenv_set_reference_filter; include/dpenv.h has the law): a
+// separate argument of the *_reff kernels only, like IntegArgs
+struct FilterArgs {
+    float4* state;            // [3][n]: axis j (N, E, psi) of env i at state[j * n + i] = (pos, vel, acc, target)
+    float* out;               // [T][n][3] the eta_d obs[t] was formed against, or NULL
+    float phi[3][9];          // Phi_j row-major, f32 from the f64 zero-order hold (dpenv_reference_filter_coeffs)
+    float gam[3][3];          // Gamma_j
+};
+
 // device-side weight packing (pack_policy_kernel): one dense network, DEVICE pointers
 struct PackNet {
     const float* W[5];        // W[l][in][out] row-major (tf.layers.dense kernel layout)
@@ -327,6 +336,10 @@ constexpr bool ws_has(int ka, int prec, int groups) { return ka < 16 || (prec ==
 constexpr bool ws_general(int mode, bool ext, int ka) { return mode == MODE_FINAL_CONT && ext && ka < 16; }
 // its integral action: the final variant / continuous angles, extended state, leaky-relu / relu of width <= 80
 constexpr bool ws_integ(int mode, bool ext, int ka) { return mode == MODE_FINAL_CONT && ext && ka == 5; }
+// the setpoint reference filter (FilterArgs): the integral action's set in both families, instantiated for the filter alone and for the
+// filter with the integral action
+constexpr bool reff_one_wave(int mode, bool ext, int ka) { return integ_one_wave(mode, ext, ka); }
+constexpr bool ws_reff(int mode, bool ext, int ka) { return ws_integ(mode, ext, ka); }
 // waves per 64 envs of the two-wave form: an env and a network wave, plus a critic wave where DPENV_WS_CRITIC_WAVE gives one
 constexpr int ws_roles(int prec, int groups) { return (groups == 2 && ((DPENV_WS_CRITIC_WAVE >> prec) & 1)) ? 3 : 2; }
 
@@ -353,19 +366,26 @@ hipError_t launch_sum(const float* x, int64_t count, const float* mean, float* o
 hipError_t launch_adv_apply(float* x, int64_t count, const float* mean, const float* std, const double* stats, double total_count,
                             hipStream_t s);
 // dpenv_policy.hip (f16) and dpenv_policy_x.hip (split arithmetics): weight packing, standalone forward, one-wave closed loop;
-// ia != NULL: the closed loop with the integral action
+// ia != NULL: the closed loop with the integral action; fa != NULL: with the reference filter (and ia, if not NULL)
 hipError_t launch_pack_policy(const PackNet* pi, const PackNet* v, const float* log_std, int adim, int ks, int nent, int nblk, int split,
                               void* frags, float* bias, float* consts, hipStream_t s);
 hipError_t launch_policy_forward(const PolicyArgs* pa, int od, int adim, const float* obs, float* mu, float* v, int n, hipStream_t s);
 hipError_t launch_policy_forward_x(const PolicyArgs* pa, int od, int adim, const float* obs, float* mu, float* v, int n, hipStream_t s);
-hipError_t launch_policy_rollout(const StepArgs* a, const PolicyArgs* pa, const IntegArgs* ia, int mode, int ext, hipStream_t s);
-hipError_t launch_policy_rollout_x(const StepArgs* a, const PolicyArgs* pa, const IntegArgs* ia, int mode, int ext, hipStream_t s);
+hipError_t launch_policy_rollout(const StepArgs* a, const PolicyArgs* pa, const IntegArgs* ia, const FilterArgs* fa, int mode, int ext,
+                                 hipStream_t s);
+hipError_t launch_policy_rollout_x(const StepArgs* a, const PolicyArgs* pa, const IntegArgs* ia, const FilterArgs* fa, int mode, int ext,
+                                   hipStream_t s);
 hipError_t launch_integ_clear(float4* state, const uint8_t* mask, int n, hipStream_t s);
 hipError_t launch_integ_state_io(float4* state, float* I, int32_t* c, int n, int write, hipStream_t s);
+// the reference filter's state: at rest on the env's reference RF[i].xyz (mask NULL = every env); and the checkpoint path
+// (x float[9][n] | r float[3][n], either may be NULL)
+hipError_t launch_reff_rest(const float4* RF, float4* state, const uint8_t* mask, int n, hipStream_t s);
+hipError_t launch_reff_state_io(float4* state, float* x, float* r, int n, int write, hipStream_t s);
 // two-wave closed loop, dpenv_policy_ws.h; one arithmetic per translation unit: dpenv_policy_ws.hip PREC_F16, dpenv_policy_xws1.hip
 // PREC_F32, dpenv_policy_xws2.hip PREC_F32_ACTOR
 template <int PREC>
-hipError_t launch_policy_rollout_ws(const StepArgs* a, const PolicyArgs* pa, const IntegArgs* ia, int mode, int ext, hipStream_t s);
+hipError_t launch_policy_rollout_ws(const StepArgs* a, const PolicyArgs* pa, const IntegArgs* ia, const FilterArgs* fa, int mode, int ext,
+                                    hipStream_t s);
 }  // namespace dev
 
 }  // namespace dpenv

@@ -61,8 +61,9 @@ __global__ __launch_bounds__(PBLOCK) void policy_forward_kernel(const PolicyArgs
 template <int MODE, bool EXT, int KA>
 __global__ __launch_bounds__(PBLOCK) void policy_rollout_kernel(const StepArgs a, const PolicyArgs pa)
 {
-    constexpr bool INTEG = false;
+    constexpr bool INTEG = false, REFF = false;
     const IntegArgs ia{};
+    const FilterArgs fa{};
 #include "dpenv_policy_rollout_body.inc"
 }
 
@@ -70,8 +71,48 @@ __global__ __launch_bounds__(PBLOCK) void policy_rollout_kernel(const StepArgs a
 template <int MODE, bool EXT, int KA>
 __global__ __launch_bounds__(PBLOCK) void policy_rollout_integ_kernel(const StepArgs a, const PolicyArgs pa, const IntegArgs ia)
 {
-    constexpr bool INTEG = true;
+    constexpr bool INTEG = true, REFF = false;
+    const FilterArgs fa{};
 #include "dpenv_policy_rollout_body.inc"
+}
+
+// REFF: the setpoint reference filter (FilterArgs, dpenv_set_reference_filter), with the integral action if INTEG_
+template <int MODE, bool EXT, int KA, bool INTEG_>
+__global__ __launch_bounds__(PBLOCK) void policy_rollout_reff_kernel(const StepArgs a, const PolicyArgs pa, const IntegArgs ia, const FilterArgs fa)
+{
+    constexpr bool INTEG = INTEG_, REFF = true;
+#include "dpenv_policy_rollout_body.inc"
+}
+
+// the reference filter at rest on the env's reference RF[i].xyz: turning it on (mask NULL) and dpenv_reset (the envs it re-draws)
+__global__ __launch_bounds__(256) void reff_rest_kernel(const float4* RF, float4* state, const uint8_t* mask, int n)
+{
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n || (mask != nullptr && mask[i] == 0)) return;
+    const float4 rf = RF[i];
+    const float ref[3] = {rf.x, rf.y, rf.z};
+#pragma unroll
+    for (int j = 0; j < 3; ++j) state[(int64_t)j * n + i] = make_float4(ref[j], 0.0f, 0.0f, ref[j]);
+}
+
+// the checkpoint path (dpenv_get_reference_filter_state / dpenv_set_reference_filter_state): float4 [3][n] <-> x float[9][n] (row 3 k + j:
+// pos, vel, acc of axis j) | r float[3][n]; either may be NULL
+__global__ __launch_bounds__(256) void reff_state_io_kernel(float4* state, float* x, float* r, int n, int write)
+{
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+        float4 q = state[(int64_t)j * n + i];
+        if (write) {
+            if (x) { q.x = x[(int64_t)j * n + i]; q.y = x[(int64_t)(3 + j) * n + i]; q.z = x[(int64_t)(6 + j) * n + i]; }
+            if (r) q.w = r[(int64_t)j * n + i];
+            state[(int64_t)j * n + i] = q;
+        } else {
+            if (x) { x[(int64_t)j * n + i] = q.x; x[(int64_t)(3 + j) * n + i] = q.y; x[(int64_t)(6 + j) * n + i] = q.z; }
+            if (r) r[(int64_t)j * n + i] = q.w;
+        }
+    }
 }
 
 // the explicit reset's side of the integral action (dpenv_reset): I = 0, count = 0 for the envs it re-draws
@@ -208,12 +249,21 @@ hipError_t dev::launch_policy_forward(const PolicyArgs* pa, int od, int adim, co
     }); });
 }
 
-// the one-wave closed loop in f16; with the integral action (ia) the set integ_one_wave admits
-hipError_t dev::launch_policy_rollout(const StepArgs* a, const PolicyArgs* pa, const IntegArgs* ia, int mode, int ext, hipStream_t s)
+// the one-wave closed loop in f16; with the integral action (ia) the set integ_one_wave admits, with the reference filter (fa) the set
+// reff_one_wave admits
+hipError_t dev::launch_policy_rollout(const StepArgs* a, const PolicyArgs* pa, const IntegArgs* ia, const FilterArgs* fa, int mode, int ext,
+                                      hipStream_t s)
 {
     const dim3 grid((a->n + PBLOCK - 1) / PBLOCK), block(PBLOCK);
     const size_t lds = policy_lds_bytes(*pa);
     return with_mode_ext_ka(mode, ext, *pa, [&](auto M, auto E, auto K) -> hipError_t {
+        if (fa) {
+            if constexpr (reff_one_wave(M, E, K)) {
+                if (ia) return launch_with_lds(policy_rollout_reff_kernel<M, E, K, true>, grid, block, lds, s, *a, *pa, *ia, *fa);
+                return launch_with_lds(policy_rollout_reff_kernel<M, E, K, false>, grid, block, lds, s, *a, *pa, IntegArgs{}, *fa);
+            }
+            return hipErrorInvalidValue;
+        }
         if (!ia) return launch_with_lds(policy_rollout_kernel<M, E, K>, grid, block, lds, s, *a, *pa);
         if constexpr (integ_one_wave(M, E, K)) return launch_with_lds(policy_rollout_integ_kernel<M, E, K>, grid, block, lds, s, *a, *pa, *ia);
         return hipErrorInvalidValue;
@@ -223,6 +273,18 @@ hipError_t dev::launch_policy_rollout(const StepArgs* a, const PolicyArgs* pa, c
 hipError_t dev::launch_integ_clear(float4* state, const uint8_t* mask, int n, hipStream_t s)
 {
     hipLaunchKernelGGL(integ_clear_kernel, dim3((n + 255) / 256), dim3(256), 0, s, state, mask, n);
+    return hipGetLastError();
+}
+
+hipError_t dev::launch_reff_rest(const float4* RF, float4* state, const uint8_t* mask, int n, hipStream_t s)
+{
+    hipLaunchKernelGGL(reff_rest_kernel, dim3((n + 255) / 256), dim3(256), 0, s, RF, state, mask, n);
+    return hipGetLastError();
+}
+
+hipError_t dev::launch_reff_state_io(float4* state, float* x, float* r, int n, int write, hipStream_t s)
+{
+    hipLaunchKernelGGL(reff_state_io_kernel, dim3((n + 255) / 256), dim3(256), 0, s, state, x, r, n, write);
     return hipGetLastError();
 }
 

@@ -525,6 +525,61 @@ __device__ __forceinline__ void integ_row(const IntegArgs& ia, int t, int n, int
     }
 }
 
+// the setpoint reference filter of the *_reff closed-loop kernels, in the f32 order include/dpenv.h states (deploy.BatchedReferenceFilter
+// is the host statement of it): per axis j, x[j] = (pos, vel, acc, target)
+struct ReffState {
+    float x[3][4];
+};
+__device__ __forceinline__ ReffState reff_load(const FilterArgs& fa, int il, int n)
+{
+    ReffState f;
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+        const float4 q = fa.state[(int64_t)j * n + il];
+        f.x[j][0] = q.x; f.x[j][1] = q.y; f.x[j][2] = q.z; f.x[j][3] = q.w;
+    }
+    return f;
+}
+__device__ __forceinline__ void reff_store(const FilterArgs& fa, int i, int n, const ReffState& f)
+{
+#pragma unroll
+    for (int j = 0; j < 3; ++j) fa.state[(int64_t)j * n + i] = make_float4(f.x[j][0], f.x[j][1], f.x[j][2], f.x[j][3]);
+}
+// a switch of the schedule: the new targets; heading the short way from the filter's present heading
+__device__ __forceinline__ void reff_target(ReffState& f, float rN, float rE, float rP)
+{
+    const float d = rP - f.x[2][0];
+    f.x[0][3] = rN;
+    f.x[1][3] = rE;
+    f.x[2][3] = f.x[2][0] + (d - 6.283185307179586f * rintf(d * 0.15915494309189535f));
+}
+// one control period: x_j <- Phi_j x_j + Gamma_j r_j, row by row ((Phi0 pos + Phi1 vel) + Phi2 acc) + Gamma r
+__device__ __forceinline__ void reff_advance(const FilterArgs& fa, ReffState& f)
+{
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+        const float p = f.x[j][0], v = f.x[j][1], c = f.x[j][2], r = f.x[j][3];
+#pragma unroll
+        for (int m = 0; m < 3; ++m)
+            f.x[j][m] = ((fa.phi[j][3 * m] * p + fa.phi[j][3 * m + 1] * v) + fa.phi[j][3 * m + 2] * c) + fa.gam[j][m] * r;
+    }
+}
+// every reset: at rest on the env's (new) reference
+__device__ __forceinline__ void reff_rest(ReffState& f, float refN, float refE, float refP)
+{
+    const float ref[3] = {refN, refE, refP};
+#pragma unroll
+    for (int j = 0; j < 3; ++j) { f.x[j][0] = ref[j]; f.x[j][1] = 0.0f; f.x[j][2] = 0.0f; f.x[j][3] = ref[j]; }
+}
+// the row of out: the reference obs[t] was formed against
+__device__ __forceinline__ void reff_row(const FilterArgs& fa, int t, int n, int i, bool live, float eN, float eE, float eP)
+{
+    if (fa.out && live) {
+        float* p = fa.out + ((int64_t)t * n + i) * 3;
+        p[0] = eN; p[1] = eE; p[2] = eP;
+    }
+}
+
 // this lane's vessel: its own per-env block (dpenv_set_vessel_params / domain randomisation), its class block from the table in HBM,
 // or the single class of the kernel arguments - loaded once per launch; the T-step kernels' staging area is the register file
 __device__ __forceinline__ Vessel launch_vessel_plain(const StepArgs& a, int il)

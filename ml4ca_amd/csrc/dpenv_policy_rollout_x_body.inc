@@ -1,5 +1,6 @@
-// dpenv_policy_rollout_x_body.inc - the body of policy_rollout_x_kernel and policy_rollout_x_integ_kernel (dpenv_policy_x.hip), included
-// into both (see dpenv_policy_rollout_body.inc for why it is spliced, not called).  In scope: a, pa, ia and the compile-time INTEG.
+// dpenv_policy_rollout_x_body.inc - the body of policy_rollout_x_kernel, policy_rollout_x_integ_kernel and policy_rollout_x_reff_kernel
+// (dpenv_policy_x.hip), included into each (see dpenv_policy_rollout_body.inc for why it is spliced, not called).  In scope: a, pa, ia, fa
+// and the compile-time INTEG and REFF.
     constexpr int A = ModeTraits<MODE>::A;
     constexpr int OD = EXT ? 9 : 6;
     extern __shared__ uint4 lds_dyn[];
@@ -45,6 +46,12 @@
         ig = integ_load(ia, il);
         integ_apply(ig, o);
     }
+    ReffState fs{};
+    if constexpr (REFF) {
+        fs = reff_load(fa, il, n);
+        reff_row(fa, 0, n, i, live, s.refN, s.refE, s.refPsi);  // the reference o_0 was formed against
+        s.refN = fs.x[0][0]; s.refE = fs.x[1][0]; s.refPsi = fs.x[2][0];   // the last launch's pending new_ref is in force from step 0
+    }
     SplitIn in;
     float vout[8], mu[8];
     obs_to_frags_x<OD>(o, in);
@@ -82,6 +89,15 @@
             has_ref = true; rf_dirty = true;
             ++next_switch;
         }
+        if constexpr (REFF) {                                    // a switch sets the filter's target; its position is the step's new_ref
+            if (has_ref) reff_target(fs, nrN, nrE, nrP);
+            reff_advance(fa, fs);
+            nrN = fs.x[0][0]; nrE = fs.x[1][0]; nrP = fs.x[2][0];
+            has_ref = t + 1 < pa.T; rf_dirty = true;             // the last step's stays pending in the filter: the state keeps the
+                                                                 // reference its last observation was formed against
+            // o_t+1 is formed before new_ref applies (Q4): against the reference in force now (a reset below overwrites the row)
+            if (t + 1 < pa.T) reff_row(fa, t + 1, n, i, live, s.refN, s.refE, s.refPsi);
+        }
         StepOut out;
         env_step<MODE, EXT>(a, ve, s, act, has_ref, nrN, nrE, nrP, a.cur_vc != nullptr, cur.vcN, cur.vcE, out, il);
         if (a.current_drift) current_drift_step(a, cur, vc0, beta0, a.env_id_base + i);
@@ -103,11 +119,18 @@
                 v_pre = vout[0];
             }
             if (do_reset) {
+                if constexpr (REFF) {                             // the last step's pending new_ref: a re-drawn env keeps it as its reference
+                    if (t == pa.T - 1) { s.refN = fs.x[0][0]; s.refE = fs.x[1][0]; s.refPsi = fs.x[2][0]; }
+                }
                 env_auto_reset<MODE>(a, s, a.env_id_base + i, episode, o);
                 if (a.rand_tab) redraw_vessel_cold(a, i, episode, ve);    // domain randomisation: the new episode runs on a new hull
                 if (a.cur_nom) current_redraw(a, i, episode, cur, vc0, beta0);    // ... in a new current (stored with the final state)
                 ++episode; ep_dirty = true; rf_dirty = true;
                 if constexpr (INTEG) integ_clear(ig);             // the new episode starts with I = 0
+                if constexpr (REFF) {                             // ... and the filter at rest on its reference
+                    reff_rest(fs, s.refN, s.refE, s.refPsi);
+                    if (t + 1 < pa.T) reff_row(fa, t + 1, n, i, live, s.refN, s.refE, s.refPsi);
+                }
             }
         }
         obs_to_frags_x<OD>(o, in);
@@ -137,4 +160,5 @@
         if (a.cur_nom && ep_dirty) store_current(a, i, cur, vc0, beta0, true);
         if (draw) a.noise_ctr[i] = nctr;
         if constexpr (INTEG) integ_store(ia, i, ig);
+        if constexpr (REFF) reff_store(fa, i, n, fs);
     }

@@ -76,8 +76,9 @@ __device__ __forceinline__ void ws_wait(int* p, int v)
 template <int MODE, bool EXT, int KA, int ROLES, int PREC = PREC_F16, int GROUPS = 4, bool RND = false, bool SLOSS = false>
 __global__ __launch_bounds__(64 * GROUPS * ROLES) void policy_rollout_ws_kernel(const StepArgs a, const PolicyArgs pa)
 {
-    constexpr bool INTEG = false;
+    constexpr bool INTEG = false, REFF = false;
     const IntegArgs ia{};
+    const FilterArgs fa{};
 #include "dpenv_policy_ws_body.inc"
 }
 
@@ -86,7 +87,17 @@ __global__ __launch_bounds__(64 * GROUPS * ROLES) void policy_rollout_ws_kernel(
 template <int MODE, bool EXT, int KA, int ROLES, int PREC, int GROUPS, bool RND, bool SLOSS>
 __global__ __launch_bounds__(64 * GROUPS * ROLES) void policy_rollout_ws_integ_kernel(const StepArgs a, const PolicyArgs pa, const IntegArgs ia)
 {
-    constexpr bool INTEG = true;
+    constexpr bool INTEG = true, REFF = false;
+    const FilterArgs fa{};
+#include "dpenv_policy_ws_body.inc"
+}
+
+//  REFF: the setpoint reference filter (FilterArgs, dpenv_set_reference_filter) on the env wave, with the integral action if INTEG_
+template <int MODE, bool EXT, int KA, int ROLES, int PREC, int GROUPS, bool RND, bool SLOSS, bool INTEG_>
+__global__ __launch_bounds__(64 * GROUPS * ROLES) void policy_rollout_ws_reff_kernel(const StepArgs a, const PolicyArgs pa, const IntegArgs ia,
+                                                                                      const FilterArgs fa)
+{
+    constexpr bool INTEG = INTEG_, REFF = true;
 #include "dpenv_policy_ws_body.inc"
 }
 
@@ -102,13 +113,23 @@ __global__ __launch_bounds__(64 * GROUPS * ROLES) void policy_rollout_ws_integ_k
 namespace dpenv {
 
 template <int MODE, bool EXT, int KA, int PREC, int GROUPS, bool RND, bool SLOSS>
-static hipError_t ws_go(const StepArgs& a, const PolicyArgs& pa, const IntegArgs* ia, hipStream_t s)
+static hipError_t ws_go(const StepArgs& a, const PolicyArgs& pa, const IntegArgs* ia, const FilterArgs* fa, hipStream_t s)
 {
     constexpr int ROLES = ws_roles(PREC, GROUPS);
     const dim3 grid((a.n + 64 * GROUPS - 1) / (64 * GROUPS)), block(64 * GROUPS * ROLES);
     const size_t lds = (size_t)ws_images(PREC) * pa.nent * 16 + (size_t)2 * pa.nblk * 32 * 4 +
                        (size_t)GROUPS * ((((PREC == PREC_F16 && ROLES == 2)) ? WS_GROUP_FLOATS : WS_GROUP_FLOATS_X) +
                                          (ROLES == 3 ? 64 * 9 : 0)) * 4;
+    if (fa) {
+        if constexpr (ws_reff(MODE, EXT, KA)) {
+            if (ia)
+                return launch_with_lds(policy_rollout_ws_reff_kernel<MODE, EXT, KA, ROLES, PREC, GROUPS, RND, SLOSS, true>, grid, block, lds, s, a, pa,
+                                       *ia, *fa);
+            return launch_with_lds(policy_rollout_ws_reff_kernel<MODE, EXT, KA, ROLES, PREC, GROUPS, RND, SLOSS, false>, grid, block, lds, s, a, pa,
+                                   IntegArgs{}, *fa);
+        }
+        return hipErrorInvalidValue;
+    }
     if (!ia) return launch_with_lds(policy_rollout_ws_kernel<MODE, EXT, KA, ROLES, PREC, GROUPS, RND, SLOSS>, grid, block, lds, s, a, pa);
     if constexpr (ws_integ(MODE, EXT, KA))
         return launch_with_lds(policy_rollout_ws_integ_kernel<MODE, EXT, KA, ROLES, PREC, GROUPS, RND, SLOSS>, grid, block, lds, s, a, pa, *ia);
@@ -117,7 +138,8 @@ static hipError_t ws_go(const StepArgs& a, const PolicyArgs& pa, const IntegArgs
 
 // the set the ws_* predicates of dpenv_dev.h admit; dpenv_api.hip routes everything else to the one-wave kernels
 template <int PREC>
-hipError_t dev::launch_policy_rollout_ws(const StepArgs* a, const PolicyArgs* pa, const IntegArgs* ia, int mode, int ext, hipStream_t s)
+hipError_t dev::launch_policy_rollout_ws(const StepArgs* a, const PolicyArgs* pa, const IntegArgs* ia, const FilterArgs* fa, int mode, int ext,
+                                         hipStream_t s)
 {
     if (pa->ws_groups != 2 && pa->ws_groups != 4) return hipErrorInvalidValue;
     const bool sloss = a->loss_on == LOSS_SHARED;                    // the single class's coefficients as kernel arguments
@@ -127,10 +149,10 @@ hipError_t dev::launch_policy_rollout_ws(const StepArgs* a, const PolicyArgs* pa
         auto groups = [&](auto G) -> hipError_t {
             if constexpr (ws_has(K, PREC, G)) {
                 if constexpr (ws_general(M, E, K)) {
-                    if (sloss) return ws_go<M, E, K, PREC, G, false, true>(*a, *pa, ia, s);
-                    if (rnd) return ws_go<M, E, K, PREC, G, true, false>(*a, *pa, ia, s);
+                    if (sloss) return ws_go<M, E, K, PREC, G, false, true>(*a, *pa, ia, fa, s);
+                    if (rnd) return ws_go<M, E, K, PREC, G, true, false>(*a, *pa, ia, fa, s);
                 }
-                if (!sloss && !rnd) return ws_go<M, E, K, PREC, G, false, false>(*a, *pa, ia, s);
+                if (!sloss && !rnd) return ws_go<M, E, K, PREC, G, false, false>(*a, *pa, ia, fa, s);
             }
             return hipErrorInvalidValue;
         };

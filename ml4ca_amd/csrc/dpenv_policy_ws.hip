@@ -13,5 +13,6 @@ using namespace dpenv;
 #endif
 
 namespace dpenv {
-template hipError_t dev::launch_policy_rollout_ws<PREC_F16>(const StepArgs*, const PolicyArgs*, const IntegArgs*, int, int, hipStream_t);
+template hipError_t dev::launch_policy_rollout_ws<PREC_F16>(const StepArgs*, const PolicyArgs*, const IntegArgs*, const FilterArgs*, int, int,
+                                                                    hipStream_t);
 }

@@ -1,6 +1,6 @@
-// dpenv_policy_ws_body.inc - the body of policy_rollout_ws_kernel and policy_rollout_ws_integ_kernel (dpenv_policy_ws.h), included into
-// both (see dpenv_policy_rollout_body.inc for why it is spliced, not called).  In scope: a, pa, ia and the compile-time INTEG; the rest
-// are the kernel's template arguments.
+// dpenv_policy_ws_body.inc - the body of policy_rollout_ws_kernel, policy_rollout_ws_integ_kernel and policy_rollout_ws_reff_kernel
+// (dpenv_policy_ws.h), included into each (see dpenv_policy_rollout_body.inc for why it is spliced, not called).  In scope: a, pa, ia, fa
+// and the compile-time INTEG and REFF; the rest are the kernel's template arguments.
     static_assert(!(RND && SLOSS), "per-env blocks carry their own coefficients");
     constexpr int IL = SLOSS ? IL_SHARED : IL_NONE;
     constexpr bool CURR = RND || SLOSS;            // the forms that re-draw the current with the episode
@@ -230,6 +230,14 @@
         ig = integ_load(ia, il);
         integ_apply(ig, o);
     }
+    // The reference filter's state (12 registers) stays in the env wave's registers across the launch; it does not depend on the actor's
+    // answer, so each step's switch and advance are made while this wave waits for mu_t, off the chain.
+    ReffState fs{};
+    if constexpr (REFF) {
+        fs = reff_load(fa, il, n);
+        reff_row(fa, 0, n, i, live, s.refN, s.refE, s.refPsi);              // the reference o_0 was formed against
+        s.refN = fs.x[0][0]; s.refE = fs.x[1][0]; s.refPsi = fs.x[2][0];     // the last launch's pending new_ref is in force from step 0
+    }
 #pragma unroll
     for (int k = 0; k < OD; ++k) obs_mb[lane * 9 + k] = o[k];               // parity 0
     ws_post(&seq[0], 1, lane);                                               // o_0 posted
@@ -311,6 +319,16 @@
         }
         if constexpr (VE_RELOAD) ve = vessel_from_env(a.env_tab, a.env_stride, il);
         if constexpr (IG_RELOAD) ig = integ_load(ia, il);                     // issued before the wait for mu_t: off the chain
+        if constexpr (REFF) {                                                // a switch sets the filter's target; its position is the step's new_ref
+            if (next_switch < pa.n_switch && pa.switch_step[next_switch] == t) {
+                const float* rp = pa.refs + (int64_t)next_switch * 3 * n;
+                reff_target(fs, rp[il], rp[(int64_t)n + il], rp[2 * (int64_t)n + il]);
+                ++next_switch;
+            }
+            reff_advance(fa, fs);
+            // o_t+1 is formed before this step's new_ref applies (Q4): against the reference in force now (a reset overwrites the row)
+            if (t + 1 < pa.T) reff_row(fa, t + 1, n, i, live, s.refN, s.refE, s.refPsi);
+        }
         if (PREDRAW && __ballot(need_draw) != 0ull) {                        // wave-uniform; lanes whose episode did not move redraw the same values
             reset_draw<MODE>(a, a.env_id_base + i, episode, rdraw);
             need_draw = false;
@@ -330,11 +348,16 @@
         for (int k = 0; k < A; ++k) act[k] = (pa.noise || draw) ? fmaf(pc.std[k], xi[k], mu[k]) : mu[k];      // core.py:85
         bool has_ref = false;
         float nrN = 0.0f, nrE = 0.0f, nrP = 0.0f;
-        if (next_switch < pa.n_switch && pa.switch_step[next_switch] == t) {
+        if (!REFF && next_switch < pa.n_switch && pa.switch_step[next_switch] == t) {
             const float* rp = pa.refs + (int64_t)next_switch * 3 * n;
             nrN = rp[il]; nrE = rp[(int64_t)n + il]; nrP = rp[2 * (int64_t)n + il];
             has_ref = true; rf_dirty = true;
             ++next_switch;
+        }
+        if constexpr (REFF) {
+            nrN = fs.x[0][0]; nrE = fs.x[1][0]; nrP = fs.x[2][0];
+            has_ref = t + 1 < pa.T; rf_dirty = true;                         // the last step's stays pending in the filter: the state keeps
+                                                                             // the reference its last observation was formed against
         }
         StepOut out;
 #ifdef DPENV_WS_SELFCHECK
@@ -416,6 +439,9 @@
         pre_owed = post_pre;
         if (__ballot(do_reset) != 0ull) {
             if (do_reset) {
+                if constexpr (REFF) {                             // the last step's pending new_ref: a re-drawn env keeps it as its reference
+                    if (t == pa.T - 1) { s.refN = fs.x[0][0]; s.refE = fs.x[1][0]; s.refPsi = fs.x[2][0]; }
+                }
                 if constexpr (PREDRAW) { reset_apply<MODE>(a, s, rdraw, o); need_draw = true; }
                 else env_auto_reset<MODE>(a, s, a.env_id_base + i, episode, o);
                 // domain randomisation: the new episode runs on a new hull (the RND instantiation also serves fixed hulls with a thrust loss)
@@ -426,6 +452,10 @@
                 if constexpr (CURR) { if (a.cur_nom) { const float2 cd = current_redraw_call(a.cur_nom, a.cur_nom_stride, a.cur_range_v, a.cur_range_b, a.seed_lo, a.seed_hi, a.env_id_base + i, i, episode); new_vc = cd.x; new_beta = cd.y; } }
                 ++episode; ep_dirty = true; rf_dirty = true;
                 if constexpr (INTEG) integ_clear(ig);                         // the new episode starts with I = 0
+                if constexpr (REFF) {                                         // ... and the filter at rest on its reference
+                    reff_rest(fs, s.refN, s.refE, s.refPsi);
+                    if (t + 1 < pa.T) reff_row(fa, t + 1, n, i, live, s.refN, s.refE, s.refPsi);
+                }
             }
         }
         // o_{t+1} replaces o_t in the mailbox: the network wave read o_t right after it saw seq[0] = t + 1 and BEFORE it posted
@@ -494,4 +524,5 @@
         if constexpr (CURR) { if (a.cur_nom && ep_dirty) store_current(a, i, cur, vc0, beta0, true); }
         if (draw) a.noise_ctr[i] = nctr;
         if constexpr (INTEG && !IG_RELOAD) integ_store(ia, i, ig);
+        if constexpr (REFF) reff_store(fa, i, n, fs);
     }

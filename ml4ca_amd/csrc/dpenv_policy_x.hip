@@ -66,8 +66,9 @@ __global__ __launch_bounds__(PBLOCK) void policy_forward_x_kernel(const PolicyAr
 template <int MODE, bool EXT, int KA>
 __global__ __launch_bounds__(PBLOCK) void policy_rollout_x_kernel(const StepArgs a, const PolicyArgs pa)
 {
-    constexpr bool INTEG = false;
+    constexpr bool INTEG = false, REFF = false;
     const IntegArgs ia{};
+    const FilterArgs fa{};
 #include "dpenv_policy_rollout_x_body.inc"
 }
 
@@ -75,7 +76,16 @@ __global__ __launch_bounds__(PBLOCK) void policy_rollout_x_kernel(const StepArgs
 template <int MODE, bool EXT, int KA>
 __global__ __launch_bounds__(PBLOCK) void policy_rollout_x_integ_kernel(const StepArgs a, const PolicyArgs pa, const IntegArgs ia)
 {
-    constexpr bool INTEG = true;
+    constexpr bool INTEG = true, REFF = false;
+    const FilterArgs fa{};
+#include "dpenv_policy_rollout_x_body.inc"
+}
+
+// REFF: the setpoint reference filter (FilterArgs, dpenv_set_reference_filter), with the integral action if INTEG_
+template <int MODE, bool EXT, int KA, bool INTEG_>
+__global__ __launch_bounds__(PBLOCK) void policy_rollout_x_reff_kernel(const StepArgs a, const PolicyArgs pa, const IntegArgs ia, const FilterArgs fa)
+{
+    constexpr bool INTEG = INTEG_, REFF = true;
 #include "dpenv_policy_rollout_x_body.inc"
 }
 
@@ -94,13 +104,22 @@ hipError_t dev::launch_policy_forward_x(const PolicyArgs* pa, int od, int adim, 
     }); });
 }
 
-// the one-wave closed loop in the split arithmetics; with the integral action (ia) the set integ_one_wave admits
-hipError_t dev::launch_policy_rollout_x(const StepArgs* a, const PolicyArgs* pa, const IntegArgs* ia, int mode, int ext, hipStream_t s)
+// the one-wave closed loop in the split arithmetics; with the integral action (ia) the set integ_one_wave admits, with the reference
+// filter (fa) the set reff_one_wave admits
+hipError_t dev::launch_policy_rollout_x(const StepArgs* a, const PolicyArgs* pa, const IntegArgs* ia, const FilterArgs* fa, int mode, int ext,
+                                        hipStream_t s)
 {
     if (!pa->split) return hipErrorInvalidValue;
     const dim3 grid((a->n + PBLOCK - 1) / PBLOCK), block(PBLOCK);
     const size_t lds = lds_bytes_x(*pa);
     return with_mode_ext_ka(mode, ext, *pa, [&](auto M, auto E, auto K) -> hipError_t {
+        if (fa) {
+            if constexpr (reff_one_wave(M, E, K)) {
+                if (ia) return launch_with_lds(policy_rollout_x_reff_kernel<M, E, K, true>, grid, block, lds, s, *a, *pa, *ia, *fa);
+                return launch_with_lds(policy_rollout_x_reff_kernel<M, E, K, false>, grid, block, lds, s, *a, *pa, IntegArgs{}, *fa);
+            }
+            return hipErrorInvalidValue;
+        }
         if (!ia) return launch_with_lds(policy_rollout_x_kernel<M, E, K>, grid, block, lds, s, *a, *pa);
         if constexpr (integ_one_wave(M, E, K)) return launch_with_lds(policy_rollout_x_integ_kernel<M, E, K>, grid, block, lds, s, *a, *pa, *ia);
         return hipErrorInvalidValue;

@@ -4,5 +4,6 @@
 #include "dpenv_policy_ws.h"
 
 namespace dpenv {
-template hipError_t dev::launch_policy_rollout_ws<PREC_F32>(const StepArgs*, const PolicyArgs*, const IntegArgs*, int, int, hipStream_t);
+template hipError_t dev::launch_policy_rollout_ws<PREC_F32>(const StepArgs*, const PolicyArgs*, const IntegArgs*, const FilterArgs*, int, int,
+                                                                    hipStream_t);
 }

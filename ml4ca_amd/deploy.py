@@ -6,7 +6,8 @@ trained on the batched env can be driven exactly the way the vessel's node drive
 wrap the node uses (unlike the training env, quirk Q1), network order -> ROS thruster order, default commands for the
 thrusters a variant does not control, the optional body-frame integral action, and the message fields published.
 BatchedBodyFrameIntegrator is the torch form of that integral action for a batch of envs (the law the closed-loop
-kernels apply while it is on, include/dpenv.h).
+kernels apply while it is on, include/dpenv.h); BatchedReferenceFilter is the same for the setpoint reference filter
+the node took its reference from.
 
   network order  [n_bow, n_port, n_star, (a_bow,) a_port, a_star]       (customEnv.py:47-61)
   ROS order      [n_port, n_star, n_bow, a_port, a_star, a_bow]         (rl_allocator.py:92-106)
@@ -142,6 +143,109 @@ class BatchedBodyFrameIntegrator(object):
         else:
             self.I[mask] = 0
             self.count[mask] = 0
+
+
+# the setpoint reference filter's defaults: the least-squares fit to the recorded filter output of the thesis' box, current box and
+# large-setpoint runs (tools/gen_golden_reffilter.py prints it; tests/golden/reference_filter.npz keeps it)
+REFERENCE_FILTER_OMEGA = (0.619, 0.619, 1.51)
+REFERENCE_FILTER_ZETA = (1.0, 1.0, 1.0)
+
+
+def reference_filter_coeffs_f64(omega, zeta, dt):
+    """(phi [3, 3, 3], gam [3, 3]) float64: per axis j the exact zero-order hold of the third-order reference model over dt,
+    exp([[A_j, B_j], [0, 0]] dt) by scaling and squaring of its degree-18 Taylor polynomial - the recipe of dpenv.h, which rounds
+    the result to f32 (dpenv_reference_filter_coeffs)."""
+    phi, gam = np.zeros((3, 3, 3)), np.zeros((3, 3))
+    for j in range(3):
+        w, c = float(omega[j]), 2.0 * float(zeta[j]) + 1.0
+        M = np.array([[0.0, 1.0, 0.0, 0.0], [0.0, 0.0, 1.0, 0.0], [-w * w * w, -c * w * w, -c * w, w * w * w], [0.0] * 4]) * float(dt)
+        norm, sq = float(np.abs(M).sum(0).max()), 0
+        while norm > 0.5 and sq < 200:
+            norm *= 0.5
+            sq += 1
+        M = M * np.ldexp(1.0, -sq)
+        E, T = np.eye(4), np.eye(4)
+        for k in range(1, 19):
+            T = (T @ M) / float(k)
+            E = E + T
+        for _ in range(sq):
+            E = E @ E
+        phi[j], gam[j] = E[:3, :3], E[:3, 3]
+    return phi, gam
+
+
+def reference_filter_coeffs(omega=REFERENCE_FILTER_OMEGA, zeta=REFERENCE_FILTER_ZETA, dt=0.2):
+    """The library's f32 coefficients (dpenv_reference_filter_coeffs): (phi [3, 3, 3], gam [3, 3]) float32.  A pure host call;
+    bad inputs raise DpenvError."""
+    import ctypes as C
+    from . import _lib
+    lib = _lib.load()
+    rf = _lib.ReferenceFilter()
+    rf.struct_size = C.sizeof(_lib.ReferenceFilter)
+    for j in range(3):
+        rf.omega[j], rf.zeta[j] = float(omega[j]), float(zeta[j])
+    phi, gam = (C.c_float * 9 * 3)(), (C.c_float * 3 * 3)()
+    _lib.check(lib.dpenv_reference_filter_coeffs(C.byref(rf), float(dt), C.byref(phi), C.byref(gam)))
+    return np.array(phi, np.float32).reshape(3, 3, 3), np.array(gam, np.float32).reshape(3, 3)
+
+
+class BatchedReferenceFilter(object):
+    """The setpoint reference filter of the deployed controller for n envs, as torch tensors: per axis j in (N, E, psi) the
+    third-order reference model x''' + (2 zeta + 1) omega x'' + (2 zeta + 1) omega^2 x' + omega^3 x = omega^3 r, stepped by its
+    exact zero-order hold over dt, in the f32 operation order of include/dpenv.h with the library's coefficients - the law the
+    closed-loop kernels apply while dpenv_set_reference_filter is on, bit for bit.  dtype=torch.float64 uses the f64 coefficients
+    instead (the recorded pin).  State: x [3 (pos, vel, acc), 3 (N, E, psi), n] and the targets r [3, n]; heading in rad, unwrapped.
+    Eager use: env.step(a, new_ref=F.advance()), F.switch(target) when the setpoint changes, F.reset(env reference, mask) after an
+    auto-reset - the fused launch is policy.policy_rollout with env.set_reference_filter on."""
+
+    def __init__(self, n, omega=REFERENCE_FILTER_OMEGA, zeta=REFERENCE_FILTER_ZETA, dt=0.2, device='cpu', dtype=None):
+        import torch
+        self.dtype = torch.float32 if dtype is None else dtype
+        if self.dtype == torch.float32:
+            phi, gam = reference_filter_coeffs(omega, zeta, dt)
+        else:
+            phi, gam = reference_filter_coeffs_f64(omega, zeta, dt)
+        t = lambda v: torch.as_tensor(v, device=device).to(self.dtype)
+        self.phi, self.gam = t(phi), t(gam)                                   # [j][m][k], [j][m]
+        if self.dtype == torch.float32:
+            self.two_pi, self.inv_two_pi = t(np.float32(2 * np.pi)), t(np.float32(1 / (2 * np.pi)))
+        else:
+            self.two_pi, self.inv_two_pi = t(2 * np.pi), t(1 / (2 * np.pi))
+        self.x = torch.zeros((3, 3, n), dtype=self.dtype, device=device)
+        self.r = torch.zeros((3, n), dtype=self.dtype, device=device)
+
+    @property
+    def pos(self):
+        return self.x[0]
+
+    def advance(self):
+        """One control period; returns the position eta_d [3, n] (contiguous): the step's new_ref."""
+        import torch
+        p, v, a = self.x[0], self.x[1], self.x[2]
+        P, G = self.phi, self.gam
+        rows = [((P[:, m, 0:1] * p + P[:, m, 1:2] * v) + P[:, m, 2:3] * a) + G[:, m:m + 1] * self.r for m in range(3)]
+        self.x = torch.stack(rows)
+        return self.x[0].clone().contiguous()
+
+    def switch(self, target, mask=None):
+        """New targets [3, n] for the envs in mask (bool [n]; None = all); heading the short way from the present heading."""
+        import torch
+        target = torch.as_tensor(target, device=self.r.device).to(self.dtype)
+        d = target[2] - self.x[0, 2]
+        psi = self.x[0, 2] + (d - self.two_pi * torch.round(d * self.inv_two_pi))
+        new = torch.stack([target[0], target[1], psi])
+        self.r = new if mask is None else torch.where(mask[None, :], new, self.r)
+
+    def reset(self, ref, mask=None):
+        """At rest on ref [3, n] (pos = target = ref, vel = acc = 0) for the envs in mask (None = all): every reset path."""
+        import torch
+        ref = torch.as_tensor(ref, device=self.r.device).to(self.dtype)
+        rest = torch.stack([ref, torch.zeros_like(ref), torch.zeros_like(ref)])
+        if mask is None:
+            self.x, self.r = rest, ref.clone()
+        else:
+            self.x = torch.where(mask[None, None, :], rest, self.x)
+            self.r = torch.where(mask[None, :], ref, self.r)
 
 
 class RLAllocatorNode(object):

@@ -21,6 +21,7 @@ import weakref
 import numpy as np
 
 from . import _lib
+from .deploy import REFERENCE_FILTER_OMEGA, REFERENCE_FILTER_ZETA
 from . import reset_samplers as simtools
 
 _VARIANTS = {'full': _lib.FULL, 'simple': _lib.SIMPLE, 'limited': _lib.LIMITED, 'final': _lib.FINAL}
@@ -182,6 +183,7 @@ class BatchedRevoltEnv(object):
         self._n1, self._r3, self._p4 = (n,), (3, n), (4, n)
         self._step_ex = self.lib.dpenv_step_ex
         self.integral_action = None          # dict of the parameters while set_integral_action() has it on
+        self.reference_filter = None         # dict of the parameters while set_reference_filter() has it on
 
     # -- plumbing -----------------------------------------------------------------------------
     # What a Python `for` over step() pays per call besides the launch is this plumbing (bench.py `eager_loop`): the stream handle and
@@ -301,6 +303,10 @@ class BatchedRevoltEnv(object):
             raise ValueError('%s(): the integral action is on (set_integral_action) and this launch\'s observations would lack I; fly the closed '
                              'loop (policy.policy_rollout), compose step() with deploy.BatchedBodyFrameIntegrator after set_integral_action(None), '
                              'or turn it off' % what)
+        if self.reference_filter is not None:
+            raise ValueError('%s(): the reference filter is on (set_reference_filter) and would not see this launch; fly the closed loop '
+                             '(policy.policy_rollout), compose step() with deploy.BatchedReferenceFilter (its position as new_ref) after '
+                             'set_reference_filter(None), or turn it off' % what)
 
     def rollout(self, actions, switch_steps=(), refs=None, out=None):
         """T env steps in one launch (dpenv_rollout): exactly T successive step() calls with actions[t], passing
@@ -396,6 +402,38 @@ class BatchedRevoltEnv(object):
         I = self._chk(I, (3, self.n_envs), torch.float32, 'I')
         count = self._chk(count, (self.n_envs,), torch.int32, 'count')
         _lib.check(self.lib.dpenv_set_integral_state(self._h, self._ptr(I), self._ptr(count), self._stream()), self._h)
+
+    # -- the deployed controller's setpoint reference filter (dpenv.h dpenv_set_reference_filter) ------------------------------------
+    def set_reference_filter(self, omega=REFERENCE_FILTER_OMEGA, zeta=REFERENCE_FILTER_ZETA):
+        """The setpoint reference filter the RL node took its reference from (include/dpenv.h has the law) in the closed-loop launches:
+        a setpoint switch sets the filter's target, and every step's new_ref is the filter's position.  omega [rad/s] / zeta: per axis
+        (N, E, psi); the defaults are the recorded fit (deploy.REFERENCE_FILTER_OMEGA / _ZETA).  omega=None turns it off.  Turning it on
+        puts every env's filter at rest on its reference.  While it is on, step() and rollout() raise ValueError."""
+        if omega is None:
+            _lib.check(self.lib.dpenv_set_reference_filter(self._h, None, self._stream()), self._h)
+            self.reference_filter = None
+            return
+        rf = _lib.ReferenceFilter()
+        rf.struct_size = C.sizeof(_lib.ReferenceFilter)
+        for j in range(3):
+            rf.omega[j], rf.zeta[j] = float(omega[j]), float(zeta[j])
+        _lib.check(self.lib.dpenv_set_reference_filter(self._h, C.byref(rf), self._stream()), self._h)
+        self.reference_filter = dict(omega=tuple(rf.omega), zeta=tuple(rf.zeta), dt=self.control_period)
+
+    def get_reference_filter_state(self):
+        """(x float32 [9, n], r float32 [3, n]): row 3 k + j of x is (pos, vel, acc)[k] of axis (N, E, psi)[j]; r the targets.  Checkpoint
+        with get_state() / get_rng_counters()."""
+        torch = _torch()
+        x = torch.empty((9, self.n_envs), dtype=torch.float32, device=self.device)
+        r = torch.empty((3, self.n_envs), dtype=torch.float32, device=self.device)
+        _lib.check(self.lib.dpenv_get_reference_filter_state(self._h, self._ptr(x), self._ptr(r), self._stream()), self._h)
+        return x, r
+
+    def set_reference_filter_state(self, x=None, r=None):
+        torch = _torch()
+        x = self._chk(x, (9, self.n_envs), torch.float32, 'x')
+        r = self._chk(r, (3, self.n_envs), torch.float32, 'r')
+        _lib.check(self.lib.dpenv_set_reference_filter_state(self._h, self._ptr(x), self._ptr(r), self._stream()), self._h)
 
     def get_rng_counters(self):
         """(noise_ctr, drift_ctr): int32 [n] draws made so far of the in-kernel exploration noise and of the current drift (uint32

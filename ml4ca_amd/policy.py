@@ -231,7 +231,8 @@ def policy_rollout(env, T, noise=None, switch_steps=(), refs=None, out=None, sam
     rew, val, logp, boot [T,n], done [T,n] uint8, last_obs [n,od], last_val [n].  GAE: rollout.gae(rew, val, end=done, boot=boot).
     reset_at_end: the reference's epoch boundary (ppo.py:305-322): every env is cut and re-drawn after step T-1 (dpenv.h).
     With the integral action on (env.set_integral_action) the launch applies it and out['integ'] [T,n,3] holds the I added to obs[t]
-    (obs[..., :3] - integ is the true error)."""
+    (obs[..., :3] - integ is the true error).  With the reference filter on (env.set_reference_filter) the switches set the filter's
+    targets, every step's new_ref is its position, and out['ref'] [T,n,3] holds the eta_d that obs[t] was formed against."""
     torch = _torch()
     n, od, ad = env.n_envs, env.num_states, env.num_actions
     dev = env.device
@@ -260,7 +261,18 @@ def policy_rollout(env, T, noise=None, switch_steps=(), refs=None, out=None, sam
     io.refs = refs.data_ptr() if k else None
     io.sample = 1 if (sample and noise is None) else 0
     io.reset_at_end = 1 if reset_at_end else 0
-    if env.integral_action is not None:
+    if env.reference_filter is not None:
+        if out.get('ref') is None:
+            out['ref'] = torch.empty((T, n, 3), dtype=f32, device=dev)
+        env._chk(out['ref'], (T, n, 3), f32, "out['ref']")
+        integ = None
+        if env.integral_action is not None:
+            if out.get('integ') is None:
+                out['integ'] = torch.empty((T, n, 3), dtype=f32, device=dev)
+            env._chk(out['integ'], (T, n, 3), f32, "out['integ']")
+            integ = out['integ'].data_ptr()
+        _lib.check(env.lib.dpenv_policy_rollout_deployed(env._h, C.byref(io), out['ref'].data_ptr(), integ, env._stream()), env._h)
+    elif env.integral_action is not None:
         if out.get('integ') is None:
             out['integ'] = torch.empty((T, n, 3), dtype=f32, device=dev)
         env._chk(out['integ'], (T, n, 3), f32, "out['integ']")

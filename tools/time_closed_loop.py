@@ -1,6 +1,8 @@
 #!/usr/bin/env python3
 """Closed-loop launch forms side by side (same call, same box): us per env step of dpenv_policy_rollout for every arithmetic x launch
 form at 65 536 envs (256-env workgroups: an env and a network wave per SIMD) and 32 768 envs (128-env workgroups: a SIMD per wave).
+--integral times the integral action on against off; --reference-filter times the setpoint reference filter on against off (with the
+integral action on in both arms if --integral is given too).
     python tools/time_closed_loop.py [--envs 65536,32768] [--steps 50] [--reps 8] [--out gpurun_out/closed_loop_forms.json]"""
 import argparse
 import json
@@ -20,6 +22,8 @@ def main():
     ap.add_argument('--out', default='')
     ap.add_argument('--integral', action='store_true', help='time every form with the deployed node\'s integral action (dpenv_set_integral_action, '
                     'the node\'s parameters) off and on, alternating launch by launch in one process; prints the ratio on / off of the medians')
+    ap.add_argument('--reference-filter', action='store_true', help='time every form with the setpoint reference filter (dpenv_set_reference_filter, '
+                    'the recorded fit) off and on, alternating launch by launch in one process; with --integral the integral action is on in both')
     ap.add_argument('--forms', default='f16:two_wave,f16:one_wave,f32_actor:two_wave,f32_actor:one_wave,f32:two_wave,f32:one_wave')
     args = ap.parse_args()
     import torch
@@ -40,6 +44,9 @@ def main():
                 print('%7d %-22s refused (%s)' % (n, spec, str(e)[:60]), flush=True)
                 continue
             env.reset()
+            if args.reference_filter:
+                res['%d/%s' % (n, spec)] = time_reference_filter(env, args, n, spec)
+                continue
             if args.integral:
                 res['%d/%s' % (n, spec)] = time_integral(env, args, n, spec)
                 continue
@@ -86,6 +93,34 @@ def time_integral(env, args, n, spec):
                                                                                     min(ts[True]), med[True] / med[False]), flush=True)
     return {'us_per_step_median_off': med[False], 'us_per_step_median_on': med[True], 'us_per_step_min_off': min(ts[False]),
             'us_per_step_min_on': min(ts[True]), 'on_over_off': med[True] / med[False]}
+
+
+def time_reference_filter(env, args, n, spec):
+    """us per env step with the reference filter off and on, alternating launch by launch (same process, same state stream); the
+    integral action on in both arms with --integral."""
+    import torch
+    from ml4ca_amd.policy import policy_rollout
+    if args.integral:
+        env.set_integral_action()
+    outs, ts = {}, {False: [], True: []}
+    for k in range(args.warm + args.reps):
+        for on in (False, True):
+            env.set_reference_filter() if on else env.set_reference_filter(None)
+            outs[on] = policy_rollout(env, args.steps, sample=True, out=outs.get(on))
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            policy_rollout(env, args.steps, sample=True, out=outs[on])
+            torch.cuda.synchronize()
+            if k >= args.warm:
+                ts[on].append((time.perf_counter() - t0) / args.steps * 1e6)
+    env.set_reference_filter(None)
+    env.set_integral_action(None)
+    med = {on: sorted(v)[len(v) // 2] for on, v in ts.items()}
+    assert bool(torch.isfinite(outs[True]['ref']).all())
+    print('%7d %-22s %s off %7.2f  on %7.2f us/step (min %6.2f / %6.2f)  on/off %.3f' % (
+        n, spec, 'integ' if args.integral else '     ', med[False], med[True], min(ts[False]), min(ts[True]), med[True] / med[False]), flush=True)
+    return {'integral': bool(args.integral), 'us_per_step_median_off': med[False], 'us_per_step_median_on': med[True],
+            'us_per_step_min_off': min(ts[False]), 'us_per_step_min_on': min(ts[True]), 'on_over_off': med[True] / med[False]}
 
 
 if __name__ == '__main__':

@@ -61,7 +61,7 @@ __global__ __launch_bounds__(PBLOCK) void policy_forward_kernel(const PolicyArgs
 template <int MODE, bool EXT, int KA>
 __global__ __launch_bounds__(PBLOCK) void policy_rollout_kernel(const StepArgs a, const PolicyArgs pa)
 {
-    constexpr bool INTEG = false, REFF = false;
+    constexpr bool INTEG = false, REFF = false, SPLIT = false;
     const IntegArgs ia{};
     const FilterArgs fa{};
 #include "dpenv_policy_rollout_body.inc"
@@ -71,7 +71,7 @@ __global__ __launch_bounds__(PBLOCK) void policy_rollout_kernel(const StepArgs a
 template <int MODE, bool EXT, int KA>
 __global__ __launch_bounds__(PBLOCK) void policy_rollout_integ_kernel(const StepArgs a, const PolicyArgs pa, const IntegArgs ia)
 {
-    constexpr bool INTEG = true, REFF = false;
+    constexpr bool INTEG = true, REFF = false, SPLIT = false;
     const FilterArgs fa{};
 #include "dpenv_policy_rollout_body.inc"
 }
@@ -80,7 +80,7 @@ __global__ __launch_bounds__(PBLOCK) void policy_rollout_integ_kernel(const Step
 template <int MODE, bool EXT, int KA, bool INTEG_>
 __global__ __launch_bounds__(PBLOCK) void policy_rollout_reff_kernel(const StepArgs a, const PolicyArgs pa, const IntegArgs ia, const FilterArgs fa)
 {
-    constexpr bool INTEG = INTEG_, REFF = true;
+    constexpr bool INTEG = INTEG_, REFF = true, SPLIT = false;
 #include "dpenv_policy_rollout_body.inc"
 }
 

@@ -985,6 +985,32 @@ __device__ __forceinline__ void mlp_eval_x(const uint4* Wh, const uint4* Wl, con
     else output(X);
 }
 
+struct SplitNets {                  // the split image of both networks in LDS (stage_weights)
+    const uint4 *Wpi_h, *Wv_h, *Wpi_l, *Wv_l;
+    const float *Bpi, *Bv;
+};
+
+__device__ __forceinline__ SplitNets split_nets(const uint4* lds_w, const PolicyArgs& pa)
+{
+    SplitNets s;
+    s.Wpi_h = lds_w;
+    s.Wv_h = lds_w + pa.nent;
+    s.Wpi_l = lds_w + 2 * pa.nent;
+    s.Wv_l = lds_w + 3 * pa.nent;
+    s.Bpi = (const float*)(lds_w + 4 * pa.nent);
+    s.Bv = s.Bpi + pa.nblk * 32;
+    return s;
+}
+
+// the critic in the arithmetic the descriptor asked for: split-f16 like the actor (DPENV_POLICY_F32), or plain f16 on the HIGH
+// image and the high parts of the input - exactly the F16 mode's critic, bit for bit (DPENV_POLICY_F32_ACTOR)
+template <int KA>
+__device__ __forceinline__ void critic_eval(const SplitNets& nets, const PolicyArgs& pa, const SplitIn& in, float leak, float out[8])
+{
+    if (pa.critic_f16) mlp_eval<KA>(nets.Wv_h, nets.Bv, pa.n_hidden, in.h0, in.h1, (_Float16)leak, out);
+    else mlp_eval_x<KA>(nets.Wv_h, nets.Wv_l, nets.Bv, pa.n_hidden, in, leak, out);
+}
+
 }  // namespace dpenv
 
 #endif

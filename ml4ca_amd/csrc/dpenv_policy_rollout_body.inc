@@ -1,25 +1,27 @@
-// dpenv_policy_rollout_body.inc - the body of policy_rollout_kernel, policy_rollout_integ_kernel and policy_rollout_reff_kernel
-// (dpenv_policy.hip), included into each.  In scope: a (StepArgs), pa (PolicyArgs), ia (IntegArgs), fa (FilterArgs) and the compile-time
-// INTEG and REFF; MODE, EXT, KA are the kernel's template arguments.
+// dpenv_policy_rollout_body.inc - the body of the one-wave closed loop, included into policy_rollout_kernel, policy_rollout_integ_kernel
+// and policy_rollout_reff_kernel (dpenv_policy.hip: f16, SPLIT = false) and their policy_rollout_x* twins (dpenv_policy_x.hip: split-f16,
+// SPLIT = true).  In scope: a (StepArgs), pa (PolicyArgs), ia (IntegArgs), fa (FilterArgs) and the compile-time INTEG, REFF and SPLIT.
 // The body is spliced into each __global__ function rather than called as a device function: inlined through a device function the
-// INTEG = false kernel came out as another instruction stream than the kernel had before the integral action existed.
+// INTEG = false kernel came out as another instruction stream than the kernel had before the integral action existed.  Lambdas for the
+// arithmetic-dependent parts changed every kernel's instruction stream too, so those are `if constexpr (SPLIT)` blocks: the network
+// evaluation, and the rows - staged through the wave's LDS area in f16; per lane in split, whose network image leaves no room for that.
+// Even dead address arithmetic changed it: neither form computes the other's lds_io, row-block strides or row.
     constexpr int A = ModeTraits<MODE>::A;
     constexpr int OD = EXT ? 9 : 6;
     extern __shared__ uint4 lds_dyn[];
     uint4* lds_w = lds_dyn;
-    float* lds_io = (float*)lds_dyn + policy_lds_io_offset_floats(pa) + (threadIdx.x >> 6) * (64 * 9);
+    float* lds_io = SPLIT ? nullptr : (float*)lds_dyn + policy_lds_io_offset_floats(pa) + (threadIdx.x >> 6) * (64 * 9);
     stage_weights(lds_w, pa);
-    const uint4* Wpi = lds_w;
-    const uint4* Wv = lds_w + pa.nent;
-    const float* Bpi = (const float*)(lds_dyn + 2 * pa.nent);
-    const float* Bv = Bpi + pa.nblk * 32;
-    const _Float16 leak = (_Float16)pa.leak;
+    const uint4 *Wpi = lds_w, *Wv = lds_w + pa.nent;            // the f16 image: Wpi, Wv, then the biases
+    const float *Bpi = (const float*)(lds_dyn + 2 * pa.nent), *Bv = Bpi + pa.nblk * 32;
+    const SplitNets nets = split_nets(lds_dyn, pa);              // the split image
+    const float leak = pa.leak;
 
     const int lane = threadIdx.x & 63;
     const int n = a.n;
     const int wave0 = blockIdx.x * PBLOCK + (threadIdx.x & ~63);
     if (wave0 >= n) return;                                      // whole wave out of range (uniform)
-    const int i = wave0 + lane;
+    const int i = SPLIT ? (int)(blockIdx.x * PBLOCK + threadIdx.x) : wave0 + lane;
     const bool live = i < n;
     const int il = live ? i : n - 1;
 
@@ -41,8 +43,8 @@
     const bool draw = pa.noise == nullptr && pa.sample != 0;
     uint32_t nctr = draw ? a.noise_ctr[il] : 0u;
 
-    const int64_t stride_a = (int64_t)n * A, stride_o = (int64_t)n * OD;
-    const int64_t w_a = (int64_t)wave0 * A, w_o = (int64_t)wave0 * OD;
+    const int64_t stride_a = SPLIT ? 0 : (int64_t)n * A, stride_o = SPLIT ? 0 : (int64_t)n * OD;
+    const int64_t w_a = SPLIT ? 0 : (int64_t)wave0 * A, w_o = SPLIT ? 0 : (int64_t)wave0 * OD;     // f16: the wave's slice of a [T][n][.] block
     const int64_t rem_a = stride_a - w_a, rem_o = stride_o - w_o;
 
     // observation of the current state = policy input of step 0 (ENV:196-205), and its value
@@ -68,23 +70,45 @@
         reff_row(fa, 0, n, i, live, s.refN, s.refE, s.refPsi);  // the reference o_0 was formed against
         s.refN = fs.x[0][0]; s.refE = fs.x[1][0]; s.refPsi = fs.x[2][0];   // the last launch's pending new_ref is in force from step 0
     }
-    half8 in0, in1;
-    obs_to_frags<OD>(o, in0, in1);
+    half8 in0, in1;                                              // f16 network input
+    SplitIn in;                                                  // split network input
     float vout[8], mu[8];
-    mlp_eval2<KA>(Wpi, Wv, Bpi, Bv, pa.n_hidden, in0, in1, leak, mu, vout);     // actor and critic of o_0
+    if constexpr (SPLIT) {                                       // actor and critic of o_0
+        obs_to_frags_x<OD>(o, in);
+        mlp_eval_x<KA>(nets.Wpi_h, nets.Wpi_l, nets.Bpi, pa.n_hidden, in, leak, mu);
+        critic_eval<KA>(nets, pa, in, leak, vout);
+    } else {
+        obs_to_frags<OD>(o, in0, in1);
+        mlp_eval2<KA>(Wpi, Wv, Bpi, Bv, pa.n_hidden, in0, in1, (_Float16)leak, mu, vout);
+    }
     float v_t = vout[0];
 
-    float pre[A];
-    if (pa.noise) load_rows<A, 64>(pa.noise + w_a, rem_a, lane, pre);
+    float pre[A];                                                // f16: the given noise row of the next step
+    if (!SPLIT && pa.noise) load_rows<A, 64>(pa.noise + w_a, rem_a, lane, pre);
     int next_switch = 0;
     for (int t = 0; t < pa.T; ++t) {
+        const int64_t row = SPLIT ? (int64_t)t * n + i : 0;      // split: this lane's row of a [T][n][.] block
         // ---- store the policy input row; the actor's mean for it is already there (joint evaluation) -------------
-        wave_store_rows<OD>(lds_io, pa.obs_out, (int64_t)t * stride_o + w_o, rem_o, o, lane, a.obs_bf16 != 0);
+        if constexpr (SPLIT) { if (live) store_row_direct<OD>(pa.obs_out, row, o, a.obs_bf16 != 0); }
+        else wave_store_rows<OD>(lds_io, pa.obs_out, (int64_t)t * stride_o + w_o, rem_o, o, lane, a.obs_bf16 != 0);
         if constexpr (INTEG) integ_row(ia, t, n, i, live, ig);
         // ---- sample: a = mu + std * xi (core.py:85), log-likelihood (core.py:42-46) -----------
-        float act[A];
-        float logp;
-        if (pa.noise) {
+        float act[A], logp;
+        if constexpr (SPLIT) {                                   // split: the given noise row per lane
+            if (pa.noise || draw) {
+                float xi[A];
+                if (pa.noise) {
+#pragma unroll
+                    for (int k = 0; k < A; ++k) xi[k] = pa.noise[((int64_t)t * n + il) * A + k];
+                } else {
+                    policy_noise<A>(a, a.env_id_base + i, nctr, xi);
+                    ++nctr;
+                }
+                logp = sample_action<A>(pc, mu, xi, act);
+            } else {
+                logp = mean_action<A>(pc, mu, act);
+            }
+        } else if (pa.noise) {                                   // f16: the given noise row through the staging, the next one fetched
             float xi[A];
             wave_rows_from_regs<A>(lds_io, pre, xi, lane);
             if (t + 1 < pa.T) load_rows<A, 64>(pa.noise + (int64_t)(t + 1) * stride_a + w_a, rem_a, lane, pre);
@@ -97,7 +121,8 @@
         } else {
             logp = mean_action<A>(pc, mu, act);
         }
-        wave_store_rows<A>(lds_io, pa.act_out, (int64_t)t * stride_a + w_a, rem_a, act, lane);
+        if constexpr (SPLIT) { if (live) store_row_direct<A>(pa.act_out, row, act, false); }
+        else wave_store_rows<A>(lds_io, pa.act_out, (int64_t)t * stride_a + w_a, rem_a, act, lane);
 
         // ---- env.step ------------------------------------------------------------------------
         bool has_ref = false;
@@ -135,10 +160,15 @@
         // run once more on the pre-reset observation of the wave before the finished envs are re-drawn.
         float v_pre = 0.0f;
         if (__ballot(do_reset) != 0ull) {                       // wave-uniform
-            // only a CUT episode (time limit) bootstraps with V of its last observation; a terminated one with 0 (ppo.py:311)
+            // only if an env of the wave was CUT (time limit): a terminated one bootstraps with 0 (ppo.py:311), as most do with termination on
             if (__ballot(do_reset && (out.d & DONE_TERMINAL) == 0u) != 0ull) {
-                obs_to_frags<OD>(o, in0, in1);
-                mlp_eval<KA>(Wv, Bv, pa.n_hidden, in0, in1, leak, vout);
+                if constexpr (SPLIT) {
+                    obs_to_frags_x<OD>(o, in);
+                    critic_eval<KA>(nets, pa, in, leak, vout);
+                } else {
+                    obs_to_frags<OD>(o, in0, in1);
+                    mlp_eval<KA>(Wv, Bv, pa.n_hidden, in0, in1, (_Float16)leak, vout);
+                }
                 v_pre = vout[0];
             }
             if (do_reset) {
@@ -156,8 +186,14 @@
                 }
             }
         }
-        obs_to_frags<OD>(o, in0, in1);
-        mlp_eval2<KA>(Wpi, Wv, Bpi, Bv, pa.n_hidden, in0, in1, leak, mu, vout);
+        if constexpr (SPLIT) {
+            obs_to_frags_x<OD>(o, in);
+            mlp_eval_x<KA>(nets.Wpi_h, nets.Wpi_l, nets.Bpi, pa.n_hidden, in, leak, mu);
+            critic_eval<KA>(nets, pa, in, leak, vout);
+        } else {
+            obs_to_frags<OD>(o, in0, in1);
+            mlp_eval2<KA>(Wpi, Wv, Bpi, Bv, pa.n_hidden, in0, in1, (_Float16)leak, mu, vout);
+        }
         const float v_next = do_reset ? v_pre : vout[0];
         const float v_new = vout[0];
         // bootstrap value at a path end (ppo.py:311): 0 if the env terminated, V(o) if only the time limit or the
@@ -167,17 +203,26 @@
         const float boot = (ended && !terminal) ? v_next : 0.0f;
 
         if (live) {
-            (pa.rew + (int64_t)t * n)[(unsigned)i] = out.reward;
-            (pa.done + (int64_t)t * n)[(unsigned)i] = (uint8_t)out.d;
-            (pa.val + (int64_t)t * n)[(unsigned)i] = v_t;
-            (pa.logp + (int64_t)t * n)[(unsigned)i] = logp;
-            (pa.boot + (int64_t)t * n)[(unsigned)i] = boot;
+            if constexpr (SPLIT) {
+                pa.rew[row] = out.reward;
+                pa.done[row] = (uint8_t)out.d;
+                pa.val[row] = v_t;
+                pa.logp[row] = logp;
+                pa.boot[row] = boot;
+            } else {
+                (pa.rew + (int64_t)t * n)[(unsigned)i] = out.reward;
+                (pa.done + (int64_t)t * n)[(unsigned)i] = (uint8_t)out.d;
+                (pa.val + (int64_t)t * n)[(unsigned)i] = v_t;
+                (pa.logp + (int64_t)t * n)[(unsigned)i] = logp;
+                (pa.boot + (int64_t)t * n)[(unsigned)i] = boot;
+            }
         }
         v_t = v_new;
     }
     // observation after the last step (policy input of the next launch) and final state
-    wave_store_rows<OD>(lds_io, pa.last_obs, w_o, rem_o, o, lane, a.obs_bf16 != 0);
+    if constexpr (!SPLIT) wave_store_rows<OD>(lds_io, pa.last_obs, w_o, rem_o, o, lane, a.obs_bf16 != 0);    // the whole wave
     if (live) {
+        if constexpr (SPLIT) store_row_direct<OD>(pa.last_obs, i, o, a.obs_bf16 != 0);
         pa.last_val[i] = v_t;
         store_env(a, i, s, rf_dirty);
         if (EXT) a.S3[i] = make_float4(o[6], o[7], o[8], 0.0f);

@@ -11,32 +11,6 @@
 
 namespace dpenv {
 
-struct SplitNets {
-    const uint4 *Wpi_h, *Wv_h, *Wpi_l, *Wv_l;
-    const float *Bpi, *Bv;
-};
-
-__device__ __forceinline__ SplitNets split_nets(const uint4* lds_w, const PolicyArgs& pa)
-{
-    SplitNets s;
-    s.Wpi_h = lds_w;
-    s.Wv_h = lds_w + pa.nent;
-    s.Wpi_l = lds_w + 2 * pa.nent;
-    s.Wv_l = lds_w + 3 * pa.nent;
-    s.Bpi = (const float*)(lds_w + 4 * pa.nent);
-    s.Bv = s.Bpi + pa.nblk * 32;
-    return s;
-}
-
-// the critic in the arithmetic the descriptor asked for: split-f16 like the actor (DPENV_POLICY_F32), or plain f16 on the HIGH
-// image and the high parts of the input - exactly the F16 mode's critic, bit for bit (DPENV_POLICY_F32_ACTOR)
-template <int KA>
-__device__ __forceinline__ void critic_eval(const SplitNets& nets, const PolicyArgs& pa, const SplitIn& in, float leak, float out[8])
-{
-    if (pa.critic_f16) mlp_eval<KA>(nets.Wv_h, nets.Bv, pa.n_hidden, in.h0, in.h1, (_Float16)leak, out);
-    else mlp_eval_x<KA>(nets.Wv_h, nets.Wv_l, nets.Bv, pa.n_hidden, in, leak, out);
-}
-
 template <int OD, int A, int KA>
 __global__ __launch_bounds__(PBLOCK) void policy_forward_x_kernel(const PolicyArgs pa, const float* obs, float* mu_out, float* v_out, int n)
 {
@@ -61,32 +35,31 @@ __global__ __launch_bounds__(PBLOCK) void policy_forward_x_kernel(const PolicyAr
     }
 }
 
-// the rollout loop of policy_rollout_kernel (dpenv_policy.hip) with the exact network evaluation; rows, bootstrap values and
-// auto-reset handling are identical
+// the one-wave closed loop of dpenv_policy.hip with the exact network evaluation (dpenv_policy_rollout_body.inc, SPLIT = true)
 template <int MODE, bool EXT, int KA>
 __global__ __launch_bounds__(PBLOCK) void policy_rollout_x_kernel(const StepArgs a, const PolicyArgs pa)
 {
-    constexpr bool INTEG = false, REFF = false;
+    constexpr bool INTEG = false, REFF = false, SPLIT = true;
     const IntegArgs ia{};
     const FilterArgs fa{};
-#include "dpenv_policy_rollout_x_body.inc"
+#include "dpenv_policy_rollout_body.inc"
 }
 
 // INTEG: the deployed node's integral action (IntegArgs, dpenv_set_integral_action)
 template <int MODE, bool EXT, int KA>
 __global__ __launch_bounds__(PBLOCK) void policy_rollout_x_integ_kernel(const StepArgs a, const PolicyArgs pa, const IntegArgs ia)
 {
-    constexpr bool INTEG = true, REFF = false;
+    constexpr bool INTEG = true, REFF = false, SPLIT = true;
     const FilterArgs fa{};
-#include "dpenv_policy_rollout_x_body.inc"
+#include "dpenv_policy_rollout_body.inc"
 }
 
 // REFF: the setpoint reference filter (FilterArgs, dpenv_set_reference_filter), with the integral action if INTEG_
 template <int MODE, bool EXT, int KA, bool INTEG_>
 __global__ __launch_bounds__(PBLOCK) void policy_rollout_x_reff_kernel(const StepArgs a, const PolicyArgs pa, const IntegArgs ia, const FilterArgs fa)
 {
-    constexpr bool INTEG = INTEG_, REFF = true;
-#include "dpenv_policy_rollout_x_body.inc"
+    constexpr bool INTEG = INTEG_, REFF = true, SPLIT = true;
+#include "dpenv_policy_rollout_body.inc"
 }
 
 }  // namespace dpenv

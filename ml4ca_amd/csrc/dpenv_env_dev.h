@@ -1028,6 +1028,40 @@ __device__ __forceinline__ void store_env(const StepArgs& a, int i, const Env& s
     if (rf_dirty) a.RF[i] = make_float4(s.refN, s.refE, s.refPsi, s.ang[0]);
 }
 
+// ---- buffer-resource I/O (the lean step, step_kernel<.., LEAN>) ---------------------------------------------------------
+// A stream is a 128-bit descriptor in SGPRs (base, byte count) plus a 32-bit per-lane byte offset: one VGPR offset serves every
+// stream of the same element size, and no 64-bit address is formed per lane.  The hardware range check against the byte count
+// does what the clamped index and the `if (live)` guards do in the general kernel: a load past the end returns 0, a store past
+// it is dropped.  Every stream's byte count is a whole number of its elements, so no access straddles the end.  The caller
+// keeps every byte count and offset below 2^31 (dev::launch_step).
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t buf_rsrc(const void* p, uint32_t bytes)
+{
+    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), 0, (int)bytes, 0x00020000);
+}
+__device__ __forceinline__ float buf_load1(__amdgpu_buffer_rsrc_t r, uint32_t off)
+{
+    return __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(r, off, 0, 0));
+}
+__device__ __forceinline__ float4 buf_load4(__amdgpu_buffer_rsrc_t r, uint32_t off)
+{
+    const u32x4 q = __builtin_amdgcn_raw_buffer_load_b128(r, off, 0, 0);
+    return make_float4(__uint_as_float(q.x), __uint_as_float(q.y), __uint_as_float(q.z), __uint_as_float(q.w));
+}
+__device__ __forceinline__ void buf_store1(__amdgpu_buffer_rsrc_t r, uint32_t off, float x)
+{
+    __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(x), r, off, 0, 0);
+}
+__device__ __forceinline__ void buf_store4(__amdgpu_buffer_rsrc_t r, uint32_t off, float x, float y, float z, float w)
+{
+    const u32x4 q = {__float_as_uint(x), __float_as_uint(y), __float_as_uint(z), __float_as_uint(w)};
+    __builtin_amdgcn_raw_buffer_store_b128(q, r, off, 0, 0);
+}
+__device__ __forceinline__ void buf_store_u8(__amdgpu_buffer_rsrc_t r, uint32_t off, uint8_t x)
+{
+    __builtin_amdgcn_raw_buffer_store_b8(x, r, off, 0, 0);
+}
+
 }  // namespace dpenv
 
 #endif

@@ -88,11 +88,81 @@ __device__ __forceinline__ void reset_from_lds(const float* lds, int lane, Env& 
     s.sn = lds[15 * 64 + lane]; s.cs = lds[16 * 64 + lane];
 }
 
+// The lean step (step_kernel<.., LEAN>): the default env.step alone - vessel from the kernel arguments, no auto-reset, no current,
+// no reward parts, no final_obs, no lagged thrust columns (S3), f32 [n][dim] rows in and out; dev::launch_step picks it when the
+// handle and the I/O say so.  Same functions on the same inputs as the general body below, in the same order of loads and stores
+// (all loads, one sched_barrier; state and done, then the observation rows, the reward last), every row bit for bit; what is
+// gone is the per-lane 64-bit addressing, the clamped index, the exec-mask guards around the stores and the run-time tests of the
+// features above (buffer descriptors: their range check drops the dead lanes' stores and zeroes their loads).
+template <int MODE, bool EXT>
+__device__ __forceinline__ void step_lean(const StepArgs& a, float* lds_io)
+{
+    constexpr int A = ModeTraits<MODE>::A;
+    constexpr int OD = EXT ? 9 : 6;
+    const int tid = threadIdx.x;
+    const uint32_t n = (uint32_t)a.n;
+    const uint32_t i = blockIdx.x * BLOCK + tid;
+    const uint32_t o16 = i * 16u, o4 = i * 4u;                                     // the float4 streams; the float ones
+    const uint32_t oact = (blockIdx.x * (BLOCK * A) + tid) * 4u;                   // element j * BLOCK + tid of the block's action rows
+    const uint32_t oobs = (blockIdx.x * (BLOCK * OD) + tid) * 4u;                  // the same of its observation rows
+    const __amdgpu_buffer_rsrc_t rS0 = buf_rsrc(a.S0, n * 16u), rS1 = buf_rsrc(a.S1, n * 16u), rS2 = buf_rsrc(a.S2, n * 16u),
+                                 rRF = buf_rsrc(a.RF, n * 16u), rAct = buf_rsrc(a.action, n * (4u * A));
+
+    // ---- every load up front (the order of the general body) ----
+    float act[A];
+#pragma unroll
+    for (int j = 0; j < A; ++j) act[j] = buf_load1(rAct, oact + j * (4u * BLOCK));
+    Env s;
+    {
+        const float4 s0 = buf_load4(rS0, o16), s1 = buf_load4(rS1, o16), s2 = buf_load4(rS2, o16), rf = buf_load4(rRF, o16);
+        s.N = s0.x; s.E = s0.y; s.psi = s0.z; s.u = s0.w; s.v = s1.x; s.r = s1.y;
+        s.ang[0] = rf.w; s.ang[1] = s1.z; s.ang[2] = s1.w;
+        s.pt[0] = s2.x; s.pt[1] = s2.y; s.pt[2] = s2.z; s.steps = __float_as_int(s2.w);
+        s.refN = rf.x; s.refE = rf.y; s.refPsi = rf.z;
+    }
+    const bool has_ref = a.new_ref != nullptr;                                     // launch-uniform: the bench's graph switches setpoints in it
+    float nrN = 0.0f, nrE = 0.0f, nrP = 0.0f;
+    if (has_ref) {
+        const __amdgpu_buffer_rsrc_t rNR = buf_rsrc(a.new_ref, n * 12u);          // [3][n]
+        nrN = buf_load1(rNR, o4); nrE = buf_load1(rNR, o4 + n * 4u); nrP = buf_load1(rNR, o4 + n * 8u);
+    }
+    __builtin_amdgcn_sched_barrier(0);
+    sincos_lean(s.psi, s.sn, s.cs);
+#pragma unroll
+    for (int j = 0; j < A; ++j) lds_io[j * BLOCK + tid] = act[j];
+    lds_order<BLOCK>();
+#pragma unroll
+    for (int k = 0; k < A; ++k) act[k] = lds_io[tid * A + k];
+    const Vessel ve = vessel_from_args(a.v0);
+
+    StepOut out;
+    StepRest rest;
+    env_step_chain<MODE, EXT, false>(a, ve, s, act, has_ref, nrN, nrE, nrP, false, 0.0f, 0.0f, out, rest, IL_NONE);
+    // ---- state and done bits, then the observation rows, while the reward is computed; the reward last ----
+    buf_store4(rS0, o16, s.N, s.E, s.psi, s.u);
+    buf_store4(rS1, o16, s.v, s.r, s.ang[1], s.ang[2]);
+    buf_store4(rS2, o16, s.pt[0], s.pt[1], s.pt[2], __int_as_float(s.steps));
+    if (has_ref || MODE == MODE_FULL) buf_store4(rRF, o16, s.refN, s.refE, s.refPsi, s.ang[0]);
+    buf_store_u8(buf_rsrc(a.done, n), i, (uint8_t)out.d);
+    __builtin_amdgcn_sched_barrier(0);
+    lds_order<BLOCK>();
+#pragma unroll
+    for (int k = 0; k < OD; ++k) lds_io[tid * OD + k] = out.o[k];
+    lds_order<BLOCK>();
+    const __amdgpu_buffer_rsrc_t rObs = buf_rsrc(a.obs, n * (4u * OD));
+#pragma unroll
+    for (int j = 0; j < OD; ++j) buf_store1(rObs, oobs + j * (4u * BLOCK), lds_io[j * BLOCK + tid]);
+    __builtin_amdgcn_sched_barrier(0);
+    env_step_finish<MODE, EXT, false>(a, s, act, rest, true, out);
+    buf_store1(buf_rsrc(a.rew, n * 4u), o4, out.reward);
+}
+
 // VES (dpenv_dev.h VES_*): where a lane's vessel comes from - kernel arguments, the LDS-staged class table, or its own per-env block
 // (straight into registers, or through an LDS image filled by LDS-DMA: the A/B SURVEY section 7 asks for, bench.py `vessel_classes.per_env`).
 // (Rejected forms of this kernel - loads not hoisted above the first branch, observation rows before the state stores, no early stores,
 // the state streams repeated as preloaded scalar arguments - were A/B switches until round 6: tools/ab/README.md, profiles/LAB_NOTES.md.)
-template <int MODE, bool EXT, int VES, bool RESETW = false>
+// LEAN: the default step alone (step_lean above).
+template <int MODE, bool EXT, int VES, bool RESETW = false, bool LEAN = false>
 __global__ __launch_bounds__(RESETW ? 2 * BLOCK : BLOCK) void step_kernel(const StepArgs a)
 {
     const float4 *pS0 = a.S0, *pS1 = a.S1, *pS2 = a.S2, *pRF = a.RF;
@@ -112,7 +182,12 @@ __global__ __launch_bounds__(RESETW ? 2 * BLOCK : BLOCK) void step_kernel(const 
     __shared__ float4 lds_pe[VES == VES_ENV_LDS ? ENV_GROUPS * 64 : 1];
     __shared__ float lds_rst[RESETW ? (CURR ? RESETW_FIELDS_RND : RESETW_FIELDS) * 64 : 1];
     __shared__ uint32_t lds_fin[RESETW ? 64 : 1];      // env wave -> reset wave: this env finished and is being re-drawn
+    static_assert(!LEAN || (VES == VES_ARGS && !RESETW), "the lean step takes its vessel from the arguments and has no reset wave");
 
+    if (LEAN) {
+        step_lean<MODE, EXT>(a, lds_io);
+        return;
+    }
     if (RESETW && threadIdx.x >= BLOCK) {
         const int lane = threadIdx.x - BLOCK;
         reset_wave<MODE>(a, lds_rst, lane, blockIdx.x);
@@ -1127,17 +1202,36 @@ static bool vessel_source_ok(const StepArgs& a, int ves)
     return !(ves >= VES_ENV_VGPR && ves <= VES_ENV_RND && !a.env_tab) && (ves == VES_ARGS_LOSS) == (a.loss_on == LOSS_SHARED);
 }
 
+// the lean step serves the launch: vessel from the arguments, none of the features it compiles out, f32 AoS rows, and every byte
+// count of its buffer descriptors (the widest: n rows of 9 floats) below 2^31
+static bool step_lean_ok(const StepArgs& a, int ves)
+{
+#ifdef DPENV_STEP_TRACE
+    return false;                                          // (the diagnostic build traces the general body)
+#else
+    return ves == VES_ARGS && !a.auto_reset && !a.final_obs && !a.parts && !a.cur_vc && !a.current_drift && !a.S3 && !a.obs_bf16 &&
+           a.obs_layout == LAYOUT_AOS && a.action_layout == LAYOUT_AOS && (int64_t)a.n * 36 < ((int64_t)1 << 31);
+#endif
+}
+
 hipError_t dev::launch_step(const StepArgs* a, int mode, int ext, int ves, int reset_wave, hipStream_t s)
 {
     if (!vessel_source_ok(*a, ves)) return hipErrorInvalidValue;
     const dim3 grid((a->n + BLOCK - 1) / BLOCK);
     // auto-reset on: a second wave per workgroup prepares the re-draws beside the plant loop (RESETW above)
     const bool two = a->auto_reset && BLOCK == 64 && reset_wave;
-    return with_mode_ext(mode, ext, [&](auto M, auto E) { return with_ves(ves, [&](auto V) {
-        if (two) hipLaunchKernelGGL((step_kernel<M, E, step_ves(V), BLOCK == 64>), grid, dim3(2 * BLOCK), 0, s, *a);
-        else hipLaunchKernelGGL((step_kernel<M, E, step_ves(V)>), grid, dim3(BLOCK), 0, s, *a);
-        return hipGetLastError();
-    }); });
+    const bool lean = step_lean_ok(*a, ves);
+    return with_mode_ext(mode, ext, [&](auto M, auto E) {
+        if (lean) {
+            hipLaunchKernelGGL((step_kernel<M, E, VES_ARGS, false, true>), grid, dim3(BLOCK), 0, s, *a);
+            return hipGetLastError();
+        }
+        return with_ves(ves, [&](auto V) {
+            if (two) hipLaunchKernelGGL((step_kernel<M, E, step_ves(V), BLOCK == 64>), grid, dim3(2 * BLOCK), 0, s, *a);
+            else hipLaunchKernelGGL((step_kernel<M, E, step_ves(V)>), grid, dim3(BLOCK), 0, s, *a);
+            return hipGetLastError();
+        });
+    });
 }
 
 hipError_t dev::launch_pack_env_vessels(const float* raw, int64_t p_stride, int64_t i_stride, float4* tab, uint32_t* loss_flag, int stride, int n,

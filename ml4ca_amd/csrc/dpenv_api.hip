@@ -1110,20 +1110,6 @@ extern "C" int dpenv_policy_forward(dpenv_handle h, const float* obs, float* mu_
     return mark_policy_read(h, s);
 }
 
-#ifdef DPENV_WS_SELFCHECK
-// diagnostic builds only (tools/ws_selfcheck.py): device buffer of mismatch records, see policy_rollout_ws_kernel
-static uint32_t* g_selfcheck_buf = nullptr;
-extern "C" int dpenv_debug_set_buffer(void* p) { g_selfcheck_buf = (uint32_t*)p; return 0; }
-extern "C" hipError_t dpenv_dev_launch_pk_probe(const PolicyArgs* pa, uint32_t* out, float* sink, int blocks, int iters, int variant, int partner,
-                                                hipStream_t s);
-extern "C" int dpenv_debug_pk_probe(dpenv_handle h, void* out, void* sink, int blocks, int iters, int variant, int partner)
-{
-    if (!h || !h->has_policy) return DPENV_EINVAL;
-    HIP_TRY(h, dpenv_dev_launch_pk_probe(&h->pol, (uint32_t*)out, (float*)sink, blocks, iters, variant, partner, nullptr));
-    return DPENV_OK;
-}
-#endif
-
 // Which closed-loop kernel runs: the one place that decides.  The two-wave form runs where its launcher has the instantiation (the ws_*
 // predicates of dpenv_dev.h, the same ones it instantiates by); everything else runs the one-wave kernels - the same rows bit for bit, the
 // hull / current re-draw and the table's thrust loss a run-time switch there, which know the thrust loss through the table alone.
@@ -1181,9 +1167,6 @@ static int policy_rollout_impl(dpenv_handle h, const dpenv_policy_rollout_io* io
     if (pa.reset_at_end && !h->cfg.auto_reset)
         return fail(h, DPENV_EINVAL, "reset_at_end re-draws every env with the training sampler: it needs config.auto_reset");
     for (int k = 0; k < io->n_switch; ++k) pa.switch_step[k] = io->switch_step[k];
-#ifdef DPENV_WS_SELFCHECK
-    pa.dbg = g_selfcheck_buf;
-#endif
     IntegArgs ia = h->integ;
     ia.out = integ_out;
     FilterArgs fa = h->reff;

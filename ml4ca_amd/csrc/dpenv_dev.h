@@ -7,13 +7,9 @@
 #include <stdint.h>
 #include <type_traits>
 
-#ifndef DPENV_BLOCK
-#define DPENV_BLOCK 64    // threads per workgroup = one wave64; one lane per environment; LDS staging is wave-private
-#endif
-
 namespace dpenv {
 
-constexpr int BLOCK = DPENV_BLOCK;
+constexpr int BLOCK = 64;         // threads per workgroup = one wave64; one lane per environment; LDS staging is wave-private
 constexpr int RBLOCK = 64;        // rollout kernel: one wave per workgroup (wave-private LDS transposes)
 constexpr int MAX_SWITCH = 8;
 constexpr int MAX_CLASSES = 64;
@@ -187,7 +183,6 @@ struct PolicyArgs {
     int32_t n_switch;
     int32_t switch_step[MAX_SWITCH];
     const float* refs;
-    uint32_t* dbg;            // diagnostic builds only (DPENV_WS_SELFCHECK): event records, NULL otherwise
 };
 
 // the deployed RL node's body-frame integral action in the closed loop (dpenv_set_integral_action; rl_allocator.py:252-273 of the
@@ -216,11 +211,6 @@ struct PackNet {
     int32_t n_layers, in_dim, H, out_dim;
 };
 
-// which arithmetics get a critic wave of their own (ROLES = 3) in the 128-env geometry of the two-wave closed loop: bit 0 f16, bit 1 all
-// exact, bit 2 exact actor (dpenv_policy_ws.h has the measurements)
-#ifndef DPENV_WS_CRITIC_WAVE
-#define DPENV_WS_CRITIC_WAVE 6
-#endif
 constexpr int POLICY_WS_MAILBOX_BYTES = 4 * (64 * 9 * 5 + 64 * 4 + 64) * 4;   // two-wave form: four groups of mailboxes
 constexpr int POLICY_WS_MAILBOX_X_BYTES = 4 * (64 * 9 * 4 + 64 * 4 + 64) * 4; // the same for the split arithmetics (no row staging area)
 constexpr int PREC_F16 = 0, PREC_F32 = 1, PREC_F32_ACTOR = 2;                 // = DPENV_POLICY_* of include/dpenv.h
@@ -322,8 +312,7 @@ hipError_t launch_with_lds(void (*kernel)(P...), dim3 grid, dim3 block, size_t l
 }
 
 // ---- the instantiation set of each kernel family, stated once: its launcher instantiates what these admit, and the host routes by them ----
-// step_kernel, rollout_kernel / rollout_ws_kernel, reset_kernel: every MODE x EXT (x VES), the vessel source mapped as follows
-constexpr int step_ves(int ves) { return ves == VES_ENV_LDS && BLOCK != 64 ? VES_ENV_VGPR : ves; }   // the LDS image is one wave's
+// step_kernel, rollout_kernel / rollout_ws_kernel, reset_kernel: every MODE x EXT (x VES), the T-step kernels' vessel source mapped as follows
 constexpr int rollout_ves(int ves) { return ves == VES_ENV_LDS ? VES_ENV_VGPR : ves; }   // a T-step kernel's staging area is the register file
 // one-wave closed loop (f16 and split arithmetics), standalone forward: every MODE x EXT x KA; with the integral action:
 constexpr bool integ_one_wave(int mode, bool ext, int ka)
@@ -340,8 +329,9 @@ constexpr bool ws_integ(int mode, bool ext, int ka) { return mode == MODE_FINAL_
 // filter with the integral action
 constexpr bool reff_one_wave(int mode, bool ext, int ka) { return integ_one_wave(mode, ext, ka); }
 constexpr bool ws_reff(int mode, bool ext, int ka) { return ws_integ(mode, ext, ka); }
-// waves per 64 envs of the two-wave form: an env and a network wave, plus a critic wave where DPENV_WS_CRITIC_WAVE gives one
-constexpr int ws_roles(int prec, int groups) { return (groups == 2 && ((DPENV_WS_CRITIC_WAVE >> prec) & 1)) ? 3 : 2; }
+// waves per 64 envs of the two-wave form: an env and a network wave, plus a critic wave of its own (ROLES = 3) in the 128-env geometry
+// for the two split arithmetics, all exact and exact actor - not f16 (dpenv_policy_ws.h has the measurements)
+constexpr int ws_roles(int prec, int groups) { return (groups == 2 && prec != PREC_F16) ? 3 : 2; }
 
 // ---- launchers: called by dpenv_api.hip, defined by the translation unit that owns the kernels; not exported from libdpenv.so ----
 namespace __attribute__((visibility("hidden"))) dev {

@@ -31,14 +31,6 @@
 
 namespace dpenv {
 
-#ifdef DPENV_STEP_TRACE
-// Diagnostic builds only (tools/build_kernels_variant.sh, tools/step_placement.py; never in the product library): where and when
-// every workgroup of step_kernel ran.  Ring of DPENV_STEP_TRACE_RING launches, slot = the env's own step counter, record per
-// workgroup = {HW_REG_XCC_ID, HW_REG_HW_ID, s_memrealtime at entry, s_memrealtime after the last store was issued}.
-__device__ uint32_t* g_step_trace = nullptr;
-constexpr int STEP_TRACE_RING = 8;
-#endif
-
 // =============================================================================================
 //  env.step: one launch = one step of every env
 // =============================================================================================
@@ -47,7 +39,7 @@ constexpr int STEP_TRACE_RING = 8;
 // first observation (reset_draw + reset_apply: ~250 VALU instructions, a pure function of (seed, global env id, episode, setpoint)) -
 // and leaves the result in LDS.  It runs beside the env wave's plant loop on another SIMD of the CU, so a finished env costs the env
 // wave a barrier and seventeen LDS reads instead of 0.6 us of lone-wave instruction issue (round 4: with termination on, some wave of
-// every launch holds a finished env, so every launch paid for the draw; tools/step_placement.py).  Same
+// every launch holds a finished env, so every launch paid for the draw).  Same
 // functions on the same inputs: every row is bit-identical to the one-wave form.
 constexpr int RESETW_FIELDS = 18;       // N, E, psi | o[0..8] | pt[0..2] | sin psi, cos psi | episode counter (bits)
 constexpr int RESETW_FIELDS_RND = 20;   // the general per-env form and the shared training form (VES 4, 5): | the new episode's current V_c, beta_c
@@ -175,8 +167,6 @@ __global__ __launch_bounds__(RESETW ? 2 * BLOCK : BLOCK) void step_kernel(const 
     constexpr bool ENV_VGPR = VES == VES_ENV_VGPR || RND;
     constexpr int IL = VES == VES_ARGS_LOSS ? IL_SHARED : IL_NONE;    // (RND: the lane's own row of the table)
     constexpr bool CURR = RND || VES == VES_ARGS_LOSS;                // the forms that re-draw the current with the episode (dpenv_set_current_randomisation)
-    static_assert(!RESETW || BLOCK == 64, "the reset wave pairs with ONE env wave");
-    static_assert(VES != VES_ENV_LDS || BLOCK == 64, "the LDS-DMA image is [group][lane] of one wave");
     __shared__ float lds_io[BLOCK * 9];
     __shared__ float lds_cls[PER_CLASS ? VD_COUNT * MAX_CLASSES : 1];
     __shared__ float4 lds_pe[VES == VES_ENV_LDS ? ENV_GROUPS * 64 : 1];
@@ -214,10 +204,6 @@ __global__ __launch_bounds__(RESETW ? 2 * BLOCK : BLOCK) void step_kernel(const 
     const int n = pn;
     const bool live = i < n;
     const int il = live ? i : n - 1;   // dead lanes shadow the last env and never store
-#ifdef DPENV_STEP_TRACE
-    const uint64_t trace_t0 = wall_clock64();
-#endif
-
     // ---- issue all global loads up front ------------------------------------------------------
     float act[A];
     if (playout == LAYOUT_AOS) {
@@ -289,11 +275,7 @@ __global__ __launch_bounds__(RESETW ? 2 * BLOCK : BLOCK) void step_kernel(const 
     // third state stream (commands and step counter: functions of the action alone) BEFORE the plant as well makes it 5.06 us: vmcnt counts
     // in order, so every later wait for a load then waits for that store too.  With auto-reset a finished env's state and row are the new
     // episode's: everything is stored after the re-draw, below.
-#ifdef DPENV_STEP_TRACE
-    const bool early = false;                              // (the diagnostic build takes its end-of-wave time stamp on the common path)
-#else
     const bool early = !RESETW && !a.auto_reset;           // launch-uniform
-#endif
     if (early) {
         if (live) {
             if (EXT && a.S3) a.S3[i] = make_float4(out.o[6], out.o[7], out.o[8], 0.0f);      // (see the stores below)
@@ -376,17 +358,6 @@ __global__ __launch_bounds__(RESETW ? 2 * BLOCK : BLOCK) void step_kernel(const 
     // written to LDS first and the state stores issued while it lands: 4.941)
     __builtin_amdgcn_sched_barrier(0);
     store_obs<OD>(a, a.obs, o_next, i, live, lds_io);
-#ifdef DPENV_STEP_TRACE
-    if (tid == 0 && g_step_trace) {
-        const uint64_t t1 = wall_clock64();
-        const uint32_t slot = (uint32_t)(s.steps - 1) % STEP_TRACE_RING;      // envs of a launch without resets share their counter
-        uint32_t* rec = g_step_trace + ((size_t)slot * gridDim.x + blockIdx.x) * 4;
-        rec[0] = __builtin_amdgcn_s_getreg((31 << 11) | 20);                  // HW_REG_XCC_ID
-        rec[1] = __builtin_amdgcn_s_getreg((31 << 11) | 4);                   // HW_REG_HW_ID
-        rec[2] = (uint32_t)trace_t0;
-        rec[3] = (uint32_t)t1;
-    }
-#endif
 }
 
 // =============================================================================================
@@ -1189,13 +1160,6 @@ __device__ double g_sum_partials[2 * SUM_MAXGRID];
 // =============================================================================================
 using namespace dpenv;
 
-#ifdef DPENV_STEP_TRACE
-extern "C" int dpenv_debug_set_step_trace(void* p)      // device buffer of STEP_TRACE_RING x workgroups x 4 dwords (or NULL)
-{
-    return (int)hipMemcpyToSymbol(HIP_SYMBOL(dpenv::g_step_trace), &p, sizeof p);
-}
-#endif
-
 // the vessel source must match the arguments: a per-env form needs the table, VES_ARGS_LOSS and only it reads StepArgs.kl
 static bool vessel_source_ok(const StepArgs& a, int ves)
 {
@@ -1206,12 +1170,8 @@ static bool vessel_source_ok(const StepArgs& a, int ves)
 // count of its buffer descriptors (the widest: n rows of 9 floats) below 2^31
 static bool step_lean_ok(const StepArgs& a, int ves)
 {
-#ifdef DPENV_STEP_TRACE
-    return false;                                          // (the diagnostic build traces the general body)
-#else
     return ves == VES_ARGS && !a.auto_reset && !a.final_obs && !a.parts && !a.cur_vc && !a.current_drift && !a.S3 && !a.obs_bf16 &&
            a.obs_layout == LAYOUT_AOS && a.action_layout == LAYOUT_AOS && (int64_t)a.n * 36 < ((int64_t)1 << 31);
-#endif
 }
 
 hipError_t dev::launch_step(const StepArgs* a, int mode, int ext, int ves, int reset_wave, hipStream_t s)
@@ -1219,7 +1179,7 @@ hipError_t dev::launch_step(const StepArgs* a, int mode, int ext, int ves, int r
     if (!vessel_source_ok(*a, ves)) return hipErrorInvalidValue;
     const dim3 grid((a->n + BLOCK - 1) / BLOCK);
     // auto-reset on: a second wave per workgroup prepares the re-draws beside the plant loop (RESETW above)
-    const bool two = a->auto_reset && BLOCK == 64 && reset_wave;
+    const bool two = a->auto_reset && reset_wave;
     const bool lean = step_lean_ok(*a, ves);
     return with_mode_ext(mode, ext, [&](auto M, auto E) {
         if (lean) {
@@ -1227,8 +1187,8 @@ hipError_t dev::launch_step(const StepArgs* a, int mode, int ext, int ves, int r
             return hipGetLastError();
         }
         return with_ves(ves, [&](auto V) {
-            if (two) hipLaunchKernelGGL((step_kernel<M, E, step_ves(V), BLOCK == 64>), grid, dim3(2 * BLOCK), 0, s, *a);
-            else hipLaunchKernelGGL((step_kernel<M, E, step_ves(V)>), grid, dim3(BLOCK), 0, s, *a);
+            if (two) hipLaunchKernelGGL((step_kernel<M, E, V, true>), grid, dim3(2 * BLOCK), 0, s, *a);
+            else hipLaunchKernelGGL((step_kernel<M, E, V>), grid, dim3(BLOCK), 0, s, *a);
             return hipGetLastError();
         });
     });

@@ -57,15 +57,6 @@ __device__ __forceinline__ void ws_wait(int* p, int v)
         __builtin_amdgcn_s_sleep(2);       // x 64 cycles between polls (A/B'd in round 3: 0 / 1 / 2 / 4 within noise in both geometries)
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
 }
-#ifdef DPENV_WS_PROFILE
-#define WS_WAIT_T(acc, p, v) do { const uint64_t t0_ = __builtin_amdgcn_s_memtime(); ws_wait(p, v); acc += __builtin_amdgcn_s_memtime() - t0_; } while (0)
-#define WS_TIC(t_) const uint64_t t_ = __builtin_amdgcn_s_memtime()
-#define WS_TOC(acc, t_) acc += __builtin_amdgcn_s_memtime() - t_
-#else
-#define WS_WAIT_T(acc, p, v) ws_wait(p, v)
-#define WS_TIC(t_)
-#define WS_TOC(acc, t_)
-#endif
 
 #define WS_EVAL(W_, B_, f0_, f1_) mlp_eval<KA>(W_, B_, pa.n_hidden, f0_, f1_, leak, outv)
 //  RND: the domain randomisation's hull re-draw compiled into the reset branch (instantiated for the shipped training configuration only -
@@ -105,7 +96,7 @@ __global__ __launch_bounds__(64 * GROUPS * ROLES) void policy_rollout_ws_reff_ke
 }  // namespace dpenv
 
 // ---- host side: one launcher per arithmetic, explicitly instantiated by the translation unit that owns it -------------------------
-// Which arithmetics get the critic wave (ws_roles, DPENV_WS_CRITIC_WAVE in dpenv_dev.h) in the 128-env geometry: measured (same call,
+// Which arithmetics get the critic wave (ws_roles in dpenv_dev.h) in the 128-env geometry: measured (same call,
 // bit-identical rows, profiles/r04_critic_wave.txt; 32 768 / 8 192 envs): all exact 9.43 -> 7.85 / 9.24 -> 7.30 us per step, exact actor
 // 7.4-7.7 -> 7.3-7.45 / 7.23 -> 7.01; f16 5.20 -> 5.50 / 4.76 -> 5.03 with row staging (116 B of scratch at the 256 registers two waves on a
 // SIMD leave), 5.27 -> 5.33 / 4.79 -> 4.92 without it (no scratch): the f16 step is its chain already - so the two split arithmetics get the

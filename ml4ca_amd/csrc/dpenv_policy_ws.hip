@@ -3,15 +3,6 @@
 // Reference: rollout loop spinup/algos/tf1/ppo/ppo.py:289-322, networks core.py:29-33,80-107.
 #include "dpenv_policy_ws.h"
 
-#ifdef DPENV_WS_SELFCHECK
-namespace dpenv {
-#include "dpenv_diag.inc"      // diagnostic builds only: pk_probe_kernel (tools/ws_pk_probe.py)
-}
-using namespace dpenv;
-#define DPENV_DIAG_LAUNCHERS
-#include "dpenv_diag.inc"
-#endif
-
 namespace dpenv {
 template hipError_t dev::launch_policy_rollout_ws<PREC_F16>(const StepArgs*, const PolicyArgs*, const IntegArgs*, const FilterArgs*, int, int,
                                                                     hipStream_t);

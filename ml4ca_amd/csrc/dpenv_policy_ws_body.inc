@@ -10,7 +10,7 @@
     constexpr bool SPLIT = PREC != PREC_F16;
     // env-wave rows through LDS transposes (else per lane).  Not in the three-role form: its env wave shares a SIMD with the critic wave and has
     // 256 registers, not 512 - with the staging code the f16 env wave spilled 116 B per lane there (round 4; without it 243 registers, no
-    // scratch - and still 1-3 % slower than two roles for f16, so DPENV_WS_CRITIC_WAVE leaves f16 out: profiles/r04_critic_wave.txt)
+    // scratch - and still 1-3 % slower than two roles for f16, so ws_roles leaves f16 out: profiles/r04_critic_wave.txt)
     constexpr bool STAGE = !SPLIT && ROLES == 2;
     constexpr int NIMG = ws_images(PREC);           // weight images staged: pi_hi, v_hi (, pi_lo (, v_lo))
     // All-exact arithmetic with a SIMD per wave (GROUPS = 2): the CRITIC runs on the ENV wave (round 3).  Two exact evaluations one after
@@ -21,12 +21,7 @@
     // rows beside the actor) and env state + evaluation do not fit 256 registers (10.0 -> 11.4 us exact actor, 13.5 -> 17.2 all exact,
     // with the vessel block and policy constants re-fetched per step and 268 / 412 B of scratch left); and not for the exact-actor
     // mode with its f16 critic, which gains nothing (7.36 vs 7.34 us).
-#ifdef DPENV_WS_SELFCHECK
-    constexpr bool ECRITIC_ON = false;  // the diagnostic double evaluation waits for the network wave's critic
-#else
-    constexpr bool ECRITIC_ON = true;
-#endif
-    constexpr bool ECRITIC = PREC == PREC_F32 && GROUPS == 2 && ROLES == 2 && ECRITIC_ON;
+    constexpr bool ECRITIC = PREC == PREC_F32 && GROUPS == 2 && ROLES == 2;
     // ROLES = 3 (round 4, 128-env workgroups only): a CRITIC WAVE of its own per 64 envs - six waves on the four SIMDs of a CU, in the
     // order E0 E1 A0 A1 C0 C1, so that the actor waves keep a SIMD each and a critic wave shares one with its env wave (matrix work beside
     // vector work, the pairing that nets; MI355X_MICROARCH.md "Two waves per SIMD").  V(o_t) is then evaluated while the actor wave
@@ -59,9 +54,9 @@
     int* seq = (int*)(vpre_mb + 128);            // [0] observations posted, [1] means posted, [2] values posted, [4..5] pre flags,
     int* flag = seq + 4;
     // Two roles: the NETWORK wave draws the exploration noise (Philox + Box-Muller, ~300 VALU per step) while it waits for the
-    // next observation - with the noise in the env wave that wave was the busy one (tools/ws_profile.py).  xi_t travels in the
-    // observation mailbox: once the network wave has turned o_t into fragments the rows are free until the env wave writes
-    // o_t+1, which it does after it has waited for mu_t and read xi_t.
+    // next observation - with the noise in the env wave that wave was the busy one (measured with a timing build since retired:
+    // tools/ab/README.md).  xi_t travels in the observation mailbox: once the network wave has turned o_t into fragments the rows
+    // are free until the env wave writes o_t+1, which it does after it has waited for mu_t and read xi_t.
     // Split arithmetics: the ENV wave draws (it idles ~4 us per step while the network wave evaluates the actor) - unless it carries the critic
     // (ECRITIC): then the network wave (actor only) has the time.  f16 with a SIMD per wave: the network wave (two evaluations per step) is the
     // busy one there, the env wave draws.
@@ -102,7 +97,6 @@
         uint32_t nctr_m = draw_m ? a.noise_ctr[il] : 0u;
         float xin[A];                                                        // xi of the step whose observation is awaited
         if (draw_m) { policy_noise<A>(a, a.env_id_base + i, nctr_m, xin); ++nctr_m; }
-        uint64_t w_obs = 0, t_act = 0, t_cri = 0; const uint64_t t_start = __builtin_amdgcn_s_memtime(); (void)t_start; (void)w_obs; (void)t_act; (void)t_cri;
         auto row_from = [&](const float* mb) {
 #pragma unroll
             for (int k = 0; k < 9; ++k) o[k] = k < OD ? mb[lane * 9 + k] : 0.0f;
@@ -119,7 +113,7 @@
         };
         for (int t = 0; t <= pa.T; ++t) {
             if (!do_critic && t == pa.T) break;                              // the actor is not asked for mu_T
-            WS_WAIT_T(w_obs, &seq[0], t + 1);                                // o_t posted (and step t-1's pre flag)
+            ws_wait(&seq[0], t + 1);                                         // o_t posted (and step t-1's pre flag)
             if constexpr (SPLIT) { row_from(obs_mb + (t & (OBS_SLOTS - 1)) * (64 * 9)); obs_to_frags_x<OD>(o, inx); }
             else frags_from(obs_mb + (t & (OBS_SLOTS - 1)) * (64 * 9), in0, in1);
             if (draw_m && t < pa.T) {                                        // o_t is in registers: its rows now carry xi_t
@@ -127,7 +121,6 @@
                 for (int k = 0; k < A; ++k) xi_mb[lane * 9 + k] = xin[k];
             }
             if (do_actor && t < pa.T) {
-                WS_TIC(ta_);
                 if constexpr (SPLIT) mlp_eval_x<KA>(Wpi, Wpi_l, Bpi, pa.n_hidden, inx, pa.leak, outv);
                 else WS_EVAL(Wpi, Bpi, in0, in1);
 #pragma unroll
@@ -143,10 +136,8 @@
                     obs_to_frags_x<OD>(o, inx);
                 }
                 ws_post(&seq[1], t + 1, lane);                               // mu_t posted
-                WS_TOC(t_act, ta_);
             }
             if (do_critic) {
-                WS_TIC(tc_);
                 if constexpr (SPLIT) critic_x(inx);
                 else WS_EVAL(Wv, Bv, in0, in1);
                 v_mb[(t & 1) * 64 + lane] = outv[0];
@@ -164,16 +155,9 @@
                     vpre_mb[(t & 1) * 64 + lane] = outv[0];
                 }
                 ws_post(&seq[2], t + 1, lane);                               // V(o_t) (and V of the pre-reset o_t) posted
-                WS_TOC(t_cri, tc_);
             }
             if (draw_m && t + 1 < pa.T) { policy_noise<A>(a, a.env_id_base + i, nctr_m, xin); ++nctr_m; }   // while the env wave steps
         }
-#ifdef DPENV_WS_PROFILE
-        if (live && pa.T >= 10 && do_actor) {
-            (pa.logp + (int64_t)3 * n)[(unsigned)i] = (float)w_obs; (pa.logp + (int64_t)4 * n)[(unsigned)i] = (float)(__builtin_amdgcn_s_memtime() - t_start);
-            (pa.logp + (int64_t)5 * n)[(unsigned)i] = (float)t_act; (pa.logp + (int64_t)6 * n)[(unsigned)i] = (float)t_cri;
-        }
-#endif
         };
         if constexpr (ROLES == 3) {
             if (role == 1) net_wave(std::true_type{}, std::false_type{});
@@ -265,8 +249,6 @@
     };
     float v_cur = 0.0f;
     bool pre_owed = false;                                                   // step t-1 left a pre-reset observation in pre_mb
-    uint64_t w_mu = 0, w_v = 0, t_env = 0, t_noi = 0; const uint64_t t_start = __builtin_amdgcn_s_memtime(); (void)t_start; (void)w_mu; (void)w_v; (void)t_env; (void)t_noi;
-    uint64_t t_pre = 0, t_post = 0, t_off = 0; (void)t_pre; (void)t_post; (void)t_off;
     bool boot_wanted = false, was_reset = false;                             // of the step whose boot row is still owed
     // Between "mu_t has arrived" and "o_t+1 is posted" the env wave is on the serial chain of the rollout (the network wave waits
     // for that observation), so only what o_t+1 needs is done there: a_t = mu_t + std xi_t, env.step, the reset of finished
@@ -304,7 +286,6 @@
         // the exploration noise of this step does not depend on the actor's answer: it is drawn while the network wave is
         // still evaluating mu_t (the env wave would otherwise only poll)
         float xi[A];
-        WS_TIC(tn_);
         if (pa.noise) {
             if constexpr (STAGE) {
                 wave_rows_from_regs<A>(lds_io, pre, xi, lane);
@@ -333,9 +314,7 @@
             reset_draw<MODE>(a, a.env_id_base + i, episode, rdraw);
             need_draw = false;
         }
-        WS_TOC(t_noi, tn_);
-        WS_WAIT_T(w_mu, &seq[1], t + 1);                                     // mu_t posted
-        WS_TIC(tp_);
+        ws_wait(&seq[1], t + 1);                                             // mu_t posted
         float act[A], mu[A];
         float logp;
 #pragma unroll
@@ -360,61 +339,9 @@
                                                                              // the reference its last observation was formed against
         }
         StepOut out;
-#ifdef DPENV_WS_SELFCHECK
-        // Diagnostic build only (tools/ws_selfcheck.py): the step is evaluated a second time from opaque copies of the same
-        // inputs AFTER the partner wave has finished its critic (it then only polls), and every field of the two results
-        // is compared bit for bit.  Both evaluations are the same deterministic IEEE arithmetic, so a difference is a
-        // transient fault of the first evaluation (the one that runs beside the partner's MFMAs) - and the record says
-        // which quantity, which lane, by how much.
-        Env sB = s;
-        const float pre6[6] = {s.N, s.E, s.psi, s.u, s.v, s.r};
-        float actB[A];
-#pragma unroll
-        for (int k = 0; k < A; ++k) { actB[k] = act[k]; asm volatile("" : "+v"(actB[k])); }
-        asm volatile("" : "+v"(sB.N), "+v"(sB.E), "+v"(sB.psi), "+v"(sB.u), "+v"(sB.v), "+v"(sB.r), "+v"(sB.sn), "+v"(sB.cs));
-        asm volatile("" : "+v"(sB.refN), "+v"(sB.refE), "+v"(sB.refPsi), "+v"(sB.pt[0]), "+v"(sB.pt[1]), "+v"(sB.pt[2]),
-                          "+v"(sB.ang[0]), "+v"(sB.ang[1]), "+v"(sB.ang[2]), "+v"(sB.steps));
-#endif
-        WS_TOC(t_pre, tp_);
-        WS_TIC(te_);
         // only what o_t+1 and the reset decision depend on stays on the chain; the reward and the azimuth bookkeeping follow the hand-over
-#ifdef DPENV_WS_SELFCHECK
-        constexpr bool DEFER = false;    // the diagnostic double evaluation compares whole steps
-#else
-        constexpr bool DEFER = true;
-#endif
         StepRest rest;
-        env_step_chain<MODE, EXT, DEFER>(a, ve, s, act, has_ref, nrN, nrE, nrP, a.cur_vc != nullptr, cur.vcN, cur.vcE, out, rest, RND ? il : IL);
-        if constexpr (!DEFER) env_step_finish<MODE, EXT, false>(a, s, act, rest, true, out);
-        WS_TOC(t_env, te_);
-        WS_TIC(tq_);
-#ifdef DPENV_WS_SELFCHECK
-        {
-            ws_wait(&seq[2], t + 1);                                         // critic(o_t) done: the partner is idle from here
-                StepOut outB;
-            env_step<MODE, EXT>(a, ve, sB, actB, has_ref, nrN, nrE, nrP, a.cur_vc != nullptr, cur.vcN, cur.vcE, outB, RND ? il : IL);
-            const float fa[20] = {s.N, s.E, s.psi, s.u, s.v, s.r, s.sn, s.cs, out.reward, out.o[0], out.o[1], out.o[2], out.o[3],
-                                  out.o[4], out.o[5], out.o[6], out.o[7], out.o[8], __uint_as_float(out.d), s.ang[1]};
-            const float fb[20] = {sB.N, sB.E, sB.psi, sB.u, sB.v, sB.r, sB.sn, sB.cs, outB.reward, outB.o[0], outB.o[1], outB.o[2],
-                                  outB.o[3], outB.o[4], outB.o[5], outB.o[6], outB.o[7], outB.o[8], __uint_as_float(outB.d), sB.ang[1]};
-            uint32_t mask = 0;
-#pragma unroll
-            for (int k = 0; k < 20; ++k) mask |= (__float_as_uint(fa[k]) != __float_as_uint(fb[k])) ? (1u << k) : 0u;
-            if (mask != 0u && pa.dbg != nullptr) {
-                const uint32_t slot = atomicAdd(pa.dbg, 1u);
-                if (slot < 2000u) {
-                    uint32_t* rec = pa.dbg + 4 + (size_t)slot * 60;
-                    rec[0] = (uint32_t)i; rec[1] = (uint32_t)t; rec[2] = mask; rec[3] = (uint32_t)lane;
-#pragma unroll
-                    for (int k = 0; k < 20; ++k) { rec[4 + k] = __float_as_uint(fa[k]); rec[24 + k] = __float_as_uint(fb[k]); }
-#pragma unroll
-                    for (int k = 0; k < 6; ++k) rec[44 + k] = __float_as_uint(pre6[k]);
-#pragma unroll
-                    for (int k = 0; k < A; ++k) rec[50 + k] = __float_as_uint(actB[k]);
-                }
-            }
-        }
-#endif
+        env_step_chain<MODE, EXT, true>(a, ve, s, act, has_ref, nrN, nrE, nrP, a.cur_vc != nullptr, cur.vcN, cur.vcE, out, rest, RND ? il : IL);
 #pragma unroll
         for (int k = 0; k < 9; ++k) o[k] = out.o[k];
         if constexpr (INTEG) {                                               // the step's update; a cut episode's pre-reset input carries it too
@@ -467,14 +394,12 @@
             for (int k = 0; k < OD; ++k) om[lane * 9 + k] = o[k];           // the next policy input
         }
         ws_post(&seq[0], t + 2, lane);                                       // o_{t+1} (and this step's pre flag) posted
-        WS_TOC(t_post, tq_);
-        WS_TIC(tr_);
         __builtin_amdgcn_sched_barrier(0);                                   // nothing of the rows below moves up into the chain
         if constexpr (IG_RELOAD) {
             if (live) integ_store(ia, i, ig);
             if (t + 1 < pa.T) integ_row(ia, t + 1, n, i, live, ig);
         }
-        if constexpr (DEFER) env_step_finish<MODE, EXT, true>(a, s, act, rest, !do_reset, out);   // reward, azimuths of a continuing env
+        env_step_finish<MODE, EXT, true>(a, s, act, rest, !do_reset, out);   // reward, azimuths of a continuing env
         logp = action_logp<A>(pc, mu, act);                                  // core.py:42-46 on (a_t, mu_t)
         if (a.current_drift) current_drift_step(a, cur, vc0, beta0, a.env_id_base + i);   // the current of step t+1: not needed by o_t+1
         if constexpr (CURR) { if (a.cur_nom && do_reset) { cur.vc = new_vc; cur.beta = new_beta; vc0 = new_vc; beta0 = new_beta; current_components(cur); } }
@@ -488,11 +413,8 @@
             (pa.done + (int64_t)t * n)[(unsigned)i] = (uint8_t)out.d;
             (pa.logp + (int64_t)t * n)[(unsigned)i] = logp;
         }
-        if constexpr (ECRITIC) {
-            WS_TOC(t_off, tr_);
-        } else {
-            WS_WAIT_T(w_v, &seq[2], t + 1);                                  // V(o_t), V(pre-reset o_t) posted
-            WS_TOC(t_off, tr_);
+        if constexpr (!ECRITIC) {
+            ws_wait(&seq[2], t + 1);                                         // V(o_t), V(pre-reset o_t) posted
             if (live) {
                 const float v_t = v_mb[(t & 1) * 64 + lane];
                 (pa.val + (int64_t)t * n)[(unsigned)i] = v_t;
@@ -501,14 +423,6 @@
         }
     }
     if constexpr (!ECRITIC) ws_wait(&seq[2], pa.T + 1);                      // V(o_T) posted
-#ifdef DPENV_WS_PROFILE
-    if (live && pa.T >= 12) {
-        (pa.logp + (int64_t)0 * n)[(unsigned)i] = (float)w_mu; (pa.logp + (int64_t)1 * n)[(unsigned)i] = (float)w_v; (pa.logp + (int64_t)2 * n)[(unsigned)i] = (float)(__builtin_amdgcn_s_memtime() - t_start);
-        (pa.logp + (int64_t)7 * n)[(unsigned)i] = (float)t_env; (pa.logp + (int64_t)8 * n)[(unsigned)i] = (float)t_noi;
-        (pa.logp + (int64_t)9 * n)[(unsigned)i] = (float)t_pre; (pa.logp + (int64_t)10 * n)[(unsigned)i] = (float)t_post;
-        (pa.logp + (int64_t)11 * n)[(unsigned)i] = (float)t_off;
-    }
-#endif
     put_rows_o(pa.last_obs, 0, o);
     if (live) {
         if constexpr (ECRITIC) pa.last_val[i] = v_cur;                       // V(o_T); boot[T-1] went out with it

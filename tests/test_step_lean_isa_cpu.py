@@ -23,7 +23,7 @@ def asm(tmp_path_factory):
         pytest.skip('no hipcc')
     csrc = os.path.join(ROOT, 'ml4ca_amd', 'csrc')
     mk = open(os.path.join(csrc, 'Makefile')).read()
-    flags = re.search(r'^CXXFLAGS \?= (.*)$', mk, re.M).group(1).replace('$(BLOCK)', '64').split()
+    flags = re.search(r'^CXXFLAGS \?= (.*)$', mk, re.M).group(1).split()
     out = str(tmp_path_factory.mktemp('isa') / 'k.s')
     subprocess.run([hipcc, '--offload-arch=gfx950'] + flags + ['-DDPENV_DEV_FAST', '--cuda-device-only', '-S', '-o', out,
                                                                 os.path.join(csrc, 'dpenv_kernels.hip')], check=True, capture_output=True)

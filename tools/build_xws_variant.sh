@@ -7,7 +7,7 @@ set -e
 cd "$(dirname "$0")/.."
 name=$1; shift
 mkdir -p /tmp/dpenv_variants build/wsdiag
-BASE="-O3 -std=c++17 -fPIC -Wall -Wno-unused-function -Wno-unused-const-variable -Wno-unused-variable -ffp-contract=off -fno-slp-vectorize -mllvm -amdgpu-mfma-vgpr-form=1 -DDPENV_BLOCK=64 -DDPENV_DEV_FAST"
+BASE="-O3 -std=c++17 -fPIC -Wall -Wno-unused-function -Wno-unused-const-variable -Wno-unused-variable -ffp-contract=off -fno-slp-vectorize -mllvm -amdgpu-mfma-vgpr-form=1 -DDPENV_DEV_FAST"
 # UNITS="ws xws1 xws2" also rebuilds the f16 two-wave unit (dpenv_policy_ws.hip)
 objs=""
 for u in ws xws1 xws2; do

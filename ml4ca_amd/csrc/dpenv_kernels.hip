@@ -149,6 +149,116 @@ __device__ __forceinline__ void step_lean(const StepArgs& a, float* lds_io)
     buf_store1(buf_rsrc(a.rew, n * 4u), o4, out.reward);
 }
 
+// The fixed step (step_fixed_kernel): the lean step for the launch every shipped handle makes - 20 plant sub-steps, the plant not held -
+// with what is launch-uniform and fixed per handle or per launch resolved at compile time (wrap in degrees or radians, end conditions on
+// or off, a setpoint handed over or not).  step_lean's body, the same calls in the same order on the same operands, so every row is bit
+// for bit the lean and the general kernel's; the shared device functions see a StepArgs whose switches are constants, and fold.
+// Arguments: the five load-stream bases and n are plain leading parameters, so that the kernarg preload (the -amdgpu-kernarg-preload-count
+// flag this unit is built with) has them in SGPRs when the wave starts and the first vector load waits for no scalar load; the rest is one
+// compact block (200 B against the 456 B of StepArgs) whose output streams arrive as ready buffer descriptors.
+struct BufDesc {            // words 0-1 base (below 2^48), word 2 byte count, word 3 the descriptor's flags word
+    const void* base;
+    uint32_t bytes;
+    uint32_t flags;
+};
+constexpr uint32_t BUF_FLAGS = 0x00020000;
+struct StepFixedArgs {
+    VesselDev v0;
+    float h, inv_dt;
+    int32_t pad;
+    BufDesc obs, done, rew, new_ref;
+    int32_t terminate, max_ep_len;       // read by the ENDS instantiations only
+};
+static_assert(sizeof(StepFixedArgs) == 200 && offsetof(StepFixedArgs, obs) == 128, "StepFixedArgs layout");
+constexpr int STEP_FIXED_SUBSTEPS = 20;  // customEnv.py:79-80
+
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t buf_rsrc(const BufDesc& d)
+{
+    __builtin_assume((reinterpret_cast<uintptr_t>(d.base) >> 48) == 0);       // the host's word 1 is the descriptor's as it stands
+    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(d.base), 0, (int)d.bytes, (int)d.flags);
+}
+// A kernel argument the wave needs later, fetched NOW: the empty asm takes it in SGPRs, so its s_load is issued - and has landed - before
+// this point, and every later use reads those registers.
+template <typename T> __device__ __forceinline__ void fetch_sgpr(T& x) { asm volatile("" : "+s"(x)); }
+__device__ __forceinline__ void fetch_sgpr(BufDesc& d) { fetch_sgpr(d.base); fetch_sgpr(d.bytes); fetch_sgpr(d.flags); }
+
+template <int MODE, bool EXT, bool DEG, bool ENDS, bool REF>
+__global__ __launch_bounds__(BLOCK) void step_fixed_kernel(float4* S0, float4* S1, float4* S2, float4* RF, const float* action, int n_,
+                                                           const StepFixedArgs fx_)
+{
+    constexpr int A = ModeTraits<MODE>::A;
+    constexpr int OD = EXT ? 9 : 6;
+    __shared__ float lds_io[BLOCK * 9];
+    const int tid = threadIdx.x;
+    const uint32_t n = (uint32_t)n_;
+    const uint32_t i = blockIdx.x * BLOCK + tid;
+    const uint32_t o16 = i * 16u, o4 = i * 4u;
+    const uint32_t oact = (blockIdx.x * (BLOCK * A) + tid) * 4u;
+    const uint32_t oobs = (blockIdx.x * (BLOCK * OD) + tid) * 4u;
+    const __amdgpu_buffer_rsrc_t rS0 = buf_rsrc(S0, n * 16u), rS1 = buf_rsrc(S1, n * 16u), rS2 = buf_rsrc(S2, n * 16u),
+                                 rRF = buf_rsrc(RF, n * 16u), rAct = buf_rsrc(action, n * (4u * A));
+    StepFixedArgs fx = fx_;
+    // what the shared step functions read of StepArgs: the switches as constants, the rest from the compact block
+    StepArgs a;
+    a.h = fx.h; a.inv_dt = fx.inv_dt;
+    a.n_substeps = STEP_FIXED_SUBSTEPS; a.hold_plant = 0;
+    a.wrap_mode = DEG ? WRAP_REFERENCE : WRAP_RADIANS;
+
+    // ---- every load up front (the order of step_lean) ----
+    float act[A];
+#pragma unroll
+    for (int j = 0; j < A; ++j) act[j] = buf_load1(rAct, oact + j * (4u * BLOCK));
+    Env s;
+    {
+        const float4 s0 = buf_load4(rS0, o16), s1 = buf_load4(rS1, o16), s2 = buf_load4(rS2, o16), rf = buf_load4(rRF, o16);
+        s.N = s0.x; s.E = s0.y; s.psi = s0.z; s.u = s0.w; s.v = s1.x; s.r = s1.y;
+        s.ang[0] = rf.w; s.ang[1] = s1.z; s.ang[2] = s1.w;
+        s.pt[0] = s2.x; s.pt[1] = s2.y; s.pt[2] = s2.z; s.steps = __float_as_int(s2.w);
+        s.refN = rf.x; s.refE = rf.y; s.refPsi = rf.z;
+    }
+    float nrN = 0.0f, nrE = 0.0f, nrP = 0.0f;
+    if (REF) {
+        const __amdgpu_buffer_rsrc_t rNR = buf_rsrc(fx.new_ref);                  // [3][n]
+        nrN = buf_load1(rNR, o4); nrE = buf_load1(rNR, o4 + n * 4u); nrP = buf_load1(rNR, o4 + n * 8u);
+    }
+    // the rest of the arguments, under the vector loads: no scalar load is left behind the first wait for one of those
+#pragma unroll
+    for (int k = 0; k < VD_COUNT; ++k) fetch_sgpr(fx.v0.p[k]);
+    fetch_sgpr(fx.h); fetch_sgpr(fx.inv_dt);
+    fetch_sgpr(fx.obs); fetch_sgpr(fx.done); fetch_sgpr(fx.rew);
+    if (ENDS) { fetch_sgpr(fx.terminate); fetch_sgpr(fx.max_ep_len); }
+    a.terminate = ENDS ? fx.terminate : 0; a.max_ep_len = ENDS ? fx.max_ep_len : 0;
+    __builtin_amdgcn_sched_barrier(0);
+    sincos_lean(s.psi, s.sn, s.cs);
+#pragma unroll
+    for (int j = 0; j < A; ++j) lds_io[j * BLOCK + tid] = act[j];
+    lds_order<BLOCK>();
+#pragma unroll
+    for (int k = 0; k < A; ++k) act[k] = lds_io[tid * A + k];
+    const Vessel ve = vessel_from_args(fx.v0);
+
+    StepOut out;
+    StepRest rest;
+    env_step_chain<MODE, EXT, false>(a, ve, s, act, REF, nrN, nrE, nrP, false, 0.0f, 0.0f, out, rest, IL_NONE);
+    // ---- state and done bits, then the observation rows, while the reward is computed; the reward last ----
+    buf_store4(rS0, o16, s.N, s.E, s.psi, s.u);
+    buf_store4(rS1, o16, s.v, s.r, s.ang[1], s.ang[2]);
+    buf_store4(rS2, o16, s.pt[0], s.pt[1], s.pt[2], __int_as_float(s.steps));
+    if (REF || MODE == MODE_FULL) buf_store4(rRF, o16, s.refN, s.refE, s.refPsi, s.ang[0]);
+    buf_store_u8(buf_rsrc(fx.done), i, (uint8_t)out.d);
+    __builtin_amdgcn_sched_barrier(0);
+    lds_order<BLOCK>();
+#pragma unroll
+    for (int k = 0; k < OD; ++k) lds_io[tid * OD + k] = out.o[k];
+    lds_order<BLOCK>();
+    const __amdgpu_buffer_rsrc_t rObs = buf_rsrc(fx.obs);
+#pragma unroll
+    for (int j = 0; j < OD; ++j) buf_store1(rObs, oobs + j * (4u * BLOCK), lds_io[j * BLOCK + tid]);
+    __builtin_amdgcn_sched_barrier(0);
+    env_step_finish<MODE, EXT, false>(a, s, act, rest, true, out);
+    buf_store1(buf_rsrc(fx.rew), o4, out.reward);
+}
+
 // VES (dpenv_dev.h VES_*): where a lane's vessel comes from - kernel arguments, the LDS-staged class table, or its own per-env block
 // (straight into registers, or through an LDS image filled by LDS-DMA: the A/B SURVEY section 7 asks for, bench.py `vessel_classes.per_env`).
 // (Rejected forms of this kernel - loads not hoisted above the first branch, observation rows before the state stores, no early stores,
@@ -1174,6 +1284,11 @@ static bool step_lean_ok(const StepArgs& a, int ves)
            a.obs_layout == LAYOUT_AOS && a.action_layout == LAYOUT_AOS && (int64_t)a.n * 36 < ((int64_t)1 << 31);
 }
 
+template <typename F> static hipError_t with_flag(bool on, F&& f)
+{
+    return on ? f(std::true_type{}) : f(std::false_type{});
+}
+
 hipError_t dev::launch_step(const StepArgs* a, int mode, int ext, int ves, int reset_wave, hipStream_t s)
 {
     if (!vessel_source_ok(*a, ves)) return hipErrorInvalidValue;
@@ -1182,6 +1297,26 @@ hipError_t dev::launch_step(const StepArgs* a, int mode, int ext, int ves, int r
     const bool two = a->auto_reset && reset_wave;
     const bool lean = step_lean_ok(*a, ves);
     return with_mode_ext(mode, ext, [&](auto M, auto E) {
+        if (lean && a->n_substeps == STEP_FIXED_SUBSTEPS && !a->hold_plant) {
+            // the shipped shape: the fixed step, its three switches resolved here
+            StepFixedArgs fx;
+            fx.v0 = a->v0;
+            fx.h = a->h; fx.inv_dt = a->inv_dt; fx.pad = 0;
+            const uint32_t n = (uint32_t)a->n;
+            constexpr uint32_t OD = decltype(E)::value ? 9u : 6u;
+            fx.obs = {a->obs, n * (4u * OD), BUF_FLAGS};
+            fx.done = {a->done, n, BUF_FLAGS};
+            fx.rew = {a->rew, n * 4u, BUF_FLAGS};
+            fx.new_ref = {a->new_ref, n * 12u, BUF_FLAGS};
+            fx.terminate = a->terminate; fx.max_ep_len = a->max_ep_len;
+            return with_flag(a->wrap_mode == WRAP_REFERENCE, [&](auto DEG) {
+                return with_flag(a->terminate || a->max_ep_len > 0, [&](auto ENDS) { return with_flag(a->new_ref != nullptr, [&](auto REF) {
+                    hipLaunchKernelGGL((step_fixed_kernel<M, E, DEG, ENDS, REF>), grid, dim3(BLOCK), 0, s, a->S0, a->S1, a->S2, a->RF, a->action,
+                                       a->n, fx);
+                    return hipGetLastError();
+                }); });
+            });
+        }
         if (lean) {
             hipLaunchKernelGGL((step_kernel<M, E, VES_ARGS, false, true>), grid, dim3(BLOCK), 0, s, *a);
             return hipGetLastError();

@@ -11,7 +11,7 @@ for v in "$@"; do
   python3 - $O/$tag $tag <<'PY'
 import csv, glob, sys, statistics, json
 f = glob.glob(sys.argv[1] + '/**/*kernel_trace.csv', recursive=True)
-d = [int(r['End_Timestamp']) - int(r['Start_Timestamp']) for r in csv.DictReader(open(f[0])) if 'step_kernel<' in r['Kernel_Name']]
+d = [int(r['End_Timestamp']) - int(r['Start_Timestamp']) for r in csv.DictReader(open(f[0])) if 'step_kernel<' in r['Kernel_Name'] or 'step_fixed_kernel<' in r['Kernel_Name']]
 b = json.loads(open(sys.argv[1] + '.json').readline())
 print('%-14s %5d dispatches: avg %.0f median %.0f min %d p95 %.0f ns; bench spacing in this traced run %.2f us' % (sys.argv[2], len(d), statistics.mean(d), statistics.median(d), min(d), sorted(d)[int(0.95 * len(d))], b['ms_per_step'] * 1e3))
 PY

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Per-kernel averages of a rocprofv3 --pmc run (counter_collection.csv under a directory): one line per kernel x counter.
-    python tools/pmc_by_kernel.py <dir> [substring-of-kernel-name]"""
+    python tools/pmc_by_kernel.py <dir> [substring-of-kernel-name]
+The headline kernel is `step_fixed_kernel` (before round 11: `step_kernel`); `step_` selects either."""
 import csv
 import glob
 import sys

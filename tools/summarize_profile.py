@@ -41,6 +41,8 @@ def kname(k):
               'adv_apply_kernel', 'pack_policy_kernel'):
         if n in k:
             return n
+    if 'dpenv::step_fixed_kernel<' in k:
+        return 'step_kernel'       # the headline since round 11: the fixed step, with and without a setpoint (two instantiations of one graph)
     m = re.search(r'dpenv::step_kernel<([^>]*)>', k)
     if m:
         # <MODE, EXT, VES, RESETW>: the headline is the shared-hull kernel without a reset wave; the bench's side records (round 5) also launch

@@ -28,7 +28,7 @@ from ml4ca_amd import rollout
 from ml4ca_amd.policy import ActorCritic
 
 
-def evaluate_actor(ac, dev, preset, precision, seed, out=print):
+def evaluate_actor(ac, dev, preset, precision, seed, out=print, eval_envs=1024):
     """The trained actor on the NOMINAL hull (and on a spread of hulls): the reference's run_RL_policy (spinup/utils/test_policy.py:97-186: six
     fixed starts, deterministic policy) and the thesis' 4-corner box test with its two metrics - IAE (results/all_plots/common.py:60-74) and
     the energy-equivalent work of the thruster power model (box_test/plot_act.py:128-135,184-211)."""
@@ -41,7 +41,7 @@ def evaluate_actor(ac, dev, preset, precision, seed, out=print):
     out('eval  run_RL_policy on the nominal hull (six fixed starts, deterministic actor): EpRet %s  EpLen %s' % (
         [round(float(x), 1) for x in r['EpRet']], [int(x) for x in r['EpLen']]))
     res = {'EpRet_mean': float(r['EpRet'].mean()), 'EpLen_mean': float(r['EpLen'].float().mean())}
-    T, nb = 1250, 1024
+    T, nb = 1250, int(eval_envs)
     # (the last two rows: the thesis' current box test - 0.2 m/s towards 135 deg, results/all_plots/current_box_test/plot_pos.py:78 - and a spread
     # of currents around it: +-0.1 m/s, +-90 deg, one draw per env)
     for tag, spread, cur in (('nominal hull', 0.0, None), ('hulls +-15 %', 0.15, None), ('hulls +-30 %', 0.30, None), ('hulls +-50 %', 0.50, None),
@@ -55,6 +55,16 @@ def evaluate_actor(ac, dev, preset, precision, seed, out=print):
                 env.set_current_randomisation(cur[0], cur[1])              # one draw per env at the reset below
         ac.upload(env, precision=precision)
         start = torch.zeros((3, nb), device=dev)
+        if nb != 1024:
+            # any other batch: the same flight in 50-step launches through one re-used set of row blocks, scored on the device as it flies
+            # (evaluate.ScoreCard: O(n) memory - 65 536 envs fit); the corner errors need the rows and are not reported
+            st = EV.deployment_box_test_streamed(env, T=T, chunk=50, integral=False, start=start)
+            iae_tot, w, rps = st['iae'], st['work'], float(st['ret'].mean()) / T
+            out('eval  box test (1250 steps, %d envs, streamed), %-13s: IAE %.2f (worst env %.2f)  work bow/port/star %s  reward/step %.3f' % (
+                nb, tag, float(iae_tot.mean()), float(iae_tot.max()), [round(float(x), 1) for x in w.mean(0)], rps))
+            res[tag] = {'IAE': float(iae_tot.mean()), 'IAE_worst': float(iae_tot.max()), 'work': [float(x) for x in w.mean(0)], 'reward_per_step': rps}
+            del env
+            continue
         env.reset(init=torch.zeros((6, nb), device=dev), new_ref=start.clone())
         steps, refs = EV.box_schedule(start)
         o = policy_rollout(env, T, noise=None, switch_steps=steps, refs=refs)
@@ -101,6 +111,8 @@ def main():
                     help="nominal hull (dpenv_default_vessel_ex); default (round 6): the thrust-loss preset - the steady speeds 'with thrust losses' are the velocity "
                          'bounds the reference trains with (customEnv.py:17,26), and the shared training form runs it at the cost of the default hull')
     ap.add_argument('--eval', action='store_true', help='after training: run_RL_policy + the box test (IAE, energy) on the nominal hull and on spreads of hulls')
+    ap.add_argument('--eval-envs', type=int, default=1024, help='envs per --eval box test; 1024 (the default) scores the resident rows as before, any other '
+                                                                'value flies the test in 50-step launches scored on the device (evaluate.ScoreCard), e.g. 65536')
     ap.add_argument('--eval-presets', default='', help="comma-separated presets to run --eval on (default: the training preset), e.g. 'no_loss,thrust_loss': "
                                                       'how an actor trained on one thrust regime fares on the other')
     ap.add_argument('--save', default='', help='write the trained parameters (reference variable names) to this .npz')
@@ -228,7 +240,7 @@ def main():
         if args.eval:
             for pz in (args.eval_presets.split(',') if args.eval_presets else [args.preset]):
                 print('eval on the %s preset (trained on %s%s)' % (pz, args.preset, ', hulls re-drawn +-%g %%' % (100 * args.randomise) if args.randomise > 0 else ''))
-                evaluate_actor(ac, dev, pz, 'f32', args.seed)
+                evaluate_actor(ac, dev, pz, 'f32', args.seed, eval_envs=args.eval_envs)
     if world > 1:
         torch.distributed.destroy_process_group()
 

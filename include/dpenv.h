@@ -548,6 +548,72 @@ int dpenv_reference_filter_coeffs(const dpenv_reference_filter* rf, float dt, fl
  * be NULL.  Plain dpenv_policy_rollout / dpenv_policy_rollout_integral apply the filter as well while it is on. */
 int dpenv_policy_rollout_deployed(dpenv_handle h, const dpenv_policy_rollout_io* io, float* ref_out, float* integ_out, dpenv_stream s);
 
+/* ---- streaming score card: box-test IAE, thruster work and returns accumulated on the device (additive to ABI 6) -----------------------
+ * evaluate.iae / evaluate.work / deployment_box_test need every row of a flight resident (105 B per env-step with the integral action and
+ * the filter on: 8.6 GB for a 250 s box test of 65 536 envs).  Closed-loop launches continue one another bit for bit, so a flight can be
+ * flown in short chunks through ONE re-used set of row blocks; these calls consume each chunk and carry the trapezoid across chunk and
+ * episode boundaries: O(n) memory, and per-episode return / length (spinup's EpRet / EpLen) for runs that auto-reset.  Handle-free, like
+ * dpenv_gae: every bulk pointer is a device pointer, the io struct is host memory, calls are stream-ordered and graph-capturable.
+ *
+ * State.  One opaque state per env, caller-owned, dpenv_score_state_bytes(n) bytes, 16-byte aligned.  All-zero bytes mean "fresh": the
+ * caller resets it with a memset (no allocation, no host sync, stream-ordered and capturable).  It holds, per env: an OPEN episode - sums
+ * iae, work[3], ret in f64; len as a count; the previous sample (q_prev, P_prev[3]) in f32; a has_prev flag - and CLOSED-episode totals -
+ * episodes as a count; sums of iae, work[3], ret in f64; the sum of len.
+ *
+ * Per-row update.  One call consumes a block of T rows, in order t = 0 ... T-1, for every env i.  Per-sample terms are f32 in exactly
+ * this order (the build uses -ffp-contract=off; sqrt is the hardware's correctly rounded one):
+ *     e_k  = f32(obs[t][i][k]) - (integ ? integ[t][i][k] : 0)          k = 0,1,2   (bf16 obs widened first)
+ *     q    = sqrtf( (e_0/norm_0)^2 + (e_1/norm_1)^2 + ((e_2*R2D)/norm_2)^2 )          R2D = (float)(180/pi), sum left to right
+ *     n_j  = fminf(fmaxf(act[t][i][j]*100, -100), 100)                 j = 0,1,2   (evaluate.commanded_thrust)
+ *     x_j  = n_j/100 * rps_j ;   P_j = sgn(n_j) * c_j * (x_j*x_j*x_j)              (evaluate.thruster_power)
+ *     if has_prev:  iae += (double)(0.5f*(q + q_prev)*dt) ;  work_j += (double)(0.5f*(P_j + P_prev_j)*dt)
+ *     ret += (double)rew[t][i] ;  len += 1 ;  (q_prev, P_prev) = (q, P) ;  has_prev = 1
+ *     if done[t][i] != 0  or  (cut_at_end and t == T-1):
+ *           closed += open ; episodes += 1 ; open = 0 ; has_prev = 0
+ * The first sample of an episode contributes no segment (like the reference's integrals[0] = 0, common.py:60-74); the trapezoid never
+ * bridges an episode end; ANY non-zero done byte ends the episode (the rule dpenv_gae's `end` uses); cut_at_end serves reset_at_end
+ * launches, whose cut envs may carry done[T-1] == 0.
+ *
+ * Inputs: row-major [T][n][stride] blocks, as dpenv_policy_rollout* and the AOS form of dpenv_rollout write them ([dim][n] layouts are not
+ * supported: there is no way to ask for them).  obs: f32 or bf16, obs_stride >= 3 elements, only columns 0..2 are read (the pose error).
+ * act: f32, act_stride >= 3, only columns 0..2 are read - the three thrust commands, which is what evaluate.commanded_thrust assumes of
+ * every variant's action vector.  rew: [T][n] f32.  done: [T][n] u8, NULL = never ends.  integ: [T][n][3] f32 (dpenv_policy_rollout_integral's
+ * integ_out) or NULL; needs obs.  Any of obs / act / rew may be NULL: the sums it feeds then stay untouched (len and episodes always count).
+ * Everything is validated on the host before any device call: DPENV_EINVAL, the field named by dpenv_last_error(NULL). */
+enum { DPENV_SCORE_IAE = 0, DPENV_SCORE_WORK = 1 /* 1..3: bow, port, star */, DPENV_SCORE_RET = 4, DPENV_SCORE_LEN = 5,   /* the open episode */
+       DPENV_SCORE_EPISODES = 6, DPENV_SCORE_EP_IAE = 7, DPENV_SCORE_EP_WORK = 8 /* 8..10 */, DPENV_SCORE_EP_RET = 11,
+       DPENV_SCORE_EP_LEN = 12,                                                                                         /* closed episodes, summed */
+       DPENV_SCORE_NOUT = 13 };
+typedef struct dpenv_score_io {
+    uint32_t struct_size;    /* sizeof(dpenv_score_io), ABI check */
+    int32_t T;               /* rows in this block, >= 1 */
+    int32_t n;               /* envs, >= 1 */
+    const void* obs;         /* [T][n][obs_stride] f32 / bf16, or NULL */
+    const float* act;        /* [T][n][act_stride], or NULL */
+    const float* rew;        /* [T][n], or NULL */
+    const uint8_t* done;     /* [T][n], or NULL = never ends */
+    const float* integ;      /* [T][n][3], or NULL; needs obs */
+    int32_t obs_dtype;       /* DPENV_F32 / DPENV_BF16 */
+    int32_t obs_stride;      /* elements per obs row, >= 3 (default 9) */
+    int32_t act_stride;      /* floats per act row, >= 3 (default 7) */
+    float dt;                /* sample period [s], 0.2 */
+    float norm[3];           /* IAE normalisation (5 m, 5 m, 25 deg), box_test/plot_pos.py:174 */
+    float power_coeff[3];    /* c_j = (float)(KQ0_j * 2 pi * 1025 * D_j^5): KQ0 0.02 / 0.036 / 0.036, D 0.06 / 0.15 / 0.15 (plot_act.py:124-135), computed in double, rounded once */
+    float rps_max[3];        /* (33, 11, 11) revolutions per second at 100 % */
+    int32_t cut_at_end;      /* 1: every env's episode is closed after row T-1 */
+} dpenv_score_io;
+int64_t dpenv_score_state_bytes(int32_t n);          /* 0 for n < 1 */
+/* Fill *io with the constants above; T, n and the block pointers are left 0 / NULL. */
+int dpenv_score_default_io(dpenv_score_io* io);
+int dpenv_score_accumulate(void* state, const dpenv_score_io* io, dpenv_stream s);
+/* out: device double[DPENV_SCORE_NOUT][n], slot DPENV_SCORE_* of every env (counts as doubles). */
+int dpenv_score_read(const void* state, int32_t n, double* out, dpenv_stream s);
+/* out: device double[DPENV_SCORE_NOUT][3] = sum, min, max over the envs of each read slot.  Two stages with a fixed pairing (a wave per 64
+ * envs, then one workgroup over the partials in index order): the sums are the same bits every run.  workspace:
+ * dpenv_score_summary_workspace_bytes(n) bytes of device memory. */
+int64_t dpenv_score_summary_workspace_bytes(int32_t n);
+int dpenv_score_summary(const void* state, int32_t n, double* out, void* workspace, dpenv_stream s);
+
 int dpenv_abi_version(void);
 
 #ifdef __cplusplus

@@ -83,6 +83,17 @@ class ReferenceFilter(C.Structure):
     _fields_ = [('struct_size', C.c_uint32), ('omega', C.c_float * 3), ('zeta', C.c_float * 3)]
 
 
+class ScoreIO(C.Structure):
+    _fields_ = [('struct_size', C.c_uint32), ('T', C.c_int32), ('n', C.c_int32), ('obs', C.c_void_p), ('act', C.c_void_p),
+                ('rew', C.c_void_p), ('done', C.c_void_p), ('integ', C.c_void_p), ('obs_dtype', C.c_int32), ('obs_stride', C.c_int32),
+                ('act_stride', C.c_int32), ('dt', C.c_float), ('norm', C.c_float * 3), ('power_coeff', C.c_float * 3),
+                ('rps_max', C.c_float * 3), ('cut_at_end', C.c_int32)]
+
+
+# read slots of the score card (dpenv.h DPENV_SCORE_*)
+SCORE_IAE, SCORE_WORK, SCORE_RET, SCORE_LEN, SCORE_EPISODES, SCORE_EP_IAE, SCORE_EP_WORK, SCORE_EP_RET, SCORE_EP_LEN, SCORE_NOUT = 0, 1, 4, 5, 6, 7, 8, 11, 12, 13
+
+
 # every symbol include/dpenv.h declares: name -> (restype, argtypes)
 _VP, _I32, _I64, _F = C.c_void_p, C.c_int32, C.c_int64, C.c_float
 SYMBOLS = {
@@ -141,6 +152,12 @@ SYMBOLS = {
     'dpenv_set_reference_filter_state': (C.c_int, [_VP, _VP, _VP, _VP]),
     'dpenv_reference_filter_coeffs': (C.c_int, [C.POINTER(ReferenceFilter), _F, C.POINTER(C.c_float * 9 * 3), C.POINTER(C.c_float * 3 * 3)]),
     'dpenv_policy_rollout_deployed': (C.c_int, [_VP, C.POINTER(PolicyRolloutIO), _VP, _VP, _VP]),
+    'dpenv_score_state_bytes': (C.c_int64, [_I32]),
+    'dpenv_score_default_io': (C.c_int, [C.POINTER(ScoreIO)]),
+    'dpenv_score_accumulate': (C.c_int, [_VP, C.POINTER(ScoreIO), _VP]),
+    'dpenv_score_read': (C.c_int, [_VP, _I32, _VP, _VP]),
+    'dpenv_score_summary_workspace_bytes': (C.c_int64, [_I32]),
+    'dpenv_score_summary': (C.c_int, [_VP, _I32, _VP, _VP, _VP]),
 }
 
 _lib = None

@@ -1477,6 +1477,81 @@ extern "C" int dpenv_gae(const float* rew, const float* val, const uint8_t* end,
     return dpenv_gae_stats(rew, val, end, boot, last_val, T, n, gamma, lam, adv_out, ret_out, nullptr, nullptr, s);
 }
 
+// ---- streaming score card (dpenv.h: dpenv_score_*): handle-free; every argument is validated here, before any device call ----
+extern "C" int64_t dpenv_score_state_bytes(int32_t n) { return n > 0 ? dev::score_state_bytes(n) : 0; }
+
+extern "C" int64_t dpenv_score_summary_workspace_bytes(int32_t n) { return n > 0 ? dev::score_summary_workspace_bytes(n) : 0; }
+
+extern "C" int dpenv_score_default_io(dpenv_score_io* io)
+{
+    if (!io) return fail(nullptr, DPENV_EINVAL, "dpenv_score_default_io: io is NULL");
+    std::memset(io, 0, sizeof *io);
+    io->struct_size = (uint32_t)sizeof *io;
+    io->obs_dtype = DPENV_F32;
+    io->obs_stride = 9;
+    io->act_stride = 7;
+    io->dt = 0.2f;
+    const double kq0[3] = {0.02, 0.036, 0.036}, diam[3] = {0.06, 0.15, 0.15};
+    const float norm[3] = {5.0f, 5.0f, 25.0f}, rps[3] = {33.0f, 11.0f, 11.0f};
+    for (int j = 0; j < 3; ++j) {
+        io->norm[j] = norm[j];
+        io->rps_max[j] = rps[j];
+        const double d = diam[j];
+        io->power_coeff[j] = (float)(kq0[j] * 2 * 3.141592653589793 * 1025.0 * (d * d * d * d * d));
+    }
+    return DPENV_OK;
+}
+
+extern "C" int dpenv_score_accumulate(void* state, const dpenv_score_io* io, dpenv_stream s)
+{
+    if (!io) return fail(nullptr, DPENV_EINVAL, "dpenv_score_accumulate: io is NULL");
+    if (io->struct_size != sizeof(dpenv_score_io))
+        return fail(nullptr, DPENV_EINVAL, "dpenv_score_accumulate: struct_size %u != %zu", io->struct_size, sizeof(dpenv_score_io));
+    if (io->T < 1) return fail(nullptr, DPENV_EINVAL, "dpenv_score_accumulate: T = %d, must be >= 1", io->T);
+    if (io->n < 1) return fail(nullptr, DPENV_EINVAL, "dpenv_score_accumulate: n = %d, must be >= 1", io->n);
+    if (!state) return fail(nullptr, DPENV_EINVAL, "dpenv_score_accumulate: state is NULL");
+    if (reinterpret_cast<uintptr_t>(state) & 15u) return fail(nullptr, DPENV_EINVAL, "dpenv_score_accumulate: state must be 16-byte aligned");
+    if (io->obs_dtype != DPENV_F32 && io->obs_dtype != DPENV_BF16)
+        return fail(nullptr, DPENV_EINVAL, "dpenv_score_accumulate: obs_dtype %d is neither DPENV_F32 nor DPENV_BF16", io->obs_dtype);
+    if (io->obs && io->obs_stride < 3) return fail(nullptr, DPENV_EINVAL, "dpenv_score_accumulate: obs_stride = %d, must be >= 3", io->obs_stride);
+    if (io->act && io->act_stride < 3) return fail(nullptr, DPENV_EINVAL, "dpenv_score_accumulate: act_stride = %d, must be >= 3", io->act_stride);
+    if (io->integ && !io->obs) return fail(nullptr, DPENV_EINVAL, "dpenv_score_accumulate: integ needs obs");
+    if (!std::isfinite(io->dt) || !(io->dt > 0.0f)) return fail(nullptr, DPENV_EINVAL, "dpenv_score_accumulate: dt must be finite and > 0");
+    for (int j = 0; j < 3; ++j) {
+        if (!std::isfinite(io->norm[j]) || !(io->norm[j] > 0.0f))
+            return fail(nullptr, DPENV_EINVAL, "dpenv_score_accumulate: norm[%d] must be finite and > 0", j);
+        if (!std::isfinite(io->power_coeff[j])) return fail(nullptr, DPENV_EINVAL, "dpenv_score_accumulate: power_coeff[%d] is not finite", j);
+        if (!std::isfinite(io->rps_max[j])) return fail(nullptr, DPENV_EINVAL, "dpenv_score_accumulate: rps_max[%d] is not finite", j);
+    }
+    ScoreArgs a;
+    a.state = (uint4*)state;
+    a.obs = io->obs; a.act = io->act; a.rew = io->rew; a.done = io->done; a.integ = io->integ;
+    a.T = io->T; a.n = io->n; a.obs_stride = io->obs_stride; a.act_stride = io->act_stride; a.cut_at_end = io->cut_at_end ? 1 : 0;
+    a.dt = io->dt;
+    for (int j = 0; j < 3; ++j) { a.norm[j] = io->norm[j]; a.coeff[j] = io->power_coeff[j]; a.rps[j] = io->rps_max[j]; }
+    HIP_TRY(nullptr, dev::launch_score(&a, io->obs_dtype == DPENV_BF16, (hipStream_t)s));
+    return DPENV_OK;
+}
+
+extern "C" int dpenv_score_read(const void* state, int32_t n, double* out, dpenv_stream s)
+{
+    if (n < 1) return fail(nullptr, DPENV_EINVAL, "dpenv_score_read: n = %d, must be >= 1", n);
+    if (!state || (reinterpret_cast<uintptr_t>(state) & 15u)) return fail(nullptr, DPENV_EINVAL, "dpenv_score_read: state is NULL or not 16-byte aligned");
+    if (!out) return fail(nullptr, DPENV_EINVAL, "dpenv_score_read: out is NULL");
+    HIP_TRY(nullptr, dev::launch_score_read(state, n, out, (hipStream_t)s));
+    return DPENV_OK;
+}
+
+extern "C" int dpenv_score_summary(const void* state, int32_t n, double* out, void* workspace, dpenv_stream s)
+{
+    if (n < 1) return fail(nullptr, DPENV_EINVAL, "dpenv_score_summary: n = %d, must be >= 1", n);
+    if (!state || (reinterpret_cast<uintptr_t>(state) & 15u)) return fail(nullptr, DPENV_EINVAL, "dpenv_score_summary: state is NULL or not 16-byte aligned");
+    if (!out) return fail(nullptr, DPENV_EINVAL, "dpenv_score_summary: out is NULL");
+    if (!workspace) return fail(nullptr, DPENV_EINVAL, "dpenv_score_summary: workspace is NULL (dpenv_score_summary_workspace_bytes)");
+    HIP_TRY(nullptr, dev::launch_score_summary(state, n, out, (double*)workspace, (hipStream_t)s));
+    return DPENV_OK;
+}
+
 extern "C" int dpenv_adv_sum(const float* adv, int64_t count, float* sum_out, dpenv_stream s)
 {
     if (!adv || !sum_out || count <= 0) return fail(nullptr, DPENV_EINVAL, "dpenv_adv_sum: bad argument");

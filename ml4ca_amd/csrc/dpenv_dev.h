@@ -333,6 +333,19 @@ constexpr bool ws_reff(int mode, bool ext, int ka) { return ws_integ(mode, ext, 
 // for the two split arithmetics, all exact and exact actor - not f16 (dpenv_policy_ws.h has the measurements)
 constexpr int ws_roles(int prec, int groups) { return (groups == 2 && prec != PREC_F16) ? 3 : 2; }
 
+// ---- the streaming score card (dpenv_score_*; kernels in dpenv_score_dev.h): the arguments of one accumulate call ----
+struct ScoreArgs {
+    uint4* state;
+    const void* obs;            // [T][n][obs_stride] f32 or bf16, columns 0..2 read
+    const float* act;           // [T][n][act_stride], columns 0..2 read
+    const float* rew;           // [T][n]
+    const uint8_t* done;        // [T][n]
+    const float* integ;         // [T][n][3]
+    int T, n, obs_stride, act_stride, cut_at_end;
+    float dt;
+    float norm[3], coeff[3], rps[3];
+};
+
 // ---- launchers: called by dpenv_api.hip, defined by the translation unit that owns the kernels; not exported from libdpenv.so ----
 namespace __attribute__((visibility("hidden"))) dev {
 // dpenv_kernels.hip.  ves: VES_* (where the vessel of a lane comes from)
@@ -352,6 +365,12 @@ hipError_t launch_thrust_map(const VesselDev* vd, const float* n_pct, const floa
 int64_t gae_workspace_bytes(int n);
 hipError_t launch_gae(const float* rew, const float* val, const uint8_t* end, const float* boot, const float* last_val, int T, int n,
                       float gamma, float lam, float* adv, float* ret, double* workspace, double* stats, hipStream_t s);
+// the score card: state / workspace sizes, the block scan (obs_bf16: the obs rows are bf16), the [13][n] read-out and the two-stage summary
+int64_t score_state_bytes(int n);
+int64_t score_summary_workspace_bytes(int n);
+hipError_t launch_score(const ScoreArgs* a, int obs_bf16, hipStream_t s);
+hipError_t launch_score_read(const void* state, int n, double* out, hipStream_t s);
+hipError_t launch_score_summary(const void* state, int n, double* out, double* workspace, hipStream_t s);
 hipError_t launch_sum(const float* x, int64_t count, const float* mean, float* out, hipStream_t s);
 hipError_t launch_adv_apply(float* x, int64_t count, const float* mean, const float* std, const double* stats, double total_count,
                             hipStream_t s);

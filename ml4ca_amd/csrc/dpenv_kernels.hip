@@ -1263,6 +1263,8 @@ __global__ __launch_bounds__(SUMB) void adv_apply_kernel(float* __restrict__ x, 
 constexpr int SUM_MAXGRID = 2048;
 __device__ double g_sum_partials[2 * SUM_MAXGRID];
 
+#include "dpenv_score_dev.h"
+
 }  // namespace dpenv
 
 // =============================================================================================
@@ -1403,6 +1405,36 @@ hipError_t dev::launch_gae(const float* rew, const float* val, const uint8_t* en
     if (e != hipSuccess || !stats) return e;
     // the vector and the scalar form size their grids differently; the workspace is sized for the larger (scalar) one
     hipLaunchKernelGGL(gae_finalize_kernel, dim3(1), dim3(256), 0, s, (const double*)parts, grid, stats);
+    return hipGetLastError();
+}
+
+int64_t dev::score_state_bytes(int n) { return (int64_t)n * SCORE_STREAMS * 16; }
+
+int64_t dev::score_summary_workspace_bytes(int n) { return (((int64_t)n + 63) / 64) * SCORE_NOUT * 3 * (int64_t)sizeof(double); }
+
+hipError_t dev::launch_score(const ScoreArgs* a, int obs_bf16, hipStream_t s)
+{
+    // plain strided row loads: 0.4 of HBM at 65 536 envs x 50 rows, above the bar set for building an LDS-transposed row fetch
+    // (profiles/LAB_NOTES.md)
+    const dim3 grid((a->n + 63) / 64);
+    if (obs_bf16) hipLaunchKernelGGL(score_kernel<true>, grid, dim3(64), 0, s, *a);
+    else hipLaunchKernelGGL(score_kernel<false>, grid, dim3(64), 0, s, *a);
+    return hipGetLastError();
+}
+
+hipError_t dev::launch_score_read(const void* state, int n, double* out, hipStream_t s)
+{
+    hipLaunchKernelGGL(score_read_kernel, dim3((n + 63) / 64), dim3(64), 0, s, (const uint4*)state, n, out);
+    return hipGetLastError();
+}
+
+hipError_t dev::launch_score_summary(const void* state, int n, double* out, double* workspace, hipStream_t s)
+{
+    const int grid = (n + 63) / 64;
+    hipLaunchKernelGGL(score_summary_partial_kernel, dim3(grid), dim3(64), 0, s, (const uint4*)state, n, workspace);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(score_summary_final_kernel, dim3(1), dim3(256), 0, s, (const double*)workspace, grid, out);
     return hipGetLastError();
 }
 

@@ -33,6 +33,7 @@ def evaluate_actor(ac, dev, preset, precision, seed, out=print, eval_envs=1024):
     fixed starts, deterministic policy) and the thesis' 4-corner box test with its two metrics - IAE (results/all_plots/common.py:60-74) and
     the energy-equivalent work of the thruster power model (box_test/plot_act.py:128-135,184-211)."""
     from ml4ca_amd import evaluate as EV
+    from ml4ca_amd.deploy import dp_controller_defaults
     from ml4ca_amd.policy import policy_rollout
     nominal = ml4ca_amd.default_vessel(preset)
     env6 = ml4ca_amd.BatchedRevoltEnv(6, device=dev, auto_reset=False, testing=True, vessel_params=nominal)
@@ -46,13 +47,27 @@ def evaluate_actor(ac, dev, preset, precision, seed, out=print, eval_envs=1024):
     # of currents around it: +-0.1 m/s, +-90 deg, one draw per env)
     for tag, spread, cur in (('nominal hull', 0.0, None), ('hulls +-15 %', 0.15, None), ('hulls +-30 %', 0.30, None), ('hulls +-50 %', 0.50, None),
                              ('current 0.2 m/s @ 135 deg', 0.0, (0.0, 0.0)), ('currents 0.2 +-0.1 m/s, 135 +-90 deg', 0.0, (0.1, 1.5708))):
-        env = ml4ca_amd.BatchedRevoltEnv(nb, device=dev, terminate=False, time_limit=False, seed=seed + 77, vessel_params=nominal, current=cur is not None)
-        if spread > 0:
-            env.set_vessel_randomisation(spread, nominal=nominal)          # one draw per env at the reset below; no resets after it
-        if cur is not None:
-            env.set_current(torch.full((nb,), 0.2, device=dev), torch.full((nb,), 2.35619, device=dev))
-            if cur[0] > 0:
-                env.set_current_randomisation(cur[0], cur[1])              # one draw per env at the reset below
+        def make_env():
+            env = ml4ca_amd.BatchedRevoltEnv(nb, device=dev, terminate=False, time_limit=False, seed=seed + 77, vessel_params=nominal, current=cur is not None)
+            if spread > 0:
+                env.set_vessel_randomisation(spread, nominal=nominal)      # one draw per env at the first reset; no resets after it
+            if cur is not None:
+                env.set_current(torch.full((nb,), 0.2, device=dev), torch.full((nb,), 2.35619, device=dev))
+                if cur[0] > 0:
+                    env.set_current_randomisation(cur[0], cur[1])          # one draw per env at the first reset
+            return env
+
+        def baseline():
+            # the classical chain on the same envs, hulls and currents (a handle made the same way draws the same ones): PID + pseudo-inverse
+            # with the pole-placement defaults of the NOMINAL hull (deploy.dp_controller_defaults), flown in 50-step launches
+            envb = make_env()
+            envb.set_dp_controller(dp_controller_defaults(nominal))
+            sb = EV.baseline_box_test_streamed(envb, T=T, start=torch.zeros((3, nb), device=dev), chunk=50)
+            out('eval  box test (1250 steps, %d envs), %-13s: baseline PID + pseudo-inverse IAE %.2f (worst env %.2f)  work bow/port/star %s' % (
+                nb, tag, float(sb['iae'].mean()), float(sb['iae'].max()), [round(float(x), 1) for x in sb['work'].mean(0)]))
+            return {'IAE': float(sb['iae'].mean()), 'IAE_worst': float(sb['iae'].max()), 'work': [float(x) for x in sb['work'].mean(0)]}
+
+        env = make_env()
         ac.upload(env, precision=precision)
         start = torch.zeros((3, nb), device=dev)
         if nb != 1024:
@@ -64,6 +79,7 @@ def evaluate_actor(ac, dev, preset, precision, seed, out=print, eval_envs=1024):
                 nb, tag, float(iae_tot.mean()), float(iae_tot.max()), [round(float(x), 1) for x in w.mean(0)], rps))
             res[tag] = {'IAE': float(iae_tot.mean()), 'IAE_worst': float(iae_tot.max()), 'work': [float(x) for x in w.mean(0)], 'reward_per_step': rps}
             del env
+            res[tag]['baseline'] = baseline()
             continue
         env.reset(init=torch.zeros((6, nb), device=dev), new_ref=start.clone())
         steps, refs = EV.box_schedule(start)
@@ -79,6 +95,7 @@ def evaluate_actor(ac, dev, preset, precision, seed, out=print, eval_envs=1024):
         res[tag] = {'IAE': float(iae_tot.mean()), 'IAE_worst': float(iae_tot.max()), 'work': [float(x) for x in w.mean(0)],
                     'corner_error_m': float(pos.mean()), 'reward_per_step': float(o['rew'].mean())}
         del env
+        res[tag]['baseline'] = baseline()
     return res
 
 

@@ -614,6 +614,71 @@ int dpenv_score_read(const void* state, int32_t n, double* out, dpenv_stream s);
 int64_t dpenv_score_summary_workspace_bytes(int32_t n);
 int dpenv_score_summary(const void* state, int32_t n, double* out, void* workspace, dpenv_stream s);
 
+/* ---- the classical baseline in the closed loop: a PID motion controller feeding a pseudo-inverse thrust allocation (additive to ABI 6) --
+ * The thesis compares the RL allocator with the classical chain; the reference tree has neither its PID nor its pseudo-inverse node, so the
+ * law is build-defined, like the plant.  While it is on, dpenv_controller_rollout flies it per env and per control step on the observation
+ * o as the env forms it (make_obs, whatever wrap_mode the handle uses): e = o[0:3] the body-frame pose error, nu = o[3:6].  State per env:
+ * z[3], the error integral.  In f32, in exactly this order (the build has -ffp-contract=off; sqrtf and / are correctly rounded):
+ *     z_j   = fminf(fmaxf(z_j + dt * e_j, -z_bound_j), z_bound_j)                    j = 0,1,2   (dt = n_substeps * substep_dt in f32)
+ *     tau_j = -((kp_j * e_j + kd_j * nu_j) + ki_j * z_j);   tau_j = fminf(fmaxf(tau_j, -tau_max_j), tau_max_j)
+ *     f_m   = (G[m][0] * tau_0 + G[m][1] * tau_1) + G[m][2] * tau_2                  m = 0..4: Fy_bow, Fx_port, Fy_port, Fx_star, Fy_star
+ *     bow:      Kb = f_0 >= 0 ? kf[0] : kr_bow;   n_b = copysignf(sqrtf(fabsf(f_0) / Kb), f_0)
+ *     stern i:  F = sqrtf(Fx * Fx + Fy * Fy);     n_i = sqrtf(F / kf[i])             (port: m = 1, 2, kf[1]; star: m = 3, 4, kf[2])
+ *               (sin_i, cos_i) = F > f_eps ? (Fy / F, Fx / F) : (0, 1)
+ *     action = [ fminf(fmaxf(n_b / 100, -1), 1), fminf(n_port / 100, 1), fminf(n_star / 100, 1), sin_port, cos_port, sin_star, cos_star ]
+ * - the final variant's continuous-angle action (customEnv.py:227-235): the bow tunnel thruster fixed at pi / 2, the stern pods free with
+ * thrust >= 0; a saturated command is not redistributed.  G is the weighted pseudo-inverse W^-1 T' (T W^-1 T')^-1 of the extended-thrust
+ * matrix T = [[0, 1, 0, 1, 0], [1, 0, 1, 0, 1], [lx_bow, -ly_port, lx_port, -ly_star, lx_star]], W = diag(weight), computed in f64 and
+ * rounded once to f32 (dpenv_dp_allocation_matrix) - from the controller's NOMINAL lever arms: a randomised hull is flown by a controller
+ * that does not know it.  z is zeroed by every reset: dpenv_reset (for the envs it re-draws), auto-reset (an env that ends an episode has
+ * z = 0 before its new episode's first action) and turning the controller on (every env).  A launch's first input is rebuilt from the stored
+ * state, its thrust columns continued as dpenv_policy_rollout's, and z is updated at every action: two launches of T/2 write the rows of
+ * one launch of T.
+ * Supported: the final variant with continuous angles and extended_state, AOS rows, f32 or bf16 obs rows (the law sees the f32 observation);
+ * the shared hull, the thrust-loss preset, per-env hulls and their randomisation, constant, drifting and per-episode currents, auto-reset,
+ * with or without the reference filter.  Vessel classes (n_classes > 1), any other variant and a handle with the integral action on:
+ * DPENV_EINVAL with the set named.  The controller is a launch form, not a mode: dpenv_step, dpenv_rollout and dpenv_policy_rollout keep
+ * working while it is on (they leave z alone).  ml4ca_amd.deploy.BatchedDPController is the host statement of the law. */
+typedef struct dpenv_dp_controller {
+    uint32_t struct_size;
+    float kp[3], kd[3], ki[3];   /* finite */
+    float z_bound[3];            /* |z_j| <= z_bound_j, >= 0 */
+    float tau_max[3];            /* |tau_j| <= tau_max_j, >= 0: (69 N, 30 N, 80 Nm) in SupervisedTau.py:37 */
+    float G[5][3];               /* dpenv_dp_allocation_matrix of the nominal lever arms, finite */
+    float kf[3];                 /* thrust constants ahead: bow, port, star, > 0 */
+    float kr_bow;                /* bow astern, > 0 */
+    float f_eps;                 /* a stern force at or below it keeps the direction (sin, cos) = (0, 1); >= 0 [N] */
+} dpenv_dp_controller;
+/* Pure host function, f64 inside: lx, ly the lever arms of bow, port, star [m] (ly[0] is not used: the tunnel thruster pushes sideways
+ * only); weight[5] > 0 per column of T.  DPENV_EINVAL if T W^-1 T' is singular. */
+int dpenv_dp_allocation_matrix(const float lx[3], const float ly[3], const float weight[5], float G_out[5][3]);
+/* c = NULL turns the controller off.  Turning it on zeroes z of every env.  Refused, before any state changes: NaN or non-finite gains and
+ * G, NaN or negative bounds and f_eps, kf <= 0, kr_bow <= 0, and a handle outside the supported set. */
+int dpenv_set_dp_controller(dpenv_handle h, const dpenv_dp_controller* c, dpenv_stream s);
+/* The checkpoint path of z, next to dpenv_get_state: device float[3][n_envs].  DPENV_EINVAL while the controller is off. */
+int dpenv_get_dp_controller_state(dpenv_handle h, float* z_out, dpenv_stream s);
+int dpenv_set_dp_controller_state(dpenv_handle h, const float* z_in, dpenv_stream s);
+typedef struct dpenv_controller_rollout_io {
+    uint32_t struct_size;    /* sizeof(dpenv_controller_rollout_io), ABI check */
+    int32_t T;
+    void* obs;               /* [T][n][9]  the controller's input at step t; f32 or bf16 */
+    float* act;              /* [T][n][7]  its action */
+    float* reward;           /* [T][n] */
+    uint8_t* done;           /* [T][n]  DPENV_DONE_* bits */
+    void* last_obs;          /* [n][9]  the controller's input of the next launch */
+    float* ref_out;          /* [T][n][3] the eta_d obs[t] was formed against, or NULL; needs the reference filter on */
+    int32_t n_switch;
+    int32_t switch_step[DPENV_MAX_SWITCH];
+    const float* refs;       /* [n_switch][3][n] */
+} dpenv_controller_rollout_io;
+/* T steps of (law -> env.step) in one launch: the row conventions of dpenv_policy_rollout, so dpenv_score_accumulate consumes the blocks
+ * unchanged.  With the reference filter on (dpenv_set_reference_filter) the switches set its targets and every step's new_ref is its
+ * position, exactly as in dpenv_policy_rollout_deployed.  Stream-ordered, no allocation and no host synchronisation: graph-capturable. */
+int dpenv_controller_rollout(dpenv_handle h, const dpenv_controller_rollout_io* io, dpenv_stream s);
+/* The stateless allocation of the law (its f_m, bow and stern lines) for n wrenches: tau device float[3][n] -> action_out device
+ * float[n][7].  Handle-free, like dpenv_thrust_map; of c only G, kf, kr_bow and f_eps are read, the whole struct is validated. */
+int dpenv_thrust_alloc(const dpenv_dp_controller* c, const float* tau, float* action_out, int32_t n, dpenv_stream s);
+
 int dpenv_abi_version(void);
 
 #ifdef __cplusplus

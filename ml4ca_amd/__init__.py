@@ -7,7 +7,7 @@ environment interface.  See DESIGN.md / INTEGRATION.md.
 from ._lib import (AOS, BF16, DONE_FAULT, DONE_TERMINAL, DONE_TIMELIMIT, F32, FINAL, FULL, LIMITED, SIMPLE, SOA,  # noqa: F401
                    DpenvError, default_vessel)
 from .env import (ENVIRONMENTS, BatchedRevoltEnv, Revolt, RevoltFinal, RevoltLimited, RevoltSimple,  # noqa: F401
-                  thrust_map, variant_constants)
+                  thrust_alloc, thrust_map, variant_constants)
 
 __all__ = ['BatchedRevoltEnv', 'Revolt', 'RevoltSimple', 'RevoltLimited', 'RevoltFinal', 'ENVIRONMENTS',
-           'thrust_map', 'variant_constants', 'default_vessel', 'DpenvError']
+           'thrust_alloc', 'thrust_map', 'variant_constants', 'default_vessel', 'DpenvError']

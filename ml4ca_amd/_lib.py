@@ -83,6 +83,18 @@ class ReferenceFilter(C.Structure):
     _fields_ = [('struct_size', C.c_uint32), ('omega', C.c_float * 3), ('zeta', C.c_float * 3)]
 
 
+class DPController(C.Structure):
+    _fields_ = [('struct_size', C.c_uint32), ('kp', C.c_float * 3), ('kd', C.c_float * 3), ('ki', C.c_float * 3),
+                ('z_bound', C.c_float * 3), ('tau_max', C.c_float * 3), ('G', C.c_float * 3 * 5), ('kf', C.c_float * 3),
+                ('kr_bow', C.c_float), ('f_eps', C.c_float)]
+
+
+class ControllerRolloutIO(C.Structure):
+    _fields_ = [('struct_size', C.c_uint32), ('T', C.c_int32), ('obs', C.c_void_p), ('act', C.c_void_p), ('reward', C.c_void_p),
+                ('done', C.c_void_p), ('last_obs', C.c_void_p), ('ref_out', C.c_void_p), ('n_switch', C.c_int32),
+                ('switch_step', C.c_int32 * 8), ('refs', C.c_void_p)]
+
+
 class ScoreIO(C.Structure):
     _fields_ = [('struct_size', C.c_uint32), ('T', C.c_int32), ('n', C.c_int32), ('obs', C.c_void_p), ('act', C.c_void_p),
                 ('rew', C.c_void_p), ('done', C.c_void_p), ('integ', C.c_void_p), ('obs_dtype', C.c_int32), ('obs_stride', C.c_int32),
@@ -158,6 +170,12 @@ SYMBOLS = {
     'dpenv_score_read': (C.c_int, [_VP, _I32, _VP, _VP]),
     'dpenv_score_summary_workspace_bytes': (C.c_int64, [_I32]),
     'dpenv_score_summary': (C.c_int, [_VP, _I32, _VP, _VP, _VP]),
+    'dpenv_dp_allocation_matrix': (C.c_int, [C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float * 3 * 5)]),
+    'dpenv_set_dp_controller': (C.c_int, [_VP, C.POINTER(DPController), _VP]),
+    'dpenv_get_dp_controller_state': (C.c_int, [_VP, _VP, _VP]),
+    'dpenv_set_dp_controller_state': (C.c_int, [_VP, _VP, _VP]),
+    'dpenv_controller_rollout': (C.c_int, [_VP, C.POINTER(ControllerRolloutIO), _VP]),
+    'dpenv_thrust_alloc': (C.c_int, [C.POINTER(DPController), _VP, _VP, _I32, _VP]),
 }
 
 _lib = None

@@ -77,6 +77,8 @@ struct dpenv_s {
     IntegArgs integ;        // its parameters and per-env state (float4 [n]: I | count), allocated by the first dpenv_set_integral_action
     bool reff_on;           // dpenv_set_reference_filter: the closed loop runs the *_reff kernels with `reff`
     FilterArgs reff;        // its f32 coefficients and per-env state (float4 [3][n]: pos | vel | acc | target), allocated on first use
+    bool ctrl_on;           // dpenv_set_dp_controller: dpenv_controller_rollout flies the baseline law with `ctrl`
+    ControlArgs ctrl;       // its numbers and per-env state (float4 [n]: z | pad), allocated by the first dpenv_set_dp_controller
     int device;
     std::string err;
 };
@@ -342,6 +344,8 @@ extern "C" int dpenv_create(const dpenv_config* cfg, const float* vessel_params,
     std::memset(&h->integ, 0, sizeof h->integ);
     h->reff_on = false;
     std::memset(&h->reff, 0, sizeof h->reff);
+    h->ctrl_on = false;
+    std::memset(&h->ctrl, 0, sizeof h->ctrl);
     std::memset(&h->pol, 0, sizeof h->pol);
 
     VesselDev tab[MAX_CLASSES];
@@ -487,6 +491,7 @@ extern "C" int dpenv_destroy(dpenv_handle h)
     if (h->pol_raw) (void)hipFree(h->pol_raw);
     if (h->integ.state) (void)hipFree(h->integ.state);
     if (h->reff.state) (void)hipFree(h->reff.state);
+    if (h->ctrl.z) (void)hipFree(h->ctrl.z);
     for (int k = 0; k < 2; ++k) if (h->pol_read[k]) (void)hipEventDestroy(h->pol_read[k]);
     if (h->loss_ev) (void)hipEventDestroy(h->loss_ev);
     if (h->loss_host) (void)hipHostFree(h->loss_host);
@@ -756,6 +761,7 @@ extern "C" int dpenv_reset(dpenv_handle h, const uint8_t* mask, const float* ini
     HIP_TRY(h, dev::launch_reset(&a, h->mode, h->cfg.extended_state, mask, init, ref, (hipStream_t)s));
     if (h->integ_on) HIP_TRY(h, dev::launch_integ_clear(h->integ.state, mask, h->cfg.n_envs, (hipStream_t)s));   // new episodes start with I = 0
     if (h->reff_on) HIP_TRY(h, dev::launch_reff_rest(a.RF, h->reff.state, mask, h->cfg.n_envs, (hipStream_t)s));   // ... the filter at rest
+    if (h->ctrl_on) HIP_TRY(h, dev::launch_control_state(h->ctrl.z, nullptr, mask, h->cfg.n_envs, 2, (hipStream_t)s));   // ... the baseline's z = 0
     // the reset kernel writes the lagged thrust columns (S3) of the envs it re-draws: a full reset makes them valid everywhere, a
     // masked one leaves the validity of the other envs' columns as it was (it used to drop the lag of every env)
     if (!mask) h->lag_valid = true;
@@ -1384,6 +1390,159 @@ extern "C" int dpenv_set_integral_state(dpenv_handle h, const float* I_in, const
     if (!I_in && !count_in) return fail(h, DPENV_EINVAL, "dpenv_set_integral_state: NULL argument");
     DeviceGuard dev_guard(h->device);
     HIP_TRY(h, dev::launch_integ_state_io(h->integ.state, (float*)I_in, (int32_t*)count_in, h->cfg.n_envs, 1, (hipStream_t)s));
+    return DPENV_OK;
+}
+
+// ---- the baseline DP controller: PID + pseudo-inverse allocation in the closed loop (dpenv.h) ---------------------------------------
+extern "C" int dpenv_dp_allocation_matrix(const float lx[3], const float ly[3], const float weight[5], float G_out[5][3])
+{
+    if (!lx || !ly || !weight || !G_out) return fail(nullptr, DPENV_EINVAL, "dpenv_dp_allocation_matrix: NULL argument");
+    for (int k = 0; k < 3; ++k)
+        if (!std::isfinite(lx[k]) || !std::isfinite(ly[k])) return fail(nullptr, DPENV_EINVAL, "dpenv_dp_allocation_matrix: lever arms must be finite");
+    for (int k = 0; k < 5; ++k)
+        if (!std::isfinite(weight[k]) || !(weight[k] > 0.0f)) return fail(nullptr, DPENV_EINVAL, "dpenv_dp_allocation_matrix: weight[%d] must be finite and > 0", k);
+    // deploy.allocation_matrix is the same recipe in the same order: V = W^-1 T', M = T V, G = V adj(M) / det(M)
+    const double T[3][5] = {{0.0, 1.0, 0.0, 1.0, 0.0},
+                            {1.0, 0.0, 1.0, 0.0, 1.0},
+                            {(double)lx[0], -(double)ly[1], (double)lx[1], -(double)ly[2], (double)lx[2]}};
+    double V[5][3], M[3][3];
+    for (int m = 0; m < 5; ++m) for (int j = 0; j < 3; ++j) V[m][j] = T[j][m] / (double)weight[m];
+    for (int r = 0; r < 3; ++r) for (int c = 0; c < 3; ++c) {
+        double acc = 0.0;
+        for (int m = 0; m < 5; ++m) acc += T[r][m] * V[m][c];
+        M[r][c] = acc;
+    }
+    double adj[3][3];                                            // adj[r][c] = cofactor of M[c][r]
+    for (int r = 0; r < 3; ++r) for (int c = 0; c < 3; ++c) {
+        const int r1 = (c + 1) % 3, r2 = (c + 2) % 3, c1 = (r + 1) % 3, c2 = (r + 2) % 3;
+        adj[r][c] = M[r1][c1] * M[r2][c2] - M[r1][c2] * M[r2][c1];
+    }
+    const double det = (M[0][0] * adj[0][0] + M[0][1] * adj[1][0]) + M[0][2] * adj[2][0];
+    if (!std::isfinite(det) || det == 0.0) return fail(nullptr, DPENV_EINVAL, "dpenv_dp_allocation_matrix: T W^-1 T' is singular");
+    for (int m = 0; m < 5; ++m) for (int c = 0; c < 3; ++c) {
+        double acc = 0.0;
+        for (int j = 0; j < 3; ++j) acc += V[m][j] * adj[j][c];
+        G_out[m][c] = (float)(acc / det);
+    }
+    return DPENV_OK;
+}
+
+// the law's numbers into ControlArgs, or an error message
+static const char* control_check(const dpenv_dp_controller* c, ControlArgs& g)
+{
+    if (c->struct_size != sizeof(dpenv_dp_controller)) return "dpenv_dp_controller ABI mismatch";
+    for (int j = 0; j < 3; ++j) {
+        if (!std::isfinite(c->kp[j]) || !std::isfinite(c->kd[j]) || !std::isfinite(c->ki[j])) return "DP controller: kp, kd and ki must be finite";
+        if (std::isnan(c->z_bound[j]) || c->z_bound[j] < 0.0f) return "DP controller: z_bound must be >= 0";
+        if (std::isnan(c->tau_max[j]) || c->tau_max[j] < 0.0f) return "DP controller: tau_max must be >= 0";
+        if (!std::isfinite(c->kf[j]) || !(c->kf[j] > 0.0f)) return "DP controller: kf must be finite and > 0";
+    }
+    if (!std::isfinite(c->kr_bow) || !(c->kr_bow > 0.0f)) return "DP controller: kr_bow must be finite and > 0";
+    if (std::isnan(c->f_eps) || c->f_eps < 0.0f) return "DP controller: f_eps must be >= 0";
+    for (int m = 0; m < 5; ++m) for (int j = 0; j < 3; ++j) if (!std::isfinite(c->G[m][j])) return "DP controller: G must be finite";
+    for (int j = 0; j < 3; ++j) {
+        g.kp[j] = c->kp[j]; g.kd[j] = c->kd[j]; g.ki[j] = c->ki[j]; g.zb[j] = c->z_bound[j]; g.tmax[j] = c->tau_max[j]; g.kf[j] = c->kf[j];
+    }
+    std::memcpy(g.G, c->G, sizeof g.G);
+    g.kr_bow = c->kr_bow;
+    g.f_eps = c->f_eps;
+    return nullptr;
+}
+
+#define CONTROL_SET_MSG                                                                                                              \
+    "the DP controller runs with the final variant (continuous angles), extended_state, AOS action and observation rows, one vessel " \
+    "class (the shared hull, the thrust-loss preset or per-env hulls) and the integral action off"
+static bool control_config_ok(dpenv_handle h)
+{
+    return control_has(h->mode, h->cfg.extended_state != 0) && h->cfg.action_layout == DPENV_AOS && h->cfg.obs_layout == DPENV_AOS &&
+           h->n_classes == 1 && !h->integ_on;
+}
+
+extern "C" int dpenv_set_dp_controller(dpenv_handle h, const dpenv_dp_controller* c, dpenv_stream s)
+{
+    if (!h) return DPENV_EINVAL;
+    if (!c) {
+        h->ctrl_on = false;
+        return DPENV_OK;
+    }
+    ControlArgs g;
+    std::memset(&g, 0, sizeof g);
+    if (const char* why = control_check(c, g)) return fail(h, DPENV_EINVAL, "%s", why);
+    if (!control_config_ok(h)) return fail(h, DPENV_EINVAL, "dpenv_set_dp_controller: " CONTROL_SET_MSG);
+    DeviceGuard dev_guard(h->device);
+    float4* z = h->ctrl.z;
+    if (!z) {
+        void* p = nullptr;
+        if (hipMalloc(&p, sizeof(float4) * (size_t)h->cfg.n_envs) != hipSuccess) return fail(h, DPENV_ENOMEM, "hipMalloc of the DP controller state failed");
+        z = (float4*)p;
+        h->ctrl.z = z;                                          // (kept by a later call even if the launch below fails)
+    }
+    HIP_TRY(h, dev::launch_control_state(z, nullptr, nullptr, h->cfg.n_envs, 2, (hipStream_t)s));
+    g.z = z;
+    g.dt = h->cfg.substep_dt * (float)h->cfg.n_substeps;
+    h->ctrl = g;
+    h->ctrl_on = true;
+    return DPENV_OK;
+}
+
+extern "C" int dpenv_get_dp_controller_state(dpenv_handle h, float* z_out, dpenv_stream s)
+{
+    if (!h) return DPENV_EINVAL;
+    if (!h->ctrl_on) return fail(h, DPENV_EINVAL, "dpenv_get_dp_controller_state: the DP controller is off");
+    if (!z_out) return fail(h, DPENV_EINVAL, "dpenv_get_dp_controller_state: NULL argument");
+    DeviceGuard dev_guard(h->device);
+    HIP_TRY(h, dev::launch_control_state(h->ctrl.z, z_out, nullptr, h->cfg.n_envs, 0, (hipStream_t)s));
+    return DPENV_OK;
+}
+
+extern "C" int dpenv_set_dp_controller_state(dpenv_handle h, const float* z_in, dpenv_stream s)
+{
+    if (!h) return DPENV_EINVAL;
+    if (!h->ctrl_on) return fail(h, DPENV_EINVAL, "dpenv_set_dp_controller_state: the DP controller is off");
+    if (!z_in) return fail(h, DPENV_EINVAL, "dpenv_set_dp_controller_state: NULL argument");
+    DeviceGuard dev_guard(h->device);
+    HIP_TRY(h, dev::launch_control_state(h->ctrl.z, (float*)z_in, nullptr, h->cfg.n_envs, 1, (hipStream_t)s));
+    return DPENV_OK;
+}
+
+extern "C" int dpenv_controller_rollout(dpenv_handle h, const dpenv_controller_rollout_io* io, dpenv_stream s)
+{
+    if (!h) return DPENV_EINVAL;
+    DeviceGuard dev_guard(h->device);
+    if (!h->ctrl_on) return fail(h, DPENV_EINVAL, "dpenv_controller_rollout: the DP controller is off (dpenv_set_dp_controller)");
+    if (!io || io->struct_size != sizeof(dpenv_controller_rollout_io)) return fail(h, DPENV_EINVAL, "dpenv_controller_rollout_io ABI mismatch");
+    if (!control_config_ok(h)) return fail(h, DPENV_EINVAL, "dpenv_controller_rollout: " CONTROL_SET_MSG);
+    if (io->T <= 0 || !io->obs || !io->act || !io->reward || !io->done || !io->last_obs)
+        return fail(h, DPENV_EINVAL, "T > 0 and the obs, act, reward, done and last_obs blocks are required");
+    if (io->ref_out && !h->reff_on)
+        return fail(h, DPENV_EINVAL, "dpenv_controller_rollout: ref_out needs the reference filter on (dpenv_set_reference_filter)");
+    if (io->n_switch < 0 || io->n_switch > DPENV_MAX_SWITCH || (io->n_switch > 0 && !io->refs))
+        return fail(h, DPENV_EINVAL, "bad setpoint schedule");
+    for (int k = 0; k < io->n_switch; ++k)
+        if (io->switch_step[k] < 0 || io->switch_step[k] >= io->T || (k > 0 && io->switch_step[k] <= io->switch_step[k - 1]))
+            return fail(h, DPENV_EINVAL, "switch_step must be strictly increasing within [0, T)");
+    StepArgs a = h->args;
+    bind_optional(h, a, (hipStream_t)s);
+    ControlArgs ca = h->ctrl;
+    ca.T = io->T; ca.obs = io->obs; ca.act = io->act; ca.rew = io->reward; ca.done = io->done; ca.last_obs = io->last_obs;
+    ca.n_switch = io->n_switch; ca.refs = io->refs;
+    for (int k = 0; k < io->n_switch; ++k) ca.switch_step[k] = io->switch_step[k];
+    ca.use_lag = h->lag_valid ? 1 : 0;
+    FilterArgs fa = h->reff;
+    fa.out = io->ref_out;
+    const hipError_t e = dev::launch_controller_rollout(&a, &ca, h->reff_on ? &fa : nullptr, rollout_ves(vessel_source(h)), (hipStream_t)s);
+    if (e != hipSuccess) return fail(h, DPENV_EHIP, "controller launch failed: %s", hipGetErrorString(e));
+    h->lag_valid = true;
+    return DPENV_OK;
+}
+
+extern "C" int dpenv_thrust_alloc(const dpenv_dp_controller* c, const float* tau, float* action_out, int32_t n, dpenv_stream s)
+{
+    if (!c || !tau || !action_out || n <= 0) return fail(nullptr, DPENV_EINVAL, "dpenv_thrust_alloc: bad argument");
+    ControlArgs g;
+    std::memset(&g, 0, sizeof g);
+    if (const char* why = control_check(c, g)) return fail(nullptr, DPENV_EINVAL, "%s", why);
+    HIP_TRY(nullptr, dev::launch_thrust_alloc(&g, tau, action_out, n, (hipStream_t)s));
     return DPENV_OK;
 }
 

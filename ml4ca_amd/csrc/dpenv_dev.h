@@ -204,6 +204,28 @@ struct FilterArgs {
     float gam[3][3];          // Gamma_j
 };
 
+// the baseline DP controller in the closed loop (dpenv_set_dp_controller / dpenv_controller_rollout; include/dpenv.h has the law,
+// dpenv_control_dev.h the kernels): the law's numbers, its per-env state and the I/O of one launch
+struct ControlArgs {
+    float4* z;                // [n] the error integral z[0..2] (one pad)
+    float kp[3], kd[3], ki[3], zb[3], tmax[3];
+    float G[5][3];            // weighted pseudo-inverse of the extended-thrust matrix, rows Fy_bow, Fx_port, Fy_port, Fx_star, Fy_star
+    float kf[3], kr_bow;      // bow, port, star ahead; bow astern
+    float f_eps;
+    float dt;                 // n_substeps * substep_dt in f32
+    int32_t use_lag;          // as PolicyArgs.use_lag: the first observation takes its thrust columns from S3
+    // rollout I/O
+    int32_t T;
+    void* obs;                // [T][n][9]  controller input of step t; f32 or bf16
+    float* act;               // [T][n][7]  its action
+    float* rew;               // [T][n]
+    uint8_t* done;            // [T][n]
+    void* last_obs;           // [n][9]     controller input of the next launch
+    int32_t n_switch;
+    int32_t switch_step[MAX_SWITCH];
+    const float* refs;        // [n_switch][3][n]
+};
+
 // device-side weight packing (pack_policy_kernel): one dense network, DEVICE pointers
 struct PackNet {
     const float* W[5];        // W[l][in][out] row-major (tf.layers.dense kernel layout)
@@ -329,6 +351,21 @@ constexpr bool ws_integ(int mode, bool ext, int ka) { return mode == MODE_FINAL_
 // filter with the integral action
 constexpr bool reff_one_wave(int mode, bool ext, int ka) { return integ_one_wave(mode, ext, ka); }
 constexpr bool ws_reff(int mode, bool ext, int ka) { return ws_integ(mode, ext, ka); }
+// the baseline controller's closed loop (controller_rollout_kernel): the final variant with continuous angles and the extended state, with
+// and without the reference filter, one instantiation per vessel source below - vessel classes have none
+constexpr bool control_has(int mode, bool ext) { return mode == MODE_FINAL_CONT && ext; }
+template <typename F> hipError_t with_control_ves(int ves, F&& f)
+{
+    switch (ves) {
+    case VES_ARGS: return f(Int<VES_ARGS>{});
+#ifndef DPENV_DEV_FAST
+    case VES_ARGS_LOSS: return f(Int<VES_ARGS_LOSS>{});
+    case VES_ENV_VGPR: return f(Int<VES_ENV_VGPR>{});
+    case VES_ENV_RND: return f(Int<VES_ENV_RND>{});
+#endif
+    }
+    return hipErrorInvalidValue;
+}
 // waves per 64 envs of the two-wave form: an env and a network wave, plus a critic wave of its own (ROLES = 3) in the 128-env geometry
 // for the two split arithmetics, all exact and exact actor - not f16 (dpenv_policy_ws.h has the measurements)
 constexpr int ws_roles(int prec, int groups) { return (groups == 2 && prec != PREC_F16) ? 3 : 2; }
@@ -390,6 +427,12 @@ hipError_t launch_integ_state_io(float4* state, float* I, int32_t* c, int n, int
 // (x float[9][n] | r float[3][n], either may be NULL)
 hipError_t launch_reff_rest(const float4* RF, float4* state, const uint8_t* mask, int n, hipStream_t s);
 hipError_t launch_reff_state_io(float4* state, float* x, float* r, int n, int write, hipStream_t s);
+// dpenv_policy.hip, from dpenv_control_dev.h: the baseline controller's closed loop (fa != NULL: with the reference filter; ves as
+// launch_rollout's, classes excluded), its state (op 0 read into ext float[3][n], 1 write from it, 2 zero the envs of mask) and the
+// stateless allocation tau [3][n] -> action [n][7]
+hipError_t launch_controller_rollout(const StepArgs* a, const ControlArgs* ca, const FilterArgs* fa, int ves, hipStream_t s);
+hipError_t launch_control_state(float4* z, float* ext, const uint8_t* mask, int n, int op, hipStream_t s);
+hipError_t launch_thrust_alloc(const ControlArgs* ca, const float* tau, float* action, int n, hipStream_t s);
 // two-wave closed loop, dpenv_policy_ws.h; one arithmetic per translation unit: dpenv_policy_ws.hip PREC_F16, dpenv_policy_xws1.hip
 // PREC_F32, dpenv_policy_xws2.hip PREC_F32_ACTOR
 template <int PREC>

@@ -248,6 +248,135 @@ class BatchedReferenceFilter(object):
             self.r = torch.where(mask[None, :], ref, self.r)
 
 
+# ---- the classical baseline: PID motion controller + weighted pseudo-inverse allocation (include/dpenv.h has the law) -------------------
+DP_TAU_MAX = (69.0, 30.0, 80.0)                 # SupervisedTau.py:37
+DP_Z_BOUND = (10.0, 10.0, 2.0)
+DP_F_EPS = 1e-6
+
+
+def allocation_matrix(lx, ly, weight=(1.0, 1.0, 1.0, 1.0, 1.0)):
+    """G [5, 3] float64: the weighted pseudo-inverse W^-1 T' (T W^-1 T')^-1 of the extended-thrust matrix
+        T = [[0, 1, 0, 1, 0], [1, 0, 1, 0, 1], [lx_bow, -ly_port, lx_port, -ly_star, lx_star]],   W = diag(weight)
+    whose columns are Fy_bow, Fx_port, Fy_port, Fx_star, Fy_star; lx, ly in env order bow, port, star.  The recipe and the
+    operation order of dpenv_dp_allocation_matrix (V = W^-1 T', M = T V, G = V adj(M) / det(M)), which rounds the result to f32."""
+    lx, ly, w = [float(v) for v in lx], [float(v) for v in ly], [float(v) for v in weight]
+    if len(w) != 5 or not all(np.isfinite(v) and v > 0 for v in w):
+        raise ValueError('allocation_matrix: five finite weights > 0')
+    T = [[0.0, 1.0, 0.0, 1.0, 0.0], [1.0, 0.0, 1.0, 0.0, 1.0], [lx[0], -ly[1], lx[1], -ly[2], lx[2]]]
+    V = [[T[j][m] / w[m] for j in range(3)] for m in range(5)]
+    M = [[0.0] * 3 for _ in range(3)]
+    for r in range(3):
+        for c in range(3):
+            acc = 0.0
+            for m in range(5):
+                acc += T[r][m] * V[m][c]
+            M[r][c] = acc
+    adj = [[0.0] * 3 for _ in range(3)]
+    for r in range(3):
+        for c in range(3):
+            r1, r2, c1, c2 = (c + 1) % 3, (c + 2) % 3, (r + 1) % 3, (r + 2) % 3
+            adj[r][c] = M[r1][c1] * M[r2][c2] - M[r1][c2] * M[r2][c1]
+    det = (M[0][0] * adj[0][0] + M[0][1] * adj[1][0]) + M[0][2] * adj[2][0]
+    if not np.isfinite(det) or det == 0.0:
+        raise ValueError("allocation_matrix: T W^-1 T' is singular")
+    G = np.zeros((5, 3))
+    for m in range(5):
+        for c in range(3):
+            acc = 0.0
+            for j in range(3):
+                acc += V[m][j] * adj[j][c]
+            G[m, c] = acc / det
+    return G
+
+
+def dp_controller_defaults(vessel=None, omega=REFERENCE_FILTER_OMEGA, zeta=(1.0, 1.0, 1.0), weight=(1.0, 1.0, 1.0, 1.0, 1.0)):
+    """The baseline's default numbers for a hull (public parameter vector; None = the default hull), float64: Fossen's pole placement
+    with the reference filter's bandwidths - Kp = m omega^2, Kd = 2 zeta omega m - d, Ki = Kp omega / 10 with m = (m11, m22, m33) and
+    d = (Xu, Yv, Nr) - z_bound (10, 10, 2), tau_max (69, 30, 80) (SupervisedTau.py:37), f_eps 1e-6 N, the hull's thrust constants and
+    G = allocation_matrix of its lever arms.  Returns the dict BatchedDPController and env.set_dp_controller take."""
+    from . import _lib
+    v = np.asarray(_lib.default_vessel() if vessel is None else vessel, np.float64)
+    P = _lib.P
+    m = np.array([v[P['M11']], v[P['M22']], v[P['M33']]])
+    d = np.array([v[P['XU']], v[P['YV']], v[P['NR']]])
+    w, z = np.asarray(omega, np.float64), np.asarray(zeta, np.float64)
+    kp = m * w * w
+    lx, ly = v[P['LX_BOW']:P['LX_BOW'] + 3], v[P['LY_BOW']:P['LY_BOW'] + 3]
+    return dict(kp=kp, kd=2.0 * z * w * m - d, ki=kp * w / 10.0, z_bound=np.array(DP_Z_BOUND), tau_max=np.array(DP_TAU_MAX),
+                G=allocation_matrix(lx, ly, weight), kf=v[P['KF_BOW']:P['KF_BOW'] + 3].copy(), kr_bow=float(v[P['KR_BOW']]),
+                f_eps=DP_F_EPS, lx=lx.copy(), ly=ly.copy(), weight=np.asarray(weight, np.float64))
+
+
+class BatchedDPController(object):
+    """The baseline law for n envs on the host: the statement of include/dpenv.h, operation by operation.  With NumPy float32 on the CPU
+    (the default) it reproduces the closed-loop kernel's actions bit for bit; dtype=np.float64 is the form for checks.  device other than
+    'cpu' (or a torch dtype) runs the same expressions on torch tensors - the eager composition env.step(ctrl.act(obs)) on the device.
+    params: the dict of dp_controller_defaults.  act(obs [n, >=6]) advances z [n, 3] one control step and returns the action [n, 7];
+    reset(mask) zeroes z of the envs in mask (None = all); allocate(tau [n, 3]) is the stateless allocation."""
+
+    def __init__(self, n, params=None, dt=0.2, dtype=None, device='cpu'):
+        p = dp_controller_defaults() if params is None else params
+        self.torch = None
+        if str(device) != 'cpu' or type(dtype).__module__ == 'torch':
+            import torch
+            self.torch = torch
+            self.dtype = torch.float32 if dtype is None else dtype
+            is32 = self.dtype == torch.float32
+            t = lambda v: torch.as_tensor(np.asarray(v, np.float64), device=device).to(self.dtype)
+            self.z = torch.zeros((n, 3), dtype=self.dtype, device=device)
+        else:
+            self.dtype = np.dtype(np.float32 if dtype is None else dtype)
+            is32 = self.dtype == np.dtype(np.float32)
+            t = lambda v: np.asarray(v, np.float64).astype(self.dtype)
+            self.z = np.zeros((n, 3), self.dtype)
+        self.kp, self.kd, self.ki, self.zb, self.tmax = t(p['kp']), t(p['kd']), t(p['ki']), t(p['z_bound']), t(p['tau_max'])
+        self.G, self.kf, self.kr_bow, self.f_eps = t(p['G']), t(p['kf']), t(p['kr_bow']), t(p['f_eps'])
+        self.dt = t(np.float32(dt)) if is32 else t(dt)          # f32: n_substeps * substep_dt as the library forms it
+        self.hundred, self.one, self.zero = t(100.0), t(1.0), t(0.0)
+
+    def _xp(self):
+        return self.torch if self.torch is not None else np
+
+    def allocate(self, tau):
+        xp = self._xp()
+        G = self.G
+        f = [(G[m, 0] * tau[:, 0] + G[m, 1] * tau[:, 1]) + G[m, 2] * tau[:, 2] for m in range(5)]
+        kb = xp.where(f[0] >= self.zero, self.kf[0], self.kr_bow)
+        nb = xp.copysign(xp.sqrt(xp.abs(f[0]) / kb), f[0])
+        cols = [xp.minimum(xp.maximum(nb / self.hundred, -self.one), self.one)]
+        sc = []
+        with np.errstate(invalid='ignore', divide='ignore'):
+            for k in range(2):
+                Fx, Fy = f[1 + 2 * k], f[2 + 2 * k]
+                F = xp.sqrt(Fx * Fx + Fy * Fy)
+                ns = xp.sqrt(F / self.kf[1 + k])
+                cols.append(xp.minimum(ns / self.hundred, self.one))
+                dirn = F > self.f_eps
+                sc += [xp.where(dirn, Fy / F, self.zero), xp.where(dirn, Fx / F, self.one)]
+        return xp.stack(cols + sc, 1)
+
+    def wrench(self, obs):
+        """Advance z on obs and return the clipped tau [n, 3]."""
+        xp = self._xp()
+        e, nu = obs[:, 0:3], obs[:, 3:6]
+        if self.torch is not None:
+            e, nu = e.to(self.dtype), nu.to(self.dtype)
+        else:
+            e, nu = np.asarray(e, self.dtype), np.asarray(nu, self.dtype)
+        self.z = xp.minimum(xp.maximum(self.z + self.dt * e, -self.zb), self.zb)
+        tau = -((self.kp * e + self.kd * nu) + self.ki * self.z)
+        return xp.minimum(xp.maximum(tau, -self.tmax), self.tmax)
+
+    def act(self, obs):
+        return self.allocate(self.wrench(obs))
+
+    def reset(self, mask=None):
+        if mask is None:
+            self.z = self.z * 0
+        else:
+            self.z[mask] = 0
+
+
 class RLAllocatorNode(object):
     """The node's callbacks as plain methods (rl_allocator.py:168-220).  `actor(state[9]) -> action[act_dim]` is any
     callable: ActorCritic.forward_ref on the CPU, or policy_forward on the GPU for one env."""

@@ -184,6 +184,7 @@ class BatchedRevoltEnv(object):
         self._step_ex = self.lib.dpenv_step_ex
         self.integral_action = None          # dict of the parameters while set_integral_action() has it on
         self.reference_filter = None         # dict of the parameters while set_reference_filter() has it on
+        self.dp_controller = None            # dict of the parameters while set_dp_controller() has it on
 
     # -- plumbing -----------------------------------------------------------------------------
     # What a Python `for` over step() pays per call besides the launch is this plumbing (bench.py `eager_loop`): the stream handle and
@@ -435,6 +436,30 @@ class BatchedRevoltEnv(object):
         r = self._chk(r, (3, self.n_envs), torch.float32, 'r')
         _lib.check(self.lib.dpenv_set_reference_filter_state(self._h, self._ptr(x), self._ptr(r), self._stream()), self._h)
 
+    # -- the classical baseline: PID + pseudo-inverse allocation in the closed loop (dpenv.h dpenv_set_dp_controller) ------------------
+    def set_dp_controller(self, params=None, off=False):
+        """The baseline DP controller for policy.controller_rollout (include/dpenv.h has the law): params is the dict of
+        deploy.dp_controller_defaults (None = the defaults of the default hull); off=True turns it off.  Turning it on zeroes the error
+        integral z of every env.  step(), rollout() and policy_rollout() keep working while it is on."""
+        if off:
+            _lib.check(self.lib.dpenv_set_dp_controller(self._h, None, self._stream()), self._h)
+            self.dp_controller = None
+            return
+        p, c = _dp_controller_struct(params)
+        _lib.check(self.lib.dpenv_set_dp_controller(self._h, C.byref(c), self._stream()), self._h)
+        self.dp_controller = dict(p)
+
+    def get_dp_controller_state(self):
+        """z float32 [3, n]: the baseline's error integral.  Checkpoint with get_state()."""
+        torch = _torch()
+        z = torch.empty((3, self.n_envs), dtype=torch.float32, device=self.device)
+        _lib.check(self.lib.dpenv_get_dp_controller_state(self._h, self._ptr(z), self._stream()), self._h)
+        return z
+
+    def set_dp_controller_state(self, z):
+        self._chk(z, (3, self.n_envs), _torch().float32, 'z')
+        _lib.check(self.lib.dpenv_set_dp_controller_state(self._h, self._ptr(z), self._stream()), self._h)
+
     def get_rng_counters(self):
         """(noise_ctr, drift_ctr): int32 [n] draws made so far of the in-kernel exploration noise and of the current drift (uint32
         bits).  With get_state() and get_current() a complete checkpoint: restoring all of them reproduces sampled rollouts."""
@@ -573,6 +598,36 @@ def thrust_map(n_pct, alpha, params=None):
         _lib.check(lib.dpenv_thrust_map(p, C.c_void_p(n_pct.data_ptr()), C.c_void_p(alpha.data_ptr()),
                                         C.c_void_p(tau.data_ptr()), n_pct.shape[1], s))
     return tau
+
+
+def _dp_controller_struct(params):
+    """(params dict, dpenv_dp_controller) for deploy.dp_controller_defaults' dict; None = the defaults of the default hull."""
+    from .deploy import dp_controller_defaults
+    p = dp_controller_defaults() if params is None else params
+    c = _lib.DPController()
+    c.struct_size = C.sizeof(_lib.DPController)
+    for j in range(3):
+        c.kp[j], c.kd[j], c.ki[j] = float(p['kp'][j]), float(p['kd'][j]), float(p['ki'][j])
+        c.z_bound[j], c.tau_max[j], c.kf[j] = float(p['z_bound'][j]), float(p['tau_max'][j]), float(p['kf'][j])
+    for m in range(5):
+        for j in range(3):
+            c.G[m][j] = float(p['G'][m][j])
+    c.kr_bow, c.f_eps = float(p['kr_bow']), float(p['f_eps'])
+    return p, c
+
+
+def thrust_alloc(tau, params=None):
+    """The baseline's stateless allocation on device (dpenv_thrust_alloc): tau float32 [3, n] = Fx, Fy, Mz -> the final variant's
+    continuous-angle action float32 [n, 7]; params: the dict of deploy.dp_controller_defaults (None = the default hull's)."""
+    torch = _torch()
+    lib = _lib.load()
+    assert tau.dim() == 2 and tau.shape[0] == 3 and tau.is_contiguous() and tau.dtype == torch.float32 and tau.is_cuda
+    _, c = _dp_controller_struct(params)
+    act = torch.empty((tau.shape[1], 7), dtype=torch.float32, device=tau.device)
+    s = C.c_void_p(torch.cuda.current_stream(tau.device).cuda_stream)
+    with torch.cuda.device(tau.device):
+        _lib.check(lib.dpenv_thrust_alloc(C.byref(c), C.c_void_p(tau.data_ptr()), C.c_void_p(act.data_ptr()), tau.shape[1], s))
+    return act
 
 
 class _ErrorFrameView(object):

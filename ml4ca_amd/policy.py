@@ -280,3 +280,43 @@ def policy_rollout(env, T, noise=None, switch_steps=(), refs=None, out=None, sam
     else:
         _lib.check(env.lib.dpenv_policy_rollout(env._h, C.byref(io), env._stream()), env._h)
     return out
+
+
+def controller_rollout(env, T, switch_steps=(), refs=None, out=None):
+    """T steps of (baseline DP controller -> env.step) in ONE launch (dpenv_controller_rollout): the PID + pseudo-inverse law of
+    env.set_dp_controller evaluated in registers on each observation, the classical counterpart of policy_rollout on the same plant.
+    Returns a dict of blocks with policy_rollout's keys and row conventions: obs [T,n,9] (the controller's inputs), act [T,n,7],
+    rew [T,n], done [T,n] uint8, last_obs [n,9]; with the reference filter on (env.set_reference_filter) also ref [T,n,3], the eta_d
+    obs[t] was formed against.  ScoreCard.add consumes the dict unchanged."""
+    torch = _torch()
+    n, od, ad = env.n_envs, env.num_states, env.num_actions
+    dev, f32 = env.device, torch.float32
+    k = len(switch_steps)
+    if k:
+        env._chk(refs, (k, 3, n), f32, 'refs')
+    if out is None:
+        out = dict(obs=torch.empty((T, n, od), dtype=env.obs_torch_dtype, device=dev), act=torch.empty((T, n, ad), dtype=f32, device=dev),
+                   rew=torch.empty((T, n), dtype=f32, device=dev), done=torch.empty((T, n), dtype=torch.uint8, device=dev),
+                   last_obs=torch.empty((n, od), dtype=env.obs_torch_dtype, device=dev))
+    env._chk(out['obs'], (T, n, od), env.obs_torch_dtype, "out['obs']")
+    env._chk(out['act'], (T, n, ad), f32, "out['act']")
+    env._chk(out['rew'], (T, n), f32, "out['rew']")
+    env._chk(out['done'], (T, n), torch.uint8, "out['done']")
+    env._chk(out['last_obs'], (n, od), env.obs_torch_dtype, "out['last_obs']")
+    io = _lib.ControllerRolloutIO()
+    io.struct_size = C.sizeof(_lib.ControllerRolloutIO)
+    io.T = int(T)
+    io.obs, io.act, io.reward, io.done = out['obs'].data_ptr(), out['act'].data_ptr(), out['rew'].data_ptr(), out['done'].data_ptr()
+    io.last_obs = out['last_obs'].data_ptr()
+    io.n_switch = k
+    for j, st in enumerate(switch_steps):
+        io.switch_step[j] = int(st)
+    io.refs = refs.data_ptr() if k else None
+    io.ref_out = None
+    if env.reference_filter is not None:
+        if out.get('ref') is None:
+            out['ref'] = torch.empty((T, n, 3), dtype=f32, device=dev)
+        env._chk(out['ref'], (T, n, 3), f32, "out['ref']")
+        io.ref_out = out['ref'].data_ptr()
+    _lib.check(env.lib.dpenv_controller_rollout(env._h, C.byref(io), env._stream()), env._h)
+    return out

@@ -1,93 +1,108 @@
-// dpenv_api.hip - host side of libdpenv.so: the C ABI declared in include/dpenv.h.
-// Owns the per-env state block in HBM, validates arguments, fills the kernel argument block and
-// launches on the caller's stream.  No CPU compute path exists here by design: if HIP or the
-// device is unavailable every entry point fails loudly.
-#include <hip/hip_runtime.h>
-
+// dpenv_api.hip - host side of libdpenv.so: every entry point of the C ABI (include/dpenv.h) that takes a handle (the others are in
+// dpenv_api_free.hip).  Owns the per-env state block in HBM, validates arguments, fills the kernel argument block and launches on the
+// caller's stream.  No CPU compute path exists here by design: if HIP or the device is unavailable every entry point fails loudly.
+// The handle's struct is defined here and nowhere else: no other unit can look inside a handle.
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
-#include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <new>
 #include <string>
-#include <vector>
 
-#include "../../include/dpenv.h"
-#include "dpenv_dev.h"
+#include "dpenv_host.h"
 
 using namespace dpenv;
-
-struct dpenv_s {
-    dpenv_config cfg;
-    StepArgs args;          // persistent part of the kernel argument block
-    int mode;
-    int n_classes;
-    float* blob;            // one allocation: S0 | S1 | S2 | RF | episode | vc | beta | class_id | class_tab
-    size_t blob_bytes;
-    float* cur_vc;
-    float* cur_beta;
-    float* cur_vc0;
-    float* cur_beta0;
-    uint32_t* drift_ctr;
-    int32_t* class_id;
-    float4* env_tab;        // per-env parameter blocks + thrust-loss rows ET[DRAW_GROUPS][env_stride] (dpenv_dev.h), always allocated
-    int env_stride;
-    uint32_t* loss_flag;    // device word BEHIND the table (ET[DRAW_GROUPS][stride] | flag): the packing kernel reports "some env has a thrust-loss
-                            //   coefficient" through it; while the host does not know the answer (LOSS_UNKNOWN) the general per-env kernels run with
-                            //   the loss applied: zero coefficients are neutral bit for bit
-    int loss_state;         // LOSS_OFF / LOSS_ON / LOSS_UNKNOWN -> StepArgs.loss_on (per-env blocks in force only)
-    bool loss_pending;      // the flag word is on its way to loss_host behind loss_ev: resolved (without blocking a capture) by the next launch
-    hipEvent_t loss_ev;
-    uint32_t* loss_host;    // pinned host word
-    bool rand_loss;         // the randomisation's nominal hull has a thrust-loss coefficient (then every drawn hull has one)
-    bool shared_loss;       // the SINGLE class of dpenv_create has thrust-loss coefficients: kernels with the shared-loss instantiation take them from
-                            //   the arguments (StepArgs.kl, VES_ARGS_LOSS); for the others env_tab holds that hull for every env while no
-                            //   per-env table is in force (repacked from raw0_dev when the caller returns to the class)
-    float* raw0_dev;        // device copy of raw0
-    bool cur_rand;          // per-episode randomisation of the current (dpenv_set_current_randomisation): needs per-env blocks in force
-    float* cur_nom;         // device float[2][env_stride]: nominal V_c | beta_c of every env
-    float* rand_tab;        // device float[RAND_TAB_FLOATS]: nominal | relative half-range of the domain randomisation
-    float rand_host[RAND_TAB_FLOATS];   // its host image (the source of the stream-ordered upload must outlive the call)
-    float raw0[DPENV_NPARAM];           // public parameter vector of class 0 (the randomisation's default nominal hull)
-    bool per_env;           // the kernels take every env's vessel from env_tab (dpenv_set_vessel_params / dpenv_set_vessel_randomisation)
-    bool randomise;         // every reset re-draws the env's hull
-    bool classes_assigned;
-    bool current_set;
-    uint32_t* noise_ctr;
-    PolicyArgs pol;         // persistent part (weights, std) of the policy kernel arguments
-    void* pol_buf;          // fragments | bias tiles | constants, as the kernels stage them: TWO images of pol_buf_bytes / 2 each,
-    size_t pol_buf_bytes;   //   written alternately, so that an upload never touches the image the launches before it read
-    int pol_slot;           // image the NEXT alternating upload writes (0 / 1)
-    int pol_cur;            // image the LAST upload wrote = the one launches read
-    hipEvent_t pol_read[2]; // recorded behind the last launch that read image k: the upload that reuses it waits for that
-    bool pol_read_valid[2];
-    hipStream_t pol_read_stream[2];   // the stream that event was last recorded on (a reader on another stream chains behind it)
-    int pol_pinned;         // >= 0: a captured graph reads this image (PolicyArgs.frags is baked into the graph's kernel nodes by value):
-                            //   every later upload is written IN PLACE into it, so that a replay sees the latest weights
-    PolicyArgs pol_pin_layout;   // ... and the kernel node ALSO holds the image's layout and the launch form by value (nent, nblk, ks, n_hidden,
-                            //   act, leak, split, critic_f16, ws, ws_groups): what an in-place upload must not change (layout_differs)
-    int n_cus;
-    float* pol_raw;         // device staging of raw fp32 weights for the host-pointer form of set_policy
-    size_t pol_raw_bytes;
-    int pol_form;           // DPENV_LAUNCH_* requested
-    bool has_policy;
-    bool lag_valid;         // the state block was last written by a closed-loop launch (PolicyArgs.use_lag)
-    bool integ_on;          // dpenv_set_integral_action: the closed loop runs the *_integ kernels with `integ`
-    IntegArgs integ;        // its parameters and per-env state (float4 [n]: I | count), allocated by the first dpenv_set_integral_action
-    bool reff_on;           // dpenv_set_reference_filter: the closed loop runs the *_reff kernels with `reff`
-    FilterArgs reff;        // its f32 coefficients and per-env state (float4 [3][n]: pos | vel | acc | target), allocated on first use
-    bool ctrl_on;           // dpenv_set_dp_controller: dpenv_controller_rollout flies the baseline law with `ctrl`
-    ControlArgs ctrl;       // its numbers and per-env state (float4 [n]: z | pad), allocated by the first dpenv_set_dp_controller
-    int device;
-    std::string err;
-};
+using namespace dpenv::host;
 
 enum { LOSS_OFF = 0, LOSS_ON = 1, LOSS_UNKNOWN = 2 };
 
+// A handle owns what it allocates: the destructor releases all of it, so a failed dpenv_create and dpenv_destroy are the same code.
+#pragma GCC visibility push(hidden)      // its constructor and destructor are no part of the library's symbol table
+struct dpenv_s {
+    dpenv_config cfg = {};
+    StepArgs args = {};     // persistent part of the kernel argument block
+    int mode = 0;
+    int n_classes = 1;
+    float* blob = nullptr;  // one allocation: S0 | S1 | S2 | RF | episode | vc | beta | class_id | class_tab
+    size_t blob_bytes = 0;
+    float* cur_vc = nullptr;
+    float* cur_beta = nullptr;
+    float* cur_vc0 = nullptr;
+    float* cur_beta0 = nullptr;
+    uint32_t* drift_ctr = nullptr;
+    int32_t* class_id = nullptr;
+    float4* env_tab = nullptr;   // per-env parameter blocks + thrust-loss rows ET[DRAW_GROUPS][env_stride] (dpenv_dev.h), always allocated
+    int env_stride = 0;
+    uint32_t* loss_flag = nullptr;   // device word BEHIND the table (ET[DRAW_GROUPS][stride] | flag): the packing kernel reports "some env has a thrust-loss
+                            //   coefficient" through it; while the host does not know the answer (LOSS_UNKNOWN) the general per-env kernels run with
+                            //   the loss applied: zero coefficients are neutral bit for bit
+    int loss_state = LOSS_OFF;   // LOSS_OFF / LOSS_ON / LOSS_UNKNOWN -> StepArgs.loss_on (per-env blocks in force only)
+    bool loss_pending = false;   // the flag word is on its way to loss_host behind loss_ev: resolved (without blocking a capture) by the next launch
+    hipEvent_t loss_ev = nullptr;
+    uint32_t* loss_host = nullptr;   // pinned host word
+    bool rand_loss = false; // the randomisation's nominal hull has a thrust-loss coefficient (then every drawn hull has one)
+    bool shared_loss = false;   // the SINGLE class of dpenv_create has thrust-loss coefficients: kernels with the shared-loss instantiation take them from
+                            //   the arguments (StepArgs.kl, VES_ARGS_LOSS); for the others env_tab holds that hull for every env while no
+                            //   per-env table is in force (repacked from raw0_dev when the caller returns to the class)
+    float* raw0_dev = nullptr;   // device copy of raw0
+    bool cur_rand = false;  // per-episode randomisation of the current (dpenv_set_current_randomisation): needs per-env blocks in force
+    float* cur_nom = nullptr;    // device float[2][env_stride]: nominal V_c | beta_c of every env
+    float* rand_tab = nullptr;   // device float[RAND_TAB_FLOATS]: nominal | relative half-range of the domain randomisation
+    float rand_host[RAND_TAB_FLOATS] = {};   // its host image (the source of the stream-ordered upload must outlive the call)
+    float raw0[DPENV_NPARAM] = {};           // public parameter vector of class 0 (the randomisation's default nominal hull)
+    bool per_env = false;   // the kernels take every env's vessel from env_tab (dpenv_set_vessel_params / dpenv_set_vessel_randomisation)
+    bool randomise = false; // every reset re-draws the env's hull
+    bool classes_assigned = false;
+    uint32_t* noise_ctr = nullptr;
+    PolicyArgs pol = {};    // persistent part (weights, std) of the policy kernel arguments
+    void* pol_buf = nullptr;     // fragments | bias tiles | constants, as the kernels stage them: TWO images of pol_buf_bytes / 2 each,
+    size_t pol_buf_bytes = 0;    //   written alternately, so that an upload never touches the image the launches before it read
+    int pol_slot = 0;       // image the NEXT alternating upload writes (0 / 1)
+    int pol_cur = 0;        // image the LAST upload wrote = the one launches read
+    hipEvent_t pol_read[2] = {nullptr, nullptr};   // recorded behind the last launch that read image k: the upload that reuses it waits for that
+    bool pol_read_valid[2] = {false, false};
+    hipStream_t pol_read_stream[2] = {nullptr, nullptr};   // the stream that event was last recorded on (a reader on another stream chains behind it)
+    int pol_pinned = -1;    // >= 0: a captured graph reads this image (PolicyArgs.frags is baked into the graph's kernel nodes by value):
+                            //   every later upload is written IN PLACE into it, so that a replay sees the latest weights
+    PolicyArgs pol_pin_layout = {};   // ... and the kernel node ALSO holds the image's layout and the launch form by value (nent, nblk, ks, n_hidden,
+                            //   act, leak, split, critic_f16, ws, ws_groups): what an in-place upload must not change (layout_differs)
+    int n_cus = 256;
+    float* pol_raw = nullptr;    // device staging of raw fp32 weights for the host-pointer form of set_policy
+    size_t pol_raw_bytes = 0;
+    int pol_form = DPENV_LAUNCH_AUTO;   // DPENV_LAUNCH_* requested
+    bool has_policy = false;
+    bool lag_valid = false; // the state block was last written by a closed-loop launch (PolicyArgs.use_lag)
+    bool integ_on = false;  // dpenv_set_integral_action: the closed loop runs the *_integ kernels with `integ`
+    IntegArgs integ = {};   // its parameters and per-env state (float4 [n]: I | count), allocated by the first dpenv_set_integral_action
+    bool reff_on = false;   // dpenv_set_reference_filter: the closed loop runs the *_reff kernels with `reff`
+    FilterArgs reff = {};   // its f32 coefficients and per-env state (float4 [3][n]: pos | vel | acc | target), allocated on first use
+    bool ctrl_on = false;   // dpenv_set_dp_controller: dpenv_controller_rollout flies the baseline law with `ctrl`
+    ControlArgs ctrl = {};  // its numbers and per-env state (float4 [n]: z | pad), allocated by the first dpenv_set_dp_controller
+    int device = 0;
+    std::string err;
+
+    dpenv_s() = default;
+    dpenv_s(const dpenv_s&) = delete;                       // (a copy would release the same resources)
+    dpenv_s& operator=(const dpenv_s&) = delete;
+    ~dpenv_s()              // on the handle's device (dpenv_create has made it current, dpenv_destroy guards it)
+    {
+        if (blob) (void)hipFree(blob);
+        if (pol_buf) (void)hipFree(pol_buf);
+        if (pol_raw) (void)hipFree(pol_raw);
+        if (integ.state) (void)hipFree(integ.state);
+        if (reff.state) (void)hipFree(reff.state);
+        if (ctrl.z) (void)hipFree(ctrl.z);
+        for (int k = 0; k < 2; ++k) if (pol_read[k]) (void)hipEventDestroy(pol_read[k]);
+        if (loss_ev) (void)hipEventDestroy(loss_ev);
+        if (loss_host) (void)hipHostFree(loss_host);
+    }
+};
+#pragma GCC visibility pop
+
 static thread_local std::string g_create_err;
 
-static int fail(dpenv_handle h, int code, const char* fmt, ...)
+int host::fail(dpenv_handle h, int code, const char* fmt, ...)
 {
     char buf[512];
     va_list ap;
@@ -97,173 +112,6 @@ static int fail(dpenv_handle h, int code, const char* fmt, ...)
     if (h) h->err = buf;
     else g_create_err = buf;
     return code;
-}
-
-// Entry points launch on the handle's device even if the caller's current device is another one.
-struct DeviceGuard {
-    int prev = -1;
-    bool switched = false;
-    explicit DeviceGuard(int want)
-    {
-        if (hipGetDevice(&prev) == hipSuccess && prev != want) switched = (hipSetDevice(want) == hipSuccess);
-    }
-    ~DeviceGuard()
-    {
-        if (switched) (void)hipSetDevice(prev);
-    }
-};
-
-#define HIP_TRY(h, expr)                                                                               \
-    do {                                                                                               \
-        hipError_t e_ = (expr);                                                                        \
-        if (e_ != hipSuccess) return fail(h, DPENV_EHIP, "%s failed: %s", #expr, hipGetErrorString(e_)); \
-    } while (0)
-
-extern "C" int dpenv_abi_version(void) { return DPENV_ABI_VERSION; }
-
-extern "C" int dpenv_default_config(dpenv_config* c)
-{
-    if (!c) return DPENV_EINVAL;
-    std::memset(c, 0, sizeof *c);
-    c->struct_size = (uint32_t)sizeof *c;
-    c->n_envs = 0;
-    c->device = -1;
-    c->variant = DPENV_FINAL;      // train.py:47 'final'
-    c->extended_state = 1;         // train.py:52
-    c->cont_ang = 1;               // train.py:54
-    c->n_substeps = 20;            // customEnv.py:79-80
-    c->substep_dt = 0.01f;         // customEnv.py:81
-    c->wrap_mode = DPENV_WRAP_REFERENCE;
-    c->terminate = 1;
-    c->max_ep_len = 400;           // customEnv.py:83 with max_ep_len=800, n_steps=20
-    c->auto_reset = 0;
-    c->action_layout = DPENV_AOS;
-    c->obs_layout = DPENV_AOS;
-    c->obs_dtype = DPENV_F32;
-    c->current_enabled = 0;
-    c->seed = 0;
-    c->env_id_base = 0;
-    c->reset_fraction = 0.8f;      // customEnv.py:135
-    c->current_drift = 0;
-    c->current_tau = 100.0f;                           // SURVEY 8(d) config 5 (build-defined)
-    c->current_sigma_v = 0.02f;
-    c->current_sigma_beta = 5.0f * 3.14159265358979f / 180.0f;
-    c->reset_acts = 0;             // customEnv.py:30 reset_acts=False
-    return DPENV_OK;
-}
-
-// BUILD-OWNED hull + the reference's thruster constants
-// (qp_allocator.py:51-55 K "as currently set in the simulator", :69-70 lever arms; env order bow,port,star).
-extern "C" int dpenv_default_vessel(float* p)
-{
-    if (!p) return DPENV_EINVAL;
-    for (int i = 0; i < DPENV_NPARAM; ++i) p[i] = 0.0f;
-    // fitted to the reference's recorded Cybersea runs by tests/calibration/calibrate_plant.py
-    p[DPENV_P_M11] = 263.93f; p[DPENV_P_M22] = 300.9f; p[DPENV_P_M23] = 7.0f; p[DPENV_P_M33] = 300.0f;
-    p[DPENV_P_XU] = 3.0f;  p[DPENV_P_XUU] = 7.1f;
-    p[DPENV_P_YV] = 19.8f; p[DPENV_P_YVV] = 80.3f;
-    p[DPENV_P_YR] = -1.1f; p[DPENV_P_NV] = 19.7f;
-    p[DPENV_P_NR] = 77.8f; p[DPENV_P_NRR] = 24.9f;
-    p[DPENV_P_NUV] = 40.0f; p[DPENV_P_YUR] = 30.0f;
-    p[DPENV_P_KF_BOW] = 0.0009f; p[DPENV_P_KF_PORT] = 0.00205f; p[DPENV_P_KF_STAR] = 0.00205f;
-    p[DPENV_P_KR_BOW] = 0.0009f; p[DPENV_P_KR_PORT] = 0.00205f; p[DPENV_P_KR_STAR] = 0.00205f;
-    p[DPENV_P_LX_BOW] = 1.08f; p[DPENV_P_LX_PORT] = -1.12f; p[DPENV_P_LX_STAR] = -1.12f;
-    p[DPENV_P_LY_BOW] = 0.0f;  p[DPENV_P_LY_PORT] = -0.15f; p[DPENV_P_LY_STAR] = 0.15f;
-    return DPENV_OK;
-}
-
-// The same hull with the thrust gains of the reference's SECOND set of steady full-thrust speeds - "with thrust losses" +1.4 / -1.1 m/s
-// ahead / astern (customEnv.py:17), which are also the velocity bounds it trains with (customEnv.py:26) - derived by
-// tests/calibration/fit_thrust_loss_preset.py as an INFLOW loss of the stern thrusters, F = K n|n| - Kl |n| u_a (u_a: the water's speed
-// along the thruster axis; never past zero thrust), their reverse gain from the no-loss astern speed (-1.60 m/s, customEnv.py:14); bow
-// unchanged (sway 0.29 m/s against the recorded 0.30); the hull is untouched, so the free-drift record is reproduced as before.  Yaw comes
-// out at 0.505 rad/s against the recorded 0.52 (a constant gain reduced to meet +1.4 m/s - round 5's first form of this preset - gave 0.35).
-// Not the default: the loss code lives in the general per-env kernels only (DESIGN.md section 3 for what it costs and what it changes).
-extern "C" int dpenv_default_vessel_ex(int32_t kind, float* p)
-{
-    if (!p || kind < 0 || kind > (DPENV_VESSEL_THRUST_LOSS | DPENV_VESSEL_DYNPOS_FIT)) return DPENV_EINVAL;
-    dpenv_default_vessel(p);
-    if (kind & DPENV_VESSEL_DYNPOS_FIT) {
-        // tests/calibration/fit_dynpos_preset.py (round 6): the sway-yaw part of the hull refitted JOINTLY to what the default is fitted to (free
-        // drift, box test, steady surge / yaw speeds) AND to the reference's 32 recorded station-keeping runs in a current from 16 directions
-        // (results/all_plots/dyn_pos/) AND to the recorded steady sway speed 0.35 m/s (customEnv.py:14), which the default hull misses (0.29)
-        p[DPENV_P_M22] = 317.3f; p[DPENV_P_M33] = 300.0f;
-        p[DPENV_P_YV] = 21.4f; p[DPENV_P_YVV] = 54.3f; p[DPENV_P_YR] = -4.9f;
-        p[DPENV_P_NV] = 11.4f; p[DPENV_P_NR] = 57.0f; p[DPENV_P_NRR] = 59.6f;
-        p[DPENV_P_NUV] = 40.0f; p[DPENV_P_YUR] = 25.3f;
-    }
-    if (kind & DPENV_VESSEL_THRUST_LOSS) {
-        // tests/calibration/fit_thrust_loss_preset.py: stern reverse gain from -1.60 m/s astern without losses, inflow-loss coefficients from
-        // +1.4 / -1.1 m/s with losses (customEnv.py:14,17); the bow thruster keeps its gain and has no loss.  (Surge only: the same numbers on
-        // either hull - Xu, Xuu and m11 are not part of the dyn_pos fit.)
-        p[DPENV_P_KR_PORT] = p[DPENV_P_KR_STAR] = 0.001149f;
-        p[DPENV_P_KLF_PORT] = p[DPENV_P_KLF_STAR] = 0.08173f;
-        p[DPENV_P_KLR_PORT] = p[DPENV_P_KLR_STAR] = 0.05039f;
-    }
-    return DPENV_OK;
-}
-
-static int mode_of(const dpenv_config* c)
-{
-    switch (c->variant) {
-    case DPENV_FULL: return MODE_FULL;
-    case DPENV_SIMPLE: return MODE_SIMPLE;
-    case DPENV_LIMITED: return MODE_LIMITED;
-    case DPENV_FINAL: return c->cont_ang ? MODE_FINAL_CONT : MODE_FINAL_WRAP;
-    }
-    return -1;
-}
-
-extern "C" int dpenv_act_dim(const dpenv_config* c)
-{
-    if (!c) return DPENV_EINVAL;
-    switch (mode_of(c)) {
-    case MODE_FULL: return 6;          // customEnv.py:24
-    case MODE_SIMPLE: return 3;        // :332
-    case MODE_LIMITED: return 5;       // :356
-    case MODE_FINAL_WRAP: return 5;    // :379
-    case MODE_FINAL_CONT: return 7;
-    }
-    return DPENV_EINVAL;
-}
-
-extern "C" int dpenv_obs_dim(const dpenv_config* c)
-{
-    if (!c) return DPENV_EINVAL;
-    return c->extended_state ? 9 : 6;   // customEnv.py:44
-}
-
-// allow_loss: the caller deals with the inflow thrust-loss coefficients (parameters 26-31), which are not part of a VesselDev
-static int derive_vessel(const float* p, VesselDev* d, std::string* why, bool allow_loss = false)
-{
-    const double m11 = p[DPENV_P_M11], m22 = p[DPENV_P_M22], m23 = p[DPENV_P_M23], m33 = p[DPENV_P_M33];
-    const double det = m22 * m33 - m23 * m23;
-    if (!(m11 > 0.0) || !(det > 0.0) || !(m22 > 0.0)) {
-        *why = "mass matrix is not positive definite";
-        return DPENV_EINVAL;
-    }
-    for (int i = 0; i < DPENV_NPARAM; ++i)
-        if (!std::isfinite(p[i])) { *why = "vessel parameter is not finite"; return DPENV_EINVAL; }
-    d->p[VD_M11] = (float)m11; d->p[VD_M22] = (float)m22; d->p[VD_M23] = (float)m23;
-    // same float operations as the fp32 oracle so that both sides integrate with identical constants
-    const float fm11 = (float)m11, fm22 = (float)m22, fm23 = (float)m23, fm33 = (float)m33;
-    const float fdet = fm22 * fm33 - fm23 * fm23;
-    d->p[VD_INV11] = 1.0f / fm11;
-    d->p[VD_I22] = fm33 / fdet; d->p[VD_I23] = -fm23 / fdet; d->p[VD_I33] = fm22 / fdet;
-    d->p[VD_XU] = p[DPENV_P_XU]; d->p[VD_XUU] = p[DPENV_P_XUU]; d->p[VD_YV] = p[DPENV_P_YV];
-    d->p[VD_YVV] = p[DPENV_P_YVV]; d->p[VD_YR] = p[DPENV_P_YR]; d->p[VD_NV] = p[DPENV_P_NV];
-    d->p[VD_NR] = p[DPENV_P_NR]; d->p[VD_NRR] = p[DPENV_P_NRR];
-    d->p[VD_NUV] = p[DPENV_P_NUV]; d->p[VD_YUR] = p[DPENV_P_YUR];
-    for (int i = 0; i < 3; ++i) {
-        d->p[VD_KF + i] = p[DPENV_P_KF_BOW + i]; d->p[VD_KR + i] = p[DPENV_P_KR_BOW + i];
-        d->p[VD_LX + i] = p[DPENV_P_LX_BOW + i]; d->p[VD_LY + i] = p[DPENV_P_LY_BOW + i];
-        if (!(p[DPENV_P_KLF_BOW + i] >= 0.0f) || !(p[DPENV_P_KLR_BOW + i] >= 0.0f)) { *why = "thrust-loss coefficients must be >= 0"; return DPENV_EINVAL; }
-        if (!allow_loss && (p[DPENV_P_KLF_BOW + i] != 0.0f || p[DPENV_P_KLR_BOW + i] != 0.0f)) {
-            *why = "thrust-loss coefficients (parameters 26-31) are not available to vessel CLASSES: one class, per-env blocks (dpenv_set_vessel_params) or the nominal hull of dpenv_set_vessel_randomisation";
-            return DPENV_EINVAL;
-        }
-    }
-    return DPENV_OK;
 }
 
 static size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
@@ -308,45 +156,17 @@ extern "C" int dpenv_create(const dpenv_config* cfg, const float* vessel_params,
     }
     if (hipSetDevice(dev) != hipSuccess) return fail(nullptr, DPENV_ENODEV, "hipSetDevice(%d) failed", dev);
 
-    dpenv_s* h = new (std::nothrow) dpenv_s();
+    // every failure from here on is a plain return: the handle releases what it holds by then
+    std::unique_ptr<dpenv_s> h(new (std::nothrow) dpenv_s());
     if (!h) return fail(nullptr, DPENV_ENOMEM, "host allocation failed");
     h->cfg = *cfg;
     h->mode = mode;
     h->n_classes = n_classes;
     h->device = dev;
-    h->classes_assigned = false;
-    h->per_env = false;
-    h->randomise = false;
-    h->loss_state = LOSS_OFF;
-    h->loss_pending = false;
-    h->loss_ev = nullptr;
-    h->loss_host = nullptr;
-    h->rand_loss = false;
-    h->shared_loss = false;
-    h->cur_rand = false;
-    h->current_set = false;
-    h->pol_buf = nullptr; h->pol_buf_bytes = 0;
-    h->pol_slot = 0;
-    h->pol_cur = 0;
-    h->pol_read[0] = h->pol_read[1] = nullptr;
-    h->pol_read_valid[0] = h->pol_read_valid[1] = false;
-    h->pol_read_stream[0] = h->pol_read_stream[1] = nullptr;
-    h->pol_pinned = -1;
     {
         hipDeviceProp_t prop;
-        h->n_cus = (hipGetDeviceProperties(&prop, dev) == hipSuccess) ? prop.multiProcessorCount : 256;
+        if (hipGetDeviceProperties(&prop, dev) == hipSuccess) h->n_cus = prop.multiProcessorCount;
     }
-    h->pol_raw = nullptr; h->pol_raw_bytes = 0;
-    h->pol_form = DPENV_LAUNCH_AUTO;
-    h->has_policy = false;
-    h->lag_valid = false;
-    h->integ_on = false;
-    std::memset(&h->integ, 0, sizeof h->integ);
-    h->reff_on = false;
-    std::memset(&h->reff, 0, sizeof h->reff);
-    h->ctrl_on = false;
-    std::memset(&h->ctrl, 0, sizeof h->ctrl);
-    std::memset(&h->pol, 0, sizeof h->pol);
 
     VesselDev tab[MAX_CLASSES];
     float defp[DPENV_NPARAM];
@@ -354,64 +174,39 @@ extern "C" int dpenv_create(const dpenv_config* cfg, const float* vessel_params,
     for (int c = 0; c < n_classes; ++c) {
         std::string why;
         const float* p = vessel_params ? vessel_params + (size_t)c * DPENV_NPARAM : defp;
-        if (derive_vessel(p, &tab[c], &why, n_classes == 1) != DPENV_OK) {
-            delete h;
+        if (derive_vessel(p, &tab[c], &why, n_classes == 1) != DPENV_OK)
             return fail(nullptr, DPENV_EINVAL, "vessel class %d: %s", c, why.c_str());
-        }
         if (c == 0) std::memcpy(h->raw0, p, sizeof h->raw0);
     }
 
     const size_t n = (size_t)cfg->n_envs;
     const size_t npad = align_up(n, 256);
     size_t off = 0;
-    const size_t o_s0 = off; off += npad * 16;
-    const size_t o_s1 = off; off += npad * 16;
-    const size_t o_s2 = off; off += npad * 16;
-    const size_t o_rf = off; off += npad * 16;
-    const size_t o_ep = off; off += npad * 4;
-    const size_t o_vc = off; off += npad * 4;
-    const size_t o_be = off; off += npad * 4;
-    const size_t o_v0 = off; off += npad * 4;
-    const size_t o_b0 = off; off += npad * 4;
-    const size_t o_dc = off; off += npad * 4;
-    const size_t o_ci = off; off += npad * 4;
-    const size_t o_nc = off; off += npad * 4;
-    const size_t o_s3 = off; off += npad * 16;
-    const size_t o_ct = off; off += align_up(sizeof(VesselDev) * MAX_CLASSES, 256);
-    const size_t o_rt = off; off += align_up(sizeof(float) * RAND_TAB_FLOATS, 256);
-    const size_t o_r0 = off; off += 256;                                 // raw0_dev
-    const size_t o_cn = off; off += npad * 4 * 2;                        // cur_nom
-    const size_t o_et = off; off += npad * 16 * DRAW_GROUPS + 256;      // the per-env table and, behind it, its thrust-loss flag word
+    auto carve = [&off](size_t bytes) { const size_t o = off; off += bytes; return o; };     // the blob's layout, in this order
+    const size_t o_s0 = carve(npad * 16), o_s1 = carve(npad * 16), o_s2 = carve(npad * 16), o_rf = carve(npad * 16);
+    const size_t o_ep = carve(npad * 4), o_vc = carve(npad * 4), o_be = carve(npad * 4), o_v0 = carve(npad * 4), o_b0 = carve(npad * 4);
+    const size_t o_dc = carve(npad * 4), o_ci = carve(npad * 4), o_nc = carve(npad * 4);
+    const size_t o_s3 = carve(npad * 16);
+    const size_t o_ct = carve(align_up(sizeof(VesselDev) * MAX_CLASSES, 256));
+    const size_t o_rt = carve(align_up(sizeof(float) * RAND_TAB_FLOATS, 256));
+    const size_t o_r0 = carve(256);                                      // raw0_dev
+    const size_t o_cn = carve(npad * 4 * 2);                             // cur_nom
+    const size_t o_et = carve(npad * 16 * DRAW_GROUPS + 256);            // the per-env table and, behind it, its thrust-loss flag word
     h->blob_bytes = off;
     void* blob = nullptr;
     e = hipMalloc(&blob, off);
-    if (e != hipSuccess) {
-        delete h;
-        return fail(nullptr, DPENV_ENOMEM, "hipMalloc(%zu) failed: %s", off, hipGetErrorString(e));
-    }
+    if (e != hipSuccess) return fail(nullptr, DPENV_ENOMEM, "hipMalloc(%zu) failed: %s", off, hipGetErrorString(e));
     h->blob = (float*)blob;
     char* b = (char*)blob;
     e = hipEventCreateWithFlags(&h->loss_ev, hipEventDisableTiming);
     if (e == hipSuccess) e = hipHostMalloc((void**)&h->loss_host, sizeof(uint32_t), hipHostMallocDefault);
-    if (e != hipSuccess) {
-        if (h->loss_ev) (void)hipEventDestroy(h->loss_ev);
-        (void)hipFree(blob);
-        delete h;
-        return fail(nullptr, DPENV_EHIP, "event / pinned word of the per-env table's flag: %s", hipGetErrorString(e));
-    }
+    if (e != hipSuccess) return fail(nullptr, DPENV_EHIP, "event / pinned word of the per-env table's flag: %s", hipGetErrorString(e));
     *h->loss_host = 0u;
     e = hipMemset(blob, 0, off);
     if (e == hipSuccess) e = hipMemcpy(b + o_ct, tab, sizeof(VesselDev) * n_classes, hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-        (void)hipEventDestroy(h->loss_ev);
-        (void)hipHostFree(h->loss_host);
-        (void)hipFree(blob);
-        delete h;
-        return fail(nullptr, DPENV_EHIP, "state initialisation failed: %s", hipGetErrorString(e));
-    }
+    if (e != hipSuccess) return fail(nullptr, DPENV_EHIP, "state initialisation failed: %s", hipGetErrorString(e));
 
     StepArgs& a = h->args;
-    std::memset(&a, 0, sizeof a);
     a.S0 = (float4*)(b + o_s0); a.S1 = (float4*)(b + o_s1); a.S2 = (float4*)(b + o_s2); a.RF = (float4*)(b + o_rf);
     a.episode = (int32_t*)(b + o_ep);
     h->cur_vc = (float*)(b + o_vc); h->cur_beta = (float*)(b + o_be);
@@ -469,16 +264,10 @@ extern "C" int dpenv_create(const dpenv_config* cfg, const float* vessel_params,
             e = dev::launch_pack_env_vessels(h->raw0_dev, 1, 0, h->env_tab, nullptr, h->env_stride, cfg->n_envs, nullptr);
             if (e == hipSuccess) e = hipDeviceSynchronize();
         }
-        if (e != hipSuccess) {
-            (void)hipEventDestroy(h->loss_ev);
-            (void)hipHostFree(h->loss_host);
-            (void)hipFree(blob);
-            delete h;
-            return fail(nullptr, DPENV_EHIP, "the class hull's device copy / per-env image: %s", hipGetErrorString(e));
-        }
+        if (e != hipSuccess) return fail(nullptr, DPENV_EHIP, "the class hull's device copy / per-env image: %s", hipGetErrorString(e));
         h->shared_loss = any && n_classes == 1;
     }
-    *out = h;
+    *out = h.release();
     return DPENV_OK;
 }
 
@@ -486,15 +275,6 @@ extern "C" int dpenv_destroy(dpenv_handle h)
 {
     if (!h) return DPENV_EINVAL;
     DeviceGuard dev_guard(h->device);
-    if (h->blob) (void)hipFree(h->blob);
-    if (h->pol_buf) (void)hipFree(h->pol_buf);
-    if (h->pol_raw) (void)hipFree(h->pol_raw);
-    if (h->integ.state) (void)hipFree(h->integ.state);
-    if (h->reff.state) (void)hipFree(h->reff.state);
-    if (h->ctrl.z) (void)hipFree(h->ctrl.z);
-    for (int k = 0; k < 2; ++k) if (h->pol_read[k]) (void)hipEventDestroy(h->pol_read[k]);
-    if (h->loss_ev) (void)hipEventDestroy(h->loss_ev);
-    if (h->loss_host) (void)hipHostFree(h->loss_host);
     delete h;
     return DPENV_OK;
 }
@@ -520,51 +300,44 @@ extern "C" int dpenv_set_vessel_class(dpenv_handle h, const int32_t* class_id, d
     return DPENV_OK;
 }
 
+static int require_current(dpenv_handle h) { return h->cfg.current_enabled ? DPENV_OK : fail(h, DPENV_EINVAL, "config.current_enabled is 0"); }
+
+// The four current accessors are one copy with the pointers permuted: the caller's two arrays against the present values (cur_vc,
+// cur_beta), the drift means (cur_vc0, cur_beta0) or, for dpenv_set_current, both in that order.
+enum { CUR_SET = 1, CUR_PRESENT = 2, CUR_MEAN = 4 };
+static int current_io(dpenv_handle h, const char* who, float* vc, float* beta, int what, dpenv_stream s)
+{
+    if (!h || !vc || !beta) return fail(h, DPENV_EINVAL, "%s: NULL argument", who);
+    DeviceGuard dev_guard(h->device);
+    if (int rc = require_current(h)) return rc;
+    const size_t bytes = sizeof(float) * (size_t)h->cfg.n_envs;
+    float* const theirs[2] = {vc, beta};
+    float* const mine[2][2] = {{h->cur_vc, h->cur_beta}, {h->cur_vc0, h->cur_beta0}};
+    const bool set = what & CUR_SET;
+    for (int k = 0; k < 2; ++k)
+        for (int j = 0; j < 2 && (what & (k ? CUR_MEAN : CUR_PRESENT)); ++j)
+            HIP_TRY(h, hipMemcpyAsync(set ? mine[k][j] : theirs[j], set ? theirs[j] : mine[k][j], bytes, hipMemcpyDeviceToDevice, (hipStream_t)s));
+    return DPENV_OK;
+}
+
 extern "C" int dpenv_set_current(dpenv_handle h, const float* vc, const float* beta, dpenv_stream s)
 {
-    if (!h || !vc || !beta) return fail(h, DPENV_EINVAL, "dpenv_set_current: NULL argument");
-    DeviceGuard dev_guard(h->device);
-    if (!h->cfg.current_enabled) return fail(h, DPENV_EINVAL, "config.current_enabled is 0");
-    const size_t bytes = sizeof(float) * (size_t)h->cfg.n_envs;
-    HIP_TRY(h, hipMemcpyAsync(h->cur_vc, vc, bytes, hipMemcpyDeviceToDevice, (hipStream_t)s));
-    HIP_TRY(h, hipMemcpyAsync(h->cur_beta, beta, bytes, hipMemcpyDeviceToDevice, (hipStream_t)s));
-    HIP_TRY(h, hipMemcpyAsync(h->cur_vc0, vc, bytes, hipMemcpyDeviceToDevice, (hipStream_t)s));
-    HIP_TRY(h, hipMemcpyAsync(h->cur_beta0, beta, bytes, hipMemcpyDeviceToDevice, (hipStream_t)s));
-    h->current_set = true;
-    return DPENV_OK;
+    return current_io(h, "dpenv_set_current", (float*)vc, (float*)beta, CUR_SET | CUR_PRESENT | CUR_MEAN, s);
 }
 
 extern "C" int dpenv_set_current_present(dpenv_handle h, const float* vc, const float* beta, dpenv_stream s)
 {
-    if (!h || !vc || !beta) return fail(h, DPENV_EINVAL, "dpenv_set_current_present: NULL argument");
-    DeviceGuard dev_guard(h->device);
-    if (!h->cfg.current_enabled) return fail(h, DPENV_EINVAL, "config.current_enabled is 0");
-    const size_t bytes = sizeof(float) * (size_t)h->cfg.n_envs;
-    HIP_TRY(h, hipMemcpyAsync(h->cur_vc, vc, bytes, hipMemcpyDeviceToDevice, (hipStream_t)s));
-    HIP_TRY(h, hipMemcpyAsync(h->cur_beta, beta, bytes, hipMemcpyDeviceToDevice, (hipStream_t)s));
-    return DPENV_OK;
+    return current_io(h, "dpenv_set_current_present", (float*)vc, (float*)beta, CUR_SET | CUR_PRESENT, s);
 }
 
 extern "C" int dpenv_get_current(dpenv_handle h, float* vc_out, float* beta_out, dpenv_stream s)
 {
-    if (!h || !vc_out || !beta_out) return fail(h, DPENV_EINVAL, "dpenv_get_current: NULL argument");
-    DeviceGuard dev_guard(h->device);
-    if (!h->cfg.current_enabled) return fail(h, DPENV_EINVAL, "config.current_enabled is 0");
-    const size_t bytes = sizeof(float) * (size_t)h->cfg.n_envs;
-    HIP_TRY(h, hipMemcpyAsync(vc_out, h->cur_vc, bytes, hipMemcpyDeviceToDevice, (hipStream_t)s));
-    HIP_TRY(h, hipMemcpyAsync(beta_out, h->cur_beta, bytes, hipMemcpyDeviceToDevice, (hipStream_t)s));
-    return DPENV_OK;
+    return current_io(h, "dpenv_get_current", vc_out, beta_out, CUR_PRESENT, s);
 }
 
 extern "C" int dpenv_get_current_mean(dpenv_handle h, float* vc_out, float* beta_out, dpenv_stream s)
 {
-    if (!h || !vc_out || !beta_out) return fail(h, DPENV_EINVAL, "dpenv_get_current_mean: NULL argument");
-    DeviceGuard dev_guard(h->device);
-    if (!h->cfg.current_enabled) return fail(h, DPENV_EINVAL, "config.current_enabled is 0");
-    const size_t bytes = sizeof(float) * (size_t)h->cfg.n_envs;
-    HIP_TRY(h, hipMemcpyAsync(vc_out, h->cur_vc0, bytes, hipMemcpyDeviceToDevice, (hipStream_t)s));
-    HIP_TRY(h, hipMemcpyAsync(beta_out, h->cur_beta0, bytes, hipMemcpyDeviceToDevice, (hipStream_t)s));
-    return DPENV_OK;
+    return current_io(h, "dpenv_get_current_mean", vc_out, beta_out, CUR_MEAN, s);
 }
 
 extern "C" int dpenv_set_current_randomisation(dpenv_handle h, const float* vc_nominal, const float* beta_nominal, float vc_range,
@@ -572,7 +345,7 @@ extern "C" int dpenv_set_current_randomisation(dpenv_handle h, const float* vc_n
 {
     if (!h) return DPENV_EINVAL;
     DeviceGuard dev_guard(h->device);
-    if (!h->cfg.current_enabled) return fail(h, DPENV_EINVAL, "config.current_enabled is 0");
+    if (int rc = require_current(h)) return rc;
     if (!(vc_range >= 0.0f) || !(beta_range >= 0.0f) || !std::isfinite(vc_range) || !std::isfinite(beta_range))
         return fail(h, DPENV_EINVAL, "the half-ranges must be finite and >= 0");
     if (vc_range == 0.0f && beta_range == 0.0f) {             // off: every env keeps the current (and the drift mean) it has
@@ -597,15 +370,20 @@ extern "C" int dpenv_set_current_randomisation(dpenv_handle h, const float* vc_n
 // The packing kernel's flag word is on its way to the host (dpenv_set_vessel_params): take it if it has arrived; wait for it unless the launch
 // that asks is being RECORDED into a graph - a recorded launch (and every launch after a setter that was itself recorded) runs the general
 // per-env kernels with the table's coefficients applied (LOSS_TABLE): where no env has one they are zeros, which leave every row as it is
+static bool is_capturing(hipStream_t s)
+{
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    (void)hipStreamIsCapturing(s, &cap);
+    return cap != hipStreamCaptureStatusNone;
+}
+
 static void resolve_loss(dpenv_handle h, hipStream_t s)
 {
     if (!h->loss_pending) return;
     hipError_t q = hipEventQuery(h->loss_ev);
     if (q == hipErrorNotReady) {
         (void)hipGetLastError();                                        // (not an error: the launch below must not report it)
-        hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-        (void)hipStreamIsCapturing(s, &cap);
-        if (cap != hipStreamCaptureStatusNone) return;
+        if (is_capturing(s)) return;
         q = hipEventSynchronize(h->loss_ev);
     }
     if (q != hipSuccess) { (void)hipGetLastError(); return; }            // unknown stays unknown: the loss stays applied
@@ -653,7 +431,44 @@ static int vessel_source(dpenv_handle h)
     return (h->shared_loss || (h->cur_rand && h->cfg.current_enabled)) ? VES_ARGS_LOSS : VES_ARGS;
 }
 
-static bool classes_missing(dpenv_handle h) { return !h->per_env && h->n_classes > 1 && !h->classes_assigned; }
+// a per-env state block of count x n_envs float4 (integral action, reference filter, DP controller): allocated by the first call that turns
+// the feature on, kept while it is off, released with the handle
+static int ensure_env_state(dpenv_handle h, float4** block, int count, const char* msg)
+{
+    if (*block) return DPENV_OK;
+    void* p = nullptr;
+    if (hipMalloc(&p, sizeof(float4) * count * (size_t)h->cfg.n_envs) != hipSuccess) return fail(h, DPENV_ENOMEM, "%s", msg);
+    *block = (float4*)p;
+    return DPENV_OK;
+}
+
+static int require_classes(dpenv_handle h)
+{
+    if (!h->per_env && h->n_classes > 1 && !h->classes_assigned)
+        return fail(h, DPENV_EINVAL, "n_classes > 1 but dpenv_set_vessel_class was never called");
+    return DPENV_OK;
+}
+
+// the setpoint schedule of a T-step launch: dpenv_rollout_io, dpenv_policy_rollout_io and dpenv_controller_rollout_io carry the same fields
+template <class IO>
+static int check_schedule(dpenv_handle h, const IO* io)
+{
+    if (io->n_switch < 0 || io->n_switch > DPENV_MAX_SWITCH || (io->n_switch > 0 && !io->refs))
+        return fail(h, DPENV_EINVAL, "bad setpoint schedule");
+    for (int k = 0; k < io->n_switch; ++k)
+        if (io->switch_step[k] < 0 || io->switch_step[k] >= io->T || (k > 0 && io->switch_step[k] <= io->switch_step[k - 1]))
+            return fail(h, DPENV_EINVAL, "switch_step must be strictly increasing within [0, T)");
+    return DPENV_OK;
+}
+
+// ... into the launch's argument block (RolloutArgs, PolicyArgs, ControlArgs)
+template <class IO, class Args>
+static void copy_schedule(const IO* io, Args& a)
+{
+    a.n_switch = io->n_switch;
+    a.refs = io->refs;
+    for (int k = 0; k < io->n_switch; ++k) a.switch_step[k] = io->switch_step[k];
+}
 
 // ---- per-env parameter blocks ------------------------------------------------------------------------------------------------
 extern "C" int dpenv_set_vessel_params_ex(dpenv_handle h, const float* params, uint32_t flags, dpenv_stream s)
@@ -680,8 +495,7 @@ extern "C" int dpenv_set_vessel_params_ex(dpenv_handle h, const float* params, u
         h->loss_state = LOSS_OFF;
         return DPENV_OK;
     }
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    HIP_TRY(h, hipStreamIsCapturing((hipStream_t)s, &cap));
+    const bool capturing = is_capturing((hipStream_t)s);
     // stream-ordered, no read-back: the packing kernel leaves "some env has a thrust-loss coefficient" in the word behind the table
     HIP_TRY(h, hipMemsetAsync(h->loss_flag, 0, sizeof(uint32_t), (hipStream_t)s));
     HIP_TRY(h, dev::launch_pack_env_vessels(params, (int64_t)h->cfg.n_envs, 1, h->env_tab, h->loss_flag, h->env_stride, h->cfg.n_envs, (hipStream_t)s));
@@ -689,7 +503,7 @@ extern "C" int dpenv_set_vessel_params_ex(dpenv_handle h, const float* params, u
     // Outside a capture it also travels to a pinned host word behind an event: the next launch takes the answer from there (resolve_loss);
     // recorded into a graph the setter leaves the answer unknown: the general kernels then apply the table's coefficients whatever they are.
     bool pending = false;
-    if (cap == hipStreamCaptureStatusNone) {
+    if (!capturing) {
         HIP_TRY(h, hipMemcpyAsync(h->loss_host, h->loss_flag, sizeof(uint32_t), hipMemcpyDeviceToHost, (hipStream_t)s));
         HIP_TRY(h, hipEventRecord(h->loss_ev, (hipStream_t)s));
         pending = true;
@@ -784,8 +598,7 @@ extern "C" int dpenv_step_ex(dpenv_handle h, const dpenv_step_io* io, dpenv_stre
     if (h->reff_on) return fail(h, DPENV_EINVAL, REFF_OPEN_LOOP_MSG, "dpenv_step");
     if (!io->action || !io->obs || !io->reward || !io->done)
         return fail(h, DPENV_EINVAL, "action, obs, reward and done buffers are required");
-    if (classes_missing(h))
-        return fail(h, DPENV_EINVAL, "n_classes > 1 but dpenv_set_vessel_class was never called");
+    if (int rc = require_classes(h)) return rc;
     StepArgs a = h->args;
     bind_optional(h, a, (hipStream_t)s);
     a.action = io->action;
@@ -811,8 +624,7 @@ extern "C" int dpenv_step_ex(dpenv_handle h, const dpenv_step_io* io, dpenv_stre
 extern "C" int dpenv_step(dpenv_handle h, const float* action, const float* new_ref, void* obs_out, float* rew_out,
                           uint8_t* done_out, dpenv_stream s)
 {
-    dpenv_step_io io;
-    std::memset(&io, 0, sizeof io);
+    dpenv_step_io io = {};
     io.struct_size = (uint32_t)sizeof io;
     io.action = action; io.new_ref = new_ref; io.obs = obs_out; io.reward = rew_out; io.done = done_out;
     return dpenv_step_ex(h, &io, s);
@@ -827,20 +639,13 @@ extern "C" int dpenv_rollout(dpenv_handle h, const dpenv_rollout_io* io, dpenv_s
     if (h->reff_on) return fail(h, DPENV_EINVAL, REFF_OPEN_LOOP_MSG, "dpenv_rollout");
     if (io->T <= 0 || !io->actions || !io->obs || !io->reward || !io->done)
         return fail(h, DPENV_EINVAL, "T > 0 and action, obs, reward, done blocks are required");
-    if (io->n_switch < 0 || io->n_switch > DPENV_MAX_SWITCH || (io->n_switch > 0 && !io->refs))
-        return fail(h, DPENV_EINVAL, "bad setpoint schedule");
-    for (int k = 0; k < io->n_switch; ++k)
-        if (io->switch_step[k] < 0 || io->switch_step[k] >= io->T || (k > 0 && io->switch_step[k] <= io->switch_step[k - 1]))
-            return fail(h, DPENV_EINVAL, "switch_step must be strictly increasing within [0, T)");
-    if (classes_missing(h))
-        return fail(h, DPENV_EINVAL, "n_classes > 1 but dpenv_set_vessel_class was never called");
+    if (int rc = check_schedule(h, io)) return rc;
+    if (int rc = require_classes(h)) return rc;
     StepArgs a = h->args;
     bind_optional(h, a, (hipStream_t)s);
-    RolloutArgs ra;
-    std::memset(&ra, 0, sizeof ra);
+    RolloutArgs ra = {};
     ra.T = io->T; ra.actions = io->actions; ra.obs = io->obs; ra.rew = io->reward; ra.done = io->done;
-    ra.n_switch = io->n_switch; ra.refs = io->refs;
-    for (int k = 0; k < io->n_switch; ++k) ra.switch_step[k] = io->switch_step[k];
+    copy_schedule(io, ra);
     // env wave + row wave while the chip has issue slots to spare (measured: 16 384 ... 98 304 envs 5-20 % faster, 131 072 equal, 262 144 and
     // above 10-15 % slower than one wave per 64 envs: profiles/r04_fused_two_wave.txt, r04_batch_sweep.txt)
     // (the randomisation's instantiation needs 201 VGPRs: two waves per SIMD, i.e. up to 256 envs per CU)
@@ -865,6 +670,89 @@ static int check_net(const dpenv_mlp* m, int in_dim, int out_dim, std::string* w
     return DPENV_OK;
 }
 
+// What an upload's shape, arithmetic, activation and launch form come to: the part of PolicyArgs a kernel node holds by value (the image's
+// layout - FragAddr, dpenv_policy_dev.h - and the launch form AUTO resolves to; the other fields zero) and the LDS footprint in either form
+struct PolicyLayout {
+    PolicyArgs pa;          // nent, nblk, ks, n_hidden, act, leak, split, critic_f16, ws, ws_groups
+    size_t bytes_frags, bytes_bias, lds_image, lds_two;
+    bool form_two, fits_one, fits_two;
+};
+
+static PolicyLayout policy_layout(const dpenv_policy_desc* d, int n_envs, int n_cus)
+{
+    PolicyLayout L = {};
+    PolicyArgs& p = L.pa;
+    const int H = d->pi->sizes[1];
+    p.n_hidden = d->pi->n_layers - 1;
+    p.ks = H <= 80 ? 5 : 6;
+    p.nent = (128 + (p.ks == 5 ? 32 : 64)) + (p.n_hidden - 1) * p.ks * (128 + (p.ks == 5 ? 32 : 64)) + p.ks * 16;
+    p.nblk = 3 * (p.n_hidden - 1) + 1;
+    p.act = d->activation;
+    p.leak = d->leak;
+    p.split = d->precision != DPENV_POLICY_F16;
+    p.critic_f16 = d->precision == DPENV_POLICY_F32_ACTOR;
+    L.bytes_frags = (size_t)2 * p.nent * 16 * (1 + p.split);
+    L.bytes_bias = (size_t)2 * p.nblk * 32 * sizeof(float);
+    // the launch form decides the LDS footprint.  The two-wave form stages the images its network wave reads (f16: actor + critic;
+    // F32_ACTOR: + the actor's low image; F32: all four) and a mailbox group per 64 envs; it exists for leaky-relu / relu in every
+    // arithmetic and for tanh in f16.
+    const size_t per_image = (size_t)p.nent * 16, lds_max = 160 * 1024;
+    const int n_img_two = !p.split ? 2 : (p.critic_f16 ? 3 : 4);
+    L.lds_image = L.bytes_frags + L.bytes_bias;
+    L.lds_two = n_img_two * per_image + L.bytes_bias + (p.split ? POLICY_WS_MAILBOX_X_BYTES : POLICY_WS_MAILBOX_BYTES);
+    L.form_two = !p.split || d->activation == DPENV_ACT_LEAKY_RELU;
+    L.fits_two = L.form_two && L.lds_two <= lds_max;
+    L.fits_one = L.lds_image + (p.split ? 0 : POLICY_STAGING_BYTES) <= lds_max;
+    // AUTO: the two-wave form where it exists and fits (the faster one), else one wave per 64 envs
+    p.ws = d->launch_form == DPENV_LAUNCH_TWO_WAVE ? 1 : (d->launch_form == DPENV_LAUNCH_ONE_WAVE ? 0 : (L.fits_two ? 1 : 0));
+    // two-wave geometry: 128-env workgroups (a SIMD per wave) while one round of them fits the chip, else 256-env workgroups;
+    // tanh has the 256-env form only
+    p.ws_groups = (d->activation == DPENV_ACT_LEAKY_RELU && (n_envs + 127) / 128 <= n_cus) ? 2 : 4;
+    return L;
+}
+
+// a captured kernel node holds these BY VALUE next to the image's address (dpenv_s::pol_pin_layout): an in-place upload that changed one
+// of them would be read with the old layout - wrong weights and no error
+static bool layout_differs(const PolicyArgs& q, const PolicyArgs& p)
+{
+    return q.nent != p.nent || q.nblk != p.nblk || q.ks != p.ks || q.n_hidden != p.n_hidden || q.act != p.act || q.leak != p.leak ||
+           q.split != p.split || q.critic_f16 != p.critic_f16 || q.ws != p.ws || q.ws_groups != p.ws_groups;
+}
+
+// host weights: staged raw in device memory by stream-ordered copies (pn and *ls_dev point into the staging), then packed on the device
+// like the other form
+static int stage_host_weights(dpenv_handle h, const dpenv_policy_desc* d, int ad, PackNet pn[2], const float** ls_dev, hipStream_t s)
+{
+    const int nl = d->pi->n_layers;
+    size_t raw = 8;
+    for (int k = 0; k < 2; ++k) {
+        const dpenv_mlp* m = k ? d->v : d->pi;
+        for (int l = 0; l < nl; ++l) raw += (size_t)m->sizes[l] * m->sizes[l + 1] + m->sizes[l + 1];
+    }
+    // the staging area is reused by every host-pointer upload: the previous one's packing kernel must be done with it (this
+    // form is synchronous anyway, see the end of dpenv_set_policy_desc)
+    if (h->pol_raw && h->pol_raw_bytes < raw * sizeof(float)) { HIP_TRY(h, hipDeviceSynchronize()); (void)hipFree(h->pol_raw); h->pol_raw = nullptr; }
+    if (!h->pol_raw) {
+        void* p = nullptr;
+        if (hipMalloc(&p, raw * sizeof(float)) != hipSuccess) return fail(h, DPENV_ENOMEM, "hipMalloc of the weight staging failed");
+        h->pol_raw = (float*)p; h->pol_raw_bytes = raw * sizeof(float);
+    }
+    float* cursor = h->pol_raw;
+    HIP_TRY(h, hipMemcpyAsync(cursor, d->log_std, sizeof(float) * ad, hipMemcpyHostToDevice, s));
+    *ls_dev = cursor; cursor += 8;
+    for (int k = 0; k < 2; ++k) {
+        const dpenv_mlp* m = k ? d->v : d->pi;
+        for (int l = 0; l < nl; ++l) {
+            const size_t nw = (size_t)m->sizes[l] * m->sizes[l + 1], nb = m->sizes[l + 1];
+            HIP_TRY(h, hipMemcpyAsync(cursor, m->W[l], nw * sizeof(float), hipMemcpyHostToDevice, s));
+            pn[k].W[l] = cursor; cursor += nw;
+            HIP_TRY(h, hipMemcpyAsync(cursor, m->b[l], nb * sizeof(float), hipMemcpyHostToDevice, s));
+            pn[k].b[l] = cursor; cursor += nb;
+        }
+    }
+    return DPENV_OK;
+}
+
 extern "C" int dpenv_set_policy_desc(dpenv_handle h, const dpenv_policy_desc* d, dpenv_stream s)
 {
     if (!h) return DPENV_EINVAL;
@@ -886,51 +774,35 @@ extern "C" int dpenv_set_policy_desc(dpenv_handle h, const dpenv_policy_desc* d,
     std::string why;
     if (check_net(pi, od, ad, &why) != DPENV_OK) return fail(h, DPENV_EINVAL, "actor: %s", why.c_str());
     if (check_net(v, od, 1, &why) != DPENV_OK) return fail(h, DPENV_EINVAL, "critic: %s", why.c_str());
-    const int nl = pi->n_layers, n_hidden = nl - 1, H = pi->sizes[1];
-    const int ks = H <= 80 ? 5 : 6;
-    const int nent = (128 + (ks == 5 ? 32 : 64)) + (n_hidden - 1) * ks * (128 + (ks == 5 ? 32 : 64)) + ks * 16;   // FragAddr, dpenv_policy_dev.h
-    const int nblk = 3 * (n_hidden - 1) + 1;
-    const int split = d->precision != DPENV_POLICY_F16;
-    const size_t bytes_frags = (size_t)2 * nent * 16 * (1 + split), bytes_bias = (size_t)2 * nblk * 32 * sizeof(float);
-    // the launch form decides the LDS footprint: refuse here what the rollout could not launch.  The two-wave form stages the
-    // images its network wave reads (f16: actor + critic; F32_ACTOR: + the actor's low image; F32: all four) and a mailbox group
-    // per 64 envs; it exists for leaky-relu / relu in every arithmetic and for tanh in f16.
-    const size_t per_image = (size_t)nent * 16, lds_max = 160 * 1024;
-    const int n_img_two = !split ? 2 : (d->precision == DPENV_POLICY_F32_ACTOR ? 3 : 4);
-    const size_t lds_image = bytes_frags + bytes_bias;
-    const size_t lds_two = n_img_two * per_image + bytes_bias + (split ? POLICY_WS_MAILBOX_X_BYTES : POLICY_WS_MAILBOX_BYTES);
-    const bool form_two = !split || d->activation == DPENV_ACT_LEAKY_RELU;
-    const bool fits_two = form_two && lds_two <= lds_max;
-    const bool fits_one = lds_image + (split ? 0 : POLICY_STAGING_BYTES) <= lds_max;
-    if (!fits_one) return fail(h, DPENV_EINVAL, "networks do not fit the 160 KiB LDS (%zu bytes of fragments and biases)", lds_image);
-    if (d->launch_form == DPENV_LAUNCH_TWO_WAVE && !fits_two)
-        return fail(h, DPENV_EINVAL, form_two ? "networks + the two-wave form's mailboxes exceed the 160 KiB LDS (%zu bytes): use DPENV_LAUNCH_ONE_WAVE"
-                                              : "the split arithmetics have a two-wave form for leaky-relu / relu only (%zu)", lds_two);
+    const int nl = pi->n_layers, H = pi->sizes[1];
+    // refuse here what the rollout could not launch
+    const PolicyLayout L = policy_layout(d, h->cfg.n_envs, h->n_cus);
+    if (!L.fits_one) return fail(h, DPENV_EINVAL, "networks do not fit the 160 KiB LDS (%zu bytes of fragments and biases)", L.lds_image);
+    if (d->launch_form == DPENV_LAUNCH_TWO_WAVE && !L.fits_two)
+        return fail(h, DPENV_EINVAL, L.form_two ? "networks + the two-wave form's mailboxes exceed the 160 KiB LDS (%zu bytes): use DPENV_LAUNCH_ONE_WAVE"
+                                                : "the split arithmetics have a two-wave form for leaky-relu / relu only (%zu)", L.lds_two);
     // two images, written alternately: launches issued before this call keep reading the one they were given (the header's
     // promise), whatever stream they run on; the image written now was last read by launches issued before the PREVIOUS upload,
     // and this stream waits for the last of them (an event recorded behind every launch that reads an image).
-    const size_t need = (bytes_frags + bytes_bias + 24 * sizeof(float) + 255) / 256 * 256;
+    const size_t need = (L.bytes_frags + L.bytes_bias + 24 * sizeof(float) + 255) / 256 * 256;
     if (h->pol_buf && h->pol_buf_bytes < 2 * need) {
         // growing the images: a launch that still reads the old ones may be in flight
         HIP_TRY(h, hipDeviceSynchronize());
         (void)hipFree(h->pol_buf); h->pol_buf = nullptr; h->pol_buf_bytes = 0;
         h->has_policy = false;
-        std::memset(&h->pol, 0, sizeof h->pol);
+        h->pol = {};
         h->pol_read_valid[0] = h->pol_read_valid[1] = false;
         h->pol_pinned = -1;                                   // graphs captured on the old images are void (dpenv.h)
     }
     if (!h->pol_buf) {
         if (hipMalloc(&h->pol_buf, 2 * need) != hipSuccess) {
-            h->pol_buf = nullptr; h->pol_buf_bytes = 0; h->has_policy = false;
-            std::memset(&h->pol, 0, sizeof h->pol);
+            h->pol_buf = nullptr;                             // (a handle without images has no policy: see above, or it never had one)
             return fail(h, DPENV_ENOMEM, "hipMalloc of the policy images failed");
         }
         h->pol_buf_bytes = 2 * need;
         h->pol_slot = 0;
     }
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    (void)hipStreamIsCapturing((hipStream_t)s, &cap);
-    const bool capturing = cap != hipStreamCaptureStatusNone;      // inside a captured graph the graph's own edges order everything
+    const bool capturing = is_capturing((hipStream_t)s);            // inside a captured graph the graph's own edges order everything
     // Which image this upload writes.  Eager launches read the image the last upload wrote (h->pol), so uploads alternate and a launch
     // in flight keeps its weights.  A launch RECORDED INTO A GRAPH has the image's address baked into its kernel node: once that has
     // happened (pol_pinned) an alternating upload would leave every second set of weights invisible to the replays - so from then on
@@ -939,49 +811,15 @@ extern "C" int dpenv_set_policy_desc(dpenv_handle h, const dpenv_policy_desc* d,
     //  An upload recorded INTO a graph after an image has been pinned goes into the pinned image as well: alternating there would
     // pin the other image at the next captured launch, and the graphs captured first would stop seeing uploads.
     const int slot = (h->pol_pinned >= 0) ? h->pol_pinned : h->pol_slot;
-    const int ws_new = d->launch_form == DPENV_LAUNCH_TWO_WAVE ? 1 : (d->launch_form == DPENV_LAUNCH_ONE_WAVE ? 0 : (fits_two ? 1 : 0));
-    const int groups_new = (d->activation == DPENV_ACT_LEAKY_RELU && (h->cfg.n_envs + 127) / 128 <= h->n_cus) ? 2 : 4;
-    if (h->pol_pinned >= 0) {
-        // the captured kernel nodes hold nent, nblk, ks, n_hidden, act, leak, split, critic_f16, ws, ws_groups BY VALUE next to the image's
-        // address: an in-place upload of another shape, arithmetic, activation or launch form would be read with the old layout - wrong
-        // weights and no error.  Refused; dpenv_release_policy_graphs() ends the pin once the graphs are gone.
-        const PolicyArgs& q = h->pol_pin_layout;
-        if (q.nent != nent || q.nblk != nblk || q.ks != ks || q.n_hidden != n_hidden || q.act != d->activation || q.leak != d->leak ||
-            q.split != split || q.critic_f16 != (d->precision == DPENV_POLICY_F32_ACTOR ? 1 : 0) || q.ws != ws_new || q.ws_groups != groups_new)
-            return fail(h, DPENV_EINVAL, "a captured graph reads the policy image with another layout (hidden shape, precision, activation, leak or launch "
-                                         "form differ): destroy the graphs and call dpenv_release_policy_graphs() before uploading this policy");
-    }
+    // Refused while pinned; dpenv_release_policy_graphs() ends the pin once the graphs are gone.
+    if (h->pol_pinned >= 0 && layout_differs(h->pol_pin_layout, L.pa))
+        return fail(h, DPENV_EINVAL, "a captured graph reads the policy image with another layout (hidden shape, precision, activation, leak or launch "
+                                     "form differ): destroy the graphs and call dpenv_release_policy_graphs() before uploading this policy");
     if (!capturing && h->pol_read_valid[slot]) HIP_TRY(h, hipStreamWaitEvent((hipStream_t)s, h->pol_read[slot], 0));
     PackNet pn[2];
     const float* ls_dev = d->log_std;
     if (!d->device_pointers) {
-        // host weights: stage them raw in device memory (stream-ordered copies), then pack on the device like the other form
-        size_t raw = 8;
-        for (int k = 0; k < 2; ++k) {
-            const dpenv_mlp* m = k ? v : pi;
-            for (int l = 0; l < nl; ++l) raw += (size_t)m->sizes[l] * m->sizes[l + 1] + m->sizes[l + 1];
-        }
-        // the staging area is reused by every host-pointer upload: the previous one's packing kernel must be done with it (this
-        // form is synchronous anyway, see the end of this function)
-        if (h->pol_raw && h->pol_raw_bytes < raw * sizeof(float)) { HIP_TRY(h, hipDeviceSynchronize()); (void)hipFree(h->pol_raw); h->pol_raw = nullptr; }
-        if (!h->pol_raw) {
-            void* p = nullptr;
-            if (hipMalloc(&p, raw * sizeof(float)) != hipSuccess) return fail(h, DPENV_ENOMEM, "hipMalloc of the weight staging failed");
-            h->pol_raw = (float*)p; h->pol_raw_bytes = raw * sizeof(float);
-        }
-        float* cursor = h->pol_raw;
-        HIP_TRY(h, hipMemcpyAsync(cursor, d->log_std, sizeof(float) * ad, hipMemcpyHostToDevice, (hipStream_t)s));
-        ls_dev = cursor; cursor += 8;
-        for (int k = 0; k < 2; ++k) {
-            const dpenv_mlp* m = k ? v : pi;
-            for (int l = 0; l < nl; ++l) {
-                const size_t nw = (size_t)m->sizes[l] * m->sizes[l + 1], nb = m->sizes[l + 1];
-                HIP_TRY(h, hipMemcpyAsync(cursor, m->W[l], nw * sizeof(float), hipMemcpyHostToDevice, (hipStream_t)s));
-                pn[k].W[l] = cursor; cursor += nw;
-                HIP_TRY(h, hipMemcpyAsync(cursor, m->b[l], nb * sizeof(float), hipMemcpyHostToDevice, (hipStream_t)s));
-                pn[k].b[l] = cursor; cursor += nb;
-            }
-        }
+        if (int rc = stage_host_weights(h, d, ad, pn, &ls_dev, (hipStream_t)s)) return rc;
     } else {
         for (int k = 0; k < 2; ++k) {
             const dpenv_mlp* m = k ? v : pi;
@@ -993,27 +831,13 @@ extern "C" int dpenv_set_policy_desc(dpenv_handle h, const dpenv_policy_desc* d,
         for (int l = nl; l < 5; ++l) { pn[k].W[l] = nullptr; pn[k].b[l] = nullptr; }
     }
     char* base = (char*)h->pol_buf + (size_t)slot * (h->pol_buf_bytes / 2);
-    float* bias = (float*)(base + bytes_frags);
-    float* consts = (float*)(base + bytes_frags + bytes_bias);
-    HIP_TRY(h, dev::launch_pack_policy(&pn[0], &pn[1], ls_dev, ad, ks, nent, nblk, split, base, bias, consts, (hipStream_t)s));
-    PolicyArgs& pa = h->pol;
-    std::memset(&pa, 0, sizeof pa);
-    pa.frags = (const uint4*)base;
-    pa.bias = bias;
-    pa.consts = consts;
-    pa.nent = nent;
-    pa.nblk = nblk;
-    pa.ks = ks;
-    pa.act = d->activation;
-    pa.split = split;
-    pa.critic_f16 = d->precision == DPENV_POLICY_F32_ACTOR;
-    pa.n_hidden = n_hidden;
-    pa.leak = d->leak;
-    // AUTO: the two-wave form where it exists and fits (the faster one), else one wave per 64 envs
-    pa.ws = ws_new;
-    // two-wave geometry: 128-env workgroups (a SIMD per wave) while one round of them fits the chip, else 256-env workgroups;
-    // tanh has the 256-env form only
-    pa.ws_groups = groups_new;
+    float* bias = (float*)(base + L.bytes_frags);
+    float* consts = (float*)(base + L.bytes_frags + L.bytes_bias);
+    HIP_TRY(h, dev::launch_pack_policy(&pn[0], &pn[1], ls_dev, ad, L.pa.ks, L.pa.nent, L.pa.nblk, L.pa.split, base, bias, consts, (hipStream_t)s));
+    h->pol = L.pa;
+    h->pol.frags = (const uint4*)base;
+    h->pol.bias = bias;
+    h->pol.consts = consts;
     h->pol_form = d->launch_form;
     h->has_policy = true;
     h->pol_cur = slot;                                       // "current" = the image just written (pinned or not)
@@ -1027,9 +851,7 @@ extern "C" int dpenv_set_policy_desc(dpenv_handle h, const dpenv_policy_desc* d,
 static int mark_policy_read(dpenv_handle h, dpenv_stream s)
 {
     const int cur = h->pol_cur;                             // the image the last upload wrote
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    (void)hipStreamIsCapturing((hipStream_t)s, &cap);
-    if (cap != hipStreamCaptureStatusNone) {
+    if (is_capturing((hipStream_t)s)) {
         h->pol_pinned = cur;                                // a graph now holds this image's address: uploads go in place from here on
         h->pol_pin_layout = h->pol;                         // ... and its layout / launch form, by value
         return DPENV_OK;
@@ -1051,8 +873,7 @@ static int mark_policy_read(dpenv_handle h, dpenv_stream s)
 extern "C" int dpenv_set_policy_ex(dpenv_handle h, const dpenv_mlp* pi, const dpenv_mlp* v, const float* log_std, int32_t activation,
                                    float leak)
 {
-    dpenv_policy_desc d;
-    std::memset(&d, 0, sizeof d);
+    dpenv_policy_desc d = {};
     d.struct_size = (uint32_t)sizeof d;
     d.pi = pi; d.v = v; d.log_std = log_std; d.activation = activation; d.leak = leak;
     d.precision = DPENV_POLICY_F16; d.launch_form = DPENV_LAUNCH_AUTO; d.device_pointers = 0;
@@ -1107,27 +928,22 @@ extern "C" int dpenv_policy_forward(dpenv_handle h, const float* obs, float* mu_
     DeviceGuard dev_guard(h->device);
     if (!h->has_policy) return fail(h, DPENV_EINVAL, "dpenv_set_policy has not been called");
     if (!obs || !mu_out || !v_out || n <= 0) return fail(h, DPENV_EINVAL, "dpenv_policy_forward: bad argument");
-    if (h->pol.split)
-        HIP_TRY(h, dev::launch_policy_forward_x(&h->pol, dpenv_obs_dim(&h->cfg), dpenv_act_dim(&h->cfg), obs, mu_out, v_out, n,
-                                                     (hipStream_t)s));
-    else
-        HIP_TRY(h, dev::launch_policy_forward(&h->pol, dpenv_obs_dim(&h->cfg), dpenv_act_dim(&h->cfg), obs, mu_out, v_out, n,
-                                                   (hipStream_t)s));
+    const auto forward = h->pol.split ? dev::launch_policy_forward_x : dev::launch_policy_forward;
+    HIP_TRY(h, forward(&h->pol, dpenv_obs_dim(&h->cfg), dpenv_act_dim(&h->cfg), obs, mu_out, v_out, n, (hipStream_t)s));
     return mark_policy_read(h, s);
 }
 
 // Which closed-loop kernel runs: the one place that decides.  The two-wave form runs where its launcher has the instantiation (the ws_*
 // predicates of dpenv_dev.h, the same ones it instantiates by); everything else runs the one-wave kernels - the same rows bit for bit, the
 // hull / current re-draw and the table's thrust loss a run-time switch there, which know the thrust loss through the table alone.
+#define ONE_WAVE_SET_MSG "%s runs with the final variant (continuous angles), limited or full, extended_state, and a leaky-relu / relu network of hidden width <= 80"
 static int launch_closed_loop(dpenv_handle h, StepArgs& a, PolicyArgs& pa, const IntegArgs* ia, const FilterArgs* fa, hipStream_t s)
 {
     const int mode = h->mode, ext = h->cfg.extended_state, ka = pa.ks + 16 * pa.act;
     if (ia && !integ_one_wave(mode, ext, ka))
-        return fail(h, DPENV_EINVAL, "the integral action runs with the final variant (continuous angles), limited or full, extended_state, and a "
-                                     "leaky-relu / relu network of hidden width <= 80");
+        return fail(h, DPENV_EINVAL, ONE_WAVE_SET_MSG, "the integral action");
     if (fa && !reff_one_wave(mode, ext, ka))
-        return fail(h, DPENV_EINVAL, "the reference filter runs with the final variant (continuous angles), limited or full, extended_state, and a "
-                                     "leaky-relu / relu network of hidden width <= 80");
+        return fail(h, DPENV_EINVAL, ONE_WAVE_SET_MSG, "the reference filter");
     const bool general = a.rand_tab || a.loss_on != LOSS_NONE || a.cur_nom;       // hull / current re-draws, a thrust loss
     if ((general && !ws_general(mode, ext, ka)) || (ia && !ws_integ(mode, ext, ka)) || (fa && !ws_reff(mode, ext, ka))) pa.ws = 0;
     hipError_t e;
@@ -1154,25 +970,19 @@ static int policy_rollout_impl(dpenv_handle h, const dpenv_policy_rollout_io* io
         return fail(h, DPENV_EINVAL, "T > 0 and every output block are required");
     if (h->cfg.action_layout != DPENV_AOS || h->cfg.obs_layout != DPENV_AOS)
         return fail(h, DPENV_EINVAL, "policy rollout needs AOS layouts");
-    if (classes_missing(h))
-        return fail(h, DPENV_EINVAL, "n_classes > 1 but dpenv_set_vessel_class was never called");
-    if (io->n_switch < 0 || io->n_switch > DPENV_MAX_SWITCH || (io->n_switch > 0 && !io->refs))
-        return fail(h, DPENV_EINVAL, "bad setpoint schedule");
-    for (int k = 0; k < io->n_switch; ++k)
-        if (io->switch_step[k] < 0 || io->switch_step[k] >= io->T || (k > 0 && io->switch_step[k] <= io->switch_step[k - 1]))
-            return fail(h, DPENV_EINVAL, "switch_step must be strictly increasing within [0, T)");
+    if (int rc = require_classes(h)) return rc;
+    if (int rc = check_schedule(h, io)) return rc;
     StepArgs a = h->args;
     bind_optional(h, a, (hipStream_t)s);
     PolicyArgs pa = h->pol;
     pa.T = io->T; pa.noise = io->noise; pa.obs_out = io->obs; pa.act_out = io->act; pa.rew = io->reward; pa.val = io->value;
     pa.logp = io->logp; pa.done = io->done; pa.boot = io->boot; pa.last_obs = io->last_obs; pa.last_val = io->last_value;
-    pa.n_switch = io->n_switch; pa.refs = io->refs;
     pa.sample = io->sample ? 1 : 0;
     pa.reset_at_end = io->reset_at_end ? 1 : 0;
     pa.use_lag = h->lag_valid ? 1 : 0;
     if (pa.reset_at_end && !h->cfg.auto_reset)
         return fail(h, DPENV_EINVAL, "reset_at_end re-draws every env with the training sampler: it needs config.auto_reset");
-    for (int k = 0; k < io->n_switch; ++k) pa.switch_step[k] = io->switch_step[k];
+    copy_schedule(io, pa);
     IntegArgs ia = h->integ;
     ia.out = integ_out;
     FilterArgs fa = h->reff;
@@ -1206,84 +1016,6 @@ extern "C" int dpenv_policy_rollout_deployed(dpenv_handle h, const dpenv_policy_
 }
 
 // ---- the setpoint reference filter (dpenv.h) -------------------------------------------------------------------------------------
-// exp(M) of the 4x4 augmented system M = [[A, B], [0, 0]] dt of one axis, in f64: scaling and squaring of the degree-18 Taylor polynomial
-// (||M / 2^sq||_1 <= 1/2: truncation below 1e-22).  deploy.reference_filter_coeffs_f64 is the same recipe in NumPy.
-static void reff_coeffs_f64(double w, double z, double dt, double phi[9], double gam[3])
-{
-    const double c = 2.0 * z + 1.0;
-    double M[4][4] = {{0.0, 1.0, 0.0, 0.0}, {0.0, 0.0, 1.0, 0.0}, {-w * w * w, -c * w * w, -c * w, w * w * w}, {0.0, 0.0, 0.0, 0.0}};
-    double norm = 0.0;
-    for (int col = 0; col < 4; ++col) {
-        double sum = 0.0;
-        for (int r = 0; r < 4; ++r) { M[r][col] *= dt; sum += std::fabs(M[r][col]); }
-        norm = std::fmax(norm, sum);
-    }
-    int sq = 0;
-    while (norm > 0.5 && sq < 200) { norm *= 0.5; ++sq; }
-    const double scale = std::ldexp(1.0, -sq);
-    for (int r = 0; r < 4; ++r) for (int col = 0; col < 4; ++col) M[r][col] *= scale;
-    double E[4][4], T[4][4];                                     // E = sum_k M^k / k!, T = the running term
-    for (int r = 0; r < 4; ++r) for (int col = 0; col < 4; ++col) E[r][col] = T[r][col] = (r == col) ? 1.0 : 0.0;
-    for (int k = 1; k <= 18; ++k) {
-        double U[4][4];
-        for (int r = 0; r < 4; ++r) for (int col = 0; col < 4; ++col) {
-            double acc = 0.0;
-            for (int q = 0; q < 4; ++q) acc += T[r][q] * M[q][col];
-            U[r][col] = acc / (double)k;
-        }
-        for (int r = 0; r < 4; ++r) for (int col = 0; col < 4; ++col) { T[r][col] = U[r][col]; E[r][col] += U[r][col]; }
-    }
-    for (int k = 0; k < sq; ++k) {
-        double U[4][4];
-        for (int r = 0; r < 4; ++r) for (int col = 0; col < 4; ++col) {
-            double acc = 0.0;
-            for (int q = 0; q < 4; ++q) acc += E[r][q] * E[q][col];
-            U[r][col] = acc;
-        }
-        std::memcpy(E, U, sizeof E);
-    }
-    for (int r = 0; r < 3; ++r) {
-        for (int col = 0; col < 3; ++col) phi[3 * r + col] = E[r][col];
-        gam[r] = E[r][3];
-    }
-}
-
-static const char* reff_check(const dpenv_reference_filter* rf)
-{
-    if (rf->struct_size != sizeof(dpenv_reference_filter)) return "dpenv_reference_filter ABI mismatch";
-    for (int j = 0; j < 3; ++j) {
-        if (!std::isfinite(rf->omega[j]) || !(rf->omega[j] > 0.0f)) return "reference filter: omega must be finite and > 0 on every axis";
-        if (!std::isfinite(rf->zeta[j]) || !(rf->zeta[j] > 0.0f)) return "reference filter: zeta must be finite and > 0 on every axis";
-    }
-    return nullptr;
-}
-
-// the f32 coefficients, or an error message
-static const char* reff_coeffs_f32(const dpenv_reference_filter* rf, float dt, float phi[3][9], float gam[3][3])
-{
-    if (const char* why = reff_check(rf)) return why;
-    if (!std::isfinite(dt) || !(dt > 0.0f)) return "reference filter: dt must be finite and > 0";
-    for (int j = 0; j < 3; ++j) {
-        double p[9], g[3];
-        reff_coeffs_f64((double)rf->omega[j], (double)rf->zeta[j], (double)dt, p, g);
-        for (int k = 0; k < 9; ++k) phi[j][k] = (float)p[k];
-        for (int k = 0; k < 3; ++k) gam[j][k] = (float)g[k];
-        for (int k = 0; k < 9; ++k) if (!std::isfinite(phi[j][k])) return "reference filter: omega * dt too large (the coefficients overflow f32)";
-        for (int k = 0; k < 3; ++k) if (!std::isfinite(gam[j][k])) return "reference filter: omega * dt too large (the coefficients overflow f32)";
-    }
-    return nullptr;
-}
-
-extern "C" int dpenv_reference_filter_coeffs(const dpenv_reference_filter* rf, float dt, float phi_out[3][9], float gam_out[3][3])
-{
-    if (!rf || !phi_out || !gam_out) return fail(nullptr, DPENV_EINVAL, "dpenv_reference_filter_coeffs: NULL argument");
-    float phi[3][9], gam[3][3];
-    if (const char* why = reff_coeffs_f32(rf, dt, phi, gam)) return fail(nullptr, DPENV_EINVAL, "%s", why);
-    std::memcpy(phi_out, phi, sizeof phi);
-    std::memcpy(gam_out, gam, sizeof gam);
-    return DPENV_OK;
-}
-
 extern "C" int dpenv_set_reference_filter(dpenv_handle h, const dpenv_reference_filter* rf, dpenv_stream s)
 {
     if (!h) return DPENV_EINVAL;
@@ -1292,18 +1024,12 @@ extern "C" int dpenv_set_reference_filter(dpenv_handle h, const dpenv_reference_
         return DPENV_OK;
     }
     if (!((h->mode == MODE_FINAL_CONT || h->mode == MODE_LIMITED || h->mode == MODE_FULL) && h->cfg.extended_state))
-        return fail(h, DPENV_EINVAL, "the reference filter runs with the final variant (continuous angles), limited or full, extended_state, and a "
-                                     "leaky-relu / relu network of hidden width <= 80");
+        return fail(h, DPENV_EINVAL, ONE_WAVE_SET_MSG, "the reference filter");
     FilterArgs& f = h->reff;
     float phi[3][9], gam[3][3];
     if (const char* why = reff_coeffs_f32(rf, h->cfg.substep_dt * (float)h->cfg.n_substeps, phi, gam)) return fail(h, DPENV_EINVAL, "%s", why);
     DeviceGuard dev_guard(h->device);
-    if (!f.state) {
-        void* p = nullptr;
-        if (hipMalloc(&p, sizeof(float4) * 3 * (size_t)h->cfg.n_envs) != hipSuccess)
-            return fail(h, DPENV_ENOMEM, "hipMalloc of the reference filter state failed");
-        f.state = (float4*)p;
-    }
+    if (int rc = ensure_env_state(h, &f.state, 3, "hipMalloc of the reference filter state failed")) return rc;
     std::memcpy(f.phi, phi, sizeof phi);
     std::memcpy(f.gam, gam, sizeof gam);
     f.out = nullptr;
@@ -1358,11 +1084,7 @@ extern "C" int dpenv_set_integral_action(dpenv_handle h, const dpenv_integral_ac
     while (D > 0 && (double)(D - 1) * dt > (double)ia->dwell_s) --D;
     while (!((double)D * dt > (double)ia->dwell_s)) ++D;
     DeviceGuard dev_guard(h->device);
-    if (!h->integ.state) {
-        void* p = nullptr;
-        if (hipMalloc(&p, sizeof(float4) * (size_t)h->cfg.n_envs) != hipSuccess) return fail(h, DPENV_ENOMEM, "hipMalloc of the integral state failed");
-        h->integ.state = (float4*)p;
-    }
+    if (int rc = ensure_env_state(h, &h->integ.state, 1, "hipMalloc of the integral state failed")) return rc;
     IntegArgs& g = h->integ;
     for (int j = 0; j < 3; ++j) { g.gain[j] = ia->gain[j]; g.bound[j] = ia->bound[j]; g.box[j] = ia->box[j]; }
     g.step_s = ia->step_s > 0.0f ? ia->step_s : h->cfg.substep_dt * (float)h->cfg.n_substeps;
@@ -1393,62 +1115,6 @@ extern "C" int dpenv_set_integral_state(dpenv_handle h, const float* I_in, const
     return DPENV_OK;
 }
 
-// ---- the baseline DP controller: PID + pseudo-inverse allocation in the closed loop (dpenv.h) ---------------------------------------
-extern "C" int dpenv_dp_allocation_matrix(const float lx[3], const float ly[3], const float weight[5], float G_out[5][3])
-{
-    if (!lx || !ly || !weight || !G_out) return fail(nullptr, DPENV_EINVAL, "dpenv_dp_allocation_matrix: NULL argument");
-    for (int k = 0; k < 3; ++k)
-        if (!std::isfinite(lx[k]) || !std::isfinite(ly[k])) return fail(nullptr, DPENV_EINVAL, "dpenv_dp_allocation_matrix: lever arms must be finite");
-    for (int k = 0; k < 5; ++k)
-        if (!std::isfinite(weight[k]) || !(weight[k] > 0.0f)) return fail(nullptr, DPENV_EINVAL, "dpenv_dp_allocation_matrix: weight[%d] must be finite and > 0", k);
-    // deploy.allocation_matrix is the same recipe in the same order: V = W^-1 T', M = T V, G = V adj(M) / det(M)
-    const double T[3][5] = {{0.0, 1.0, 0.0, 1.0, 0.0},
-                            {1.0, 0.0, 1.0, 0.0, 1.0},
-                            {(double)lx[0], -(double)ly[1], (double)lx[1], -(double)ly[2], (double)lx[2]}};
-    double V[5][3], M[3][3];
-    for (int m = 0; m < 5; ++m) for (int j = 0; j < 3; ++j) V[m][j] = T[j][m] / (double)weight[m];
-    for (int r = 0; r < 3; ++r) for (int c = 0; c < 3; ++c) {
-        double acc = 0.0;
-        for (int m = 0; m < 5; ++m) acc += T[r][m] * V[m][c];
-        M[r][c] = acc;
-    }
-    double adj[3][3];                                            // adj[r][c] = cofactor of M[c][r]
-    for (int r = 0; r < 3; ++r) for (int c = 0; c < 3; ++c) {
-        const int r1 = (c + 1) % 3, r2 = (c + 2) % 3, c1 = (r + 1) % 3, c2 = (r + 2) % 3;
-        adj[r][c] = M[r1][c1] * M[r2][c2] - M[r1][c2] * M[r2][c1];
-    }
-    const double det = (M[0][0] * adj[0][0] + M[0][1] * adj[1][0]) + M[0][2] * adj[2][0];
-    if (!std::isfinite(det) || det == 0.0) return fail(nullptr, DPENV_EINVAL, "dpenv_dp_allocation_matrix: T W^-1 T' is singular");
-    for (int m = 0; m < 5; ++m) for (int c = 0; c < 3; ++c) {
-        double acc = 0.0;
-        for (int j = 0; j < 3; ++j) acc += V[m][j] * adj[j][c];
-        G_out[m][c] = (float)(acc / det);
-    }
-    return DPENV_OK;
-}
-
-// the law's numbers into ControlArgs, or an error message
-static const char* control_check(const dpenv_dp_controller* c, ControlArgs& g)
-{
-    if (c->struct_size != sizeof(dpenv_dp_controller)) return "dpenv_dp_controller ABI mismatch";
-    for (int j = 0; j < 3; ++j) {
-        if (!std::isfinite(c->kp[j]) || !std::isfinite(c->kd[j]) || !std::isfinite(c->ki[j])) return "DP controller: kp, kd and ki must be finite";
-        if (std::isnan(c->z_bound[j]) || c->z_bound[j] < 0.0f) return "DP controller: z_bound must be >= 0";
-        if (std::isnan(c->tau_max[j]) || c->tau_max[j] < 0.0f) return "DP controller: tau_max must be >= 0";
-        if (!std::isfinite(c->kf[j]) || !(c->kf[j] > 0.0f)) return "DP controller: kf must be finite and > 0";
-    }
-    if (!std::isfinite(c->kr_bow) || !(c->kr_bow > 0.0f)) return "DP controller: kr_bow must be finite and > 0";
-    if (std::isnan(c->f_eps) || c->f_eps < 0.0f) return "DP controller: f_eps must be >= 0";
-    for (int m = 0; m < 5; ++m) for (int j = 0; j < 3; ++j) if (!std::isfinite(c->G[m][j])) return "DP controller: G must be finite";
-    for (int j = 0; j < 3; ++j) {
-        g.kp[j] = c->kp[j]; g.kd[j] = c->kd[j]; g.ki[j] = c->ki[j]; g.zb[j] = c->z_bound[j]; g.tmax[j] = c->tau_max[j]; g.kf[j] = c->kf[j];
-    }
-    std::memcpy(g.G, c->G, sizeof g.G);
-    g.kr_bow = c->kr_bow;
-    g.f_eps = c->f_eps;
-    return nullptr;
-}
-
 #define CONTROL_SET_MSG                                                                                                              \
     "the DP controller runs with the final variant (continuous angles), extended_state, AOS action and observation rows, one vessel " \
     "class (the shared hull, the thrust-loss preset or per-env hulls) and the integral action off"
@@ -1465,20 +1131,13 @@ extern "C" int dpenv_set_dp_controller(dpenv_handle h, const dpenv_dp_controller
         h->ctrl_on = false;
         return DPENV_OK;
     }
-    ControlArgs g;
-    std::memset(&g, 0, sizeof g);
+    ControlArgs g = {};
     if (const char* why = control_check(c, g)) return fail(h, DPENV_EINVAL, "%s", why);
     if (!control_config_ok(h)) return fail(h, DPENV_EINVAL, "dpenv_set_dp_controller: " CONTROL_SET_MSG);
     DeviceGuard dev_guard(h->device);
-    float4* z = h->ctrl.z;
-    if (!z) {
-        void* p = nullptr;
-        if (hipMalloc(&p, sizeof(float4) * (size_t)h->cfg.n_envs) != hipSuccess) return fail(h, DPENV_ENOMEM, "hipMalloc of the DP controller state failed");
-        z = (float4*)p;
-        h->ctrl.z = z;                                          // (kept by a later call even if the launch below fails)
-    }
-    HIP_TRY(h, dev::launch_control_state(z, nullptr, nullptr, h->cfg.n_envs, 2, (hipStream_t)s));
-    g.z = z;
+    if (int rc = ensure_env_state(h, &h->ctrl.z, 1, "hipMalloc of the DP controller state failed")) return rc;
+    HIP_TRY(h, dev::launch_control_state(h->ctrl.z, nullptr, nullptr, h->cfg.n_envs, 2, (hipStream_t)s));   // (the block stays if this fails)
+    g.z = h->ctrl.z;
     g.dt = h->cfg.substep_dt * (float)h->cfg.n_substeps;
     h->ctrl = g;
     h->ctrl_on = true;
@@ -1516,33 +1175,18 @@ extern "C" int dpenv_controller_rollout(dpenv_handle h, const dpenv_controller_r
         return fail(h, DPENV_EINVAL, "T > 0 and the obs, act, reward, done and last_obs blocks are required");
     if (io->ref_out && !h->reff_on)
         return fail(h, DPENV_EINVAL, "dpenv_controller_rollout: ref_out needs the reference filter on (dpenv_set_reference_filter)");
-    if (io->n_switch < 0 || io->n_switch > DPENV_MAX_SWITCH || (io->n_switch > 0 && !io->refs))
-        return fail(h, DPENV_EINVAL, "bad setpoint schedule");
-    for (int k = 0; k < io->n_switch; ++k)
-        if (io->switch_step[k] < 0 || io->switch_step[k] >= io->T || (k > 0 && io->switch_step[k] <= io->switch_step[k - 1]))
-            return fail(h, DPENV_EINVAL, "switch_step must be strictly increasing within [0, T)");
+    if (int rc = check_schedule(h, io)) return rc;
     StepArgs a = h->args;
     bind_optional(h, a, (hipStream_t)s);
     ControlArgs ca = h->ctrl;
     ca.T = io->T; ca.obs = io->obs; ca.act = io->act; ca.rew = io->reward; ca.done = io->done; ca.last_obs = io->last_obs;
-    ca.n_switch = io->n_switch; ca.refs = io->refs;
-    for (int k = 0; k < io->n_switch; ++k) ca.switch_step[k] = io->switch_step[k];
+    copy_schedule(io, ca);
     ca.use_lag = h->lag_valid ? 1 : 0;
     FilterArgs fa = h->reff;
     fa.out = io->ref_out;
     const hipError_t e = dev::launch_controller_rollout(&a, &ca, h->reff_on ? &fa : nullptr, rollout_ves(vessel_source(h)), (hipStream_t)s);
     if (e != hipSuccess) return fail(h, DPENV_EHIP, "controller launch failed: %s", hipGetErrorString(e));
     h->lag_valid = true;
-    return DPENV_OK;
-}
-
-extern "C" int dpenv_thrust_alloc(const dpenv_dp_controller* c, const float* tau, float* action_out, int32_t n, dpenv_stream s)
-{
-    if (!c || !tau || !action_out || n <= 0) return fail(nullptr, DPENV_EINVAL, "dpenv_thrust_alloc: bad argument");
-    ControlArgs g;
-    std::memset(&g, 0, sizeof g);
-    if (const char* why = control_check(c, g)) return fail(nullptr, DPENV_EINVAL, "%s", why);
-    HIP_TRY(nullptr, dev::launch_thrust_alloc(&g, tau, action_out, n, (hipStream_t)s));
     return DPENV_OK;
 }
 
@@ -1603,138 +1247,3 @@ extern "C" int dpenv_set_obs_thrust(dpenv_handle h, const float* in, dpenv_strea
     return DPENV_OK;
 }
 
-extern "C" int dpenv_thrust_map(const float* params, const float* n_pct, const float* alpha, float* tau_out, int32_t n,
-                                dpenv_stream s)
-{
-    if (!n_pct || !alpha || !tau_out || n <= 0) return fail(nullptr, DPENV_EINVAL, "dpenv_thrust_map: bad argument");
-    float defp[DPENV_NPARAM];
-    if (!params) { dpenv_default_vessel(defp); params = defp; }
-    VesselDev vd;
-    std::string why;
-    if (derive_vessel(params, &vd, &why, true) != DPENV_OK) return fail(nullptr, DPENV_EINVAL, "%s", why.c_str());
-    HIP_TRY(nullptr, dev::launch_thrust_map(&vd, n_pct, alpha, tau_out, n, (hipStream_t)s));
-    return DPENV_OK;
-}
-
-extern "C" int64_t dpenv_gae_workspace_bytes(int32_t n) { return n > 0 ? dev::gae_workspace_bytes(n) : 0; }
-
-extern "C" int dpenv_gae_stats(const float* rew, const float* val, const uint8_t* end, const float* boot, const float* last_val,
-                               int32_t T, int32_t n, float gamma, float lam, float* adv_out, float* ret_out, void* workspace,
-                               double* stats_out, dpenv_stream s)
-{
-    if (!rew || !val || !adv_out || !ret_out || T <= 0 || n <= 0)
-        return fail(nullptr, DPENV_EINVAL, "dpenv_gae: bad argument");
-    if (stats_out && !workspace) return fail(nullptr, DPENV_EINVAL, "dpenv_gae_stats: statistics need the workspace (dpenv_gae_workspace_bytes)");
-    HIP_TRY(nullptr, dev::launch_gae(rew, val, end, boot, last_val, T, n, gamma, lam, adv_out, ret_out, (double*)workspace,
-                                          stats_out, (hipStream_t)s));
-    return DPENV_OK;
-}
-
-extern "C" int dpenv_gae(const float* rew, const float* val, const uint8_t* end, const float* boot, const float* last_val,
-                         int32_t T, int32_t n, float gamma, float lam, float* adv_out, float* ret_out, dpenv_stream s)
-{
-    return dpenv_gae_stats(rew, val, end, boot, last_val, T, n, gamma, lam, adv_out, ret_out, nullptr, nullptr, s);
-}
-
-// ---- streaming score card (dpenv.h: dpenv_score_*): handle-free; every argument is validated here, before any device call ----
-extern "C" int64_t dpenv_score_state_bytes(int32_t n) { return n > 0 ? dev::score_state_bytes(n) : 0; }
-
-extern "C" int64_t dpenv_score_summary_workspace_bytes(int32_t n) { return n > 0 ? dev::score_summary_workspace_bytes(n) : 0; }
-
-extern "C" int dpenv_score_default_io(dpenv_score_io* io)
-{
-    if (!io) return fail(nullptr, DPENV_EINVAL, "dpenv_score_default_io: io is NULL");
-    std::memset(io, 0, sizeof *io);
-    io->struct_size = (uint32_t)sizeof *io;
-    io->obs_dtype = DPENV_F32;
-    io->obs_stride = 9;
-    io->act_stride = 7;
-    io->dt = 0.2f;
-    const double kq0[3] = {0.02, 0.036, 0.036}, diam[3] = {0.06, 0.15, 0.15};
-    const float norm[3] = {5.0f, 5.0f, 25.0f}, rps[3] = {33.0f, 11.0f, 11.0f};
-    for (int j = 0; j < 3; ++j) {
-        io->norm[j] = norm[j];
-        io->rps_max[j] = rps[j];
-        const double d = diam[j];
-        io->power_coeff[j] = (float)(kq0[j] * 2 * 3.141592653589793 * 1025.0 * (d * d * d * d * d));
-    }
-    return DPENV_OK;
-}
-
-extern "C" int dpenv_score_accumulate(void* state, const dpenv_score_io* io, dpenv_stream s)
-{
-    if (!io) return fail(nullptr, DPENV_EINVAL, "dpenv_score_accumulate: io is NULL");
-    if (io->struct_size != sizeof(dpenv_score_io))
-        return fail(nullptr, DPENV_EINVAL, "dpenv_score_accumulate: struct_size %u != %zu", io->struct_size, sizeof(dpenv_score_io));
-    if (io->T < 1) return fail(nullptr, DPENV_EINVAL, "dpenv_score_accumulate: T = %d, must be >= 1", io->T);
-    if (io->n < 1) return fail(nullptr, DPENV_EINVAL, "dpenv_score_accumulate: n = %d, must be >= 1", io->n);
-    if (!state) return fail(nullptr, DPENV_EINVAL, "dpenv_score_accumulate: state is NULL");
-    if (reinterpret_cast<uintptr_t>(state) & 15u) return fail(nullptr, DPENV_EINVAL, "dpenv_score_accumulate: state must be 16-byte aligned");
-    if (io->obs_dtype != DPENV_F32 && io->obs_dtype != DPENV_BF16)
-        return fail(nullptr, DPENV_EINVAL, "dpenv_score_accumulate: obs_dtype %d is neither DPENV_F32 nor DPENV_BF16", io->obs_dtype);
-    if (io->obs && io->obs_stride < 3) return fail(nullptr, DPENV_EINVAL, "dpenv_score_accumulate: obs_stride = %d, must be >= 3", io->obs_stride);
-    if (io->act && io->act_stride < 3) return fail(nullptr, DPENV_EINVAL, "dpenv_score_accumulate: act_stride = %d, must be >= 3", io->act_stride);
-    if (io->integ && !io->obs) return fail(nullptr, DPENV_EINVAL, "dpenv_score_accumulate: integ needs obs");
-    if (!std::isfinite(io->dt) || !(io->dt > 0.0f)) return fail(nullptr, DPENV_EINVAL, "dpenv_score_accumulate: dt must be finite and > 0");
-    for (int j = 0; j < 3; ++j) {
-        if (!std::isfinite(io->norm[j]) || !(io->norm[j] > 0.0f))
-            return fail(nullptr, DPENV_EINVAL, "dpenv_score_accumulate: norm[%d] must be finite and > 0", j);
-        if (!std::isfinite(io->power_coeff[j])) return fail(nullptr, DPENV_EINVAL, "dpenv_score_accumulate: power_coeff[%d] is not finite", j);
-        if (!std::isfinite(io->rps_max[j])) return fail(nullptr, DPENV_EINVAL, "dpenv_score_accumulate: rps_max[%d] is not finite", j);
-    }
-    ScoreArgs a;
-    a.state = (uint4*)state;
-    a.obs = io->obs; a.act = io->act; a.rew = io->rew; a.done = io->done; a.integ = io->integ;
-    a.T = io->T; a.n = io->n; a.obs_stride = io->obs_stride; a.act_stride = io->act_stride; a.cut_at_end = io->cut_at_end ? 1 : 0;
-    a.dt = io->dt;
-    for (int j = 0; j < 3; ++j) { a.norm[j] = io->norm[j]; a.coeff[j] = io->power_coeff[j]; a.rps[j] = io->rps_max[j]; }
-    HIP_TRY(nullptr, dev::launch_score(&a, io->obs_dtype == DPENV_BF16, (hipStream_t)s));
-    return DPENV_OK;
-}
-
-extern "C" int dpenv_score_read(const void* state, int32_t n, double* out, dpenv_stream s)
-{
-    if (n < 1) return fail(nullptr, DPENV_EINVAL, "dpenv_score_read: n = %d, must be >= 1", n);
-    if (!state || (reinterpret_cast<uintptr_t>(state) & 15u)) return fail(nullptr, DPENV_EINVAL, "dpenv_score_read: state is NULL or not 16-byte aligned");
-    if (!out) return fail(nullptr, DPENV_EINVAL, "dpenv_score_read: out is NULL");
-    HIP_TRY(nullptr, dev::launch_score_read(state, n, out, (hipStream_t)s));
-    return DPENV_OK;
-}
-
-extern "C" int dpenv_score_summary(const void* state, int32_t n, double* out, void* workspace, dpenv_stream s)
-{
-    if (n < 1) return fail(nullptr, DPENV_EINVAL, "dpenv_score_summary: n = %d, must be >= 1", n);
-    if (!state || (reinterpret_cast<uintptr_t>(state) & 15u)) return fail(nullptr, DPENV_EINVAL, "dpenv_score_summary: state is NULL or not 16-byte aligned");
-    if (!out) return fail(nullptr, DPENV_EINVAL, "dpenv_score_summary: out is NULL");
-    if (!workspace) return fail(nullptr, DPENV_EINVAL, "dpenv_score_summary: workspace is NULL (dpenv_score_summary_workspace_bytes)");
-    HIP_TRY(nullptr, dev::launch_score_summary(state, n, out, (double*)workspace, (hipStream_t)s));
-    return DPENV_OK;
-}
-
-extern "C" int dpenv_adv_sum(const float* adv, int64_t count, float* sum_out, dpenv_stream s)
-{
-    if (!adv || !sum_out || count <= 0) return fail(nullptr, DPENV_EINVAL, "dpenv_adv_sum: bad argument");
-    HIP_TRY(nullptr, dev::launch_sum(adv, count, nullptr, sum_out, (hipStream_t)s));
-    return DPENV_OK;
-}
-
-extern "C" int dpenv_adv_sumsq(const float* adv, int64_t count, const float* mean, float* sumsq_out, dpenv_stream s)
-{
-    if (!adv || !mean || !sumsq_out || count <= 0) return fail(nullptr, DPENV_EINVAL, "dpenv_adv_sumsq: bad argument");
-    HIP_TRY(nullptr, dev::launch_sum(adv, count, mean, sumsq_out, (hipStream_t)s));
-    return DPENV_OK;
-}
-
-extern "C" int dpenv_adv_apply(float* adv, int64_t count, const float* mean, const float* std, dpenv_stream s)
-{
-    if (!adv || !mean || !std || count <= 0) return fail(nullptr, DPENV_EINVAL, "dpenv_adv_apply: bad argument");
-    HIP_TRY(nullptr, dev::launch_adv_apply(adv, count, mean, std, nullptr, 0.0, (hipStream_t)s));
-    return DPENV_OK;
-}
-
-extern "C" int dpenv_adv_apply_stats(float* adv, int64_t count, const double* stats, double total_count, dpenv_stream s)
-{
-    if (!adv || !stats || count <= 0 || !(total_count >= 1.0)) return fail(nullptr, DPENV_EINVAL, "dpenv_adv_apply_stats: bad argument");
-    HIP_TRY(nullptr, dev::launch_adv_apply(adv, count, nullptr, nullptr, stats, total_count, (hipStream_t)s));
-    return DPENV_OK;
-}

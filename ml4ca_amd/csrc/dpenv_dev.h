@@ -1,4 +1,4 @@
-// dpenv_dev.h - internal contract between the host API (dpenv_api.hip) and the kernels
+// dpenv_dev.h - internal contract between the host API (dpenv_api.hip, dpenv_api_free.hip) and the kernels
 // (dpenv_kernels.hip) of libdpenv.so.  Not part of the public ABI (that is include/dpenv.h).
 #ifndef DPENV_DEV_H
 #define DPENV_DEV_H
@@ -383,7 +383,7 @@ struct ScoreArgs {
     float norm[3], coeff[3], rps[3];
 };
 
-// ---- launchers: called by dpenv_api.hip, defined by the translation unit that owns the kernels; not exported from libdpenv.so ----
+// ---- launchers: called by the host units (dpenv_api.hip, dpenv_api_free.hip), defined by the translation unit that owns the kernels; not exported from libdpenv.so ----
 namespace __attribute__((visibility("hidden"))) dev {
 // dpenv_kernels.hip.  ves: VES_* (where the vessel of a lane comes from)
 hipError_t launch_step(const StepArgs* a, int mode, int ext, int ves, int reset_wave, hipStream_t s);

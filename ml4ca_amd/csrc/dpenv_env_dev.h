@@ -220,7 +220,7 @@ __device__ __forceinline__ Vessel vessel_from_env_lds(const float4* lds, int lan
 }
 
 // raw public parameters (DPENV_P_* order, include/dpenv.h) -> one per-env block: the SAME float operations in the same order as the
-// host's derive_vessel (dpenv_api.hip), so that an env given its class's parameters integrates with the
+// host's derive_vessel (dpenv_api_free.hip), so that an env given its class's parameters integrates with the
 // class path's constants bit for bit.  fp32 division is IEEE-correct here (no -ffast-math; hipcc's default correctly rounded divide).
 // A block that is not a vessel (mass matrix not positive definite, non-finite entries) becomes NaN: the env then reports
 // DPENV_DONE_FAULT at its first step instead of integrating garbage.

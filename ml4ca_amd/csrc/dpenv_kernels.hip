@@ -1268,7 +1268,7 @@ __device__ double g_sum_partials[2 * SUM_MAXGRID];
 }  // namespace dpenv
 
 // =============================================================================================
-//  launchers (called from dpenv_api.hip through dpenv_dev.h)
+//  launchers (called from dpenv_api.hip and dpenv_api_free.hip through dpenv_dev.h)
 // =============================================================================================
 using namespace dpenv;
 

@@ -99,6 +99,41 @@ def evaluate_actor(ac, dev, preset, precision, seed, out=print, eval_envs=1024):
     return res
 
 
+def tune_baseline(ac, dev, preset, precision, K, seed=0, out=print, directions=16, vc=0.2):
+    """The baseline's trade-off curve beside the actor (evaluate.baseline_gain_sweep): K gain sets around the pole-placement defaults
+    (deploy.gain_population; set 0 is the default baseline) x 16 current directions in ONE scored box test behind the reference filter,
+    every env on its own row of the per-env controller table, and the actor (no integral action) flown in the same currents."""
+    from ml4ca_amd import evaluate as EV
+    from ml4ca_amd.deploy import dp_controller_defaults, gain_population
+    nominal = ml4ca_amd.default_vessel(preset)
+    n = K * directions
+    env = ml4ca_amd.BatchedRevoltEnv(n, device=dev, terminate=False, time_limit=False, seed=seed + 77, vessel_params=nominal, current=True)
+    pop = gain_population(K, dp_controller_defaults(nominal), seed=seed)
+    env.set_dp_controller(dp_controller_defaults(nominal))
+    sw = EV.baseline_gain_sweep(env, pop, directions=directions, vc=vc, reference_filter=True)
+    iae, work = sw['mean_iae'].cpu().numpy(), sw['mean_work'].cpu().numpy()
+    tot = work.sum(1)
+    ac.upload(env, precision=precision)
+    sa = EV.deployment_box_test_streamed(env, chunk=50, integral=False, reference_filter=True)       # (the sweep left the currents set)
+    a_iae, a_work = float(sa['iae'].mean()), sa['work'].mean(0).cpu().numpy()
+    row = lambda k: 'set %4d  IAE %.2f  work bow/port/star %s (total %.1f)  kp x %s  kd x %s  ki x %s' % (
+        k, iae[k], [round(float(x), 1) for x in work[k]], tot[k], *([round(float(x), 2) for x in pop['factors'][g][k]] for g in ('kp', 'kd', 'ki')))
+    out('tune  %d gain sets x %d directions of %.1f m/s, 1250-step box test behind the reference filter' % (K, directions, vc))
+    out('tune  actor (no integral action): IAE %.2f  work bow/port/star %s (total %.1f)' % (a_iae, [round(float(x), 1) for x in a_work], a_work.sum()))
+    out('tune  default baseline : ' + row(0))
+    out('tune  front (%d of %d sets, by IAE):' % (len(sw['front']), K))
+    for k in sw['front']:
+        out('tune      ' + row(int(k)))
+    best = int(iae.argmin())
+    out('tune  lowest IAE       : ' + row(best))
+    fair = [int(k) for k in range(K) if tot[k] <= a_work.sum()]
+    if fair:
+        out('tune  lowest IAE at no more than the actor\'s work: ' + row(min(fair, key=lambda k: iae[k])))
+    else:
+        out('tune  no gain set spends as little work as the actor (the least: ' + row(int(tot.argmin())) + ')')
+    return {'mean_iae': iae.tolist(), 'mean_work': work.tolist(), 'front': [int(k) for k in sw['front']], 'actor': {'IAE': a_iae, 'work': a_work.tolist()}}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--envs', type=int, default=4096)
@@ -128,6 +163,8 @@ def main():
                     help="nominal hull (dpenv_default_vessel_ex); default (round 6): the thrust-loss preset - the steady speeds 'with thrust losses' are the velocity "
                          'bounds the reference trains with (customEnv.py:17,26), and the shared training form runs it at the cost of the default hull')
     ap.add_argument('--eval', action='store_true', help='after training: run_RL_policy + the box test (IAE, energy) on the nominal hull and on spreads of hulls')
+    ap.add_argument('--tune-baseline', type=int, default=0, metavar='K', help='with --eval: a scored sweep of K baseline gain sets x 16 current directions in one '
+                    'flight (per-env controller table): the default baseline, the IAE / work front, the best set, and the best at no more than the actor\'s work')
     ap.add_argument('--eval-envs', type=int, default=1024, help='envs per --eval box test; 1024 (the default) scores the resident rows as before, any other '
                                                                 'value flies the test in 50-step launches scored on the device (evaluate.ScoreCard), e.g. 65536')
     ap.add_argument('--eval-presets', default='', help="comma-separated presets to run --eval on (default: the training preset), e.g. 'no_loss,thrust_loss': "
@@ -258,6 +295,8 @@ def main():
             for pz in (args.eval_presets.split(',') if args.eval_presets else [args.preset]):
                 print('eval on the %s preset (trained on %s%s)' % (pz, args.preset, ', hulls re-drawn +-%g %%' % (100 * args.randomise) if args.randomise > 0 else ''))
                 evaluate_actor(ac, dev, pz, 'f32', args.seed, eval_envs=args.eval_envs)
+                if args.tune_baseline > 0:
+                    tune_baseline(ac, dev, pz, 'f32', args.tune_baseline, seed=args.seed)
     if world > 1:
         torch.distributed.destroy_process_group()
 

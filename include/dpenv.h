@@ -630,7 +630,7 @@ int dpenv_score_summary(const void* state, int32_t n, double* out, void* workspa
  * thrust >= 0; a saturated command is not redistributed.  G is the weighted pseudo-inverse W^-1 T' (T W^-1 T')^-1 of the extended-thrust
  * matrix T = [[0, 1, 0, 1, 0], [1, 0, 1, 0, 1], [lx_bow, -ly_port, lx_port, -ly_star, lx_star]], W = diag(weight), computed in f64 and
  * rounded once to f32 (dpenv_dp_allocation_matrix) - from the controller's NOMINAL lever arms: a randomised hull is flown by a controller
- * that does not know it.  z is zeroed by every reset: dpenv_reset (for the envs it re-draws), auto-reset (an env that ends an episode has
+ * that does not know it (dpenv_set_dp_controller_table below gives every env its own numbers, lever arms included).  z is zeroed by every reset: dpenv_reset (for the envs it re-draws), auto-reset (an env that ends an episode has
  * z = 0 before its new episode's first action) and turning the controller on (every env).  A launch's first input is rebuilt from the stored
  * state, its thrust columns continued as dpenv_policy_rollout's, and z is updated at every action: two launches of T/2 write the rows of
  * one launch of T.
@@ -658,6 +658,42 @@ int dpenv_set_dp_controller(dpenv_handle h, const dpenv_dp_controller* c, dpenv_
 /* The checkpoint path of z, next to dpenv_get_state: device float[3][n_envs].  DPENV_EINVAL while the controller is off. */
 int dpenv_get_dp_controller_state(dpenv_handle h, float* z_out, dpenv_stream s);
 int dpenv_set_dp_controller_state(dpenv_handle h, const float* z_in, dpenv_stream s);
+
+/* Per-env numbers for the law (additive to ABI 6): one controller per env, for a gain sweep in one launch or a baseline that knows each
+ * env's hull.  The public table is a DEVICE float[DPENV_CTRL_NPARAM][n_envs], laid out like the vessel table (row p = slot p of every env);
+ * the caller owns it.  Slots: */
+#define DPENV_CTRL_NPARAM 32
+#define DPENV_CTRL_KP 0       /* 0-2  kp, finite */
+#define DPENV_CTRL_KD 3       /* 3-5  kd, finite */
+#define DPENV_CTRL_KI 6       /* 6-8  ki, finite */
+#define DPENV_CTRL_ZB 9       /* 9-11 z_bound, >= 0 */
+#define DPENV_CTRL_TMAX 12    /* 12-14 tau_max, >= 0 */
+#define DPENV_CTRL_WEIGHT 15  /* 15-19 the five allocation weights (columns of T), finite and > 0 */
+#define DPENV_CTRL_LX 20      /* 20-22 lever arms lx: bow, port, star, finite */
+#define DPENV_CTRL_LY 23      /* 23-25 lever arms ly: bow (not used by T), port, star, finite */
+#define DPENV_CTRL_KF 26      /* 26-28 thrust constants ahead: bow, port, star, finite and > 0 */
+#define DPENV_CTRL_KR_BOW 29  /* bow astern, finite and > 0 */
+#define DPENV_CTRL_F_EPS 30   /* direction threshold, >= 0 */
+                              /* 31 reserved, 0 */
+/* The call needs the controller on (dpenv_set_dp_controller first: it supplies dt, the z block and the supported-set check), else
+ * DPENV_EINVAL.  A packing kernel, one lane per env, computes every env's G from its lever arms and weights with the recipe and the
+ * operation order of dpenv_dp_allocation_matrix (V = W^-1 T', M = T V with the sums started at 0.0 in index order, the adjugate,
+ * det = (M00 adj00 + M01 adj10) + M02 adj20, G = V adj / det), in f64, rounded once to f32, and writes the env's 36 numbers into a
+ * library-owned block (allocated by the first call, released with the handle): every later call is stream-ordered without allocation and
+ * graph-capturable, and a captured launch flies whatever the last packing wrote.
+ * Refused rows: a row is refused if it breaks any condition dpenv_set_dp_controller refuses (non-finite gains, NaN or negative bounds and
+ * f_eps, kf <= 0, kr_bow <= 0), has a weight <= 0 or non-finite, a non-finite lever arm, a det that is non-finite or zero, or a non-finite
+ * G.  A refused row is packed as the ZERO CONTROLLER - gains, bounds and G all 0, kf = kr_bow = 1, f_eps = 0 - with which the law commands
+ * the action [0, 0, 0, 0, 1, 0, 1] at every step; the other rows are not affected.  refused_out: NULL, or a device uint8[n_envs] that
+ * gets 1 for a refused env and 0 for the others.  The library reads nothing back, does not synchronise and uses no atomics: the caller
+ * decides whether to look.
+ * While a table is in force dpenv_controller_rollout flies row i on env i: the law above, read with per-env operands (dt stays the
+ * handle's).  Rows, resets, the reference filter, currents and hull sources are what they are without it.  The call leaves z alone: gains can
+ * change between the launches of one flight, and a checkpoint restores as table + dpenv_set_dp_controller_state.  table = NULL returns to
+ * the numbers of dpenv_set_dp_controller; dpenv_set_dp_controller(h, c) with c != NULL installs that scalar law again and drops the
+ * table, NULL turns everything off.  dpenv_thrust_alloc takes no table. */
+int dpenv_set_dp_controller_table(dpenv_handle h, const float* table, uint8_t* refused_out, dpenv_stream s);
+
 typedef struct dpenv_controller_rollout_io {
     uint32_t struct_size;    /* sizeof(dpenv_controller_rollout_io), ABI check */
     int32_t T;

@@ -174,6 +174,7 @@ SYMBOLS = {
     'dpenv_set_dp_controller': (C.c_int, [_VP, C.POINTER(DPController), _VP]),
     'dpenv_get_dp_controller_state': (C.c_int, [_VP, _VP, _VP]),
     'dpenv_set_dp_controller_state': (C.c_int, [_VP, _VP, _VP]),
+    'dpenv_set_dp_controller_table': (C.c_int, [_VP, _VP, _VP, _VP]),
     'dpenv_controller_rollout': (C.c_int, [_VP, C.POINTER(ControllerRolloutIO), _VP]),
     'dpenv_thrust_alloc': (C.c_int, [C.POINTER(DPController), _VP, _VP, _I32, _VP]),
 }

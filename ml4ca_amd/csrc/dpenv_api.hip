@@ -79,6 +79,8 @@ struct dpenv_s {
     FilterArgs reff = {};   // its f32 coefficients and per-env state (float4 [3][n]: pos | vel | acc | target), allocated on first use
     bool ctrl_on = false;   // dpenv_set_dp_controller: dpenv_controller_rollout flies the baseline law with `ctrl`
     ControlArgs ctrl = {};  // its numbers and per-env state (float4 [n]: z | pad), allocated by the first dpenv_set_dp_controller
+    bool ctrl_tab_on = false;    // dpenv_set_dp_controller_table: env i flies row i of ctrl_tab instead of ctrl's numbers
+    float4* ctrl_tab = nullptr;  // the packed per-env controller block (ctrl_tab_float4s(n) float4), allocated by the first dpenv_set_dp_controller_table
     int device = 0;
     std::string err;
 
@@ -93,6 +95,7 @@ struct dpenv_s {
         if (integ.state) (void)hipFree(integ.state);
         if (reff.state) (void)hipFree(reff.state);
         if (ctrl.z) (void)hipFree(ctrl.z);
+        if (ctrl_tab) (void)hipFree(ctrl_tab);
         for (int k = 0; k < 2; ++k) if (pol_read[k]) (void)hipEventDestroy(pol_read[k]);
         if (loss_ev) (void)hipEventDestroy(loss_ev);
         if (loss_host) (void)hipHostFree(loss_host);
@@ -1129,6 +1132,7 @@ extern "C" int dpenv_set_dp_controller(dpenv_handle h, const dpenv_dp_controller
     if (!h) return DPENV_EINVAL;
     if (!c) {
         h->ctrl_on = false;
+        h->ctrl_tab_on = false;
         return DPENV_OK;
     }
     ControlArgs g = {};
@@ -1141,6 +1145,32 @@ extern "C" int dpenv_set_dp_controller(dpenv_handle h, const dpenv_dp_controller
     g.dt = h->cfg.substep_dt * (float)h->cfg.n_substeps;
     h->ctrl = g;
     h->ctrl_on = true;
+    h->ctrl_tab_on = false;                                // the scalar law again: a table in force is dropped
+    return DPENV_OK;
+}
+
+static_assert(CTRL_NPARAM == DPENV_CTRL_NPARAM && CTRL_KP == DPENV_CTRL_KP && CTRL_KD == DPENV_CTRL_KD && CTRL_KI == DPENV_CTRL_KI &&
+                  CTRL_ZB == DPENV_CTRL_ZB && CTRL_TMAX == DPENV_CTRL_TMAX && CTRL_WEIGHT == DPENV_CTRL_WEIGHT && CTRL_LX == DPENV_CTRL_LX &&
+                  CTRL_LY == DPENV_CTRL_LY && CTRL_KF == DPENV_CTRL_KF && CTRL_KR_BOW == DPENV_CTRL_KR_BOW && CTRL_F_EPS == DPENV_CTRL_F_EPS,
+              "the packing kernel's slots are the header's");
+
+extern "C" int dpenv_set_dp_controller_table(dpenv_handle h, const float* table, uint8_t* refused_out, dpenv_stream s)
+{
+    if (!h) return DPENV_EINVAL;
+    if (!h->ctrl_on) return fail(h, DPENV_EINVAL, "dpenv_set_dp_controller_table: the DP controller is off (dpenv_set_dp_controller first)");
+    if (!table) {
+        h->ctrl_tab_on = false;
+        return DPENV_OK;
+    }
+    DeviceGuard dev_guard(h->device);
+    if (!h->ctrl_tab) {                                    // (whole waves of 64 envs: not ensure_env_state's count x n_envs)
+        void* p = nullptr;
+        if (hipMalloc(&p, sizeof(float4) * (size_t)ctrl_tab_float4s(h->cfg.n_envs)) != hipSuccess)
+            return fail(h, DPENV_ENOMEM, "hipMalloc of the DP controller table failed");
+        h->ctrl_tab = (float4*)p;
+    }
+    HIP_TRY(h, dev::launch_pack_controllers(table, h->ctrl_tab, refused_out, h->cfg.n_envs, (hipStream_t)s));
+    h->ctrl_tab_on = true;
     return DPENV_OK;
 }
 
@@ -1184,7 +1214,7 @@ extern "C" int dpenv_controller_rollout(dpenv_handle h, const dpenv_controller_r
     ca.use_lag = h->lag_valid ? 1 : 0;
     FilterArgs fa = h->reff;
     fa.out = io->ref_out;
-    const hipError_t e = dev::launch_controller_rollout(&a, &ca, h->reff_on ? &fa : nullptr, rollout_ves(vessel_source(h)), (hipStream_t)s);
+    const hipError_t e = dev::launch_controller_rollout(&a, &ca, h->reff_on ? &fa : nullptr, h->ctrl_tab_on ? h->ctrl_tab : nullptr, rollout_ves(vessel_source(h)), (hipStream_t)s);
     if (e != hipSuccess) return fail(h, DPENV_EHIP, "controller launch failed: %s", hipGetErrorString(e));
     h->lag_valid = true;
     return DPENV_OK;

@@ -9,8 +9,48 @@
 #ifndef DPENV_CONTROL_DEV_H
 #define DPENV_CONTROL_DEV_H
 
+// The law's numbers of ONE env, in registers: what controller_rollout_tab_kernel flies instead of ControlArgs' shared set while a
+// per-env table is in force (dpenv_set_dp_controller_table).  Same member names, so dp_control / dp_allocate read either.
+struct ControlLane {
+    float kp[3], kd[3], ki[3], zb[3], tmax[3];
+    float G[5][3];
+    float kf[3], kr_bow;
+    float f_eps;
+    float dt;                                                    // the handle's (wave-uniform)
+};
+
+// The packed per-env block pack_controllers_kernel writes: per wave of 64 envs CTRL_TAB_STREAMS float4 streams of 64 lanes, stream k of
+// env i at ctrl_tab_index(i, k) - a wave's load is 1 KiB contiguous, and the nine addresses of a lane differ by constants (with
+// [k][n] streams the nine wave-uniform bases cost the randomised-hull form with the filter 36 B of scratch).  ctrl_tab_float4s(n) is
+// the block's size.  Flat slot q = 4 k + component:
+// kp 0-2 | kd 3-5 | ki 6-8 | zb 9-11 | tmax 12-14 | G row-major 15-29 | kf 30-32 | kr_bow 33 | f_eps 34 | 35 pad
+__host__ __device__ __forceinline__ int64_t ctrl_tab_index(int i, int k) { return ((int64_t)(i >> 6) * CTRL_TAB_STREAMS + k) * 64 + (i & 63); }
+
+__device__ __forceinline__ void load_control_lane(const float4* __restrict__ tab, int il, float dt, ControlLane& c)
+{
+    float q[4 * CTRL_TAB_STREAMS];
+#pragma unroll
+    for (int k = 0; k < CTRL_TAB_STREAMS; ++k) {
+        const float4 v = tab[ctrl_tab_index(il, k)];
+        q[4 * k] = v.x; q[4 * k + 1] = v.y; q[4 * k + 2] = v.z; q[4 * k + 3] = v.w;
+    }
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+        c.kp[j] = q[j]; c.kd[j] = q[3 + j]; c.ki[j] = q[6 + j]; c.zb[j] = q[9 + j]; c.tmax[j] = q[12 + j]; c.kf[j] = q[30 + j];
+    }
+#pragma unroll
+    for (int m = 0; m < 5; ++m)
+#pragma unroll
+        for (int j = 0; j < 3; ++j) c.G[m][j] = q[15 + 3 * m + j];
+    c.kr_bow = q[33];
+    c.f_eps = q[34];
+    c.dt = dt;
+}
+
 // tau[3] -> the final variant's continuous-angle action [n_bow, n_port, n_star, sin_port, cos_port, sin_star, cos_star] / 100 %
-__device__ __forceinline__ void dp_allocate(const ControlArgs& c, const float tau[3], float act[7])
+// (C: ControlArgs, the shared numbers as kernel arguments, or ControlLane)
+template <class C>
+__device__ __forceinline__ void dp_allocate(const C& c, const float tau[3], float act[7])
 {
     float f[5];                                                  // Fy_bow, Fx_port, Fy_port, Fx_star, Fy_star
 #pragma unroll
@@ -31,7 +71,8 @@ __device__ __forceinline__ void dp_allocate(const ControlArgs& c, const float ta
 }
 
 // one control step of the law on the observation o (e = o[0:3], nu = o[3:6]): the integral first, then the wrench, then the allocation
-__device__ __forceinline__ void dp_control(const ControlArgs& c, const float o[9], float z[3], float act[7])
+template <class C>
+__device__ __forceinline__ void dp_control(const C& c, const float o[9], float z[3], float act[7])
 {
     float tau[3];
 #pragma unroll
@@ -79,120 +120,105 @@ __device__ __forceinline__ void control_store_rows(float* lds, void* dst, int64_
 template <int VES, bool REFF>
 __global__ __launch_bounds__(RBLOCK) void controller_rollout_kernel(const StepArgs a, const ControlArgs ca, const FilterArgs fa)
 {
-    constexpr int MODE = MODE_FINAL_CONT;
-    constexpr bool EXT = true;
-    constexpr int A = 7, OD = 9;
-    constexpr bool RND = VES == VES_ENV_RND, PER_ENV = VES == VES_ENV_VGPR || RND;
-    constexpr int IL = VES == VES_ARGS_LOSS ? IL_SHARED : IL_NONE;
-    constexpr bool CURR = RND || VES == VES_ARGS_LOSS;
-    __shared__ float lds_row[RBLOCK * 9];
+    constexpr bool TAB = false;
+    const float4* const tab = nullptr;
+#include "dpenv_control_rollout_body.inc"
+}
 
-    const int tid = threadIdx.x;
-    const int n = a.n;
-    const int wave0 = blockIdx.x * RBLOCK;
-    const int i = wave0 + tid;
-    const bool live = i < n;
-    const int il = live ? i : n - 1;
+// TAB: every env flies its own row of the packed controller block (dpenv_set_dp_controller_table) - nine 16-byte loads per env and launch
+// behind the state loads, the numbers held in VGPRs for the launch, read only.  The law, the rows and everything else are the kernel above.
+template <int VES, bool REFF>
+__global__ __launch_bounds__(RBLOCK) void controller_rollout_tab_kernel(const StepArgs a, const ControlArgs ca, const FilterArgs fa,
+                                                                         const float4* __restrict__ tab)
+{
+    constexpr bool TAB = true;
+#include "dpenv_control_rollout_body.inc"
+}
 
-    Env s;
-    load_env(a, il, s);
-    sincos_lean(s.psi, s.sn, s.cs);
-    Current cur = {0.0f, 0.0f, 0.0f, 0.0f, 0u};
-    float vc0 = 0.0f, beta0 = 0.0f;
-    if (a.cur_vc) {
-        cur.vc = a.cur_vc[il]; cur.beta = a.cur_beta[il];
-        if (a.current_drift) { vc0 = a.cur_vc0[il]; beta0 = a.cur_beta0[il]; cur.ctr = a.drift_ctr[il]; }
-        current_components(cur);
-    }
-    Vessel ve = PER_ENV ? vessel_from_env(a.env_tab, a.env_stride, il) : vessel_from_args(a.v0);
-    if (!PER_ENV) pin_vessel_in_vgprs(ve);
-    uint32_t episode = a.auto_reset ? (uint32_t)a.episode[il] : 0u;
-    bool ep_dirty = false, rf_dirty = false, cur_dirty = false;
-
-    const int64_t stride_a = (int64_t)n * A, stride_o = (int64_t)n * OD;
-    const int64_t w_a = (int64_t)wave0 * A, w_o = (int64_t)wave0 * OD;       // the wave's slice of a [T][n][.] block
-    const int64_t rem_a = stride_a - w_a, rem_o = stride_o - w_o;
-
-    // observation of the current state = controller input of step 0 (ENV:196-205)
-    float o[9];
-    {
-        float sr_, cr_;
-        bool same_;
-        make_obs(s.N, s.E, s.psi, s.u, s.v, s.r, s.refN, s.refE, s.refPsi, s.pt, a.wrap_mode == WRAP_REFERENCE, o, sr_, cr_, same_);
-    }
-    if (ca.use_lag) {                                            // continue the episode with the observation the last launch ended with
-        const float4 lg = a.S3[il];
-        o[6] = lg.x; o[7] = lg.y; o[8] = lg.z;
-    }
-    float z[3];
-    {
-        const float4 q = ca.z[il];
-        z[0] = q.x; z[1] = q.y; z[2] = q.z;
-    }
-    ReffState fs{};
-    if constexpr (REFF) {
-        fs = reff_load(fa, il, n);
-        reff_row(fa, 0, n, i, live, s.refN, s.refE, s.refPsi);  // the reference o_0 was formed against
-        s.refN = fs.x[0][0]; s.refE = fs.x[1][0]; s.refPsi = fs.x[2][0];   // the last launch's pending new_ref is in force from step 0
-    }
-
-    int next_switch = 0;
-    for (int t = 0; t < ca.T; ++t) {
-        control_store_rows<OD>(lds_row, ca.obs, (int64_t)t * stride_o + w_o, rem_o, o, tid, a.obs_bf16 != 0);
-        float act[A];
-        dp_control(ca, o, z, act);
-        control_store_rows<A>(lds_row, ca.act, (int64_t)t * stride_a + w_a, rem_a, act, tid, false);
-
-        bool has_ref = false;
-        float nrN = 0.0f, nrE = 0.0f, nrP = 0.0f;
-        if (next_switch < ca.n_switch && ca.switch_step[next_switch] == t) {   // wave-uniform
-            const float* rp = ca.refs + (int64_t)next_switch * 3 * n;
-            nrN = rp[il]; nrE = rp[(int64_t)n + il]; nrP = rp[2 * (int64_t)n + il];
-            has_ref = true; rf_dirty = true;
-            ++next_switch;
-        }
-        if constexpr (REFF) {                                    // a switch sets the filter's target; its position is the step's new_ref
-            if (has_ref) reff_target(fs, nrN, nrE, nrP);
-            reff_advance(fa, fs);
-            nrN = fs.x[0][0]; nrE = fs.x[1][0]; nrP = fs.x[2][0];
-            has_ref = t + 1 < ca.T; rf_dirty = true;             // the last step's stays pending in the filter
-            if (t + 1 < ca.T) reff_row(fa, t + 1, n, i, live, s.refN, s.refE, s.refPsi);
-        }
-        StepOut out;
-        env_step<MODE, EXT>(a, ve, s, act, has_ref, nrN, nrE, nrP, a.cur_vc != nullptr, cur.vcN, cur.vcE, out, RND ? il : IL);
-        if (a.current_drift) current_drift_step(a, cur, vc0, beta0, a.env_id_base + i);
+// The public controller table float[DPENV_CTRL_NPARAM][n] -> the packed block, one lane per env (dpenv_set_dp_controller_table).  G is
+// dpenv_dp_allocation_matrix's recipe in its operation order (dpenv_api_free.hip), in f64, rounded once.  A row that breaks a condition of
+// include/dpenv.h is packed as the zero controller and marked in refused (uint8 [n], or NULL).
+__global__ __launch_bounds__(256) void pack_controllers_kernel(const float* __restrict__ pub, float4* __restrict__ tab,
+                                                                uint8_t* __restrict__ refused, int n)
+{
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    float p[CTRL_NPARAM];
 #pragma unroll
-        for (int k = 0; k < 9; ++k) o[k] = out.o[k];
-        if (a.auto_reset && out.d != 0u && live) {
-            if constexpr (REFF) {                                // the last step's pending new_ref: a re-drawn env keeps it as its reference
-                if (t == ca.T - 1) { s.refN = fs.x[0][0]; s.refE = fs.x[1][0]; s.refPsi = fs.x[2][0]; }
-            }
-            env_auto_reset<MODE>(a, s, a.env_id_base + i, episode, o);
-            if (RND && a.rand_tab) redraw_vessel(a, i, episode, ve);   // domain randomisation: the new episode runs on a new hull
-            if (CURR && a.cur_nom) { current_redraw_inline(a, i, episode, cur, vc0, beta0); cur_dirty = true; }  // ... in a new current
-            ++episode; ep_dirty = true; rf_dirty = true;
-            z[0] = z[1] = z[2] = 0.0f;                           // the new episode's first action is the law at z = 0
-            if constexpr (REFF) {                                // ... and the filter at rest on its reference
-                reff_rest(fs, s.refN, s.refE, s.refPsi);
-                if (t + 1 < ca.T) reff_row(fa, t + 1, n, i, live, s.refN, s.refE, s.refPsi);
-            }
-        }
-        if (live) {
-            (ca.rew + (int64_t)t * n)[(unsigned)i] = out.reward;
-            (ca.done + (int64_t)t * n)[(unsigned)i] = (uint8_t)out.d;
-        }
+    for (int k = 0; k < CTRL_NPARAM; ++k) p[k] = pub[(int64_t)k * n + i];
+    const float *kp = p + CTRL_KP, *kd = p + CTRL_KD, *ki = p + CTRL_KI, *zb = p + CTRL_ZB, *tmax = p + CTRL_TMAX, *w = p + CTRL_WEIGHT;
+    const float *lx = p + CTRL_LX, *ly = p + CTRL_LY, *kf = p + CTRL_KF;
+    const float kr_bow = p[CTRL_KR_BOW], f_eps = p[CTRL_F_EPS];
+    bool ok = true;
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+        ok = ok && isfinite(kp[j]) && isfinite(kd[j]) && isfinite(ki[j]);
+        ok = ok && zb[j] >= 0.0f && tmax[j] >= 0.0f;             // (false for a NaN)
+        ok = ok && isfinite(kf[j]) && kf[j] > 0.0f;
+        ok = ok && isfinite(lx[j]) && isfinite(ly[j]);
     }
-    // observation after the last step (controller input of the next launch) and final state
-    control_store_rows<OD>(lds_row, ca.last_obs, w_o, rem_o, o, tid, a.obs_bf16 != 0);
-    if (live) {
-        store_env(a, i, s, rf_dirty);
-        a.S3[i] = make_float4(o[6], o[7], o[8], 0.0f);
-        ca.z[i] = make_float4(z[0], z[1], z[2], 0.0f);
-        if (ep_dirty) a.episode[i] = (int)episode;
-        if (a.current_drift) { a.cur_vc[i] = cur.vc; a.cur_beta[i] = cur.beta; a.drift_ctr[i] = cur.ctr; }
-        if (CURR && cur_dirty) store_current(a, i, cur, vc0, beta0, true);
-        if constexpr (REFF) reff_store(fa, i, n, fs);
+    ok = ok && isfinite(kr_bow) && kr_bow > 0.0f && f_eps >= 0.0f;
+#pragma unroll
+    for (int m = 0; m < 5; ++m) ok = ok && isfinite(w[m]) && w[m] > 0.0f;
+
+    const double T[3][5] = {{0.0, 1.0, 0.0, 1.0, 0.0},
+                            {1.0, 0.0, 1.0, 0.0, 1.0},
+                            {(double)lx[0], -(double)ly[1], (double)lx[1], -(double)ly[2], (double)lx[2]}};
+    double V[5][3], M[3][3], adj[3][3];
+#pragma unroll
+    for (int m = 0; m < 5; ++m)
+#pragma unroll
+        for (int j = 0; j < 3; ++j) V[m][j] = T[j][m] / (double)w[m];
+#pragma unroll
+    for (int r = 0; r < 3; ++r)
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            double acc = 0.0;
+#pragma unroll
+            for (int m = 0; m < 5; ++m) acc += T[r][m] * V[m][c];
+            M[r][c] = acc;
+        }
+#pragma unroll
+    for (int r = 0; r < 3; ++r)
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {                            // adj[r][c] = cofactor of M[c][r]
+            const int r1 = (c + 1) % 3, r2 = (c + 2) % 3, c1 = (r + 1) % 3, c2 = (r + 2) % 3;
+            adj[r][c] = M[r1][c1] * M[r2][c2] - M[r1][c2] * M[r2][c1];
+        }
+    const double det = (M[0][0] * adj[0][0] + M[0][1] * adj[1][0]) + M[0][2] * adj[2][0];
+    ok = ok && isfinite(det) && det != 0.0;
+    float G[5][3];
+#pragma unroll
+    for (int m = 0; m < 5; ++m)
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            double acc = 0.0;
+#pragma unroll
+            for (int j = 0; j < 3; ++j) acc += V[m][j] * adj[j][c];
+            G[m][c] = (float)(acc / det);
+            ok = ok && isfinite(G[m][c]);
+        }
+
+    float q[4 * CTRL_TAB_STREAMS];
+#pragma unroll
+    for (int k = 0; k < 4 * CTRL_TAB_STREAMS; ++k) q[k] = 0.0f;
+    if (ok) {
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+            q[j] = kp[j]; q[3 + j] = kd[j]; q[6 + j] = ki[j]; q[9 + j] = zb[j]; q[12 + j] = tmax[j]; q[30 + j] = kf[j];
+        }
+#pragma unroll
+        for (int m = 0; m < 5; ++m)
+#pragma unroll
+            for (int j = 0; j < 3; ++j) q[15 + 3 * m + j] = G[m][j];
+        q[33] = kr_bow;
+        q[34] = f_eps;
+    } else {                                                     // the zero controller: the action [0, 0, 0, 0, 1, 0, 1] whatever the observation
+        q[30] = q[31] = q[32] = q[33] = 1.0f;
     }
+#pragma unroll
+    for (int k = 0; k < CTRL_TAB_STREAMS; ++k) tab[ctrl_tab_index(i, k)] = make_float4(q[4 * k], q[4 * k + 1], q[4 * k + 2], q[4 * k + 3]);
+    if (refused) refused[i] = ok ? 0 : 1;
 }
 
 // the controller's state z, float4 [n] <-> float [3][n]: op 0 reads it out (dpenv_get_dp_controller_state), 1 writes it

@@ -12,6 +12,11 @@ namespace dpenv {
 constexpr int BLOCK = 64;         // threads per workgroup = one wave64; one lane per environment; LDS staging is wave-private
 constexpr int RBLOCK = 64;        // rollout kernel: one wave per workgroup (wave-private LDS transposes)
 constexpr int MAX_SWITCH = 8;
+// slots of the public per-env controller table float[CTRL_NPARAM][n] = DPENV_CTRL_* of include/dpenv.h (dpenv_api.hip asserts it)
+constexpr int CTRL_NPARAM = 32, CTRL_KP = 0, CTRL_KD = 3, CTRL_KI = 6, CTRL_ZB = 9, CTRL_TMAX = 12, CTRL_WEIGHT = 15, CTRL_LX = 20,
+              CTRL_LY = 23, CTRL_KF = 26, CTRL_KR_BOW = 29, CTRL_F_EPS = 30;
+constexpr int CTRL_TAB_STREAMS = 9;   // float4 streams of the packed per-env block (dpenv_control_dev.h has its layout)
+constexpr int64_t ctrl_tab_float4s(int n) { return ((int64_t)n + 63) / 64 * 64 * CTRL_TAB_STREAMS; }   // whole waves of 64 envs
 constexpr int MAX_CLASSES = 64;
 
 // kernel specialisations: variant x azimuth-head style (customEnv.py:11,327,351,373 + cont_ang :90)
@@ -430,7 +435,10 @@ hipError_t launch_reff_state_io(float4* state, float* x, float* r, int n, int wr
 // dpenv_policy.hip, from dpenv_control_dev.h: the baseline controller's closed loop (fa != NULL: with the reference filter; ves as
 // launch_rollout's, classes excluded), its state (op 0 read into ext float[3][n], 1 write from it, 2 zero the envs of mask) and the
 // stateless allocation tau [3][n] -> action [n][7]
-hipError_t launch_controller_rollout(const StepArgs* a, const ControlArgs* ca, const FilterArgs* fa, int ves, hipStream_t s);
+// tab: the packed per-env block launch_pack_controllers wrote (every env flies its own row: the *_tab kernels), or NULL (ca's shared numbers)
+hipError_t launch_controller_rollout(const StepArgs* a, const ControlArgs* ca, const FilterArgs* fa, const float4* tab, int ves, hipStream_t s);
+// the public table float[CTRL_NPARAM][n] -> the packed block of ctrl_tab_float4s(n) float4; refused: uint8 [n] or NULL (dpenv_set_dp_controller_table)
+hipError_t launch_pack_controllers(const float* table, float4* tab, uint8_t* refused, int n, hipStream_t s);
 hipError_t launch_control_state(float4* z, float* ext, const uint8_t* mask, int n, int op, hipStream_t s);
 hipError_t launch_thrust_alloc(const ControlArgs* ca, const float* tau, float* action, int n, hipStream_t s);
 // two-wave closed loop, dpenv_policy_ws.h; one arithmetic per translation unit: dpenv_policy_ws.hip PREC_F16, dpenv_policy_xws1.hip

@@ -274,17 +274,29 @@ hipError_t dev::launch_policy_rollout(const StepArgs* a, const PolicyArgs* pa, c
     });
 }
 
-hipError_t dev::launch_controller_rollout(const StepArgs* a, const ControlArgs* ca, const FilterArgs* fa, int ves, hipStream_t s)
+hipError_t dev::launch_controller_rollout(const StepArgs* a, const ControlArgs* ca, const FilterArgs* fa, const float4* tab, int ves,
+                                          hipStream_t s)
 {
     // the vessel source must match the arguments (as launch_rollout's): a per-env form needs the table, VES_ARGS_LOSS and only it reads StepArgs.kl
     if ((ves == VES_ENV_VGPR || ves == VES_ENV_RND) && !a->env_tab) return hipErrorInvalidValue;
     if ((ves == VES_ARGS_LOSS) != (a->loss_on == LOSS_SHARED)) return hipErrorInvalidValue;
     const dim3 grid((a->n + RBLOCK - 1) / RBLOCK), block(RBLOCK);
     return with_control_ves(ves, [&](auto V) {
+        if (tab) {
+            if (fa) hipLaunchKernelGGL((controller_rollout_tab_kernel<V, true>), grid, block, 0, s, *a, *ca, *fa, tab);
+            else hipLaunchKernelGGL((controller_rollout_tab_kernel<V, false>), grid, block, 0, s, *a, *ca, FilterArgs{}, tab);
+            return hipGetLastError();
+        }
         if (fa) hipLaunchKernelGGL((controller_rollout_kernel<V, true>), grid, block, 0, s, *a, *ca, *fa);
         else hipLaunchKernelGGL((controller_rollout_kernel<V, false>), grid, block, 0, s, *a, *ca, FilterArgs{});
         return hipGetLastError();
     });
+}
+
+hipError_t dev::launch_pack_controllers(const float* table, float4* tab, uint8_t* refused, int n, hipStream_t s)
+{
+    hipLaunchKernelGGL(pack_controllers_kernel, dim3((n + 255) / 256), dim3(256), 0, s, table, tab, refused, n);
+    return hipGetLastError();
 }
 
 hipError_t dev::launch_control_state(float4* z, float* ext, const uint8_t* mask, int n, int op, hipStream_t s)

@@ -289,6 +289,115 @@ def allocation_matrix(lx, ly, weight=(1.0, 1.0, 1.0, 1.0, 1.0)):
     return G
 
 
+def allocation_matrix_batched(lx, ly, weight, check=True):
+    """allocation_matrix for n rows at once: lx, ly [n, 3], weight [n, 5] -> G [n, 5, 3] float64.  The vectorised NumPy statement of the
+    same recipe - the same operations in the same order, so every row equals allocation_matrix of that row bit for bit - and the host
+    statement of what the library's packing kernel computes for every env of a controller table (dpenv_set_dp_controller_table) before it
+    rounds to f32.  check=True raises ValueError for a row allocation_matrix would refuse; check=False leaves such rows non-finite."""
+    lx, ly, w = (np.asarray(v, np.float64) for v in (lx, ly, weight))
+    n = lx.shape[0]
+    if lx.shape != (n, 3) or ly.shape != (n, 3) or w.shape != (n, 5):
+        raise ValueError('allocation_matrix_batched: lx, ly [n, 3] and weight [n, 5]')
+    bad = ~(np.isfinite(w) & (w > 0)).all(1)
+    if check and bad.any():
+        raise ValueError('allocation_matrix_batched: five finite weights > 0 (rows %s)' % np.flatnonzero(bad)[:8].tolist())
+    zero, one = np.zeros(n), np.ones(n)
+    T = [[zero, one, zero, one, zero], [one, zero, one, zero, one], [lx[:, 0], -ly[:, 1], lx[:, 1], -ly[:, 2], lx[:, 2]]]
+    with np.errstate(all='ignore'):
+        V = [[T[j][m] / w[:, m] for j in range(3)] for m in range(5)]
+        M = [[None] * 3 for _ in range(3)]
+        for r in range(3):
+            for c in range(3):
+                acc = np.zeros(n)
+                for m in range(5):
+                    acc = acc + T[r][m] * V[m][c]
+                M[r][c] = acc
+        adj = [[None] * 3 for _ in range(3)]
+        for r in range(3):
+            for c in range(3):
+                r1, r2, c1, c2 = (c + 1) % 3, (c + 2) % 3, (r + 1) % 3, (r + 2) % 3
+                adj[r][c] = M[r1][c1] * M[r2][c2] - M[r1][c2] * M[r2][c1]
+        det = (M[0][0] * adj[0][0] + M[0][1] * adj[1][0]) + M[0][2] * adj[2][0]
+        bad = ~np.isfinite(det) | (det == 0.0)
+        if check and bad.any():
+            raise ValueError("allocation_matrix_batched: T W^-1 T' is singular (rows %s)" % np.flatnonzero(bad)[:8].tolist())
+        G = np.zeros((n, 5, 3))
+        for m in range(5):
+            for c in range(3):
+                acc = np.zeros(n)
+                for j in range(3):
+                    acc = acc + V[m][j] * adj[j][c]
+                G[:, m, c] = acc / det
+    return G
+
+
+# the public per-env controller table float[32][n] (include/dpenv.h DPENV_CTRL_*): parameter name -> (first slot, width)
+CTRL_NPARAM = 32
+CTRL_SLOTS = dict(kp=(0, 3), kd=(3, 3), ki=(6, 3), z_bound=(9, 3), tau_max=(12, 3), weight=(15, 5), lx=(20, 3), ly=(23, 3), kf=(26, 3),
+                  kr_bow=(29, 1), f_eps=(30, 1))
+
+
+def dp_controller_table(n, params=None, **per_env):
+    """The public controller table [32, n] float32 in the slot order of include/dpenv.h (env.set_dp_controller_table takes it as a
+    tensor): every env starts from params (the dict of dp_controller_defaults; None = the default hull's), and any of kp, kd, ki, z_bound,
+    tau_max, weight, lx, ly, kf, kr_bow, f_eps may be given per env as an array with a leading n.  The table carries lever arms and
+    weights, not G: the library computes every env's G from them (allocation_matrix_batched is that computation)."""
+    p = dp_controller_defaults() if params is None else params
+    unknown = sorted(set(per_env) - set(CTRL_SLOTS))
+    if unknown:
+        raise TypeError('dp_controller_table: unknown per-env parameter(s) %s (of %s)' % (unknown, sorted(CTRL_SLOTS)))
+    tab = np.zeros((CTRL_NPARAM, int(n)), np.float32)
+    for name, (first, width) in CTRL_SLOTS.items():
+        if name in per_env:
+            v = np.asarray(per_env[name], np.float64)
+            if v.shape not in ((n, width),) + (((n,),) if width == 1 else ()):
+                raise ValueError('dp_controller_table: %s has shape %s, want [%d, %d]' % (name, v.shape, n, width))
+            tab[first:first + width] = v.reshape(n, width).T
+        else:
+            v = np.asarray(p[name], np.float64).reshape(-1)
+            if v.shape != (width,):
+                raise ValueError('dp_controller_table: params[%r] has %d entries, want %d' % (name, v.size, width))
+            tab[first:first + width] = v[:, None]
+    return tab
+
+
+def dp_controller_table_params(table):
+    """The per-env parameter dict BatchedDPController takes for a public table [32, n]: every entry with a leading n, G [n, 5, 3] the
+    float64 allocation matrix of each row's f32 lever arms and weights (rounded to f32 by the controller, once, as the library does).
+    Rows the library would refuse are not treated here (their G is non-finite or the law meaningless)."""
+    tab = np.asarray(table, np.float32)
+    if tab.ndim != 2 or tab.shape[0] != CTRL_NPARAM:
+        raise ValueError('dp_controller_table_params: a [32, n] table')
+    p = {}
+    for name, (first, width) in CTRL_SLOTS.items():
+        v = tab[first:first + width].T.astype(np.float64)
+        p[name] = v[:, 0] if width == 1 else v
+    p['G'] = allocation_matrix_batched(p['lx'], p['ly'], p['weight'], check=False)
+    return p
+
+
+def gain_population(K, base=None, span=4.0, seed=0, what=('kp', 'kd', 'ki')):
+    """K parameter sets around base (the dict of dp_controller_defaults; None = the default hull's) for evaluate.baseline_gain_sweep: the
+    dict of base with every entry named in `what` as an array [K, 3].  Row 0 is the base itself; the others multiply each named gain, per
+    axis, by a factor drawn log-uniformly from [1 / span, span] (np.random.RandomState(seed): the same sets for the same arguments).
+    'factors' holds the factors drawn, name -> [K, 3]."""
+    base = dp_controller_defaults() if base is None else base
+    span = float(span)
+    if K < 1 or not span >= 1.0:
+        raise ValueError('gain_population: K >= 1 and span >= 1')
+    rng = np.random.RandomState(seed)
+    lo, hi = 1.0 / span, span
+    pop = dict(base)
+    pop['factors'] = {}
+    for name in what:
+        b = np.asarray(base[name], np.float64)
+        f = np.clip(np.exp(rng.uniform(np.log(lo), np.log(hi), size=(K,) + b.shape)), lo, hi)
+        f[0] = 1.0
+        pop['factors'][name] = f
+        pop[name] = b[None] * f
+    return pop
+
+
 def dp_controller_defaults(vessel=None, omega=REFERENCE_FILTER_OMEGA, zeta=(1.0, 1.0, 1.0), weight=(1.0, 1.0, 1.0, 1.0, 1.0)):
     """The baseline's default numbers for a hull (public parameter vector; None = the default hull), float64: Fossen's pole placement
     with the reference filter's bandwidths - Kp = m omega^2, Kd = 2 zeta omega m - d, Ki = Kp omega / 10 with m = (m11, m22, m33) and
@@ -312,10 +421,19 @@ class BatchedDPController(object):
     (the default) it reproduces the closed-loop kernel's actions bit for bit; dtype=np.float64 is the form for checks.  device other than
     'cpu' (or a torch dtype) runs the same expressions on torch tensors - the eager composition env.step(ctrl.act(obs)) on the device.
     params: the dict of dp_controller_defaults.  act(obs [n, >=6]) advances z [n, 3] one control step and returns the action [n, 7];
-    reset(mask) zeroes z of the envs in mask (None = all); allocate(tau [n, 3]) is the stateless allocation."""
+    reset(mask) zeroes z of the envs in mask (None = all); allocate(tau [n, 3]) is the stateless allocation.
+    Per-env parameters (the law of dpenv_set_dp_controller_table, env i on its own row): params is a public table [32, n]
+    (dp_controller_table) or a dict whose entries carry a leading n - kp [n, 3] ... G [n, 5, 3], kr_bow and f_eps [n]; shared and per-env
+    entries may be mixed.  The expressions are the same, so all-equal rows give the shared form's bits."""
 
     def __init__(self, n, params=None, dt=0.2, dtype=None, device='cpu'):
         p = dp_controller_defaults() if params is None else params
+        if not isinstance(p, dict):
+            p = dp_controller_table_params(p.detach().cpu().numpy() if hasattr(p, 'detach') else p)
+        for name, shape in (('kp', (3,)), ('kd', (3,)), ('ki', (3,)), ('z_bound', (3,)), ('tau_max', (3,)), ('G', (5, 3)), ('kf', (3,)),
+                            ('kr_bow', ()), ('f_eps', ())):
+            if np.shape(p[name]) not in (shape, (n,) + shape):
+                raise ValueError('BatchedDPController: %s has shape %s, want %s or %s' % (name, np.shape(p[name]), shape, (n,) + shape))
         self.torch = None
         if str(device) != 'cpu' or type(dtype).__module__ == 'torch':
             import torch
@@ -340,8 +458,8 @@ class BatchedDPController(object):
     def allocate(self, tau):
         xp = self._xp()
         G = self.G
-        f = [(G[m, 0] * tau[:, 0] + G[m, 1] * tau[:, 1]) + G[m, 2] * tau[:, 2] for m in range(5)]
-        kb = xp.where(f[0] >= self.zero, self.kf[0], self.kr_bow)
+        f = [(G[..., m, 0] * tau[:, 0] + G[..., m, 1] * tau[:, 1]) + G[..., m, 2] * tau[:, 2] for m in range(5)]
+        kb = xp.where(f[0] >= self.zero, self.kf[..., 0], self.kr_bow)
         nb = xp.copysign(xp.sqrt(xp.abs(f[0]) / kb), f[0])
         cols = [xp.minimum(xp.maximum(nb / self.hundred, -self.one), self.one)]
         sc = []
@@ -349,7 +467,7 @@ class BatchedDPController(object):
             for k in range(2):
                 Fx, Fy = f[1 + 2 * k], f[2 + 2 * k]
                 F = xp.sqrt(Fx * Fx + Fy * Fy)
-                ns = xp.sqrt(F / self.kf[1 + k])
+                ns = xp.sqrt(F / self.kf[..., 1 + k])
                 cols.append(xp.minimum(ns / self.hundred, self.one))
                 dirn = F > self.f_eps
                 sc += [xp.where(dirn, Fy / F, self.zero), xp.where(dirn, Fx / F, self.one)]

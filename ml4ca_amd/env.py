@@ -185,6 +185,7 @@ class BatchedRevoltEnv(object):
         self.integral_action = None          # dict of the parameters while set_integral_action() has it on
         self.reference_filter = None         # dict of the parameters while set_reference_filter() has it on
         self.dp_controller = None            # dict of the parameters while set_dp_controller() has it on
+        self.dp_controller_table = None      # the [32, n] tensor while set_dp_controller_table() has per-env numbers in force
 
     # -- plumbing -----------------------------------------------------------------------------
     # What a Python `for` over step() pays per call besides the launch is this plumbing (bench.py `eager_loop`): the stream handle and
@@ -443,11 +444,35 @@ class BatchedRevoltEnv(object):
         integral z of every env.  step(), rollout() and policy_rollout() keep working while it is on."""
         if off:
             _lib.check(self.lib.dpenv_set_dp_controller(self._h, None, self._stream()), self._h)
-            self.dp_controller = None
+            self.dp_controller = self.dp_controller_table = None
             return
         p, c = _dp_controller_struct(params)
         _lib.check(self.lib.dpenv_set_dp_controller(self._h, C.byref(c), self._stream()), self._h)
         self.dp_controller = dict(p)
+        self.dp_controller_table = None      # the scalar law again: the library dropped a table in force
+
+    def set_dp_controller_table(self, table, check=True):
+        """Per-env numbers for the baseline (dpenv_set_dp_controller_table): table is a float32 tensor [32, n] on the env's device in
+        the slot order of include/dpenv.h (deploy.dp_controller_table builds it), and controller_rollout then flies row i on env i; None
+        returns to the numbers of set_dp_controller, which has to be on.  The library computes every env's allocation matrix from the row's
+        lever arms and weights, and packs a row it refuses as the zero controller.  check=True passes a mask, reads it back and, if any row
+        was refused, removes the table again and raises ValueError naming the first refused envs.  check=False reads nothing back: the
+        form to record into a graph (a replay packs the tensor's contents of that moment).  z is left alone."""
+        torch = _torch()
+        if table is None:
+            _lib.check(self.lib.dpenv_set_dp_controller_table(self._h, None, None, self._stream()), self._h)
+            self.dp_controller_table = None
+            return
+        self._chk(table, (32, self.n_envs), torch.float32, 'table')
+        mask = torch.empty(self.n_envs, dtype=torch.uint8, device=self.device) if check else None
+        _lib.check(self.lib.dpenv_set_dp_controller_table(self._h, self._ptr(table), self._ptr(mask), self._stream()), self._h)
+        self.dp_controller_table = table
+        if check and bool(mask.any()):
+            bad = torch.nonzero(mask).flatten()
+            self.set_dp_controller_table(None)
+            raise ValueError('set_dp_controller_table: %d row(s) refused (envs %s%s): non-finite gains, a negative bound, kf or a weight '
+                             '<= 0, or lever arms with a singular allocation - the scalar law stays in force'
+                             % (bad.numel(), bad[:8].tolist(), ', ...' if bad.numel() > 8 else ''))
 
     def get_dp_controller_state(self):
         """z float32 [3, n]: the baseline's error integral.  Checkpoint with get_state()."""

@@ -3,8 +3,9 @@
 on a pre-made action block - the same one-wave T-step loop minus the law, the parent's kernel.  One process, device events, the arms
 alternating launch by launch, medians of --reps launches of --steps steps at --envs envs.  Also: the eager composition (env.step plus
 the law in torch on the device), and a 1 250-step streamed box test with scoring, calm and in 0.2 m/s from 16 directions, with the IAE
-and work it scores (beside the thesis actor's with --actor).
-    python tools/time_controller.py [--envs 65536] [--steps 50] [--reps 20] [--actor] [--out time_controller.json]"""
+and work it scores (beside the thesis actor's with --actor).  --table adds the per-env controller table's arm (every row the defaults:
+the same flight through controller_rollout_tab_kernel), alternating with the scalar arm launch by launch, and the packing kernel's time.
+    python tools/time_controller.py [--envs 65536] [--steps 50] [--reps 20] [--actor] [--table] [--no-box] [--out time_controller.json]"""
 import argparse
 import json
 import math
@@ -37,13 +38,15 @@ def main():
     ap.add_argument('--eager-reps', type=int, default=5)
     ap.add_argument('--box-steps', type=int, default=1250)
     ap.add_argument('--actor', action='store_true', help='fly the thesis actor (tests/golden/final_policy.npz) through the same box tests')
+    ap.add_argument('--table', action='store_true', help='also time the per-env controller table form and its packing kernel')
+    ap.add_argument('--no-box', action='store_true', help='skip the eager composition and the box tests')
     ap.add_argument('--out', default='')
     args = ap.parse_args()
     import numpy as np
     import torch
     import ml4ca_amd
     from ml4ca_amd import evaluate as EV
-    from ml4ca_amd.deploy import BatchedDPController
+    from ml4ca_amd.deploy import BatchedDPController, dp_controller_table
     from ml4ca_amd.policy import controller_rollout
     dev = torch.device('cuda', 0)
     n, T = args.envs, args.steps
@@ -77,6 +80,41 @@ def main():
           'reference filter %.2f (x %.3f)' % (n, T, args.reps, med['yardstick'], med[False], med[False] / med['yardstick'], med[True],
                                               med[True] / med['yardstick']), flush=True)
     assert bool(torch.isfinite(out[False]['act']).all()) and bool(torch.isfinite(out[True]['ref']).all())
+
+    # ---- the per-env table form against the scalar form: the same flight, operands per lane ----
+    if args.table:
+        table = torch.from_numpy(dp_controller_table(n, env.dp_controller)).to(dev)
+        env.set_dp_controller_table(table)                          # (the first call allocates the packed block; rows checked once)
+        tt = {('scalar', False): [], ('table', False): [], ('scalar', True): [], ('table', True): [], 'pack': []}
+        for k in range(args.warm + args.reps):
+            t = {}
+            for filt in (False, True):
+                if filt:
+                    env.set_reference_filter()
+                env.set_dp_controller_table(None)
+                t[('scalar', filt)] = timed(torch, lambda: controller_rollout(env, T, out=out[filt])) / T * 1e3
+                t['pack'] = timed(torch, lambda: env.set_dp_controller_table(table, check=False)) * 1e3
+                t[('table', filt)] = timed(torch, lambda: controller_rollout(env, T, out=out[filt])) / T * 1e3
+                if filt:
+                    env.set_reference_filter(None)
+            if k >= args.warm:
+                for key, v in t.items():
+                    tt[key].append(v)
+        m = {key: median(v) for key, v in tt.items()}
+        res['table'] = {'scalar_us_per_step': m[('scalar', False)], 'table_us_per_step': m[('table', False)],
+                        'ratio': m[('table', False)] / m[('scalar', False)], 'scalar_filter_us_per_step': m[('scalar', True)],
+                        'table_filter_us_per_step': m[('table', True)], 'ratio_filter': m[('table', True)] / m[('scalar', True)],
+                        'pack_us': m['pack']}
+        print('per-env table, %d envs, %d-step launches, arms alternating, medians of %d: scalar %.2f us/step, table %.2f (x %.3f); with the '
+              'reference filter scalar %.2f, table %.2f (x %.3f); packing kernel (setter call, one launch) %.1f us' % (
+                  n, T, args.reps, m[('scalar', False)], m[('table', False)], res['table']['ratio'], m[('scalar', True)], m[('table', True)],
+                  res['table']['ratio_filter'], m['pack']), flush=True)
+        env.set_dp_controller_table(None)
+    if args.no_box:
+        if args.out:
+            os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+            json.dump(res, open(args.out, 'w'), indent=1)
+        return
 
     # ---- the eager composition: env.step + the law in torch on the device ----
     ctrl = BatchedDPController(n, env.dp_controller, dt=env.control_period, device=dev)

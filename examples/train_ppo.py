@@ -1,14 +1,17 @@
 #!/usr/bin/env python3
 """PPO-clip on the batched ReVolt DP environment with the rollout entirely inside one launch per epoch.
 
-Host-side glue around the accelerated path (the PPO update is out of the hot path's scope: SURVEY section 2 row 9):
-the algorithm and hyper-parameters are the reference's (spinup/algos/tf1/ppo/ppo.py:109-347, train.py:29-55,
+Host-side glue around the accelerated path.  The update runs either way: --update torch (the default) is autograd and
+torch.optim.Adam, the form SURVEY section 2 row 9 scoped out of the hot path; --update fused runs the 80 + 80 gradient steps as the
+library's kernels (ml4ca_amd/train.py: PPO-clip and MSE gradients on the matrix cores, Adam gated on the KL on the device), since
+with the rollout at 3 ms the update is where an epoch's time goes.  The algorithm and hyper-parameters are the reference's (spinup/algos/tf1/ppo/ppo.py:109-347, train.py:29-55,
 config.json of the shipped run): clip 0.2, pi_lr 3e-4, vf_lr 1e-3, <= 80 policy iterations with early stop at
 KL > 1.5 * 0.01, 80 value iterations, gamma 0.99, lambda 0.97, hidden 3 x 80 leaky-relu, T = 400.
 What differs is the rollout: N environments x T steps from ONE dpenv_policy_rollout launch (actor, sampling,
 env.step, critic, trajectory rows), GAE by one scan kernel, advantage statistics by device reductions.
 
     python examples/train_ppo.py --envs 4096 --epochs 30
+    python examples/train_ppo.py --envs 4096 --epochs 30 --update fused
     python examples/train_ppo.py --envs 4096 --epochs 40 --randomise 0.15 --eval      domain randomisation: every episode of every env
                                                                                       runs on its own hull, +-15 % on all 26 parameters, re-drawn by the reset path
                                                                                       inside the rollout launch; --eval: the reference's evaluation harness
@@ -134,6 +137,40 @@ def tune_baseline(ac, dev, preset, precision, K, seed=0, out=print, directions=1
     return {'mean_iae': iae.tolist(), 'mean_work': work.tolist(), 'front': [int(k) for k in sw['front']], 'actor': {'IAE': a_iae, 'work': a_work.tolist()}}
 
 
+def torch_update(ac, pi_opt, v_opt, pi_params, v_params, obs, act, adv, ret, logp_old, mb, clip=0.2, target_kl=0.01, gather=False, iters=80):
+    """The update of ppo.py:265-273 through torch autograd and torch.optim.Adam (--update torch): the baseline the fused update
+    (ml4ca_amd.train.PPOUpdater, --update fused) is held to and timed against.  Returns (pi_iters, kl, v_loss)."""
+    dev, N = obs.device, obs.shape[0]
+    kl, pi_iters = 0.0, 0
+    for i in range(iters):                                                  # ppo.py:265-271
+        idx = torch.randint(0, N, (mb,), device=dev) if mb < N else slice(None)
+        mu = ac._mlp(obs[idx], ac.pi_W, ac.pi_b)
+        logp = ac.logp_ref(act[idx], mu)
+        ratio = torch.exp(logp - logp_old[idx])
+        a = adv[idx]
+        pi_loss = -torch.min(ratio * a, torch.clamp(ratio, 1 - clip, 1 + clip) * a).mean()   # ppo.py:238-240
+        kl_t = (logp_old[idx] - logp).mean().detach()
+        kl = float(kl_t if gather else D.mean_across_ranks(kl_t))             # mpi_avg(kl), ppo.py:267 (identical on every rank when gathered)
+        if kl > 1.5 * target_kl:                                            # ppo.py:267-270
+            break
+        pi_opt.zero_grad()
+        pi_loss.backward()
+        if not gather:
+            D.average_gradients(pi_params)                                 # mpi_tf.py:59-62 (no-op on one rank)
+        pi_opt.step()
+        pi_iters += 1
+    for i in range(iters):                                                  # ppo.py:272-273
+        idx = torch.randint(0, N, (mb,), device=dev) if mb < N else slice(None)
+        v = ac._mlp(obs[idx], ac.v_W, ac.v_b)[:, 0]
+        v_loss = ((ret[idx] - v) ** 2).mean()                               # ppo.py:241
+        v_opt.zero_grad()
+        v_loss.backward()
+        if not gather:
+            D.average_gradients(v_params)
+        v_opt.step()
+    return pi_iters, kl, float(v_loss.detach())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--envs', type=int, default=4096)
@@ -144,6 +181,9 @@ def main():
     ap.add_argument('--activation', default='leaky', choices=('leaky', 'relu', 'tanh'), help='hidden activation (train.py:24,31)')
     ap.add_argument('--precision', default='f32', choices=('f16', 'f32', 'f32_actor'),
                     help="in-kernel network arithmetic: 'f32' (split-f16, within 1e-5 of the fp32 update's own evaluation: the PPO ratio starts at 1) or 'f16' (fast)")
+    ap.add_argument('--update', default='torch', choices=('torch', 'fused'),
+                    help="the 80 + 80 gradient steps: 'torch' = autograd + torch.optim.Adam (torch_update below); 'fused' = the library's gradient and "
+                         'gated-Adam kernels (ml4ca_amd.train.PPOUpdater): the whole update queues without a host round trip, one read at the end')
     ap.add_argument('--exchange', default='gradients', choices=('gradients', 'rollout'),
                     help="multi-rank runs: 'gradients' = every rank updates on ITS OWN episode and the gradients are averaged, exactly the "
                          "reference (ppo.py:226, mpi_tf.py:29-62: no trajectory ever crosses); 'rollout' = BASELINE.json config 4: the ranks "
@@ -197,13 +237,20 @@ def main():
             env.set_current_randomisation(r_v, math.radians(r_b))
     ac = ActorCritic(9, 7, (80, 80, 80), leak=0.2, seed=args.seed, device=dev, activation=args.activation)
     D.sync_params(ac.parameters())                                               # sync_all_params, ppo.py:255
-    for p in ac.parameters():
-        p.requires_grad_(True)
+    clip, target_kl, T, n = 0.2, 0.01, args.steps, args.envs
+    upd = average = None
+    if args.update == 'fused':
+        from ml4ca_amd.train import PPOUpdater
+        upd = PPOUpdater(ac, pi_lr=3e-4, v_lr=1e-3, clip=clip, target_kl=target_kl)      # ac's tensors are now views of its two flat vectors
+        if world > 1 and args.exchange == 'gradients':
+            average = D.average_flat                                             # gradient AND statistics (the KL of the gate) in one all-reduce
+    else:
+        for p in ac.parameters():
+            p.requires_grad_(True)
     pi_params = ac.pi_W + ac.pi_b + [ac.log_std]
     v_params = ac.v_W + ac.v_b
-    pi_opt = torch.optim.Adam(pi_params, lr=3e-4)
-    v_opt = torch.optim.Adam(v_params, lr=1e-3)
-    clip, target_kl, T, n = 0.2, 0.01, args.steps, args.envs
+    pi_opt = torch.optim.Adam(pi_params, lr=3e-4) if upd is None else None
+    v_opt = torch.optim.Adam(v_params, lr=1e-3) if upd is None else None
     buf = rollout.RolloutBuffer(T, env, gamma=0.99, lam=0.97)
     ac.upload(env, precision=args.precision)          # device pointers: one packing kernel, no host copy
     env.reset()
@@ -241,33 +288,10 @@ def main():
         N = obs.shape[0]
         mb = min(args.minibatch, N)
         t1 = time.perf_counter()
-        kl, pi_iters = 0.0, 0
-        for i in range(80):                                                     # ppo.py:265-271
-            idx = torch.randint(0, N, (mb,), device=dev) if mb < N else slice(None)
-            mu = ac._mlp(obs[idx], ac.pi_W, ac.pi_b)
-            logp = ac.logp_ref(act[idx], mu)
-            ratio = torch.exp(logp - logp_old[idx])
-            a = adv[idx]
-            pi_loss = -torch.min(ratio * a, torch.clamp(ratio, 1 - clip, 1 + clip) * a).mean()   # ppo.py:238-240
-            kl_t = (logp_old[idx] - logp).mean().detach()
-            kl = float(kl_t if gather else D.mean_across_ranks(kl_t))             # mpi_avg(kl), ppo.py:267 (identical on every rank when gathered)
-            if kl > 1.5 * target_kl:                                            # ppo.py:267-270
-                break
-            pi_opt.zero_grad()
-            pi_loss.backward()
-            if not gather:
-                D.average_gradients(pi_params)                                 # mpi_tf.py:59-62 (no-op on one rank)
-            pi_opt.step()
-            pi_iters += 1
-        for i in range(80):                                                     # ppo.py:272-273
-            idx = torch.randint(0, N, (mb,), device=dev) if mb < N else slice(None)
-            v = ac._mlp(obs[idx], ac.v_W, ac.v_b)[:, 0]
-            v_loss = ((ret[idx] - v) ** 2).mean()                               # ppo.py:241
-            v_opt.zero_grad()
-            v_loss.backward()
-            if not gather:
-                D.average_gradients(v_params)
-            v_opt.step()
+        if upd is not None:
+            pi_iters, kl, v_loss = upd.update(obs, act, adv, ret, logp_old, iters=80, minibatch=mb, average=average)
+        else:
+            pi_iters, kl, v_loss = torch_update(ac, pi_opt, v_opt, pi_params, v_params, obs, act, adv, ret, logp_old, mb, clip, target_kl, gather)
         with torch.no_grad():
             ac.log_std.clamp_(-4.0, 1.0)
         if gather:
@@ -279,7 +303,7 @@ def main():
         if rank == 0:
             print('%5d  %10.3f  %22.2f  %8d  %.4f  %8.1f  %9.1f  %8.2f' % (
                 epoch, float(blk['rew'].mean()), 1000.0 * float((done & 1).float().mean()), pi_iters, kl,
-                float(v_loss.detach()), t_roll * 1e3, t_upd))
+                v_loss, t_roll * 1e3, t_upd))
     if rank == 0:
         print('env-steps collected: %d (%.1f M per epoch, %d rank(s))' % (args.epochs * T * n * world, T * n * world / 1e6, world))
         if args.randomise > 0:

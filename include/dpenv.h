@@ -715,6 +715,82 @@ int dpenv_controller_rollout(dpenv_handle h, const dpenv_controller_rollout_io* 
  * float[n][7].  Handle-free, like dpenv_thrust_map; of c only G, kf, kr_bow and f_eps are read, the whole struct is validated. */
 int dpenv_thrust_alloc(const dpenv_dp_controller* c, const float* tau, float* action_out, int32_t n, dpenv_stream s);
 
+/* ---- The PPO update: actor and critic gradients and a device-gated Adam step --------------------------------------------------------
+ * Handle-free like dpenv_gae / dpenv_adv_*: device pointers and a stream; no call allocates or synchronises, so a whole update (80
+ * actor steps, 80 critic steps) queues without a host round trip and every call can be captured into a graph (each call is a chain of
+ * kernels, no parallel branches).  Everything is validated on the host before any device call; a refused call launches nothing.
+ *
+ * PARAMETERS.  One flat float theta[P] per network: W0 row-major [in][out] (the x @ W orientation), b0, W1, b1, ..., and for the actor
+ * log_std[out] at the end.  9 -> 80 -> 80 -> 80 -> 7 with log_std: P = 14 334; 9 -> 80 -> 80 -> 80 -> 1: P = 13 841
+ * (dpenv_train_param_count).  Hidden activation h = max(z, leak z), 0 <= leak <= 1 (0 = relu); its derivative is 1 where z > 0 and
+ * leak elsewhere (z = 0 included).
+ *
+ * ROWS.  f32: obs [n_rows][in], act [n_rows][out], adv, ret, logp_old [n_rows].  idx: `count` row indices in [0, n_rows), repeats
+ * allowed, or NULL = rows 0 .. count-1 (then n_rows >= count).  The indices are the CALLER'S CONTRACT: they live on the device and are
+ * not checked there; an index outside [0, n_rows) reads outside the blocks.
+ *
+ * ACTOR LOSS (ppo.py:238-240), per row, sums over the out action components j:
+ *     sd_j  = exp(log_std_j) + 1e-8
+ *     q_j   = (act_j - mu_j) / sd_j
+ *     logp  = sum_j -0.5 ((q_j^2 + 2 log_std_j) + log(2 pi))                          (gaussian_likelihood, core.py:42-46)
+ *     ratio = exp(logp - logp_old)
+ *     s1 = ratio A,   s2 = min(max(ratio, 1 - clip), 1 + clip) A,   L = -mean(min(s1, s2))
+ * GRADIENT RULE.  dL/dlogp = -A ratio / count  if  s1 <= s2,  else 0.  s1 < s2 is the unclipped term being the minimum (also with the
+ * ratio outside the bounds, when the advantage pulls it back); s1 == s2 happens where A == 0 or 1 - clip <= ratio <= 1 + clip, bounds
+ * INCLUDED, and there torch.minimum's half-and-half tie split and torch.clamp's inclusive bounds add up to the same -A ratio / count.
+ *     dlogp/dmu_j = q_j / sd_j        dlogp/dlog_std_j = q_j^2 exp(log_std_j) / sd_j - 1
+ * STATISTICS behind the gradient, grad_out[P .. P+3] (so a multi-rank caller averages gradient and KL in the one all-reduce):
+ *     pi_loss = L,  approx_kl = mean(logp_old - logp),  clip_frac = mean(ratio > 1 + clip or ratio < 1 - clip),  mean_ratio = mean(ratio).
+ * CRITIC.  L = mean((ret - v)^2), dL/dv = 2 (v - ret) / count;  grad_out[P] = v_loss = L.
+ *
+ * ARITHMETIC.  Every product of the forward pass, the backward pass and the weight gradients is an exact-f32 matrix instruction (a
+ * k-ordered fmaf chain); rows are summed unscaled and 1/count is applied once, by the final reduction.  DETERMINISM.  The grid is a
+ * function of count alone (ceil(count / 64) workgroups, at most 256); each workgroup writes one partial to the workspace and the
+ * partials are summed in workgroup order (in f64, rounded once).  No floating-point atomics: equal inputs give equal bits.
+ *
+ * WHAT IS IMPLEMENTED, everything else being refused with DPENV_EINVAL and the reason in dpenv_last_error(NULL):
+ *     n_layers == 4 with sizes = {in, 80, 80, 80, out}, 1 <= in <= 16;  actor (log_std = 1): 1 <= out <= 7;  critic (log_std = 0): out == 1;
+ *     activation DPENV_ACT_LEAKY_RELU with 0 <= leak <= 1;  row_dtype DPENV_F32.
+ *     Refused: DPENV_ACT_TANH, any other depth or width, bf16 rows. */
+typedef struct dpenv_train_shape {
+    uint32_t struct_size;
+    int32_t n_layers;        /* dense layers */
+    int32_t sizes[6];        /* in, hidden ..., out */
+    int32_t activation;      /* DPENV_ACT_* */
+    float leak;
+    int32_t row_dtype;       /* DPENV_F32 */
+    int32_t log_std;         /* 1: actor, theta ends with log_std[out];  0: critic */
+} dpenv_train_shape;
+/* P of the shape, or DPENV_EINVAL. */
+int64_t dpenv_train_param_count(const dpenv_train_shape* shape);
+/* Bytes of device workspace a gradient call on up to max_count rows needs (the per-workgroup partials).  The caller allocates;
+ * a gradient call whose workspace_bytes is smaller than its count needs is refused. */
+int dpenv_train_workspace_bytes(const dpenv_train_shape* shape, int32_t max_count, int64_t* bytes_out);
+/* count <= 2^30.  The first gradient call of a process on a device raises the kernel's LDS limit (a function attribute, not a stream
+ * operation): make that call outside a stream capture; every later call can be captured.
+ * grad_out: device float[P + 4].  stop_flag: device int32 or NULL; a launch that finds it set returns at once and leaves grad_out
+ * as it is (the gate of dpenv_adam_step has closed: the rest of a queued update falls through). */
+int dpenv_ppo_actor_grad(const dpenv_train_shape* shape, const float* theta, const float* obs, const float* act, const float* adv,
+                         const float* logp_old, const int32_t* idx, int32_t count, int32_t n_rows, float clip, const int32_t* stop_flag,
+                         float* grad_out, void* workspace, int64_t workspace_bytes, dpenv_stream s);
+/* grad_out: device float[P + 1]. */
+int dpenv_value_grad(const dpenv_train_shape* shape, const float* theta, const float* obs, const float* ret, const int32_t* idx,
+                     int32_t count, int32_t n_rows, float* grad_out, void* workspace, int64_t workspace_bytes, dpenv_stream s);
+/* ADAM, torch.optim.Adam's update (bias correction and eps placement included; not TF's variant).  theta, grad, m, v: device float[P],
+ * 16-byte aligned.  step_counter: device int32, the steps taken so far.  With t = *step_counter + 1, every operation in f32 and
+ * correctly rounded unless marked f64:
+ *     pow(b, t): f64, p = 1; while t: { if (t & 1) p *= b; b *= b; t >>= 1; }
+ *     step_size = lr / (float)(1 - pow(beta1, t))        bc2s = sqrt((float)(1 - pow(beta2, t)))
+ *     m     = fmaf(1 - beta1, g - m, m)
+ *     v     = fmaf((1 - beta2) g, g, beta2 v)
+ *     denom = sqrt(v) / bc2s + eps
+ *     theta = fmaf(-step_size, m / denom, theta)
+ * THE GATE replaces the host's float(kl) + break (ppo.py:267-270).  gate_kl: device float or NULL; stop_flag: device int32, required
+ * with gate_kl.  If gate_kl != NULL and (*stop_flag != 0 or *gate_kl > kl_limit): *stop_flag = 1 and nothing else changes.  Otherwise
+ * the step is taken and *step_counter incremented.  gate_kl == NULL: no gate, stop_flag is not read. */
+int dpenv_adam_step(float* theta, const float* grad, float* m, float* v, int32_t P, float lr, float beta1, float beta2, float eps,
+                    int32_t* step_counter, const float* gate_kl, float kl_limit, int32_t* stop_flag, dpenv_stream s);
+
 int dpenv_abi_version(void);
 
 #ifdef __cplusplus

@@ -102,6 +102,11 @@ class ScoreIO(C.Structure):
                 ('rps_max', C.c_float * 3), ('cut_at_end', C.c_int32)]
 
 
+class TrainShape(C.Structure):
+    _fields_ = [('struct_size', C.c_uint32), ('n_layers', C.c_int32), ('sizes', C.c_int32 * 6), ('activation', C.c_int32),
+                ('leak', C.c_float), ('row_dtype', C.c_int32), ('log_std', C.c_int32)]
+
+
 # read slots of the score card (dpenv.h DPENV_SCORE_*)
 SCORE_IAE, SCORE_WORK, SCORE_RET, SCORE_LEN, SCORE_EPISODES, SCORE_EP_IAE, SCORE_EP_WORK, SCORE_EP_RET, SCORE_EP_LEN, SCORE_NOUT = 0, 1, 4, 5, 6, 7, 8, 11, 12, 13
 
@@ -177,6 +182,11 @@ SYMBOLS = {
     'dpenv_set_dp_controller_table': (C.c_int, [_VP, _VP, _VP, _VP]),
     'dpenv_controller_rollout': (C.c_int, [_VP, C.POINTER(ControllerRolloutIO), _VP]),
     'dpenv_thrust_alloc': (C.c_int, [C.POINTER(DPController), _VP, _VP, _I32, _VP]),
+    'dpenv_train_param_count': (C.c_int64, [C.POINTER(TrainShape)]),
+    'dpenv_train_workspace_bytes': (C.c_int, [C.POINTER(TrainShape), _I32, C.POINTER(C.c_int64)]),
+    'dpenv_ppo_actor_grad': (C.c_int, [C.POINTER(TrainShape), _VP, _VP, _VP, _VP, _VP, _VP, _I32, _I32, _F, _VP, _VP, _VP, _I64, _VP]),
+    'dpenv_value_grad': (C.c_int, [C.POINTER(TrainShape), _VP, _VP, _VP, _VP, _I32, _I32, _VP, _VP, _I64, _VP]),
+    'dpenv_adam_step': (C.c_int, [_VP, _VP, _VP, _VP, _I32, _F, _F, _F, _F, _VP, _VP, _F, _VP, _VP]),
 }
 
 _lib = None

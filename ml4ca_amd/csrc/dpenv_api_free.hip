@@ -1,11 +1,12 @@
 // dpenv_api_free.hip - the entry points of the C ABI (include/dpenv.h) that take no handle: the defaults, the stateless device helpers
-// (thrust map, allocation, GAE, advantage statistics, score card) and the pure validators they share with the handle code in
+// (thrust map, allocation, GAE, advantage statistics, score card, the PPO update) and the pure validators they share with the handle code in
 // dpenv_api.hip (dpenv_host.h).  Nothing here can look inside a handle: its struct is private to dpenv_api.hip.
 #include <cmath>
 #include <cstring>
 #include <string>
 
 #include "dpenv_host.h"
+#include "dpenv_train_dev.h"
 
 using namespace dpenv;
 using namespace dpenv::host;
@@ -431,5 +432,103 @@ extern "C" int dpenv_adv_apply_stats(float* adv, int64_t count, const double* st
 {
     if (!adv || !stats || count <= 0 || !(total_count >= 1.0)) return fail(nullptr, DPENV_EINVAL, "dpenv_adv_apply_stats: bad argument");
     HIP_TRY(nullptr, dev::launch_adv_apply(adv, count, nullptr, nullptr, stats, total_count, (hipStream_t)s));
+    return DPENV_OK;
+}
+
+// ---- the PPO update (dpenv.h: dpenv_ppo_actor_grad, dpenv_value_grad, dpenv_adam_step): every argument is validated here, before any device call ----
+static const char* train_shape_check(const dpenv_train_shape* sh, TrainLayout* L)
+{
+    if (!sh) return "shape is NULL";
+    if (sh->struct_size != sizeof(dpenv_train_shape)) return "dpenv_train_shape ABI mismatch";
+    if (sh->row_dtype != DPENV_F32) return "rows must be DPENV_F32 (bf16 rows are not implemented)";
+    if (sh->activation != DPENV_ACT_LEAKY_RELU) return "activation must be DPENV_ACT_LEAKY_RELU (tanh is not implemented)";
+    if (!(sh->leak >= 0.0f && sh->leak <= 1.0f)) return "leak must be in [0, 1]";
+    if (sh->n_layers != 4) return "n_layers must be 4 (in -> 80 -> 80 -> 80 -> out)";
+    if (sh->sizes[1] != TR_H || sh->sizes[2] != TR_H || sh->sizes[3] != TR_H) return "the three hidden layers must be 80 wide";
+    if (sh->sizes[0] < 1 || sh->sizes[0] > TR_PAD) return "the input width must be in 1 .. 16";
+    if (sh->log_std != 0 && sh->log_std != 1) return "log_std must be 0 (critic) or 1 (actor)";
+    if (sh->log_std ? (sh->sizes[4] < 1 || sh->sizes[4] > 7) : sh->sizes[4] != 1) return "the output width must be 1 .. 7 for an actor and 1 for a critic";
+    *L = train_layout(sh->sizes[0], sh->sizes[4], sh->log_std);
+    return nullptr;
+}
+
+static int64_t train_ws_bytes(const TrainLayout& L, int count)
+{
+    return (int64_t)train_grid(count) * (L.P + (L.actor ? TR_NSTAT_ACTOR : TR_NSTAT_CRITIC)) * (int64_t)sizeof(float);
+}
+
+extern "C" int64_t dpenv_train_param_count(const dpenv_train_shape* shape)
+{
+    TrainLayout L;
+    if (const char* why = train_shape_check(shape, &L)) return fail(nullptr, DPENV_EINVAL, "dpenv_train_param_count: %s", why);
+    return L.P;
+}
+
+extern "C" int dpenv_train_workspace_bytes(const dpenv_train_shape* shape, int32_t max_count, int64_t* bytes_out)
+{
+    TrainLayout L;
+    if (const char* why = train_shape_check(shape, &L)) return fail(nullptr, DPENV_EINVAL, "dpenv_train_workspace_bytes: %s", why);
+    if (!bytes_out) return fail(nullptr, DPENV_EINVAL, "dpenv_train_workspace_bytes: bytes_out is NULL");
+    if (max_count < 1 || max_count > TR_MAX_COUNT)
+        return fail(nullptr, DPENV_EINVAL, "dpenv_train_workspace_bytes: max_count = %d, must be in 1 .. %d", max_count, TR_MAX_COUNT);
+    *bytes_out = train_ws_bytes(L, max_count);
+    return DPENV_OK;
+}
+
+static int train_grad(const char* who, const dpenv_train_shape* shape, int actor, const float* theta, const float* obs, const float* act,
+                      const float* adv, const float* logp_old, const int32_t* idx, int32_t count, int32_t n_rows, float clip,
+                      const int32_t* stop_flag, float* grad_out, void* workspace, int64_t workspace_bytes, dpenv_stream s)
+{
+    GradArgs a = {};
+    if (const char* why = train_shape_check(shape, &a.L)) return fail(nullptr, DPENV_EINVAL, "%s: %s", who, why);
+    if (a.L.actor != actor) return fail(nullptr, DPENV_EINVAL, "%s: the shape's log_std = %d is the other network's", who, a.L.actor);
+    if (count <= 0) return fail(nullptr, DPENV_EINVAL, "%s: count = %d, must be >= 1", who, count);
+    if (count > TR_MAX_COUNT) return fail(nullptr, DPENV_EINVAL, "%s: count = %d, at most %d rows per call", who, count, TR_MAX_COUNT);
+    if (n_rows <= 0) return fail(nullptr, DPENV_EINVAL, "%s: n_rows = %d, must be >= 1", who, n_rows);
+    if (!idx && n_rows < count) return fail(nullptr, DPENV_EINVAL, "%s: without idx the rows are 0 .. count-1: n_rows = %d < count = %d", who, n_rows, count);
+    if (!theta || !obs || !adv || !grad_out) return fail(nullptr, DPENV_EINVAL, "%s: NULL argument", who);
+    if (actor && (!act || !logp_old)) return fail(nullptr, DPENV_EINVAL, "%s: NULL argument", who);
+    if (actor && !(std::isfinite(clip) && clip >= 0.0f)) return fail(nullptr, DPENV_EINVAL, "%s: clip must be finite and >= 0", who);
+    if (!workspace) return fail(nullptr, DPENV_EINVAL, "%s: workspace is NULL (dpenv_train_workspace_bytes)", who);
+    if (reinterpret_cast<uintptr_t>(workspace) & 3u) return fail(nullptr, DPENV_EINVAL, "%s: workspace must be 4-byte aligned", who);
+    if (workspace_bytes < train_ws_bytes(a.L, count))
+        return fail(nullptr, DPENV_EINVAL, "%s: workspace of %lld bytes, count = %d needs %lld (dpenv_train_workspace_bytes)", who,
+                    (long long)workspace_bytes, count, (long long)train_ws_bytes(a.L, count));
+    a.theta = theta; a.obs = obs; a.act = act; a.adv = adv; a.logp_old = logp_old; a.idx = idx; a.stop_flag = stop_flag;
+    a.partial = (float*)workspace; a.grad_out = grad_out; a.count = count; a.leak = shape->leak; a.clip = clip;
+    HIP_TRY(nullptr, dev::launch_mlp_grad(&a, (hipStream_t)s));
+    return DPENV_OK;
+}
+
+extern "C" int dpenv_ppo_actor_grad(const dpenv_train_shape* shape, const float* theta, const float* obs, const float* act, const float* adv,
+                                    const float* logp_old, const int32_t* idx, int32_t count, int32_t n_rows, float clip,
+                                    const int32_t* stop_flag, float* grad_out, void* workspace, int64_t workspace_bytes, dpenv_stream s)
+{
+    return train_grad("dpenv_ppo_actor_grad", shape, 1, theta, obs, act, adv, logp_old, idx, count, n_rows, clip, stop_flag, grad_out, workspace,
+                      workspace_bytes, s);
+}
+
+extern "C" int dpenv_value_grad(const dpenv_train_shape* shape, const float* theta, const float* obs, const float* ret, const int32_t* idx,
+                                int32_t count, int32_t n_rows, float* grad_out, void* workspace, int64_t workspace_bytes, dpenv_stream s)
+{
+    return train_grad("dpenv_value_grad", shape, 0, theta, obs, nullptr, ret, nullptr, idx, count, n_rows, 0.0f, nullptr, grad_out, workspace,
+                      workspace_bytes, s);
+}
+
+extern "C" int dpenv_adam_step(float* theta, const float* grad, float* m, float* v, int32_t P, float lr, float beta1, float beta2, float eps,
+                               int32_t* step_counter, const float* gate_kl, float kl_limit, int32_t* stop_flag, dpenv_stream s)
+{
+    if (!theta || !grad || !m || !v || !step_counter) return fail(nullptr, DPENV_EINVAL, "dpenv_adam_step: NULL argument");
+    if (P < 1) return fail(nullptr, DPENV_EINVAL, "dpenv_adam_step: P = %d, must be >= 1", P);
+    if ((reinterpret_cast<uintptr_t>(theta) | reinterpret_cast<uintptr_t>(grad) | reinterpret_cast<uintptr_t>(m) | reinterpret_cast<uintptr_t>(v)) & 15u)
+        return fail(nullptr, DPENV_EINVAL, "dpenv_adam_step: theta, grad, m and v must be 16-byte aligned");
+    if (!std::isfinite(lr) || !(beta1 >= 0.0f && beta1 < 1.0f) || !(beta2 >= 0.0f && beta2 < 1.0f) || !(eps >= 0.0f) || !std::isfinite(eps))
+        return fail(nullptr, DPENV_EINVAL, "dpenv_adam_step: lr must be finite, beta1 and beta2 in [0, 1), eps finite and >= 0");
+    if (gate_kl && !stop_flag) return fail(nullptr, DPENV_EINVAL, "dpenv_adam_step: the gate (gate_kl) needs stop_flag");
+    if (gate_kl && std::isnan(kl_limit)) return fail(nullptr, DPENV_EINVAL, "dpenv_adam_step: kl_limit is NaN");
+    AdamArgs a = {};
+    a.theta = theta; a.grad = grad; a.m = m; a.v = v; a.P = P; a.lr = lr; a.beta1 = beta1; a.beta2 = beta2; a.eps = eps;
+    a.step_counter = step_counter; a.gate_kl = gate_kl; a.kl_limit = kl_limit; a.stop_flag = stop_flag;
+    HIP_TRY(nullptr, dev::launch_adam_step(&a, (hipStream_t)s));
     return DPENV_OK;
 }

@@ -90,6 +90,17 @@ def average_gradients(params, group=None):
         off += n
 
 
+def average_flat(flat, group=None):
+    """average_gradients for a gradient that already IS one flat tensor (ml4ca_amd.train.PPOUpdater's gradient-and-statistics buffer: the
+    gradient and the KL the device gate reads cross in the same SUM all-reduce, divided by the rank count).  In place; no-op on one rank."""
+    import torch.distributed as dist
+    if not (dist.is_available() and dist.is_initialized()) or dist.get_world_size(group) == 1:
+        return flat
+    dist.all_reduce(flat, group=group)
+    flat /= dist.get_world_size(group)
+    return flat
+
+
 def assert_params_in_step(params, group=None, what='parameters'):
     """Replicated updates (examples/train_ppo.py --exchange rollout: every rank computes the SAME update from the gathered batch, no
     gradient or parameter collective) stay replicated only while every rank's arithmetic is bit-identical.  One 16-byte all-reduce

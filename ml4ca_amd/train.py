@@ -1,0 +1,355 @@
+"""The PPO update on the device (include/dpenv.h, "The PPO update"): PPO-clip actor gradient, the critic's MSE gradient and a
+device-gated Adam step, so that the 80 + 80 gradient steps of an epoch (ppo.py:265-273) queue without a host round trip.
+
+``ppo_actor_grad`` / ``value_grad`` / ``adam_step`` bind the handle-free C entry points; ``PPOUpdater`` re-homes the tensors of a
+``policy.ActorCritic`` as views of two flat parameter vectors and runs the whole update.  The host statements of the same law -
+``ppo_actor_grad_ref`` / ``value_grad_ref`` (closed form, float64) and ``adam_step_ref`` (NumPy float32 in the header's operation
+order) - are what the tests hold the kernels to.  There is no fallback: without the library or a GPU the device functions raise.
+"""
+import ctypes as C
+import math
+
+import numpy as np
+
+from . import _lib
+
+HIDDEN = 80
+NSTAT_ACTOR, NSTAT_CRITIC = 4, 1          # pi_loss, approx_kl, clip_frac, mean_ratio | v_loss
+ROWS_PER_TILE, MAX_WORKGROUPS = 64, 256   # the gradient kernel's grid: min(ceil(count / 64), 256) workgroups
+
+
+def _torch():
+    import torch
+    return torch
+
+
+def grid(count):
+    """Workgroups the gradient kernel runs for `count` rows (a function of count alone: dpenv.h, DETERMINISM)."""
+    return min((int(count) + ROWS_PER_TILE - 1) // ROWS_PER_TILE, MAX_WORKGROUPS)
+
+
+def layout(in_dim, out_dim, actor):
+    """Offsets of the flat parameter vector: {'W': [...], 'b': [...], 'log_std': off or None, 'P': P, 'sizes': [...]}."""
+    sizes = [int(in_dim), HIDDEN, HIDDEN, HIDDEN, int(out_dim)]
+    W, b, o = [], [], 0
+    for i in range(4):
+        W.append(o)
+        o += sizes[i] * sizes[i + 1]
+        b.append(o)
+        o += sizes[i + 1]
+    ls = o if actor else None
+    if actor:
+        o += sizes[4]
+    return dict(W=W, b=b, log_std=ls, P=o, sizes=sizes)
+
+
+def flatten(Ws, bs, log_std=None):
+    """[W0 [in][out], b0, W1, b1, ...] (+ log_std) -> one flat vector of the same kind (torch tensor or NumPy array)."""
+    parts = []
+    for W, b in zip(Ws, bs):
+        parts += [W.reshape(-1), b.reshape(-1)]
+    if log_std is not None:
+        parts.append(log_std.reshape(-1))
+    if isinstance(parts[0], np.ndarray):
+        return np.concatenate(parts)
+    return _torch().cat(parts)
+
+
+def unflatten(theta, in_dim, out_dim, actor):
+    """Views of a flat vector: (Ws, bs, log_std or None)."""
+    L = layout(in_dim, out_dim, actor)
+    s = L['sizes']
+    Ws = [theta[L['W'][i]:L['W'][i] + s[i] * s[i + 1]].reshape(s[i], s[i + 1]) for i in range(4)]
+    bs = [theta[L['b'][i]:L['b'][i] + s[i + 1]] for i in range(4)]
+    return Ws, bs, (theta[L['log_std']:L['log_std'] + s[4]] if actor else None)
+
+
+def make_shape(in_dim, out_dim, actor, leak=0.2, activation='leaky', hidden=(HIDDEN, HIDDEN, HIDDEN), row_dtype=_lib.F32):
+    sh = _lib.TrainShape()
+    sh.struct_size = C.sizeof(_lib.TrainShape)
+    sizes = [int(in_dim)] + [int(h) for h in hidden] + [int(out_dim)]
+    if len(sizes) > 6:
+        raise ValueError('at most 5 dense layers')
+    sh.n_layers = len(sizes) - 1
+    for i, v in enumerate(sizes):
+        sh.sizes[i] = v
+    sh.activation = _lib.ACT_TANH if activation == 'tanh' else _lib.ACT_LEAKY_RELU
+    sh.leak = 0.0 if activation == 'relu' else float(leak)
+    sh.row_dtype = int(row_dtype)
+    sh.log_std = 1 if actor else 0
+    return sh
+
+
+def param_count(shape):
+    n = int(_lib.load().dpenv_train_param_count(C.byref(shape)))
+    if n < 0:
+        _lib.check(n)
+    return n
+
+
+def workspace_bytes(shape, max_count):
+    out = C.c_int64(0)
+    _lib.check(_lib.load().dpenv_train_workspace_bytes(C.byref(shape), int(max_count), C.byref(out)))
+    return int(out.value)
+
+
+def _p(t):
+    return None if t is None else C.c_void_p(t.data_ptr())
+
+
+def _s(t):
+    return C.c_void_p(_torch().cuda.current_stream(t.device).cuda_stream)
+
+
+def _req(t, shape, dtype, what):
+    if t is None:
+        return
+    if (shape is not None and tuple(t.shape) != tuple(shape)) or t.dtype != dtype or not t.is_contiguous() or not t.is_cuda:
+        raise ValueError('%s must be a contiguous cuda %s tensor%s' % (what, dtype, '' if shape is None else ' of shape %s' % (tuple(shape),)))
+
+
+def _grad_call(actor, theta, obs, act, adv, logp_old, clip, idx, out, workspace, leak, stop_flag, count):
+    torch = _torch()
+    f32 = torch.float32
+    n_rows, in_dim = obs.shape
+    out_dim = act.shape[1] if actor else 1
+    sh = make_shape(in_dim, out_dim, actor, leak=leak)
+    P = param_count(sh)
+    _req(theta, (P,), f32, 'theta')
+    _req(obs, (n_rows, in_dim), f32, 'obs')
+    _req(act, (n_rows, out_dim), f32, 'act')
+    _req(adv, (n_rows,), f32, 'adv' if actor else 'ret')
+    _req(logp_old, (n_rows,), f32, 'logp_old')
+    _req(idx, None, torch.int32, 'idx')
+    _req(stop_flag, (1,), torch.int32, 'stop_flag')
+    if count is None:
+        count = int(idx.numel()) if idx is not None else n_rows
+    if idx is not None and int(count) > idx.numel():
+        raise ValueError('count = %d, idx holds %d indices' % (count, idx.numel()))
+    nstat = NSTAT_ACTOR if actor else NSTAT_CRITIC
+    if out is None:
+        out = torch.empty(P + nstat, dtype=f32, device=theta.device)
+    _req(out, (P + nstat,), f32, 'out')
+    if workspace is None:
+        workspace = torch.empty((workspace_bytes(sh, max(count, 1)) + 3) // 4, dtype=f32, device=theta.device)
+    lib = _lib.load()
+    with torch.cuda.device(theta.device):
+        if actor:
+            _lib.check(lib.dpenv_ppo_actor_grad(C.byref(sh), _p(theta), _p(obs), _p(act), _p(adv), _p(logp_old), _p(idx), int(count), int(n_rows),
+                                                float(clip), _p(stop_flag), _p(out), _p(workspace), workspace.numel() * workspace.element_size(),
+                                                _s(theta)))
+        else:
+            _lib.check(lib.dpenv_value_grad(C.byref(sh), _p(theta), _p(obs), _p(adv), _p(idx), int(count), int(n_rows), _p(out), _p(workspace),
+                                            workspace.numel() * workspace.element_size(), _s(theta)))
+    return out
+
+
+def ppo_actor_grad(theta, obs, act, adv, logp_old, clip, idx=None, out=None, workspace=None, leak=0.2, stop_flag=None, count=None):
+    """dpenv_ppo_actor_grad: the PPO-clip gradient of the flat actor `theta` over rows `idx` (int32; None = all rows) of
+    obs [n, in] / act [n, out] / adv / logp_old [n].  Returns out [P + 4]: the gradient, then pi_loss, approx_kl, clip_frac, mean_ratio.
+    stop_flag: int32 [1]; a call that finds it set leaves `out` as it is.  Stream-ordered, nothing is read back."""
+    return _grad_call(True, theta, obs, act, adv, logp_old, clip, idx, out, workspace, leak, stop_flag, count)
+
+
+def value_grad(theta, obs, ret, idx=None, out=None, workspace=None, leak=0.2, count=None):
+    """dpenv_value_grad: the gradient of mean((ret - v)^2) for the flat critic `theta`.  Returns out [P + 1]: the gradient, then v_loss."""
+    return _grad_call(False, theta, obs, None, ret, None, 0.0, idx, out, workspace, leak, None, count)
+
+
+def adam_step(theta, grad, m, v, step_counter, lr, beta1=0.9, beta2=0.999, eps=1e-8, gate_kl=None, kl_limit=float('inf'), stop_flag=None):
+    """dpenv_adam_step: one torch.optim.Adam step of theta [P] with grad[:P] in place; step_counter int32 [1] counts the steps taken.
+    gate_kl (float32 [1], e.g. the approx_kl slot of the gradient buffer) with stop_flag (int32 [1]): if the flag is set or
+    gate_kl > kl_limit the flag is set and nothing else changes."""
+    torch = _torch()
+    P = theta.numel()
+    for t, what in ((theta, 'theta'), (m, 'm'), (v, 'v')):
+        _req(t, (P,), torch.float32, what)
+    if grad.numel() < P:
+        raise ValueError('grad has %d elements, theta %d' % (grad.numel(), P))
+    _req(grad, None, torch.float32, 'grad')
+    _req(step_counter, (1,), torch.int32, 'step_counter')
+    _req(gate_kl, (1,), torch.float32, 'gate_kl')
+    _req(stop_flag, (1,), torch.int32, 'stop_flag')
+    with torch.cuda.device(theta.device):
+        _lib.check(_lib.load().dpenv_adam_step(_p(theta), _p(grad), _p(m), _p(v), int(P), float(lr), float(beta1), float(beta2), float(eps),
+                                               _p(step_counter), _p(gate_kl), float(kl_limit), _p(stop_flag), _s(theta)))
+    return theta
+
+
+# ---- host statements of the law (NumPy) --------------------------------------------------------------------------------------------
+def _forward64(theta, obs, in_dim, out_dim, actor, leak):
+    Ws, bs, ls = unflatten(np.asarray(theta, np.float64), in_dim, out_dim, actor)
+    h, hs, zs = np.asarray(obs, np.float64), [], []
+    for i in range(3):
+        hs.append(h)
+        z = h @ Ws[i] + bs[i]
+        zs.append(z)
+        h = np.maximum(z, leak * z)
+    hs.append(h)
+    return Ws, bs, ls, hs, zs, h @ Ws[3] + bs[3]
+
+
+def _backward64(Ws, hs, zs, dout, leak, extra=None):
+    """dout = dL/d(output) [count, out] -> the flat gradient (extra: the log_std part)."""
+    gW, gb = [None] * 4, [None] * 4
+    g = dout
+    for i in (3, 2, 1, 0):
+        gW[i] = hs[i].T @ g
+        gb[i] = g.sum(0)
+        if i > 0:
+            g = (g @ Ws[i].T) * np.where(zs[i - 1] > 0, 1.0, leak)      # act'(z): 1 where z > 0, leak elsewhere (z = 0 included)
+    return flatten(gW, gb, extra)
+
+
+def ppo_actor_grad_ref(theta, obs, act, adv, logp_old, clip, leak=0.2, hidden_z=False):
+    """The header's actor law in closed form, float64: (grad [P], stats [4] = pi_loss, approx_kl, clip_frac, mean_ratio); with hidden_z
+    also the hidden pre-activations and the ratio (the tests' fixture conditions)."""
+    obs, act = np.asarray(obs, np.float64), np.asarray(act, np.float64)
+    A, lpo = np.asarray(adv, np.float64), np.asarray(logp_old, np.float64)
+    count, in_dim, out_dim = obs.shape[0], obs.shape[1], act.shape[1]
+    Ws, bs, ls, hs, zs, mu = _forward64(theta, obs, in_dim, out_dim, True, leak)
+    sd = np.exp(ls) + 1e-8
+    q = (act - mu) / sd
+    logp = (-0.5 * ((q * q + 2.0 * ls) + math.log(2.0 * math.pi))).sum(1)
+    ratio = np.exp(logp - lpo)
+    lo, hi = 1.0 - clip, 1.0 + clip
+    s1, s2 = ratio * A, np.minimum(np.maximum(ratio, lo), hi) * A
+    # THE RULE: the gradient flows where the unclipped term is the minimum; at a tie (A == 0, or lo <= ratio <= hi with the bounds included) it flows too
+    gl = np.where(s1 <= s2, -A * ratio, 0.0) / count
+    dmu = gl[:, None] * (q / sd)
+    dls = (gl[:, None] * (q * q * (np.exp(ls) / sd) - 1.0)).sum(0)
+    grad = _backward64(Ws, hs, zs, dmu, leak, dls)
+    stats = np.array([(-np.minimum(s1, s2)).mean(), (lpo - logp).mean(), ((ratio > hi) | (ratio < lo)).mean(), ratio.mean()])
+    if hidden_z:
+        return grad, stats, zs, ratio
+    return grad, stats
+
+
+def value_grad_ref(theta, obs, ret, leak=0.2):
+    """The critic's law in closed form, float64: (grad [P], stats [1] = v_loss)."""
+    obs, ret = np.asarray(obs, np.float64), np.asarray(ret, np.float64)
+    count = obs.shape[0]
+    Ws, bs, _, hs, zs, out = _forward64(theta, obs, obs.shape[1], 1, False, leak)
+    e = out[:, 0] - ret
+    return _backward64(Ws, hs, zs, (2.0 * e / count)[:, None], leak), np.array([(e * e).mean()])
+
+
+def _fma32(a, b, c):
+    """fmaf on float32 operands, correctly rounded: the product is exact in float64, the sum is rounded to ODD there (TwoSum gives the
+    rounding error), and a round-to-odd float64 rounds to float32 as the exact value would."""
+    a, b, c = (np.asarray(x, np.float32).astype(np.float64) for x in (a, b, c))
+    p = a * b
+    s = p + c
+    bb = s - p
+    err = (p - (s - bb)) + (c - bb)
+    s = np.atleast_1d(s).copy()
+    err = np.broadcast_to(np.atleast_1d(err), s.shape)
+    fix = (err != 0) & ((s.view(np.int64) & 1) == 0) & np.isfinite(s)
+    s[fix] = np.nextafter(s[fix], np.where(err[fix] > 0, np.inf, -np.inf))
+    return s.astype(np.float32)
+
+
+def _powi(b, e):
+    p, b = 1.0, float(b)
+    while e > 0:
+        if e & 1:
+            p *= b
+        b *= b
+        e >>= 1
+    return p
+
+
+def adam_step_ref(theta, grad, m, v, step, lr, beta1=0.9, beta2=0.999, eps=1e-8, gate_kl=None, kl_limit=float('inf'), stop=0):
+    """dpenv_adam_step in NumPy float32, operation by operation as include/dpenv.h writes it.  step: the steps taken so far.
+    Returns (theta, m, v, step, stop) after the call; with the gate closed (gate_kl given and (stop or gate_kl > kl_limit)) only stop changes."""
+    f = np.float32
+    theta, grad, m, v = (np.asarray(x, f) for x in (theta, grad, m, v))
+    if gate_kl is not None and (stop or f(gate_kl) > f(kl_limit)):
+        return theta.copy(), m.copy(), v.copy(), int(step), 1
+    t = int(step) + 1
+    b1, b2 = f(beta1), f(beta2)
+    step_size = f(lr) / f(1.0 - _powi(float(b1), t))
+    bc2s = np.sqrt(f(1.0 - _powi(float(b2), t)))
+    m2 = _fma32(f(1) - b1, grad - m, m)
+    v2 = _fma32((f(1) - b2) * grad, grad, b2 * v)
+    denom = np.sqrt(v2) / bc2s + f(eps)
+    theta2 = _fma32(-step_size, m2 / denom, theta)
+    return theta2, m2, v2, t, int(stop)
+
+
+# ---- the whole update ----------------------------------------------------------------------------------------------------------------
+class PPOUpdater(object):
+    """The update of ppo.py:265-273 on the device for a cuda ``ActorCritic`` (9 or 6 -> 80 -> 80 -> 80 -> 7 / 1, leaky-relu or relu).
+
+    The tensors of `ac` are re-homed as views of two flat vectors (``pi_theta`` [14 334], ``v_theta`` [13 841]), so ``ac.upload``,
+    ``state_dict`` and ``forward_ref`` keep working on the values the kernels update.  Owns Adam's m and v, the step counters, the
+    stop flag, the gradient buffers and the workspace."""
+
+    def __init__(self, ac, pi_lr=3e-4, v_lr=1e-3, clip=0.2, target_kl=0.01, betas=(0.9, 0.999), eps=1e-8):
+        torch = _torch()
+        if ac.activation == 'tanh':
+            raise ValueError('the fused update implements leaky-relu / relu networks (tanh is refused by the library)')
+        if tuple(ac.hidden_sizes) != (HIDDEN,) * 3:
+            raise ValueError('the fused update implements three hidden layers of 80 (got %r)' % (tuple(ac.hidden_sizes),))
+        if not all(p.is_cuda for p in ac.parameters()):
+            raise ValueError('the ActorCritic must live on the GPU: there is no CPU fallback')
+        self.ac, self.clip, self.target_kl = ac, float(clip), float(target_kl)
+        self.pi_lr, self.v_lr, self.betas, self.eps = float(pi_lr), float(v_lr), betas, float(eps)
+        dev = ac.log_std.device
+        self.device = dev
+        with torch.no_grad():
+            self.pi_theta = flatten(ac.pi_W, ac.pi_b, ac.log_std).detach().float().contiguous().clone()
+            self.v_theta = flatten(ac.v_W, ac.v_b).detach().float().contiguous().clone()
+        ac.pi_W, ac.pi_b, ac.log_std = unflatten(self.pi_theta, ac.obs_dim, ac.act_dim, True)
+        ac.v_W, ac.v_b, _ = unflatten(self.v_theta, ac.obs_dim, 1, False)
+        self.pi_shape = make_shape(ac.obs_dim, ac.act_dim, True, leak=ac.leak)
+        self.v_shape = make_shape(ac.obs_dim, 1, False, leak=ac.leak)
+        self.P_pi, self.P_v = param_count(self.pi_shape), param_count(self.v_shape)
+        assert self.P_pi == self.pi_theta.numel() and self.P_v == self.v_theta.numel()
+        z = lambda n, dt=torch.float32: torch.zeros(n, dtype=dt, device=dev)
+        self.pi_m, self.pi_v, self.v_m, self.v_v = z(self.P_pi), z(self.P_pi), z(self.P_v), z(self.P_v)
+        self.pi_grad, self.v_grad = z(self.P_pi + NSTAT_ACTOR), z(self.P_v + NSTAT_CRITIC)
+        self.pi_steps, self.v_steps, self.stop = z(1, torch.int32), z(1, torch.int32), z(1, torch.int32)
+        self._pi_steps_host = 0
+        self._ws, self._out = None, z(3, torch.float64)
+
+    def _workspace(self, count):
+        need = max(workspace_bytes(self.pi_shape, count), workspace_bytes(self.v_shape, count))
+        if self._ws is None or self._ws.numel() * 4 < need:
+            self._ws = _torch().empty((need + 3) // 4, dtype=_torch().float32, device=self.device)
+        return self._ws
+
+    def update(self, obs, act, adv, ret, logp_old, iters=80, minibatch=None, average=None):
+        """Queue `iters` actor steps (gated on approx_kl > 1.5 target_kl, ppo.py:267-270) and `iters` critic steps, then read
+        (pi_iters, kl, v_loss) back ONCE.  obs [N, od], act [N, ad], adv / ret / logp_old [N], float32 on the device.
+        minibatch: rows per gradient step, drawn with torch.randint as the torch loop draws them (None or >= N: every row).
+        average: callable applied in place to the flat [P + nstat] gradient-and-statistics buffer between gradient and Adam
+        (a multi-rank caller's all-reduce)."""
+        torch = _torch()
+        N = obs.shape[0]
+        mb = N if minibatch is None else min(int(minibatch), N)
+        ws = self._workspace(mb)
+        b1, b2 = self.betas
+        kl_slot = self.pi_grad[self.P_pi + 1:self.P_pi + 2]
+        self.stop.zero_()
+        for _ in range(iters):
+            idx = torch.randint(0, N, (mb,), device=self.device).to(torch.int32) if mb < N else None
+            ppo_actor_grad(self.pi_theta, obs, act, adv, logp_old, self.clip, idx=idx, out=self.pi_grad, workspace=ws, leak=self.ac.leak,
+                           stop_flag=self.stop, count=mb)
+            if average is not None:
+                average(self.pi_grad)
+            adam_step(self.pi_theta, self.pi_grad, self.pi_m, self.pi_v, self.pi_steps, self.pi_lr, b1, b2, self.eps, gate_kl=kl_slot,
+                      kl_limit=1.5 * self.target_kl, stop_flag=self.stop)
+        for _ in range(iters):
+            idx = torch.randint(0, N, (mb,), device=self.device).to(torch.int32) if mb < N else None
+            value_grad(self.v_theta, obs, ret, idx=idx, out=self.v_grad, workspace=ws, leak=self.ac.leak, count=mb)
+            if average is not None:
+                average(self.v_grad)
+            adam_step(self.v_theta, self.v_grad, self.v_m, self.v_v, self.v_steps, self.v_lr, b1, b2, self.eps)
+        self._out[0] = self.pi_steps[0]
+        self._out[1] = self.pi_grad[self.P_pi + 1]
+        self._out[2] = self.v_grad[self.P_v]
+        steps, kl, v_loss = self._out.tolist()                         # the one read
+        pi_iters = int(steps) - self._pi_steps_host
+        self._pi_steps_host = int(steps)
+        return pi_iters, kl, v_loss

@@ -12,6 +12,8 @@ env.step, critic, trajectory rows), GAE by one scan kernel, advantage statistics
 
     python examples/train_ppo.py --envs 4096 --epochs 30
     python examples/train_ppo.py --envs 4096 --epochs 30 --update fused
+    python examples/train_ppo.py --envs 4096 --epochs 30 --update fused --warm-start 300 --eval      clone the PID + pseudo-inverse baseline into the
+                                                                                      actor first (PPOUpdater.pretrain on one controller_rollout), then PPO
     python examples/train_ppo.py --envs 4096 --epochs 40 --randomise 0.15 --eval      domain randomisation: every episode of every env
                                                                                       runs on its own hull, +-15 % on all 26 parameters, re-drawn by the reset path
                                                                                       inside the rollout launch; --eval: the reference's evaluation harness
@@ -31,7 +33,7 @@ from ml4ca_amd import rollout
 from ml4ca_amd.policy import ActorCritic
 
 
-def evaluate_actor(ac, dev, preset, precision, seed, out=print, eval_envs=1024):
+def evaluate_actor(ac, dev, preset, precision, seed, out=print, eval_envs=1024, only=None):
     """The trained actor on the NOMINAL hull (and on a spread of hulls): the reference's run_RL_policy (spinup/utils/test_policy.py:97-186: six
     fixed starts, deterministic policy) and the thesis' 4-corner box test with its two metrics - IAE (results/all_plots/common.py:60-74) and
     the energy-equivalent work of the thruster power model (box_test/plot_act.py:128-135,184-211)."""
@@ -50,6 +52,8 @@ def evaluate_actor(ac, dev, preset, precision, seed, out=print, eval_envs=1024):
     # of currents around it: +-0.1 m/s, +-90 deg, one draw per env)
     for tag, spread, cur in (('nominal hull', 0.0, None), ('hulls +-15 %', 0.15, None), ('hulls +-30 %', 0.30, None), ('hulls +-50 %', 0.50, None),
                              ('current 0.2 m/s @ 135 deg', 0.0, (0.0, 0.0)), ('currents 0.2 +-0.1 m/s, 135 +-90 deg', 0.0, (0.1, 1.5708))):
+        if only is not None and tag not in only:
+            continue
         def make_env():
             env = ml4ca_amd.BatchedRevoltEnv(nb, device=dev, terminate=False, time_limit=False, seed=seed + 77, vessel_params=nominal, current=cur is not None)
             if spread > 0:
@@ -137,6 +141,36 @@ def tune_baseline(ac, dev, preset, precision, K, seed=0, out=print, directions=1
     return {'mean_iae': iae.tolist(), 'mean_work': work.tolist(), 'front': [int(k) for k in sw['front']], 'actor': {'IAE': a_iae, 'work': a_work.tolist()}}
 
 
+def warm_start(upd, env, args, out=print):
+    """--warm-start: clone the classical baseline into the actor before epoch 0.  The baseline (PID + pseudo-inverse with the pole-placement
+    defaults of the nominal hull) flies the training envs for --warm-start-steps steps in one launch; its obs / act rows are the
+    demonstration PPOUpdater.pretrain fits the actor to, and their discounted returns what pretrain_critic fits the critic to.  The
+    actor is memoryless: it sees o, not the PID's integral z, so in a current the clone holds station with an offset unless it is flown
+    with env.set_integral_action().
+    Several ranks: every rank flies its own envs and draws its own minibatches, exactly as in the PPO epochs with --exchange gradients, and
+    every step's gradient-and-statistics buffer is averaged across the ranks (dist.average_flat) before its Adam step, whatever --exchange
+    says: the replicas take the same steps and enter PPO with the same parameters (checked once, dist.assert_params_in_step)."""
+    from ml4ca_amd.deploy import dp_controller_defaults
+    from ml4ca_amd.policy import controller_rollout
+    T = args.warm_start_steps or args.steps
+    env.set_dp_controller(dp_controller_defaults(ml4ca_amd.default_vessel(args.preset)))
+    env.reset()
+    o = controller_rollout(env, T)
+    _, ret = rollout.gae(o['rew'], torch.zeros_like(o['rew']), end=o['done'], gamma=0.99, lam=0.97)      # rewards-to-go (ppo.py:88)
+    obs, act, ret = o['obs'].reshape(-1, 9).float().contiguous(), o['act'].reshape(-1, 7), ret.reshape(-1)
+    mb = min(args.minibatch, obs.shape[0])
+    t0 = time.perf_counter()
+    h = upd.pretrain(obs, act, args.warm_start, minibatch=mb, loss=args.warm_start_loss, average=D.average_flat)      # (a no-op on one rank)
+    hv = upd.pretrain_critic(obs, ret, args.warm_start, minibatch=mb, average=D.average_flat)
+    torch.cuda.synchronize()
+    D.assert_params_in_step(list(upd.ac.parameters()), what='warm-started parameters')
+    env.set_dp_controller(off=True)
+    out('warm start: %d rows of the baseline (reward/step %.3f), %d %s steps + as many critic steps in %.2f s: MSE %.4g -> %.4g  NLL %.4g -> %.4g  V-loss %.4g -> %.4g' % (
+        obs.shape[0], float(o['rew'].mean()), args.warm_start, args.warm_start_loss, time.perf_counter() - t0,
+        float(h[0, 2]), float(h[-1, 2]), float(h[0, 1]), float(h[-1, 1]), float(hv[0, 0]), float(hv[-1, 0])))
+    return h, hv
+
+
 def torch_update(ac, pi_opt, v_opt, pi_params, v_params, obs, act, adv, ret, logp_old, mb, clip=0.2, target_kl=0.01, gather=False, iters=80):
     """The update of ppo.py:265-273 through torch autograd and torch.optim.Adam (--update torch): the baseline the fused update
     (ml4ca_amd.train.PPOUpdater, --update fused) is held to and timed against.  Returns (pi_iters, kl, v_loss)."""
@@ -184,6 +218,14 @@ def main():
     ap.add_argument('--update', default='torch', choices=('torch', 'fused'),
                     help="the 80 + 80 gradient steps: 'torch' = autograd + torch.optim.Adam (torch_update below); 'fused' = the library's gradient and "
                          'gated-Adam kernels (ml4ca_amd.train.PPOUpdater): the whole update queues without a host round trip, one read at the end')
+    ap.add_argument('--warm-start', type=int, default=0, metavar='ITERS',
+                    help='with --update fused: before epoch 0 fly the baseline DP controller (PID + pseudo-inverse) on the training envs, fit the actor to '
+                         'its obs -> act rows for ITERS gradient steps (ml4ca_amd.train.PPOUpdater.pretrain) and the critic to their discounted returns, '
+                         'reset Adam, and let PPO fine-tune from there.  The actor is memoryless: it sees o, not the PID\'s integral z, so in a current '
+                         'the clone holds station with an offset unless it is flown with env.set_integral_action()')
+    ap.add_argument('--warm-start-loss', default='mse', choices=('mse', 'nll'), help="the imitation loss: 'mse' on the mean action, or the Gaussian 'nll' "
+                                                                                       '(which also fits log_std)')
+    ap.add_argument('--warm-start-steps', type=int, default=0, metavar='T', help='steps of the demonstration flight (default: one episode, --steps)')
     ap.add_argument('--exchange', default='gradients', choices=('gradients', 'rollout'),
                     help="multi-rank runs: 'gradients' = every rank updates on ITS OWN episode and the gradients are averaged, exactly the "
                          "reference (ppo.py:226, mpi_tf.py:29-62: no trajectory ever crosses); 'rollout' = BASELINE.json config 4: the ranks "
@@ -213,6 +255,8 @@ def main():
     ap.add_argument('--backend', default='nccl', help="'nccl' (RCCL, one GPU per rank) or 'gloo' (rehearsal)")
     ap.add_argument('--same-device', action='store_true', help='all ranks on cuda:0 (multi-rank rehearsal on a one-GPU box)')
     args = ap.parse_args()
+    if args.warm_start > 0 and args.update != 'fused':
+        ap.error('--warm-start needs --update fused (the imitation gradient is a kernel of the fused update)')
     # one process per GPU under torch.distributed.run (backend nccl = RCCL); envs shard by global id, gradients average
     rank, world, local = int(os.environ.get('RANK', 0)), int(os.environ.get('WORLD_SIZE', 1)), int(os.environ.get('LOCAL_RANK', 0))
     dev = torch.device('cuda', 0 if args.same_device else local)
@@ -252,6 +296,13 @@ def main():
     pi_opt = torch.optim.Adam(pi_params, lr=3e-4) if upd is None else None
     v_opt = torch.optim.Adam(v_params, lr=1e-3) if upd is None else None
     buf = rollout.RolloutBuffer(T, env, gamma=0.99, lam=0.97)
+    if args.warm_start > 0:
+        warm_start(upd, env, args, out=print if rank == 0 else (lambda *a: None))
+        with torch.no_grad():
+            ac.log_std.clamp_(-4.0, 1.0)
+        if args.eval and rank == 0:
+            print('eval of the cloned actor, before any PPO epoch')
+            evaluate_actor(ac, dev, args.preset, 'f32', args.seed, eval_envs=args.eval_envs, only=('nominal hull',))
     ac.upload(env, precision=args.precision)          # device pointers: one packing kernel, no host copy
     env.reset()
     gather = world > 1 and args.exchange == 'rollout'

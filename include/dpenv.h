@@ -776,6 +776,29 @@ int dpenv_ppo_actor_grad(const dpenv_train_shape* shape, const float* theta, con
 /* grad_out: device float[P + 1]. */
 int dpenv_value_grad(const dpenv_train_shape* shape, const float* theta, const float* obs, const float* ret, const int32_t* idx,
                      int32_t count, int32_t n_rows, float* grad_out, void* workspace, int64_t workspace_bytes, dpenv_stream s);
+/* IMITATION LOSS: the supervised gradient of the actor on demonstration rows (obs [n_rows][in], act [n_rows][out]), e.g. the obs / act
+ * blocks of dpenv_controller_rollout, with an optional weight per row.  weight: device float[n_rows] or NULL = 1; w_i = weight ?
+ * weight[row_i] : 1.  weight = advantage is the vanilla policy gradient, 0 masks a row, exp(A / beta) is advantage-weighted regression.
+ * shape must be an actor's (log_std = 1); idx, count, n_rows, stop_flag, the workspace (dpenv_train_workspace_bytes) and the first-call
+ * rule are dpenv_ppo_actor_grad's, and so are ARITHMETIC and DETERMINISM above: the same kernel body with another per-row stage.
+ * Per row, with sd_j, q_j and logp as in ACTOR LOSS and sums over the out action components in j order:
+ *     e_j = mu_j - act_j          se = sum_j e_j^2
+ * DPENV_IMITATE_NLL.  L = -(1/count) sum_i w_i logp_i
+ *     dL/dmu_j      = -w_i (q_j / sd_j) / count
+ *     dL/dlog_std_j = -w_i (q_j^2 exp(log_std_j) / sd_j - 1) / count
+ * DPENV_IMITATE_MSE.  L = (1/count) sum_i w_i se_i
+ *     dL/dmu_j      = (2 w_i) e_j / count
+ *     the log_std part of the gradient is +0.0, as bits
+ * STATISTICS, grad_out[P .. P+3]:  the chosen L,  the weighted NLL (1/count) sum_i w_i (-logp_i),  the weighted MSE (1/count) sum_i w_i se_i
+ * (both whichever loss is chosen),  +0.0 (reserved).  The buffer is the actor's float[P + 4].
+ * The divisor is count, not sum(w).  A zero-weight row contributes exactly zero; its obs and act must still be finite.
+ * Refused with DPENV_EINVAL, launching and touching nothing: an unknown loss, a critic shape, and everything dpenv_ppo_actor_grad
+ * refuses for the corresponding arguments. */
+#define DPENV_IMITATE_NLL 0
+#define DPENV_IMITATE_MSE 1
+int dpenv_imitation_grad(const dpenv_train_shape* shape, const float* theta, const float* obs, const float* act, const float* weight,
+                         const int32_t* idx, int32_t count, int32_t n_rows, int32_t loss, const int32_t* stop_flag, float* grad_out,
+                         void* workspace, int64_t workspace_bytes, dpenv_stream s);
 /* ADAM, torch.optim.Adam's update (bias correction and eps placement included; not TF's variant).  theta, grad, m, v: device float[P],
  * 16-byte aligned.  step_counter: device int32, the steps taken so far.  With t = *step_counter + 1, every operation in f32 and
  * correctly rounded unless marked f64:

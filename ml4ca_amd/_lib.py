@@ -16,6 +16,7 @@ AOS, SOA = 0, 1
 WRAP_REFERENCE, WRAP_RADIANS = 0, 1
 F32, BF16 = 0, 1
 ACT_LEAKY_RELU, ACT_TANH = 0, 1
+IMITATE_NLL, IMITATE_MSE = 0, 1
 POLICY_F16, POLICY_F32, POLICY_F32_ACTOR = 0, 1, 2
 LAUNCH_AUTO, LAUNCH_ONE_WAVE, LAUNCH_TWO_WAVE = 0, 1, 2
 DONE_TERMINAL, DONE_TIMELIMIT, DONE_FAULT = 1, 2, 4
@@ -186,6 +187,7 @@ SYMBOLS = {
     'dpenv_train_workspace_bytes': (C.c_int, [C.POINTER(TrainShape), _I32, C.POINTER(C.c_int64)]),
     'dpenv_ppo_actor_grad': (C.c_int, [C.POINTER(TrainShape), _VP, _VP, _VP, _VP, _VP, _VP, _I32, _I32, _F, _VP, _VP, _VP, _I64, _VP]),
     'dpenv_value_grad': (C.c_int, [C.POINTER(TrainShape), _VP, _VP, _VP, _VP, _I32, _I32, _VP, _VP, _I64, _VP]),
+    'dpenv_imitation_grad': (C.c_int, [C.POINTER(TrainShape), _VP, _VP, _VP, _VP, _VP, _I32, _I32, _I32, _VP, _VP, _VP, _I64, _VP]),
     'dpenv_adam_step': (C.c_int, [_VP, _VP, _VP, _VP, _I32, _F, _F, _F, _F, _VP, _VP, _F, _VP, _VP]),
 }
 

@@ -475,6 +475,22 @@ extern "C" int dpenv_train_workspace_bytes(const dpenv_train_shape* shape, int32
     return DPENV_OK;
 }
 
+// what every gradient entry point asks of its row selection and its workspace: the one statement of the limits
+static int train_rows_check(const char* who, const TrainLayout& L, const int32_t* idx, int32_t count, int32_t n_rows, const void* workspace,
+                            int64_t workspace_bytes)
+{
+    if (count <= 0) return fail(nullptr, DPENV_EINVAL, "%s: count = %d, must be >= 1", who, count);
+    if (count > TR_MAX_COUNT) return fail(nullptr, DPENV_EINVAL, "%s: count = %d, at most %d rows per call", who, count, TR_MAX_COUNT);
+    if (n_rows <= 0) return fail(nullptr, DPENV_EINVAL, "%s: n_rows = %d, must be >= 1", who, n_rows);
+    if (!idx && n_rows < count) return fail(nullptr, DPENV_EINVAL, "%s: without idx the rows are 0 .. count-1: n_rows = %d < count = %d", who, n_rows, count);
+    if (!workspace) return fail(nullptr, DPENV_EINVAL, "%s: workspace is NULL (dpenv_train_workspace_bytes)", who);
+    if (reinterpret_cast<uintptr_t>(workspace) & 3u) return fail(nullptr, DPENV_EINVAL, "%s: workspace must be 4-byte aligned", who);
+    if (workspace_bytes < train_ws_bytes(L, count))
+        return fail(nullptr, DPENV_EINVAL, "%s: workspace of %lld bytes, count = %d needs %lld (dpenv_train_workspace_bytes)", who,
+                    (long long)workspace_bytes, count, (long long)train_ws_bytes(L, count));
+    return DPENV_OK;
+}
+
 static int train_grad(const char* who, const dpenv_train_shape* shape, int actor, const float* theta, const float* obs, const float* act,
                       const float* adv, const float* logp_old, const int32_t* idx, int32_t count, int32_t n_rows, float clip,
                       const int32_t* stop_flag, float* grad_out, void* workspace, int64_t workspace_bytes, dpenv_stream s)
@@ -482,21 +498,13 @@ static int train_grad(const char* who, const dpenv_train_shape* shape, int actor
     GradArgs a = {};
     if (const char* why = train_shape_check(shape, &a.L)) return fail(nullptr, DPENV_EINVAL, "%s: %s", who, why);
     if (a.L.actor != actor) return fail(nullptr, DPENV_EINVAL, "%s: the shape's log_std = %d is the other network's", who, a.L.actor);
-    if (count <= 0) return fail(nullptr, DPENV_EINVAL, "%s: count = %d, must be >= 1", who, count);
-    if (count > TR_MAX_COUNT) return fail(nullptr, DPENV_EINVAL, "%s: count = %d, at most %d rows per call", who, count, TR_MAX_COUNT);
-    if (n_rows <= 0) return fail(nullptr, DPENV_EINVAL, "%s: n_rows = %d, must be >= 1", who, n_rows);
-    if (!idx && n_rows < count) return fail(nullptr, DPENV_EINVAL, "%s: without idx the rows are 0 .. count-1: n_rows = %d < count = %d", who, n_rows, count);
+    if (int rc = train_rows_check(who, a.L, idx, count, n_rows, workspace, workspace_bytes)) return rc;
     if (!theta || !obs || !adv || !grad_out) return fail(nullptr, DPENV_EINVAL, "%s: NULL argument", who);
     if (actor && (!act || !logp_old)) return fail(nullptr, DPENV_EINVAL, "%s: NULL argument", who);
     if (actor && !(std::isfinite(clip) && clip >= 0.0f)) return fail(nullptr, DPENV_EINVAL, "%s: clip must be finite and >= 0", who);
-    if (!workspace) return fail(nullptr, DPENV_EINVAL, "%s: workspace is NULL (dpenv_train_workspace_bytes)", who);
-    if (reinterpret_cast<uintptr_t>(workspace) & 3u) return fail(nullptr, DPENV_EINVAL, "%s: workspace must be 4-byte aligned", who);
-    if (workspace_bytes < train_ws_bytes(a.L, count))
-        return fail(nullptr, DPENV_EINVAL, "%s: workspace of %lld bytes, count = %d needs %lld (dpenv_train_workspace_bytes)", who,
-                    (long long)workspace_bytes, count, (long long)train_ws_bytes(a.L, count));
     a.theta = theta; a.obs = obs; a.act = act; a.adv = adv; a.logp_old = logp_old; a.idx = idx; a.stop_flag = stop_flag;
     a.partial = (float*)workspace; a.grad_out = grad_out; a.count = count; a.leak = shape->leak; a.clip = clip;
-    HIP_TRY(nullptr, dev::launch_mlp_grad(&a, (hipStream_t)s));
+    HIP_TRY(nullptr, dev::launch_mlp_grad(&a, actor ? TR_STAGE_PPO : TR_STAGE_VALUE, (hipStream_t)s));
     return DPENV_OK;
 }
 
@@ -513,6 +521,28 @@ extern "C" int dpenv_value_grad(const dpenv_train_shape* shape, const float* the
 {
     return train_grad("dpenv_value_grad", shape, 0, theta, obs, nullptr, ret, nullptr, idx, count, n_rows, 0.0f, nullptr, grad_out, workspace,
                       workspace_bytes, s);
+}
+
+// the weighted imitation loss (dpenv.h, IMITATION LOSS): dpenv_ppo_actor_grad's conventions, every refusal naming its argument
+extern "C" int dpenv_imitation_grad(const dpenv_train_shape* shape, const float* theta, const float* obs, const float* act, const float* weight,
+                                    const int32_t* idx, int32_t count, int32_t n_rows, int32_t loss, const int32_t* stop_flag, float* grad_out,
+                                    void* workspace, int64_t workspace_bytes, dpenv_stream s)
+{
+    const char* who = "dpenv_imitation_grad";
+    GradArgs a = {};
+    if (const char* why = train_shape_check(shape, &a.L)) return fail(nullptr, DPENV_EINVAL, "%s: %s", who, why);
+    if (!a.L.actor) return fail(nullptr, DPENV_EINVAL, "%s: the shape's log_std = 0 is a critic's; the imitation loss is the actor's", who);
+    if (loss != DPENV_IMITATE_NLL && loss != DPENV_IMITATE_MSE)
+        return fail(nullptr, DPENV_EINVAL, "%s: loss = %d, must be DPENV_IMITATE_NLL (0) or DPENV_IMITATE_MSE (1)", who, loss);
+    if (int rc = train_rows_check(who, a.L, idx, count, n_rows, workspace, workspace_bytes)) return rc;
+    if (!theta) return fail(nullptr, DPENV_EINVAL, "%s: theta is NULL", who);
+    if (!obs) return fail(nullptr, DPENV_EINVAL, "%s: obs is NULL", who);
+    if (!act) return fail(nullptr, DPENV_EINVAL, "%s: act is NULL", who);
+    if (!grad_out) return fail(nullptr, DPENV_EINVAL, "%s: grad_out is NULL", who);
+    a.theta = theta; a.obs = obs; a.act = act; a.adv = weight; a.logp_old = nullptr; a.idx = idx; a.stop_flag = stop_flag;
+    a.partial = (float*)workspace; a.grad_out = grad_out; a.count = count; a.leak = shape->leak; a.clip = 0.0f;
+    HIP_TRY(nullptr, dev::launch_mlp_grad(&a, loss == DPENV_IMITATE_NLL ? TR_STAGE_IMIT_NLL : TR_STAGE_IMIT_MSE, (hipStream_t)s));
+    return DPENV_OK;
 }
 
 extern "C" int dpenv_adam_step(float* theta, const float* grad, float* m, float* v, int32_t P, float lr, float beta1, float beta2, float eps,

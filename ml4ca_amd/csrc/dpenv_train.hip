@@ -1,6 +1,8 @@
 // dpenv_train.hip - the PPO update on the device (include/dpenv.h: "The PPO update"): mlp_grad_kernel<ACTOR> (forward, output gradient,
 // backward and the weight gradients of one in -> 80 -> 80 -> 80 -> out network on the matrix cores, one partial per workgroup),
 // grad_reduce_kernel (the partials summed in a fixed order) and the gated Adam step (adam_step_kernel + adam_commit_kernel).
+// imitation_grad_kernel<LOSS> (dpenv_imitation_grad) is the same body with a third per-row output stage: dpenv_train_grad_body.inc is
+// the one text of all four kernels, the stage chosen at compile time.
 //
 // Arithmetic: the exact-f32 MFMA v_mfma_f32_16x16x4_f32 (bit for bit a k-ordered fmaf chain).  80 = 5 x 16, so the hidden layers tile
 // without padding; the 9- or 6-wide input and the 7- or 1-wide output are padded to one 16-wide tile with zeros.  No operand split, no
@@ -43,7 +45,7 @@ constexpr int O_H3 = O_H2 + TR_ROWS * LDH;
 constexpr int O_D = O_H3 + TR_ROWS * LDH;            // [64][LDD]: the network's output, then its gradient (actor: d/dmu | d/dlog_std)
 constexpr int O_ST = O_D + TR_ROWS * LDD;            // [64][4] per-row statistics
 constexpr int O_A = O_ST + TR_ROWS * 4;              // [64][8] the rows' actions (actor)
-constexpr int O_AUX = O_A + TR_ROWS * 8;             // [64][2] advantage | logp_old (actor), return (critic)
+constexpr int O_AUX = O_A + TR_ROWS * 8;             // [64][2] advantage | logp_old (actor), return (critic), weight (imitation)
 constexpr int LDS_FLOATS = O_AUX + TR_ROWS * 2;
 static_assert(LDS_FLOATS * 4 <= 160 * 1024, "the tile does not fit the CU's LDS");
 
@@ -153,180 +155,19 @@ __device__ __forceinline__ float column_sum(const float* p, int ld)
     return s;
 }
 
-template <bool ACTOR>
+template <bool ACTOR_NET>
 __global__ __launch_bounds__(256) void mlp_grad_kernel(GradArgs a)
 {
-    extern __shared__ float lds[];
-    if (a.stop_flag && *a.stop_flag) return;                  // the gate has closed: the update is over (uniform over the grid)
-    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int lr = lane & 15, lk = lane >> 4;
-    const TrainLayout& L = a.L;
-    const int in = L.in_dim, od = L.out_dim;
-    constexpr int NSTAT = ACTOR ? TR_NSTAT_ACTOR : TR_NSTAT_CRITIC;
+    constexpr int STAGE = ACTOR_NET ? TR_STAGE_PPO : TR_STAGE_VALUE;
+#include "dpenv_train_grad_body.inc"
+}
 
-    // ---- the parameters, once per workgroup ----
-    for (int e = tid; e < TR_PAD * TR_H; e += 256) {
-        const int k = e / TR_H;
-        lds[O_W0 + e] = k < in ? a.theta[L.w[0] + e] : 0.0f;
-    }
-    for (int e = tid; e < TR_H * TR_H; e += 256) {
-        const int k = e / TR_H, j = e - k * TR_H;
-        lds[O_W1 + k * LDW + j] = a.theta[L.w[1] + e];
-        lds[O_W2 + k * LDW + j] = a.theta[L.w[2] + e];
-    }
-    for (int e = tid; e < TR_H * TR_PAD; e += 256) {
-        const int k = e >> 4, j = e & 15;
-        lds[O_W3 + k * LDW3 + j] = j < od ? a.theta[L.w[3] + k * od + j] : 0.0f;
-    }
-    if (tid < TR_H) {
-        lds[O_B + tid] = a.theta[L.b[0] + tid];
-        lds[O_B + TR_H + tid] = a.theta[L.b[1] + tid];
-        lds[O_B + 2 * TR_H + tid] = a.theta[L.b[2] + tid];
-    }
-    if (tid < TR_PAD) {
-        lds[O_B + 3 * TR_H + tid] = tid < od ? a.theta[L.b[3] + tid] : 0.0f;
-        if (ACTOR) {
-            const float ls = tid < od ? a.theta[L.ls + tid] : 0.0f;
-            const float es = expf(ls);
-            lds[O_LS + tid] = ls;
-            lds[O_LS + TR_PAD + tid] = es + 1e-8f;
-            lds[O_LS + 2 * TR_PAD + tid] = es;
-        }
-    }
-
-    f4 dw[15];
-#pragma unroll
-    for (int s = 0; s < 15; ++s) dw[s] = f4{0.0f, 0.0f, 0.0f, 0.0f};
-    float db0 = 0.0f, db1 = 0.0f, db2 = 0.0f, db3 = 0.0f;
-    double stat = 0.0;
-    const float lo = (float)(1.0 - (double)a.clip), hi = (float)(1.0 + (double)a.clip);
-    const int tiles = (a.count + TR_ROWS - 1) / TR_ROWS;
-    const int r0 = wave * 16;
-
-    for (int tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
-        const int base = tile * TR_ROWS;
-        __syncthreads();                                       // the previous tile's last readers are done (and the parameters are in)
-        {   // the tile's inputs, gathered; rows past count and columns past in_dim are zero
-            const int row = tid >> 2, part = tid & 3, g = base + row;
-            const bool ok = g < a.count;
-            const int64_t src = ok ? (a.idx ? (int64_t)a.idx[g] : (int64_t)g) : 0;
-#pragma unroll
-            for (int c = part; c < TR_PAD; c += 4) lds[O_X + row * LDX + c] = (ok && c < in) ? a.obs[src * in + c] : 0.0f;
-            // what the output gradient needs of the row, fetched in the same burst
-            if (ACTOR) {
-#pragma unroll
-                for (int c = part; c < 8; c += 4) lds[O_A + row * 8 + c] = (ok && c < od) ? a.act[src * od + c] : 0.0f;
-                if (part == 1) lds[O_AUX + row * 2 + 1] = ok ? a.logp_old[src] : 0.0f;
-            }
-            if (part == 0) lds[O_AUX + row * 2] = ok ? a.adv[src] : 0.0f;
-        }
-        __syncthreads();
-        // ---- forward: the wave's 16 rows ----
-        layer_forward<TR_PAD / 4>(lds + O_X + r0 * LDX, LDX, lds + O_W0, TR_H, lds + O_B, lds + O_H1 + r0 * LDH, a.leak, lane);
-        __syncthreads();
-        layer_forward<TR_H / 4>(lds + O_H1 + r0 * LDH, LDH, lds + O_W1, LDW, lds + O_B + TR_H, lds + O_H2 + r0 * LDH, a.leak, lane);
-        __syncthreads();
-        layer_forward<TR_H / 4>(lds + O_H2 + r0 * LDH, LDH, lds + O_W2, LDW, lds + O_B + 2 * TR_H, lds + O_H3 + r0 * LDH, a.leak, lane);
-        __syncthreads();
-        {
-            const float b = lds[O_B + 3 * TR_H + lr];
-            f4 o[1] = {f4{b, b, b, b}};
-            gemm_rows<TR_H / 4, 1, false>(lds + O_H3 + r0 * LDH, LDH, lds + O_W3, LDW3, o, lane);
-#pragma unroll
-            for (int r = 0; r < 4; ++r) lds[O_D + (r0 + 4 * lk + r) * LDD + lr] = o[0][r];
-        }
-        __syncthreads();
-        // ---- the output gradient, one lane per row, times count (the reduction divides) ----
-        if (lane < 16) {
-            const int row = r0 + lane, g = base + row;
-            float* d = lds + O_D + row * LDD;
-            float* st = lds + O_ST + row * 4;
-            if (g < a.count) {
-                const float* ra = lds + O_A + row * 8;
-                if (ACTOR) {
-                    float logp = 0.0f;
-                    for (int j = 0; j < od; ++j) {
-                        const float q = (ra[j] - d[j]) / lds[O_LS + TR_PAD + j];
-                        logp += -0.5f * ((q * q + 2.0f * lds[O_LS + j]) + 1.8378770664093453f);
-                    }
-                    const float lpo = lds[O_AUX + row * 2 + 1], A = lds[O_AUX + row * 2];
-                    const float ratio = expf(logp - lpo);
-                    const float s1 = ratio * A, s2 = fminf(fmaxf(ratio, lo), hi) * A;
-                    const float gl = s1 <= s2 ? -(A * ratio) : 0.0f;       // dL/dlogp x count: the unclipped term is the minimum (ties included)
-                    for (int j = 0; j < od; ++j) {
-                        const float sd = lds[O_LS + TR_PAD + j];
-                        const float q = (ra[j] - d[j]) / sd;
-                        d[j] = gl * (q / sd);                                                    // dlogp/dmu = (a - mu) / sd^2
-                        d[od + j] = gl * (q * q * (lds[O_LS + 2 * TR_PAD + j] / sd) - 1.0f);     // dlogp/dlog_std = q^2 e^ls / sd - 1
-                    }
-                    for (int j = 2 * od; j < TR_PAD; ++j) d[j] = 0.0f;
-                    st[0] = -fminf(s1, s2);
-                    st[1] = lpo - logp;
-                    st[2] = (ratio > hi || ratio < lo) ? 1.0f : 0.0f;
-                    st[3] = ratio;
-                } else {
-                    const float e = d[0] - lds[O_AUX + row * 2];           // v - ret
-                    d[0] = 2.0f * e;
-                    for (int j = 1; j < TR_PAD; ++j) d[j] = 0.0f;
-                    st[0] = e * e;
-                }
-            } else {
-                for (int j = 0; j < TR_PAD; ++j) d[j] = 0.0f;
-                st[0] = st[1] = st[2] = st[3] = 0.0f;
-            }
-        }
-        __syncthreads();
-        if (tid < NSTAT) {
-#pragma unroll 16
-            for (int row = 0; row < TR_ROWS; ++row) stat += (double)lds[O_ST + row * 4 + tid];
-        }
-        // ---- backward and the weight gradients, layer by layer ----
-        dw_step<3>(dw, lds, wave, lane);
-        if (tid < TR_PAD) db3 += column_sum(lds + O_D + tid, LDD);
-        __syncthreads();
-        layer_backward<TR_PAD / 4>(lds + O_D + r0 * LDD, LDD, lds + O_W3, LDW3, lds + O_H3 + r0 * LDH, a.leak, lane);
-        __syncthreads();
-        dw_step<2>(dw, lds, wave, lane);
-        if (tid < TR_H) db2 += column_sum(lds + O_H3 + tid, LDH);
-        __syncthreads();
-        layer_backward<TR_H / 4>(lds + O_H3 + r0 * LDH, LDH, lds + O_W2, LDW, lds + O_H2 + r0 * LDH, a.leak, lane);
-        __syncthreads();
-        dw_step<1>(dw, lds, wave, lane);
-        if (tid < TR_H) db1 += column_sum(lds + O_H2 + tid, LDH);
-        __syncthreads();
-        layer_backward<TR_H / 4>(lds + O_H2 + r0 * LDH, LDH, lds + O_W1, LDW, lds + O_H1 + r0 * LDH, a.leak, lane);
-        __syncthreads();
-        dw_step<0>(dw, lds, wave, lane);
-        if (tid < TR_H) db0 += column_sum(lds + O_H1 + tid, LDH);
-    }
-
-    // ---- one partial per workgroup, in theta's layout, the statistics behind it ----
-    float* out = a.partial + (size_t)blockIdx.x * (size_t)(L.P + NSTAT);
-#pragma unroll
-    for (int s = 0; s < 15; ++s) {
-        const int t = 4 * s + wave;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const int ti = 4 * lk + r;                         // row / column inside the 16 x 16 tile
-            const float val = dw[s][r];
-            if (t < 5) {
-                if (lr < od) out[L.w[3] + (t * 16 + ti) * od + lr] = val;
-            } else if (t < 55) {
-                const int u = t < 30 ? t - 5 : t - 30, it = u / 5, jt = u - 5 * it;
-                out[L.w[t < 30 ? 2 : 1] + (it * 16 + ti) * TR_H + jt * 16 + lr] = val;
-            } else {
-                if (ti < in) out[L.w[0] + ti * TR_H + (t - 55) * 16 + lr] = val;
-            }
-        }
-    }
-    if (tid < TR_H) {
-        out[L.b[0] + tid] = db0;
-        out[L.b[1] + tid] = db1;
-        out[L.b[2] + tid] = db2;
-    }
-    if (tid < od) out[L.b[3] + tid] = db3;
-    if (ACTOR && tid >= od && tid < 2 * od) out[L.ls + tid - od] = db3;
-    if (tid < NSTAT) out[L.P + tid] = (float)stat;
+// the imitation loss (dpenv_imitation_grad): the same body with the third per-row stage.  LOSS: DPENV_IMITATE_NLL (0) or DPENV_IMITATE_MSE (1)
+template <int LOSS>
+__global__ __launch_bounds__(256) void imitation_grad_kernel(GradArgs a)
+{
+    constexpr int STAGE = LOSS == 0 ? TR_STAGE_IMIT_NLL : TR_STAGE_IMIT_MSE;
+#include "dpenv_train_grad_body.inc"
 }
 
 // grad_out[p] = (sum over the workgroups' partials, in workgroup order) / count
@@ -401,30 +242,40 @@ __global__ void adam_commit_kernel(AdamArgs a)
 
 }  // namespace
 
-hipError_t dev::launch_mlp_grad(const GradArgs* a, hipStream_t s)
+hipError_t dev::launch_mlp_grad(const GradArgs* a, int stage, hipStream_t s)
 {
     const int grid = train_grid(a->count);
     const int nstat = a->L.actor ? TR_NSTAT_ACTOR : TR_NSTAT_CRITIC;
     const int total = a->L.P + nstat;
     const size_t lds_bytes = (size_t)LDS_FLOATS * sizeof(float);
+    const void* fn;
+    switch (stage) {
+    case TR_STAGE_VALUE: fn = reinterpret_cast<const void*>(&mlp_grad_kernel<false>); break;
+    case TR_STAGE_PPO: fn = reinterpret_cast<const void*>(&mlp_grad_kernel<true>); break;
+    case TR_STAGE_IMIT_NLL: fn = reinterpret_cast<const void*>(&imitation_grad_kernel<0>); break;
+    case TR_STAGE_IMIT_MSE: fn = reinterpret_cast<const void*>(&imitation_grad_kernel<1>); break;
+    default: return hipErrorInvalidValue;
+    }
     // the tile needs more LDS than a kernel gets by default: the limit is raised once per kernel and device, by whichever call comes first
     // (a function attribute, not a stream operation; dpenv.h asks for that first call to be made outside a stream capture)
-    static std::once_flag once[2][64];
+    static std::once_flag once[TR_NSTAGE][64];
     int devid = 0;
     hipError_t e = hipGetDevice(&devid);
     if (e != hipSuccess) return e;
-    const int act = a->L.actor ? 1 : 0;
-    const void* fn = act ? reinterpret_cast<const void*>(&mlp_grad_kernel<true>) : reinterpret_cast<const void*>(&mlp_grad_kernel<false>);
     if (devid >= 0 && devid < 64) {
         hipError_t first = hipSuccess;
-        std::call_once(once[act][devid], [&] { first = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes); });
+        std::call_once(once[stage][devid], [&] { first = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes); });
         if (first != hipSuccess) return first;
     } else {
         e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
         if (e != hipSuccess) return e;
     }
-    if (act) hipLaunchKernelGGL(mlp_grad_kernel<true>, dim3(grid), dim3(256), lds_bytes, s, *a);
-    else hipLaunchKernelGGL(mlp_grad_kernel<false>, dim3(grid), dim3(256), lds_bytes, s, *a);
+    switch (stage) {
+    case TR_STAGE_VALUE: hipLaunchKernelGGL(mlp_grad_kernel<false>, dim3(grid), dim3(256), lds_bytes, s, *a); break;
+    case TR_STAGE_PPO: hipLaunchKernelGGL(mlp_grad_kernel<true>, dim3(grid), dim3(256), lds_bytes, s, *a); break;
+    case TR_STAGE_IMIT_NLL: hipLaunchKernelGGL(imitation_grad_kernel<0>, dim3(grid), dim3(256), lds_bytes, s, *a); break;
+    default: hipLaunchKernelGGL(imitation_grad_kernel<1>, dim3(grid), dim3(256), lds_bytes, s, *a); break;
+    }
     hipLaunchKernelGGL(grad_reduce_kernel, dim3((total + 255) / 256), dim3(256), 0, s, (const float*)a->partial, grid, total, a->count, a->stop_flag,
                        a->grad_out);
     return hipGetLastError();

@@ -15,7 +15,7 @@ constexpr int TR_H = 80;           // hidden width
 constexpr int TR_PAD = 16;         // the input and the output layer are padded to one 16-wide MFMA tile
 constexpr int TR_ROWS = 64;        // rows per tile: four waves x 16 rows in the forward / backward phase, K = 64 in the dW phase
 constexpr int TR_MAX_WG = 256;     // workgroups at most (one per CU of an MI355X); the grid is min(tiles, TR_MAX_WG): a function of count alone
-constexpr int TR_NSTAT_ACTOR = 4;  // pi_loss, approx_kl, clip_frac, mean_ratio
+constexpr int TR_NSTAT_ACTOR = 4;  // pi_loss, approx_kl, clip_frac, mean_ratio; the imitation loss: L, weighted NLL, weighted MSE, 0
 constexpr int TR_NSTAT_CRITIC = 1; // v_loss
 
 // flat theta: W0 [in][80] | b0 [80] | W1 [80][80] | b1 | W2 [80][80] | b2 | W3 [80][out] | b3 [out] | (actor) log_std [out]
@@ -44,12 +44,15 @@ inline int train_grid(int count)
     return tiles < TR_MAX_WG ? (int)tiles : TR_MAX_WG;
 }
 
+// the per-row output stage of the gradient kernel, a template parameter of its body (dpenv_train.hip)
+constexpr int TR_STAGE_VALUE = 0, TR_STAGE_PPO = 1, TR_STAGE_IMIT_NLL = 2, TR_STAGE_IMIT_MSE = 3, TR_NSTAGE = 4;
+
 struct GradArgs {
     TrainLayout L;
     const float* theta;
     const float* obs;        // [n_rows][in_dim]
     const float* act;        // [n_rows][out_dim]   (actor)
-    const float* adv;        // [n_rows] advantage (actor) or return (critic)
+    const float* adv;        // [n_rows] advantage (actor), return (critic) or row weight (imitation; NULL = 1)
     const float* logp_old;   // [n_rows]            (actor)
     const int32_t* idx;      // [count] or NULL
     const int32_t* stop_flag;// or NULL
@@ -70,8 +73,8 @@ struct AdamArgs {
 };
 
 namespace __attribute__((visibility("hidden"))) dev {
-// dpenv_train.hip: the gradient (mlp_grad_kernel + grad_reduce_kernel) and the gated Adam step (adam_step_kernel + adam_commit_kernel)
-hipError_t launch_mlp_grad(const GradArgs* a, hipStream_t s);
+// dpenv_train.hip: the gradient (mlp_grad_kernel or imitation_grad_kernel + grad_reduce_kernel) and the gated Adam step (adam_step_kernel + adam_commit_kernel)
+hipError_t launch_mlp_grad(const GradArgs* a, int stage, hipStream_t s);   // stage: TR_STAGE_*
 hipError_t launch_adam_step(const AdamArgs* a, hipStream_t s);
 }  // namespace dev
 

@@ -1,10 +1,11 @@
 """The PPO update on the device (include/dpenv.h, "The PPO update"): PPO-clip actor gradient, the critic's MSE gradient and a
 device-gated Adam step, so that the 80 + 80 gradient steps of an epoch (ppo.py:265-273) queue without a host round trip.
 
-``ppo_actor_grad`` / ``value_grad`` / ``adam_step`` bind the handle-free C entry points; ``PPOUpdater`` re-homes the tensors of a
-``policy.ActorCritic`` as views of two flat parameter vectors and runs the whole update.  The host statements of the same law -
-``ppo_actor_grad_ref`` / ``value_grad_ref`` (closed form, float64) and ``adam_step_ref`` (NumPy float32 in the header's operation
-order) - are what the tests hold the kernels to.  There is no fallback: without the library or a GPU the device functions raise.
+``ppo_actor_grad`` / ``value_grad`` / ``imitation_grad`` / ``adam_step`` bind the handle-free C entry points; ``PPOUpdater`` re-homes
+the tensors of a ``policy.ActorCritic`` as views of two flat parameter vectors and runs the whole update, and - before it - the
+supervised warm start on demonstration rows (``pretrain`` / ``pretrain_critic``).  The host statements of the same law -
+``ppo_actor_grad_ref`` / ``value_grad_ref`` / ``imitation_grad_ref`` (closed form, float64) and ``adam_step_ref`` (NumPy float32 in
+the header's operation order) - are what the tests hold the kernels to.  There is no fallback: without the library or a GPU the device functions raise.
 """
 import ctypes as C
 import math
@@ -108,7 +109,9 @@ def _req(t, shape, dtype, what):
         raise ValueError('%s must be a contiguous cuda %s tensor%s' % (what, dtype, '' if shape is None else ' of shape %s' % (tuple(shape),)))
 
 
-def _grad_call(actor, theta, obs, act, adv, logp_old, clip, idx, out, workspace, leak, stop_flag, count):
+def _grad_call(actor, theta, obs, act, adv, logp_old, clip, idx, out, workspace, leak, stop_flag, count, loss=None):
+    """The one binding of the three gradient entry points.  loss (a code of LOSSES): dpenv_imitation_grad, `adv` then being the row
+    weight or None."""
     torch = _torch()
     f32 = torch.float32
     n_rows, in_dim = obs.shape
@@ -118,7 +121,7 @@ def _grad_call(actor, theta, obs, act, adv, logp_old, clip, idx, out, workspace,
     _req(theta, (P,), f32, 'theta')
     _req(obs, (n_rows, in_dim), f32, 'obs')
     _req(act, (n_rows, out_dim), f32, 'act')
-    _req(adv, (n_rows,), f32, 'adv' if actor else 'ret')
+    _req(adv, (n_rows,), f32, 'weight' if loss is not None else ('adv' if actor else 'ret'))
     _req(logp_old, (n_rows,), f32, 'logp_old')
     _req(idx, None, torch.int32, 'idx')
     _req(stop_flag, (1,), torch.int32, 'stop_flag')
@@ -133,14 +136,17 @@ def _grad_call(actor, theta, obs, act, adv, logp_old, clip, idx, out, workspace,
     if workspace is None:
         workspace = torch.empty((workspace_bytes(sh, max(count, 1)) + 3) // 4, dtype=f32, device=theta.device)
     lib = _lib.load()
+    ws_bytes = workspace.numel() * workspace.element_size()
     with torch.cuda.device(theta.device):
-        if actor:
+        if loss is not None:
+            _lib.check(lib.dpenv_imitation_grad(C.byref(sh), _p(theta), _p(obs), _p(act), _p(adv), _p(idx), int(count), int(n_rows), int(loss),
+                                                _p(stop_flag), _p(out), _p(workspace), ws_bytes, _s(theta)))
+        elif actor:
             _lib.check(lib.dpenv_ppo_actor_grad(C.byref(sh), _p(theta), _p(obs), _p(act), _p(adv), _p(logp_old), _p(idx), int(count), int(n_rows),
-                                                float(clip), _p(stop_flag), _p(out), _p(workspace), workspace.numel() * workspace.element_size(),
-                                                _s(theta)))
+                                                float(clip), _p(stop_flag), _p(out), _p(workspace), ws_bytes, _s(theta)))
         else:
             _lib.check(lib.dpenv_value_grad(C.byref(sh), _p(theta), _p(obs), _p(adv), _p(idx), int(count), int(n_rows), _p(out), _p(workspace),
-                                            workspace.numel() * workspace.element_size(), _s(theta)))
+                                            ws_bytes, _s(theta)))
     return out
 
 
@@ -154,6 +160,24 @@ def ppo_actor_grad(theta, obs, act, adv, logp_old, clip, idx=None, out=None, wor
 def value_grad(theta, obs, ret, idx=None, out=None, workspace=None, leak=0.2, count=None):
     """dpenv_value_grad: the gradient of mean((ret - v)^2) for the flat critic `theta`.  Returns out [P + 1]: the gradient, then v_loss."""
     return _grad_call(False, theta, obs, None, ret, None, 0.0, idx, out, workspace, leak, None, count)
+
+
+LOSSES = {'nll': _lib.IMITATE_NLL, 'mse': _lib.IMITATE_MSE}
+
+
+def _loss_code(loss):
+    if loss in LOSSES:
+        return LOSSES[loss]
+    if isinstance(loss, str):
+        raise ValueError("loss must be 'nll' or 'mse' (got %r)" % (loss,))
+    return int(loss)                                           # a raw code goes to the library, which refuses what it does not know
+
+
+def imitation_grad(theta, obs, act, loss='nll', weight=None, idx=None, out=None, workspace=None, leak=0.2, stop_flag=None, count=None):
+    """dpenv_imitation_grad: the gradient of the weighted imitation loss of the flat actor `theta` over rows `idx` (int32; None = all rows)
+    of obs [n, in] / act [n, out], weight [n] or None = 1.  loss: 'nll' (-mean(w logp)) or 'mse' (mean(w sum_j (mu_j - act_j)^2)).
+    Returns out [P + 4]: the gradient, then the chosen loss, the weighted NLL, the weighted MSE, 0.  Stream-ordered, nothing is read back."""
+    return _grad_call(True, theta, obs, act, weight, None, 0.0, idx, out, workspace, leak, stop_flag, count, loss=_loss_code(loss))
 
 
 def adam_step(theta, grad, m, v, step_counter, lr, beta1=0.9, beta2=0.999, eps=1e-8, gate_kl=None, kl_limit=float('inf'), stop_flag=None):
@@ -223,6 +247,31 @@ def ppo_actor_grad_ref(theta, obs, act, adv, logp_old, clip, leak=0.2, hidden_z=
     if hidden_z:
         return grad, stats, zs, ratio
     return grad, stats
+
+
+def imitation_grad_ref(theta, obs, act, loss, weight=None, leak=0.2):
+    """The header's imitation law in closed form, float64: (grad [P], stats [4] = the chosen loss, weighted NLL, weighted MSE, 0)."""
+    code = _loss_code(loss)
+    if code not in (_lib.IMITATE_NLL, _lib.IMITATE_MSE):
+        raise ValueError('unknown loss %r' % (loss,))
+    obs, act = np.asarray(obs, np.float64), np.asarray(act, np.float64)
+    count, in_dim, out_dim = obs.shape[0], obs.shape[1], act.shape[1]
+    w = np.ones(count) if weight is None else np.asarray(weight, np.float64)
+    Ws, bs, ls, hs, zs, mu = _forward64(theta, obs, in_dim, out_dim, True, leak)
+    sd = np.exp(ls) + 1e-8
+    q = (act - mu) / sd
+    logp = (-0.5 * ((q * q + 2.0 * ls) + math.log(2.0 * math.pi))).sum(1)
+    e = mu - act
+    nll, mse = (w * -logp).sum() / count, (w * (e * e).sum(1)).sum() / count
+    if code == _lib.IMITATE_NLL:
+        gl = -w / count
+        dmu = gl[:, None] * (q / sd)
+        dls = (gl[:, None] * (q * q * (np.exp(ls) / sd) - 1.0)).sum(0)
+    else:
+        dmu = (2.0 * w / count)[:, None] * e
+        dls = np.zeros(out_dim)
+    grad = _backward64(Ws, hs, zs, dmu, leak, dls)
+    return grad, np.array([nll if code == _lib.IMITATE_NLL else mse, nll, mse, 0.0])
 
 
 def value_grad_ref(theta, obs, ret, leak=0.2):
@@ -353,3 +402,57 @@ class PPOUpdater(object):
         pi_iters = int(steps) - self._pi_steps_host
         self._pi_steps_host = int(steps)
         return pi_iters, kl, v_loss
+
+    # ---- the supervised warm start: demonstration rows (e.g. a controller_rollout of the DP baseline) before the first PPO epoch ----
+    def pretrain(self, obs, act, iters, minibatch=None, loss='mse', weight=None, lr=None, average=None, keep_optimizer_state=False):
+        """Queue `iters` x (imitation_grad -> adam_step, no gate) on the actor: obs [N, od], act [N, ad], weight [N] or None, float32 on
+        the device; indices drawn as `update` draws them.  Returns the [iters, 4] history (chosen loss, weighted NLL, weighted MSE, 0 per
+        step, each measured BEFORE that step's Adam), read back once.  Unless keep_optimizer_state, the actor's Adam m, v and step counter
+        are then zeroed, so PPO starts with a fresh optimiser."""
+        torch = _torch()
+        N = obs.shape[0]
+        mb = N if minibatch is None else min(int(minibatch), N)
+        ws = self._workspace(mb)
+        b1, b2 = self.betas
+        lr = self.pi_lr if lr is None else float(lr)
+        hist = torch.zeros((iters, NSTAT_ACTOR), dtype=torch.float32, device=self.device)
+        for k in range(iters):
+            idx = torch.randint(0, N, (mb,), device=self.device).to(torch.int32) if mb < N else None
+            imitation_grad(self.pi_theta, obs, act, loss=loss, weight=weight, idx=idx, out=self.pi_grad, workspace=ws, leak=self.ac.leak, count=mb)
+            if average is not None:
+                average(self.pi_grad)
+            hist[k].copy_(self.pi_grad[self.P_pi:])                    # stream-ordered, device to device
+            adam_step(self.pi_theta, self.pi_grad, self.pi_m, self.pi_v, self.pi_steps, lr, b1, b2, self.eps)
+        out = hist.cpu()                                               # the one read
+        if not keep_optimizer_state:
+            self.pi_m.zero_()
+            self.pi_v.zero_()
+            self.pi_steps.zero_()
+            self._pi_steps_host = 0
+        else:
+            self._pi_steps_host += iters                               # ungated: every queued step was taken
+        return out
+
+    def pretrain_critic(self, obs, ret, iters, minibatch=None, lr=None, average=None, keep_optimizer_state=False):
+        """The critic's half of the warm start: `iters` x (value_grad -> adam_step) on ret [N] (the demonstration's discounted returns).
+        Returns the [iters, 1] history of v_loss, read back once; the critic's Adam state is then zeroed unless keep_optimizer_state."""
+        torch = _torch()
+        N = obs.shape[0]
+        mb = N if minibatch is None else min(int(minibatch), N)
+        ws = self._workspace(mb)
+        b1, b2 = self.betas
+        lr = self.v_lr if lr is None else float(lr)
+        hist = torch.zeros((iters, NSTAT_CRITIC), dtype=torch.float32, device=self.device)
+        for k in range(iters):
+            idx = torch.randint(0, N, (mb,), device=self.device).to(torch.int32) if mb < N else None
+            value_grad(self.v_theta, obs, ret, idx=idx, out=self.v_grad, workspace=ws, leak=self.ac.leak, count=mb)
+            if average is not None:
+                average(self.v_grad)
+            hist[k].copy_(self.v_grad[self.P_v:])
+            adam_step(self.v_theta, self.v_grad, self.v_m, self.v_v, self.v_steps, lr, b1, b2, self.eps)
+        out = hist.cpu()
+        if not keep_optimizer_state:
+            self.v_m.zero_()
+            self.v_v.zero_()
+            self.v_steps.zero_()
+        return out

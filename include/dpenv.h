@@ -100,7 +100,12 @@ typedef struct dpenv_config {
     int32_t device;          /* HIP device ordinal, -1 = current */
     int32_t variant;         /* DPENV_FULL .. DPENV_FINAL */
     int32_t extended_state;  /* obs dim 9 (1) or 6 (0), customEnv.py:44,201-205 */
-    int32_t cont_ang;        /* FINAL only: 7 actions with sin/cos azimuth heads, customEnv.py:227-235 */
+    int32_t cont_ang;        /* FINAL only: 7 actions with sin/cos azimuth heads, customEnv.py:227-235.  Supported head magnitudes:
+                                2^-60 <= max(|sin head|, |cos head|) <= 2^60 per pair, or both heads zero (then, like numpy.arctan2,
+                                the sign of the zero cos head decides: +0 -> azimuth +-0, -0 -> azimuth +-pi, force and bookkeeping
+                                alike).  Outside that range a step stays finite and raises no fault bit, but the force no longer
+                                follows the azimuth: a pair with sin^2 + cos^2 below the smallest normal float pushes as a zero
+                                pair, one whose sum overflows (heads above about 2^63) gives no force. */
     int32_t n_substeps;      /* plant sub-steps per env step, 20 (customEnv.py:79-80) */
     float substep_dt;        /* 0.01 s (customEnv.py:81) */
     int32_t wrap_mode;       /* DPENV_WRAP_* */

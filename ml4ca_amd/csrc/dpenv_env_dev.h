@@ -753,13 +753,18 @@ __device__ __forceinline__ void env_decode(const Vessel& ve, float ang[3], const
 {
     env_decode_cmd<MODE, DEFER_ANG>(ang, act, w.thr);
     if (MODE == MODE_FINAL_CONT) {
-        // the azimuth is atan2 of the two heads, so its sine and cosine are the normalised heads themselves:
-        // no sincos of the angle just computed ((0, 0) -> angle 0 -> (0, 1))
+        // the azimuth is atan2 of the two heads, so its sine and cosine are the normalised heads themselves: no sincos of the angle
+        // just computed.  A pair whose s^2 + c^2 is below the smallest normal float (both heads zero, or so small that the sum
+        // underflows: v_rsq_f32 takes a subnormal for zero and would return inf) is pushed as a zero pair, and a zero pair follows
+        // atan2_lean / numpy.arctan2, which keep signed zeros: (+-0, +0) -> angle +-0 -> (0, 1), (+-0, -0) -> angle +-pi -> (0, -1).
+        // Supported head magnitudes (include/dpenv.h): 2^-60 <= max(|s|, |c|) <= 2^60; above 2^63 the sum overflows and the thruster
+        // gives no force.
         float sc[4];
         const float np2 = fmaf(act[3], act[3], act[4] * act[4]), ns2 = fmaf(act[5], act[5], act[6] * act[6]);
         const float ip = __builtin_amdgcn_rsqf(np2), is = __builtin_amdgcn_rsqf(ns2);
-        sc[0] = (np2 > 0.0f) ? act[3] * ip : 0.0f; sc[1] = (np2 > 0.0f) ? act[4] * ip : 1.0f;
-        sc[2] = (ns2 > 0.0f) ? act[5] * is : 0.0f; sc[3] = (ns2 > 0.0f) ? act[6] * is : 1.0f;
+        constexpr float kMinNormal = 1.17549435e-38f;
+        sc[0] = (np2 >= kMinNormal) ? act[3] * ip : 0.0f; sc[1] = (np2 >= kMinNormal) ? act[4] * ip : copysignf(1.0f, act[4]);
+        sc[2] = (ns2 >= kMinNormal) ? act[5] * is : 0.0f; sc[3] = (ns2 >= kMinNormal) ? act[6] * is : copysignf(1.0f, act[6]);
         thrust_map(ve, w.thr, ang, w.tx, w.ty, w.tn, sc, tl);
     } else {
         thrust_map(ve, w.thr, ang, w.tx, w.ty, w.tn, nullptr, tl);

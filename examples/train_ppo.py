@@ -14,6 +14,8 @@ env.step, critic, trajectory rows), GAE by one scan kernel, advantage statistics
     python examples/train_ppo.py --envs 4096 --epochs 30 --update fused
     python examples/train_ppo.py --envs 4096 --epochs 30 --update fused --warm-start 300 --eval      clone the PID + pseudo-inverse baseline into the
                                                                                       actor first (PPOUpdater.pretrain on one controller_rollout), then PPO
+    python examples/train_ppo.py --envs 4096 --epochs 30 --update fused --warm-start 300 --dagger 5 --eval      ... then DAgger: fly the clone, label ITS
+                                                                                      states with the baseline (policy.controller_label), aggregate, refit
     python examples/train_ppo.py --envs 4096 --epochs 40 --randomise 0.15 --eval      domain randomisation: every episode of every env
                                                                                       runs on its own hull, +-15 % on all 26 parameters, re-drawn by the reset path
                                                                                       inside the rollout launch; --eval: the reference's evaluation harness
@@ -171,6 +173,35 @@ def warm_start(upd, env, args, out=print):
     return h, hv
 
 
+def dagger(upd, env, args, out=print):
+    """--dagger: after the warm start (if any) and before PPO, fly the ACTOR on the training envs, label the states it visits with the
+    baseline (policy.controller_label: the PID + pseudo-inverse law scanned over the actor's rows in one launch), aggregate the rounds and
+    refit (PPOUpdater.dagger).  A clone trained on the expert's states alone has no labels where its own errors take it; these rounds
+    supply them.  The labels carry the PID's integral, which the memoryless actor cannot see: it can only fit their mean given o."""
+    from ml4ca_amd.deploy import dp_controller_defaults
+    T = args.dagger_steps or args.steps
+    env.set_dp_controller(dp_controller_defaults(ml4ca_amd.default_vessel(args.preset)))
+    env.reset()
+    mb = min(args.minibatch, T * env.n_envs)
+    t0 = time.perf_counter()
+    rec = upd.dagger(env, args.dagger, T, args.dagger_iters, minibatch=mb, loss=args.warm_start_loss, keep=args.dagger_keep or None,
+                     average=D.average_flat, upload=dict(precision=args.precision))
+    torch.cuda.synchronize()
+    D.assert_params_in_step(list(upd.ac.parameters()), what='parameters after DAgger')
+    env.set_dp_controller(off=True)
+    for r, x in enumerate(rec):
+        h = x['history']
+        out('dagger round %2d: actor reward/step %.3f  |actor - baseline|^2 on its own states %.4g  %d rows  %d %s steps: MSE %.4g -> %.4g  NLL %.4g -> %.4g' % (
+            r, x['reward_per_step'], x['label_msd'], x['rows'], h.shape[0], args.warm_start_loss, float(h[0, 2]), float(h[-1, 2]),
+            float(h[0, 1]), float(h[-1, 1])))
+    out('dagger: %d rounds of %d steps on %d envs in %.2f s' % (len(rec), T, env.n_envs, time.perf_counter() - t0))
+    upd.pi_m.zero_()                                                             # PPO starts with a fresh actor optimiser, as after the warm start
+    upd.pi_v.zero_()
+    upd.pi_steps.zero_()
+    upd._pi_steps_host = 0
+    return rec
+
+
 def torch_update(ac, pi_opt, v_opt, pi_params, v_params, obs, act, adv, ret, logp_old, mb, clip=0.2, target_kl=0.01, gather=False, iters=80):
     """The update of ppo.py:265-273 through torch autograd and torch.optim.Adam (--update torch): the baseline the fused update
     (ml4ca_amd.train.PPOUpdater, --update fused) is held to and timed against.  Returns (pi_iters, kl, v_loss)."""
@@ -226,6 +257,12 @@ def main():
     ap.add_argument('--warm-start-loss', default='mse', choices=('mse', 'nll'), help="the imitation loss: 'mse' on the mean action, or the Gaussian 'nll' "
                                                                                        '(which also fits log_std)')
     ap.add_argument('--warm-start-steps', type=int, default=0, metavar='T', help='steps of the demonstration flight (default: one episode, --steps)')
+    ap.add_argument('--dagger', type=int, default=0, metavar='ROUNDS',
+                    help='with --update fused, after --warm-start (if given) and before PPO: ROUNDS x (fly the actor, label the states it visits with the '
+                         'baseline DP controller in one launch, aggregate, refit the actor: ml4ca_amd.train.PPOUpdater.dagger); one line per round')
+    ap.add_argument('--dagger-iters', type=int, default=100, metavar='ITERS', help='gradient steps per DAgger round (loss: --warm-start-loss)')
+    ap.add_argument('--dagger-steps', type=int, default=0, metavar='T', help='steps of each DAgger flight (default: one episode, --steps)')
+    ap.add_argument('--dagger-keep', type=int, default=0, metavar='K', help='rounds kept in the aggregated dataset, a ring (default 0: all of them)')
     ap.add_argument('--exchange', default='gradients', choices=('gradients', 'rollout'),
                     help="multi-rank runs: 'gradients' = every rank updates on ITS OWN episode and the gradients are averaged, exactly the "
                          "reference (ppo.py:226, mpi_tf.py:29-62: no trajectory ever crosses); 'rollout' = BASELINE.json config 4: the ranks "
@@ -257,6 +294,8 @@ def main():
     args = ap.parse_args()
     if args.warm_start > 0 and args.update != 'fused':
         ap.error('--warm-start needs --update fused (the imitation gradient is a kernel of the fused update)')
+    if args.dagger > 0 and args.update != 'fused':
+        ap.error('--dagger needs --update fused (the imitation gradient is a kernel of the fused update)')
     # one process per GPU under torch.distributed.run (backend nccl = RCCL); envs shard by global id, gradients average
     rank, world, local = int(os.environ.get('RANK', 0)), int(os.environ.get('WORLD_SIZE', 1)), int(os.environ.get('LOCAL_RANK', 0))
     dev = torch.device('cuda', 0 if args.same_device else local)
@@ -302,6 +341,13 @@ def main():
             ac.log_std.clamp_(-4.0, 1.0)
         if args.eval and rank == 0:
             print('eval of the cloned actor, before any PPO epoch')
+            evaluate_actor(ac, dev, args.preset, 'f32', args.seed, eval_envs=args.eval_envs, only=('nominal hull',))
+    if args.dagger > 0:
+        dagger(upd, env, args, out=print if rank == 0 else (lambda *a: None))
+        with torch.no_grad():
+            ac.log_std.clamp_(-4.0, 1.0)
+        if args.eval and rank == 0:
+            print('eval of the actor after DAgger, before any PPO epoch')
             evaluate_actor(ac, dev, args.preset, 'f32', args.seed, eval_envs=args.eval_envs, only=('nominal hull',))
     ac.upload(env, precision=args.precision)          # device pointers: one packing kernel, no host copy
     env.reset()

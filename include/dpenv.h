@@ -716,6 +716,34 @@ typedef struct dpenv_controller_rollout_io {
  * unchanged.  With the reference filter on (dpenv_set_reference_filter) the switches set its targets and every step's new_ref is its
  * position, exactly as in dpenv_policy_rollout_deployed.  Stream-ordered, no allocation and no host synchronisation: graph-capturable. */
 int dpenv_controller_rollout(dpenv_handle h, const dpenv_controller_rollout_io* io, dpenv_stream s);
+/* The law on rows some other flight wrote (additive to ABI 6): expert labels for the states an actor visited (DAgger-style relabelling),
+ * or the baseline's answer beside an actor's on the same states.  A forward scan in one launch, one lane per env; per row t and env i
+ *     act[t][i][0:7] = the law above on o = obs[t][i][0:6] with the env's z_i (z_i is advanced first, exactly as in the closed loop)
+ *     if (done && done[t][i] != 0) z_i = 0                         -- the next row is a new episode's first
+ * z_i starts from z_in[:, i] (NULL = 0) and is written to z_out[:, i] at the end (NULL = not wanted; z_out may be z_in), so a block
+ * labelled in pieces with z handed over gives the rows of one call.  The numbers are the handle's controller in force: the table of
+ * dpenv_set_dp_controller_table when there is one (row i on env i), else dpenv_set_dp_controller's; dt is the handle's.  obs rows are
+ * f32 or bf16 as obs_dtype says, whatever the handle's config says; a bf16 value is widened exactly and the law runs in f32.  The thrust
+ * columns obs[..][6:9] are not read.
+ * For f32 rows written by dpenv_controller_rollout with auto-reset on, labelled with that launch's done block, the z the launch started
+ * from and the same controller, the labels are that launch's act rows bit for bit and z_out is its final z.  (Without auto-reset the
+ * closed loop keeps z across a done row; pass done = NULL to label such a block.)
+ * The call reads and writes nothing of the handle's env state, its own z, the lagged thrust columns or the RNG counters: a labelled block
+ * changes no later row of any launch.  Stream-ordered, no allocation, no host synchronisation; one kernel node when captured into a
+ * graph (a captured call flies whatever table the last packing wrote; the scalar numbers are those at capture).
+ * DPENV_EINVAL with the reason in dpenv_last_error, before anything is launched or written: the controller off, a wrong struct_size,
+ * T <= 0, NULL obs or act, an obs_dtype that is neither DPENV_F32 nor DPENV_BF16.  ml4ca_amd.deploy.label_rows is the host statement. */
+typedef struct dpenv_controller_label_io {
+    uint32_t struct_size;    /* sizeof(dpenv_controller_label_io), ABI check */
+    int32_t T;
+    const void* obs;         /* [T][n][9] rows in dpenv_policy_rollout's conventions; f32 or bf16 */
+    int32_t obs_dtype;       /* DPENV_F32 / DPENV_BF16: the block's, independent of the handle's config */
+    const uint8_t* done;     /* [T][n] DPENV_DONE_* bits, or NULL = no episode ends in the block */
+    const float* z_in;       /* [3][n] (dpenv_get_dp_controller_state's layout) or NULL = 0 */
+    float* z_out;            /* [3][n] or NULL; may be z_in */
+    float* act;              /* [T][n][7] the law's action on obs[t] */
+} dpenv_controller_label_io;
+int dpenv_controller_label(dpenv_handle h, const dpenv_controller_label_io* io, dpenv_stream s);
 /* The stateless allocation of the law (its f_m, bow and stern lines) for n wrenches: tau device float[3][n] -> action_out device
  * float[n][7].  Handle-free, like dpenv_thrust_map; of c only G, kf, kr_bow and f_eps are read, the whole struct is validated. */
 int dpenv_thrust_alloc(const dpenv_dp_controller* c, const float* tau, float* action_out, int32_t n, dpenv_stream s);

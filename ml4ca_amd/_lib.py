@@ -96,6 +96,11 @@ class ControllerRolloutIO(C.Structure):
                 ('switch_step', C.c_int32 * 8), ('refs', C.c_void_p)]
 
 
+class ControllerLabelIO(C.Structure):
+    _fields_ = [('struct_size', C.c_uint32), ('T', C.c_int32), ('obs', C.c_void_p), ('obs_dtype', C.c_int32), ('done', C.c_void_p),
+                ('z_in', C.c_void_p), ('z_out', C.c_void_p), ('act', C.c_void_p)]
+
+
 class ScoreIO(C.Structure):
     _fields_ = [('struct_size', C.c_uint32), ('T', C.c_int32), ('n', C.c_int32), ('obs', C.c_void_p), ('act', C.c_void_p),
                 ('rew', C.c_void_p), ('done', C.c_void_p), ('integ', C.c_void_p), ('obs_dtype', C.c_int32), ('obs_stride', C.c_int32),
@@ -182,6 +187,7 @@ SYMBOLS = {
     'dpenv_set_dp_controller_state': (C.c_int, [_VP, _VP, _VP]),
     'dpenv_set_dp_controller_table': (C.c_int, [_VP, _VP, _VP, _VP]),
     'dpenv_controller_rollout': (C.c_int, [_VP, C.POINTER(ControllerRolloutIO), _VP]),
+    'dpenv_controller_label': (C.c_int, [_VP, C.POINTER(ControllerLabelIO), _VP]),
     'dpenv_thrust_alloc': (C.c_int, [C.POINTER(DPController), _VP, _VP, _I32, _VP]),
     'dpenv_train_param_count': (C.c_int64, [C.POINTER(TrainShape)]),
     'dpenv_train_workspace_bytes': (C.c_int, [C.POINTER(TrainShape), _I32, C.POINTER(C.c_int64)]),

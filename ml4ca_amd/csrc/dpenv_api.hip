@@ -1220,6 +1220,25 @@ extern "C" int dpenv_controller_rollout(dpenv_handle h, const dpenv_controller_r
     return DPENV_OK;
 }
 
+// the law on rows some other flight wrote: nothing of the handle but the controller's numbers (or its table) and dt is read
+extern "C" int dpenv_controller_label(dpenv_handle h, const dpenv_controller_label_io* io, dpenv_stream s)
+{
+    if (!h) return DPENV_EINVAL;
+    DeviceGuard dev_guard(h->device);
+    if (!h->ctrl_on) return fail(h, DPENV_EINVAL, "dpenv_controller_label: the DP controller is off (dpenv_set_dp_controller)");
+    if (!io || io->struct_size != sizeof(dpenv_controller_label_io)) return fail(h, DPENV_EINVAL, "dpenv_controller_label_io ABI mismatch");
+    if (io->T <= 0) return fail(h, DPENV_EINVAL, "dpenv_controller_label: T > 0 is required");
+    if (!io->obs || !io->act) return fail(h, DPENV_EINVAL, "dpenv_controller_label: the obs and act blocks are required");
+    if (io->obs_dtype != DPENV_F32 && io->obs_dtype != DPENV_BF16)
+        return fail(h, DPENV_EINVAL, "dpenv_controller_label: obs_dtype must be DPENV_F32 or DPENV_BF16");
+    LabelArgs la = {};
+    la.obs = io->obs; la.done = io->done; la.z_in = io->z_in; la.z_out = io->z_out; la.act = io->act;
+    la.T = io->T; la.n = h->cfg.n_envs;
+    const hipError_t e = dev::launch_controller_label(&h->ctrl, &la, h->ctrl_tab_on ? h->ctrl_tab : nullptr, io->obs_dtype == DPENV_BF16, (hipStream_t)s);
+    if (e != hipSuccess) return fail(h, DPENV_EHIP, "label launch failed: %s", hipGetErrorString(e));
+    return DPENV_OK;
+}
+
 extern "C" int dpenv_get_state(dpenv_handle h, float* state_out, int32_t* counters_out, dpenv_stream s)
 {
     if (!h) return DPENV_EINVAL;

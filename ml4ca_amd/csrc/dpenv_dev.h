@@ -388,6 +388,17 @@ struct ScoreArgs {
     float norm[3], coeff[3], rps[3];
 };
 
+// ---- the baseline controller's law on rows some other flight wrote (dpenv_controller_label; the kernel is dpenv_label.hip's): the I/O of
+// one labelling scan.  The law's numbers travel as ControlArgs (its z and rollout I/O are not read) or as the packed per-env table.
+struct LabelArgs {
+    const void* obs;            // [T][n][9] f32 or bf16, columns 0..5 read
+    const uint8_t* done;        // [T][n] or NULL
+    const float* z_in;          // [3][n] or NULL = 0
+    float* z_out;               // [3][n] or NULL; may be z_in
+    float* act;                 // [T][n][7]
+    int T, n;
+};
+
 // ---- launchers: called by the host units (dpenv_api.hip, dpenv_api_free.hip), defined by the translation unit that owns the kernels; not exported from libdpenv.so ----
 namespace __attribute__((visibility("hidden"))) dev {
 // dpenv_kernels.hip.  ves: VES_* (where the vessel of a lane comes from)
@@ -441,6 +452,9 @@ hipError_t launch_controller_rollout(const StepArgs* a, const ControlArgs* ca, c
 hipError_t launch_pack_controllers(const float* table, float4* tab, uint8_t* refused, int n, hipStream_t s);
 hipError_t launch_control_state(float4* z, float* ext, const uint8_t* mask, int n, int op, hipStream_t s);
 hipError_t launch_thrust_alloc(const ControlArgs* ca, const float* tau, float* action, int n, hipStream_t s);
+// dpenv_label.hip: the law scanned over the T rows of a block, one lane per env (tab as launch_controller_rollout's; obs_bf16: the obs rows
+// are bf16); reads ca's numbers and dt only
+hipError_t launch_controller_label(const ControlArgs* ca, const LabelArgs* la, const float4* tab, int obs_bf16, hipStream_t s);
 // two-wave closed loop, dpenv_policy_ws.h; one arithmetic per translation unit: dpenv_policy_ws.hip PREC_F16, dpenv_policy_xws1.hip
 // PREC_F32, dpenv_policy_xws2.hip PREC_F32_ACTOR
 template <int PREC>

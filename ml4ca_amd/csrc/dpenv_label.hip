@@ -1,0 +1,135 @@
+// dpenv_label.hip - the baseline DP controller's law evaluated on rows some other flight wrote (dpenv_controller_label in dpenv.h): expert
+// labels for the states an actor visited (DAgger), or the distance between an actor's actions and the baseline's on those states.
+//
+// The law exists once, in dpenv_control_law.h; the closed-loop kernels (dpenv_control_dev.h, dpenv_policy.hip) weld it to env_step, this unit
+// scans it over a [T][n][9] observation block.  The integral z is carried along each env's row sequence and zeroed behind every done
+// row, so the label of row t depends on every row before it: a scan, one lane per env, not a map over rows.
+//
+// A unit of its own with the library's CXXFLAGS: no other unit's kernels see a new instantiation (dpenv_control_dev.h records what a
+// second instantiation of a shared template does to its neighbours' schedules).  Per env-row 36 B of observation (18 B as bf16) and a
+// done byte come in, 28 B of action go out; the handle's state is neither read nor written.
+#include "dpenv_env_dev.h"
+
+namespace dpenv {
+
+#include "dpenv_control_law.h"
+
+namespace {
+
+// rows fetched ahead per register bank, two banks (score_kernel's scheme and its winner, dpenv_score_dev.h): a row is 7 loads per lane
+constexpr int LABEL_U = 2;
+
+struct LabelRow {
+    float o[6];
+    uint32_t d;
+};
+
+// control_store_rows<7> of dpenv_control_dev.h restated for f32 rows: a wave's 64 action rows staged through the wave-private LDS area,
+// stored coalesced.  A copy for the reason given there.
+__device__ __forceinline__ void label_store_rows(float* lds, float* dst, int64_t base, int64_t rem, const float* v, int lane)
+{
+    constexpr int W = 7;
+    lds_order<64>();
+#pragma unroll
+    for (int k = 0; k < W; ++k) lds[lane * W + k] = v[k];
+    lds_order<64>();
+    const bool full = rem >= (int64_t)64 * W;                    // uniform; the last wave's dead lanes hold no row
+    float* p = dst + base;
+#pragma unroll
+    for (int j = 0; j < W; ++j)
+        if (full || j * 64 + lane < rem) p[(unsigned)(j * 64 + lane)] = lds[j * 64 + lane];
+}
+
+// Forward scan over the T rows of a block, one lane per env, one wave per workgroup.  The law is serial in t, but no load depends on it:
+// rows are fetched LABEL_U at a time into one of two register banks while the other is consumed.  TAB: the env's own row of the packed
+// controller table, nine 16-byte loads in the opening burst; else the shared numbers of ca (SGPRs).  Dead lanes shadow env n - 1 and
+// store nothing.
+template <bool TAB, bool BF16>
+__global__ __launch_bounds__(64) void controller_label_kernel(const ControlArgs ca, const LabelArgs la, const float4* __restrict__ tab)
+{
+    constexpr int A = 7, OD = 9;
+    __shared__ float lds_row[64 * A];
+
+    const int n = la.n, T = la.T;
+    const int lane = threadIdx.x;
+    const int wave0 = blockIdx.x * 64;
+    const int i = wave0 + lane;
+    const bool live = i < n;
+    const int il = live ? i : n - 1;
+
+    ControlLane cl;
+    if constexpr (TAB) load_control_lane(tab, il, ca.dt, cl);
+    float z[3] = {0.0f, 0.0f, 0.0f};
+    if (la.z_in) {
+        z[0] = la.z_in[il]; z[1] = la.z_in[(int64_t)n + il]; z[2] = la.z_in[2 * (int64_t)n + il];
+    }
+
+    const int64_t stride_a = (int64_t)n * A;
+    const int64_t w_a = (int64_t)wave0 * A;                      // the wave's slice of the [T][n][7] block
+    const int64_t rem_a = stride_a - w_a;
+
+    LabelRow RA[LABEL_U], RB[LABEL_U];
+    auto load = [&](LabelRow (&buf)[LABEL_U], int j) {
+#pragma unroll
+        for (int u = 0; u < LABEL_U; ++u) {
+            int t = j * LABEL_U + u;
+            t = t < T ? t : T - 1;                               // past the end: re-read the last row (never consumed)
+            const int64_t k = (int64_t)t * n + il;
+            if (BF16) {
+                const uint16_t* p = (const uint16_t*)la.obs + k * OD;
+#pragma unroll
+                for (int c = 0; c < 6; ++c) buf[u].o[c] = __uint_as_float((uint32_t)p[c] << 16);
+            } else {
+                const float* p = (const float*)la.obs + k * OD;
+#pragma unroll
+                for (int c = 0; c < 6; ++c) buf[u].o[c] = p[c];
+            }
+            buf[u].d = la.done ? (uint32_t)la.done[k] : 0u;
+        }
+    };
+    auto consume = [&](const LabelRow (&buf)[LABEL_U], int j) {
+#pragma unroll
+        for (int u = 0; u < LABEL_U; ++u) {
+            const int t = j * LABEL_U + u;
+            if (t >= T) break;
+            float o[OD], act[A];
+#pragma unroll
+            for (int c = 0; c < 6; ++c) o[c] = buf[u].o[c];
+            o[6] = o[7] = o[8] = 0.0f;                           // the thrust columns: the law does not read them
+            if constexpr (TAB) dp_control(cl, o, z, act);
+            else dp_control(ca, o, z, act);
+            label_store_rows(lds_row, la.act, (int64_t)t * stride_a + w_a, rem_a, act, lane);
+            if (buf[u].d != 0u) z[0] = z[1] = z[2] = 0.0f;       // the next row is a new episode's first
+        }
+    };
+    const int nb = (T + LABEL_U - 1) / LABEL_U;
+    load(RA, 0);
+    for (int j = 0; j < nb; j += 2) {
+        load(RB, j + 1);
+        consume(RA, j);
+        load(RA, j + 2);
+        consume(RB, j + 1);
+    }
+    if (live && la.z_out) {
+        la.z_out[i] = z[0]; la.z_out[(int64_t)n + i] = z[1]; la.z_out[2 * (int64_t)n + i] = z[2];
+    }
+}
+
+}  // namespace
+}  // namespace dpenv
+
+using namespace dpenv;
+
+hipError_t dev::launch_controller_label(const ControlArgs* ca, const LabelArgs* la, const float4* tab, int obs_bf16, hipStream_t s)
+{
+    if (la->n <= 0 || la->T <= 0 || !la->obs || !la->act) return hipErrorInvalidValue;
+    const dim3 grid((la->n + 63) / 64), block(64);
+    if (tab) {
+        if (obs_bf16) hipLaunchKernelGGL((controller_label_kernel<true, true>), grid, block, 0, s, *ca, *la, tab);
+        else hipLaunchKernelGGL((controller_label_kernel<true, false>), grid, block, 0, s, *ca, *la, tab);
+    } else {
+        if (obs_bf16) hipLaunchKernelGGL((controller_label_kernel<false, true>), grid, block, 0, s, *ca, *la, tab);
+        else hipLaunchKernelGGL((controller_label_kernel<false, false>), grid, block, 0, s, *ca, *la, tab);
+    }
+    return hipGetLastError();
+}

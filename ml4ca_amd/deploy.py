@@ -495,6 +495,37 @@ class BatchedDPController(object):
             self.z[mask] = 0
 
 
+def label_rows(params_or_table, obs, done=None, z=None, dt=0.2, dtype=None):
+    """The baseline's actions on a block of observation rows some other flight wrote - the host statement of dpenv_controller_label
+    (policy.controller_label), NumPy on the CPU.  obs [T, n, >= 6] (columns 0:6 read), done [T, n] (any non-zero byte ends an episode) or
+    None, z [3, n] the integral each env starts from (get_dp_controller_state's layout) or None = 0.  Per row t, in this order:
+        tau = ctrl.wrench(obs[t]);  act[t] = ctrl.allocate(tau);  ctrl.reset(done[t] != 0)
+    - z is advanced before the wrench and zeroed BEHIND a done row, so the next row is a new episode's first.  params_or_table: the dict
+    of dp_controller_defaults (None = the defaults) or a public table [32, n], as BatchedDPController takes them; dt the control period.
+    Returns (act [T, n, 7], z [3, n]) in dtype (None = float32, which reproduces the kernel's bits); labelling rows [0:k] and [k:T] with z
+    handed over equals one call."""
+    obs = np.asarray(obs)
+    if obs.ndim != 3 or obs.shape[2] < 6:
+        raise ValueError('label_rows: obs is [T, n, >= 6]')
+    T, n = obs.shape[0], obs.shape[1]
+    if done is not None:
+        done = np.asarray(done)
+        if done.shape != (T, n):
+            raise ValueError('label_rows: done is [T, n]')
+    ctrl = BatchedDPController(n, params_or_table, dt=dt, dtype=dtype)
+    if z is not None:
+        z = np.asarray(z)
+        if z.shape != (3, n):
+            raise ValueError('label_rows: z is [3, n]')
+        ctrl.z = np.ascontiguousarray(z.T).astype(ctrl.dtype)
+    act = np.empty((T, n, 7), ctrl.dtype)
+    for t in range(T):
+        act[t] = ctrl.allocate(ctrl.wrench(obs[t]))
+        if done is not None:
+            ctrl.reset(done[t] != 0)
+    return act, np.ascontiguousarray(np.asarray(ctrl.z).T)
+
+
 class RLAllocatorNode(object):
     """The node's callbacks as plain methods (rl_allocator.py:168-220).  `actor(state[9]) -> action[act_dim]` is any
     callable: ActorCritic.forward_ref on the CPU, or policy_forward on the GPU for one env."""

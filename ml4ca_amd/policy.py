@@ -320,3 +320,41 @@ def controller_rollout(env, T, switch_steps=(), refs=None, out=None):
         io.ref_out = out['ref'].data_ptr()
     _lib.check(env.lib.dpenv_controller_rollout(env._h, C.byref(io), env._stream()), env._h)
     return out
+
+
+def controller_label(env, obs, done=None, z=None, out=None):
+    """The baseline DP controller's actions on a block of rows some OTHER flight wrote (dpenv_controller_label), in one launch: expert
+    labels for the states an actor visited, or the baseline's answer beside the actor's on the same states.  obs [T, n, 9] float32 or
+    bfloat16 on the env's device (the block's own dtype, whatever the env writes), rows in policy_rollout's conventions; done [T, n]
+    uint8 or None (no episode ends in the block); z [3, n] float32, the integral every env starts from (get_dp_controller_state's
+    layout), or None = 0.  Per row: the law of env.set_dp_controller - row i of the table while set_dp_controller_table has one in
+    force - on obs[t], z advanced first and zeroed behind a done row.  Returns (act [T, n, 7], z [3, n]); out = (act, z) supplies the
+    buffers (z may be the input tensor itself).  Nothing of the env changes: not its state, not its own z, not a counter.  For float32
+    rows of controller_rollout with auto-reset on the labels are that launch's act rows bit for bit.  deploy.label_rows is the host
+    statement."""
+    torch = _torch()
+    n, ad = env.n_envs, env.num_actions
+    dev, f32 = env.device, torch.float32
+    if not isinstance(obs, torch.Tensor) or obs.dim() != 3:
+        raise ValueError('controller_label: obs is a tensor [T, n, 9]')
+    if obs.dtype not in (torch.float32, torch.bfloat16):
+        raise ValueError('controller_label: obs rows are float32 or bfloat16, not %s' % (obs.dtype,))
+    T = int(obs.shape[0])
+    env._chk(obs, (T, n, 9), obs.dtype, 'obs')
+    env._chk(done, (T, n), torch.uint8, 'done')
+    env._chk(z, (3, n), f32, 'z')
+    if out is None:
+        out = (torch.empty((T, n, ad), dtype=f32, device=dev), torch.empty((3, n), dtype=f32, device=dev))
+    act, z_out = out
+    env._chk(act, (T, n, 7), f32, 'out[0]')
+    env._chk(z_out, (3, n), f32, 'out[1]')
+    io = _lib.ControllerLabelIO()
+    io.struct_size = C.sizeof(_lib.ControllerLabelIO)
+    io.T = T
+    io.obs = obs.data_ptr()
+    io.obs_dtype = 1 if obs.dtype == torch.bfloat16 else 0
+    io.done = done.data_ptr() if done is not None else None
+    io.z_in = z.data_ptr() if z is not None else None
+    io.z_out, io.act = z_out.data_ptr(), act.data_ptr()
+    _lib.check(env.lib.dpenv_controller_label(env._h, C.byref(io), env._stream()), env._h)
+    return act, z_out

@@ -433,6 +433,70 @@ class PPOUpdater(object):
             self._pi_steps_host += iters                               # ungated: every queued step was taken
         return out
 
+    # ---- DAgger: expert labels on the states the ACTOR visits, aggregated over rounds (Ross et al. 2011) ----
+    def dagger(self, env, rounds, T, iters, minibatch=None, loss='mse', keep=None, sample=False, reset_at_end=False, lr=None, average=None,
+               upload=None):
+        """`rounds` x (fly the actor, label its states with the baseline DP controller, aggregate, refit).  env: a float32-row env with
+        the baseline on (env.set_dp_controller; a table of set_dp_controller_table in force is the one that labels).  Per round:
+          1. ac.upload(env, **upload)                       (upload: keyword arguments of ActorCritic.upload, e.g. dict(precision='f32'))
+          2. policy_rollout(env, T, sample=sample, reset_at_end=reset_at_end): the learner flies, T x n rows
+          3. policy.controller_label on the block's obs / done: the expert's action on every state the learner saw.  The expert's
+             integral z is carried along each env's rows, zeroed behind a done row, handed from round to round by this driver and zeroed
+             when reset_at_end cuts every env
+          4. the round's obs and labels go into slot `round % keep` of a preallocated [keep * T * n] dataset (keep=None: every round has
+             its own slot); the labels are written there by the kernel
+          5. pretrain(dataset[:filled], iters, minibatch, loss, lr=lr, average=average, keep_optimizer_state=True)
+        Returns one record per round: dict(history=[iters, 4] imitation statistics (pretrain's), reward_per_step=the actor's mean reward
+        on that round's flight, label_msd=the mean squared distance between the actor's act rows and the labels, rows=dataset rows fitted).
+        The dataset stays on the updater as self.dagger_data = dict(obs [keep * T * n, od], act [.., ad], filled, T, n, keep).  The only
+        host reads are pretrain's one per round and one for the flight figures after the last round.  Adam's state runs on through the
+        rounds and is left as it is; the caller uploads the final actor where it wants it flown.
+        A memoryless actor cannot represent ki * z: the labels depend on the integral, the actor sees o alone.  A caller who wants a target
+        the actor can represent labels with a ki = 0 controller or table.
+        Not here: beta-mixed flights in which the expert executes some of the steps, an integral-augmented actor, bf16 rows (the gradient
+        kernels take float32 rows: a bf16 env raises ValueError)."""
+        torch = _torch()
+        from .policy import controller_label, policy_rollout
+        rounds, T, iters = int(rounds), int(T), int(iters)
+        if rounds < 1 or T < 1 or iters < 1:
+            raise ValueError('dagger: rounds, T and iters are >= 1')
+        if env.obs_torch_dtype != torch.float32:
+            raise ValueError('dagger: the gradient kernels take float32 rows; make the env with float32 obs rows (got %s)' % (env.obs_torch_dtype,))
+        if env.dp_controller is None:
+            raise ValueError('dagger: the baseline DP controller labels the rows; env.set_dp_controller() first')
+        keep = rounds if keep is None else int(keep)
+        if keep < 1:
+            raise ValueError('dagger: keep >= 1')
+        keep = min(keep, rounds)
+        n, od, ad = env.n_envs, env.num_states, env.num_actions
+        dev, f32 = self.device, torch.float32
+        R = T * n
+        data_obs = torch.empty((keep * R, od), dtype=f32, device=dev)
+        data_act = torch.empty((keep * R, ad), dtype=f32, device=dev)
+        self.dagger_data = dict(obs=data_obs, act=data_act, filled=0, T=T, n=n, keep=keep)
+        z = torch.zeros((3, n), dtype=f32, device=dev)
+        flight = torch.zeros((rounds, 2), dtype=torch.float64, device=dev)
+        out, records = None, []
+        for r in range(rounds):
+            self.ac.upload(env, **(upload or {}))
+            out = policy_rollout(env, T, out=out, sample=sample, reset_at_end=reset_at_end)
+            slot = r % keep
+            labels = data_act[slot * R:(slot + 1) * R].view(T, n, ad)
+            controller_label(env, out['obs'], out['done'], z=z, out=(labels, z))
+            if reset_at_end:
+                z.zero_()
+            data_obs[slot * R:(slot + 1) * R].copy_(out['obs'].view(R, od))
+            filled = min(r + 1, keep) * R
+            self.dagger_data['filled'] = filled
+            flight[r, 0] = out['rew'].mean()
+            flight[r, 1] = ((out['act'] - labels) ** 2).mean()
+            hist = self.pretrain(data_obs[:filled], data_act[:filled], iters, minibatch=minibatch, loss=loss, lr=lr, average=average,
+                                 keep_optimizer_state=True)
+            records.append(dict(history=hist, rows=filled))
+        for rec, (rew, msd) in zip(records, flight.tolist()):
+            rec['reward_per_step'], rec['label_msd'] = rew, msd
+        return records
+
     def pretrain_critic(self, obs, ret, iters, minibatch=None, lr=None, average=None, keep_optimizer_state=False):
         """The critic's half of the warm start: `iters` x (value_grad -> adam_step) on ret [N] (the demonstration's discounted returns).
         Returns the [iters, 1] history of v_loss, read back once; the critic's Adam state is then zeroed unless keep_optimizer_state."""

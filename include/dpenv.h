@@ -311,7 +311,25 @@ typedef struct dpenv_mlp {
  * the reference's fp32 TF1 networks is claimed on; three times the matrix work of F16.
  * F32_ACTOR: the actor (mu, and with it the sampled action and logp) in the F32 arithmetic, the critic in the F16 arithmetic: what a
  * PPO update needs exactly is the log-likelihood (the ratio exp(logp_new - logp_old) then starts at 1); values carry the F16 mode's
- * ~5e-4 and are bit-identical to the F16 mode's.  Two thirds of the matrix work of F32. */
+ * ~5e-4 and are bit-identical to the F16 mode's.  Two thirds of the matrix work of F32.
+ * SUPPORTED RANGE of these figures (tests/policy_edges.py domain(), measured in DESIGN.md section 4).  Every mode passes the
+ * observation and every hidden activation through f16: their magnitudes must stay below 2^15 (f16 ends at 65 504).  An env whose
+ * observation or hidden value leaves f16's range gets meaningless rows - non-finite mu, v, action and logp in every mode, except F16
+ * with tanh, where the infinite pre-activation saturates to +-1 and the rows are finite and wrong - for that env alone: every other
+ * env of the launch, the other columns of its MFMA tile and the other wave of its pair included, keeps its rows bit for bit.  An fp32
+ * network is finite there; the library neither rescales nor clamps.  Below 2^15, with S = the largest |output| and never less than 1:
+ *   leaky-relu / relu: F32 within 1e-5 S, F16 within 2e-3 S (5e-4 S is typical, 1e-3 S the largest measured) at every observation and
+ *     weight scale - the output scale grows with the input's, and the error with it; exact zeros and f16-subnormal inputs included.
+ *   tanh: its outputs stay O(1) while the rounding of the first layer's inputs grows with them, so the figures hold only while
+ *     growth = max(1, max|obs| / 16) x weight scale  is at most 2^5 in F32 and at most 2 in F16, with weight scale = the largest
+ *     max|W| / sqrt(6 / (fan_in + fan_out)) over the dense kernels of both networks and never less than 1 (it is 1 at the
+ *     glorot-uniform initialisation).  The limits are conservative and come from a CPU model of this arithmetic, swept at weights
+ *     x 1, x 2, x 4: F32 stays below 4e-6 S up to growth 2^5 and first misses 1e-5 S at 2^7; F16 stays below 1e-3 S up to growth 2
+ *     and first misses 2e-3 S at 2^3.  Measured on the device beyond them: F16 off by 5.9e-3 S at growth 57 (max|obs| 909) and by
+ *     1.5e-2 S at growth 114; at growth 4 (weights x 4, |obs| < 16) F16 is at 1.1e-3 S - still within 2e-3 S, but not promised.
+ * At log_std = -4 (std = e^-4, the lower clamp of examples/train_ppo.py) an error of mu is 55 x as large in z.  Measured with noise
+ * up to +-5 (summed terms of logp up to 87): F32 / F32_ACTOR are within 9e-5 in logp and the first PPO ratio of dpenv_ppo_actor_grad on
+ * those rows within 4e-7 of 1; F16's logp is off by 0.2 and a fresh update clips some of its rows. */
 enum { DPENV_POLICY_F16 = 0, DPENV_POLICY_F32 = 1, DPENV_POLICY_F32_ACTOR = 2 };
 /* Launch form of dpenv_policy_rollout.  TWO_WAVE: every 64 envs get an env wave and a network wave (pair-level LDS hand-over;
  * 256-env workgroups with both waves of a pair on one SIMD, or - while one round of them fits the chip, n_envs <= 128 x CUs -

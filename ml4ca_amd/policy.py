@@ -142,6 +142,13 @@ class ActorCritic(object):
         fp32 evaluation - the reference's networks are fp32, core.py:29-33) or 'f32_actor' (the actor - mu, action, logp - as in
         'f32', the critic as in 'f16': the PPO ratio is exact, values carry the fast mode's ~5e-4; ~1.5 x the speed of 'f32').
         launch_form: 'auto' | 'one_wave' | 'two_wave'.
+        SUPPORTED RANGE of those figures (include/dpenv.h; tests/policy_edges.py domain()): observations and hidden activations pass
+        through f16 in every mode, so their magnitudes must stay below 2^15.  An env outside that range gets meaningless rows
+        (non-finite; finite and wrong in 'f16' with tanh) for that env alone - every other env of the launch keeps its rows bit for
+        bit.  Below it, relative to S = max(largest |output|, 1): leaky / relu hold 1e-5 S ('f32') and 2e-3 S ('f16', 5e-4 S
+        typical) at every observation and weight scale; tanh only while growth = max(1, max|obs| / 16) x weight scale is at most
+        2^5 for 'f32' and at most 2 for 'f16', weight scale being the largest max|W| / sqrt(6 / (fan_in + fan_out)) over the dense
+        kernels, at least 1.
         Parameters that live on the env's device are handed over as DEVICE pointers: one packing kernel on the current stream,
         no host copy and no synchronisation; parameters elsewhere (CPU tensors) go through a host copy."""
         torch = _torch()

@@ -245,5 +245,36 @@ int main(int argc, char** argv)
            "randomised: obs %.17g rew %.17g table %.17g\n", n3, S3, same ? "exactly" : "DIFFERENT", refused ? "left the handle alone" : "CHANGED THE HANDLE", sums[0][0],
            sums[0][1], sums[0][2], sums[1][0], sums[1][1], sums[1][2]);
     CHECK(dpenv_destroy(h));
-    return same && refused ? 0 : 3;
+    h = NULL;
+
+    /* ---- the rate-limited QP thrust allocation, handle-free: 20 control steps towards one wrench, the thruster state carried in place ---- */
+    const int n4 = 1024, S4 = 20;
+    dpenv_qp_allocator qp;
+    CHECK(dpenv_qp_allocator_defaults(&qp));
+    float *tau4, *st4, *act4, *cost4;
+    if (hipMalloc((void**)&tau4, 4 * 3 * n4) != hipSuccess || hipMalloc((void**)&st4, 4 * 5 * n4) != hipSuccess ||
+        hipMalloc((void**)&act4, 4 * 7 * n4) != hipSuccess || hipMalloc((void**)&cost4, 4 * n4) != hipSuccess) {
+        fprintf(stderr, "hipMalloc failed\n");
+        return 1;
+    }
+    float* htau = (float*)malloc(4 * 3 * n4);
+    for (int i = 0; i < n4; ++i) {                                /* [3][n]: Fx, Fy, Mz */
+        htau[i] = 20.0f * (float)i / n4; htau[n4 + i] = -5.0f; htau[2 * n4 + i] = 4.0f;
+    }
+    hipMemcpy(tau4, htau, 4 * 3 * n4, hipMemcpyHostToDevice);
+    hipMemset(st4, 0, 4 * 5 * n4);
+    for (int t = 0; t < S4; ++t) CHECK(dpenv_thrust_alloc_qp(&qp, 0.2f, tau4, st4, st4, act4, cost4, n4, stream));
+    hipStreamSynchronize(stream);
+    float* hcost = (float*)malloc(4 * n4);
+    float* hact4 = (float*)malloc(4 * 7 * n4);
+    hipMemcpy(hcost, cost4, 4 * n4, hipMemcpyDeviceToHost);
+    hipMemcpy(hact4, act4, 4 * 7 * n4, hipMemcpyDeviceToHost);
+    double jsum = 0.0, asum = 0.0;
+    for (int i = 0; i < n4; ++i) jsum += hcost[i];
+    for (int i = 0; i < 7 * n4; ++i) asum += hact4[i];
+    qp.iterations = 0;
+    const int qp_refused = dpenv_thrust_alloc_qp(&qp, 0.2f, tau4, st4, st4, act4, cost4, n4, stream) == DPENV_EINVAL;
+    printf("c_abi_demo qp: %d envs x %d control steps of dpenv_thrust_alloc_qp; mean objective %.6g; checksum act %.17g; iterations = 0 %s\n", n4, S4,
+           jsum / n4, asum, qp_refused ? "refused" : "ACCEPTED");
+    return same && refused && qp_refused ? 0 : 3;
 }

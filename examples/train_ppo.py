@@ -40,7 +40,7 @@ def evaluate_actor(ac, dev, preset, precision, seed, out=print, eval_envs=1024, 
     fixed starts, deterministic policy) and the thesis' 4-corner box test with its two metrics - IAE (results/all_plots/common.py:60-74) and
     the energy-equivalent work of the thruster power model (box_test/plot_act.py:128-135,184-211)."""
     from ml4ca_amd import evaluate as EV
-    from ml4ca_amd.deploy import dp_controller_defaults
+    from ml4ca_amd.deploy import dp_controller_defaults, qp_allocator_defaults
     from ml4ca_amd.policy import policy_rollout
     nominal = ml4ca_amd.default_vessel(preset)
     env6 = ml4ca_amd.BatchedRevoltEnv(6, device=dev, auto_reset=False, testing=True, vessel_params=nominal)
@@ -74,7 +74,16 @@ def evaluate_actor(ac, dev, preset, precision, seed, out=print, eval_envs=1024, 
             sb = EV.baseline_box_test_streamed(envb, T=T, start=torch.zeros((3, nb), device=dev), chunk=50)
             out('eval  box test (1250 steps, %d envs), %-13s: baseline PID + pseudo-inverse IAE %.2f (worst env %.2f)  work bow/port/star %s' % (
                 nb, tag, float(sb['iae'].mean()), float(sb['iae'].max()), [round(float(x), 1) for x in sb['work'].mean(0)]))
-            return {'IAE': float(sb['iae'].mean()), 'IAE_worst': float(sb['iae'].max()), 'work': [float(x) for x in sb['work'].mean(0)]}
+            rb = {'IAE': float(sb['iae'].mean()), 'IAE_worst': float(sb['iae'].max()), 'work': [float(x) for x in sb['work'].mean(0)]}
+            if spread > 0:
+                return rb                                                  # (the QP allocation flies the shared hull only: no per-env hull blocks)
+            # the thesis' third contender: the same PID with the rate-limited QP allocation in place of the pseudo-inverse
+            envb.set_qp_allocator(qp_allocator_defaults(nominal))
+            sq = EV.baseline_box_test_streamed(envb, T=T, start=torch.zeros((3, nb), device=dev), chunk=50, allocator='qp')
+            out('eval  box test (1250 steps, %d envs), %-13s: baseline PID + QP allocation IAE %.2f (worst env %.2f)  work bow/port/star %s' % (
+                nb, tag, float(sq['iae'].mean()), float(sq['iae'].max()), [round(float(x), 1) for x in sq['work'].mean(0)]))
+            rb['qp'] = {'IAE': float(sq['iae'].mean()), 'IAE_worst': float(sq['iae'].max()), 'work': [float(x) for x in sq['work'].mean(0)]}
+            return rb
 
         env = make_env()
         ac.upload(env, precision=precision)

@@ -750,7 +750,8 @@ int dpenv_controller_rollout(dpenv_handle h, const dpenv_controller_rollout_io* 
  * changes no later row of any launch.  Stream-ordered, no allocation, no host synchronisation; one kernel node when captured into a
  * graph (a captured call flies whatever table the last packing wrote; the scalar numbers are those at capture).
  * DPENV_EINVAL with the reason in dpenv_last_error, before anything is launched or written: the controller off, a wrong struct_size,
- * T <= 0, NULL obs or act, an obs_dtype that is neither DPENV_F32 nor DPENV_BF16.  ml4ca_amd.deploy.label_rows is the host statement. */
+ * T <= 0, NULL obs or act, an obs_dtype that is neither DPENV_F32 nor DPENV_BF16.  ml4ca_amd.deploy.label_rows is the host statement.
+ * The labels are always the pseudo-inverse law's, also while dpenv_set_qp_allocator has the QP allocation in the closed loop. */
 typedef struct dpenv_controller_label_io {
     uint32_t struct_size;    /* sizeof(dpenv_controller_label_io), ABI check */
     int32_t T;
@@ -765,6 +766,103 @@ int dpenv_controller_label(dpenv_handle h, const dpenv_controller_label_io* io, 
 /* The stateless allocation of the law (its f_m, bow and stern lines) for n wrenches: tau device float[3][n] -> action_out device
  * float[n][7].  Handle-free, like dpenv_thrust_map; of c only G, kf, kr_bow and f_eps are read, the whole struct is validated. */
 int dpenv_thrust_alloc(const dpenv_dp_controller* c, const float* tau, float* action_out, int32_t n, dpenv_stream s);
+
+/* ---- the rate-limited QP thrust allocation: the thesis' third allocator (additive to ABI 6) ---------------------------------------------
+ * The reference's nonlinear "QP" allocator (src/qp/ROS/qp_allocator/src/qp_allocator.py:108-234) as a handle-free, STATEFUL map on the
+ * device: per env and control step a wrench tau and the thruster state in force go in, the new state and the final variant's
+ * continuous-angle action come out.  The formulation is the reference's; the solver is build-defined.  SLSQP is not ported, and neither
+ * are the +-s_bnd bound on the slack and the node's retry loop that widens it (:209-226): the slack is eliminated, which is the problem
+ * that loop converges to, so the solve cannot fail on an infeasible wrench - the wrench is followed as far as the rate limits allow.
+ *
+ * Unknowns x = (F_bow, F_port, F_star, a_port, a_star) in env order; the bow tunnel thruster's azimuth is fixed at pi / 2, so its column
+ * of B is (0, 1, lx_bow).  With x^- the state in force (F^-, a^-):
+ *     r(x) = B(a) F - tau                  B column i: (cos a_i, sin a_i, lx_i sin a_i - ly_i cos a_i)
+ *     J(x) = 1/2 sum_j w_slack_j r_j^2 + 1/2 w_power sum_i |F_i|^3 + 1/2 w_dalpha sum_i (a_i - a_i^-)^2 + 1/2 w_dforce sum_i (F_i - F_i^-)^2
+ *     lo_i = fmaxf(-f_max_i, F_i^- - dF_i)   hi_i = fminf(f_max_i, F_i^- + dF_i)      dF_i = force_rate_i * dt      (forces, i = 0..2)
+ *     lo_k = a_k^- - da_k                    hi_k = a_k^- + da_k                      da_k = azimuth_rate_k * dt    (azimuths, k = 0, 1)
+ * dF and da are one f32 product each, formed on the host.  Defaults (dpenv_qp_allocator_defaults; :52-58,116-150): w_slack (1, 1, 1),
+ * w_power 1, w_dalpha = w_dforce = 0.25, f_max (9, 20.5, 20.5) N, force_rate (10, 25, 25) N/s and azimuth_rate 5 pi / 12 rad/s - with
+ * dt = 0.2 s the reference's (2, 5, 5) N and pi / 12 per step - and the default hull's lever arms and thrust constants.
+ *
+ * SOLVER: `iterations` (K, 1..32, default 16) projected Levenberg-Marquardt steps with accept / reject from x = clip(x^-, lo, hi) (x^-
+ * itself wherever |F^-| <= f_max) and lambda = 0.  In f32, in exactly this order (-ffp-contract=off: no product below is fused into a
+ * sum; sqrtf and / are correctly rounded; clip(v, lo, hi) = fminf(fmaxf(v, lo), hi); sin / cos are the library's call-free polynomial,
+ * max abs error 9.2e-8):
+ *   evaluate(x):   (s_k, c_k) = sincos(a_k);   b3_k = lx_k * s_k - ly_k * c_k                         k = port, star
+ *     r_0 = (c_p * F_p + c_s * F_s) - tau_0
+ *     r_1 = ((F_b + s_p * F_p) + s_s * F_s) - tau_1
+ *     r_2 = ((lx_b * F_b + b3_p * F_p) + b3_s * F_s) - tau_2
+ *     Js = (w_slack_0 * (r_0 * r_0) + w_slack_1 * (r_1 * r_1)) + w_slack_2 * (r_2 * r_2)
+ *     Jp = (|F_b| * (F_b * F_b) + |F_p| * (F_p * F_p)) + |F_s| * (F_s * F_s)
+ *     e_i = x_i - x_i^-;   Ja = e_3 * e_3 + e_4 * e_4;   Jf = (e_0 * e_0 + e_1 * e_1) + e_2 * e_2
+ *     J = 0.5 * (((Js + w_power * Jp) + w_dalpha * Ja) + w_dforce * Jf)
+ *   per iteration, at the current x with its s, c, b3, r, J:
+ *   1. Jm [3][5], the Jacobian of r: column F_b = (0, 1, lx_b); column F_k = (c_k, s_k, b3_k);
+ *      column a_k = (-(F_k * s_k), F_k * c_k, F_k * (lx_k * c_k + ly_k * s_k))
+ *   2. wr_j = w_slack_j * r_j;  WJ[j][l] = w_slack_j * Jm[j][l];  g_l = (Jm[0][l] * wr_0 + Jm[1][l] * wr_1) + Jm[2][l] * wr_2, then
+ *      g_i = g_i + ((1.5 * w_power) * (F_i * |F_i|) + w_dforce * (F_i - F_i^-))  for the forces,  g_k = g_k + w_dalpha * (a_k - a_k^-)
+ *   3. H[k][l] = (Jm[0][k] * WJ[0][l] + Jm[1][k] * WJ[1][l]) + Jm[2][k] * WJ[2][l]  for l <= k (the lower triangle is H), then
+ *      H[i][i] = H[i][i] + ((3 * w_power) * |F_i| + w_dforce),  H[k][k] = H[k][k] + w_dalpha: Gauss-Newton, definite by its diagonal
+ *   4. H[k][k] = H[k][k] + lambda * H[k][k]
+ *   5. frozen_k = (x_k <= lo_k and g_k > 0) or (x_k >= hi_k and g_k < 0), with the g of step 2 and the H[k][k] of step 4; a frozen k
+ *      has g_k = 0, H[k][k] = 1 and zeros in the rest of its row and column
+ *   6. H = L D L' without pivoting, for j = 0..4:  v_m = L[j][m] * D_m (m < j);  D_j = H[j][j] - L[j][0] * v_0 - ... in order of m;
+ *      iD_j = 1 / D_j;  L[i][j] = (H[i][j] - L[i][0] * v_0 - ...) * iD_j (i > j).  y_i = -g_i - L[i][0] * y_0 - ... (m < i, in order);
+ *      d_i = y_i * iD_i - L[i+1][i] * d_{i+1} - ... (m > i, ascending), i = 4..0
+ *   7. x_t = clip(x + d, lo, hi);  evaluate(x_t)
+ *   8. J(x_t) < J(x): x = x_t, lambda = 0.25 * lambda;  else x stays, lambda = 8 * fmaxf(lambda, 0.125)
+ * J never increases, and x stays in [lo, hi].  PRECONDITION on the state a caller supplies (state_in, dpenv_set_qp_allocator_state): finite,
+ * and |F_i^-| <= f_max_i.  The law's own outputs meet it.  Then lo <= x^- <= hi and the start is x^- itself; a state with
+ * |F_i^-| > f_max_i + dF_i has lo_i > hi_i, clip then returns hi_i and "inside [lo, hi]" no longer holds for that force; a state that
+ * is not finite gives an action that is not finite.  Neither is checked: the state lives on the device.  A plain projected Gauss-Newton without step 8 does not converge on rate-infeasible jumps.
+ * After the last iteration F^- = F and a^- = a wrapped to [-pi, pi) (k = floorf((a + pi) * (0.5 / pi)), a^- = fmaf(-k, 2 pi, a); mapToPi
+ * :101-106,277), and
+ *     action = [ n_b, n_p, n_s, sin a_p, cos a_p, sin a_s, cos a_s ],   n_i = clip(copysignf(sqrtf(|F_i| / K_i), F_i) / 100, -1, 1)
+ * with K_i = F_i >= 0 ? kf_i : kr_i (:287-288) and the heads taken once more, of the un-wrapped a.  If any component of tau is not finite
+ * the env's state is left bit for bit what it was and the action is that state's - the node's rule for a failed solve (:267-269); no
+ * other env is affected.  cost_out gets the final J (NaN for such an env).
+ * ml4ca_amd.deploy.BatchedQPAllocator is the host statement of the law. */
+typedef struct dpenv_qp_allocator {
+    uint32_t struct_size;
+    int32_t iterations;          /* K, 1..32 */
+    float w_slack[3];            /* >= 0 */
+    float w_power;               /* >= 0 */
+    float w_dalpha, w_dforce;    /* > 0: they keep H definite */
+    float f_max[3];              /* >= 0 [N]: bow, port, star */
+    float force_rate[3];         /* >= 0 [N/s] */
+    float azimuth_rate[2];       /* >= 0 [rad/s]: port, star */
+    float lx[3], ly[3];          /* lever arms [m]: bow, port, star, finite (ly[0] is not used) */
+    float kf[3], kr[3];          /* thrust constants ahead / astern, > 0 */
+} dpenv_qp_allocator;
+int dpenv_qp_allocator_defaults(dpenv_qp_allocator* q);
+/* One control step for n envs, one lane per env.  Device pointers: tau float[3][n]; state_in float[5][n] = F_bow, F_port, F_star, a_port,
+ * a_star (NULL = zeros); state_out float[5][n] (NULL = not wanted; may be state_in); action_out float[n][7]; cost_out float[n] or NULL.
+ * dt [s] > 0 is the control period.  Refused with DPENV_EINVAL before anything is launched: a wrong struct_size, a number that is not
+ * finite, a weight < 0, w_dalpha or w_dforce <= 0, a bound or rate < 0, kf or kr <= 0, iterations outside 1..32, dt <= 0, n <= 0, NULL
+ * tau or action_out.  Stream-ordered, no allocation, no host synchronisation: graph-capturable, one kernel node.
+ * A caller with its own motion controller closes the loop with this call between two launches. */
+int dpenv_thrust_alloc_qp(const dpenv_qp_allocator* q, float dt, const float* tau, const float* state_in, float* state_out,
+                          float* action_out, float* cost_out, int32_t n, dpenv_stream s);
+/* The QP law as the allocation stage of the baseline's closed loop: while one is set, dpenv_controller_rollout (signature and rows
+ * unchanged) forms tau with the PID lines of the DP controller's law - z advanced, the wrench clipped to tau_max, bit for bit what they
+ * are without it - and allocates it with the law above in place of the f_m / bow / stern lines; dt is the handle's.  Per env the
+ * thruster state x^- [5] travels beside z: loaded with it, stored with it, and zeroed wherever z is zeroed - auto-reset (the new
+ * episode's first action starts from thrusters at rest), dpenv_reset for the envs it re-draws, and this call (every env).  So the act
+ * rows of a launch are dpenv_thrust_alloc_qp applied row by row to the PID's tau, bit for bit, and two launches of T/2 write the rows of
+ * one launch of T.
+ * Needs the DP controller on (it supplies tau, z and dt), else DPENV_EINVAL.  q = NULL returns the handle to the pseudo-inverse.
+ * dpenv_set_dp_controller (on or off) drops the QP, as it drops the table.  Supported: the shared hull and the thrust-loss preset (one
+ * class, hull as kernel arguments), constant, drifting and per-episode currents, auto-reset, with or without the reference filter.
+ * Per-env hull blocks and their randomisation, a per-env controller table in force (and dpenv_set_dp_controller_table while a QP is set),
+ * and whatever dpenv_set_dp_controller refuses: DPENV_EINVAL with the set named, at this call or - if the handle changed since - at the
+ * launch.  Every refusal of a q that dpenv_thrust_alloc_qp refuses happens before any state changes.  The first call allocates the state
+ * block (released with the handle); every later call is stream-ordered without allocation and graph-capturable.
+ * dpenv_controller_label keeps labelling with the pseudo-inverse law whatever is set here. */
+int dpenv_set_qp_allocator(dpenv_handle h, const dpenv_qp_allocator* q, dpenv_stream s);
+/* The checkpoint path of the thruster state, beside z's: device float[5][n_envs] = F_bow, F_port, F_star, a_port, a_star.  DPENV_EINVAL
+ * while no QP allocator is set. */
+int dpenv_get_qp_allocator_state(dpenv_handle h, float* state_out, dpenv_stream s);
+int dpenv_set_qp_allocator_state(dpenv_handle h, const float* state_in, dpenv_stream s);
 
 /* ---- The PPO update: actor and critic gradients and a device-gated Adam step --------------------------------------------------------
  * Handle-free like dpenv_gae / dpenv_adv_*: device pointers and a stream; no call allocates or synchronises, so a whole update (80

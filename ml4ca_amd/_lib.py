@@ -90,6 +90,12 @@ class DPController(C.Structure):
                 ('kr_bow', C.c_float), ('f_eps', C.c_float)]
 
 
+class QPAllocator(C.Structure):
+    _fields_ = [('struct_size', C.c_uint32), ('iterations', C.c_int32), ('w_slack', C.c_float * 3), ('w_power', C.c_float),
+                ('w_dalpha', C.c_float), ('w_dforce', C.c_float), ('f_max', C.c_float * 3), ('force_rate', C.c_float * 3),
+                ('azimuth_rate', C.c_float * 2), ('lx', C.c_float * 3), ('ly', C.c_float * 3), ('kf', C.c_float * 3), ('kr', C.c_float * 3)]
+
+
 class ControllerRolloutIO(C.Structure):
     _fields_ = [('struct_size', C.c_uint32), ('T', C.c_int32), ('obs', C.c_void_p), ('act', C.c_void_p), ('reward', C.c_void_p),
                 ('done', C.c_void_p), ('last_obs', C.c_void_p), ('ref_out', C.c_void_p), ('n_switch', C.c_int32),
@@ -189,6 +195,11 @@ SYMBOLS = {
     'dpenv_controller_rollout': (C.c_int, [_VP, C.POINTER(ControllerRolloutIO), _VP]),
     'dpenv_controller_label': (C.c_int, [_VP, C.POINTER(ControllerLabelIO), _VP]),
     'dpenv_thrust_alloc': (C.c_int, [C.POINTER(DPController), _VP, _VP, _I32, _VP]),
+    'dpenv_qp_allocator_defaults': (C.c_int, [C.POINTER(QPAllocator)]),
+    'dpenv_thrust_alloc_qp': (C.c_int, [C.POINTER(QPAllocator), _F, _VP, _VP, _VP, _VP, _VP, _I32, _VP]),
+    'dpenv_set_qp_allocator': (C.c_int, [_VP, C.POINTER(QPAllocator), _VP]),
+    'dpenv_get_qp_allocator_state': (C.c_int, [_VP, _VP, _VP]),
+    'dpenv_set_qp_allocator_state': (C.c_int, [_VP, _VP, _VP]),
     'dpenv_train_param_count': (C.c_int64, [C.POINTER(TrainShape)]),
     'dpenv_train_workspace_bytes': (C.c_int, [C.POINTER(TrainShape), _I32, C.POINTER(C.c_int64)]),
     'dpenv_ppo_actor_grad': (C.c_int, [C.POINTER(TrainShape), _VP, _VP, _VP, _VP, _VP, _VP, _I32, _I32, _F, _VP, _VP, _VP, _I64, _VP]),

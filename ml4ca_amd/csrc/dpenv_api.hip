@@ -81,6 +81,8 @@ struct dpenv_s {
     ControlArgs ctrl = {};  // its numbers and per-env state (float4 [n]: z | pad), allocated by the first dpenv_set_dp_controller
     bool ctrl_tab_on = false;    // dpenv_set_dp_controller_table: env i flies row i of ctrl_tab instead of ctrl's numbers
     float4* ctrl_tab = nullptr;  // the packed per-env controller block (ctrl_tab_float4s(n) float4), allocated by the first dpenv_set_dp_controller_table
+    bool qp_on = false;     // dpenv_set_qp_allocator: dpenv_controller_rollout allocates the PID's wrench with the QP law of `qp`
+    QpRollout qp = {};      // its numbers and per-env thruster state (float [5][n]), allocated by the first dpenv_set_qp_allocator
     int device = 0;
     std::string err;
 
@@ -96,6 +98,7 @@ struct dpenv_s {
         if (reff.state) (void)hipFree(reff.state);
         if (ctrl.z) (void)hipFree(ctrl.z);
         if (ctrl_tab) (void)hipFree(ctrl_tab);
+        if (qp.state) (void)hipFree(qp.state);
         for (int k = 0; k < 2; ++k) if (pol_read[k]) (void)hipEventDestroy(pol_read[k]);
         if (loss_ev) (void)hipEventDestroy(loss_ev);
         if (loss_host) (void)hipHostFree(loss_host);
@@ -579,6 +582,7 @@ extern "C" int dpenv_reset(dpenv_handle h, const uint8_t* mask, const float* ini
     if (h->integ_on) HIP_TRY(h, dev::launch_integ_clear(h->integ.state, mask, h->cfg.n_envs, (hipStream_t)s));   // new episodes start with I = 0
     if (h->reff_on) HIP_TRY(h, dev::launch_reff_rest(a.RF, h->reff.state, mask, h->cfg.n_envs, (hipStream_t)s));   // ... the filter at rest
     if (h->ctrl_on) HIP_TRY(h, dev::launch_control_state(h->ctrl.z, nullptr, mask, h->cfg.n_envs, 2, (hipStream_t)s));   // ... the baseline's z = 0
+    if (h->qp_on) HIP_TRY(h, dev::launch_qp_state_clear(h->qp.state, mask, h->cfg.n_envs, (hipStream_t)s));               // ... and its QP allocator's thrusters at rest
     // the reset kernel writes the lagged thrust columns (S3) of the envs it re-draws: a full reset makes them valid everywhere, a
     // masked one leaves the validity of the other envs' columns as it was (it used to drop the lag of every env)
     if (!mask) h->lag_valid = true;
@@ -1133,6 +1137,7 @@ extern "C" int dpenv_set_dp_controller(dpenv_handle h, const dpenv_dp_controller
     if (!c) {
         h->ctrl_on = false;
         h->ctrl_tab_on = false;
+        h->qp_on = false;
         return DPENV_OK;
     }
     ControlArgs g = {};
@@ -1146,8 +1151,13 @@ extern "C" int dpenv_set_dp_controller(dpenv_handle h, const dpenv_dp_controller
     h->ctrl = g;
     h->ctrl_on = true;
     h->ctrl_tab_on = false;                                // the scalar law again: a table in force is dropped
+    h->qp_on = false;                                      // ... and so is a QP allocator: the pseudo-inverse allocates again
     return DPENV_OK;
 }
+
+#define QP_SET_MSG                                                                                                                   \
+    "the QP allocator runs with the DP controller on and its scalar numbers (no per-env controller table), on the shared hull or the " \
+    "thrust-loss preset (no per-env hull blocks, one vessel class)"
 
 static_assert(CTRL_NPARAM == DPENV_CTRL_NPARAM && CTRL_KP == DPENV_CTRL_KP && CTRL_KD == DPENV_CTRL_KD && CTRL_KI == DPENV_CTRL_KI &&
                   CTRL_ZB == DPENV_CTRL_ZB && CTRL_TMAX == DPENV_CTRL_TMAX && CTRL_WEIGHT == DPENV_CTRL_WEIGHT && CTRL_LX == DPENV_CTRL_LX &&
@@ -1162,6 +1172,7 @@ extern "C" int dpenv_set_dp_controller_table(dpenv_handle h, const float* table,
         h->ctrl_tab_on = false;
         return DPENV_OK;
     }
+    if (h->qp_on) return fail(h, DPENV_EINVAL, "dpenv_set_dp_controller_table: " QP_SET_MSG);
     DeviceGuard dev_guard(h->device);
     if (!h->ctrl_tab) {                                    // (whole waves of 64 envs: not ensure_env_state's count x n_envs)
         void* p = nullptr;
@@ -1214,9 +1225,61 @@ extern "C" int dpenv_controller_rollout(dpenv_handle h, const dpenv_controller_r
     ca.use_lag = h->lag_valid ? 1 : 0;
     FilterArgs fa = h->reff;
     fa.out = io->ref_out;
-    const hipError_t e = dev::launch_controller_rollout(&a, &ca, h->reff_on ? &fa : nullptr, h->ctrl_tab_on ? h->ctrl_tab : nullptr, rollout_ves(vessel_source(h)), (hipStream_t)s);
+    const int ves = rollout_ves(vessel_source(h));
+    hipError_t e;
+    if (h->qp_on) {                                        // the handle may have changed since dpenv_set_qp_allocator
+        if (h->ctrl_tab_on || (ves != VES_ARGS && ves != VES_ARGS_LOSS)) return fail(h, DPENV_EINVAL, "dpenv_controller_rollout: " QP_SET_MSG);
+        e = dev::launch_controller_rollout_qp(&a, &ca, h->reff_on ? &fa : nullptr, &h->qp, ves, (hipStream_t)s);
+    } else {
+        e = dev::launch_controller_rollout(&a, &ca, h->reff_on ? &fa : nullptr, h->ctrl_tab_on ? h->ctrl_tab : nullptr, ves, (hipStream_t)s);
+    }
     if (e != hipSuccess) return fail(h, DPENV_EHIP, "controller launch failed: %s", hipGetErrorString(e));
     h->lag_valid = true;
+    return DPENV_OK;
+}
+
+// ---- the QP allocation as the closed loop's allocation stage (dpenv.h) ----
+extern "C" int dpenv_set_qp_allocator(dpenv_handle h, const dpenv_qp_allocator* q, dpenv_stream s)
+{
+    if (!h) return DPENV_EINVAL;
+    if (!q) {
+        h->qp_on = false;
+        return DPENV_OK;
+    }
+    if (!h->ctrl_on) return fail(h, DPENV_EINVAL, "dpenv_set_qp_allocator: the DP controller is off (dpenv_set_dp_controller first)");
+    QpArgs g = {};
+    if (const char* why = qp_check(q, h->ctrl.dt, g)) return fail(h, DPENV_EINVAL, "%s", why);
+    if (!control_config_ok(h)) return fail(h, DPENV_EINVAL, "dpenv_set_qp_allocator: " CONTROL_SET_MSG);
+    if (h->ctrl_tab_on || h->per_env) return fail(h, DPENV_EINVAL, "dpenv_set_qp_allocator: " QP_SET_MSG);
+    DeviceGuard dev_guard(h->device);
+    if (!h->qp.state) {
+        void* p = nullptr;
+        if (hipMalloc(&p, sizeof(float) * 5 * (size_t)h->cfg.n_envs) != hipSuccess) return fail(h, DPENV_ENOMEM, "hipMalloc of the QP allocator state failed");
+        h->qp.state = (float*)p;
+    }
+    HIP_TRY(h, dev::launch_qp_state_clear(h->qp.state, nullptr, h->cfg.n_envs, (hipStream_t)s));   // (the block stays if this fails)
+    h->qp.q = g;
+    h->qp_on = true;
+    return DPENV_OK;
+}
+
+extern "C" int dpenv_get_qp_allocator_state(dpenv_handle h, float* state_out, dpenv_stream s)
+{
+    if (!h) return DPENV_EINVAL;
+    if (!h->qp_on) return fail(h, DPENV_EINVAL, "dpenv_get_qp_allocator_state: no QP allocator is set");
+    if (!state_out) return fail(h, DPENV_EINVAL, "dpenv_get_qp_allocator_state: NULL argument");
+    DeviceGuard dev_guard(h->device);
+    HIP_TRY(h, hipMemcpyAsync(state_out, h->qp.state, sizeof(float) * 5 * (size_t)h->cfg.n_envs, hipMemcpyDeviceToDevice, (hipStream_t)s));
+    return DPENV_OK;
+}
+
+extern "C" int dpenv_set_qp_allocator_state(dpenv_handle h, const float* state_in, dpenv_stream s)
+{
+    if (!h) return DPENV_EINVAL;
+    if (!h->qp_on) return fail(h, DPENV_EINVAL, "dpenv_set_qp_allocator_state: no QP allocator is set");
+    if (!state_in) return fail(h, DPENV_EINVAL, "dpenv_set_qp_allocator_state: NULL argument");
+    DeviceGuard dev_guard(h->device);
+    HIP_TRY(h, hipMemcpyAsync(h->qp.state, state_in, sizeof(float) * 5 * (size_t)h->cfg.n_envs, hipMemcpyDeviceToDevice, (hipStream_t)s));
     return DPENV_OK;
 }
 

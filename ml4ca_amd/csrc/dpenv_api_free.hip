@@ -299,6 +299,74 @@ extern "C" int dpenv_thrust_alloc(const dpenv_dp_controller* c, const float* tau
     return DPENV_OK;
 }
 
+// ---- the rate-limited QP thrust allocation (dpenv.h; the kernel is dpenv_qp.hip's) -----------------------------------------------------
+extern "C" int dpenv_qp_allocator_defaults(dpenv_qp_allocator* q)
+{
+    if (!q) return fail(nullptr, DPENV_EINVAL, "dpenv_qp_allocator_defaults: q is NULL");
+    std::memset(q, 0, sizeof *q);
+    q->struct_size = (uint32_t)sizeof *q;
+    q->iterations = 16;
+    float v[DPENV_NPARAM];
+    dpenv_default_vessel(v);
+    const float f_max[3] = {9.0f, 20.5f, 20.5f};                 // qp_allocator.py:52, env order
+    const float rate[3] = {10.0f, 25.0f, 25.0f};                 // :57: 2, 5, 5 N per 0.2 s step
+    for (int k = 0; k < 3; ++k) {
+        q->w_slack[k] = 1.0f;                                    // :116-150
+        q->f_max[k] = f_max[k];
+        q->force_rate[k] = rate[k];
+        q->lx[k] = v[DPENV_P_LX_BOW + k]; q->ly[k] = v[DPENV_P_LY_BOW + k];
+        q->kf[k] = v[DPENV_P_KF_BOW + k]; q->kr[k] = v[DPENV_P_KR_BOW + k];
+    }
+    q->w_power = 1.0f;
+    q->w_dalpha = q->w_dforce = 0.25f;
+    q->azimuth_rate[0] = q->azimuth_rate[1] = (float)(5.0 * 3.14159265358979323846 / 12.0);   // :58: pi / 12 per 0.2 s step
+    return DPENV_OK;
+}
+
+// validates q and dt and forms the kernel's numbers; the reason for a refusal, or NULL
+const char* host::qp_check(const dpenv_qp_allocator* q, float dt, QpArgs& g)
+{
+    if (q->struct_size != sizeof(dpenv_qp_allocator)) return "dpenv_qp_allocator ABI mismatch";
+    if (q->iterations < 1 || q->iterations > QP_MAX_ITERS) return "QP allocator: iterations must be in 1..32";
+    if (!std::isfinite(dt) || !(dt > 0.0f)) return "QP allocator: dt must be finite and > 0";
+    for (int k = 0; k < 3; ++k) {
+        if (!std::isfinite(q->w_slack[k]) || q->w_slack[k] < 0.0f) return "QP allocator: w_slack must be finite and >= 0";
+        if (!std::isfinite(q->f_max[k]) || q->f_max[k] < 0.0f) return "QP allocator: f_max must be finite and >= 0";
+        if (!std::isfinite(q->force_rate[k]) || q->force_rate[k] < 0.0f) return "QP allocator: force_rate must be finite and >= 0";
+        if (!std::isfinite(q->lx[k]) || !std::isfinite(q->ly[k])) return "QP allocator: lever arms must be finite";
+        if (!std::isfinite(q->kf[k]) || !(q->kf[k] > 0.0f)) return "QP allocator: kf must be finite and > 0";
+        if (!std::isfinite(q->kr[k]) || !(q->kr[k] > 0.0f)) return "QP allocator: kr must be finite and > 0";
+    }
+    for (int k = 0; k < 2; ++k)
+        if (!std::isfinite(q->azimuth_rate[k]) || q->azimuth_rate[k] < 0.0f) return "QP allocator: azimuth_rate must be finite and >= 0";
+    if (!std::isfinite(q->w_power) || q->w_power < 0.0f) return "QP allocator: w_power must be finite and >= 0";
+    if (!std::isfinite(q->w_dalpha) || !(q->w_dalpha > 0.0f)) return "QP allocator: w_dalpha must be finite and > 0";
+    if (!std::isfinite(q->w_dforce) || !(q->w_dforce > 0.0f)) return "QP allocator: w_dforce must be finite and > 0";
+    for (int k = 0; k < 3; ++k) {
+        g.ws[k] = q->w_slack[k]; g.fmax[k] = q->f_max[k]; g.dF[k] = q->force_rate[k] * dt;
+        g.lx[k] = q->lx[k]; g.ly[k] = q->ly[k]; g.kf[k] = q->kf[k]; g.kr[k] = q->kr[k];
+        if (!std::isfinite(g.dF[k])) return "QP allocator: force_rate * dt overflows";
+    }
+    for (int k = 0; k < 2; ++k) {
+        g.da[k] = q->azimuth_rate[k] * dt;
+        if (!std::isfinite(g.da[k])) return "QP allocator: azimuth_rate * dt overflows";
+    }
+    g.wp = q->w_power; g.wda = q->w_dalpha; g.wdf = q->w_dforce;
+    g.iters = q->iterations;
+    return nullptr;
+}
+
+extern "C" int dpenv_thrust_alloc_qp(const dpenv_qp_allocator* q, float dt, const float* tau, const float* state_in, float* state_out,
+                                     float* action_out, float* cost_out, int32_t n, dpenv_stream s)
+{
+    if (!q || !tau || !action_out || n <= 0) return fail(nullptr, DPENV_EINVAL, "dpenv_thrust_alloc_qp: bad argument");
+    QpArgs g = {};
+    if (const char* why = qp_check(q, dt, g)) return fail(nullptr, DPENV_EINVAL, "%s", why);
+    const QpAllocIO io = {tau, state_in, state_out, action_out, cost_out, n};
+    HIP_TRY(nullptr, dev::launch_qp_alloc(&g, &io, (hipStream_t)s));
+    return DPENV_OK;
+}
+
 extern "C" int dpenv_thrust_map(const float* params, const float* n_pct, const float* alpha, float* tau_out, int32_t n,
                                 dpenv_stream s)
 {

@@ -11,6 +11,8 @@
 
 // the law itself - ControlLane, ctrl_tab_index, load_control_lane, dp_allocate, dp_control - shared with the labelling scan (dpenv_label.hip)
 #include "dpenv_control_law.h"
+// the QP allocation, the other allocation stage the closed loop's body can be compiled with (controller_rollout_qp_kernel, dpenv_qp.hip)
+#include "dpenv_qp_law.h"
 
 // A wave's 64 rows of W floats to a [.][n][W] block: staged through the wave-private LDS area, stored coalesced - wave_store_rows /
 // store_rows (dpenv_policy_dev.h, dpenv_env_dev.h) restated.  A copy on purpose: instantiating those two templates for W = 9 and 7 a second
@@ -48,8 +50,9 @@ __device__ __forceinline__ void control_store_rows(float* lds, void* dst, int64_
 template <int VES, bool REFF>
 __global__ __launch_bounds__(RBLOCK) void controller_rollout_kernel(const StepArgs a, const ControlArgs ca, const FilterArgs fa)
 {
-    constexpr bool TAB = false;
+    constexpr bool TAB = false, QP = false;
     const float4* const tab = nullptr;
+    const QpRollout qr = {};
 #include "dpenv_control_rollout_body.inc"
 }
 
@@ -59,7 +62,8 @@ template <int VES, bool REFF>
 __global__ __launch_bounds__(RBLOCK) void controller_rollout_tab_kernel(const StepArgs a, const ControlArgs ca, const FilterArgs fa,
                                                                          const float4* __restrict__ tab)
 {
-    constexpr bool TAB = true;
+    constexpr bool TAB = true, QP = false;
+    const QpRollout qr = {};
 #include "dpenv_control_rollout_body.inc"
 }
 

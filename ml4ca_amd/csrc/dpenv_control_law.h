@@ -67,17 +67,24 @@ __device__ __forceinline__ void dp_allocate(const C& c, const float tau[3], floa
     }
 }
 
-// one control step of the law on the observation o (e = o[0:3], nu = o[3:6]): the integral first, then the wrench, then the allocation
+// the PID lines of one control step on the observation o (e = o[0:3], nu = o[3:6]): the integral first, then the clipped wrench
 template <class C>
-__device__ __forceinline__ void dp_control(const C& c, const float o[9], float z[3], float act[7])
+__device__ __forceinline__ void dp_wrench(const C& c, const float o[9], float z[3], float tau[3])
 {
-    float tau[3];
 #pragma unroll
     for (int j = 0; j < 3; ++j) {
         z[j] = fminf(fmaxf(z[j] + c.dt * o[j], -c.zb[j]), c.zb[j]);
         const float t = -((c.kp[j] * o[j] + c.kd[j] * o[3 + j]) + c.ki[j] * z[j]);
         tau[j] = fminf(fmaxf(t, -c.tmax[j]), c.tmax[j]);
     }
+}
+
+// one control step of the law: the integral, the wrench, then the pseudo-inverse allocation
+template <class C>
+__device__ __forceinline__ void dp_control(const C& c, const float o[9], float z[3], float act[7])
+{
+    float tau[3];
+    dp_wrench(c, o, z, tau);
     dp_allocate(c, tau, act);
 }
 

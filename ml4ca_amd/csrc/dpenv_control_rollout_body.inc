@@ -1,7 +1,8 @@
 // dpenv_control_rollout_body.inc - the body of controller_rollout_kernel and controller_rollout_tab_kernel (dpenv_control_dev.h), included
 // into each (see dpenv_policy_rollout_body.inc for why it is spliced, not called).  In scope: a (StepArgs), ca (ControlArgs), fa
-// (FilterArgs), the compile-time TAB and, if TAB, tab (the packed per-env controller block, ctrl_tab_index); the rest are
-// the kernel's template arguments.
+// (FilterArgs), the compile-time TAB and, if TAB, tab (the packed per-env controller block, ctrl_tab_index), the compile-time QP and, if QP,
+// qr (QpRollout: the rate-limited QP allocation of dpenv_qp_law.h in place of dp_allocate, its thruster state carried beside z); the
+// rest are the kernel's template arguments.
     constexpr int MODE = MODE_FINAL_CONT;
     constexpr bool EXT = true;
     constexpr int A = 7, OD = 9;
@@ -54,6 +55,11 @@
         const float4 q = ca.z[il];
         z[0] = q.x; z[1] = q.y; z[2] = q.z;
     }
+    float xq[5] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f};                // QP: the thruster state in force
+    if constexpr (QP) {
+#pragma unroll
+        for (int k = 0; k < 5; ++k) xq[k] = qr.state[(int64_t)k * n + il];
+    }
     ReffState fs{};
     if constexpr (REFF) {
         fs = reff_load(fa, il, n);
@@ -65,7 +71,11 @@
     for (int t = 0; t < ca.T; ++t) {
         control_store_rows<OD>(lds_row, ca.obs, (int64_t)t * stride_o + w_o, rem_o, o, tid, a.obs_bf16 != 0);
         float act[A];
-        if constexpr (TAB) dp_control(cl, o, z, act);
+        if constexpr (QP) {                                      // the PID's wrench, allocated by the QP law
+            float tau[3], J;
+            dp_wrench(ca, o, z, tau);
+            qp_allocate(qr.q, tau, xq, act, J);
+        } else if constexpr (TAB) dp_control(cl, o, z, act);
         else dp_control(ca, o, z, act);
         control_store_rows<A>(lds_row, ca.act, (int64_t)t * stride_a + w_a, rem_a, act, tid, false);
 
@@ -98,6 +108,10 @@
             if (CURR && a.cur_nom) { current_redraw_inline(a, i, episode, cur, vc0, beta0); cur_dirty = true; }  // ... in a new current
             ++episode; ep_dirty = true; rf_dirty = true;
             z[0] = z[1] = z[2] = 0.0f;                           // the new episode's first action is the law at z = 0
+            if constexpr (QP) {                                  // ... and from thrusters at rest
+#pragma unroll
+                for (int k = 0; k < 5; ++k) xq[k] = 0.0f;
+            }
             if constexpr (REFF) {                                // ... and the filter at rest on its reference
                 reff_rest(fs, s.refN, s.refE, s.refPsi);
                 if (t + 1 < ca.T) reff_row(fa, t + 1, n, i, live, s.refN, s.refE, s.refPsi);
@@ -114,6 +128,10 @@
         store_env(a, i, s, rf_dirty);
         a.S3[i] = make_float4(o[6], o[7], o[8], 0.0f);
         ca.z[i] = make_float4(z[0], z[1], z[2], 0.0f);
+        if constexpr (QP) {
+#pragma unroll
+            for (int k = 0; k < 5; ++k) qr.state[(int64_t)k * n + i] = xq[k];
+        }
         if (ep_dirty) a.episode[i] = (int)episode;
         if (a.current_drift) { a.cur_vc[i] = cur.vc; a.cur_beta[i] = cur.beta; a.drift_ctr[i] = cur.ctr; }
         if (CURR && cur_dirty) store_current(a, i, cur, vc0, beta0, true);

@@ -231,6 +231,31 @@ struct ControlArgs {
     const float* refs;        // [n_switch][3][n]
 };
 
+// the rate-limited QP thrust allocation (dpenv_thrust_alloc_qp; include/dpenv.h has the law, dpenv_qp_law.h its device text, dpenv_qp.hip
+// the kernel): the law's numbers in env order bow, port, star, and the I/O of one call
+struct QpArgs {
+    float ws[3], wp, wda, wdf;  // slack, power, azimuth-change and force-change weights
+    float fmax[3];
+    float dF[3], da[2];         // per control step: force_rate * dt, azimuth_rate * dt, each one f32 product formed on the host
+    float lx[3], ly[3], kf[3], kr[3];
+    int32_t iters;              // 1 .. QP_MAX_ITERS
+};
+constexpr int QP_MAX_ITERS = 32;
+// the allocation as the allocation stage of the baseline's closed loop (dpenv_set_qp_allocator): the numbers and the per-env thruster
+// state, a separate argument of controller_rollout_qp_kernel only
+struct QpRollout {
+    QpArgs q;
+    float* state;               // [5][n], dpenv_get_qp_allocator_state's layout
+};
+struct QpAllocIO {
+    const float* tau;           // [3][n]
+    const float* state_in;      // [5][n] F_bow, F_port, F_star, a_port, a_star, or NULL = 0
+    float* state_out;           // [5][n] or NULL; may be state_in
+    float* act;                 // [n][7]
+    float* cost;                // [n] the final objective, or NULL
+    int32_t n;
+};
+
 // device-side weight packing (pack_policy_kernel): one dense network, DEVICE pointers
 struct PackNet {
     const float* W[5];        // W[l][in][out] row-major (tf.layers.dense kernel layout)
@@ -455,6 +480,12 @@ hipError_t launch_thrust_alloc(const ControlArgs* ca, const float* tau, float* a
 // dpenv_label.hip: the law scanned over the T rows of a block, one lane per env (tab as launch_controller_rollout's; obs_bf16: the obs rows
 // are bf16); reads ca's numbers and dt only
 hipError_t launch_controller_label(const ControlArgs* ca, const LabelArgs* la, const float4* tab, int obs_bf16, hipStream_t s);
+// dpenv_qp.hip: one control step of the QP allocation for n envs, one lane per env
+hipError_t launch_qp_alloc(const QpArgs* qa, const QpAllocIO* io, hipStream_t s);
+// the baseline's closed loop with the QP allocation in place of the pseudo-inverse (fa, ves as launch_controller_rollout's; VES_ARGS and
+// VES_ARGS_LOSS only), and the zeroing of its state for the envs of mask (NULL = every env)
+hipError_t launch_controller_rollout_qp(const StepArgs* a, const ControlArgs* ca, const FilterArgs* fa, const QpRollout* qr, int ves, hipStream_t s);
+hipError_t launch_qp_state_clear(float* state, const uint8_t* mask, int n, hipStream_t s);
 // two-wave closed loop, dpenv_policy_ws.h; one arithmetic per translation unit: dpenv_policy_ws.hip PREC_F16, dpenv_policy_xws1.hip
 // PREC_F32, dpenv_policy_xws2.hip PREC_F32_ACTOR
 template <int PREC>

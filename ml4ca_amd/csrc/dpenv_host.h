@@ -46,6 +46,8 @@ int derive_vessel(const float* p, VesselDev* d, std::string* why, bool allow_los
 const char* reff_coeffs_f32(const dpenv_reference_filter* rf, float dt, float phi[3][9], float gam[3][3]);
 // the law's numbers into ControlArgs, or an error message
 const char* control_check(const dpenv_dp_controller* c, ControlArgs& g);
+// the QP allocation's numbers for the control period dt into QpArgs, or an error message
+const char* qp_check(const dpenv_qp_allocator* q, float dt, QpArgs& g);
 
 }  // namespace host
 }  // namespace dpenv

@@ -526,6 +526,195 @@ def label_rows(params_or_table, obs, done=None, z=None, dt=0.2, dtype=None):
     return act, np.ascontiguousarray(np.asarray(ctrl.z).T)
 
 
+QP_MAX_ITERATIONS = 32
+
+
+def qp_allocator_defaults(vessel=None):
+    """The rate-limited QP allocator's default numbers (dpenv_qp_allocator_defaults; qp_allocator.py:52-58,116-150), env order bow, port,
+    star: slack, power and change weights, force bounds, force rates [N/s] and azimuth rates [rad/s] (2, 5, 5 N and pi/12 per 0.2 s
+    step), and the lever arms and thrust constants of `vessel` (public parameter vector; None = the default hull).  Returns the dict
+    BatchedQPAllocator and policy.thrust_alloc_qp take."""
+    from . import _lib
+    v = np.asarray(_lib.default_vessel() if vessel is None else vessel, np.float64)
+    P = _lib.P
+    return dict(iterations=16, w_slack=np.ones(3), w_power=1.0, w_dalpha=0.25, w_dforce=0.25, f_max=np.array([9.0, 20.5, 20.5]),
+                force_rate=np.array([10.0, 25.0, 25.0]), azimuth_rate=np.full(2, 5.0 * np.pi / 12.0),
+                lx=v[P['LX_BOW']:P['LX_BOW'] + 3].copy(), ly=v[P['LY_BOW']:P['LY_BOW'] + 3].copy(),
+                kf=v[P['KF_BOW']:P['KF_BOW'] + 3].copy(), kr=v[P['KR_BOW']:P['KR_BOW'] + 3].copy())
+
+
+class BatchedQPAllocator(object):
+    """The rate-limited QP thrust allocation for n envs on the host: the statement of include/dpenv.h (dpenv_thrust_alloc_qp), operation
+    by operation, in batched NumPy.  dtype float32 (the default) is the kernel's arithmetic except for sin / cos (np.sin / np.cos here, the
+    kernel's own polynomial there); float64 is the form for checks.  params: the dict of qp_allocator_defaults; dt the control period.
+    State x [n, 5] = F_bow, F_port, F_star, a_port, a_star (the thruster state in force, azimuths wrapped to [-pi, pi)).
+    allocate(tau [n, 3]) advances the state one control step and returns the action [n, 7]; an env whose tau is not finite keeps its
+    state and commands it.  reset(mask) zeroes the state of the envs in mask (None = all).  objective(x, tau, prev) is J [n].
+    After allocate: last_x is the un-wrapped solution, last_J the objective per iteration [iterations + 1, n]."""
+
+    def __init__(self, n, params=None, dt=0.2, dtype=None):
+        p = qp_allocator_defaults() if params is None else params
+        self.dtype = np.dtype(np.float32 if dtype is None else dtype)
+        is32 = self.dtype == np.dtype(np.float32)
+        t = lambda v: np.asarray(v, np.float64).astype(self.dtype)
+        self.n = int(n)
+        self.iterations = int(p['iterations'])
+        if not 1 <= self.iterations <= QP_MAX_ITERATIONS:
+            raise ValueError('BatchedQPAllocator: iterations must be in 1..%d' % QP_MAX_ITERATIONS)
+        for name, shape in (('w_slack', (3,)), ('f_max', (3,)), ('force_rate', (3,)), ('azimuth_rate', (2,)), ('lx', (3,)), ('ly', (3,)),
+                            ('kf', (3,)), ('kr', (3,))):
+            if np.shape(p[name]) != shape:
+                raise ValueError('BatchedQPAllocator: %s has shape %s, want %s' % (name, np.shape(p[name]), shape))
+        self.ws, self.wp, self.wda, self.wdf = t(p['w_slack']), t(p['w_power']), t(p['w_dalpha']), t(p['w_dforce'])
+        self.fmax, self.lx, self.ly, self.kf, self.kr = t(p['f_max']), t(p['lx']), t(p['ly']), t(p['kf']), t(p['kr'])
+        dt = t(np.float32(dt)) if is32 else t(dt)                 # f32: the library's n_substeps * substep_dt
+        self.dF, self.da = t(p['force_rate']) * dt, t(p['azimuth_rate']) * dt
+        self.x = np.zeros((self.n, 5), self.dtype)
+        self.last_x, self.last_J = self.x.copy(), None
+
+    def box(self, prev):
+        """(lo, hi) [n, 5] of one control step from the state prev [n, 5]."""
+        Fp, ap = prev[:, 0:3], prev[:, 3:5]
+        lo = np.concatenate([np.fmax(-self.fmax, Fp - self.dF), ap - self.da], 1)
+        hi = np.concatenate([np.fmin(self.fmax, Fp + self.dF), ap + self.da], 1)
+        return lo, hi
+
+    def _residual(self, x, tau):
+        """sin, cos [n, 2], the moment arms b3 [n, 2] and r [n, 3] at x."""
+        F = x[:, 0:3]
+        s, c = np.sin(x[:, 3:5]).astype(self.dtype), np.cos(x[:, 3:5]).astype(self.dtype)
+        b3 = self.lx[1:3] * s - self.ly[1:3] * c
+        r0 = (c[:, 0] * F[:, 1] + c[:, 1] * F[:, 2]) - tau[:, 0]
+        r1 = ((F[:, 0] + s[:, 0] * F[:, 1]) + s[:, 1] * F[:, 2]) - tau[:, 1]
+        r2 = ((self.lx[0] * F[:, 0] + b3[:, 0] * F[:, 1]) + b3[:, 1] * F[:, 2]) - tau[:, 2]
+        return s, c, b3, np.stack([r0, r1, r2], 1)
+
+    def _objective(self, x, r, prev):
+        t = self.dtype.type
+        F, ws = x[:, 0:3], self.ws
+        Js = (ws[0] * (r[:, 0] * r[:, 0]) + ws[1] * (r[:, 1] * r[:, 1])) + ws[2] * (r[:, 2] * r[:, 2])
+        c3 = np.abs(F) * (F * F)
+        Jp = (c3[:, 0] + c3[:, 1]) + c3[:, 2]
+        e = x - prev
+        e2 = e * e
+        Ja = e2[:, 3] + e2[:, 4]
+        Jf = (e2[:, 0] + e2[:, 1]) + e2[:, 2]
+        return t(0.5) * (((Js + self.wp * Jp) + self.wda * Ja) + self.wdf * Jf)
+
+    def objective(self, x, tau, prev):
+        x, tau, prev = (np.asarray(v, self.dtype) for v in (x, tau, prev))
+        return self._objective(x, self._residual(x, tau)[3], prev)
+
+    def solve(self, tau, prev):
+        """The K iterations from the state prev on tau: (x [n, 5] un-wrapped, J [K + 1, n])."""
+        t = self.dtype.type
+        tau, prev = np.asarray(tau, self.dtype), np.asarray(prev, self.dtype)
+        n = prev.shape[0]
+        lo, hi = self.box(prev)
+        x = np.fmin(np.fmax(prev, lo), hi)
+        s, c, b3, r = self._residual(x, tau)
+        J = self._objective(x, r, prev)
+        lam = np.zeros(n, self.dtype)
+        hist = [J]
+        zero, one = np.zeros(n, self.dtype), np.ones(n, self.dtype)
+        with np.errstate(all='ignore'):
+            for _ in range(self.iterations):
+                F = x[:, 0:3]
+                # the 3 x 5 Jacobian, columns F_bow, F_port, F_star, a_port, a_star
+                d3 = self.lx[1:3] * c + self.ly[1:3] * s
+                Jm = [[zero, c[:, 0], c[:, 1], -(F[:, 1] * s[:, 0]), -(F[:, 2] * s[:, 1])],
+                      [one, s[:, 0], s[:, 1], F[:, 1] * c[:, 0], F[:, 2] * c[:, 1]],
+                      [self.lx[0] * one, b3[:, 0], b3[:, 1], F[:, 1] * d3[:, 0], F[:, 2] * d3[:, 1]]]
+                wr = [self.ws[j] * r[:, j] for j in range(3)]
+                WJ = [[self.ws[j] * Jm[j][k] for k in range(5)] for j in range(3)]
+                g, H = [None] * 5, [[None] * 5 for _ in range(5)]
+                for k in range(5):
+                    g[k] = (Jm[0][k] * wr[0] + Jm[1][k] * wr[1]) + Jm[2][k] * wr[2]
+                    for l in range(k + 1):
+                        H[k][l] = (Jm[0][k] * WJ[0][l] + Jm[1][k] * WJ[1][l]) + Jm[2][k] * WJ[2][l]
+                for k in range(3):
+                    g[k] = g[k] + ((t(1.5) * self.wp) * (F[:, k] * np.abs(F[:, k])) + self.wdf * (F[:, k] - prev[:, k]))
+                    H[k][k] = H[k][k] + ((t(3.0) * self.wp) * np.abs(F[:, k]) + self.wdf)
+                for k in range(3, 5):
+                    g[k] = g[k] + self.wda * (x[:, k] - prev[:, k])
+                    H[k][k] = H[k][k] + self.wda
+                fr = []
+                for k in range(5):
+                    H[k][k] = H[k][k] + lam * H[k][k]
+                    fr.append(((x[:, k] <= lo[:, k]) & (g[k] > 0)) | ((x[:, k] >= hi[:, k]) & (g[k] < 0)))
+                for k in range(5):
+                    g[k] = np.where(fr[k], zero, g[k])
+                    H[k][k] = np.where(fr[k], one, H[k][k])
+                    for l in range(k):
+                        H[k][l] = np.where(fr[k] | fr[l], zero, H[k][l])
+                # LDL' without pivoting: H = L D L', L unit lower triangular
+                L, D, iD = [[None] * 5 for _ in range(5)], [None] * 5, [None] * 5
+                for j in range(5):
+                    v = [L[j][m] * D[m] for m in range(j)]
+                    D[j] = H[j][j]
+                    for m in range(j):
+                        D[j] = D[j] - L[j][m] * v[m]
+                    iD[j] = one / D[j]
+                    for i in range(j + 1, 5):
+                        a = H[i][j]
+                        for m in range(j):
+                            a = a - L[i][m] * v[m]
+                        L[i][j] = a * iD[j]
+                y = [None] * 5
+                for i in range(5):
+                    a = -g[i]
+                    for m in range(i):
+                        a = a - L[i][m] * y[m]
+                    y[i] = a
+                d = [None] * 5
+                for i in range(4, -1, -1):
+                    a = y[i] * iD[i]
+                    for m in range(i + 1, 5):
+                        a = a - L[m][i] * d[m]
+                    d[i] = a
+                xt = np.fmin(np.fmax(x + np.stack(d, 1), lo), hi)
+                st, ct, b3t, rt = self._residual(xt, tau)
+                Jt = self._objective(xt, rt, prev)
+                acc = Jt < J
+                a1 = acc[:, None]
+                x, s, c, b3, r = np.where(a1, xt, x), np.where(a1, st, s), np.where(a1, ct, c), np.where(a1, b3t, b3), np.where(a1, rt, r)
+                J = np.where(acc, Jt, J)
+                lam = np.where(acc, t(0.25) * lam, t(8.0) * np.fmax(lam, t(0.125)))
+                hist.append(J)
+        return x, np.stack(hist)
+
+    def thrust_columns(self, F):
+        """F [n, 3] -> the action's thrust columns: clip(copysign(sqrt(|F| / K), F) / 100, -1, 1), K forward or reverse by F's sign."""
+        t = self.dtype.type
+        K = np.where(F >= 0, self.kf, self.kr)
+        nn = np.copysign(np.sqrt(np.abs(F) / K), F)
+        return np.fmin(np.fmax(nn / t(100.0), -t(1.0)), t(1.0))
+
+    def wrap(self, a):
+        """[-pi, pi): a - 2 pi floor((a + pi) / (2 pi)), the last step one fused multiply-add (exact here in float64)."""
+        t = self.dtype.type
+        pi = t(np.float32(np.pi)) if self.dtype == np.dtype(np.float32) else t(np.pi)
+        k = np.floor((a + pi) * (t(0.5) / pi))
+        return (np.asarray(a, np.float64) - np.asarray(k, np.float64) * np.float64(t(2.0) * pi)).astype(self.dtype)
+
+    def allocate(self, tau):
+        tau = np.asarray(tau, self.dtype)
+        prev = self.x
+        x, self.last_J = self.solve(tau, prev)
+        ok = np.isfinite(tau).all(1)[:, None]
+        x = np.where(ok, x, prev)
+        self.last_x = x
+        self.x = np.where(ok, np.concatenate([x[:, 0:3], self.wrap(x[:, 3:5])], 1), prev)
+        s, c = np.sin(x[:, 3:5]).astype(self.dtype), np.cos(x[:, 3:5]).astype(self.dtype)
+        return np.concatenate([self.thrust_columns(x[:, 0:3]), np.stack([s[:, 0], c[:, 0], s[:, 1], c[:, 1]], 1)], 1)
+
+    def reset(self, mask=None):
+        if mask is None:
+            self.x = self.x * 0
+        else:
+            self.x[mask] = 0
+
+
 class RLAllocatorNode(object):
     """The node's callbacks as plain methods (rl_allocator.py:168-220).  `actor(state[9]) -> action[act_dim]` is any
     callable: ActorCritic.forward_ref on the CPU, or policy_forward on the GPU for one env."""

@@ -186,6 +186,7 @@ class BatchedRevoltEnv(object):
         self.reference_filter = None         # dict of the parameters while set_reference_filter() has it on
         self.dp_controller = None            # dict of the parameters while set_dp_controller() has it on
         self.dp_controller_table = None      # the [32, n] tensor while set_dp_controller_table() has per-env numbers in force
+        self.qp_allocator = None             # dict of the parameters while set_qp_allocator() has the QP allocation in the closed loop
 
     # -- plumbing -----------------------------------------------------------------------------
     # What a Python `for` over step() pays per call besides the launch is this plumbing (bench.py `eager_loop`): the stream handle and
@@ -444,12 +445,13 @@ class BatchedRevoltEnv(object):
         integral z of every env.  step(), rollout() and policy_rollout() keep working while it is on."""
         if off:
             _lib.check(self.lib.dpenv_set_dp_controller(self._h, None, self._stream()), self._h)
-            self.dp_controller = self.dp_controller_table = None
+            self.dp_controller = self.dp_controller_table = self.qp_allocator = None
             return
         p, c = _dp_controller_struct(params)
         _lib.check(self.lib.dpenv_set_dp_controller(self._h, C.byref(c), self._stream()), self._h)
         self.dp_controller = dict(p)
         self.dp_controller_table = None      # the scalar law again: the library dropped a table in force
+        self.qp_allocator = None             # ... and a QP allocator
 
     def set_dp_controller_table(self, table, check=True):
         """Per-env numbers for the baseline (dpenv_set_dp_controller_table): table is a float32 tensor [32, n] on the env's device in
@@ -484,6 +486,36 @@ class BatchedRevoltEnv(object):
     def set_dp_controller_state(self, z):
         self._chk(z, (3, self.n_envs), _torch().float32, 'z')
         _lib.check(self.lib.dpenv_set_dp_controller_state(self._h, self._ptr(z), self._stream()), self._h)
+
+    def set_qp_allocator(self, params=None, off=False):
+        """The rate-limited QP thrust allocation as the allocation stage of policy.controller_rollout (dpenv_set_qp_allocator; include/dpenv.h
+        has the law): the baseline's PID forms the wrench, the QP allocates it in place of the pseudo-inverse.  params is the dict of
+        deploy.qp_allocator_defaults (None = the defaults of the DEFAULT hull, whatever hull the env flies: for another hull, the thrust-loss
+        preset included, pass deploy.qp_allocator_defaults(its parameter vector) - its lever arms and thrust constants); off=True returns to
+        the pseudo-inverse.  Needs
+        set_dp_controller on (set_dp_controller drops it again), the shared hull or the thrust-loss preset and no per-env controller table.
+        Turning it on puts every env's thrusters at rest; resets do the same for the envs they re-draw."""
+        if off:
+            _lib.check(self.lib.dpenv_set_qp_allocator(self._h, None, self._stream()), self._h)
+            self.qp_allocator = None
+            return
+        from .deploy import qp_allocator_defaults
+        from .policy import qp_allocator_struct
+        p = qp_allocator_defaults() if params is None else params
+        q = qp_allocator_struct(p)
+        _lib.check(self.lib.dpenv_set_qp_allocator(self._h, C.byref(q), self._stream()), self._h)
+        self.qp_allocator = dict(p)
+
+    def get_qp_allocator_state(self):
+        """float32 [5, n]: the QP allocator's thruster state F_bow, F_port, F_star, a_port, a_star.  Checkpoint with get_dp_controller_state()."""
+        torch = _torch()
+        x = torch.empty((5, self.n_envs), dtype=torch.float32, device=self.device)
+        _lib.check(self.lib.dpenv_get_qp_allocator_state(self._h, self._ptr(x), self._stream()), self._h)
+        return x
+
+    def set_qp_allocator_state(self, x):
+        self._chk(x, (5, self.n_envs), _torch().float32, 'x')
+        _lib.check(self.lib.dpenv_set_qp_allocator_state(self._h, self._ptr(x), self._stream()), self._h)
 
     def get_rng_counters(self):
         """(noise_ctr, drift_ctr): int32 [n] draws made so far of the in-kernel exploration noise and of the current drift (uint32

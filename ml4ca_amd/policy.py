@@ -365,3 +365,55 @@ def controller_label(env, obs, done=None, z=None, out=None):
     io.z_out, io.act = z_out.data_ptr(), act.data_ptr()
     _lib.check(env.lib.dpenv_controller_label(env._h, C.byref(io), env._stream()), env._h)
     return act, z_out
+
+
+def qp_allocator_struct(params=None):
+    """dpenv_qp_allocator for deploy.qp_allocator_defaults' dict; None = the library's defaults (the default hull's)."""
+    q = _lib.QPAllocator()
+    if params is None:
+        _lib.check(_lib.load().dpenv_qp_allocator_defaults(C.byref(q)))
+        return q
+    q.struct_size = C.sizeof(_lib.QPAllocator)
+    q.iterations = int(params['iterations'])
+    q.w_power, q.w_dalpha, q.w_dforce = float(params['w_power']), float(params['w_dalpha']), float(params['w_dforce'])
+    for name, count in (('w_slack', 3), ('f_max', 3), ('force_rate', 3), ('azimuth_rate', 2), ('lx', 3), ('ly', 3), ('kf', 3), ('kr', 3)):
+        if len(params[name]) != count:
+            raise ValueError('qp_allocator_struct: %s has %d entries, want %d' % (name, len(params[name]), count))
+        for k in range(count):
+            getattr(q, name)[k] = float(params[name][k])
+    return q
+
+
+def thrust_alloc_qp(tau, state=None, params=None, dt=0.2, out=None, cost=False):
+    """One control step of the rate-limited QP thrust allocation on the device (dpenv_thrust_alloc_qp), one lane per env: tau float32
+    [3, n] = Fx, Fy, Mz and the thruster state in force, state float32 [5, n] = F_bow, F_port, F_star, a_port, a_star (None = zeros), ->
+    (action [n, 7], new state [5, n]) and, with cost=True, the final objective [n] as a third value.  params: the dict of
+    deploy.qp_allocator_defaults (None = the defaults); dt the control period.  out = (action, state) supplies the buffers; the state
+    buffer may be the input tensor itself.  An env whose tau is not finite keeps its state and commands it.  Handle-free: a caller with
+    its own motion controller closes the loop with this between two launches.  deploy.BatchedQPAllocator is the host statement."""
+    torch = _torch()
+    lib = _lib.load()
+    f32 = torch.float32
+    if not isinstance(tau, torch.Tensor) or tau.dim() != 2 or tau.shape[0] != 3 or tau.dtype != f32 or not tau.is_cuda or not tau.is_contiguous():
+        raise ValueError('thrust_alloc_qp: tau is a contiguous float32 device tensor [3, n]')
+    n = int(tau.shape[1])
+
+    def chk(t, shape, what):
+        if not isinstance(t, torch.Tensor) or tuple(t.shape) != shape or t.dtype != f32 or t.device != tau.device or not t.is_contiguous():
+            raise ValueError('thrust_alloc_qp: %s is a contiguous float32 tensor %s on tau\'s device' % (what, list(shape)))
+
+    if state is not None:
+        chk(state, (5, n), 'state')
+    if out is None:
+        out = (torch.empty((n, 7), dtype=f32, device=tau.device), torch.empty((5, n), dtype=f32, device=tau.device))
+    act, state_out = out
+    chk(act, (n, 7), 'out[0]')
+    chk(state_out, (5, n), 'out[1]')
+    J = torch.empty((n,), dtype=f32, device=tau.device) if cost else None
+    q = qp_allocator_struct(params)
+    s = C.c_void_p(torch.cuda.current_stream(tau.device).cuda_stream)
+    with torch.cuda.device(tau.device):
+        _lib.check(lib.dpenv_thrust_alloc_qp(C.byref(q), float(dt), C.c_void_p(tau.data_ptr()),
+                                             C.c_void_p(state.data_ptr()) if state is not None else None, C.c_void_p(state_out.data_ptr()),
+                                             C.c_void_p(act.data_ptr()), C.c_void_p(J.data_ptr()) if cost else None, n, s))
+    return (act, state_out, J) if cost else (act, state_out)

@@ -1,0 +1,595 @@
+"""The rate-limited QP thrust allocation on the device (include/dpenv.h: dpenv_thrust_alloc_qp) against its host statement
+(deploy.BatchedQPAllocator): the exact properties on the device's own state, and the objective it reaches by the float32 yardstick.
+Then the same law as the allocation stage of the fused closed loop (dpenv_set_qp_allocator): the launch against its own parts bit for
+bit, pieces, graph replay, checkpoints, the refusals, and the scored box test.
+
+One flight per iteration count is flown once for the whole module: the five shapes side by side, every shape carrying its own state on
+the device through the same 71 control steps.  The host law then solves every step of every shape from the state the DEVICE had, in
+float32 and float64, in one batched call per step."""
+import numpy as np
+import pytest
+
+from tests import helpers as H
+from tests.test_qp_allocator_cpu import TAU_MAX, box_of, wrench_sequence
+
+pytestmark = pytest.mark.gpu
+
+SHAPES = (1, 63, 64, 65, 130)            # one lane; a wave less one, a wave, a wave and one; a workgroup boundary away from every wave's
+ITERATIONS = (1, 16, 32)
+DT = 0.2
+_CACHE = {}
+
+
+def _np(t):
+    return t.detach().cpu().numpy()
+
+
+def _params(K):
+    from ml4ca_amd.deploy import qp_allocator_defaults
+    p = qp_allocator_defaults()
+    p['iterations'] = K
+    return p
+
+
+def wrenches(n, shape_index):
+    """[steps, n, 3] float32: the CPU test's first 40 wrenches with a per-env offset; zeros; one rate-infeasible jump; four phases that
+    drive every force and both azimuths against their lower and their upper bounds (half the envs mirrored); a last free step."""
+    rng = np.random.default_rng(100 + shape_index)
+    offs = rng.uniform(-0.5, 0.5, (n, 3)) * TAU_MAX
+    sgn = np.where(np.arange(n) % 2 == 0, 1.0, -1.0)[:, None]
+    steps = [tau[None] + offs for tau in wrench_sequence(40)]
+    steps += [np.zeros((n, 3))] * 3
+    steps += [sgn * TAU_MAX[None] * np.array([0.9, -0.8, 0.7])]
+    for phase, count in (((0, 150, 0), 5), ((0, -150, 0), 8), ((150, 0, 60), 6), ((-150, 0, -60), 7)):
+        steps += [sgn * np.array(phase, np.float64)[None]] * count
+    steps += [rng.uniform(-0.3, 0.3, (n, 3)) * TAU_MAX]
+    return np.array(steps).astype(np.float32)
+
+
+def bad_lanes(n):
+    return sorted({0, n // 2, n - 1})
+
+
+def flight(K):
+    """Every shape's flight on the device at K iterations, and the host law's answers from the device's own states."""
+    if K in _CACHE:
+        return _CACHE[K]
+    import torch
+    from ml4ca_amd.deploy import BatchedQPAllocator
+    from ml4ca_amd.policy import thrust_alloc_qp
+    p = _params(K)
+    rec = {}
+    for si, n in enumerate(SHAPES):
+        tau = wrenches(n, si)
+        S = torch.zeros((5, n), dtype=torch.float32, device='cuda:0')
+        prevs, states, acts, costs = [], [], [], []
+        for t in range(len(tau)):
+            prevs.append(_np(S).T.copy())
+            td = H.to_dev(np.ascontiguousarray(tau[t].T))
+            if t % 2 == 0:                                   # state_out aliases state_in
+                out = (torch.empty((n, 7), dtype=torch.float32, device=S.device), S)
+            else:
+                out = None
+            if t % 3 == 0:                                   # cost_out = NULL
+                act, S = thrust_alloc_qp(td, S, p, DT, out=out)
+                costs.append(np.full(n, np.nan, np.float32))
+            else:
+                act, S, J = thrust_alloc_qp(td, S, p, DT, out=out, cost=True)
+                costs.append(_np(J))
+            states.append(_np(S).T.copy())
+            acts.append(_np(act))
+        # the last step again with three lanes' wrench not finite
+        bad = tau[-1].copy()
+        lanes = bad_lanes(n)
+        for j, v in zip(lanes, (np.nan, np.inf, -np.inf)):
+            bad[j, j % 3] = v
+        Sb = H.to_dev(np.ascontiguousarray(prevs[-1].T))
+        act_b, Sb2 = thrust_alloc_qp(H.to_dev(np.ascontiguousarray(bad.T)), Sb, p, DT)
+        rec[n] = dict(tau=tau, prev=np.array(prevs), state=np.array(states), act=np.array(acts), cost=np.array(costs),
+                      bad_act=_np(act_b), bad_state=_np(Sb2).T.copy())
+    torch.cuda.synchronize()
+    # the host law from the device's own previous states, every shape in one batch per step
+    tau = np.concatenate([rec[n]['tau'] for n in SHAPES], 1)
+    prev = np.concatenate([rec[n]['prev'] for n in SHAPES], 1)
+    dev = np.concatenate([rec[n]['state'] for n in SHAPES], 1)
+    L = tau.shape[1]
+    h32, h64 = BatchedQPAllocator(L, p, DT, np.float32), BatchedQPAllocator(L, p, DT, np.float64)
+    J32, J64, JD = (np.zeros(tau.shape[:2]) for _ in range(3))
+    for t in range(tau.shape[0]):
+        pv, tv = prev[t].astype(np.float64), tau[t].astype(np.float64)
+        x32, _ = h32.solve(tau[t], prev[t])
+        x64, _ = h64.solve(tv, pv)
+        J32[t] = h64.objective(x32.astype(np.float64), tv, pv)
+        J64[t] = h64.objective(x64, tv, pv)
+        JD[t] = h64.objective(dev[t].astype(np.float64), tv, pv)
+    lo, hi = box_of(h32, prev.reshape(-1, 5))
+    lo, hi = lo.reshape(prev.shape), hi.reshape(prev.shape)
+    # lanes whose azimuth box lies inside (-pi, pi): there the wrap that state_out went through is the identity, state_out IS the solution
+    plain = ((lo[..., 3:5] > -np.float32(np.pi)) & (hi[..., 3:5] < np.float32(np.pi))).all(-1)
+    edges = np.cumsum([0] + list(SHAPES))
+    for k, n in enumerate(SHAPES):
+        sl = slice(edges[k], edges[k + 1])
+        rec[n].update(J32=J32[:, sl], J64=J64[:, sl], JD=JD[:, sl], lo=lo[:, sl], hi=hi[:, sl], plain=plain[:, sl])
+    rec['h32'] = h32
+    _CACHE[K] = rec
+    return rec
+
+
+def wrap32(v):
+    """The header's wrap in NumPy float32: k = floorf((v + pi) * (0.5 / pi)); fmaf(-k, 2 pi, v) (the fused step is exact in float64)."""
+    pi = np.float32(np.pi)
+    k = np.floor((v + pi) * (np.float32(0.5) / pi))
+    return (v.astype(np.float64) - k.astype(np.float64) * np.float64(np.float32(2.0) * pi)).astype(np.float32)
+
+
+def thrust_columns_f32(F, p):
+    """clip(copysign(sqrt(|F| / K), F) / 100, -1, 1) in NumPy float32, K forward or reverse by the sign of F."""
+    kf, kr = np.asarray(p['kf'], np.float32), np.asarray(p['kr'], np.float32)
+    K = np.where(F >= 0, kf, kr).astype(np.float32)
+    nn = np.copysign(np.sqrt(np.abs(F) / K), F)
+    out = np.minimum(np.maximum(nn / np.float32(100.0), np.float32(-1.0)), np.float32(1.0))
+    assert out.dtype == np.float32
+    return out
+
+
+@pytest.mark.parametrize('K', ITERATIONS)
+@pytest.mark.parametrize('n', SHAPES)
+def test_exact_properties_on_the_devices_own_state(n, K):
+    r = flight(K)[n]
+    p = _params(K)
+    state, prev, act, lo, hi, plain = r['state'], r['prev'], r['act'], r['lo'], r['hi'], r['plain']
+    assert np.isfinite(state).all() and np.isfinite(act).all()
+    assert np.array_equal(prev[1:].view(np.uint32), state[:-1].view(np.uint32))             # the state was carried, aliased or not
+    # inside the box of the device's own previous state, no tolerance: forces everywhere, azimuths where the wrap is the identity
+    assert (lo[..., :3] <= state[..., :3]).all() and (state[..., :3] <= hi[..., :3]).all()
+    assert plain.mean() > 0.9
+    assert (lo[plain] <= state[plain]).all() and (state[plain] <= hi[plain]).all()
+    assert (state[..., 3:5] >= -np.float32(np.pi)).all() and (state[..., 3:5] < np.float32(np.pi)).all()
+    # ... and on the other rows, whose box reaches past +-pi: some float32 x inside [lo, hi] wraps to state_out bit for bit (searched two
+    # ulps either side of state_out + 2 pi k, k = -1, 0, 1)
+    rest = ~plain
+    a, l, h = state[rest][:, 3:5], lo[rest][:, 3:5], hi[rest][:, 3:5]
+    found = np.zeros(a.shape, bool)
+    for k in (-1.0, 0.0, 1.0):
+        c = (a.astype(np.float64) + k * np.float64(np.float32(2.0) * np.float32(np.pi))).astype(np.float32)
+        for d in range(-2, 3):
+            x = c.copy()
+            for _ in range(abs(d)):
+                x = np.nextafter(x, np.float32(np.inf if d > 0 else -np.inf))
+            found |= (l <= x) & (x <= h) & (wrap32(x).view(np.uint32) == a.view(np.uint32))
+    assert found.all(), int((~found).sum())
+    if n >= 63:                                              # every bound was met exactly, from below and from above
+        assert ((state == lo) & plain[..., None]).any(axis=(0, 1)).all() and ((state == hi) & plain[..., None]).any(axis=(0, 1)).all()
+    # the thrust columns are the stated map of state_out, bit for bit
+    assert np.array_equal(act[..., :3].view(np.uint32), thrust_columns_f32(state[..., :3], p).view(np.uint32))
+    assert (np.abs(act[..., :3]) == 1).any() or n == 1
+    # the heads: within 2e-7 of float64 sin / cos of the final angle (the polynomial's documented 9.2e-8 and a float32 rounding, twice over)
+    a = state[plain][:, 3:5].astype(np.float64)
+    want = np.stack([np.sin(a[:, 0]), np.cos(a[:, 0]), np.sin(a[:, 1]), np.cos(a[:, 1])], 1)
+    err = np.abs(act[plain][:, 3:7].astype(np.float64) - want).max()
+    print('n = %d, K = %d: heads max abs err %.3g on %d rows' % (n, K, err, int(plain.sum())))
+    assert err <= 2e-7
+    # cost_out is the final objective of state_out (NULL on every third step: those calls ran without it)
+    got = r['cost']
+    asked = np.isfinite(got)
+    assert asked[np.arange(len(got)) % 3 != 0].all() and not asked[np.arange(len(got)) % 3 == 0].any()
+    m = asked & plain
+    assert np.allclose(got[m], r['JD'][m], rtol=1e-5, atol=1e-5)
+    # a wrench that is not finite: the env keeps its state bit for bit and commands it; the other envs fly what they flew without it
+    lanes = bad_lanes(n)
+    rest = np.setdiff1d(np.arange(n), lanes)
+    assert np.array_equal(r['bad_state'][lanes].view(np.uint32), prev[-1][lanes].view(np.uint32))
+    assert np.array_equal(r['bad_state'][rest].view(np.uint32), state[-1][rest].view(np.uint32))
+    assert np.array_equal(r['bad_act'][rest].view(np.uint32), act[-1][rest].view(np.uint32))
+    kept = prev[-1][lanes]
+    assert np.array_equal(r['bad_act'][lanes][:, :3].view(np.uint32), thrust_columns_f32(kept[:, :3], p).view(np.uint32))
+    ak = kept[:, 3:5].astype(np.float64)
+    want = np.stack([np.sin(ak[:, 0]), np.cos(ak[:, 0]), np.sin(ak[:, 1]), np.cos(ak[:, 1])], 1)
+    assert np.abs(r['bad_act'][lanes][:, 3:7] - want).max() <= 2e-7
+
+
+@pytest.mark.parametrize('K', ITERATIONS)
+def test_objective_by_the_float32_yardstick(K):
+    """With D the device's result and H32, H64 the host law in the two precisions from the same state and wrench, every J in float64:
+    |J(D) - J(H64)| <= 4 max |J(H32) - J(H64)| + 1e-6 (1 + J(H64)), the maximum over every step, env and shape of the flight.  The
+    yardstick is the host law's own float32 error, never the device's.  Rows whose azimuth box reaches past +-pi are left out (the
+    wrapped state_out is not the solution there).  Measured on an MI355X: DESIGN.md section 7."""
+    rec = flight(K)
+    yard = max(np.abs(rec[n]['J32'] - rec[n]['J64'])[rec[n]['plain']].max() for n in SHAPES)
+    worst = 0.0
+    for n in SHAPES:
+        r = rec[n]
+        m = r['plain']
+        gap = np.abs(r['JD'] - r['J64'])[m]
+        allow = 4.0 * yard + 1e-6 * (1.0 + r['J64'][m])
+        worst = max(worst, float((gap / allow).max()))
+        print('K = %d, n = %d: max |J(D) - J(H64)| = %.3g (yardstick max |J(H32) - J(H64)| = %.3g, largest J %.4g)'
+              % (K, n, gap.max(), yard, r['J64'][m].max()))
+        assert (gap <= allow).all(), (n, float(gap.max()), yard)
+    print('K = %d: worst |J(D) - J(H64)| / allowed = %.3g' % (K, worst))
+
+
+def test_wrap_and_refusals():
+    """A state whose azimuths lie outside [-pi, pi) at rest (no force, no wrench: the solution is the state): state_out is the stated
+    wrap, the heads are those of the un-wrapped angle.  And the refusals reach the caller as errors, nothing launched."""
+    import torch
+    from ml4ca_amd import _lib
+    from ml4ca_amd.policy import thrust_alloc_qp
+    n = 65
+    a = np.linspace(-6.0, 6.0, n).astype(np.float32)
+    S = np.zeros((5, n), np.float32)
+    S[3], S[4] = a, -a
+    act, out = thrust_alloc_qp(torch.zeros((3, n), device='cuda:0'), H.to_dev(S))
+    wrap = wrap32
+    got = _np(out)
+    assert np.array_equal(got[3].view(np.uint32), wrap(a).view(np.uint32)) and np.array_equal(got[4].view(np.uint32), wrap(-a).view(np.uint32))
+    assert (got[:3] == 0).all() and (np.abs(got[3:]) <= np.pi).all() and (np.abs(a) > np.pi).any()
+    g = _np(act)
+    a64 = a.astype(np.float64)
+    assert np.abs(g[:, 3:7] - np.stack([np.sin(a64), np.cos(a64), np.sin(-a64), np.cos(-a64)], 1)).max() <= 2e-7
+    assert (g[:, :3] == 0).all()
+    tau = torch.zeros((3, n), device='cuda:0')
+    for field, value in (('iterations', 0), ('iterations', 33), ('w_dalpha', 0.0), ('w_power', -1.0), ('kf', [0.0, 1.0, 1.0])):
+        p = _params(16)
+        p[field] = value
+        with pytest.raises(_lib.DpenvError):
+            thrust_alloc_qp(tau, None, p)
+    with pytest.raises(_lib.DpenvError):
+        thrust_alloc_qp(tau, None, None, dt=0.0)
+    with pytest.raises(ValueError):
+        thrust_alloc_qp(tau, torch.zeros((3, n), device='cuda:0'))
+
+
+def test_graph_replay_equals_eager():
+    """The call is one kernel node: captured and replayed it writes what the eager call writes."""
+    import torch
+    from ml4ca_amd.policy import thrust_alloc_qp
+    n = 130
+    tau = H.to_dev(np.ascontiguousarray(wrenches(n, 0)[10].T))
+    S0 = H.to_dev(np.ascontiguousarray(np.random.default_rng(0).uniform(-1, 1, (5, n)).astype(np.float32)))
+    act_e, S_e, J_e = thrust_alloc_qp(tau, S0, cost=True)
+    act_g, S_g = torch.empty_like(act_e), torch.empty_like(S_e)
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):
+        thrust_alloc_qp(tau, S0, out=(act_g, S_g))                                   # warm-up outside the capture
+    torch.cuda.current_stream().wait_stream(side)
+    act_g.zero_(); S_g.zero_()
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g):
+        thrust_alloc_qp(tau, S0, out=(act_g, S_g))
+    g.replay()
+    torch.cuda.synchronize()
+    assert torch.equal(act_g, act_e) and torch.equal(S_g, S_e) and bool(torch.isfinite(J_e).all())
+
+
+# ---- the QP allocation as the allocation stage of the fused closed loop (dpenv_set_qp_allocator) ------------------------------------------
+NC, TC = 130, 24
+ROWS = ('obs', 'act', 'rew', 'done', 'last_obs')
+
+
+def _env(n=NC, preset=False, **kw):
+    import ml4ca_amd
+    kw.setdefault('current', True)
+    kw.setdefault('seed', 5)
+    if preset:
+        kw['vessel_params'] = ml4ca_amd.default_vessel('thrust_loss')
+    return H.make_pair('final_cont', n, **kw)[0]
+
+
+def _start(env, filt=False, preset=False, K=16, qp=True, nudge=True):
+    """The current from 16 directions (the preset: re-drawn per episode, the shared training form), the filter, the controller and the QP
+    on, every env from the training sampler but (nudge) a quarter of them next to the position bound, so that they end an episode early.
+    env.obs0 is the observation the reset returned."""
+    import math
+    import torch
+    n = env.n_envs
+    beta = (2 * math.pi / 16) * (torch.arange(n, device=env.device) % 16).float()
+    env.set_current(torch.full((n,), 0.2, device=env.device), beta.contiguous())
+    if preset:
+        env.set_current_randomisation(0.1, 0.785)
+    if filt:
+        env.set_reference_filter()
+    env.set_dp_controller()
+    if qp:
+        env.set_qp_allocator(_params(K))
+    env.obs0 = env.reset().clone()
+    if nudge:
+        st, ctr = env.get_state()
+        st = st.clone()
+        st[0, ::4] = st[6, ::4] + 7.9                          # 0.1 m inside the 8 m bound, drifting: done within a few steps
+        st[3, ::4] = 0.5
+        env.set_state(st, ctr)
+    return env
+
+
+def _checkpoint(env, filt):
+    """Everything a flight continues from, cloned: state and counters (the episode counter keys the re-draws), the current's mean and
+    present value, z, the thruster state, the lag columns and the filter."""
+    ck = dict(state=env.get_state(), mean=env.get_current_mean(), cur=env.get_current(), z=env.get_dp_controller_state(),
+              x=env.get_qp_allocator_state(), thrust=env.get_obs_thrust())
+    if filt:
+        ck['filter'] = env.get_reference_filter_state()
+    return {k: tuple(t.clone() for t in v) if isinstance(v, tuple) else v.clone() for k, v in ck.items()}
+
+
+def _restore(env, ck):
+    env.set_state(*ck['state'])
+    env.set_current(*ck['mean'])
+    env.set_current(*ck['cur'], present_only=True)
+    env.set_dp_controller_state(ck['z'])
+    env.set_qp_allocator_state(ck['x'])
+    env.set_obs_thrust(ck['thrust'])
+    if 'filter' in ck:
+        env.set_reference_filter_state(*ck['filter'])
+
+
+def _same(a, b, keys=ROWS, what=''):
+    import torch
+    for k in keys:
+        assert torch.equal(a[k], b[k]), '%s %s: %d elements differ' % (what, k, int((a[k] != b[k]).sum()))
+
+
+def _refs(dev):
+    import math
+    import torch
+    refs = torch.zeros((1, 3, NC), device=dev)
+    refs[0, 0], refs[0, 1], refs[0, 2] = 3.0, -2.0, math.radians(-30.0)
+    return refs
+
+
+@pytest.mark.parametrize('preset', [False, True])
+@pytest.mark.parametrize('filt', [False, True])
+def test_closed_loop_equals_its_own_parts_bit_for_bit(filt, preset):
+    """The launch's act rows = dpenv_thrust_alloc_qp applied row by row to the tau the host PID (NumPy float32, bit for bit the kernel's)
+    forms from the launch's own obs rows and starting z, the QP state carried and zeroed behind a done row; the act rows replayed
+    through dpenv_rollout give the launch's obs, reward and done rows; and the final z and thruster state are the parts'."""
+    import torch
+    from ml4ca_amd.deploy import BatchedDPController
+    from ml4ca_amd.policy import controller_rollout, thrust_alloc_qp
+    env = _start(_env(preset=preset, auto_reset=True, terminate=True, max_ep_len=40, step_one_wave=True), filt, preset)
+    ck = _checkpoint(env, filt)
+    x0 = env.get_qp_allocator_state().clone()
+    assert not bool(x0.any())
+    out = controller_rollout(env, TC, switch_steps=(5,), refs=_refs(env.device))
+    out = {k: v.clone() for k, v in out.items()}
+    done = _np(out['done'])
+    assert (done[:6] != 0).any() and (done[:19] == 0).all(0).any()                      # early terminations; other envs fly to the time limit
+    ctrl = BatchedDPController(NC, env.dp_controller, dt=env.control_period)
+    S = x0.clone()
+    obs = _np(out['obs'])
+    for t in range(TC):
+        if t > 0:
+            ctrl.reset(done[t - 1] != 0)
+            S[:, torch.from_numpy(done[t - 1] != 0).to(S.device)] = 0.0
+        tau = H.to_dev(np.ascontiguousarray(ctrl.wrench(obs[t]).T))
+        act, S = thrust_alloc_qp(tau, S, env.qp_allocator, env.control_period)
+        assert torch.equal(act, out['act'][t]), (t, int((act != out['act'][t]).sum()))
+    ctrl.reset(done[-1] != 0)
+    S[:, torch.from_numpy(done[-1] != 0).to(S.device)] = 0.0
+    assert torch.equal(env.get_qp_allocator_state(), S) and bool(S.any())
+    assert np.array_equal(_np(env.get_dp_controller_state()).T.view(np.uint32), ctrl.z.view(np.uint32))
+    if filt:
+        return                                           # dpenv_rollout and dpenv_step refuse a handle with the filter on: the test below
+    # the env's side: the same act block through dpenv_rollout from the same state, counters and current writes the same rows - on the
+    # preset with the currents the auto-resets re-draw
+    st1, ctr1 = env.get_state()
+    cur1 = env.get_current()
+    _restore(env, ck)
+    o, rew, dn = env.rollout(out['act'], switch_steps=(5,), refs=_refs(env.device))
+    assert torch.equal(o[:-1], out['obs'][1:]) and torch.equal(o[-1], out['last_obs'])
+    assert torch.equal(rew, out['rew']) and torch.equal(dn, out['done'])
+    for x, y in zip(env.get_state() + env.get_current(), (st1, ctr1) + cur1):
+        assert torch.equal(x, y)
+    if preset:
+        assert not torch.equal(cur1[0], ck['cur'][0])                                  # currents were re-drawn
+
+
+@pytest.mark.parametrize('preset', [False, True])
+def test_launch_with_the_filter_equals_the_eager_composition(preset):
+    """With the reference filter on the env's side cannot be replayed through dpenv_rollout (it refuses such a handle, as dpenv_step does),
+    so the launch is held to the eager composition, as the pseudo-inverse launch is in tests/test_gpu_dp_controller.py: a handle WITHOUT
+    the filter stepped by dpenv_step with the host filter's position as new_ref, the action from the host PID and dpenv_thrust_alloc_qp.
+    obs, act, reward, done, ref and last_obs bit for bit, on the shared hull and on the thrust-loss preset's kernel."""
+    import torch
+    from ml4ca_amd.deploy import BatchedDPController, BatchedReferenceFilter
+    from ml4ca_amd.policy import controller_rollout, thrust_alloc_qp
+    K = 20
+    kw = dict(preset=preset, auto_reset=False, terminate=False)
+    a = _start(_env(**kw), True, preset, nudge=False)
+    b = _start(_env(**kw), False, preset, nudge=False)
+    assert torch.equal(a.obs0, b.obs0)
+    dev = a.device
+    ref0 = a.get_state()[0][6:9].clone().contiguous()
+    refs = _refs(dev)
+    fused = controller_rollout(a, K, switch_steps=(3,), refs=refs)
+    p = a.reference_filter
+    F = BatchedReferenceFilter(NC, omega=p['omega'], zeta=p['zeta'], dt=a.control_period, device=dev)
+    F.reset(ref0)
+    ctrl = BatchedDPController(NC, b.dp_controller, dt=b.control_period)
+    S = torch.zeros((5, NC), device=dev)
+    rows = {k: [] for k in ('obs', 'act', 'rew', 'done', 'ref')}
+    o, eta, in_force = b.obs0.clone(), ref0.clone(), ref0.clone()
+    for t in range(K):
+        tau = H.to_dev(np.ascontiguousarray(ctrl.wrench(_np(o)).T))
+        act, S = thrust_alloc_qp(tau, S, b.qp_allocator, b.control_period)
+        rows['obs'].append(o.clone())
+        rows['act'].append(act)
+        rows['ref'].append(eta.T.clone())
+        if t == 3:
+            F.switch(refs[0])
+        nr = F.advance()
+        o, rew, done, _ = b.step(act, new_ref=nr)
+        o = o.clone()
+        rows['rew'].append(rew.clone())
+        rows['done'].append(done.clone())
+        eta, in_force = in_force, nr                                # o_t+1 was formed before new_ref applied
+    eager = {k: torch.stack(v) for k, v in rows.items()}
+    eager['last_obs'] = o
+    _same(fused, eager, ROWS + ('ref',))
+    assert torch.equal(a.get_qp_allocator_state(), S) and bool(S.any())
+
+
+@pytest.mark.parametrize('preset', [False, True])
+@pytest.mark.parametrize('filt', [False, True])
+def test_pieces_graph_replay_and_checkpoint_give_the_rows_of_one_flight(filt, preset):
+    import torch
+    from ml4ca_amd.policy import controller_rollout
+    kw = dict(preset=preset, auto_reset=True, terminate=True, max_ep_len=40)
+    a, b, c = (_start(_env(**kw), filt, preset) for _ in range(3))
+    refs = _refs(a.device)
+    keys = ('obs', 'act', 'rew', 'done') + (('ref',) if filt else ())
+    one = controller_rollout(a, TC, switch_steps=(5,), refs=refs)
+    # two launches of T / 2
+    h1 = {k: v.clone() for k, v in controller_rollout(b, TC // 2, switch_steps=(5,), refs=refs).items()}
+    # ... with a checkpoint between them: state, counters, current, z, thruster state, lag columns and the filter into a fresh handle
+    d = _start(_env(**kw), filt, preset)
+    _restore(d, _checkpoint(b, filt))
+    h2 = controller_rollout(b, TC // 2)
+    for k in keys:
+        assert torch.equal(one[k][:TC // 2], h1[k]) and torch.equal(one[k][TC // 2:], h2[k]), k
+    assert torch.equal(one['last_obs'], h2['last_obs'])
+    assert torch.equal(a.get_qp_allocator_state(), b.get_qp_allocator_state())
+    assert torch.equal(a.get_dp_controller_state(), b.get_dp_controller_state())
+    h2d = controller_rollout(d, TC // 2)
+    _same(h2, h2d, keys + ('last_obs',), what='checkpoint')
+    assert torch.equal(d.get_qp_allocator_state(), b.get_qp_allocator_state())
+    for x, y in zip(d.get_state() + d.get_current(), b.get_state() + b.get_current()):
+        assert torch.equal(x, y)
+    assert bool((one['done'] != 0).any())
+    # graph replay = eager: c is replayed, a flies on eagerly
+    out = controller_rollout(c, TC, switch_steps=(5,), refs=refs)
+    _same(out, one, keys + ('last_obs',), what='third handle')
+    buf = controller_rollout(c, 8)
+    eager = {k: v.clone() for k, v in controller_rollout(a, 8).items()}
+    _same(buf, eager, keys + ('last_obs',), what='warm-up')
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g):
+        controller_rollout(c, 8, out=buf)
+    for k in range(2):
+        g.replay()
+        eager = controller_rollout(a, 8)
+        torch.cuda.synchronize()
+        _same(buf, eager, keys + ('last_obs',), what='replay %d' % k)
+    assert torch.equal(a.get_qp_allocator_state(), c.get_qp_allocator_state())
+
+
+def _refused(fn, word):
+    from ml4ca_amd import DpenvError
+    with pytest.raises(DpenvError, match=word):
+        fn()
+
+
+def test_refusals_leave_the_handle_alone():
+    import ml4ca_amd
+    import torch
+    from ml4ca_amd.deploy import dp_controller_table
+    from ml4ca_amd.policy import controller_rollout
+    n = 64
+    kw = dict(auto_reset=True, terminate=True, max_ep_len=40)
+    a, b = (_start(_env(n, **kw)) for _ in range(2))
+    # each refused field, one by one: the handle flies the rows of one that never asked
+    cases = [('iterations', 0), ('iterations', 33), ('w_power', -1.0), ('w_power', float('nan')), ('w_dalpha', 0.0), ('w_dforce', 0.0),
+             ('w_dforce', float('inf'))]
+    for field, bad in (('w_slack', -1.0), ('w_slack', float('nan')), ('f_max', -1.0), ('force_rate', -1.0), ('azimuth_rate', -1.0),
+                       ('lx', float('nan')), ('ly', float('inf')), ('kf', 0.0), ('kr', 0.0)):
+        cases += [(field, k, bad) for k in range(2 if field == 'azimuth_rate' else 3)]
+    for case in cases:
+        p = {k: (np.array(v, np.float64) if np.ndim(v) else v) for k, v in _params(16).items()}
+        if len(case) == 2:
+            p[case[0]] = case[1]
+        else:
+            p[case[0]][case[1]] = case[2]
+        _refused(lambda: a.set_qp_allocator(p), 'QP allocator')
+        assert a.qp_allocator is not None and a.qp_allocator['iterations'] == 16
+    _same(controller_rollout(a, 6), controller_rollout(b, 6), what='after the refused fields')
+    assert torch.equal(a.get_qp_allocator_state(), b.get_qp_allocator_state())
+    # a per-env controller table while the QP is set
+    tab = torch.from_numpy(dp_controller_table(n)).to(a.device)
+    _refused(lambda: a.set_dp_controller_table(tab, check=False), 'per-env controller table')
+    _same(controller_rollout(a, 6), controller_rollout(b, 6), what='after the refused table')
+    # NULL returns to the pseudo-inverse rows bit for bit; dpenv_set_dp_controller drops the QP
+    c, d, e = (_env(n, **kw) for _ in range(3))
+    for x in (c, d, e):
+        _start(x)
+    c.set_qp_allocator(off=True)
+    d.set_dp_controller()
+    assert c.qp_allocator is None and d.qp_allocator is None
+    e.set_qp_allocator(off=True)
+    e.set_dp_controller()
+    for x in (c, d, e):                                  # (set_dp_controller zeroed z of d and e; c's z was zero already)
+        x.set_state(*b.get_state())
+    plain = _start(_env(n, **kw), qp=False)                                            # a handle that never had one
+    plain.set_state(*b.get_state())
+    ref = controller_rollout(plain, 6)
+    for x in (c, d, e):
+        _same(controller_rollout(x, 6), ref, what='pseudo-inverse again')
+        _refused(x.get_qp_allocator_state, 'no QP allocator')
+    assert not torch.equal(ref['act'], controller_rollout(b, 6)['act'])                # ... which are not the QP's rows
+    # the QP with the controller off; and each unsupported kind of handle, with the set named
+    f = _env(n, **kw)
+    f.reset()
+    _refused(f.set_qp_allocator, 'DP controller is off')
+    for mode, mkw in (('limited', {}), ('final_wrap', {}), ('final_cont', dict(ext=False))):   # kinds the DP controller itself refuses: never on
+        v = H.make_pair(mode, n, seed=2, **mkw)[0]
+        v.reset()
+        _refused(v.set_qp_allocator, 'DP controller is off')
+    w = _env(n, **kw)
+    w.set_integral_action()                                                            # ... and a handle with the integral action
+    w.reset()
+    _refused(w.set_qp_allocator, 'DP controller is off')
+    two = np.stack([ml4ca_amd.default_vessel(), ml4ca_amd.default_vessel() * np.float32(1.1)])        # two vessel classes
+    v = H.make_pair('final_cont', n, seed=2, vessel_params=two)[0]
+    v.set_vessel_class((torch.arange(n, device=v.device) % 2).to(torch.int32))
+    v.reset()
+    _refused(v.set_qp_allocator, 'DP controller is off')
+    # the integral action turned on behind the controller and the QP: the setter and the launch name the supported set
+    u, u2 = (_start(_env(n, **kw)) for _ in range(2))
+    u.set_integral_action()
+    _refused(u.set_qp_allocator, 'integral action off')
+    _refused(lambda: controller_rollout(u, 6), 'integral action off')
+    u.set_integral_action(None)
+    _same(controller_rollout(u, 6), controller_rollout(u2, 6), what='after the integral action')
+    g = _env(n, **kw)
+    g.set_vessel_params(ml4ca_amd.default_vessel())                                    # per-env hull blocks
+    g.set_dp_controller()
+    _refused(g.set_qp_allocator, 'per-env hull blocks')
+    h = _env(n, **kw)
+    h.set_dp_controller()
+    h.set_dp_controller_table(tab)
+    _refused(h.set_qp_allocator, 'per-env controller table')
+    h.reset()
+    g.reset()
+    for x, tabbed in ((g, False), (h, True)):                                          # they fly what they flew before
+        y = _env(n, **kw)
+        if not tabbed:
+            y.set_vessel_params(ml4ca_amd.default_vessel())
+        y.set_dp_controller()
+        if tabbed:
+            y.set_dp_controller_table(tab)
+        y.reset()
+        _same(controller_rollout(x, 6), controller_rollout(y, 6), what='unsupported kind')
+    # a handle that becomes unsupported after the QP was set is refused at the launch
+    a.set_vessel_params(ml4ca_amd.default_vessel())
+    _refused(lambda: controller_rollout(a, 6), 'per-env hull blocks')
+
+
+def test_scored_comparison_on_the_box_test():
+    """evaluate.baseline_box_test(allocator='qp'), 64 envs, calm: the IAE of the float64 host flight on the float64 oracle within 4 x the
+    float32-vs-float64 difference of the HOST flights (both flown and pinned by tests/test_qp_allocator_cpu.py, which takes a minute of
+    NumPy: BOX_IAE_F64, BOX_IAE_F32_GAP); thruster work below the pseudo-inverse's from the same call."""
+    import torch
+    from ml4ca_amd import evaluate
+    from tests.test_qp_allocator_cpu import BOX_IAE_F32_GAP, BOX_IAE_F64
+    yard = BOX_IAE_F32_GAP
+    env = H.make_pair('final_cont', 64, terminate=False, seed=3)[0]
+    qp = evaluate.baseline_box_test(env, allocator='qp')
+    pinv = evaluate.baseline_box_test(env, allocator='pinv')
+    assert env.qp_allocator is None
+    gap = float((qp['iae'].double() - BOX_IAE_F64).abs().max())
+    print('box test IAE: device QP %.4f, float64 host flight %.4f, float32 host flight within %.4f of it (yardstick %.3g, device gap %.3g); '
+          'pseudo-inverse %.2f; work QP %s, pseudo-inverse %s' % (float(qp['iae'].mean()), BOX_IAE_F64, BOX_IAE_F32_GAP, yard, gap,
+                                                                    float(pinv['iae'].mean()), qp['work'].mean(0).tolist(), pinv['work'].mean(0).tolist()))
+    assert gap <= 4.0 * yard
+    assert bool((qp['work'].sum(1) < pinv['work'].sum(1)).all())
+    assert bool(torch.isfinite(qp['e']).all())

@@ -1226,13 +1226,10 @@ extern "C" int dpenv_controller_rollout(dpenv_handle h, const dpenv_controller_r
     FilterArgs fa = h->reff;
     fa.out = io->ref_out;
     const int ves = rollout_ves(vessel_source(h));
-    hipError_t e;
-    if (h->qp_on) {                                        // the handle may have changed since dpenv_set_qp_allocator
-        if (h->ctrl_tab_on || (ves != VES_ARGS && ves != VES_ARGS_LOSS)) return fail(h, DPENV_EINVAL, "dpenv_controller_rollout: " QP_SET_MSG);
-        e = dev::launch_controller_rollout_qp(&a, &ca, h->reff_on ? &fa : nullptr, &h->qp, ves, (hipStream_t)s);
-    } else {
-        e = dev::launch_controller_rollout(&a, &ca, h->reff_on ? &fa : nullptr, h->ctrl_tab_on ? h->ctrl_tab : nullptr, ves, (hipStream_t)s);
-    }
+    // the handle may have changed since dpenv_set_qp_allocator
+    if (h->qp_on && (h->ctrl_tab_on || (ves != VES_ARGS && ves != VES_ARGS_LOSS))) return fail(h, DPENV_EINVAL, "dpenv_controller_rollout: " QP_SET_MSG);
+    const hipError_t e = dev::launch_controller_rollout(&a, &ca, h->reff_on ? &fa : nullptr, h->ctrl_tab_on ? h->ctrl_tab : nullptr,
+                                                        h->qp_on ? &h->qp : nullptr, ves, (hipStream_t)s);
     if (e != hipSuccess) return fail(h, DPENV_EHIP, "controller launch failed: %s", hipGetErrorString(e));
     h->lag_valid = true;
     return DPENV_OK;

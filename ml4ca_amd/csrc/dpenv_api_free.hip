@@ -299,7 +299,7 @@ extern "C" int dpenv_thrust_alloc(const dpenv_dp_controller* c, const float* tau
     return DPENV_OK;
 }
 
-// ---- the rate-limited QP thrust allocation (dpenv.h; the kernel is dpenv_qp.hip's) -----------------------------------------------------
+// ---- the rate-limited QP thrust allocation (dpenv.h; the kernel is dpenv_control.hip's) ------------------------------------------------
 extern "C" int dpenv_qp_allocator_defaults(dpenv_qp_allocator* q)
 {
     if (!q) return fail(nullptr, DPENV_EINVAL, "dpenv_qp_allocator_defaults: q is NULL");

@@ -1,6 +1,6 @@
 // dpenv_control_law.h - the baseline DP controller's law (include/dpenv.h states it operation by operation): the numbers of one env, the
 // packed per-env table's index and load, the allocation and one control step.  The ONE text of the law on the device: included inside
-// namespace dpenv by dpenv_control_dev.h (the closed-loop kernels, dpenv_policy.hip) and by dpenv_label.hip (the labelling scan), after
+// namespace dpenv by dpenv_control.hip (the closed-loop kernels) and by dpenv_label.hip (the labelling scan), after
 // dpenv_dev.h.  Everything here is plain f32 in the stated order: the build has -ffp-contract=off, `/` and sqrtf are the compiler's
 // correctly rounded forms.
 #ifndef DPENV_CONTROL_LAW_H

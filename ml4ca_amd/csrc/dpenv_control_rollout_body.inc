@@ -1,5 +1,5 @@
-// dpenv_control_rollout_body.inc - the body of controller_rollout_kernel and controller_rollout_tab_kernel (dpenv_control_dev.h), included
-// into each (see dpenv_policy_rollout_body.inc for why it is spliced, not called).  In scope: a (StepArgs), ca (ControlArgs), fa
+// dpenv_control_rollout_body.inc - the body of controller_rollout_kernel, controller_rollout_tab_kernel and controller_rollout_qp_kernel
+// (dpenv_control.hip), included into each (see dpenv_policy_rollout_body.inc for why it is spliced, not called).  In scope: a (StepArgs), ca (ControlArgs), fa
 // (FilterArgs), the compile-time TAB and, if TAB, tab (the packed per-env controller block, ctrl_tab_index), the compile-time QP and, if QP,
 // qr (QpRollout: the rate-limited QP allocation of dpenv_qp_law.h in place of dp_allocate, its thruster state carried beside z); the
 // rest are the kernel's template arguments.

@@ -15,7 +15,7 @@ constexpr int MAX_SWITCH = 8;
 // slots of the public per-env controller table float[CTRL_NPARAM][n] = DPENV_CTRL_* of include/dpenv.h (dpenv_api.hip asserts it)
 constexpr int CTRL_NPARAM = 32, CTRL_KP = 0, CTRL_KD = 3, CTRL_KI = 6, CTRL_ZB = 9, CTRL_TMAX = 12, CTRL_WEIGHT = 15, CTRL_LX = 20,
               CTRL_LY = 23, CTRL_KF = 26, CTRL_KR_BOW = 29, CTRL_F_EPS = 30;
-constexpr int CTRL_TAB_STREAMS = 9;   // float4 streams of the packed per-env block (dpenv_control_dev.h has its layout)
+constexpr int CTRL_TAB_STREAMS = 9;   // float4 streams of the packed per-env block (dpenv_control_law.h has its layout)
 constexpr int64_t ctrl_tab_float4s(int n) { return ((int64_t)n + 63) / 64 * 64 * CTRL_TAB_STREAMS; }   // whole waves of 64 envs
 constexpr int MAX_CLASSES = 64;
 
@@ -210,7 +210,7 @@ struct FilterArgs {
 };
 
 // the baseline DP controller in the closed loop (dpenv_set_dp_controller / dpenv_controller_rollout; include/dpenv.h has the law,
-// dpenv_control_dev.h the kernels): the law's numbers, its per-env state and the I/O of one launch
+// dpenv_control.hip the kernels): the law's numbers, its per-env state and the I/O of one launch
 struct ControlArgs {
     float4* z;                // [n] the error integral z[0..2] (one pad)
     float kp[3], kd[3], ki[3], zb[3], tmax[3];
@@ -231,7 +231,7 @@ struct ControlArgs {
     const float* refs;        // [n_switch][3][n]
 };
 
-// the rate-limited QP thrust allocation (dpenv_thrust_alloc_qp; include/dpenv.h has the law, dpenv_qp_law.h its device text, dpenv_qp.hip
+// the rate-limited QP thrust allocation (dpenv_thrust_alloc_qp; include/dpenv.h has the law, dpenv_qp_law.h its device text, dpenv_control.hip
 // the kernel): the law's numbers in env order bow, port, star, and the I/O of one call
 struct QpArgs {
     float ws[3], wp, wda, wdf;  // slack, power, azimuth-change and force-change weights
@@ -468,11 +468,13 @@ hipError_t launch_integ_state_io(float4* state, float* I, int32_t* c, int n, int
 // (x float[9][n] | r float[3][n], either may be NULL)
 hipError_t launch_reff_rest(const float4* RF, float4* state, const uint8_t* mask, int n, hipStream_t s);
 hipError_t launch_reff_state_io(float4* state, float* x, float* r, int n, int write, hipStream_t s);
-// dpenv_policy.hip, from dpenv_control_dev.h: the baseline controller's closed loop (fa != NULL: with the reference filter; ves as
+// dpenv_control.hip: the baseline controller's closed loop (fa != NULL: with the reference filter; ves as
 // launch_rollout's, classes excluded), its state (op 0 read into ext float[3][n], 1 write from it, 2 zero the envs of mask) and the
 // stateless allocation tau [3][n] -> action [n][7]
 // tab: the packed per-env block launch_pack_controllers wrote (every env flies its own row: the *_tab kernels), or NULL (ca's shared numbers)
-hipError_t launch_controller_rollout(const StepArgs* a, const ControlArgs* ca, const FilterArgs* fa, const float4* tab, int ves, hipStream_t s);
+// qr: the QP allocation in place of the pseudo-inverse (tab NULL; VES_ARGS and VES_ARGS_LOSS only), or NULL
+hipError_t launch_controller_rollout(const StepArgs* a, const ControlArgs* ca, const FilterArgs* fa, const float4* tab, const QpRollout* qr, int ves,
+                                     hipStream_t s);
 // the public table float[CTRL_NPARAM][n] -> the packed block of ctrl_tab_float4s(n) float4; refused: uint8 [n] or NULL (dpenv_set_dp_controller_table)
 hipError_t launch_pack_controllers(const float* table, float4* tab, uint8_t* refused, int n, hipStream_t s);
 hipError_t launch_control_state(float4* z, float* ext, const uint8_t* mask, int n, int op, hipStream_t s);
@@ -480,11 +482,9 @@ hipError_t launch_thrust_alloc(const ControlArgs* ca, const float* tau, float* a
 // dpenv_label.hip: the law scanned over the T rows of a block, one lane per env (tab as launch_controller_rollout's; obs_bf16: the obs rows
 // are bf16); reads ca's numbers and dt only
 hipError_t launch_controller_label(const ControlArgs* ca, const LabelArgs* la, const float4* tab, int obs_bf16, hipStream_t s);
-// dpenv_qp.hip: one control step of the QP allocation for n envs, one lane per env
+// dpenv_control.hip: one control step of the QP allocation for n envs, one lane per env
 hipError_t launch_qp_alloc(const QpArgs* qa, const QpAllocIO* io, hipStream_t s);
-// the baseline's closed loop with the QP allocation in place of the pseudo-inverse (fa, ves as launch_controller_rollout's; VES_ARGS and
-// VES_ARGS_LOSS only), and the zeroing of its state for the envs of mask (NULL = every env)
-hipError_t launch_controller_rollout_qp(const StepArgs* a, const ControlArgs* ca, const FilterArgs* fa, const QpRollout* qr, int ves, hipStream_t s);
+// the zeroing of the closed loop's QP thruster state for the envs of mask (NULL = every env)
 hipError_t launch_qp_state_clear(float* state, const uint8_t* mask, int n, hipStream_t s);
 // two-wave closed loop, dpenv_policy_ws.h; one arithmetic per translation unit: dpenv_policy_ws.hip PREC_F16, dpenv_policy_xws1.hip
 // PREC_F32, dpenv_policy_xws2.hip PREC_F32_ACTOR

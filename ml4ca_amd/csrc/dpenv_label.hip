@@ -1,18 +1,21 @@
 // dpenv_label.hip - the baseline DP controller's law evaluated on rows some other flight wrote (dpenv_controller_label in dpenv.h): expert
 // labels for the states an actor visited (DAgger), or the distance between an actor's actions and the baseline's on those states.
 //
-// The law exists once, in dpenv_control_law.h; the closed-loop kernels (dpenv_control_dev.h, dpenv_policy.hip) weld it to env_step, this unit
-// scans it over a [T][n][9] observation block.  The integral z is carried along each env's row sequence and zeroed behind every done
-// row, so the label of row t depends on every row before it: a scan, one lane per env, not a map over rows.
+// The law exists once, in dpenv_control_law.h; the closed-loop kernels (dpenv_control.hip) weld it to env_step, this unit scans it over a
+// [T][n][9] observation block.  The integral z is carried along each env's row sequence and zeroed behind every done row, so the label
+// of row t depends on every row before it: a scan, one lane per env, not a map over rows.
 //
-// A unit of its own with the library's CXXFLAGS: no other unit's kernels see a new instantiation (dpenv_control_dev.h records what a
-// second instantiation of a shared template does to its neighbours' schedules).  Per env-row 36 B of observation (18 B as bf16) and a
+// A unit of its own with the library's CXXFLAGS: no other unit's kernels see a new instantiation (dpenv_control_rows.h records what a
+// second instantiation of a shared template does to its neighbours' schedules).  Not merged into dpenv_control.hip: that re-schedules
+// the QP closed loop (all four controller_rollout_qp_kernel instantiations).  Per env-row 36 B of observation (18 B as bf16) and a
 // done byte come in, 28 B of action go out; the handle's state is neither read nor written.
 #include "dpenv_env_dev.h"
 
 namespace dpenv {
 
 #include "dpenv_control_law.h"
+// control_store_rows: a wave's 64 action rows staged through the wave-private LDS area, stored coalesced
+#include "dpenv_control_rows.h"
 
 namespace {
 
@@ -23,22 +26,6 @@ struct LabelRow {
     float o[6];
     uint32_t d;
 };
-
-// control_store_rows<7> of dpenv_control_dev.h restated for f32 rows: a wave's 64 action rows staged through the wave-private LDS area,
-// stored coalesced.  A copy for the reason given there.
-__device__ __forceinline__ void label_store_rows(float* lds, float* dst, int64_t base, int64_t rem, const float* v, int lane)
-{
-    constexpr int W = 7;
-    lds_order<64>();
-#pragma unroll
-    for (int k = 0; k < W; ++k) lds[lane * W + k] = v[k];
-    lds_order<64>();
-    const bool full = rem >= (int64_t)64 * W;                    // uniform; the last wave's dead lanes hold no row
-    float* p = dst + base;
-#pragma unroll
-    for (int j = 0; j < W; ++j)
-        if (full || j * 64 + lane < rem) p[(unsigned)(j * 64 + lane)] = lds[j * 64 + lane];
-}
 
 // Forward scan over the T rows of a block, one lane per env, one wave per workgroup.  The law is serial in t, but no load depends on it:
 // rows are fetched LABEL_U at a time into one of two register banks while the other is consumed.  TAB: the env's own row of the packed
@@ -98,7 +85,7 @@ __global__ __launch_bounds__(64) void controller_label_kernel(const ControlArgs 
             o[6] = o[7] = o[8] = 0.0f;                           // the thrust columns: the law does not read them
             if constexpr (TAB) dp_control(cl, o, z, act);
             else dp_control(ca, o, z, act);
-            label_store_rows(lds_row, la.act, (int64_t)t * stride_a + w_a, rem_a, act, lane);
+            control_store_rows<A>(lds_row, la.act, (int64_t)t * stride_a + w_a, rem_a, act, lane, false);
             if (buf[u].d != 0u) z[0] = z[1] = z[2] = 0.0f;       // the next row is a new episode's first
         }
     };

@@ -223,10 +223,6 @@ __global__ __launch_bounds__(256) void pack_policy_kernel(const PackNet pi, cons
     }
 }
 
-// the baseline DP controller's closed loop, its state and the stateless allocation: this unit has both the env's and the filter's device
-// functions
-#include "dpenv_control_dev.h"
-
 }  // namespace dpenv
 
 using namespace dpenv;
@@ -272,43 +268,6 @@ hipError_t dev::launch_policy_rollout(const StepArgs* a, const PolicyArgs* pa, c
         if constexpr (integ_one_wave(M, E, K)) return launch_with_lds(policy_rollout_integ_kernel<M, E, K>, grid, block, lds, s, *a, *pa, *ia);
         return hipErrorInvalidValue;
     });
-}
-
-hipError_t dev::launch_controller_rollout(const StepArgs* a, const ControlArgs* ca, const FilterArgs* fa, const float4* tab, int ves,
-                                          hipStream_t s)
-{
-    // the vessel source must match the arguments (as launch_rollout's): a per-env form needs the table, VES_ARGS_LOSS and only it reads StepArgs.kl
-    if ((ves == VES_ENV_VGPR || ves == VES_ENV_RND) && !a->env_tab) return hipErrorInvalidValue;
-    if ((ves == VES_ARGS_LOSS) != (a->loss_on == LOSS_SHARED)) return hipErrorInvalidValue;
-    const dim3 grid((a->n + RBLOCK - 1) / RBLOCK), block(RBLOCK);
-    return with_control_ves(ves, [&](auto V) {
-        if (tab) {
-            if (fa) hipLaunchKernelGGL((controller_rollout_tab_kernel<V, true>), grid, block, 0, s, *a, *ca, *fa, tab);
-            else hipLaunchKernelGGL((controller_rollout_tab_kernel<V, false>), grid, block, 0, s, *a, *ca, FilterArgs{}, tab);
-            return hipGetLastError();
-        }
-        if (fa) hipLaunchKernelGGL((controller_rollout_kernel<V, true>), grid, block, 0, s, *a, *ca, *fa);
-        else hipLaunchKernelGGL((controller_rollout_kernel<V, false>), grid, block, 0, s, *a, *ca, FilterArgs{});
-        return hipGetLastError();
-    });
-}
-
-hipError_t dev::launch_pack_controllers(const float* table, float4* tab, uint8_t* refused, int n, hipStream_t s)
-{
-    hipLaunchKernelGGL(pack_controllers_kernel, dim3((n + 255) / 256), dim3(256), 0, s, table, tab, refused, n);
-    return hipGetLastError();
-}
-
-hipError_t dev::launch_control_state(float4* z, float* ext, const uint8_t* mask, int n, int op, hipStream_t s)
-{
-    hipLaunchKernelGGL(control_state_kernel, dim3((n + 255) / 256), dim3(256), 0, s, z, ext, mask, n, op);
-    return hipGetLastError();
-}
-
-hipError_t dev::launch_thrust_alloc(const ControlArgs* ca, const float* tau, float* action, int n, hipStream_t s)
-{
-    hipLaunchKernelGGL(alloc_kernel, dim3((n + 255) / 256), dim3(256), 0, s, *ca, tau, action, n);
-    return hipGetLastError();
 }
 
 hipError_t dev::launch_integ_clear(float4* state, const uint8_t* mask, int n, hipStream_t s)

@@ -1,7 +1,7 @@
 // dpenv_qp_law.h - the rate-limited QP thrust allocation (dpenv_thrust_alloc_qp in include/dpenv.h, which states the law operation by
 // operation): the reference's nonlinear "QP" allocator (qp_allocator.py:108-234) with the slack eliminated, solved by a fixed number of
-// projected Levenberg-Marquardt steps with accept / reject.  The ONE text of the law on the device: included inside namespace dpenv, after
-// dpenv_env_dev.h (sincos_lean, wrap_angle).  deploy.BatchedQPAllocator is the host statement.
+// projected Levenberg-Marquardt steps with accept / reject.  The ONE text of the law on the device: included inside namespace dpenv by
+// dpenv_control.hip, after dpenv_env_dev.h (sincos_lean, wrap_angle).  deploy.BatchedQPAllocator is the host statement.
 //
 // Everything is plain f32 in the stated order (the build has -ffp-contract=off; `/` and sqrtf are the compiler's correctly rounded forms),
 // branch-free per lane apart from the iteration loop, whose count is wave-uniform.  Five unknowns per env: every array below is indexed

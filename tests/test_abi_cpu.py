@@ -150,8 +150,8 @@ def test_no_packed_fp32_in_any_translation_unit():
     flags = re.search(r'^CXXFLAGS \?= (.*)$', mk, re.M).group(1).split()
     assert '-fno-slp-vectorize' in flags
     units = re.search(r'^SRC := (.*)$', mk, re.M).group(1).split()
-    assert sorted(units) == ['dpenv_api.hip', 'dpenv_api_free.hip', 'dpenv_kernels.hip', 'dpenv_policy.hip', 'dpenv_policy_ws.hip', 'dpenv_policy_x.hip',
-                             'dpenv_policy_xws1.hip', 'dpenv_policy_xws2.hip']
+    assert sorted(units) == ['dpenv_api.hip', 'dpenv_api_free.hip', 'dpenv_control.hip', 'dpenv_kernels.hip', 'dpenv_label.hip', 'dpenv_policy.hip',
+                             'dpenv_policy_ws.hip', 'dpenv_policy_x.hip', 'dpenv_policy_xws1.hip', 'dpenv_policy_xws2.hip']
 
     def isa(unit):
         # the policy units instantiate ~40 kernels each from ONE template (env variant x obs width x layer width x activation) and

@@ -19,7 +19,7 @@ for u in ws xws1 xws2; do
   fi
 done
 wait
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -o build/wsdiag/$name.so build/obj/dpenv_kernels.o build/obj/dpenv_api.o build/obj/dpenv_api_free.o build/obj/dpenv_policy.o \
+/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -o build/wsdiag/$name.so build/obj/dpenv_kernels.o build/obj/dpenv_api.o build/obj/dpenv_api_free.o build/obj/dpenv_control.o build/obj/dpenv_policy.o \
     build/obj/dpenv_policy_x.o $objs
 grep -h -A9 "Function Name" /tmp/dpenv_variants/*_$name.res | grep -E "Function Name|VGPRs:|ScratchSize|LDS Size|Occupancy" | sed 's/.*remark: //'
 echo built build/wsdiag/$name.so

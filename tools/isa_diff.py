@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Which kernels of two builds of the library are the same instruction stream?  Disassembles every code object of both (llvm-objdump), splits by
-kernel symbol, strips addresses / encodings, and compares; a kernel of only one build is NEW or MISSING.  Usage: python tools/isa_diff.py OLD.so
+kernel symbol, strips addresses / encodings / the alignment fill behind the last instruction, and compares; a kernel of only one build is NEW or MISSING.  Usage: python tools/isa_diff.py OLD.so
 NEW.so [substring ...]   (kernels whose demangled name contains every substring).  Used in round 5 to show that a feature compiled into the general per-env kernels left every default kernel alone."""
 import os
 import re
@@ -27,6 +27,11 @@ def kernels(lib):
                 ln = pc_relative(ln, addr, pc, labels)
                 if ln and ln != '...':                      # '...': zero padding up to whatever the linker placed next
                     body.append(ln)
+            # s_nop 0 behind the last instruction: the assembler's fill up to the next kernel of the same section (256-byte starts), which
+            # the unit's last kernel does not have.  Like the linker's padding it is never executed and says where the kernel sits, not
+            # what it is: a kernel that only moved to another unit, or whose neighbour left, would DIFFER.
+            while body and body[-1] == 's_nop 0':
+                body.pop()
             out[m.group(1)] = body
     return out
 

@@ -16,6 +16,8 @@ env.step, critic, trajectory rows), GAE by one scan kernel, advantage statistics
                                                                                       actor first (PPOUpdater.pretrain on one controller_rollout), then PPO
     python examples/train_ppo.py --envs 4096 --epochs 30 --update fused --warm-start 300 --dagger 5 --eval      ... then DAgger: fly the clone, label ITS
                                                                                       states with the baseline (policy.controller_label), aggregate, refit
+    python examples/train_ppo.py --envs 4096 --epochs 30 --update fused --warm-start 300 --dagger 5 --expert qp --eval      the same with the PID + QP
+                                                                                      chain as the expert: it flies the demonstration and labels the rounds
     python examples/train_ppo.py --envs 4096 --epochs 40 --randomise 0.15 --eval      domain randomisation: every episode of every env
                                                                                       runs on its own hull, +-15 % on all 26 parameters, re-drawn by the reset path
                                                                                       inside the rollout launch; --eval: the reference's evaluation harness
@@ -157,14 +159,16 @@ def warm_start(upd, env, args, out=print):
     defaults of the nominal hull) flies the training envs for --warm-start-steps steps in one launch; its obs / act rows are the
     demonstration PPOUpdater.pretrain fits the actor to, and their discounted returns what pretrain_critic fits the critic to.  The
     actor is memoryless: it sees o, not the PID's integral z, so in a current the clone holds station with an offset unless it is flown
-    with env.set_integral_action().
+    with env.set_integral_action().  --expert qp: the same PID with the rate-limited QP allocation flies the demonstration.
     Several ranks: every rank flies its own envs and draws its own minibatches, exactly as in the PPO epochs with --exchange gradients, and
     every step's gradient-and-statistics buffer is averaged across the ranks (dist.average_flat) before its Adam step, whatever --exchange
     says: the replicas take the same steps and enter PPO with the same parameters (checked once, dist.assert_params_in_step)."""
-    from ml4ca_amd.deploy import dp_controller_defaults
+    from ml4ca_amd.deploy import dp_controller_defaults, qp_allocator_defaults
     from ml4ca_amd.policy import controller_rollout
     T = args.warm_start_steps or args.steps
     env.set_dp_controller(dp_controller_defaults(ml4ca_amd.default_vessel(args.preset)))
+    if args.expert == 'qp':                                                       # the demonstration is the PID + QP chain's flight
+        env.set_qp_allocator(qp_allocator_defaults(ml4ca_amd.default_vessel(args.preset)))
     env.reset()
     o = controller_rollout(env, T)
     _, ret = rollout.gae(o['rew'], torch.zeros_like(o['rew']), end=o['done'], gamma=0.99, lam=0.97)      # rewards-to-go (ppo.py:88)
@@ -175,6 +179,8 @@ def warm_start(upd, env, args, out=print):
     hv = upd.pretrain_critic(obs, ret, args.warm_start, minibatch=mb, average=D.average_flat)
     torch.cuda.synchronize()
     D.assert_params_in_step(list(upd.ac.parameters()), what='warm-started parameters')
+    if args.expert == 'qp':
+        env.set_qp_allocator(off=True)
     env.set_dp_controller(off=True)
     out('warm start: %d rows of the baseline (reward/step %.3f), %d %s steps + as many critic steps in %.2f s: MSE %.4g -> %.4g  NLL %.4g -> %.4g  V-loss %.4g -> %.4g' % (
         obs.shape[0], float(o['rew'].mean()), args.warm_start, args.warm_start_loss, time.perf_counter() - t0,
@@ -186,15 +192,21 @@ def dagger(upd, env, args, out=print):
     """--dagger: after the warm start (if any) and before PPO, fly the ACTOR on the training envs, label the states it visits with the
     baseline (policy.controller_label: the PID + pseudo-inverse law scanned over the actor's rows in one launch), aggregate the rounds and
     refit (PPOUpdater.dagger).  A clone trained on the expert's states alone has no labels where its own errors take it; these rounds
-    supply them.  The labels carry the PID's integral, which the memoryless actor cannot see: it can only fit their mean given o."""
-    from ml4ca_amd.deploy import dp_controller_defaults
+    supply them.  The labels carry the PID's integral, which the memoryless actor cannot see: it can only fit their mean given o.
+    --expert qp labels with the PID + rate-limited QP chain instead (policy.controller_label_qp), whose labels carry its thruster state
+    as well."""
+    from ml4ca_amd.deploy import dp_controller_defaults, qp_allocator_defaults
     T = args.dagger_steps or args.steps
-    env.set_dp_controller(dp_controller_defaults(ml4ca_amd.default_vessel(args.preset)))
+    nominal = ml4ca_amd.default_vessel(args.preset)
+    env.set_dp_controller(dp_controller_defaults(nominal))
     env.reset()
     mb = min(args.minibatch, T * env.n_envs)
     t0 = time.perf_counter()
+    # --expert qp: the labels are the PID + QP chain's (policy.controller_label_qp), with the nominal hull's lever arms and thrust constants;
+    # the scan touches no hull, so it labels the randomised-hull envs the QP closed loop cannot fly
     rec = upd.dagger(env, args.dagger, T, args.dagger_iters, minibatch=mb, loss=args.warm_start_loss, keep=args.dagger_keep or None,
-                     average=D.average_flat, upload=dict(precision=args.precision))
+                     average=D.average_flat, upload=dict(precision=args.precision), expert=args.expert,
+                     qp_params=qp_allocator_defaults(nominal) if args.expert == 'qp' else None)
     torch.cuda.synchronize()
     D.assert_params_in_step(list(upd.ac.parameters()), what='parameters after DAgger')
     env.set_dp_controller(off=True)
@@ -272,6 +284,10 @@ def main():
     ap.add_argument('--dagger-iters', type=int, default=100, metavar='ITERS', help='gradient steps per DAgger round (loss: --warm-start-loss)')
     ap.add_argument('--dagger-steps', type=int, default=0, metavar='T', help='steps of each DAgger flight (default: one episode, --steps)')
     ap.add_argument('--dagger-keep', type=int, default=0, metavar='K', help='rounds kept in the aggregated dataset, a ring (default 0: all of them)')
+    ap.add_argument('--expert', default='pinv', choices=('pinv', 'qp'),
+                    help="the expert of --warm-start and --dagger: 'pinv' = PID + pseudo-inverse; 'qp' = the same PID with the rate-limited QP allocation "
+                         '(55 %% of the pseudo-inverse\'s thruster work on the box test): the warm-start flight flies it (env.set_qp_allocator), --dagger '
+                         'labels with it (policy.controller_label_qp)')
     ap.add_argument('--exchange', default='gradients', choices=('gradients', 'rollout'),
                     help="multi-rank runs: 'gradients' = every rank updates on ITS OWN episode and the gradients are averaged, exactly the "
                          "reference (ppo.py:226, mpi_tf.py:29-62: no trajectory ever crosses); 'rollout' = BASELINE.json config 4: the ranks "
@@ -305,6 +321,9 @@ def main():
         ap.error('--warm-start needs --update fused (the imitation gradient is a kernel of the fused update)')
     if args.dagger > 0 and args.update != 'fused':
         ap.error('--dagger needs --update fused (the imitation gradient is a kernel of the fused update)')
+    if args.expert == 'qp' and args.randomise > 0 and args.warm_start > 0:
+        ap.error('--expert qp with --randomise cannot fly the warm-start demonstration: the QP closed loop runs on a shared hull, not on per-env '
+                 'hulls.  Use --dagger without --warm-start: the labelling scan touches no hull')
     # one process per GPU under torch.distributed.run (backend nccl = RCCL); envs shard by global id, gradients average
     rank, world, local = int(os.environ.get('RANK', 0)), int(os.environ.get('WORLD_SIZE', 1)), int(os.environ.get('LOCAL_RANK', 0))
     dev = torch.device('cuda', 0 if args.same_device else local)

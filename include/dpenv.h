@@ -857,12 +857,57 @@ int dpenv_thrust_alloc_qp(const dpenv_qp_allocator* q, float dt, const float* ta
  * and whatever dpenv_set_dp_controller refuses: DPENV_EINVAL with the set named, at this call or - if the handle changed since - at the
  * launch.  Every refusal of a q that dpenv_thrust_alloc_qp refuses happens before any state changes.  The first call allocates the state
  * block (released with the handle); every later call is stream-ordered without allocation and graph-capturable.
- * dpenv_controller_label keeps labelling with the pseudo-inverse law whatever is set here. */
+ * dpenv_controller_label keeps labelling with the pseudo-inverse law whatever is set here; dpenv_controller_label_qp (below) labels with
+ * this one. */
 int dpenv_set_qp_allocator(dpenv_handle h, const dpenv_qp_allocator* q, dpenv_stream s);
 /* The checkpoint path of the thruster state, beside z's: device float[5][n_envs] = F_bow, F_port, F_star, a_port, a_star.  DPENV_EINVAL
  * while no QP allocator is set. */
 int dpenv_get_qp_allocator_state(dpenv_handle h, float* state_out, dpenv_stream s);
 int dpenv_set_qp_allocator_state(dpenv_handle h, const float* state_in, dpenv_stream s);
+/* The PID + QP chain on rows some other flight wrote (additive to ABI 6): dpenv_controller_label's scan with the QP law in place of the
+ * f_m / bow / stern lines - the low-energy expert's labels for the states an actor visited.  One launch, one lane per env; per row t and
+ * env i, in the order of the closed loop with a QP set:
+ *     o   = obs[t][i][0:6]                              (a bf16 value widened exactly)
+ *     tau = the PID lines of the DP controller's law on o with the env's z_i: z_i advanced first, the wrench clipped to tau_max
+ *     act[t][i][0:7], J = the QP law above on tau and the env's thruster state x_i, which it advances (the rule for a tau that is not
+ *                         finite and the wrap of the azimuths included)
+ *     cost[t][i] = J                                    (if cost is not NULL)
+ *     if (done && done[t][i] != 0) z_i = 0, x_i = 0     -- the next row is a new episode's first, from thrusters at rest
+ * z_i starts from z_in[:, i] and x_i from x_in[:, i] (NULL = 0); they are written to z_out / x_out at the end (NULL = not wanted; each
+ * may be its input), so a block labelled in pieces with z and x handed over gives the rows of one call.  x is the EXPERT'S OWN recursion
+ * along the rows, as z is: not the thruster state the flown actions would have left.
+ * The PID's numbers are the handle's controller in force: row i of dpenv_set_dp_controller_table's table on env i when there is one (G
+ * is not read), else dpenv_set_dp_controller's.  dt is the handle's, for z and for dF = force_rate * dt and da = azimuth_rate * dt, one
+ * f32 product each formed on the host.  q: the QP's numbers, validated with the checks of dpenv_thrust_alloc_qp; NULL = the ones
+ * dpenv_set_qp_allocator has in force on h.  The handle's hull kind does not matter - no hull is touched - so a handle with per-env hull
+ * blocks or a controller table, on which dpenv_set_qp_allocator is refused, labels with an explicit q.
+ * (A) For f32 rows written by dpenv_controller_rollout with a QP set and auto-reset on, labelled with that launch's done block, the z and
+ *     the thruster state it started from, the same controller and the same q, the labels are that launch's act rows bit for bit, z_out is
+ *     its final z and x_out its final dpenv_get_qp_allocator_state.
+ * (B) On any block the labels are dpenv_thrust_alloc_qp applied row by row to the PID's tau, with the state zeroed behind done rows, bit
+ *     for bit, cost included.
+ * The call reads and writes nothing of the handle's env state, its z, its own QP thruster state, the lagged thrust columns or the RNG
+ * counters.  Stream-ordered, no allocation, no host synchronisation; one kernel node when captured into a graph (a captured call flies
+ * the scalar numbers and the q of capture time, and whatever table the last packing wrote).  The scan is serial in T per env: at small n
+ * its cost is the closed loop's latency per row.
+ * DPENV_EINVAL with the reason in dpenv_last_error, before anything is launched or written: the controller off, a wrong struct_size,
+ * T <= 0, NULL obs or act, an obs_dtype that is neither DPENV_F32 nor DPENV_BF16, q NULL with no QP allocator set, and whatever
+ * dpenv_thrust_alloc_qp refuses of q.  ml4ca_amd.deploy.label_rows_qp is the host statement. */
+typedef struct dpenv_controller_label_qp_io {
+    uint32_t struct_size;    /* sizeof(dpenv_controller_label_qp_io), ABI check */
+    int32_t T;
+    const void* obs;         /* [T][n][9] rows in dpenv_policy_rollout's conventions; f32 or bf16; columns 0..5 read */
+    int32_t obs_dtype;       /* DPENV_F32 / DPENV_BF16: the block's, independent of the handle's config */
+    const uint8_t* done;     /* [T][n] DPENV_DONE_* bits, or NULL = no episode ends in the block */
+    const float* z_in;       /* [3][n] (dpenv_get_dp_controller_state's layout) or NULL = 0 */
+    float* z_out;            /* [3][n] or NULL; may be z_in */
+    const float* x_in;       /* [5][n] thruster state (dpenv_get_qp_allocator_state's layout) or NULL = 0 */
+    float* x_out;            /* [5][n] or NULL; may be x_in */
+    float* act;              /* [T][n][7] the chain's action on obs[t] */
+    float* cost;             /* [T][n] the final J of each row's solve, or NULL */
+    const dpenv_qp_allocator* q;   /* the QP's numbers; NULL = the ones dpenv_set_qp_allocator has in force on h */
+} dpenv_controller_label_qp_io;
+int dpenv_controller_label_qp(dpenv_handle h, const dpenv_controller_label_qp_io* io, dpenv_stream s);
 
 /* ---- The PPO update: actor and critic gradients and a device-gated Adam step --------------------------------------------------------
  * Handle-free like dpenv_gae / dpenv_adv_*: device pointers and a stream; no call allocates or synchronises, so a whole update (80

@@ -107,6 +107,12 @@ class ControllerLabelIO(C.Structure):
                 ('z_in', C.c_void_p), ('z_out', C.c_void_p), ('act', C.c_void_p)]
 
 
+class ControllerLabelQpIO(C.Structure):
+    _fields_ = [('struct_size', C.c_uint32), ('T', C.c_int32), ('obs', C.c_void_p), ('obs_dtype', C.c_int32), ('done', C.c_void_p),
+                ('z_in', C.c_void_p), ('z_out', C.c_void_p), ('x_in', C.c_void_p), ('x_out', C.c_void_p), ('act', C.c_void_p),
+                ('cost', C.c_void_p), ('q', C.POINTER(QPAllocator))]
+
+
 class ScoreIO(C.Structure):
     _fields_ = [('struct_size', C.c_uint32), ('T', C.c_int32), ('n', C.c_int32), ('obs', C.c_void_p), ('act', C.c_void_p),
                 ('rew', C.c_void_p), ('done', C.c_void_p), ('integ', C.c_void_p), ('obs_dtype', C.c_int32), ('obs_stride', C.c_int32),
@@ -200,6 +206,7 @@ SYMBOLS = {
     'dpenv_set_qp_allocator': (C.c_int, [_VP, C.POINTER(QPAllocator), _VP]),
     'dpenv_get_qp_allocator_state': (C.c_int, [_VP, _VP, _VP]),
     'dpenv_set_qp_allocator_state': (C.c_int, [_VP, _VP, _VP]),
+    'dpenv_controller_label_qp': (C.c_int, [_VP, C.POINTER(ControllerLabelQpIO), _VP]),
     'dpenv_train_param_count': (C.c_int64, [C.POINTER(TrainShape)]),
     'dpenv_train_workspace_bytes': (C.c_int, [C.POINTER(TrainShape), _I32, C.POINTER(C.c_int64)]),
     'dpenv_ppo_actor_grad': (C.c_int, [C.POINTER(TrainShape), _VP, _VP, _VP, _VP, _VP, _VP, _I32, _I32, _F, _VP, _VP, _VP, _I64, _VP]),

@@ -1299,6 +1299,36 @@ extern "C" int dpenv_controller_label(dpenv_handle h, const dpenv_controller_lab
     return DPENV_OK;
 }
 
+// ... with the QP allocation behind the PID lines: io->q's numbers, or the ones dpenv_set_qp_allocator has in force.  The handle's hull
+// kind does not matter (no hull is touched), and neither its z nor its QP thruster state is read or written.
+extern "C" int dpenv_controller_label_qp(dpenv_handle h, const dpenv_controller_label_qp_io* io, dpenv_stream s)
+{
+    if (!h) return DPENV_EINVAL;
+    DeviceGuard dev_guard(h->device);
+    if (!h->ctrl_on) return fail(h, DPENV_EINVAL, "dpenv_controller_label_qp: the DP controller is off (dpenv_set_dp_controller)");
+    if (!io || io->struct_size != sizeof(dpenv_controller_label_qp_io)) return fail(h, DPENV_EINVAL, "dpenv_controller_label_qp_io ABI mismatch");
+    if (io->T <= 0) return fail(h, DPENV_EINVAL, "dpenv_controller_label_qp: T > 0 is required");
+    if (!io->obs || !io->act) return fail(h, DPENV_EINVAL, "dpenv_controller_label_qp: the obs and act blocks are required");
+    if (io->obs_dtype != DPENV_F32 && io->obs_dtype != DPENV_BF16)
+        return fail(h, DPENV_EINVAL, "dpenv_controller_label_qp: obs_dtype must be DPENV_F32 or DPENV_BF16");
+    QpArgs g = {};
+    if (io->q) {
+        if (const char* why = qp_check(io->q, h->ctrl.dt, g)) return fail(h, DPENV_EINVAL, "%s", why);
+    } else if (h->qp_on) {
+        g = h->qp.q;
+    } else {
+        return fail(h, DPENV_EINVAL, "dpenv_controller_label_qp: no QP allocator (pass q, or dpenv_set_qp_allocator first)");
+    }
+    LabelQpArgs la = {};
+    la.obs = io->obs; la.done = io->done; la.z_in = io->z_in; la.z_out = io->z_out; la.x_in = io->x_in; la.x_out = io->x_out;
+    la.act = io->act; la.cost = io->cost;
+    la.T = io->T; la.n = h->cfg.n_envs;
+    const hipError_t e = dev::launch_controller_label_qp(&h->ctrl, &g, &la, h->ctrl_tab_on ? h->ctrl_tab : nullptr, io->obs_dtype == DPENV_BF16,
+                                                         (hipStream_t)s);
+    if (e != hipSuccess) return fail(h, DPENV_EHIP, "QP label launch failed: %s", hipGetErrorString(e));
+    return DPENV_OK;
+}
+
 extern "C" int dpenv_get_state(dpenv_handle h, float* state_out, int32_t* counters_out, dpenv_stream s)
 {
     if (!h) return DPENV_EINVAL;

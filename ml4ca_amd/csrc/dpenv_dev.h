@@ -423,6 +423,19 @@ struct LabelArgs {
     float* act;                 // [T][n][7]
     int T, n;
 };
+// the same scan with the rate-limited QP allocation behind the PID lines (dpenv_controller_label_qp): the thruster state x travels beside
+// z.  The QP's numbers travel as QpArgs, the PID's as ControlArgs (G and the thrust constants are not read) or as the packed table.
+struct LabelQpArgs {
+    const void* obs;            // [T][n][9] f32 or bf16, columns 0..5 read
+    const uint8_t* done;        // [T][n] or NULL
+    const float* z_in;          // [3][n] or NULL = 0
+    float* z_out;               // [3][n] or NULL; may be z_in
+    const float* x_in;          // [5][n] (QpRollout.state's layout) or NULL = 0
+    float* x_out;               // [5][n] or NULL; may be x_in
+    float* act;                 // [T][n][7]
+    float* cost;                // [T][n] the final objective of each row's solve, or NULL
+    int T, n;
+};
 
 // ---- launchers: called by the host units (dpenv_api.hip, dpenv_api_free.hip), defined by the translation unit that owns the kernels; not exported from libdpenv.so ----
 namespace __attribute__((visibility("hidden"))) dev {
@@ -482,6 +495,8 @@ hipError_t launch_thrust_alloc(const ControlArgs* ca, const float* tau, float* a
 // dpenv_label.hip: the law scanned over the T rows of a block, one lane per env (tab as launch_controller_rollout's; obs_bf16: the obs rows
 // are bf16); reads ca's numbers and dt only
 hipError_t launch_controller_label(const ControlArgs* ca, const LabelArgs* la, const float4* tab, int obs_bf16, hipStream_t s);
+// ... with the QP allocation of qa in place of the pseudo-inverse; of ca (or tab) the PID's numbers and dt only
+hipError_t launch_controller_label_qp(const ControlArgs* ca, const QpArgs* qa, const LabelQpArgs* la, const float4* tab, int obs_bf16, hipStream_t s);
 // dpenv_control.hip: one control step of the QP allocation for n envs, one lane per env
 hipError_t launch_qp_alloc(const QpArgs* qa, const QpAllocIO* io, hipStream_t s);
 // the zeroing of the closed loop's QP thruster state for the envs of mask (NULL = every env)

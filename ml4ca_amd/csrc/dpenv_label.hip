@@ -9,11 +9,17 @@
 // second instantiation of a shared template does to its neighbours' schedules).  Not merged into dpenv_control.hip: that re-schedules
 // the QP closed loop (all four controller_rollout_qp_kernel instantiations).  Per env-row 36 B of observation (18 B as bf16) and a
 // done byte come in, 28 B of action go out; the handle's state is neither read nor written.
+//
+// Two scans: controller_label_kernel allocates the PID's wrench with the pseudo-inverse (dp_control), controller_label_qp_kernel with the
+// rate-limited QP law of dpenv_qp_law.h (dpenv_controller_label_qp), whose thruster state travels beside z and whose objective can go
+// out beside the action (4 B per env-row).  The first is bound by its row traffic, the second by VALU issue.
 #include "dpenv_env_dev.h"
 
 namespace dpenv {
 
 #include "dpenv_control_law.h"
+// the QP allocation the second scan (controller_label_qp_kernel) puts behind the PID lines
+#include "dpenv_qp_law.h"
 // control_store_rows: a wave's 64 action rows staged through the wave-private LDS area, stored coalesced
 #include "dpenv_control_rows.h"
 
@@ -102,6 +108,84 @@ __global__ __launch_bounds__(64) void controller_label_kernel(const ControlArgs 
     }
 }
 
+// The same scan with the rate-limited QP allocation behind the PID lines (dpenv_controller_label_qp): per row the closed loop's QP branch
+// (dpenv_control_rollout_body.inc) - dp_wrench on the env's z, qp_allocate on its thruster state x - and both zeroed behind a done row.
+// z[3] and x[5] come in with the opening burst and go out once at the end.  About 620 VALU instructions per LM iteration stand against 7
+// loads per row, so the fetch is one row ahead and no deeper: row t + 1 is in flight under the solve of row t.  The iteration count is
+// a kernel argument, the loop wave-uniform; dead lanes solve env n - 1's rows again and store nothing.
+template <bool TAB, bool BF16>
+__global__ __launch_bounds__(64) void controller_label_qp_kernel(const ControlArgs ca, const QpArgs qa, const LabelQpArgs la,
+                                                                  const float4* __restrict__ tab)
+{
+    constexpr int A = 7, OD = 9;
+    __shared__ float lds_row[64 * A];
+
+    const int n = la.n, T = la.T;
+    const int lane = threadIdx.x;
+    const int wave0 = blockIdx.x * 64;
+    const int i = wave0 + lane;
+    const bool live = i < n;
+    const int il = live ? i : n - 1;
+
+    ControlLane cl;
+    if constexpr (TAB) load_control_lane(tab, il, ca.dt, cl);
+    float z[3] = {0.0f, 0.0f, 0.0f};
+    if (la.z_in) {
+        z[0] = la.z_in[il]; z[1] = la.z_in[(int64_t)n + il]; z[2] = la.z_in[2 * (int64_t)n + il];
+    }
+    float x[5] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+    if (la.x_in) {
+#pragma unroll
+        for (int k = 0; k < 5; ++k) x[k] = la.x_in[(int64_t)k * n + il];
+    }
+
+    const int64_t stride_a = (int64_t)n * A;
+    const int64_t w_a = (int64_t)wave0 * A;                      // the wave's slice of the [T][n][7] block
+    const int64_t rem_a = stride_a - w_a;
+
+    auto load = [&](LabelRow& row, int t) {
+        t = t < T ? t : T - 1;                                   // past the end: re-read the last row (never consumed)
+        const int64_t k = (int64_t)t * n + il;
+        if (BF16) {
+            const uint16_t* p = (const uint16_t*)la.obs + k * OD;
+#pragma unroll
+            for (int c = 0; c < 6; ++c) row.o[c] = __uint_as_float((uint32_t)p[c] << 16);
+        } else {
+            const float* p = (const float*)la.obs + k * OD;
+#pragma unroll
+            for (int c = 0; c < 6; ++c) row.o[c] = p[c];
+        }
+        row.d = la.done ? (uint32_t)la.done[k] : 0u;
+    };
+    LabelRow cur, nxt;
+    load(cur, 0);
+    for (int t = 0; t < T; ++t) {
+        load(nxt, t + 1);
+        float o[OD], tau[3], act[A], J;
+#pragma unroll
+        for (int c = 0; c < 6; ++c) o[c] = cur.o[c];
+        o[6] = o[7] = o[8] = 0.0f;                               // the thrust columns: the law does not read them
+        if constexpr (TAB) dp_wrench(cl, o, z, tau);
+        else dp_wrench(ca, o, z, tau);
+        qp_allocate(qa, tau, x, act, J);
+        control_store_rows<A>(lds_row, la.act, (int64_t)t * stride_a + w_a, rem_a, act, lane, false);
+        if (live && la.cost) (la.cost + (int64_t)t * n)[(unsigned)i] = J;
+        if (cur.d != 0u) {                                       // the next row is a new episode's first: thrusters at rest
+            z[0] = z[1] = z[2] = 0.0f;
+#pragma unroll
+            for (int k = 0; k < 5; ++k) x[k] = 0.0f;
+        }
+        cur = nxt;
+    }
+    if (live && la.z_out) {
+        la.z_out[i] = z[0]; la.z_out[(int64_t)n + i] = z[1]; la.z_out[2 * (int64_t)n + i] = z[2];
+    }
+    if (live && la.x_out) {
+#pragma unroll
+        for (int k = 0; k < 5; ++k) la.x_out[(int64_t)k * n + i] = x[k];
+    }
+}
+
 }  // namespace
 }  // namespace dpenv
 
@@ -117,6 +201,21 @@ hipError_t dev::launch_controller_label(const ControlArgs* ca, const LabelArgs* 
     } else {
         if (obs_bf16) hipLaunchKernelGGL((controller_label_kernel<false, true>), grid, block, 0, s, *ca, *la, tab);
         else hipLaunchKernelGGL((controller_label_kernel<false, false>), grid, block, 0, s, *ca, *la, tab);
+    }
+    return hipGetLastError();
+}
+
+hipError_t dev::launch_controller_label_qp(const ControlArgs* ca, const QpArgs* qa, const LabelQpArgs* la, const float4* tab, int obs_bf16,
+                                           hipStream_t s)
+{
+    if (la->n <= 0 || la->T <= 0 || !la->obs || !la->act || qa->iters < 1 || qa->iters > QP_MAX_ITERS) return hipErrorInvalidValue;
+    const dim3 grid((la->n + 63) / 64), block(64);
+    if (tab) {
+        if (obs_bf16) hipLaunchKernelGGL((controller_label_qp_kernel<true, true>), grid, block, 0, s, *ca, *qa, *la, tab);
+        else hipLaunchKernelGGL((controller_label_qp_kernel<true, false>), grid, block, 0, s, *ca, *qa, *la, tab);
+    } else {
+        if (obs_bf16) hipLaunchKernelGGL((controller_label_qp_kernel<false, true>), grid, block, 0, s, *ca, *qa, *la, tab);
+        else hipLaunchKernelGGL((controller_label_qp_kernel<false, false>), grid, block, 0, s, *ca, *qa, *la, tab);
     }
     return hipGetLastError();
 }

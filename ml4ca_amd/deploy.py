@@ -715,6 +715,45 @@ class BatchedQPAllocator(object):
             self.x[mask] = 0
 
 
+def label_rows_qp(params_or_table, qp_params, obs, done=None, z=None, x=None, dt=0.2, dtype=None):
+    """The PID + rate-limited QP chain's actions on a block of observation rows some other flight wrote - the host statement of
+    dpenv_controller_label_qp (policy.controller_label_qp), NumPy on the CPU.  obs, done and z as label_rows takes them; x [5, n] the
+    thruster state each env starts from (get_qp_allocator_state's layout) or None = 0.  Per row t, in this order:
+        tau = ctrl.wrench(obs[t]);  act[t] = qp.allocate(tau);  ctrl.reset(done[t] != 0);  qp.reset(done[t] != 0)
+    - z is advanced before the wrench, x by the allocation, and both are zeroed BEHIND a done row.  params_or_table: the dict of
+    dp_controller_defaults (None = the defaults) or a public table [32, n]; qp_params: the dict of qp_allocator_defaults (None = the
+    defaults); dt the control period.  Returns (act [T, n, 7], z [3, n], x [5, n]) in dtype (None = float32: the kernel's arithmetic
+    except for its own sin / cos polynomial, as BatchedQPAllocator says; float64 is the form for checks); labelling rows [0:k] and [k:T]
+    with z and x handed over equals one call."""
+    obs = np.asarray(obs)
+    if obs.ndim != 3 or obs.shape[2] < 6:
+        raise ValueError('label_rows_qp: obs is [T, n, >= 6]')
+    T, n = obs.shape[0], obs.shape[1]
+    if done is not None:
+        done = np.asarray(done)
+        if done.shape != (T, n):
+            raise ValueError('label_rows_qp: done is [T, n]')
+    ctrl = BatchedDPController(n, params_or_table, dt=dt, dtype=dtype)
+    qp = BatchedQPAllocator(n, qp_params, dt=dt, dtype=dtype)
+    if z is not None:
+        z = np.asarray(z)
+        if z.shape != (3, n):
+            raise ValueError('label_rows_qp: z is [3, n]')
+        ctrl.z = np.ascontiguousarray(z.T).astype(ctrl.dtype)
+    if x is not None:
+        x = np.asarray(x)
+        if x.shape != (5, n):
+            raise ValueError('label_rows_qp: x is [5, n]')
+        qp.x = np.ascontiguousarray(x.T).astype(qp.dtype)
+    act = np.empty((T, n, 7), ctrl.dtype)
+    for t in range(T):
+        act[t] = qp.allocate(ctrl.wrench(obs[t]))
+        if done is not None:
+            ctrl.reset(done[t] != 0)
+            qp.reset(done[t] != 0)
+    return act, np.ascontiguousarray(np.asarray(ctrl.z).T), np.ascontiguousarray(np.asarray(qp.x).T)
+
+
 class RLAllocatorNode(object):
     """The node's callbacks as plain methods (rl_allocator.py:168-220).  `actor(state[9]) -> action[act_dim]` is any
     callable: ActorCritic.forward_ref on the CPU, or policy_forward on the GPU for one env."""

@@ -384,6 +384,55 @@ def qp_allocator_struct(params=None):
     return q
 
 
+def controller_label_qp(env, obs, done=None, z=None, x=None, params=None, out=None, cost=False):
+    """The PID + rate-limited QP chain's actions on a block of rows some OTHER flight wrote (dpenv_controller_label_qp), in one launch:
+    controller_label with the QP law in place of the pseudo-inverse - the low-energy expert's labels for the states an actor visited.
+    obs [T, n, 9] float32 or bfloat16, done [T, n] uint8 or None, z [3, n] float32 or None = 0 as controller_label takes them; x [5, n]
+    float32, the thruster state every env starts from (get_qp_allocator_state's layout), or None = 0.  Per row: the PID lines of
+    env.set_dp_controller (row i of the table while one is in force) on obs[t] with z advanced first, the QP law on that wrench with
+    x advanced, both zeroed behind a done row.  params: the dict of deploy.qp_allocator_defaults; None = the numbers
+    env.set_qp_allocator has in force (an error if none is set).  The env's hull kind does not matter: an env with per-env hulls or a
+    controller table, which cannot fly the QP, labels with explicit params.  Returns (act [T, n, 7], z [3, n], x [5, n]) and, with
+    cost=True, the final objective of every row's solve [T, n] as a fourth value; out = (act, z, x) supplies the buffers (z and x may
+    be the input tensors themselves).  Nothing of the env changes: not its state, not its own z or thruster state, not a counter.  For
+    float32 rows of controller_rollout with the QP set and auto-reset on the labels are that launch's act rows bit for bit.
+    deploy.label_rows_qp is the host statement."""
+    torch = _torch()
+    n, ad = env.n_envs, env.num_actions
+    dev, f32 = env.device, torch.float32
+    if not isinstance(obs, torch.Tensor) or obs.dim() != 3:
+        raise ValueError('controller_label_qp: obs is a tensor [T, n, 9]')
+    if obs.dtype not in (torch.float32, torch.bfloat16):
+        raise ValueError('controller_label_qp: obs rows are float32 or bfloat16, not %s' % (obs.dtype,))
+    T = int(obs.shape[0])
+    env._chk(obs, (T, n, 9), obs.dtype, 'obs')
+    env._chk(done, (T, n), torch.uint8, 'done')
+    env._chk(z, (3, n), f32, 'z')
+    env._chk(x, (5, n), f32, 'x')
+    if out is None:
+        out = (torch.empty((T, n, ad), dtype=f32, device=dev), torch.empty((3, n), dtype=f32, device=dev),
+               torch.empty((5, n), dtype=f32, device=dev))
+    act, z_out, x_out = out
+    env._chk(act, (T, n, 7), f32, 'out[0]')
+    env._chk(z_out, (3, n), f32, 'out[1]')
+    env._chk(x_out, (5, n), f32, 'out[2]')
+    J = torch.empty((T, n), dtype=f32, device=dev) if cost else None
+    q = qp_allocator_struct(params) if params is not None else None
+    io = _lib.ControllerLabelQpIO()
+    io.struct_size = C.sizeof(_lib.ControllerLabelQpIO)
+    io.T = T
+    io.obs = obs.data_ptr()
+    io.obs_dtype = 1 if obs.dtype == torch.bfloat16 else 0
+    io.done = done.data_ptr() if done is not None else None
+    io.z_in = z.data_ptr() if z is not None else None
+    io.x_in = x.data_ptr() if x is not None else None
+    io.z_out, io.x_out, io.act = z_out.data_ptr(), x_out.data_ptr(), act.data_ptr()
+    io.cost = J.data_ptr() if cost else None
+    io.q = C.pointer(q) if q is not None else None
+    _lib.check(env.lib.dpenv_controller_label_qp(env._h, C.byref(io), env._stream()), env._h)
+    return (act, z_out, x_out, J) if cost else (act, z_out, x_out)
+
+
 def thrust_alloc_qp(tau, state=None, params=None, dt=0.2, out=None, cost=False):
     """One control step of the rate-limited QP thrust allocation on the device (dpenv_thrust_alloc_qp), one lane per env: tau float32
     [3, n] = Fx, Fy, Mz and the thruster state in force, state float32 [5, n] = F_bow, F_port, F_star, a_port, a_star (None = zeros), ->

@@ -435,7 +435,7 @@ class PPOUpdater(object):
 
     # ---- DAgger: expert labels on the states the ACTOR visits, aggregated over rounds (Ross et al. 2011) ----
     def dagger(self, env, rounds, T, iters, minibatch=None, loss='mse', keep=None, sample=False, reset_at_end=False, lr=None, average=None,
-               upload=None):
+               upload=None, expert='pinv', qp_params=None):
         """`rounds` x (fly the actor, label its states with the baseline DP controller, aggregate, refit).  env: a float32-row env with
         the baseline on (env.set_dp_controller; a table of set_dp_controller_table in force is the one that labels).  Per round:
           1. ac.upload(env, **upload)                       (upload: keyword arguments of ActorCritic.upload, e.g. dict(precision='f32'))
@@ -453,13 +453,21 @@ class PPOUpdater(object):
         rounds and is left as it is; the caller uploads the final actor where it wants it flown.
         A memoryless actor cannot represent ki * z: the labels depend on the integral, the actor sees o alone.  A caller who wants a target
         the actor can represent labels with a ki = 0 controller or table.
+        expert: 'pinv' (the PID + pseudo-inverse law, as above) or 'qp': step 3 is policy.controller_label_qp, the same PID with the
+        rate-limited QP allocation - the low-energy contender.  Its thruster state x is carried beside z: along each env's rows, from round
+        to round, zeroed with z.  The QP's numbers are qp_params (the dict of deploy.qp_allocator_defaults), else the ones
+        env.set_qp_allocator has in force, else the defaults of the DEFAULT hull, as evaluate.baseline_box_test takes them.  The env need
+        not be able to fly the QP: per-env hulls (randomised ones too) and a controller table label like any other.  x is the expert's own
+        recursion, not the thruster state the actor's actions would have left.
         Not here: beta-mixed flights in which the expert executes some of the steps, an integral-augmented actor, bf16 rows (the gradient
         kernels take float32 rows: a bf16 env raises ValueError)."""
         torch = _torch()
-        from .policy import controller_label, policy_rollout
+        from .policy import controller_label, controller_label_qp, policy_rollout
         rounds, T, iters = int(rounds), int(T), int(iters)
         if rounds < 1 or T < 1 or iters < 1:
             raise ValueError('dagger: rounds, T and iters are >= 1')
+        if expert not in ('pinv', 'qp'):
+            raise ValueError("dagger: expert is 'pinv' or 'qp', not %r" % (expert,))
         if env.obs_torch_dtype != torch.float32:
             raise ValueError('dagger: the gradient kernels take float32 rows; make the env with float32 obs rows (got %s)' % (env.obs_torch_dtype,))
         if env.dp_controller is None:
@@ -475,6 +483,10 @@ class PPOUpdater(object):
         data_act = torch.empty((keep * R, ad), dtype=f32, device=dev)
         self.dagger_data = dict(obs=data_obs, act=data_act, filled=0, T=T, n=n, keep=keep)
         z = torch.zeros((3, n), dtype=f32, device=dev)
+        if expert == 'qp':
+            from .deploy import qp_allocator_defaults
+            x = torch.zeros((5, n), dtype=f32, device=dev)
+            qp = qp_params if qp_params is not None else env.qp_allocator if env.qp_allocator is not None else qp_allocator_defaults()
         flight = torch.zeros((rounds, 2), dtype=torch.float64, device=dev)
         out, records = None, []
         for r in range(rounds):
@@ -482,7 +494,12 @@ class PPOUpdater(object):
             out = policy_rollout(env, T, out=out, sample=sample, reset_at_end=reset_at_end)
             slot = r % keep
             labels = data_act[slot * R:(slot + 1) * R].view(T, n, ad)
-            controller_label(env, out['obs'], out['done'], z=z, out=(labels, z))
+            if expert == 'qp':
+                controller_label_qp(env, out['obs'], out['done'], z=z, x=x, params=qp, out=(labels, z, x))
+                if reset_at_end:
+                    x.zero_()
+            else:
+                controller_label(env, out['obs'], out['done'], z=z, out=(labels, z))
             if reset_at_end:
                 z.zero_()
             data_obs[slot * R:(slot + 1) * R].copy_(out['obs'].view(R, od))

@@ -154,6 +154,33 @@ def tune_baseline(ac, dev, preset, precision, K, seed=0, out=print, directions=1
     return {'mean_iae': iae.tolist(), 'mean_work': work.tolist(), 'front': [int(k) for k in sw['front']], 'actor': {'IAE': a_iae, 'work': a_work.tolist()}}
 
 
+def tune_qp(dev, preset, K, seed=0, out=print, directions=16, vc=0.2):
+    """The QP allocator's trade-off curve beside tune_baseline's (evaluate.qp_weight_sweep): K weight sets around the reference's weights
+    (deploy.qp_weight_population; set 0 is the default QP) x 16 current directions in ONE scored box test behind the reference filter,
+    every env on its own row of the per-env QP table, the PID the hull's default controller."""
+    from ml4ca_amd import evaluate as EV
+    from ml4ca_amd.deploy import dp_controller_defaults, qp_allocator_defaults, qp_weight_population
+    nominal = ml4ca_amd.default_vessel(preset)
+    n = K * directions
+    env = ml4ca_amd.BatchedRevoltEnv(n, device=dev, terminate=False, time_limit=False, seed=seed + 77, vessel_params=nominal, current=True)
+    pop = qp_weight_population(K, qp_allocator_defaults(nominal), seed=seed)
+    env.set_dp_controller(dp_controller_defaults(nominal))
+    sw = EV.qp_weight_sweep(env, pop, directions=directions, vc=vc, reference_filter=True)
+    iae, work = sw['mean_iae'].cpu().numpy(), sw['mean_work'].cpu().numpy()
+    tot = work.sum(1)
+    names = ('w_power', 'w_dalpha', 'w_dforce')
+    row = lambda k: 'set %4d  IAE %.2f  work bow/port/star %s (total %.1f)  %s' % (
+        k, iae[k], [round(float(x), 1) for x in work[k]], tot[k], '  '.join('%s x %.2f' % (g, float(pop['factors'][g][k])) for g in names))
+    out('tuneqp  %d QP weight sets x %d directions of %.1f m/s, 1250-step box test behind the reference filter' % (K, directions, vc))
+    out('tuneqp  default QP       : ' + row(0))
+    out('tuneqp  front (%d of %d sets, by IAE):' % (len(sw['front']), K))
+    for k in sw['front']:
+        out('tuneqp      ' + row(int(k)))
+    out('tuneqp  lowest IAE       : ' + row(int(iae.argmin())))
+    out('tuneqp  least work       : ' + row(int(tot.argmin())))
+    return {'mean_iae': iae.tolist(), 'mean_work': work.tolist(), 'front': [int(k) for k in sw['front']]}
+
+
 def warm_start(upd, env, args, out=print):
     """--warm-start: clone the classical baseline into the actor before epoch 0.  The baseline (PID + pseudo-inverse with the pole-placement
     defaults of the nominal hull) flies the training envs for --warm-start-steps steps in one launch; its obs / act rows are the
@@ -309,6 +336,8 @@ def main():
     ap.add_argument('--eval', action='store_true', help='after training: run_RL_policy + the box test (IAE, energy) on the nominal hull and on spreads of hulls')
     ap.add_argument('--tune-baseline', type=int, default=0, metavar='K', help='with --eval: a scored sweep of K baseline gain sets x 16 current directions in one '
                     'flight (per-env controller table): the default baseline, the IAE / work front, the best set, and the best at no more than the actor\'s work')
+    ap.add_argument('--tune-qp', type=int, default=0, metavar='K', help='with --eval: a scored sweep of K QP weight sets (w_power, w_dalpha, w_dforce) x 16 current '
+                    'directions in one flight (per-env QP table): the default QP and its IAE / work front, to read beside --tune-baseline\'s')
     ap.add_argument('--eval-envs', type=int, default=1024, help='envs per --eval box test; 1024 (the default) scores the resident rows as before, any other '
                                                                 'value flies the test in 50-step launches scored on the device (evaluate.ScoreCard), e.g. 65536')
     ap.add_argument('--eval-presets', default='', help="comma-separated presets to run --eval on (default: the training preset), e.g. 'no_loss,thrust_loss': "
@@ -446,6 +475,8 @@ def main():
                 evaluate_actor(ac, dev, pz, 'f32', args.seed, eval_envs=args.eval_envs)
                 if args.tune_baseline > 0:
                     tune_baseline(ac, dev, pz, 'f32', args.tune_baseline, seed=args.seed)
+                if args.tune_qp > 0:
+                    tune_qp(dev, pz, args.tune_qp, seed=args.seed)
     if world > 1:
         torch.distributed.destroy_process_group()
 

@@ -864,6 +864,50 @@ int dpenv_set_qp_allocator(dpenv_handle h, const dpenv_qp_allocator* q, dpenv_st
  * while no QP allocator is set. */
 int dpenv_get_qp_allocator_state(dpenv_handle h, float* state_out, dpenv_stream s);
 int dpenv_set_qp_allocator_state(dpenv_handle h, const float* state_in, dpenv_stream s);
+/* One QP allocator PER ENV (additive to ABI 6): the tool that turns the QP's one point on the tracking-error / energy plane into a curve -
+ * K weight sets x D current directions in ONE flight (ml4ca_amd.evaluate.qp_weight_sweep), as dpenv_set_dp_controller_table does for the
+ * pseudo-inverse baseline.  The table is a DEVICE float[DPENV_QP_NPARAM][n_envs], laid out like the controller table - row p = slot p of
+ * every env - and owned by the caller.  Slots, in the order of dpenv_qp_allocator's fields and with its conditions: */
+#define DPENV_QP_NPARAM 32
+#define DPENV_QP_WSLACK 0     /* 0-2  w_slack, finite and >= 0 */
+#define DPENV_QP_WPOWER 3     /* w_power, finite and >= 0 */
+#define DPENV_QP_WDALPHA 4    /* w_dalpha, finite and > 0 */
+#define DPENV_QP_WDFORCE 5    /* w_dforce, finite and > 0 */
+#define DPENV_QP_FMAX 6       /* 6-8  f_max: bow, port, star, finite and >= 0 */
+#define DPENV_QP_FRATE 9      /* 9-11 force_rate [N/s], finite and >= 0 */
+#define DPENV_QP_ARATE 12     /* 12-13 azimuth_rate [rad/s]: port, star, finite and >= 0 */
+#define DPENV_QP_LX 14        /* 14-16 lever arms lx: bow, port, star, finite */
+#define DPENV_QP_LY 17        /* 17-19 lever arms ly: bow (not used), port, star, finite */
+#define DPENV_QP_KF 20        /* 20-22 thrust constants ahead, finite and > 0 */
+#define DPENV_QP_KR 23        /* 23-25 thrust constants astern, finite and > 0 */
+                              /* 26-31 reserved, not read */
+/* The iteration count is NOT in the table: it is one number per call (1..32), so the solver's loop stays uniform across a wave.
+ * dpenv_set_qp_allocator_table is dpenv_set_qp_allocator with row i flown on env i: the same preconditions and refusals with the same
+ * messages (the DP controller on, no per-env hull blocks, no controller table in force, iterations in 1..32), the same law, the same
+ * zeroing of every env's thruster state by a valid call.  A packing kernel, one lane per env, copies the table into a library-owned block
+ * (allocated by the first call, released with the handle; 112 B per env) - the caller's buffer is free after the call, on the stream - and
+ * forms dF = force_rate * dt and da = azimuth_rate * dt as one f32 product each with the handle's dt: exactly what the host forms for the
+ * scalar call, so a table of equal rows flies the scalar call's rows bit for bit.  Later calls are stream-ordered without allocation and
+ * graph-capturable; a captured launch flies whatever the last packing wrote.
+ * Refused rows: dpenv_thrust_alloc_qp's checks, row by row (a number that is not finite, a weight < 0, w_dalpha or w_dforce <= 0, a bound
+ * or rate < 0, kf or kr <= 0, a dF or da that is not finite).  A refused row is packed as the REST ALLOCATOR - f_max = force_rate =
+ * azimuth_rate = 0, w_slack = w_power = 0, w_dalpha = w_dforce = 1, lx = ly = 0, kf = kr = 1 - with which the law commands zero thrust
+ * and holds the azimuths, every output finite (from forces at rest, which is the law's precondition |F^-| <= f_max with f_max = 0: a
+ * valid call leaves every env there); the other rows are not affected.  refused_out: NULL, or a device uint8[n_envs] that gets 1
+ * for a refused env and 0 for the others.  The library reads nothing back and does not synchronise.
+ * table = NULL returns to the scalar numbers dpenv_set_qp_allocator last set, or to the pseudo-inverse if none were set, and leaves z and
+ * the thruster state alone (as dpenv_set_dp_controller_table(NULL) leaves z).  dpenv_set_qp_allocator(h, q) replaces the table by scalar
+ * numbers (q = NULL: the pseudo-inverse again, nothing to return to); dpenv_set_dp_controller drops both; dpenv_set_dp_controller_table is
+ * refused while a table is set, as it is while a scalar QP is set.  dpenv_get / dpenv_set_qp_allocator_state work unchanged.
+ * dpenv_controller_label_qp with q = NULL is refused while a TABLE is in force (the scan takes one set of numbers: pass q). */
+int dpenv_set_qp_allocator_table(dpenv_handle h, const float* table, int32_t iterations, uint8_t* refused_out, dpenv_stream s);
+/* dpenv_thrust_alloc_qp with row i of the PUBLIC table (device float[DPENV_QP_NPARAM][n]) on env i; the other arguments are that call's.
+ * There is no packing launch: each lane reads its 26 numbers and checks them itself, with the device function the packing kernel uses, so
+ * the two never disagree.  A refused lane runs the rest allocator above, reports NaN in cost_out and sets its byte of refused_out (device
+ * uint8[n] or NULL; 0 for the others).  DPENV_EINVAL before anything is launched: NULL table, tau or action_out, n <= 0, iterations
+ * outside 1..32, dt not finite or <= 0.  Stream-ordered, no allocation, no host synchronisation: graph-capturable, one kernel node. */
+int dpenv_thrust_alloc_qp_table(const float* table, int32_t iterations, float dt, const float* tau, const float* state_in,
+                                float* state_out, float* action_out, float* cost_out, uint8_t* refused_out, int32_t n, dpenv_stream s);
 /* The PID + QP chain on rows some other flight wrote (additive to ABI 6): dpenv_controller_label's scan with the QP law in place of the
  * f_m / bow / stern lines - the low-energy expert's labels for the states an actor visited.  One launch, one lane per env; per row t and
  * env i, in the order of the closed loop with a QP set:

@@ -207,6 +207,8 @@ SYMBOLS = {
     'dpenv_get_qp_allocator_state': (C.c_int, [_VP, _VP, _VP]),
     'dpenv_set_qp_allocator_state': (C.c_int, [_VP, _VP, _VP]),
     'dpenv_controller_label_qp': (C.c_int, [_VP, C.POINTER(ControllerLabelQpIO), _VP]),
+    'dpenv_set_qp_allocator_table': (C.c_int, [_VP, _VP, _I32, _VP, _VP]),
+    'dpenv_thrust_alloc_qp_table': (C.c_int, [_VP, _I32, _F, _VP, _VP, _VP, _VP, _VP, _VP, _I32, _VP]),
     'dpenv_train_param_count': (C.c_int64, [C.POINTER(TrainShape)]),
     'dpenv_train_workspace_bytes': (C.c_int, [C.POINTER(TrainShape), _I32, C.POINTER(C.c_int64)]),
     'dpenv_ppo_actor_grad': (C.c_int, [C.POINTER(TrainShape), _VP, _VP, _VP, _VP, _VP, _VP, _I32, _I32, _F, _VP, _VP, _VP, _I64, _VP]),

@@ -82,7 +82,11 @@ struct dpenv_s {
     bool ctrl_tab_on = false;    // dpenv_set_dp_controller_table: env i flies row i of ctrl_tab instead of ctrl's numbers
     float4* ctrl_tab = nullptr;  // the packed per-env controller block (ctrl_tab_float4s(n) float4), allocated by the first dpenv_set_dp_controller_table
     bool qp_on = false;     // dpenv_set_qp_allocator: dpenv_controller_rollout allocates the PID's wrench with the QP law of `qp`
-    QpRollout qp = {};      // its numbers and per-env thruster state (float [5][n]), allocated by the first dpenv_set_qp_allocator
+    QpRollout qp = {};      // its numbers and per-env thruster state (float [5][n]), allocated by the first dpenv_set_qp_allocator[_table]
+    bool qp_scalar = false; // qp.q holds numbers dpenv_set_qp_allocator set: what dpenv_set_qp_allocator_table(NULL) returns to
+    bool qp_tab_on = false; // dpenv_set_qp_allocator_table (qp_on is set with it): env i flies row i of qp_tab, qp_tab_iters iterations
+    float4* qp_tab = nullptr;    // the packed per-env QP block (qp_tab_float4s(n) float4), allocated by the first dpenv_set_qp_allocator_table
+    int32_t qp_tab_iters = 0;
     int device = 0;
     std::string err;
 
@@ -99,6 +103,7 @@ struct dpenv_s {
         if (ctrl.z) (void)hipFree(ctrl.z);
         if (ctrl_tab) (void)hipFree(ctrl_tab);
         if (qp.state) (void)hipFree(qp.state);
+        if (qp_tab) (void)hipFree(qp_tab);
         for (int k = 0; k < 2; ++k) if (pol_read[k]) (void)hipEventDestroy(pol_read[k]);
         if (loss_ev) (void)hipEventDestroy(loss_ev);
         if (loss_host) (void)hipHostFree(loss_host);
@@ -1137,7 +1142,7 @@ extern "C" int dpenv_set_dp_controller(dpenv_handle h, const dpenv_dp_controller
     if (!c) {
         h->ctrl_on = false;
         h->ctrl_tab_on = false;
-        h->qp_on = false;
+        h->qp_on = h->qp_scalar = h->qp_tab_on = false;
         return DPENV_OK;
     }
     ControlArgs g = {};
@@ -1151,7 +1156,7 @@ extern "C" int dpenv_set_dp_controller(dpenv_handle h, const dpenv_dp_controller
     h->ctrl = g;
     h->ctrl_on = true;
     h->ctrl_tab_on = false;                                // the scalar law again: a table in force is dropped
-    h->qp_on = false;                                      // ... and so is a QP allocator: the pseudo-inverse allocates again
+    h->qp_on = h->qp_scalar = h->qp_tab_on = false;        // ... and so is a QP allocator, scalar or per-env: the pseudo-inverse allocates again
     return DPENV_OK;
 }
 
@@ -1228,8 +1233,11 @@ extern "C" int dpenv_controller_rollout(dpenv_handle h, const dpenv_controller_r
     const int ves = rollout_ves(vessel_source(h));
     // the handle may have changed since dpenv_set_qp_allocator
     if (h->qp_on && (h->ctrl_tab_on || (ves != VES_ARGS && ves != VES_ARGS_LOSS))) return fail(h, DPENV_EINVAL, "dpenv_controller_rollout: " QP_SET_MSG);
+    QpRollout qr = h->qp;
+    if (h->qp_tab_on) qr.q.iters = h->qp_tab_iters;         // (of q only iters is read while the table flies)
     const hipError_t e = dev::launch_controller_rollout(&a, &ca, h->reff_on ? &fa : nullptr, h->ctrl_tab_on ? h->ctrl_tab : nullptr,
-                                                        h->qp_on ? &h->qp : nullptr, ves, (hipStream_t)s);
+                                                        h->qp_on ? &qr : nullptr, h->qp_on && h->qp_tab_on ? h->qp_tab : nullptr, ves,
+                                                        (hipStream_t)s);
     if (e != hipSuccess) return fail(h, DPENV_EHIP, "controller launch failed: %s", hipGetErrorString(e));
     h->lag_valid = true;
     return DPENV_OK;
@@ -1240,7 +1248,7 @@ extern "C" int dpenv_set_qp_allocator(dpenv_handle h, const dpenv_qp_allocator* 
 {
     if (!h) return DPENV_EINVAL;
     if (!q) {
-        h->qp_on = false;
+        h->qp_on = h->qp_scalar = h->qp_tab_on = false;
         return DPENV_OK;
     }
     if (!h->ctrl_on) return fail(h, DPENV_EINVAL, "dpenv_set_qp_allocator: the DP controller is off (dpenv_set_dp_controller first)");
@@ -1256,7 +1264,46 @@ extern "C" int dpenv_set_qp_allocator(dpenv_handle h, const dpenv_qp_allocator* 
     }
     HIP_TRY(h, dev::launch_qp_state_clear(h->qp.state, nullptr, h->cfg.n_envs, (hipStream_t)s));   // (the block stays if this fails)
     h->qp.q = g;
-    h->qp_on = true;
+    h->qp_on = h->qp_scalar = true;
+    h->qp_tab_on = false;                                  // the scalar numbers replace a table in force
+    return DPENV_OK;
+}
+
+static_assert(QP_NPARAM == DPENV_QP_NPARAM && QP_WSLACK == DPENV_QP_WSLACK && QP_WPOWER == DPENV_QP_WPOWER && QP_WDALPHA == DPENV_QP_WDALPHA &&
+                  QP_WDFORCE == DPENV_QP_WDFORCE && QP_FMAX == DPENV_QP_FMAX && QP_FRATE == DPENV_QP_FRATE && QP_ARATE == DPENV_QP_ARATE &&
+                  QP_LX == DPENV_QP_LX && QP_LY == DPENV_QP_LY && QP_KF == DPENV_QP_KF && QP_KR == DPENV_QP_KR,
+              "the QP packing kernel's slots are the header's");
+
+// dpenv_set_qp_allocator with row i of the table on env i
+extern "C" int dpenv_set_qp_allocator_table(dpenv_handle h, const float* table, int32_t iterations, uint8_t* refused_out, dpenv_stream s)
+{
+    if (!h) return DPENV_EINVAL;
+    if (!table) {                                          // back to the scalar numbers last set, or to the pseudo-inverse; z and x stay
+        h->qp_tab_on = false;
+        h->qp_on = h->qp_scalar;
+        return DPENV_OK;
+    }
+    if (!h->ctrl_on) return fail(h, DPENV_EINVAL, "dpenv_set_qp_allocator_table: the DP controller is off (dpenv_set_dp_controller first)");
+    if (iterations < 1 || iterations > QP_MAX_ITERS) return fail(h, DPENV_EINVAL, "QP allocator: iterations must be in 1..32");
+    if (!std::isfinite(h->ctrl.dt) || !(h->ctrl.dt > 0.0f)) return fail(h, DPENV_EINVAL, "QP allocator: dt must be finite and > 0");
+    if (!control_config_ok(h)) return fail(h, DPENV_EINVAL, "dpenv_set_qp_allocator_table: " CONTROL_SET_MSG);
+    if (h->ctrl_tab_on || h->per_env) return fail(h, DPENV_EINVAL, "dpenv_set_qp_allocator_table: " QP_SET_MSG);
+    DeviceGuard dev_guard(h->device);
+    if (!h->qp.state) {
+        void* p = nullptr;
+        if (hipMalloc(&p, sizeof(float) * 5 * (size_t)h->cfg.n_envs) != hipSuccess) return fail(h, DPENV_ENOMEM, "hipMalloc of the QP allocator state failed");
+        h->qp.state = (float*)p;
+    }
+    if (!h->qp_tab) {                                      // (whole waves of 64 envs)
+        void* p = nullptr;
+        if (hipMalloc(&p, sizeof(float4) * (size_t)qp_tab_float4s(h->cfg.n_envs)) != hipSuccess)
+            return fail(h, DPENV_ENOMEM, "hipMalloc of the QP allocator table failed");
+        h->qp_tab = (float4*)p;
+    }
+    HIP_TRY(h, dev::launch_pack_qp_table(table, h->qp_tab, refused_out, h->ctrl.dt, h->cfg.n_envs, (hipStream_t)s));
+    HIP_TRY(h, dev::launch_qp_state_clear(h->qp.state, nullptr, h->cfg.n_envs, (hipStream_t)s));
+    h->qp_tab_iters = iterations;
+    h->qp_on = h->qp_tab_on = true;
     return DPENV_OK;
 }
 
@@ -1314,6 +1361,9 @@ extern "C" int dpenv_controller_label_qp(dpenv_handle h, const dpenv_controller_
     QpArgs g = {};
     if (io->q) {
         if (const char* why = qp_check(io->q, h->ctrl.dt, g)) return fail(h, DPENV_EINVAL, "%s", why);
+    } else if (h->qp_tab_on) {
+        return fail(h, DPENV_EINVAL, "dpenv_controller_label_qp: a per-env QP table (dpenv_set_qp_allocator_table) is in force and the scan "
+                                     "takes one set of numbers: pass q");
     } else if (h->qp_on) {
         g = h->qp.q;
     } else {

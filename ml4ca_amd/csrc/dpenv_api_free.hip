@@ -367,6 +367,19 @@ extern "C" int dpenv_thrust_alloc_qp(const dpenv_qp_allocator* q, float dt, cons
     return DPENV_OK;
 }
 
+// ... with row i of the public table on env i: the lane checks its own row (no packing launch, one kernel node)
+extern "C" int dpenv_thrust_alloc_qp_table(const float* table, int32_t iterations, float dt, const float* tau, const float* state_in,
+                                           float* state_out, float* action_out, float* cost_out, uint8_t* refused_out, int32_t n,
+                                           dpenv_stream s)
+{
+    if (!table || !tau || !action_out || n <= 0) return fail(nullptr, DPENV_EINVAL, "dpenv_thrust_alloc_qp_table: bad argument");
+    if (iterations < 1 || iterations > QP_MAX_ITERS) return fail(nullptr, DPENV_EINVAL, "QP allocator: iterations must be in 1..32");
+    if (!std::isfinite(dt) || !(dt > 0.0f)) return fail(nullptr, DPENV_EINVAL, "QP allocator: dt must be finite and > 0");
+    const QpAllocIO io = {tau, state_in, state_out, action_out, cost_out, n};
+    HIP_TRY(nullptr, dev::launch_qp_alloc_tab(table, iterations, dt, &io, refused_out, (hipStream_t)s));
+    return DPENV_OK;
+}
+
 extern "C" int dpenv_thrust_map(const float* params, const float* n_pct, const float* alpha, float* tau_out, int32_t n,
                                 dpenv_stream s)
 {

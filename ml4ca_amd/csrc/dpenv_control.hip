@@ -4,7 +4,9 @@
 // evaluated in registers inside a T-step launch.  One body, dpenv_control_rollout_body.inc, compiled with the weighted pseudo-inverse
 // on the shared numbers (controller_rollout_kernel), on every env's own row of the packed table (controller_rollout_tab_kernel), and
 // with the rate-limited QP allocation (controller_rollout_qp_kernel, dpenv_set_qp_allocator): the PID's lines form tau, qp_allocate
-// takes dp_allocate's place, the thruster state travels beside z.  Beside it the table's packing, the controller's state, and the two
+// takes dp_allocate's place, the thruster state travels beside z - and the same with every env's own QP numbers held per lane
+// (controller_rollout_qp_tab_kernel, dpenv_set_qp_allocator_table; pack_qp_table_kernel packs them, dpenv_thrust_alloc_qp_table is
+// the handle-free form).  Beside it the table's packing, the controller's state, and the two
 // allocations as handle-free maps tau -> action for n envs (dpenv_thrust_alloc, dpenv_thrust_alloc_qp: the thesis' third allocator
 // beside the RL actor and the PID + pseudo-inverse chain).  The handle-free QP call: per env 12 B of wrench and 20 B of thruster state
 // come in; 20 B of state, 28 B of action and (optionally) 4 B of objective go out; everything between is registers.
@@ -39,8 +41,9 @@ namespace dpenv {
 template <int VES, bool REFF>
 __global__ __launch_bounds__(RBLOCK) void controller_rollout_kernel(const StepArgs a, const ControlArgs ca, const FilterArgs fa)
 {
-    constexpr bool TAB = false, QP = false;
+    constexpr bool TAB = false, QP = false, QTAB = false;
     const float4* const tab = nullptr;
+    const float4* const qtab = nullptr;
     const QpRollout qr = {};
 #include "dpenv_control_rollout_body.inc"
 }
@@ -51,7 +54,8 @@ template <int VES, bool REFF>
 __global__ __launch_bounds__(RBLOCK) void controller_rollout_tab_kernel(const StepArgs a, const ControlArgs ca, const FilterArgs fa,
                                                                          const float4* __restrict__ tab)
 {
-    constexpr bool TAB = true, QP = false;
+    constexpr bool TAB = true, QP = false, QTAB = false;
+    const float4* const qtab = nullptr;
     const QpRollout qr = {};
 #include "dpenv_control_rollout_body.inc"
 }
@@ -177,9 +181,39 @@ template <int VES, bool REFF>
 __global__ __launch_bounds__(RBLOCK) void controller_rollout_qp_kernel(const StepArgs a, const ControlArgs ca, const FilterArgs fa,
                                                                         const QpRollout qr)
 {
-    constexpr bool TAB = false, QP = true;
+    constexpr bool TAB = false, QP = true, QTAB = false;
+    const float4* const tab = nullptr;
+    const float4* const qtab = nullptr;
+#include "dpenv_control_rollout_body.inc"
+}
+
+// QTAB: every env flies its own row of the packed QP block (dpenv_set_qp_allocator_table) - seven 16-byte loads per env and launch in the
+// opening burst, the numbers held in VGPRs for the launch, read only; of qr.q only iters is read (one count per launch: the iteration
+// loop stays wave-uniform).  The law, the rows and everything else are the kernel above.  A kernel of its own name, as
+// controller_rollout_tab_kernel is, so that the four scalar instantiations keep their symbols.
+template <int VES, bool REFF>
+__global__ __launch_bounds__(RBLOCK) void controller_rollout_qp_tab_kernel(const StepArgs a, const ControlArgs ca, const FilterArgs fa,
+                                                                            const QpRollout qr, const float4* __restrict__ qtab)
+{
+    constexpr bool TAB = false, QP = true, QTAB = true;
     const float4* const tab = nullptr;
 #include "dpenv_control_rollout_body.inc"
+}
+
+// The public QP table float[DPENV_QP_NPARAM][n] -> the packed block, one lane per env (dpenv_set_qp_allocator_table): qp_lane_from_row
+// forms dF / da with the handle's dt, checks the row and packs a refused one as the rest allocator; refused: uint8 [n] or NULL.
+__global__ __launch_bounds__(256) void pack_qp_table_kernel(const float* __restrict__ pub, float4* __restrict__ qtab,
+                                                             uint8_t* __restrict__ refused, float dt, int n)
+{
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    QpLane q;
+    const bool ok = qp_lane_from_row(pub, n, i, dt, 0, q);
+    float f[4 * QP_TAB_STREAMS];
+    qp_lane_flatten(q, f);
+#pragma unroll
+    for (int k = 0; k < QP_TAB_STREAMS; ++k) qtab[qp_tab_index(i, k)] = make_float4(f[4 * k], f[4 * k + 1], f[4 * k + 2], f[4 * k + 3]);
+    if (refused) refused[i] = ok ? 0 : 1;
 }
 
 // zeroes the thruster state [5][n] of the envs of mask (NULL = every env): dpenv_reset, turning the allocator on
@@ -215,6 +249,36 @@ __global__ __launch_bounds__(256) void qp_alloc_kernel(const QpArgs qa, const Qp
     if (io.cost) io.cost[i] = J;
 }
 
+// qp_alloc_kernel with row i of the PUBLIC table on env i (dpenv_thrust_alloc_qp_table): the lane reads its 26 numbers (lane-contiguous
+// rows) and checks them itself, with the packing kernel's device function.  A refused lane runs the rest allocator, reports a NaN
+// objective and sets its byte of refused (uint8 [n] or NULL).
+__global__ __launch_bounds__(256) void qp_alloc_tab_kernel(const float* __restrict__ pub, const int iters, const float dt, const QpAllocIO io,
+                                                            uint8_t* __restrict__ refused)
+{
+    const int n = io.n;
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    QpLane q;
+    const bool ok = qp_lane_from_row(pub, n, i, dt, iters, q);
+    const float tau[3] = {io.tau[i], io.tau[(int64_t)n + i], io.tau[2 * (int64_t)n + i]};
+    float x[5] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+    if (io.state_in) {
+#pragma unroll
+        for (int k = 0; k < 5; ++k) x[k] = io.state_in[(int64_t)k * n + i];
+    }
+    float act[7], J;
+    qp_allocate(q, tau, x, act, J);
+    if (io.state_out) {
+#pragma unroll
+        for (int k = 0; k < 5; ++k) io.state_out[(int64_t)k * n + i] = x[k];
+    }
+    float* p = io.act + (int64_t)i * 7;
+#pragma unroll
+    for (int k = 0; k < 7; ++k) p[k] = act[k];
+    if (io.cost) io.cost[i] = ok ? J : __builtin_nanf("");
+    if (refused) refused[i] = ok ? 0 : 1;
+}
+
 }  // namespace
 }  // namespace dpenv
 
@@ -231,14 +295,27 @@ hipError_t dev::launch_qp_alloc(const QpArgs* qa, const QpAllocIO* io, hipStream
 }
 
 hipError_t dev::launch_controller_rollout(const StepArgs* a, const ControlArgs* ca, const FilterArgs* fa, const float4* tab, const QpRollout* qr,
-                                          int ves, hipStream_t s)
+                                          const float4* qtab, int ves, hipStream_t s)
 {
     // the vessel source must match the arguments (as launch_rollout's): a per-env form needs the table, VES_ARGS_LOSS and only it reads StepArgs.kl
     if ((ves == VES_ENV_VGPR || ves == VES_ENV_RND) && !a->env_tab) return hipErrorInvalidValue;
     if ((ves == VES_ARGS_LOSS) != (a->loss_on == LOSS_SHARED)) return hipErrorInvalidValue;
     const dim3 grid((a->n + RBLOCK - 1) / RBLOCK), block(RBLOCK);
-    if (qr) {                                                    // the QP allocation: the shared numbers and a shared hull only
+    if (!qr && qtab) return hipErrorInvalidValue;
+    if (qr) {                                                    // the QP allocation: a shared hull only
         if (tab || !qr->state || qr->q.iters < 1 || qr->q.iters > QP_MAX_ITERS) return hipErrorInvalidValue;
+        if (qtab) {                                              // every env on its own row of the packed QP block
+            if (ves == VES_ARGS) {
+                if (fa) hipLaunchKernelGGL((controller_rollout_qp_tab_kernel<VES_ARGS, true>), grid, block, 0, s, *a, *ca, *fa, *qr, qtab);
+                else hipLaunchKernelGGL((controller_rollout_qp_tab_kernel<VES_ARGS, false>), grid, block, 0, s, *a, *ca, FilterArgs{}, *qr, qtab);
+            } else if (ves == VES_ARGS_LOSS) {
+                if (fa) hipLaunchKernelGGL((controller_rollout_qp_tab_kernel<VES_ARGS_LOSS, true>), grid, block, 0, s, *a, *ca, *fa, *qr, qtab);
+                else hipLaunchKernelGGL((controller_rollout_qp_tab_kernel<VES_ARGS_LOSS, false>), grid, block, 0, s, *a, *ca, FilterArgs{}, *qr, qtab);
+            } else {
+                return hipErrorInvalidValue;
+            }
+            return hipGetLastError();
+        }
         if (ves == VES_ARGS) {
             if (fa) hipLaunchKernelGGL((controller_rollout_qp_kernel<VES_ARGS, true>), grid, block, 0, s, *a, *ca, *fa, *qr);
             else hipLaunchKernelGGL((controller_rollout_qp_kernel<VES_ARGS, false>), grid, block, 0, s, *a, *ca, FilterArgs{}, *qr);
@@ -284,5 +361,19 @@ hipError_t dev::launch_control_state(float4* z, float* ext, const uint8_t* mask,
 hipError_t dev::launch_thrust_alloc(const ControlArgs* ca, const float* tau, float* action, int n, hipStream_t s)
 {
     hipLaunchKernelGGL(alloc_kernel, dim3((n + 255) / 256), dim3(256), 0, s, *ca, tau, action, n);
+    return hipGetLastError();
+}
+
+hipError_t dev::launch_pack_qp_table(const float* table, float4* qtab, uint8_t* refused, float dt, int n, hipStream_t s)
+{
+    if (!table || !qtab || n <= 0) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(pack_qp_table_kernel, dim3((n + 255) / 256), dim3(256), 0, s, table, qtab, refused, dt, n);
+    return hipGetLastError();
+}
+
+hipError_t dev::launch_qp_alloc_tab(const float* table, int iters, float dt, const QpAllocIO* io, uint8_t* refused, hipStream_t s)
+{
+    if (!table || io->n <= 0 || !io->tau || !io->act || iters < 1 || iters > QP_MAX_ITERS) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(qp_alloc_tab_kernel, dim3((io->n + 255) / 256), dim3(256), 0, s, table, iters, dt, *io, refused);
     return hipGetLastError();
 }

@@ -1,8 +1,9 @@
 // dpenv_control_rollout_body.inc - the body of controller_rollout_kernel, controller_rollout_tab_kernel and controller_rollout_qp_kernel
 // (dpenv_control.hip), included into each (see dpenv_policy_rollout_body.inc for why it is spliced, not called).  In scope: a (StepArgs), ca (ControlArgs), fa
 // (FilterArgs), the compile-time TAB and, if TAB, tab (the packed per-env controller block, ctrl_tab_index), the compile-time QP and, if QP,
-// qr (QpRollout: the rate-limited QP allocation of dpenv_qp_law.h in place of dp_allocate, its thruster state carried beside z); the
-// rest are the kernel's template arguments.
+// qr (QpRollout: the rate-limited QP allocation of dpenv_qp_law.h in place of dp_allocate, its thruster state carried beside z), the
+// compile-time QTAB (with QP) and, if QTAB, qtab (the packed per-env QP block, qp_tab_index: the env's own numbers in place of qr.q's,
+// of which only iters is read); the rest are the kernel's template arguments.
     constexpr int MODE = MODE_FINAL_CONT;
     constexpr bool EXT = true;
     constexpr int A = 7, OD = 9;
@@ -22,6 +23,8 @@
     load_env(a, il, s);
     ControlLane cl;                                              // TAB: the env's own numbers, read once, in the opening burst
     if constexpr (TAB) load_control_lane(tab, il, ca.dt, cl);
+    QpLane ql;                                                   // QTAB: the env's own QP numbers, likewise
+    if constexpr (QTAB) load_qp_lane(qtab, il, qr.q.iters, ql);
     sincos_lean(s.psi, s.sn, s.cs);
     Current cur = {0.0f, 0.0f, 0.0f, 0.0f, 0u};
     float vc0 = 0.0f, beta0 = 0.0f;
@@ -74,7 +77,8 @@
         if constexpr (QP) {                                      // the PID's wrench, allocated by the QP law
             float tau[3], J;
             dp_wrench(ca, o, z, tau);
-            qp_allocate(qr.q, tau, xq, act, J);
+            if constexpr (QTAB) qp_allocate(ql, tau, xq, act, J);
+            else qp_allocate(qr.q, tau, xq, act, J);
         } else if constexpr (TAB) dp_control(cl, o, z, act);
         else dp_control(ca, o, z, act);
         control_store_rows<A>(lds_row, ca.act, (int64_t)t * stride_a + w_a, rem_a, act, tid, false);

@@ -241,6 +241,22 @@ struct QpArgs {
     int32_t iters;              // 1 .. QP_MAX_ITERS
 };
 constexpr int QP_MAX_ITERS = 32;
+// The numbers of ONE env, in registers: what the *_qp_tab kernels fly instead of QpArgs' shared set while a per-env QP table is in force
+// (dpenv_set_qp_allocator_table, dpenv_thrust_alloc_qp_table).  QpArgs' members under QpArgs' names, so qp_allocate reads either; iters
+// is the call's (wave-uniform).
+struct QpLane {
+    float ws[3], wp, wda, wdf;
+    float fmax[3];
+    float dF[3], da[2];
+    float lx[3], ly[3], kf[3], kr[3];
+    int32_t iters;
+};
+// slots of the public per-env QP table float[QP_NPARAM][n] = DPENV_QP_* of include/dpenv.h (dpenv_api.hip asserts it), in the order of
+// dpenv_qp_allocator's fields; QP_NREAD of them are read
+constexpr int QP_NPARAM = 32, QP_WSLACK = 0, QP_WPOWER = 3, QP_WDALPHA = 4, QP_WDFORCE = 5, QP_FMAX = 6, QP_FRATE = 9, QP_ARATE = 12,
+              QP_LX = 14, QP_LY = 17, QP_KF = 20, QP_KR = 23, QP_NREAD = 26;
+constexpr int QP_TAB_STREAMS = 7;     // float4 streams of the packed per-env QP block (dpenv_qp_law.h has its layout): 112 B per env
+constexpr int64_t qp_tab_float4s(int n) { return ((int64_t)n + 63) / 64 * 64 * QP_TAB_STREAMS; }   // whole waves of 64 envs
 // the allocation as the allocation stage of the baseline's closed loop (dpenv_set_qp_allocator): the numbers and the per-env thruster
 // state, a separate argument of controller_rollout_qp_kernel only
 struct QpRollout {
@@ -486,8 +502,10 @@ hipError_t launch_reff_state_io(float4* state, float* x, float* r, int n, int wr
 // stateless allocation tau [3][n] -> action [n][7]
 // tab: the packed per-env block launch_pack_controllers wrote (every env flies its own row: the *_tab kernels), or NULL (ca's shared numbers)
 // qr: the QP allocation in place of the pseudo-inverse (tab NULL; VES_ARGS and VES_ARGS_LOSS only), or NULL
-hipError_t launch_controller_rollout(const StepArgs* a, const ControlArgs* ca, const FilterArgs* fa, const float4* tab, const QpRollout* qr, int ves,
-                                     hipStream_t s);
+// qtab (with qr): the packed per-env QP block launch_pack_qp_table wrote - every env flies its own row (the *_qp_tab kernels) and of qr->q
+// only iters is read - or NULL (qr->q's shared numbers)
+hipError_t launch_controller_rollout(const StepArgs* a, const ControlArgs* ca, const FilterArgs* fa, const float4* tab, const QpRollout* qr,
+                                     const float4* qtab, int ves, hipStream_t s);
 // the public table float[CTRL_NPARAM][n] -> the packed block of ctrl_tab_float4s(n) float4; refused: uint8 [n] or NULL (dpenv_set_dp_controller_table)
 hipError_t launch_pack_controllers(const float* table, float4* tab, uint8_t* refused, int n, hipStream_t s);
 hipError_t launch_control_state(float4* z, float* ext, const uint8_t* mask, int n, int op, hipStream_t s);
@@ -501,6 +519,11 @@ hipError_t launch_controller_label_qp(const ControlArgs* ca, const QpArgs* qa, c
 hipError_t launch_qp_alloc(const QpArgs* qa, const QpAllocIO* io, hipStream_t s);
 // the zeroing of the closed loop's QP thruster state for the envs of mask (NULL = every env)
 hipError_t launch_qp_state_clear(float* state, const uint8_t* mask, int n, hipStream_t s);
+// the public QP table float[QP_NPARAM][n] -> the packed block of qp_tab_float4s(n) float4, dF and da formed with dt; refused: uint8 [n] or
+// NULL (dpenv_set_qp_allocator_table)
+hipError_t launch_pack_qp_table(const float* table, float4* qtab, uint8_t* refused, float dt, int n, hipStream_t s);
+// launch_qp_alloc with row i of the PUBLIC table on env i, checked by the lane itself (dpenv_thrust_alloc_qp_table)
+hipError_t launch_qp_alloc_tab(const float* table, int iters, float dt, const QpAllocIO* io, uint8_t* refused, hipStream_t s);
 // two-wave closed loop, dpenv_policy_ws.h; one arithmetic per translation unit: dpenv_policy_ws.hip PREC_F16, dpenv_policy_xws1.hip
 // PREC_F32, dpenv_policy_xws2.hip PREC_F32_ACTOR
 template <int PREC>

@@ -190,4 +190,92 @@ __device__ __forceinline__ void qp_allocate(const Q& q, const float tau[3], floa
     J_out = p.J;
 }
 
+// ---- one QP allocator per env (dpenv_set_qp_allocator_table, dpenv_thrust_alloc_qp_table): QpLane (dpenv_dev.h) holds an env's numbers in
+// registers and qp_allocate<QpLane> above is the law, unedited ----
+
+// The packed per-env block pack_qp_table_kernel writes, ctrl_tab_index's layout with QP_TAB_STREAMS streams: per wave of 64 envs seven
+// float4 streams of 64 lanes, stream k of env i at qp_tab_index(i, k).  Flat slot q = 4 k + component:
+// ws 0-2 | wp 3 | wda 4 | wdf 5 | fmax 6-8 | dF 9-11 | da 12-13 | lx 14-16 | ly 17-19 | kf 20-22 | kr 23-25 | 26, 27 pad
+__host__ __device__ __forceinline__ int64_t qp_tab_index(int i, int k) { return ((int64_t)(i >> 6) * QP_TAB_STREAMS + k) * 64 + (i & 63); }
+
+__device__ __forceinline__ void qp_lane_flatten(const QpLane& q, float f[4 * QP_TAB_STREAMS])
+{
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        f[k] = q.ws[k]; f[6 + k] = q.fmax[k]; f[9 + k] = q.dF[k]; f[14 + k] = q.lx[k]; f[17 + k] = q.ly[k]; f[20 + k] = q.kf[k];
+        f[23 + k] = q.kr[k];
+    }
+    f[3] = q.wp; f[4] = q.wda; f[5] = q.wdf;
+    f[12] = q.da[0]; f[13] = q.da[1];
+    f[26] = f[27] = 0.0f;
+}
+
+// the env's numbers out of the packed block: seven 16-byte loads, checked and with dF / da formed when the block was packed
+__device__ __forceinline__ void load_qp_lane(const float4* __restrict__ qtab, int il, int iters, QpLane& q)
+{
+    float f[4 * QP_TAB_STREAMS];
+#pragma unroll
+    for (int k = 0; k < QP_TAB_STREAMS; ++k) {
+        const float4 v = qtab[qp_tab_index(il, k)];
+        f[4 * k] = v.x; f[4 * k + 1] = v.y; f[4 * k + 2] = v.z; f[4 * k + 3] = v.w;
+    }
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        q.ws[k] = f[k]; q.fmax[k] = f[6 + k]; q.dF[k] = f[9 + k]; q.lx[k] = f[14 + k]; q.ly[k] = f[17 + k]; q.kf[k] = f[20 + k];
+        q.kr[k] = f[23 + k];
+    }
+    q.wp = f[3]; q.wda = f[4]; q.wdf = f[5];
+    q.da[0] = f[12]; q.da[1] = f[13];
+    q.iters = iters;
+}
+
+// Row i of the PUBLIC table float[QP_NPARAM][n] -> the lane's numbers: dF = force_rate * dt and da = azimuth_rate * dt as one f32 product
+// each (what the host forms for dpenv_set_qp_allocator), then dpenv_thrust_alloc_qp's checks.  A row that breaks one is replaced by the
+// REST allocator - f_max = dF = da = 0, w_slack = w_power = 0, w_dalpha = w_dforce = 1, lx = ly = 0, kf = kr = 1: zero thrust, azimuths
+// held, every output finite - and false is returned.  The ONLY statement of the per-row checks on the device: the packing kernel and the
+// handle-free kernel both call it.
+__device__ __forceinline__ bool qp_lane_from_row(const float* __restrict__ pub, int n, int i, float dt, int iters, QpLane& q)
+{
+    float p[QP_NREAD];
+#pragma unroll
+    for (int k = 0; k < QP_NREAD; ++k) p[k] = pub[(int64_t)k * n + i];
+    float dF[3], da[2];
+    bool ok = true;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        dF[k] = p[QP_FRATE + k] * dt;
+        ok = ok && isfinite(p[QP_WSLACK + k]) && p[QP_WSLACK + k] >= 0.0f;
+        ok = ok && isfinite(p[QP_FMAX + k]) && p[QP_FMAX + k] >= 0.0f;
+        ok = ok && isfinite(p[QP_FRATE + k]) && p[QP_FRATE + k] >= 0.0f && isfinite(dF[k]);
+        ok = ok && isfinite(p[QP_LX + k]) && isfinite(p[QP_LY + k]);
+        ok = ok && isfinite(p[QP_KF + k]) && p[QP_KF + k] > 0.0f;
+        ok = ok && isfinite(p[QP_KR + k]) && p[QP_KR + k] > 0.0f;
+    }
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+        da[k] = p[QP_ARATE + k] * dt;
+        ok = ok && isfinite(p[QP_ARATE + k]) && p[QP_ARATE + k] >= 0.0f && isfinite(da[k]);
+    }
+    ok = ok && isfinite(p[QP_WPOWER]) && p[QP_WPOWER] >= 0.0f;
+    ok = ok && isfinite(p[QP_WDALPHA]) && p[QP_WDALPHA] > 0.0f;
+    ok = ok && isfinite(p[QP_WDFORCE]) && p[QP_WDFORCE] > 0.0f;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        q.ws[k] = ok ? p[QP_WSLACK + k] : 0.0f;
+        q.fmax[k] = ok ? p[QP_FMAX + k] : 0.0f;
+        q.dF[k] = ok ? dF[k] : 0.0f;
+        q.lx[k] = ok ? p[QP_LX + k] : 0.0f;
+        q.ly[k] = ok ? p[QP_LY + k] : 0.0f;
+        q.kf[k] = ok ? p[QP_KF + k] : 1.0f;
+        q.kr[k] = ok ? p[QP_KR + k] : 1.0f;
+    }
+    q.da[0] = ok ? da[0] : 0.0f;
+    q.da[1] = ok ? da[1] : 0.0f;
+    q.wp = ok ? p[QP_WPOWER] : 0.0f;
+    q.wda = ok ? p[QP_WDALPHA] : 1.0f;
+    q.wdf = ok ? p[QP_WDFORCE] : 1.0f;
+    q.iters = iters;
+    return ok;
+}
+
 #endif

@@ -543,6 +543,78 @@ def qp_allocator_defaults(vessel=None):
                 kf=v[P['KF_BOW']:P['KF_BOW'] + 3].copy(), kr=v[P['KR_BOW']:P['KR_BOW'] + 3].copy())
 
 
+# the public per-env QP table float[32][n] (include/dpenv.h DPENV_QP_*): parameter name -> (first slot, width), in the order of
+# dpenv_qp_allocator's fields; the iteration count is not in the table (one number per call)
+QP_NPARAM = 32
+QP_SLOTS = dict(w_slack=(0, 3), w_power=(3, 1), w_dalpha=(4, 1), w_dforce=(5, 1), f_max=(6, 3), force_rate=(9, 3), azimuth_rate=(12, 2),
+                lx=(14, 3), ly=(17, 3), kf=(20, 3), kr=(23, 3))
+
+
+def qp_allocator_table(n, params=None, **per_env):
+    """The public QP table [32, n] float32 in the slot order of include/dpenv.h (env.set_qp_allocator_table and policy.thrust_alloc_qp take
+    it as a tensor): every env starts from params (the dict of qp_allocator_defaults; None = the default hull's), and any of w_slack,
+    w_power, w_dalpha, w_dforce, f_max, force_rate, azimuth_rate, lx, ly, kf, kr may be given per env as an array with a leading n.  The
+    table carries rates, not per-step limits: the library multiplies by its dt.  The iteration count is not in the table: an `iterations`
+    entry is accepted and ignored, so qp_allocator_table(n, **qp_allocator_table_params(table)) is the table again."""
+    p = qp_allocator_defaults() if params is None else params
+    per_env.pop('iterations', None)
+    unknown = sorted(set(per_env) - set(QP_SLOTS))
+    if unknown:
+        raise TypeError('qp_allocator_table: unknown per-env parameter(s) %s (of %s)' % (unknown, sorted(QP_SLOTS)))
+    tab = np.zeros((QP_NPARAM, int(n)), np.float32)
+    for name, (first, width) in QP_SLOTS.items():
+        if name in per_env:
+            v = np.asarray(per_env[name], np.float64)
+            if v.shape not in ((n, width),) + (((n,),) if width == 1 else ()):
+                raise ValueError('qp_allocator_table: %s has shape %s, want [%d, %d]' % (name, v.shape, n, width))
+            tab[first:first + width] = v.reshape(n, width).T
+        else:
+            v = np.asarray(p[name], np.float64).reshape(-1)
+            if v.shape != (width,):
+                raise ValueError('qp_allocator_table: params[%r] has %d entries, want %d' % (name, v.size, width))
+            tab[first:first + width] = v[:, None]
+    return tab
+
+
+def qp_allocator_table_params(table, iterations=16):
+    """The per-env parameter dict BatchedQPAllocator takes for a public table [32, n]: every entry with a leading n (float64 of the
+    table's f32 numbers), plus iterations.  qp_allocator_table(n, **that dict without iterations) is the table again.  Rows the library
+    would refuse are not treated here."""
+    tab = np.asarray(table, np.float32)
+    if tab.ndim != 2 or tab.shape[0] != QP_NPARAM:
+        raise ValueError('qp_allocator_table_params: a [32, n] table')
+    p = dict(iterations=int(iterations))
+    for name, (first, width) in QP_SLOTS.items():
+        v = tab[first:first + width].T.astype(np.float64)
+        p[name] = v[:, 0] if width == 1 else v
+    return p
+
+
+def qp_weight_population(K, base=None, span=4.0, seed=0, what=('w_power', 'w_dalpha', 'w_dforce')):
+    """K QP parameter sets around base (the dict of qp_allocator_defaults; None = the default hull's) for evaluate.qp_weight_sweep:
+    gain_population's contract.  The dict of base with every entry named in `what` as an array with a leading K; row 0 is the base
+    itself, the others multiply each named entry (per component) by a factor drawn log-uniformly from [1 / span, span]
+    (np.random.RandomState(seed): the same sets for the same arguments).  'factors' holds the factors drawn, name -> [K, ...]."""
+    base = qp_allocator_defaults() if base is None else base
+    span = float(span)
+    if K < 1 or not span >= 1.0:
+        raise ValueError('qp_weight_population: K >= 1 and span >= 1')
+    unknown = sorted(set(what) - set(QP_SLOTS))
+    if unknown:
+        raise ValueError('qp_weight_population: unknown parameter(s) %s (of %s)' % (unknown, sorted(QP_SLOTS)))
+    rng = np.random.RandomState(seed)
+    lo, hi = 1.0 / span, span
+    pop = dict(base)
+    pop['factors'] = {}
+    for name in what:
+        b = np.asarray(base[name], np.float64)
+        f = np.clip(np.exp(rng.uniform(np.log(lo), np.log(hi), size=(K,) + b.shape)), lo, hi)
+        f[0] = 1.0
+        pop['factors'][name] = f
+        pop[name] = b[None] * f
+    return pop
+
+
 class BatchedQPAllocator(object):
     """The rate-limited QP thrust allocation for n envs on the host: the statement of include/dpenv.h (dpenv_thrust_alloc_qp), operation
     by operation, in batched NumPy.  dtype float32 (the default) is the kernel's arithmetic except for sin / cos (np.sin / np.cos here, the
@@ -550,10 +622,17 @@ class BatchedQPAllocator(object):
     State x [n, 5] = F_bow, F_port, F_star, a_port, a_star (the thruster state in force, azimuths wrapped to [-pi, pi)).
     allocate(tau [n, 3]) advances the state one control step and returns the action [n, 7]; an env whose tau is not finite keeps its
     state and commands it.  reset(mask) zeroes the state of the envs in mask (None = all).  objective(x, tau, prev) is J [n].
-    After allocate: last_x is the un-wrapped solution, last_J the objective per iteration [iterations + 1, n]."""
+    After allocate: last_x is the un-wrapped solution, last_J the objective per iteration [iterations + 1, n].
+    Per-env parameters (the law of dpenv_set_qp_allocator_table, env i on its own row): params is a public table [32, n]
+    (qp_allocator_table; `iterations` then gives the count, default 16) or a dict whose entries carry a leading n - w_slack [n, 3] ...
+    w_power [n]; shared and per-env entries may be mixed.  The expressions are the same, so all-equal rows give the shared form's bits."""
 
-    def __init__(self, n, params=None, dt=0.2, dtype=None):
+    def __init__(self, n, params=None, dt=0.2, dtype=None, iterations=None):
         p = qp_allocator_defaults() if params is None else params
+        if not isinstance(p, dict):
+            p = qp_allocator_table_params(p.detach().cpu().numpy() if hasattr(p, 'detach') else p, 16 if iterations is None else iterations)
+        elif iterations is not None:
+            p = dict(p, iterations=iterations)
         self.dtype = np.dtype(np.float32 if dtype is None else dtype)
         is32 = self.dtype == np.dtype(np.float32)
         t = lambda v: np.asarray(v, np.float64).astype(self.dtype)
@@ -563,8 +642,11 @@ class BatchedQPAllocator(object):
             raise ValueError('BatchedQPAllocator: iterations must be in 1..%d' % QP_MAX_ITERATIONS)
         for name, shape in (('w_slack', (3,)), ('f_max', (3,)), ('force_rate', (3,)), ('azimuth_rate', (2,)), ('lx', (3,)), ('ly', (3,)),
                             ('kf', (3,)), ('kr', (3,))):
-            if np.shape(p[name]) != shape:
-                raise ValueError('BatchedQPAllocator: %s has shape %s, want %s' % (name, np.shape(p[name]), shape))
+            if np.shape(p[name]) not in (shape, (self.n,) + shape):
+                raise ValueError('BatchedQPAllocator: %s has shape %s, want %s or %s' % (name, np.shape(p[name]), shape, (self.n,) + shape))
+        for name in ('w_power', 'w_dalpha', 'w_dforce'):
+            if np.shape(p[name]) not in ((), (self.n,)):
+                raise ValueError('BatchedQPAllocator: %s has shape %s, want a scalar or %s' % (name, np.shape(p[name]), (self.n,)))
         self.ws, self.wp, self.wda, self.wdf = t(p['w_slack']), t(p['w_power']), t(p['w_dalpha']), t(p['w_dforce'])
         self.fmax, self.lx, self.ly, self.kf, self.kr = t(p['f_max']), t(p['lx']), t(p['ly']), t(p['kf']), t(p['kr'])
         dt = t(np.float32(dt)) if is32 else t(dt)                 # f32: the library's n_substeps * substep_dt
@@ -583,16 +665,16 @@ class BatchedQPAllocator(object):
         """sin, cos [n, 2], the moment arms b3 [n, 2] and r [n, 3] at x."""
         F = x[:, 0:3]
         s, c = np.sin(x[:, 3:5]).astype(self.dtype), np.cos(x[:, 3:5]).astype(self.dtype)
-        b3 = self.lx[1:3] * s - self.ly[1:3] * c
+        b3 = self.lx[..., 1:3] * s - self.ly[..., 1:3] * c
         r0 = (c[:, 0] * F[:, 1] + c[:, 1] * F[:, 2]) - tau[:, 0]
         r1 = ((F[:, 0] + s[:, 0] * F[:, 1]) + s[:, 1] * F[:, 2]) - tau[:, 1]
-        r2 = ((self.lx[0] * F[:, 0] + b3[:, 0] * F[:, 1]) + b3[:, 1] * F[:, 2]) - tau[:, 2]
+        r2 = ((self.lx[..., 0] * F[:, 0] + b3[:, 0] * F[:, 1]) + b3[:, 1] * F[:, 2]) - tau[:, 2]
         return s, c, b3, np.stack([r0, r1, r2], 1)
 
     def _objective(self, x, r, prev):
         t = self.dtype.type
         F, ws = x[:, 0:3], self.ws
-        Js = (ws[0] * (r[:, 0] * r[:, 0]) + ws[1] * (r[:, 1] * r[:, 1])) + ws[2] * (r[:, 2] * r[:, 2])
+        Js = (ws[..., 0] * (r[:, 0] * r[:, 0]) + ws[..., 1] * (r[:, 1] * r[:, 1])) + ws[..., 2] * (r[:, 2] * r[:, 2])
         c3 = np.abs(F) * (F * F)
         Jp = (c3[:, 0] + c3[:, 1]) + c3[:, 2]
         e = x - prev
@@ -621,12 +703,12 @@ class BatchedQPAllocator(object):
             for _ in range(self.iterations):
                 F = x[:, 0:3]
                 # the 3 x 5 Jacobian, columns F_bow, F_port, F_star, a_port, a_star
-                d3 = self.lx[1:3] * c + self.ly[1:3] * s
+                d3 = self.lx[..., 1:3] * c + self.ly[..., 1:3] * s
                 Jm = [[zero, c[:, 0], c[:, 1], -(F[:, 1] * s[:, 0]), -(F[:, 2] * s[:, 1])],
                       [one, s[:, 0], s[:, 1], F[:, 1] * c[:, 0], F[:, 2] * c[:, 1]],
-                      [self.lx[0] * one, b3[:, 0], b3[:, 1], F[:, 1] * d3[:, 0], F[:, 2] * d3[:, 1]]]
-                wr = [self.ws[j] * r[:, j] for j in range(3)]
-                WJ = [[self.ws[j] * Jm[j][k] for k in range(5)] for j in range(3)]
+                      [self.lx[..., 0] * one, b3[:, 0], b3[:, 1], F[:, 1] * d3[:, 0], F[:, 2] * d3[:, 1]]]
+                wr = [self.ws[..., j] * r[:, j] for j in range(3)]
+                WJ = [[self.ws[..., j] * Jm[j][k] for k in range(5)] for j in range(3)]
                 g, H = [None] * 5, [[None] * 5 for _ in range(5)]
                 for k in range(5):
                     g[k] = (Jm[0][k] * wr[0] + Jm[1][k] * wr[1]) + Jm[2][k] * wr[2]

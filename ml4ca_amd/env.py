@@ -187,6 +187,8 @@ class BatchedRevoltEnv(object):
         self.dp_controller = None            # dict of the parameters while set_dp_controller() has it on
         self.dp_controller_table = None      # the [32, n] tensor while set_dp_controller_table() has per-env numbers in force
         self.qp_allocator = None             # dict of the parameters while set_qp_allocator() has the QP allocation in the closed loop
+        self.qp_allocator_table = None       # the [32, n] tensor while set_qp_allocator_table() has per-env QP numbers in force
+        self._qp_table_iterations = 0
 
     # -- plumbing -----------------------------------------------------------------------------
     # What a Python `for` over step() pays per call besides the launch is this plumbing (bench.py `eager_loop`): the stream handle and
@@ -445,13 +447,13 @@ class BatchedRevoltEnv(object):
         integral z of every env.  step(), rollout() and policy_rollout() keep working while it is on."""
         if off:
             _lib.check(self.lib.dpenv_set_dp_controller(self._h, None, self._stream()), self._h)
-            self.dp_controller = self.dp_controller_table = self.qp_allocator = None
+            self.dp_controller = self.dp_controller_table = self.qp_allocator = self.qp_allocator_table = None
             return
         p, c = _dp_controller_struct(params)
         _lib.check(self.lib.dpenv_set_dp_controller(self._h, C.byref(c), self._stream()), self._h)
         self.dp_controller = dict(p)
         self.dp_controller_table = None      # the scalar law again: the library dropped a table in force
-        self.qp_allocator = None             # ... and a QP allocator
+        self.qp_allocator = self.qp_allocator_table = None   # ... and a QP allocator, scalar or per-env
 
     def set_dp_controller_table(self, table, check=True):
         """Per-env numbers for the baseline (dpenv_set_dp_controller_table): table is a float32 tensor [32, n] on the env's device in
@@ -497,7 +499,7 @@ class BatchedRevoltEnv(object):
         Turning it on puts every env's thrusters at rest; resets do the same for the envs they re-draw."""
         if off:
             _lib.check(self.lib.dpenv_set_qp_allocator(self._h, None, self._stream()), self._h)
-            self.qp_allocator = None
+            self.qp_allocator = self.qp_allocator_table = None
             return
         from .deploy import qp_allocator_defaults
         from .policy import qp_allocator_struct
@@ -505,6 +507,40 @@ class BatchedRevoltEnv(object):
         q = qp_allocator_struct(p)
         _lib.check(self.lib.dpenv_set_qp_allocator(self._h, C.byref(q), self._stream()), self._h)
         self.qp_allocator = dict(p)
+        self.qp_allocator_table = None       # the scalar numbers replace a table in force
+
+    def set_qp_allocator_table(self, table, iterations=16, check=True):
+        """One QP allocator per env (dpenv_set_qp_allocator_table): table is a float32 tensor [32, n] on the env's device in the slot order
+        of include/dpenv.h (deploy.qp_allocator_table builds it), and controller_rollout then allocates env i's wrench with row i;
+        iterations (1..32) is one count for every env.  Needs what set_qp_allocator needs, and like it puts every env's thrusters at rest.
+        None returns to the numbers of set_qp_allocator - or to the pseudo-inverse if none were set - and leaves z and the thruster state
+        alone.  The library packs a row it refuses as the rest allocator (zero thrust, azimuths held).  check=True passes a mask, reads it
+        back and, if any row was refused, puts the previous allocator back in force - a previous table is packed again, the thruster
+        state restored - and raises ValueError naming the first refused envs.  check=False reads nothing back: the form to record into a
+        graph (a replay packs the tensor's contents of that moment)."""
+        torch = _torch()
+        if table is None:
+            _lib.check(self.lib.dpenv_set_qp_allocator_table(self._h, None, 0, None, self._stream()), self._h)
+            self.qp_allocator_table = None
+            return
+        self._chk(table, (32, self.n_envs), torch.float32, 'table')
+        qp_was_on = self.qp_allocator is not None or self.qp_allocator_table is not None
+        mask = torch.empty(self.n_envs, dtype=torch.uint8, device=self.device) if check else None
+        x = self.get_qp_allocator_state() if check and qp_was_on else None
+        _lib.check(self.lib.dpenv_set_qp_allocator_table(self._h, self._ptr(table), int(iterations), self._ptr(mask), self._stream()), self._h)
+        prev, prev_iters = self.qp_allocator_table, self._qp_table_iterations
+        self.qp_allocator_table, self._qp_table_iterations = table, int(iterations)
+        if check and bool(mask.any()):
+            bad = torch.nonzero(mask).flatten()
+            if prev is not None:
+                self.set_qp_allocator_table(prev, prev_iters, check=False)
+            else:
+                self.set_qp_allocator_table(None)
+            if x is not None:
+                self.set_qp_allocator_state(x)
+            raise ValueError('set_qp_allocator_table: %d row(s) refused (envs %s%s): a number that is not finite, a negative weight, bound '
+                             'or rate, w_dalpha or w_dforce <= 0, kf or kr <= 0 - the previous allocator stays in force'
+                             % (bad.numel(), bad[:8].tolist(), ', ...' if bad.numel() > 8 else ''))
 
     def get_qp_allocator_state(self):
         """float32 [5, n]: the QP allocator's thruster state F_bow, F_port, F_star, a_port, a_star.  Checkpoint with get_dp_controller_state()."""

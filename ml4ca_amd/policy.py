@@ -433,13 +433,16 @@ def controller_label_qp(env, obs, done=None, z=None, x=None, params=None, out=No
     return (act, z_out, x_out, J) if cost else (act, z_out, x_out)
 
 
-def thrust_alloc_qp(tau, state=None, params=None, dt=0.2, out=None, cost=False):
+def thrust_alloc_qp(tau, state=None, params=None, dt=0.2, out=None, cost=False, table=None, iterations=None, refused=None):
     """One control step of the rate-limited QP thrust allocation on the device (dpenv_thrust_alloc_qp), one lane per env: tau float32
     [3, n] = Fx, Fy, Mz and the thruster state in force, state float32 [5, n] = F_bow, F_port, F_star, a_port, a_star (None = zeros), ->
     (action [n, 7], new state [5, n]) and, with cost=True, the final objective [n] as a third value.  params: the dict of
     deploy.qp_allocator_defaults (None = the defaults); dt the control period.  out = (action, state) supplies the buffers; the state
     buffer may be the input tensor itself.  An env whose tau is not finite keeps its state and commands it.  Handle-free: a caller with
-    its own motion controller closes the loop with this between two launches.  deploy.BatchedQPAllocator is the host statement."""
+    its own motion controller closes the loop with this between two launches.  deploy.BatchedQPAllocator is the host statement.
+    table: a float32 device tensor [32, n] (deploy.qp_allocator_table) - env i is allocated with row i (dpenv_thrust_alloc_qp_table), in
+    iterations solver steps (None = 16); giving params too is an error.  Each lane checks its own row: a refused one runs the rest
+    allocator (zero thrust, azimuths held), reports a NaN objective and sets its byte of refused (a uint8 tensor [n], or None)."""
     torch = _torch()
     lib = _lib.load()
     f32 = torch.float32
@@ -459,8 +462,24 @@ def thrust_alloc_qp(tau, state=None, params=None, dt=0.2, out=None, cost=False):
     chk(act, (n, 7), 'out[0]')
     chk(state_out, (5, n), 'out[1]')
     J = torch.empty((n,), dtype=f32, device=tau.device) if cost else None
-    q = qp_allocator_struct(params)
     s = C.c_void_p(torch.cuda.current_stream(tau.device).cuda_stream)
+    if table is not None:
+        if params is not None:
+            raise ValueError('thrust_alloc_qp: params or table, not both')
+        chk(table, (32, n), 'table')
+        if refused is not None and (not isinstance(refused, torch.Tensor) or tuple(refused.shape) != (n,) or refused.dtype != torch.uint8
+                                    or refused.device != tau.device or not refused.is_contiguous()):
+            raise ValueError('thrust_alloc_qp: refused is a contiguous uint8 tensor [%d] on tau\'s device' % n)
+        with torch.cuda.device(tau.device):
+            _lib.check(lib.dpenv_thrust_alloc_qp_table(C.c_void_p(table.data_ptr()), 16 if iterations is None else int(iterations), float(dt),
+                                                       C.c_void_p(tau.data_ptr()), C.c_void_p(state.data_ptr()) if state is not None else None,
+                                                       C.c_void_p(state_out.data_ptr()), C.c_void_p(act.data_ptr()),
+                                                       C.c_void_p(J.data_ptr()) if cost else None,
+                                                       C.c_void_p(refused.data_ptr()) if refused is not None else None, n, s))
+        return (act, state_out, J) if cost else (act, state_out)
+    if iterations is not None or refused is not None:
+        raise ValueError('thrust_alloc_qp: iterations and refused go with table (params carries its own iterations)')
+    q = qp_allocator_struct(params)
     with torch.cuda.device(tau.device):
         _lib.check(lib.dpenv_thrust_alloc_qp(C.byref(q), float(dt), C.c_void_p(tau.data_ptr()),
                                              C.c_void_p(state.data_ptr()) if state is not None else None, C.c_void_p(state_out.data_ptr()),

@@ -18,6 +18,8 @@ env.step, critic, trajectory rows), GAE by one scan kernel, advantage statistics
                                                                                       states with the baseline (policy.controller_label), aggregate, refit
     python examples/train_ppo.py --envs 4096 --epochs 30 --update fused --warm-start 300 --dagger 5 --expert qp --eval      the same with the PID + QP
                                                                                       chain as the expert: it flies the demonstration and labels the rounds
+    python examples/train_ppo.py --envs 4096 --epochs 30 --update fused --warm-start 300 --dagger 5 --expert qp --expert-state flown --eval      ... each
+                                                                                      row labelled from the thruster state the ACTOR's last action left
     python examples/train_ppo.py --envs 4096 --epochs 40 --randomise 0.15 --eval      domain randomisation: every episode of every env
                                                                                       runs on its own hull, +-15 % on all 26 parameters, re-drawn by the reset path
                                                                                       inside the rollout launch; --eval: the reference's evaluation harness
@@ -233,7 +235,7 @@ def dagger(upd, env, args, out=print):
     # the scan touches no hull, so it labels the randomised-hull envs the QP closed loop cannot fly
     rec = upd.dagger(env, args.dagger, T, args.dagger_iters, minibatch=mb, loss=args.warm_start_loss, keep=args.dagger_keep or None,
                      average=D.average_flat, upload=dict(precision=args.precision), expert=args.expert,
-                     qp_params=qp_allocator_defaults(nominal) if args.expert == 'qp' else None)
+                     qp_params=qp_allocator_defaults(nominal) if args.expert == 'qp' else None, thruster_state=args.expert_state)
     torch.cuda.synchronize()
     D.assert_params_in_step(list(upd.ac.parameters()), what='parameters after DAgger')
     env.set_dp_controller(off=True)
@@ -315,6 +317,10 @@ def main():
                     help="the expert of --warm-start and --dagger: 'pinv' = PID + pseudo-inverse; 'qp' = the same PID with the rate-limited QP allocation "
                          '(55 %% of the pseudo-inverse\'s thruster work on the box test): the warm-start flight flies it (env.set_qp_allocator), --dagger '
                          'labels with it (policy.controller_label_qp)')
+    ap.add_argument('--expert-state', default='own', choices=('own', 'flown'),
+                    help="--dagger --expert qp: the thruster state the QP labels a row from: 'own' = the expert's own recursion along the rows; 'flown' = "
+                         'the state the ACTOR\'s executed action of the row before left (PPOUpdater.dagger thruster_state), whose thrust part the actor '
+                         'sees in its lagged thrust columns')
     ap.add_argument('--exchange', default='gradients', choices=('gradients', 'rollout'),
                     help="multi-rank runs: 'gradients' = every rank updates on ITS OWN episode and the gradients are averaged, exactly the "
                          "reference (ppo.py:226, mpi_tf.py:29-62: no trajectory ever crosses); 'rollout' = BASELINE.json config 4: the ranks "
@@ -350,6 +356,8 @@ def main():
         ap.error('--warm-start needs --update fused (the imitation gradient is a kernel of the fused update)')
     if args.dagger > 0 and args.update != 'fused':
         ap.error('--dagger needs --update fused (the imitation gradient is a kernel of the fused update)')
+    if args.expert_state == 'flown' and args.expert != 'qp':
+        ap.error('--expert-state flown goes with --expert qp (the pseudo-inverse has no thruster state)')
     if args.expert == 'qp' and args.randomise > 0 and args.warm_start > 0:
         ap.error('--expert qp with --randomise cannot fly the warm-start demonstration: the QP closed loop runs on a shared hull, not on per-env '
                  'hulls.  Use --dagger without --warm-start: the labelling scan touches no hull')

@@ -899,7 +899,8 @@ int dpenv_set_qp_allocator_state(dpenv_handle h, const float* state_in, dpenv_st
  * the thruster state alone (as dpenv_set_dp_controller_table(NULL) leaves z).  dpenv_set_qp_allocator(h, q) replaces the table by scalar
  * numbers (q = NULL: the pseudo-inverse again, nothing to return to); dpenv_set_dp_controller drops both; dpenv_set_dp_controller_table is
  * refused while a table is set, as it is while a scalar QP is set.  dpenv_get / dpenv_set_qp_allocator_state work unchanged.
- * dpenv_controller_label_qp with q = NULL is refused while a TABLE is in force (the scan takes one set of numbers: pass q). */
+ * dpenv_controller_label_qp with q = NULL is refused while a TABLE is in force (the scan takes one set of numbers: pass q);
+ * dpenv_controller_label_qp_ex labels with a table of its own. */
 int dpenv_set_qp_allocator_table(dpenv_handle h, const float* table, int32_t iterations, uint8_t* refused_out, dpenv_stream s);
 /* dpenv_thrust_alloc_qp with row i of the PUBLIC table (device float[DPENV_QP_NPARAM][n]) on env i; the other arguments are that call's.
  * There is no packing launch: each lane reads its 26 numbers and checks them itself, with the device function the packing kernel uses, so
@@ -919,7 +920,7 @@ int dpenv_thrust_alloc_qp_table(const float* table, int32_t iterations, float dt
  *     if (done && done[t][i] != 0) z_i = 0, x_i = 0     -- the next row is a new episode's first, from thrusters at rest
  * z_i starts from z_in[:, i] and x_i from x_in[:, i] (NULL = 0); they are written to z_out / x_out at the end (NULL = not wanted; each
  * may be its input), so a block labelled in pieces with z and x handed over gives the rows of one call.  x is the EXPERT'S OWN recursion
- * along the rows, as z is: not the thruster state the flown actions would have left.
+ * along the rows, as z is: not the thruster state the flown actions would have left (dpenv_controller_label_qp_ex, below, takes that one).
  * The PID's numbers are the handle's controller in force: row i of dpenv_set_dp_controller_table's table on env i when there is one (G
  * is not read), else dpenv_set_dp_controller's.  dt is the handle's, for z and for dF = force_rate * dt and da = azimuth_rate * dt, one
  * f32 product each formed on the host.  q: the QP's numbers, validated with the checks of dpenv_thrust_alloc_qp; NULL = the ones
@@ -952,6 +953,61 @@ typedef struct dpenv_controller_label_qp_io {
     const dpenv_qp_allocator* q;   /* the QP's numbers; NULL = the ones dpenv_set_qp_allocator has in force on h */
 } dpenv_controller_label_qp_io;
 int dpenv_controller_label_qp(dpenv_handle h, const dpenv_controller_label_qp_io* io, dpenv_stream s);
+/* The same scan with the thruster state taken from the FLOWN actions and / or one QP allocator per env (additive to ABI 6).  The DAgger
+ * label is the expert's answer in the state the learner is in, and the actuators are part of that state: with `flown`, row t is solved
+ * from the thruster state the EXECUTED action of row t - 1 left, not from the expert's own recursion.
+ * S(q, a[7]) -> x[5], the thruster state an executed action row of the final variant's continuous-angle form leaves: the env's own command
+ * decode followed by the QP's thrust law, f32, in this order (clip(v, b) = fminf(fmaxf(v, -b), b)):
+ *     thr_k = clip(a[k] * 100, 100)                                        k = bow, port, star
+ *     K     = thr_k >= 0 ? kf_k : kr_k
+ *     F_k   = (K * thr_k) * |thr_k|
+ *     F_k   = clip(F_k, f_max_k)                       -- the law's precondition |F^-| <= f_max
+ *     x_k   = F_k, or 0 if a[k] or F_k is not finite
+ *     al_i  = clip(atan2(a[3 + 2 i], a[4 + 2 i]), pi)                      i = port, star; the library's call-free atan2, max abs error 2.6e-7
+ *     al_i  = al_i - 2 pi floorf((al_i + pi) * (0.5 / pi))                 -- the wrap of the law's own state, the last step one fmaf
+ *     x_{3+i} = al_i, or 0 if either head or al_i is not finite
+ * kf, kr and f_max are the QP's numbers: row i's when a table labels.  A component fed by an entry that is not finite is AT REST (the env
+ * itself flies a NaN thrust entry as -100 %: such a row has no meaning and the scan does not follow it).
+ * Per row t and env i, everything else as dpenv_controller_label_qp:
+ *     x_used = x_i                                       (x_in[:, i] at t = 0; NULL = 0)
+ *     tau    = the PID lines on obs[t][i] with z_i       (unchanged)
+ *     act[t][i], J = the QP law on tau from x_used       (the law's own advance of x is dropped)
+ *     x_i    = S(q_i, flown[t][i])
+ *     if (done && done[t][i] != 0) z_i = 0, x_i = 0
+ * x_out is the last x_i, so a block labelled in pieces with z and x handed over equals one call; the label of row t does not depend on
+ * flown[t:].  Behind a done row the flown form keeps the convention "thrusters at rest": the thrust the reset drew for the new episode is
+ * not known to the scan.  There is NO float32 bit-for-bit identity against the QP closed loop's own rows for the flown form - S of the law's
+ * own action returns its state to within 2 ulp of the forces and 1e-6 rad, and the solver's accept / reject turns amplify that (a few 1e-2
+ * in an action entry at 16 iterations); the identity that holds is by parts: act[t][i] and cost[t][i] are dpenv_thrust_alloc_qp on the PID's
+ * tau and the x_used above, bit for bit.
+ * qp_table: a DEVICE float[DPENV_QP_NPARAM][n_envs], the public table of dpenv_set_qp_allocator_table, env i labelled with row i in
+ * `iterations` (1..32) solver steps: K weight sets label one block of states in one launch.  There is no packing launch: each lane reads
+ * and checks its row itself, as in dpenv_thrust_alloc_qp_table; a refused row runs the rest allocator, reports NaN in cost and sets its
+ * byte of refused_out (device uint8[n_envs] or NULL; 0 for the others).  dF and da are formed with the handle's dt.
+ * q and qp_table both given: DPENV_EINVAL.  refused_out without qp_table: DPENV_EINVAL.  With neither q nor qp_table the rules of
+ * dpenv_controller_label_qp apply (the handle's scalar numbers; refused while a table is in force: pass q or qp_table).  With flown = NULL
+ * and no qp_table the call IS dpenv_controller_label_qp.  All other refusals are that call's, before anything is launched, and so are its
+ * guarantees: the handle untouched, no allocation, no synchronisation, one kernel node under capture.
+ * ml4ca_amd.deploy.label_rows_qp(flown=...) and deploy.qp_state_from_action are the host statements. */
+typedef struct dpenv_controller_label_qp_ex_io {
+    uint32_t struct_size;    /* sizeof(dpenv_controller_label_qp_ex_io), ABI check */
+    int32_t T;
+    const void* obs;         /* as dpenv_controller_label_qp_io, field by field ... */
+    int32_t obs_dtype;
+    const uint8_t* done;
+    const float* z_in;
+    float* z_out;
+    const float* x_in;
+    float* x_out;
+    float* act;
+    float* cost;
+    const dpenv_qp_allocator* q;
+    const float* flown;      /* ... then: [T][n][7] f32 the executed actions, or NULL = the expert's own recursion */
+    const float* qp_table;   /* device float[DPENV_QP_NPARAM][n], or NULL */
+    int32_t iterations;      /* read with qp_table: 1..32 */
+    uint8_t* refused_out;    /* [n] or NULL; with qp_table */
+} dpenv_controller_label_qp_ex_io;
+int dpenv_controller_label_qp_ex(dpenv_handle h, const dpenv_controller_label_qp_ex_io* io, dpenv_stream s);
 
 /* ---- The PPO update: actor and critic gradients and a device-gated Adam step --------------------------------------------------------
  * Handle-free like dpenv_gae / dpenv_adv_*: device pointers and a stream; no call allocates or synchronises, so a whole update (80

@@ -113,6 +113,11 @@ class ControllerLabelQpIO(C.Structure):
                 ('cost', C.c_void_p), ('q', C.POINTER(QPAllocator))]
 
 
+class ControllerLabelQpExIO(C.Structure):
+    _fields_ = ControllerLabelQpIO._fields_ + [('flown', C.c_void_p), ('qp_table', C.c_void_p), ('iterations', C.c_int32),
+                                               ('refused_out', C.c_void_p)]
+
+
 class ScoreIO(C.Structure):
     _fields_ = [('struct_size', C.c_uint32), ('T', C.c_int32), ('n', C.c_int32), ('obs', C.c_void_p), ('act', C.c_void_p),
                 ('rew', C.c_void_p), ('done', C.c_void_p), ('integ', C.c_void_p), ('obs_dtype', C.c_int32), ('obs_stride', C.c_int32),
@@ -207,6 +212,7 @@ SYMBOLS = {
     'dpenv_get_qp_allocator_state': (C.c_int, [_VP, _VP, _VP]),
     'dpenv_set_qp_allocator_state': (C.c_int, [_VP, _VP, _VP]),
     'dpenv_controller_label_qp': (C.c_int, [_VP, C.POINTER(ControllerLabelQpIO), _VP]),
+    'dpenv_controller_label_qp_ex': (C.c_int, [_VP, C.POINTER(ControllerLabelQpExIO), _VP]),
     'dpenv_set_qp_allocator_table': (C.c_int, [_VP, _VP, _I32, _VP, _VP]),
     'dpenv_thrust_alloc_qp_table': (C.c_int, [_VP, _I32, _F, _VP, _VP, _VP, _VP, _VP, _VP, _I32, _VP]),
     'dpenv_train_param_count': (C.c_int64, [C.POINTER(TrainShape)]),

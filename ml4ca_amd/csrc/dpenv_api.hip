@@ -1379,6 +1379,52 @@ extern "C" int dpenv_controller_label_qp(dpenv_handle h, const dpenv_controller_
     return DPENV_OK;
 }
 
+// ... with the thruster state taken from the flown action rows and / or one QP allocator per env, read from the public table by the lanes
+// themselves.  With neither, the call above (its kernels, its launcher).
+extern "C" int dpenv_controller_label_qp_ex(dpenv_handle h, const dpenv_controller_label_qp_ex_io* io, dpenv_stream s)
+{
+    if (!h) return DPENV_EINVAL;
+    DeviceGuard dev_guard(h->device);
+    if (!h->ctrl_on) return fail(h, DPENV_EINVAL, "dpenv_controller_label_qp_ex: the DP controller is off (dpenv_set_dp_controller)");
+    if (!io || io->struct_size != sizeof(dpenv_controller_label_qp_ex_io)) return fail(h, DPENV_EINVAL, "dpenv_controller_label_qp_ex_io ABI mismatch");
+    if (io->T <= 0) return fail(h, DPENV_EINVAL, "dpenv_controller_label_qp_ex: T > 0 is required");
+    if (!io->obs || !io->act) return fail(h, DPENV_EINVAL, "dpenv_controller_label_qp_ex: the obs and act blocks are required");
+    if (io->obs_dtype != DPENV_F32 && io->obs_dtype != DPENV_BF16)
+        return fail(h, DPENV_EINVAL, "dpenv_controller_label_qp_ex: obs_dtype must be DPENV_F32 or DPENV_BF16");
+    if (io->q && io->qp_table) return fail(h, DPENV_EINVAL, "dpenv_controller_label_qp_ex: q or qp_table, not both");
+    if (io->refused_out && !io->qp_table) return fail(h, DPENV_EINVAL, "dpenv_controller_label_qp_ex: refused_out goes with qp_table");
+    QpArgs g = {};
+    if (io->qp_table) {
+        if (io->iterations < 1 || io->iterations > QP_MAX_ITERS) return fail(h, DPENV_EINVAL, "QP allocator: iterations must be in 1..32");
+        if (!std::isfinite(h->ctrl.dt) || !(h->ctrl.dt > 0.0f)) return fail(h, DPENV_EINVAL, "QP allocator: dt must be finite and > 0");
+    } else if (io->q) {
+        if (const char* why = qp_check(io->q, h->ctrl.dt, g)) return fail(h, DPENV_EINVAL, "%s", why);
+    } else if (h->qp_tab_on) {
+        return fail(h, DPENV_EINVAL, "dpenv_controller_label_qp_ex: a per-env QP table (dpenv_set_qp_allocator_table) is in force and the scan "
+                                     "takes the numbers of the call: pass q or qp_table");
+    } else if (h->qp_on) {
+        g = h->qp.q;
+    } else {
+        return fail(h, DPENV_EINVAL, "dpenv_controller_label_qp_ex: no QP allocator (pass q or qp_table, or dpenv_set_qp_allocator first)");
+    }
+    LabelQpArgs la = {};
+    la.obs = io->obs; la.done = io->done; la.z_in = io->z_in; la.z_out = io->z_out; la.x_in = io->x_in; la.x_out = io->x_out;
+    la.act = io->act; la.cost = io->cost;
+    la.T = io->T; la.n = h->cfg.n_envs;
+    const float4* tab = h->ctrl_tab_on ? h->ctrl_tab : nullptr;
+    const int bf16 = io->obs_dtype == DPENV_BF16;
+    hipError_t e;
+    if (!io->flown && !io->qp_table) {
+        e = dev::launch_controller_label_qp(&h->ctrl, &g, &la, tab, bf16, (hipStream_t)s);
+    } else {
+        LabelQpExArgs xa = {};
+        xa.flown = io->flown; xa.qp_table = io->qp_table; xa.refused = io->refused_out; xa.iters = io->iterations;
+        e = dev::launch_controller_label_qp_ex(&h->ctrl, &g, &la, &xa, tab, bf16, (hipStream_t)s);
+    }
+    if (e != hipSuccess) return fail(h, DPENV_EHIP, "QP label launch failed: %s", hipGetErrorString(e));
+    return DPENV_OK;
+}
+
 extern "C" int dpenv_get_state(dpenv_handle h, float* state_out, int32_t* counters_out, dpenv_stream s)
 {
     if (!h) return DPENV_EINVAL;

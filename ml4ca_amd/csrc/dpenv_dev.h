@@ -452,6 +452,14 @@ struct LabelQpArgs {
     float* cost;                // [T][n] the final objective of each row's solve, or NULL
     int T, n;
 };
+// what dpenv_controller_label_qp_ex adds to that scan: the thruster state taken from the FLOWN action rows, and one QP allocator per env
+// read from the public table by the lane itself (qp_lane_from_row)
+struct LabelQpExArgs {
+    const float* flown;         // [T][n][7] the executed actions, or NULL = the expert's own recursion
+    const float* qp_table;      // PUBLIC table float[QP_NPARAM][n], or NULL = QpArgs' shared numbers
+    uint8_t* refused;           // [n] or NULL; with qp_table
+    int32_t iters;              // with qp_table: 1 .. QP_MAX_ITERS
+};
 
 // ---- launchers: called by the host units (dpenv_api.hip, dpenv_api_free.hip), defined by the translation unit that owns the kernels; not exported from libdpenv.so ----
 namespace __attribute__((visibility("hidden"))) dev {
@@ -515,6 +523,9 @@ hipError_t launch_thrust_alloc(const ControlArgs* ca, const float* tau, float* a
 hipError_t launch_controller_label(const ControlArgs* ca, const LabelArgs* la, const float4* tab, int obs_bf16, hipStream_t s);
 // ... with the QP allocation of qa in place of the pseudo-inverse; of ca (or tab) the PID's numbers and dt only
 hipError_t launch_controller_label_qp(const ControlArgs* ca, const QpArgs* qa, const LabelQpArgs* la, const float4* tab, int obs_bf16, hipStream_t s);
+// ... with xa's flown rows and / or per-env QP table (at least one of the two; qa is not read with a table)
+hipError_t launch_controller_label_qp_ex(const ControlArgs* ca, const QpArgs* qa, const LabelQpArgs* la, const LabelQpExArgs* xa, const float4* tab,
+                                         int obs_bf16, hipStream_t s);
 // dpenv_control.hip: one control step of the QP allocation for n envs, one lane per env
 hipError_t launch_qp_alloc(const QpArgs* qa, const QpAllocIO* io, hipStream_t s);
 // the zeroing of the closed loop's QP thruster state for the envs of mask (NULL = every env)

@@ -190,6 +190,30 @@ __device__ __forceinline__ void qp_allocate(const Q& q, const float tau[3], floa
     J_out = p.J;
 }
 
+// S(q, a) of include/dpenv.h (dpenv_controller_label_qp_ex): the thruster state an EXECUTED action row of the final variant's
+// continuous-angle form leaves - the env's own command decode (env_decode_cmd<MODE_FINAL_CONT>: thrust percent, clipped azimuths), then
+// the QP's thrust law F = K n |n| brought inside the law's precondition |F| <= f_max, the azimuths wrapped as qp_allocate wraps its state.
+// A component fed by an action entry that is not finite (or that comes out not finite) is 0: thrusters at rest.  The ONLY statement of S
+// on the device; deploy.qp_state_from_action is the host statement.
+template <class Q>
+__device__ __forceinline__ void qp_state_from_action(const Q& q, const float a[7], float x[5])
+{
+    float ang[3], thr[3];
+    env_decode_cmd<MODE_FINAL_CONT>(ang, a, thr);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const float K = thr[k] >= 0.0f ? q.kf[k] : q.kr[k];
+        float F = (K * thr[k]) * fabsf(thr[k]);
+        F = fminf(fmaxf(F, -q.fmax[k]), q.fmax[k]);
+        x[k] = (isfinite(a[k]) && isfinite(F)) ? F : 0.0f;
+    }
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+        const float al = wrap_angle(ang[1 + i], false);
+        x[3 + i] = (isfinite(a[3 + 2 * i]) && isfinite(a[4 + 2 * i]) && isfinite(al)) ? al : 0.0f;
+    }
+}
+
 // ---- one QP allocator per env (dpenv_set_qp_allocator_table, dpenv_thrust_alloc_qp_table): QpLane (dpenv_dev.h) holds an env's numbers in
 // registers and qp_allocate<QpLane> above is the law, unedited ----
 

@@ -615,6 +615,84 @@ def qp_weight_population(K, base=None, span=4.0, seed=0, what=('w_power', 'w_dal
     return pop
 
 
+def _qp_wrap(a, dtype):
+    """[-pi, pi) in dtype: a - 2 pi floor((a + pi) / (2 pi)), the last step one fused multiply-add (formed in float64 and rounded once)."""
+    dtype = np.dtype(dtype)
+    t = dtype.type
+    pi = t(np.float32(np.pi)) if dtype == np.dtype(np.float32) else t(np.pi)
+    k = np.floor((a + pi) * (t(0.5) / pi))
+    return (np.asarray(a, np.float64) - np.asarray(k, np.float64) * np.float64(t(2.0) * pi)).astype(dtype)
+
+
+def _qp_state(kf, kr, fmax, act, dtype):
+    """S of include/dpenv.h on act [n, 7] with kf, kr, fmax [3] or [n, 3] already in dtype: x [n, 5]."""
+    dtype = np.dtype(dtype)
+    t = dtype.type
+    a = np.asarray(act).astype(dtype)
+    pi = t(np.float32(np.pi)) if dtype == np.dtype(np.float32) else t(np.pi)
+    with np.errstate(all='ignore'):
+        n3 = a[:, 0:3]
+        thr = np.fmin(np.fmax(n3 * t(100.0), -t(100.0)), t(100.0))
+        K = np.where(thr >= 0, kf, kr)
+        F = (K * thr) * np.abs(thr)
+        F = np.fmin(np.fmax(F, -fmax), fmax)
+        F = np.where(np.isfinite(n3) & np.isfinite(F), F, t(0.0))
+        s, c = a[:, 3:7:2], a[:, 4:7:2]
+        al = np.arctan2(s, c).astype(dtype)
+        al = _qp_wrap(np.fmin(np.fmax(al, -pi), pi), dtype)
+        al = np.where(np.isfinite(s) & np.isfinite(c) & np.isfinite(al), al, t(0.0))
+    return np.concatenate([F, al], 1).astype(dtype)
+
+
+def qp_state_from_action(params_or_table, act, dtype=None):
+    """S(q, a) of include/dpenv.h (dpenv_controller_label_qp_ex): the thruster state x [n, 5] = F_bow, F_port, F_star, a_port, a_star that
+    the EXECUTED action rows act [n, 7] of the final variant's continuous-angle form leave - the env's command decode (thrust percent
+    clipped to +-100, azimuth = arctan2 of the heads clipped to +-pi), the QP's thrust law F = K n |n| clipped to +-f_max, the azimuths
+    wrapped to [-pi, pi).  A component fed by an entry that is not finite is 0.  params_or_table: the dict of qp_allocator_defaults (None =
+    the defaults; entries may carry a leading n) or a public table [32, n]; of it kf, kr and f_max are read.  dtype float32 (the default)
+    is the kernel's arithmetic except for the arctangent (np.arctan2 here, the kernel's own polynomial there: the forces agree in bits);
+    float64 is the form for checks."""
+    p = qp_allocator_defaults() if params_or_table is None else params_or_table
+    if not isinstance(p, dict):
+        p = qp_allocator_table_params(p.detach().cpu().numpy() if hasattr(p, 'detach') else p)
+    dtype = np.dtype(np.float32 if dtype is None else dtype)
+    act = np.asarray(act)
+    if act.ndim != 2 or act.shape[1] != 7:
+        raise ValueError('qp_state_from_action: act is [n, 7]')
+    kf, kr, fmax = (np.asarray(p[k], np.float64).astype(dtype) for k in ('kf', 'kr', 'f_max'))
+    for v in (kf, kr, fmax):
+        if v.shape not in ((3,), (act.shape[0], 3)):
+            raise ValueError('qp_state_from_action: kf, kr and f_max are [3] or [n, 3]')
+    return _qp_state(kf, kr, fmax, act, dtype)
+
+
+# the REST allocator a refused row of a per-env QP table is replaced by (include/dpenv.h): zero thrust, azimuths held, every output finite
+QP_REST = dict(w_slack=0.0, w_power=0.0, w_dalpha=1.0, w_dforce=1.0, f_max=0.0, force_rate=0.0, azimuth_rate=0.0, lx=0.0, ly=0.0, kf=1.0, kr=1.0)
+
+
+def qp_table_refused(table, dt):
+    """The mask [n] (bool) of the rows of a public QP table [32, n] the library refuses - the byte dpenv_thrust_alloc_qp_table,
+    dpenv_set_qp_allocator_table and dpenv_controller_label_qp_ex set in refused_out: a number that is not finite, a weight < 0, w_dalpha
+    or w_dforce <= 0, a bound or rate < 0, kf or kr <= 0, or a dF = force_rate * dt / da = azimuth_rate * dt (one float32 product each)
+    that is not finite.  Slots 26-31 are not read."""
+    tab = np.asarray(table.detach().cpu().numpy() if hasattr(table, 'detach') else table, np.float32)
+    if tab.ndim != 2 or tab.shape[0] != QP_NPARAM:
+        raise ValueError('qp_table_refused: a [32, n] table')
+    dt = np.float32(dt)
+    ok = np.isfinite(tab[0:26]).all(0)
+    with np.errstate(all='ignore'):
+        for name in ('w_slack', 'w_power', 'f_max', 'force_rate', 'azimuth_rate'):
+            first, width = QP_SLOTS[name]
+            ok &= (tab[first:first + width] >= 0).all(0)
+        for name in ('w_dalpha', 'w_dforce', 'kf', 'kr'):
+            first, width = QP_SLOTS[name]
+            ok &= (tab[first:first + width] > 0).all(0)
+        for name in ('force_rate', 'azimuth_rate'):
+            first, width = QP_SLOTS[name]
+            ok &= np.isfinite(tab[first:first + width] * dt).all(0)
+    return ~ok
+
+
 class BatchedQPAllocator(object):
     """The rate-limited QP thrust allocation for n envs on the host: the statement of include/dpenv.h (dpenv_thrust_alloc_qp), operation
     by operation, in batched NumPy.  dtype float32 (the default) is the kernel's arithmetic except for sin / cos (np.sin / np.cos here, the
@@ -774,10 +852,7 @@ class BatchedQPAllocator(object):
 
     def wrap(self, a):
         """[-pi, pi): a - 2 pi floor((a + pi) / (2 pi)), the last step one fused multiply-add (exact here in float64)."""
-        t = self.dtype.type
-        pi = t(np.float32(np.pi)) if self.dtype == np.dtype(np.float32) else t(np.pi)
-        k = np.floor((a + pi) * (t(0.5) / pi))
-        return (np.asarray(a, np.float64) - np.asarray(k, np.float64) * np.float64(t(2.0) * pi)).astype(self.dtype)
+        return _qp_wrap(a, self.dtype)
 
     def allocate(self, tau):
         tau = np.asarray(tau, self.dtype)
@@ -797,7 +872,7 @@ class BatchedQPAllocator(object):
             self.x[mask] = 0
 
 
-def label_rows_qp(params_or_table, qp_params, obs, done=None, z=None, x=None, dt=0.2, dtype=None):
+def label_rows_qp(params_or_table, qp_params, obs, done=None, z=None, x=None, dt=0.2, dtype=None, flown=None, iterations=None):
     """The PID + rate-limited QP chain's actions on a block of observation rows some other flight wrote - the host statement of
     dpenv_controller_label_qp (policy.controller_label_qp), NumPy on the CPU.  obs, done and z as label_rows takes them; x [5, n] the
     thruster state each env starts from (get_qp_allocator_state's layout) or None = 0.  Per row t, in this order:
@@ -806,7 +881,12 @@ def label_rows_qp(params_or_table, qp_params, obs, done=None, z=None, x=None, dt
     dp_controller_defaults (None = the defaults) or a public table [32, n]; qp_params: the dict of qp_allocator_defaults (None = the
     defaults); dt the control period.  Returns (act [T, n, 7], z [3, n], x [5, n]) in dtype (None = float32: the kernel's arithmetic
     except for its own sin / cos polynomial, as BatchedQPAllocator says; float64 is the form for checks); labelling rows [0:k] and [k:T]
-    with z and x handed over equals one call."""
+    with z and x handed over equals one call.
+    flown [T, n, 7] (dpenv_controller_label_qp_ex): the actions that were EXECUTED on these rows.  Row t is then solved from the thruster
+    state the executed row t - 1 left, qp_state_from_action(flown[t - 1]), instead of the expert's own recursion - after the allocation
+    of row t, qp.x = S(flown[t]), then the resets; the label of row t does not depend on flown[t:], and x out is the last such state.
+    qp_params may be a public QP table [32, n] (env i labelled with row i, in `iterations` solver steps, None = 16): rows the library
+    refuses (qp_table_refused) run the rest allocator here too - zero thrust, azimuths held."""
     obs = np.asarray(obs)
     if obs.ndim != 3 or obs.shape[2] < 6:
         raise ValueError('label_rows_qp: obs is [T, n, >= 6]')
@@ -815,6 +895,20 @@ def label_rows_qp(params_or_table, qp_params, obs, done=None, z=None, x=None, dt
         done = np.asarray(done)
         if done.shape != (T, n):
             raise ValueError('label_rows_qp: done is [T, n]')
+    if flown is not None:
+        flown = np.asarray(flown)
+        if flown.shape != (T, n, 7):
+            raise ValueError('label_rows_qp: flown is [T, n, 7]')
+    if qp_params is not None and not isinstance(qp_params, dict):                      # a public table: refused rows fly the rest allocator
+        tab = np.array(qp_params.detach().cpu().numpy() if hasattr(qp_params, 'detach') else qp_params, np.float32)
+        if tab.shape != (QP_NPARAM, n):
+            raise ValueError('label_rows_qp: a QP table is [32, n]')
+        bad = qp_table_refused(tab, dt)
+        for name, (first, width) in QP_SLOTS.items():
+            tab[first:first + width, bad] = QP_REST[name]
+        qp_params = qp_allocator_table_params(tab, 16 if iterations is None else iterations)
+    elif iterations is not None:
+        raise ValueError('label_rows_qp: iterations goes with a QP table (the dict carries its own)')
     ctrl = BatchedDPController(n, params_or_table, dt=dt, dtype=dtype)
     qp = BatchedQPAllocator(n, qp_params, dt=dt, dtype=dtype)
     if z is not None:
@@ -830,6 +924,8 @@ def label_rows_qp(params_or_table, qp_params, obs, done=None, z=None, x=None, dt
     act = np.empty((T, n, 7), ctrl.dtype)
     for t in range(T):
         act[t] = qp.allocate(ctrl.wrench(obs[t]))
+        if flown is not None:                                                          # the law's own advance of x is dropped
+            qp.x = _qp_state(qp.kf, qp.kr, qp.fmax, flown[t], qp.dtype)
         if done is not None:
             ctrl.reset(done[t] != 0)
             qp.reset(done[t] != 0)

@@ -384,7 +384,8 @@ def qp_allocator_struct(params=None):
     return q
 
 
-def controller_label_qp(env, obs, done=None, z=None, x=None, params=None, out=None, cost=False):
+def controller_label_qp(env, obs, done=None, z=None, x=None, params=None, out=None, cost=False, flown=None, table=None, iterations=None,
+                        refused=None):
     """The PID + rate-limited QP chain's actions on a block of rows some OTHER flight wrote (dpenv_controller_label_qp), in one launch:
     controller_label with the QP law in place of the pseudo-inverse - the low-energy expert's labels for the states an actor visited.
     obs [T, n, 9] float32 or bfloat16, done [T, n] uint8 or None, z [3, n] float32 or None = 0 as controller_label takes them; x [5, n]
@@ -396,10 +397,20 @@ def controller_label_qp(env, obs, done=None, z=None, x=None, params=None, out=No
     cost=True, the final objective of every row's solve [T, n] as a fourth value; out = (act, z, x) supplies the buffers (z and x may
     be the input tensors themselves).  Nothing of the env changes: not its state, not its own z or thruster state, not a counter.  For
     float32 rows of controller_rollout with the QP set and auto-reset on the labels are that launch's act rows bit for bit.
-    deploy.label_rows_qp is the host statement."""
+    deploy.label_rows_qp is the host statement.
+    flown [T, n, 7] float32 (dpenv_controller_label_qp_ex): the actions that were EXECUTED on these rows - a policy_rollout's out['act'].
+    Row t is then solved from the thruster state the executed row t - 1 left (deploy.qp_state_from_action) instead of the expert's own
+    recursion; the x returned is the state the last executed row left, to hand to the next block.  table: a float32 device tensor [32, n]
+    (deploy.qp_allocator_table) - env i is labelled with row i, in `iterations` solver steps (None = 16); giving params too is an error.
+    Each lane checks its own row: a refused one runs the rest allocator (zero thrust, azimuths held), reports a NaN objective and sets
+    its byte of refused (a uint8 tensor [n], or None).  With neither flown nor table the call is dpenv_controller_label_qp itself."""
     torch = _torch()
     n, ad = env.n_envs, env.num_actions
     dev, f32 = env.device, torch.float32
+    if table is not None and params is not None:
+        raise ValueError('controller_label_qp: params or table, not both')
+    if table is None and (iterations is not None or refused is not None):
+        raise ValueError('controller_label_qp: iterations and refused go with table (params carries its own iterations)')
     if not isinstance(obs, torch.Tensor) or obs.dim() != 3:
         raise ValueError('controller_label_qp: obs is a tensor [T, n, 9]')
     if obs.dtype not in (torch.float32, torch.bfloat16):
@@ -418,8 +429,13 @@ def controller_label_qp(env, obs, done=None, z=None, x=None, params=None, out=No
     env._chk(x_out, (5, n), f32, 'out[2]')
     J = torch.empty((T, n), dtype=f32, device=dev) if cost else None
     q = qp_allocator_struct(params) if params is not None else None
-    io = _lib.ControllerLabelQpIO()
-    io.struct_size = C.sizeof(_lib.ControllerLabelQpIO)
+    ex = flown is not None or table is not None
+    if ex:
+        env._chk(flown, (T, n, 7), f32, 'flown')
+        env._chk(table, (32, n), f32, 'table')
+        env._chk(refused, (n,), torch.uint8, 'refused')
+    io = _lib.ControllerLabelQpExIO() if ex else _lib.ControllerLabelQpIO()
+    io.struct_size = C.sizeof(io)
     io.T = T
     io.obs = obs.data_ptr()
     io.obs_dtype = 1 if obs.dtype == torch.bfloat16 else 0
@@ -429,6 +445,13 @@ def controller_label_qp(env, obs, done=None, z=None, x=None, params=None, out=No
     io.z_out, io.x_out, io.act = z_out.data_ptr(), x_out.data_ptr(), act.data_ptr()
     io.cost = J.data_ptr() if cost else None
     io.q = C.pointer(q) if q is not None else None
+    if ex:
+        io.flown = flown.data_ptr() if flown is not None else None
+        io.qp_table = table.data_ptr() if table is not None else None
+        io.iterations = (16 if iterations is None else int(iterations)) if table is not None else 0
+        io.refused_out = refused.data_ptr() if refused is not None else None
+        _lib.check(env.lib.dpenv_controller_label_qp_ex(env._h, C.byref(io), env._stream()), env._h)
+        return (act, z_out, x_out, J) if cost else (act, z_out, x_out)
     _lib.check(env.lib.dpenv_controller_label_qp(env._h, C.byref(io), env._stream()), env._h)
     return (act, z_out, x_out, J) if cost else (act, z_out, x_out)
 

@@ -435,7 +435,7 @@ class PPOUpdater(object):
 
     # ---- DAgger: expert labels on the states the ACTOR visits, aggregated over rounds (Ross et al. 2011) ----
     def dagger(self, env, rounds, T, iters, minibatch=None, loss='mse', keep=None, sample=False, reset_at_end=False, lr=None, average=None,
-               upload=None, expert='pinv', qp_params=None):
+               upload=None, expert='pinv', qp_params=None, thruster_state='own', qp_table=None):
         """`rounds` x (fly the actor, label its states with the baseline DP controller, aggregate, refit).  env: a float32-row env with
         the baseline on (env.set_dp_controller; a table of set_dp_controller_table in force is the one that labels).  Per round:
           1. ac.upload(env, **upload)                       (upload: keyword arguments of ActorCritic.upload, e.g. dict(precision='f32'))
@@ -459,6 +459,13 @@ class PPOUpdater(object):
         env.set_qp_allocator has in force, else the defaults of the DEFAULT hull, as evaluate.baseline_box_test takes them.  The env need
         not be able to fly the QP: per-env hulls (randomised ones too) and a controller table label like any other.  x is the expert's own
         recursion, not the thruster state the actor's actions would have left.
+        thruster_state (expert='qp'): 'own' (the default: the recursion above, bit for bit the driver without this keyword) or 'flown':
+        the round's out['act'] goes to controller_label_qp(flown=...), so row t is labelled from the thruster state the actor's executed
+        action of row t - 1 left (dpenv_controller_label_qp_ex) - the expert's answer in the state the learner is in.  The thrust part
+        of that state is a function of the observation's lagged thrust columns, which the actor sees.  x, the state the last executed
+        row left, is handed from round to round and zeroed by reset_at_end.  qp_table (expert='qp'): a float32 device tensor [32, n]
+        (deploy.qp_allocator_table), env i labelled with row i in qp_params['iterations'] solver steps (16 without qp_params) - one
+        expert per env; the scalar numbers are then not read.
         Not here: beta-mixed flights in which the expert executes some of the steps, an integral-augmented actor, bf16 rows (the gradient
         kernels take float32 rows: a bf16 env raises ValueError)."""
         torch = _torch()
@@ -468,6 +475,10 @@ class PPOUpdater(object):
             raise ValueError('dagger: rounds, T and iters are >= 1')
         if expert not in ('pinv', 'qp'):
             raise ValueError("dagger: expert is 'pinv' or 'qp', not %r" % (expert,))
+        if thruster_state not in ('own', 'flown'):
+            raise ValueError("dagger: thruster_state is 'own' or 'flown', not %r" % (thruster_state,))
+        if expert != 'qp' and (thruster_state != 'own' or qp_table is not None):
+            raise ValueError("dagger: thruster_state and qp_table go with expert='qp' (the pseudo-inverse has no thruster state)")
         if env.obs_torch_dtype != torch.float32:
             raise ValueError('dagger: the gradient kernels take float32 rows; make the env with float32 obs rows (got %s)' % (env.obs_torch_dtype,))
         if env.dp_controller is None:
@@ -494,8 +505,10 @@ class PPOUpdater(object):
             out = policy_rollout(env, T, out=out, sample=sample, reset_at_end=reset_at_end)
             slot = r % keep
             labels = data_act[slot * R:(slot + 1) * R].view(T, n, ad)
-            if expert == 'qp':
-                controller_label_qp(env, out['obs'], out['done'], z=z, x=x, params=qp, out=(labels, z, x))
+            if expert == 'qp':                                         # neither flown nor a table: the call of the driver before them
+                controller_label_qp(env, out['obs'], out['done'], z=z, x=x, params=qp if qp_table is None else None, out=(labels, z, x),
+                                    flown=out['act'] if thruster_state == 'flown' else None, table=qp_table,
+                                    iterations=int(qp['iterations']) if qp_table is not None else None)
                 if reset_at_end:
                     x.zero_()
             else:

@@ -821,6 +821,13 @@ int dpenv_thrust_alloc(const dpenv_dp_controller* c, const float* tau, float* ac
  * with K_i = F_i >= 0 ? kf_i : kr_i (:287-288) and the heads taken once more, of the un-wrapped a.  If any component of tau is not finite
  * the env's state is left bit for bit what it was and the action is that state's - the node's rule for a failed solve (:267-269); no
  * other env is affected.  cost_out gets the final J (NaN for such an env).
+ * AT THE EDGES of the numbers (tests/qp_edges.py flies them).  A finite tau so large that the f32 J of the start is not finite (|tau_j|
+ * from about 1e19 / sqrt(w_slack_j); +inf, or NaN = 0 * inf where w_slack_j = 0): every trial's J is not finite either, J(x_t) < J(x) is
+ * false each time, so the env holds its clipped start - state_out is that start with the azimuths wrapped, the action is finite - and
+ * cost_out gets that J, which is NOT finite although tau is.  Azimuths beyond 3e4 rad in magnitude, where sincos folds in f32 first: the
+ * heads are a valid rotation of about that angle, not one within 9.2e-8 of it.  A thruster with f_max_i = 0 or dF_i = 0 whose F_i^- is
+ * -0.0 has lo_i = -0.0 and hi_i = +0.0: the sign of the zero that clip returns there is not specified; everywhere else a force of -0.0
+ * that stays is -0.0 and commands n_i = -0.0.  With every f_max_i = 0 the forces stay 0 and with every rate 0 nothing moves, whatever tau.
  * ml4ca_amd.deploy.BatchedQPAllocator is the host statement of the law. */
 typedef struct dpenv_qp_allocator {
     uint32_t struct_size;

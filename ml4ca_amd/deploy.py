@@ -765,8 +765,11 @@ class BatchedQPAllocator(object):
         x, tau, prev = (np.asarray(v, self.dtype) for v in (x, tau, prev))
         return self._objective(x, self._residual(x, tau)[3], prev)
 
-    def solve(self, tau, prev):
-        """The K iterations from the state prev on tau: (x [n, 5] un-wrapped, J [K + 1, n])."""
+    def solve(self, tau, prev, trace=None):
+        """The K iterations from the state prev on tau: (x [n, 5] un-wrapped, J [K + 1, n]).  trace: a dict that receives what the
+        iterations computed on their way, one entry per iteration - 'trial_J' [K, n] (J of x_t, step 7), 'accept' [K, n] (step 8),
+        'frozen' [K, n, 5] (step 5) and 'g' [K, n, 5] (the gradient of step 2, before the frozen entries are zeroed).  Nothing of the
+        solve depends on it."""
         t = self.dtype.type
         tau, prev = np.asarray(tau, self.dtype), np.asarray(prev, self.dtype)
         n = prev.shape[0]
@@ -776,6 +779,8 @@ class BatchedQPAllocator(object):
         J = self._objective(x, r, prev)
         lam = np.zeros(n, self.dtype)
         hist = [J]
+        if trace is not None:
+            trace.update(trial_J=[], accept=[], frozen=[], g=[])
         zero, one = np.zeros(n, self.dtype), np.ones(n, self.dtype)
         with np.errstate(all='ignore'):
             for _ in range(self.iterations):
@@ -802,6 +807,9 @@ class BatchedQPAllocator(object):
                 for k in range(5):
                     H[k][k] = H[k][k] + lam * H[k][k]
                     fr.append(((x[:, k] <= lo[:, k]) & (g[k] > 0)) | ((x[:, k] >= hi[:, k]) & (g[k] < 0)))
+                if trace is not None:
+                    trace['frozen'].append(np.stack(fr, 1))
+                    trace['g'].append(np.stack(g, 1))
                 for k in range(5):
                     g[k] = np.where(fr[k], zero, g[k])
                     H[k][k] = np.where(fr[k], one, H[k][k])
@@ -836,11 +844,17 @@ class BatchedQPAllocator(object):
                 st, ct, b3t, rt = self._residual(xt, tau)
                 Jt = self._objective(xt, rt, prev)
                 acc = Jt < J
+                if trace is not None:
+                    trace['trial_J'].append(Jt)
+                    trace['accept'].append(acc)
                 a1 = acc[:, None]
                 x, s, c, b3, r = np.where(a1, xt, x), np.where(a1, st, s), np.where(a1, ct, c), np.where(a1, b3t, b3), np.where(a1, rt, r)
                 J = np.where(acc, Jt, J)
                 lam = np.where(acc, t(0.25) * lam, t(8.0) * np.fmax(lam, t(0.125)))
                 hist.append(J)
+        if trace is not None:
+            for k in ('trial_J', 'accept', 'frozen', 'g'):
+                trace[k] = np.stack(trace[k])
         return x, np.stack(hist)
 
     def thrust_columns(self, F):

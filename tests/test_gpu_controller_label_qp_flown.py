@@ -161,17 +161,21 @@ def test_state_from_action_on_the_device_against_the_host_statement():
     """x_out of a one-row call without a done byte is S(flown[0]).  Forces: the float32 host statement in bits (the same operations in
     the same order, no transcendental).  Azimuths: within 1e-6 rad on the circle of the float64 statement (atan2_lean's stated 2.6e-7 and
     two roundings at pi).  Entries that are not finite give 0, and labels from such states are finite."""
+    state_from_action_against_the_host_statement(_params(K))
+
+
+def state_from_action_against_the_host_statement(p):
+    """The check of the test above for the QP numbers p (tests/test_gpu_qp_edges.py runs it on its asymmetric set)."""
     from ml4ca_amd.deploy import BatchedQPAllocator, qp_state_from_action
     from ml4ca_amd.policy import controller_label_qp
     torch = torch_()
     n = 130
     env = _start(_env(n), qp=False, nudge=False)
-    p = _params(K)
     rng = np.random.RandomState(7)
     a = rng.uniform(-1.3, 1.3, (TL, n, 7)).astype(np.float32)
     a[0, :, 3:7] *= rng.uniform(0.01, 30.0, (n, 1)).astype(np.float32)                 # heads of any length
     qp = BatchedQPAllocator(n, p, dt=env.control_period)
-    xr = (rng.uniform(-1, 1, (n, 5)) * np.array([9, 20.5, 20.5, 3.14, 3.14])).astype(np.float32)
+    xr = (rng.uniform(-1, 1, (n, 5)) * np.concatenate([np.asarray(p['f_max'], np.float64), [3.14, 3.14]])).astype(np.float32)
     s, c = np.sin(xr[:, 3:5]), np.cos(xr[:, 3:5])
     a[1] = np.concatenate([qp.thrust_columns(xr[:, 0:3]), np.stack([s[:, 0], c[:, 0], s[:, 1], c[:, 1]], 1)], 1)   # the law's own rows
     a[2, :, 0:3] = np.sign(a[2, :, 0:3]) * 1.5

@@ -122,6 +122,20 @@ def wrap32(v):
     return (v.astype(np.float64) - k.astype(np.float64) * np.float64(np.float32(2.0) * pi)).astype(np.float32)
 
 
+def wrapped_from_the_box(a, l, h, turns=1, k0=0.0):
+    """Where some float32 x inside [l, h] wraps to a bit for bit: searched two ulps either side of a + 2 pi k, k = k0 - turns .. k0 + turns
+    (k0 a number or an array of a's shape: the turn the box lies in)."""
+    found = np.zeros(a.shape, bool)
+    for k in range(-int(turns), int(turns) + 1):
+        c = (a.astype(np.float64) + (k0 + np.float64(k)) * np.float64(np.float32(2.0) * np.float32(np.pi))).astype(np.float32)
+        for d in range(-2, 3):
+            x = c.copy()
+            for _ in range(abs(d)):
+                x = np.nextafter(x, np.float32(np.inf if d > 0 else -np.inf))
+            found |= (l <= x) & (x <= h) & (wrap32(x).view(np.uint32) == a.view(np.uint32))
+    return found
+
+
 def thrust_columns_f32(F, p):
     """clip(copysign(sqrt(|F| / K), F) / 100, -1, 1) in NumPy float32, K forward or reverse by the sign of F."""
     kf, kr = np.asarray(p['kf'], np.float32), np.asarray(p['kr'], np.float32)
@@ -148,15 +162,7 @@ def test_exact_properties_on_the_devices_own_state(n, K):
     # ... and on the other rows, whose box reaches past +-pi: some float32 x inside [lo, hi] wraps to state_out bit for bit (searched two
     # ulps either side of state_out + 2 pi k, k = -1, 0, 1)
     rest = ~plain
-    a, l, h = state[rest][:, 3:5], lo[rest][:, 3:5], hi[rest][:, 3:5]
-    found = np.zeros(a.shape, bool)
-    for k in (-1.0, 0.0, 1.0):
-        c = (a.astype(np.float64) + k * np.float64(np.float32(2.0) * np.float32(np.pi))).astype(np.float32)
-        for d in range(-2, 3):
-            x = c.copy()
-            for _ in range(abs(d)):
-                x = np.nextafter(x, np.float32(np.inf if d > 0 else -np.inf))
-            found |= (l <= x) & (x <= h) & (wrap32(x).view(np.uint32) == a.view(np.uint32))
+    found = wrapped_from_the_box(state[rest][:, 3:5], lo[rest][:, 3:5], hi[rest][:, 3:5])
     assert found.all(), int((~found).sum())
     if n >= 63:                                              # every bound was met exactly, from below and from above
         assert ((state == lo) & plain[..., None]).any(axis=(0, 1)).all() and ((state == hi) & plain[..., None]).any(axis=(0, 1)).all()

@@ -24,6 +24,8 @@ env.step, critic, trajectory rows), GAE by one scan kernel, advantage statistics
                                                                                       runs on its own hull, +-15 % on all 26 parameters, re-drawn by the reset path
                                                                                       inside the rollout launch; --eval: the reference's evaluation harness
                                                                                       (test_policy.py:97-186) and the box test (IAE, energy) on the NOMINAL hull
+    python examples/train_ppo.py --envs 4096 --epochs 30 --eval --nn-allocator 5000   ... with the supervised neural allocator (src/sl) fitted and flown
+                                                                                      behind the baseline's PID beside the pseudo-inverse and the QP
 """
 import argparse
 import os
@@ -39,7 +41,7 @@ from ml4ca_amd import rollout
 from ml4ca_amd.policy import ActorCritic
 
 
-def evaluate_actor(ac, dev, preset, precision, seed, out=print, eval_envs=1024, only=None):
+def evaluate_actor(ac, dev, preset, precision, seed, out=print, eval_envs=1024, only=None, nn_net=None):
     """The trained actor on the NOMINAL hull (and on a spread of hulls): the reference's run_RL_policy (spinup/utils/test_policy.py:97-186: six
     fixed starts, deterministic policy) and the thesis' 4-corner box test with its two metrics - IAE (results/all_plots/common.py:60-74) and
     the energy-equivalent work of the thruster power model (box_test/plot_act.py:128-135,184-211)."""
@@ -79,6 +81,16 @@ def evaluate_actor(ac, dev, preset, precision, seed, out=print, eval_envs=1024, 
             out('eval  box test (1250 steps, %d envs), %-13s: baseline PID + pseudo-inverse IAE %.2f (worst env %.2f)  work bow/port/star %s' % (
                 nb, tag, float(sb['iae'].mean()), float(sb['iae'].max()), [round(float(x), 1) for x in sb['work'].mean(0)]))
             rb = {'IAE': float(sb['iae'].mean()), 'IAE_worst': float(sb['iae'].max()), 'work': [float(x) for x in sb['work'].mean(0)]}
+            if nn_net is not None:
+                # the supervised contender (--nn-allocator): the same PID with the fitted network in place of the pseudo-inverse; it touches
+                # no hull, so it flies the spreads of hulls too - on a handle made the same way, which draws the same hulls and currents
+                envn = make_env()
+                envn.set_dp_controller(dp_controller_defaults(nominal))
+                sn = EV.baseline_box_test_streamed(envn, T=T, start=torch.zeros((3, nb), device=dev), chunk=50, allocator='nn', net=nn_net)
+                out('eval  box test (1250 steps, %d envs), %-13s: baseline PID + neural allocation IAE %.2f (worst env %.2f)  work bow/port/star %s' % (
+                    nb, tag, float(sn['iae'].mean()), float(sn['iae'].max()), [round(float(x), 1) for x in sn['work'].mean(0)]))
+                rb['nn'] = {'IAE': float(sn['iae'].mean()), 'IAE_worst': float(sn['iae'].max()), 'work': [float(x) for x in sn['work'].mean(0)]}
+                del envn
             if spread > 0:
                 return rb                                                  # (the QP allocation flies the shared hull only: no per-env hull blocks)
             # the thesis' third contender: the same PID with the rate-limited QP allocation in place of the pseudo-inverse
@@ -344,6 +356,9 @@ def main():
                     'flight (per-env controller table): the default baseline, the IAE / work front, the best set, and the best at no more than the actor\'s work')
     ap.add_argument('--tune-qp', type=int, default=0, metavar='K', help='with --eval: a scored sweep of K QP weight sets (w_power, w_dalpha, w_dforce) x 16 current '
                     'directions in one flight (per-env QP table): the default QP and its IAE / work front, to read beside --tune-baseline\'s')
+    ap.add_argument('--nn-allocator', type=int, default=0, metavar='ITERS', help='with --eval: fit the supervised neural allocator (9-80-80-80-6, '
+                    'train.fit_nn_allocator: ITERS Adam steps on 16 384 rows of deploy.nn_allocator_dataset for the preset\'s hull) and fly it behind the '
+                    'baseline\'s PID on every box test, beside the pseudo-inverse and the QP')
     ap.add_argument('--eval-envs', type=int, default=1024, help='envs per --eval box test; 1024 (the default) scores the resident rows as before, any other '
                                                                 'value flies the test in 50-step launches scored on the device (evaluate.ScoreCard), e.g. 65536')
     ap.add_argument('--eval-presets', default='', help="comma-separated presets to run --eval on (default: the training preset), e.g. 'no_loss,thrust_loss': "
@@ -480,7 +495,14 @@ def main():
         if args.eval:
             for pz in (args.eval_presets.split(',') if args.eval_presets else [args.preset]):
                 print('eval on the %s preset (trained on %s%s)' % (pz, args.preset, ', hulls re-drawn +-%g %%' % (100 * args.randomise) if args.randomise > 0 else ''))
-                evaluate_actor(ac, dev, pz, 'f32', args.seed, eval_envs=args.eval_envs)
+                nn_net = None
+                if args.nn_allocator > 0:
+                    from ml4ca_amd.deploy import nn_allocator_dataset
+                    from ml4ca_amd.train import fit_nn_allocator
+                    nn_net = fit_nn_allocator(nn_allocator_dataset(16384, args.seed, vessel=ml4ca_amd.default_vessel(pz)), iters=args.nn_allocator,
+                                              seed=args.seed, device=dev)
+                    print('eval  neural allocator fitted in %d Adam steps: MSE %.4g -> %.4g' % (args.nn_allocator, nn_net['mse_initial'], nn_net['mse_final']))
+                evaluate_actor(ac, dev, pz, 'f32', args.seed, eval_envs=args.eval_envs, nn_net=nn_net)
                 if args.tune_baseline > 0:
                     tune_baseline(ac, dev, pz, 'f32', args.tune_baseline, seed=args.seed)
                 if args.tune_qp > 0:

@@ -916,6 +916,68 @@ int dpenv_set_qp_allocator_table(dpenv_handle h, const float* table, int32_t ite
  * outside 1..32, dt not finite or <= 0.  Stream-ordered, no allocation, no host synchronisation: graph-capturable, one kernel node. */
 int dpenv_thrust_alloc_qp_table(const float* table, int32_t iterations, float dt, const float* tau, const float* state_in,
                                 float* state_out, float* action_out, float* cost_out, uint8_t* refused_out, int32_t n, dpenv_stream s);
+/* ---- the neural thrust allocation: the supervised contender (additive to ABI 6) ---------------------------------------------------------
+ * The reference's first allocator, the supervised feed-forward network of src/sl (FFNN.py / train.py fit a 9-20-20-20-20-6 relu network
+ * to SupervisedTau.py's dataset tau = B(alpha) F(u); ROS/neural_allocator/src/neural_allocator.py flies it behind the DP controller's
+ * wrench), as a handle-free, STATELESS map on the device and as the allocation stage of the baseline's closed loop.  The network is a
+ * dpenv_mlp: sizes[0] inputs (9: the node's six lever-arm constants and the scaled wrench; 3: the scaled wrench alone), n_layers - 1
+ * hidden layers of one width, six outputs.  Per env and control step, in f32, in exactly this order (-ffp-contract=off; the only fused
+ * operations are the fmaf written below):
+ *     input       x_{6+j} = tau_j * tau_scale_j, j = 0..2 (one product each), behind x_0..5 = in_const when sizes[0] == 9; x_j = tau_j *
+ *                 tau_scale_j alone when sizes[0] == 3                                                      (neural_allocator.py:117-126)
+ *     dense layer y_j = b_j, then for k ascending y_j = fmaf(W[k][j], h_k, y_j)           (h = x for the first layer; W[l][in][out])
+ *     activation  h_j = y_j > 0 ? y_j : leak * y_j for a hidden layer (leak = 0: relu, src/sl/train.py:111); the last layer is linear
+ *     output      p = (u_port, u_star, u_bow, a_port, a_star, a_bow), the node's order (:137)
+ *     thrust      n_i = fminf(fmaxf(p_i, -1), 1), i = 0..2: the node's * 100, its saturation at +-100 % (:178-192) and the env's / 100,
+ *                 stated once
+ *     stern angle ang_k = p_{3+k} * angle_scale, k = port, star (azimuth_mode 0, the node's `rotating`), or ang_k = azimuth[k]
+ *                 (azimuth_mode 1: the node's fixed pods, :225)
+ *     heads       (sin_k, cos_k) = the library's call-free sincos of ang_k (max abs error 9.2e-8)
+ *     action      [ n_bow, n_port, n_star, sin_port, cos_port, sin_star, cos_star ]
+ * a_bow is not used: the env's tunnel thruster is fixed.  REST RULE: if any tau_j or any of the six p is not finite, that env's action is
+ * the rest action [0, 0, 0, 0, 1, 0, 1]; no other env is affected.  (With leak = 0 a hidden pre-activation of -inf gives 0 * -inf = NaN
+ * and so the rest action.)  The law has no state and reads no hull.  ml4ca_amd.deploy.BatchedNNAllocator is its host statement.
+ * NOT HERE: a reader for the reference's .h5 models (weights arrive as arrays), a labelling scan with the network, one network per env,
+ * and an evaluation on the matrix cores - the network is evaluated on the VALU, one fmaf per weight and env. */
+typedef struct dpenv_nn_allocator {
+    uint32_t struct_size;
+    const dpenv_mlp* net;     /* sizes[0] in {3, 9}; sizes[n_layers] == 6; n_layers 2..5; hidden widths equal, 1..96 */
+    float leak;               /* hidden activation y > 0 ? y : leak * y; 0 <= leak <= 1, 0 = relu (src/sl/train.py:111) */
+    float in_const[6];        /* inputs 0..5 when sizes[0] == 9: lx_port, ly_port, lx_star, ly_star, lx_bow, ly_bow (neural_allocator.py:74-79) */
+    float tau_scale[3];       /* (1/54, 1/69.2, 1/76.9), formed in f64, rounded once (:60) */
+    float angle_scale;        /* pi (:50,61) */
+    int32_t azimuth_mode;     /* 0: the network's stern angles (the node's `rotating`); 1: fixed at azimuth[2] (:225: -3pi/4, 3pi/4) */
+    float azimuth[2];         /* port, star [rad], read in mode 1 */
+    int32_t device_pointers;  /* as dpenv_policy_desc's */
+} dpenv_nn_allocator;
+/* Fills the constants above (leak 0, azimuth_mode 0, device_pointers 1) and leaves net NULL. */
+int dpenv_nn_allocator_defaults(dpenv_nn_allocator* a);
+/* One control step for n envs, one lane per env.  Device pointers: tau float[3][n]; action_out float[n][7]; raw_out float[n][6] = the six
+ * p, or NULL.  The network's W and b must be DEVICE pointers (device_pointers = 1) and are read in place: no packing launch, no
+ * allocation, no synchronisation - graph-capturable, one kernel node.  Refused with DPENV_EINVAL before anything is launched, the field
+ * named in dpenv_last_error(NULL): a wrong struct_size, a NULL net, a shape outside the set above, a NULL W / b / tau / action_out, a leak
+ * outside [0, 1], an in_const, tau_scale, angle_scale or azimuth that is not finite, an azimuth_mode other than 0 and 1, n <= 0,
+ * device_pointers other than 1. */
+int dpenv_thrust_alloc_nn(const dpenv_nn_allocator* a, const float* tau, float* action_out, float* raw_out, int32_t n, dpenv_stream s);
+/* The network as the allocation stage of the baseline's closed loop: while one is set, dpenv_controller_rollout (signature and rows
+ * unchanged) forms tau with the PID lines of the DP controller's law - z advanced, the wrench clipped to tau_max, bit for bit what they
+ * are without it - and allocates it with the law above in place of the f_m / bow / stern lines.  So the act rows of a launch are
+ * dpenv_thrust_alloc_nn applied row by row to the PID's tau, bit for bit, and two launches of T/2 write the rows of one launch of T.
+ * The weights are copied into a library-owned, zero-padded image (allocated by the first call at the size of the largest shape, released
+ * with the handle), so the caller's arrays are free after the call, on the stream.  device_pointers = 1: one packing launch on s -
+ * stream-ordered, no allocation after the first call, graph-capturable; the image of a shape always lies at the same addresses, so a
+ * captured launch flies whatever the last upload of that shape wrote (an upload of another shape voids graphs captured before).
+ * device_pointers = 0 (host arrays): the call synchronises s before it returns, as dpenv_set_policy_desc does.  An upload is ordered
+ * behind earlier launches by stream order alone: issue it on the stream the launches use.
+ * Needs the DP controller on (it supplies tau, z and dt), else DPENV_EINVAL.  a = NULL returns the handle to the pseudo-inverse.
+ * dpenv_set_dp_controller (on or off) drops the network, as it drops the QP.  The law touches no hull, so it is supported wherever
+ * dpenv_set_dp_controller is: the shared hull, the thrust-loss preset, per-env hull blocks and their randomisation, every current,
+ * auto-reset, with or without the reference filter.  Refused with DPENV_EINVAL and the reason named: a per-env controller table in force,
+ * a QP allocator (scalar or table) set, and whatever dpenv_set_dp_controller refuses (the integral action on, ...); in the other
+ * direction dpenv_set_qp_allocator, dpenv_set_qp_allocator_table and dpenv_set_dp_controller_table are refused while a network is set.
+ * dpenv_controller_label, dpenv_controller_label_qp and dpenv_controller_label_qp_ex are untouched: they label with the pseudo-inverse
+ * and the QP law whatever is set here. */
+int dpenv_set_nn_allocator(dpenv_handle h, const dpenv_nn_allocator* a, dpenv_stream s);
 /* The PID + QP chain on rows some other flight wrote (additive to ABI 6): dpenv_controller_label's scan with the QP law in place of the
  * f_m / bow / stern lines - the low-energy expert's labels for the states an actor visited.  One launch, one lane per env; per row t and
  * env i, in the order of the closed loop with a QP set:

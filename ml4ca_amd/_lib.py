@@ -96,6 +96,12 @@ class QPAllocator(C.Structure):
                 ('azimuth_rate', C.c_float * 2), ('lx', C.c_float * 3), ('ly', C.c_float * 3), ('kf', C.c_float * 3), ('kr', C.c_float * 3)]
 
 
+class NNAllocator(C.Structure):
+    _fields_ = [('struct_size', C.c_uint32), ('net', C.POINTER(Mlp)), ('leak', C.c_float), ('in_const', C.c_float * 6),
+                ('tau_scale', C.c_float * 3), ('angle_scale', C.c_float), ('azimuth_mode', C.c_int32), ('azimuth', C.c_float * 2),
+                ('device_pointers', C.c_int32)]
+
+
 class ControllerRolloutIO(C.Structure):
     _fields_ = [('struct_size', C.c_uint32), ('T', C.c_int32), ('obs', C.c_void_p), ('act', C.c_void_p), ('reward', C.c_void_p),
                 ('done', C.c_void_p), ('last_obs', C.c_void_p), ('ref_out', C.c_void_p), ('n_switch', C.c_int32),
@@ -215,6 +221,9 @@ SYMBOLS = {
     'dpenv_controller_label_qp_ex': (C.c_int, [_VP, C.POINTER(ControllerLabelQpExIO), _VP]),
     'dpenv_set_qp_allocator_table': (C.c_int, [_VP, _VP, _I32, _VP, _VP]),
     'dpenv_thrust_alloc_qp_table': (C.c_int, [_VP, _I32, _F, _VP, _VP, _VP, _VP, _VP, _VP, _I32, _VP]),
+    'dpenv_nn_allocator_defaults': (C.c_int, [C.POINTER(NNAllocator)]),
+    'dpenv_thrust_alloc_nn': (C.c_int, [C.POINTER(NNAllocator), _VP, _VP, _VP, _I32, _VP]),
+    'dpenv_set_nn_allocator': (C.c_int, [_VP, C.POINTER(NNAllocator), _VP]),
     'dpenv_train_param_count': (C.c_int64, [C.POINTER(TrainShape)]),
     'dpenv_train_workspace_bytes': (C.c_int, [C.POINTER(TrainShape), _I32, C.POINTER(C.c_int64)]),
     'dpenv_ppo_actor_grad': (C.c_int, [C.POINTER(TrainShape), _VP, _VP, _VP, _VP, _VP, _VP, _I32, _I32, _F, _VP, _VP, _VP, _I64, _VP]),

@@ -9,6 +9,7 @@
 #include <memory>
 #include <new>
 #include <string>
+#include <vector>
 
 #include "dpenv_host.h"
 
@@ -87,6 +88,9 @@ struct dpenv_s {
     bool qp_tab_on = false; // dpenv_set_qp_allocator_table (qp_on is set with it): env i flies row i of qp_tab, qp_tab_iters iterations
     float4* qp_tab = nullptr;    // the packed per-env QP block (qp_tab_float4s(n) float4), allocated by the first dpenv_set_qp_allocator_table
     int32_t qp_tab_iters = 0;
+    bool nn_on = false;     // dpenv_set_nn_allocator: dpenv_controller_rollout allocates the PID's wrench with the network of `nn`
+    NnRollout nn = {};      // its constants and the layers' addresses inside nn_img
+    float* nn_img = nullptr;     // the zero-padded weight image (NN_IMAGE_FLOATS floats: the largest shape), allocated by the first dpenv_set_nn_allocator
     int device = 0;
     std::string err;
 
@@ -104,6 +108,7 @@ struct dpenv_s {
         if (ctrl_tab) (void)hipFree(ctrl_tab);
         if (qp.state) (void)hipFree(qp.state);
         if (qp_tab) (void)hipFree(qp_tab);
+        if (nn_img) (void)hipFree(nn_img);
         for (int k = 0; k < 2; ++k) if (pol_read[k]) (void)hipEventDestroy(pol_read[k]);
         if (loss_ev) (void)hipEventDestroy(loss_ev);
         if (loss_host) (void)hipHostFree(loss_host);
@@ -1143,6 +1148,7 @@ extern "C" int dpenv_set_dp_controller(dpenv_handle h, const dpenv_dp_controller
         h->ctrl_on = false;
         h->ctrl_tab_on = false;
         h->qp_on = h->qp_scalar = h->qp_tab_on = false;
+        h->nn_on = false;
         return DPENV_OK;
     }
     ControlArgs g = {};
@@ -1157,9 +1163,13 @@ extern "C" int dpenv_set_dp_controller(dpenv_handle h, const dpenv_dp_controller
     h->ctrl_on = true;
     h->ctrl_tab_on = false;                                // the scalar law again: a table in force is dropped
     h->qp_on = h->qp_scalar = h->qp_tab_on = false;        // ... and so is a QP allocator, scalar or per-env: the pseudo-inverse allocates again
+    h->nn_on = false;                                      // ... and a neural allocator
     return DPENV_OK;
 }
 
+#define NN_SET_MSG                                                                                                                   \
+    "the NN allocator runs with the DP controller on and its scalar numbers (no per-env controller table in force) and no QP "       \
+    "allocator, scalar or per-env, set; while one is set, the controller table and the QP allocator are refused"
 #define QP_SET_MSG                                                                                                                   \
     "the QP allocator runs with the DP controller on and its scalar numbers (no per-env controller table), on the shared hull or the " \
     "thrust-loss preset (no per-env hull blocks, one vessel class)"
@@ -1178,6 +1188,7 @@ extern "C" int dpenv_set_dp_controller_table(dpenv_handle h, const float* table,
         return DPENV_OK;
     }
     if (h->qp_on) return fail(h, DPENV_EINVAL, "dpenv_set_dp_controller_table: " QP_SET_MSG);
+    if (h->nn_on) return fail(h, DPENV_EINVAL, "dpenv_set_dp_controller_table: a neural allocator is set: " NN_SET_MSG);
     DeviceGuard dev_guard(h->device);
     if (!h->ctrl_tab) {                                    // (whole waves of 64 envs: not ensure_env_state's count x n_envs)
         void* p = nullptr;
@@ -1233,6 +1244,13 @@ extern "C" int dpenv_controller_rollout(dpenv_handle h, const dpenv_controller_r
     const int ves = rollout_ves(vessel_source(h));
     // the handle may have changed since dpenv_set_qp_allocator
     if (h->qp_on && (h->ctrl_tab_on || (ves != VES_ARGS && ves != VES_ARGS_LOSS))) return fail(h, DPENV_EINVAL, "dpenv_controller_rollout: " QP_SET_MSG);
+    if (h->nn_on) {                                        // the neural allocation behind the PID lines: its own kernels (dpenv_control_nn.hip)
+        if (h->ctrl_tab_on || h->qp_on) return fail(h, DPENV_EINVAL, "dpenv_controller_rollout: " NN_SET_MSG);
+        const hipError_t en = dev::launch_controller_rollout_nn(&a, &ca, h->reff_on ? &fa : nullptr, &h->nn, ves, (hipStream_t)s);
+        if (en != hipSuccess) return fail(h, DPENV_EHIP, "controller launch failed: %s", hipGetErrorString(en));
+        h->lag_valid = true;
+        return DPENV_OK;
+    }
     QpRollout qr = h->qp;
     if (h->qp_tab_on) qr.q.iters = h->qp_tab_iters;         // (of q only iters is read while the table flies)
     const hipError_t e = dev::launch_controller_rollout(&a, &ca, h->reff_on ? &fa : nullptr, h->ctrl_tab_on ? h->ctrl_tab : nullptr,
@@ -1252,6 +1270,7 @@ extern "C" int dpenv_set_qp_allocator(dpenv_handle h, const dpenv_qp_allocator* 
         return DPENV_OK;
     }
     if (!h->ctrl_on) return fail(h, DPENV_EINVAL, "dpenv_set_qp_allocator: the DP controller is off (dpenv_set_dp_controller first)");
+    if (h->nn_on) return fail(h, DPENV_EINVAL, "dpenv_set_qp_allocator: a neural allocator is set: " NN_SET_MSG);
     QpArgs g = {};
     if (const char* why = qp_check(q, h->ctrl.dt, g)) return fail(h, DPENV_EINVAL, "%s", why);
     if (!control_config_ok(h)) return fail(h, DPENV_EINVAL, "dpenv_set_qp_allocator: " CONTROL_SET_MSG);
@@ -1284,6 +1303,7 @@ extern "C" int dpenv_set_qp_allocator_table(dpenv_handle h, const float* table, 
         return DPENV_OK;
     }
     if (!h->ctrl_on) return fail(h, DPENV_EINVAL, "dpenv_set_qp_allocator_table: the DP controller is off (dpenv_set_dp_controller first)");
+    if (h->nn_on) return fail(h, DPENV_EINVAL, "dpenv_set_qp_allocator_table: a neural allocator is set: " NN_SET_MSG);
     if (iterations < 1 || iterations > QP_MAX_ITERS) return fail(h, DPENV_EINVAL, "QP allocator: iterations must be in 1..32");
     if (!std::isfinite(h->ctrl.dt) || !(h->ctrl.dt > 0.0f)) return fail(h, DPENV_EINVAL, "QP allocator: dt must be finite and > 0");
     if (!control_config_ok(h)) return fail(h, DPENV_EINVAL, "dpenv_set_qp_allocator_table: " CONTROL_SET_MSG);
@@ -1304,6 +1324,57 @@ extern "C" int dpenv_set_qp_allocator_table(dpenv_handle h, const float* table, 
     HIP_TRY(h, dev::launch_qp_state_clear(h->qp.state, nullptr, h->cfg.n_envs, (hipStream_t)s));
     h->qp_tab_iters = iterations;
     h->qp_on = h->qp_tab_on = true;
+    return DPENV_OK;
+}
+
+// ---- the neural allocation as the closed loop's allocation stage (dpenv.h) ----
+extern "C" int dpenv_set_nn_allocator(dpenv_handle h, const dpenv_nn_allocator* a, dpenv_stream s)
+{
+    if (!h) return DPENV_EINVAL;
+    if (!a) {
+        h->nn_on = false;
+        return DPENV_OK;
+    }
+    if (!h->ctrl_on) return fail(h, DPENV_EINVAL, "dpenv_set_nn_allocator: the DP controller is off (dpenv_set_dp_controller first)");
+    NnArgs g;
+    if (const char* why = nn_check(a, g)) return fail(h, DPENV_EINVAL, "%s", why);
+    if (a->device_pointers != 0 && a->device_pointers != 1) return fail(h, DPENV_EINVAL, "NN allocator: device_pointers must be 0 or 1");
+    if (!control_config_ok(h)) return fail(h, DPENV_EINVAL, "dpenv_set_nn_allocator: " CONTROL_SET_MSG);
+    if (h->ctrl_tab_on) return fail(h, DPENV_EINVAL, "dpenv_set_nn_allocator: a per-env controller table is in force: " NN_SET_MSG);
+    if (h->qp_on) return fail(h, DPENV_EINVAL, "dpenv_set_nn_allocator: a QP allocator is set: " NN_SET_MSG);
+    DeviceGuard dev_guard(h->device);
+    if (!h->nn_img) {                                      // the largest shape's image, once: a later call never allocates
+        void* p = nullptr;
+        if (hipMalloc(&p, sizeof(float) * (size_t)NN_IMAGE_FLOATS) != hipSuccess) return fail(h, DPENV_ENOMEM, "hipMalloc of the NN allocator image failed");
+        h->nn_img = (float*)p;
+    }
+    // the image: per layer W [in][nn_pad(out)] then b [nn_pad(out)], zero-padded; a shape's layout is a function of the shape alone
+    NnPack pk = {};
+    pk.n_layers = g.n_layers; pk.in_dim = g.in_dim; pk.H = g.H;
+    size_t off = 0, w_off[NN_MAX_LAYERS], b_off[NN_MAX_LAYERS];
+    for (int l = 0; l < g.n_layers; ++l) {
+        const size_t in = l == 0 ? g.in_dim : g.H, ld = (size_t)nn_pad(l == g.n_layers - 1 ? 6 : g.H);
+        w_off[l] = off; off += in * ld;
+        b_off[l] = off; off += ld;
+        pk.W[l] = g.W[l]; pk.b[l] = g.b[l];
+        pk.dW[l] = h->nn_img + w_off[l]; pk.db[l] = h->nn_img + b_off[l];
+    }
+    if (a->device_pointers) {
+        HIP_TRY(h, dev::launch_nn_pack(&pk, (hipStream_t)s));
+    } else {                                               // host arrays: the image is formed here and copied; the call waits for the copy
+        std::vector<float> img(off, 0.0f);
+        for (int l = 0; l < g.n_layers; ++l) {
+            const size_t in = l == 0 ? g.in_dim : g.H, out = l == g.n_layers - 1 ? 6 : g.H, ld = (size_t)nn_pad((int)out);
+            for (size_t k = 0; k < in; ++k)
+                for (size_t j = 0; j < out; ++j) img[w_off[l] + k * ld + j] = g.W[l][k * out + j];
+            for (size_t j = 0; j < out; ++j) img[b_off[l] + j] = g.b[l][j];
+        }
+        HIP_TRY(h, hipMemcpyAsync(h->nn_img, img.data(), sizeof(float) * off, hipMemcpyHostToDevice, (hipStream_t)s));
+        HIP_TRY(h, hipStreamSynchronize((hipStream_t)s));
+    }
+    for (int l = 0; l < g.n_layers; ++l) { g.W[l] = pk.dW[l]; g.b[l] = pk.db[l]; }
+    h->nn.a = g;
+    h->nn_on = true;
     return DPENV_OK;
 }
 

@@ -380,6 +380,71 @@ extern "C" int dpenv_thrust_alloc_qp_table(const float* table, int32_t iteration
     return DPENV_OK;
 }
 
+// ---- the neural thrust allocation (dpenv.h; the kernels are dpenv_control_nn.hip's) ------------------------------------------------------
+extern "C" int dpenv_nn_allocator_defaults(dpenv_nn_allocator* a)
+{
+    if (!a) return fail(nullptr, DPENV_EINVAL, "dpenv_nn_allocator_defaults: a is NULL");
+    std::memset(a, 0, sizeof *a);
+    a->struct_size = (uint32_t)sizeof *a;
+    const float l[6] = {-1.12f, -0.15f, -1.12f, 0.15f, 1.08f, 0.0f};     // neural_allocator.py:74-79: lx, ly of port, star, bow
+    for (int k = 0; k < 6; ++k) a->in_const[k] = l[k];
+    a->tau_scale[0] = (float)(1.0 / 54.0);                               // :60
+    a->tau_scale[1] = (float)(1.0 / 69.2);
+    a->tau_scale[2] = (float)(1.0 / 76.9);
+    a->angle_scale = (float)3.14159265358979323846;                      // :50,61
+    a->azimuth_mode = 0;
+    a->azimuth[0] = (float)(-3.0 * 3.14159265358979323846 / 4.0);        // :225
+    a->azimuth[1] = (float)(3.0 * 3.14159265358979323846 / 4.0);
+    a->device_pointers = 1;
+    return DPENV_OK;
+}
+
+// validates a and forms the kernel's numbers; the reason for a refusal, or NULL
+const char* host::nn_check(const dpenv_nn_allocator* a, NnArgs& g)
+{
+    if (a->struct_size != sizeof(dpenv_nn_allocator)) return "dpenv_nn_allocator ABI mismatch (struct_size)";
+    const dpenv_mlp* m = a->net;
+    if (!m) return "NN allocator: net is NULL";
+    if (m->n_layers < 2 || m->n_layers > NN_MAX_LAYERS) return "NN allocator: net n_layers must be in 2..5";
+    const int L = m->n_layers;
+    if (m->sizes[0] != 3 && m->sizes[0] != 9) return "NN allocator: net sizes[0] must be 3 or 9";
+    if (m->sizes[L] != 6) return "NN allocator: net sizes[n_layers] must be 6";
+    for (int l = 1; l < L; ++l)
+        if (m->sizes[l] < 1 || m->sizes[l] > NN_MAX_H || m->sizes[l] != m->sizes[1]) return "NN allocator: net hidden sizes must be equal and in 1..96";
+    for (int l = 0; l < L; ++l)
+        if (!m->W[l] || !m->b[l]) return "NN allocator: net W and b must not be NULL";
+    if (!std::isfinite(a->leak) || a->leak < 0.0f || a->leak > 1.0f) return "NN allocator: leak must be in [0, 1]";
+    for (int k = 0; k < 6; ++k)
+        if (!std::isfinite(a->in_const[k])) return "NN allocator: in_const must be finite";
+    for (int k = 0; k < 3; ++k)
+        if (!std::isfinite(a->tau_scale[k])) return "NN allocator: tau_scale must be finite";
+    if (!std::isfinite(a->angle_scale)) return "NN allocator: angle_scale must be finite";
+    if (a->azimuth_mode != 0 && a->azimuth_mode != 1) return "NN allocator: azimuth_mode must be 0 or 1";
+    if (!std::isfinite(a->azimuth[0]) || !std::isfinite(a->azimuth[1])) return "NN allocator: azimuth must be finite";
+    g = NnArgs{};
+    for (int l = 0; l < L; ++l) { g.W[l] = m->W[l]; g.b[l] = m->b[l]; }
+    g.n_layers = L; g.in_dim = m->sizes[0]; g.H = m->sizes[1];
+    g.leak = a->leak;
+    for (int k = 0; k < 6; ++k) g.in_const[k] = a->in_const[k];
+    for (int k = 0; k < 3; ++k) g.tau_scale[k] = a->tau_scale[k];
+    g.angle_scale = a->angle_scale;
+    g.azimuth_mode = a->azimuth_mode;
+    g.azimuth[0] = a->azimuth[0]; g.azimuth[1] = a->azimuth[1];
+    return nullptr;
+}
+
+extern "C" int dpenv_thrust_alloc_nn(const dpenv_nn_allocator* a, const float* tau, float* action_out, float* raw_out, int32_t n, dpenv_stream s)
+{
+    if (!a) return fail(nullptr, DPENV_EINVAL, "dpenv_thrust_alloc_nn: a is NULL");
+    if (!tau || !action_out) return fail(nullptr, DPENV_EINVAL, "dpenv_thrust_alloc_nn: tau and action_out must not be NULL");
+    if (n <= 0) return fail(nullptr, DPENV_EINVAL, "dpenv_thrust_alloc_nn: n must be > 0");
+    NnArgs g;
+    if (const char* why = nn_check(a, g)) return fail(nullptr, DPENV_EINVAL, "%s", why);
+    if (a->device_pointers != 1) return fail(nullptr, DPENV_EINVAL, "dpenv_thrust_alloc_nn: device_pointers must be 1 (the weights are read in place)");
+    HIP_TRY(nullptr, dev::launch_nn_alloc(&g, tau, action_out, raw_out, n, (hipStream_t)s));
+    return DPENV_OK;
+}
+
 extern "C" int dpenv_thrust_map(const float* params, const float* n_pct, const float* alpha, float* tau_out, int32_t n,
                                 dpenv_stream s)
 {

@@ -27,6 +27,8 @@ namespace dpenv {
 #include "dpenv_control_law.h"
 // the QP allocation, the other allocation stage the closed loop's body can be compiled with (controller_rollout_qp_kernel)
 #include "dpenv_qp_law.h"
+// the neural allocation, the third stage the body can be compiled with - in dpenv_control_nn.hip, not here: only the names its NN branch mentions
+#include "dpenv_nn_law.h"
 // control_store_rows, which the closed-loop body calls
 #include "dpenv_control_rows.h"
 
@@ -41,7 +43,8 @@ namespace dpenv {
 template <int VES, bool REFF>
 __global__ __launch_bounds__(RBLOCK) void controller_rollout_kernel(const StepArgs a, const ControlArgs ca, const FilterArgs fa)
 {
-    constexpr bool TAB = false, QP = false, QTAB = false;
+    constexpr bool TAB = false, QP = false, QTAB = false, NN = false;
+    const NnRollout nr = {};
     const float4* const tab = nullptr;
     const float4* const qtab = nullptr;
     const QpRollout qr = {};
@@ -54,7 +57,8 @@ template <int VES, bool REFF>
 __global__ __launch_bounds__(RBLOCK) void controller_rollout_tab_kernel(const StepArgs a, const ControlArgs ca, const FilterArgs fa,
                                                                          const float4* __restrict__ tab)
 {
-    constexpr bool TAB = true, QP = false, QTAB = false;
+    constexpr bool TAB = true, QP = false, QTAB = false, NN = false;
+    const NnRollout nr = {};
     const float4* const qtab = nullptr;
     const QpRollout qr = {};
 #include "dpenv_control_rollout_body.inc"
@@ -181,7 +185,8 @@ template <int VES, bool REFF>
 __global__ __launch_bounds__(RBLOCK) void controller_rollout_qp_kernel(const StepArgs a, const ControlArgs ca, const FilterArgs fa,
                                                                         const QpRollout qr)
 {
-    constexpr bool TAB = false, QP = true, QTAB = false;
+    constexpr bool TAB = false, QP = true, QTAB = false, NN = false;
+    const NnRollout nr = {};
     const float4* const tab = nullptr;
     const float4* const qtab = nullptr;
 #include "dpenv_control_rollout_body.inc"
@@ -195,7 +200,8 @@ template <int VES, bool REFF>
 __global__ __launch_bounds__(RBLOCK) void controller_rollout_qp_tab_kernel(const StepArgs a, const ControlArgs ca, const FilterArgs fa,
                                                                             const QpRollout qr, const float4* __restrict__ qtab)
 {
-    constexpr bool TAB = false, QP = true, QTAB = true;
+    constexpr bool TAB = false, QP = true, QTAB = true, NN = false;
+    const NnRollout nr = {};
     const float4* const tab = nullptr;
 #include "dpenv_control_rollout_body.inc"
 }

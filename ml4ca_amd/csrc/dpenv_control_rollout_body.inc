@@ -3,7 +3,8 @@
 // (FilterArgs), the compile-time TAB and, if TAB, tab (the packed per-env controller block, ctrl_tab_index), the compile-time QP and, if QP,
 // qr (QpRollout: the rate-limited QP allocation of dpenv_qp_law.h in place of dp_allocate, its thruster state carried beside z), the
 // compile-time QTAB (with QP) and, if QTAB, qtab (the packed per-env QP block, qp_tab_index: the env's own numbers in place of qr.q's,
-// of which only iters is read); the rest are the kernel's template arguments.
+// of which only iters is read); the compile-time NN and, if NN, nr (NnRollout: the neural allocation of dpenv_nn_law.h in place of
+// dp_allocate; it has no state); the rest are the kernel's template arguments.
     constexpr int MODE = MODE_FINAL_CONT;
     constexpr bool EXT = true;
     constexpr int A = 7, OD = 9;
@@ -74,7 +75,11 @@
     for (int t = 0; t < ca.T; ++t) {
         control_store_rows<OD>(lds_row, ca.obs, (int64_t)t * stride_o + w_o, rem_o, o, tid, a.obs_bf16 != 0);
         float act[A];
-        if constexpr (QP) {                                      // the PID's wrench, allocated by the QP law
+        if constexpr (NN) {                                      // the PID's wrench, allocated by the network
+            float tau[3], p[6];
+            dp_wrench(ca, o, z, tau);
+            nn_allocate<true>(nr.a, nn_lds() + tid, tau, act, p);
+        } else if constexpr (QP) {                               // the PID's wrench, allocated by the QP law
             float tau[3], J;
             dp_wrench(ca, o, z, tau);
             if constexpr (QTAB) qp_allocate(ql, tau, xq, act, J);

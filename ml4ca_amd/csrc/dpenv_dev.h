@@ -272,6 +272,36 @@ struct QpAllocIO {
     int32_t n;
 };
 
+// the neural thrust allocation (dpenv_thrust_alloc_nn / dpenv_set_nn_allocator; include/dpenv.h has the law, dpenv_nn_law.h its device
+// text, dpenv_control_nn.hip the kernels): a dense network in -> H -> ... -> H -> 6 and the constants around it.  W[l] is [in_l][ld_l]
+// row-major: the caller's arrays in place (ld_l = the layer's width) or the library's zero-padded image (ld_l = the width rounded up to
+// NN_CHUNK, b[l] padded likewise); every pointer is a DEVICE pointer.
+constexpr int NN_MAX_H = 96, NN_CHUNK = 16, NN_MAX_LAYERS = 5;
+constexpr int nn_pad(int w) { return (w + NN_CHUNK - 1) / NN_CHUNK * NN_CHUNK; }
+constexpr int NN_IMAGE_FLOATS = NN_MAX_LAYERS * (NN_MAX_H * NN_MAX_H + NN_MAX_H);   // the largest image: what a handle allocates once
+struct NnArgs {
+    const float* W[NN_MAX_LAYERS];
+    const float* b[NN_MAX_LAYERS];
+    int32_t n_layers, in_dim, H;    // dense layers 2..5, inputs 3 or 9, hidden width 1..NN_MAX_H; the last layer has 6 outputs
+    float leak;
+    float in_const[6], tau_scale[3], angle_scale;
+    int32_t azimuth_mode;
+    float azimuth[2];
+};
+// the allocation as the allocation stage of the baseline's closed loop (dpenv_set_nn_allocator): a separate argument of
+// controller_rollout_nn_kernel only; the weights are the handle's padded image
+struct NnRollout {
+    NnArgs a;
+};
+// the packing of that image from DEVICE arrays (dpenv_set_nn_allocator with device_pointers = 1): src in place, dst the image's layers
+struct NnPack {
+    const float* W[NN_MAX_LAYERS];
+    const float* b[NN_MAX_LAYERS];
+    float* dW[NN_MAX_LAYERS];
+    float* db[NN_MAX_LAYERS];
+    int32_t n_layers, in_dim, H;
+};
+
 // device-side weight packing (pack_policy_kernel): one dense network, DEVICE pointers
 struct PackNet {
     const float* W[5];        // W[l][in][out] row-major (tf.layers.dense kernel layout)
@@ -535,6 +565,13 @@ hipError_t launch_qp_state_clear(float* state, const uint8_t* mask, int n, hipSt
 hipError_t launch_pack_qp_table(const float* table, float4* qtab, uint8_t* refused, float dt, int n, hipStream_t s);
 // launch_qp_alloc with row i of the PUBLIC table on env i, checked by the lane itself (dpenv_thrust_alloc_qp_table)
 hipError_t launch_qp_alloc_tab(const float* table, int iters, float dt, const QpAllocIO* io, uint8_t* refused, hipStream_t s);
+// dpenv_control_nn.hip: the neural allocation for n envs, one lane per env, weights read in place (raw: [n][6] the network's outputs, or NULL)
+hipError_t launch_nn_alloc(const NnArgs* na, const float* tau, float* action, float* raw, int n, hipStream_t s);
+// the baseline's closed loop with the neural allocation behind the PID lines (launch_controller_rollout's a, ca, fa and ves; every
+// vessel source of with_control_ves); nr->a points into the padded image launch_nn_pack or the host wrote
+hipError_t launch_controller_rollout_nn(const StepArgs* a, const ControlArgs* ca, const FilterArgs* fa, const NnRollout* nr, int ves, hipStream_t s);
+// the caller's DEVICE arrays -> the zero-padded image, one launch
+hipError_t launch_nn_pack(const NnPack* np, hipStream_t s);
 // two-wave closed loop, dpenv_policy_ws.h; one arithmetic per translation unit: dpenv_policy_ws.hip PREC_F16, dpenv_policy_xws1.hip
 // PREC_F32, dpenv_policy_xws2.hip PREC_F32_ACTOR
 template <int PREC>

@@ -48,6 +48,9 @@ const char* reff_coeffs_f32(const dpenv_reference_filter* rf, float dt, float ph
 const char* control_check(const dpenv_dp_controller* c, ControlArgs& g);
 // the QP allocation's numbers for the control period dt into QpArgs, or an error message
 const char* qp_check(const dpenv_qp_allocator* q, float dt, QpArgs& g);
+// the neural allocation's shape and constants into NnArgs (W and b are the caller's pointers, required non-NULL, not dereferenced), or an
+// error message; device_pointers is not looked at
+const char* nn_check(const dpenv_nn_allocator* a, NnArgs& g);
 
 }  // namespace host
 }  // namespace dpenv

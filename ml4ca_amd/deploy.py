@@ -14,6 +14,8 @@ the node took its reference from.
 """
 import numpy as np
 
+from ._num import _fma32
+
 ROS_ORDER = ('n_port', 'n_star', 'n_bow', 'a_port', 'a_star', 'a_bow')
 
 # rl_allocator.py:92-106
@@ -998,3 +1000,163 @@ class RLAllocatorNode(object):
         self.prev_thrust_state = u.copy()
         self.state[-3:] = np.array([u[2], u[0], u[1]]) / 100.0          # back to network order (:218)
         return u, publishable(u, self.simulation)
+
+
+# ---- the neural thrust allocation: the reference's supervised allocator (src/sl) ---------------------------------------------------------
+NN_TAU_SCALE = (1.0 / 54.0, 1.0 / 69.2, 1.0 / 76.9)              # neural_allocator.py:60, SupervisedTau.py:189
+NN_IN_CONST = (-1.12, -0.15, -1.12, 0.15, 1.08, 0.0)             # neural_allocator.py:74-79: lx, ly of port, star, bow
+NN_FIXED_AZIMUTH = (-3.0 * np.pi / 4.0, 3.0 * np.pi / 4.0)       # neural_allocator.py:225
+NN_REST_ACTION = (0.0, 0.0, 0.0, 0.0, 1.0, 0.0, 1.0)
+
+
+def nn_allocator_defaults():
+    """The neural allocator's constants (dpenv_nn_allocator_defaults; the node's, neural_allocator.py:50-79,225), float64: leak 0 (relu,
+    src/sl/train.py:111), the six lever-arm inputs, the wrench scale, the angle scale pi, azimuth_mode 0 (the network's stern angles; 1 =
+    the pods fixed at `azimuth`).  Returns the dict BatchedNNAllocator, policy.thrust_alloc_nn and env.set_nn_allocator take."""
+    return dict(leak=0.0, in_const=np.array(NN_IN_CONST), tau_scale=np.array(NN_TAU_SCALE), angle_scale=float(np.pi), azimuth_mode=0,
+                azimuth=np.array(NN_FIXED_AZIMUTH))
+
+
+def nn_allocator_params(net=None, **constants):
+    """nn_allocator_defaults with `constants` on top; a net dict that carries 'leak' (train.fit_nn_allocator's does) supplies the leak
+    unless constants names one."""
+    p = nn_allocator_defaults()
+    if isinstance(net, dict) and 'leak' in net:
+        p['leak'] = float(net['leak'])
+    for k, v in constants.items():
+        if k not in p:
+            raise ValueError('nn allocator: unknown constant %r (known: %s)' % (k, sorted(p)))
+        p[k] = v
+    return p
+
+
+def nn_net_sizes(Ws, bs):
+    """The layer widths [in, H, ..., H, 6] of dense kernels Ws and biases bs (arrays or tensors; only their shapes are read), with the
+    shape dpenv_nn_allocator admits checked: inputs 3 or 9, 2..5 dense layers, equal hidden widths in 1..96, 6 outputs."""
+    L = len(Ws)
+    if L != len(bs) or not 2 <= L <= 5:
+        raise ValueError('nn allocator: 2..5 dense layers, as many W as b')
+    if any(len(w.shape) != 2 for w in Ws):
+        raise ValueError('nn allocator: W[l] is [in][out]')
+    sizes = [int(Ws[0].shape[0])] + [int(w.shape[1]) for w in Ws]
+    if any(int(Ws[l].shape[0]) != sizes[l] or int(np.prod(bs[l].shape)) != sizes[l + 1] for l in range(L)):
+        raise ValueError('nn allocator: W[l] is [in][out], b[l] is [out], layer by layer')
+    if sizes[0] not in (3, 9) or sizes[-1] != 6 or any(h != sizes[1] for h in sizes[1:-1]) or not 1 <= sizes[1] <= 96:
+        raise ValueError('nn allocator: sizes %s - inputs 3 or 9, equal hidden widths in 1..96, 6 outputs' % (sizes,))
+    return sizes
+
+
+def nn_net_arrays(net):
+    """(Ws, bs) of a net - a dict with 'W' and 'b' (lists of arrays or tensors, W[l] [in][out]) or a pair (Ws, bs) - as float32 NumPy
+    arrays, shape checked (nn_net_sizes)."""
+    Ws, bs = (net['W'], net['b']) if isinstance(net, dict) else net
+    nn_net_sizes(Ws, bs)
+    cv = lambda a: np.ascontiguousarray((a.detach().cpu().numpy() if hasattr(a, 'detach') else np.asarray(a)), dtype=np.float32)
+    return [cv(w) for w in Ws], [cv(b).reshape(-1) for b in bs]
+
+
+class BatchedNNAllocator(object):
+    """The neural thrust allocation for n envs on the host: the statement of include/dpenv.h, operation by operation, in batched NumPy.
+    dtype float32 (the default) is the device's arithmetic - every product-sum of a layer through the exact host fmaf, in the order of
+    k - except for sin / cos (np.sin / np.cos of the f32 angle here, the library's polynomial on the device: the heads agree to 9.2e-8
+    plus a rounding, everything else bit for bit); dtype=np.float64 is the form for checks, on the same f32 constants and weights.
+    net: see nn_net_arrays; params: the dict of nn_allocator_defaults (None = the defaults, with the net's leak if it carries one).
+    allocate(tau [n, 3]) returns the action [n, 7]; with raw=True also the network's outputs p [n, 6].  The law has no state."""
+
+    def __init__(self, n, net, dtype=None, params=None):
+        self.n = int(n)
+        self.dtype = np.dtype(np.float32 if dtype is None else dtype)
+        self.is32 = self.dtype == np.dtype(np.float32)
+        self.Ws32, self.bs32 = nn_net_arrays(net)
+        p = nn_allocator_params(net) if params is None else params
+        t = lambda v: np.asarray(v, np.float64).astype(np.float32).astype(self.dtype)    # the struct's f32 numbers
+        self.Ws, self.bs = [w.astype(self.dtype) for w in self.Ws32], [b.astype(self.dtype) for b in self.bs32]
+        self.leak, self.in_const, self.tau_scale = t(p['leak']), t(p['in_const']), t(p['tau_scale'])
+        self.angle_scale, self.azimuth, self.mode = t(p['angle_scale']), t(p['azimuth']), int(p['azimuth_mode'])
+        if self.mode not in (0, 1) or not 0.0 <= float(self.leak) <= 1.0:
+            raise ValueError('BatchedNNAllocator: azimuth_mode is 0 or 1, leak in [0, 1]')
+
+    def inputs(self, tau):
+        tau = np.asarray(tau, self.dtype)
+        if tau.shape != (self.n, 3):
+            raise ValueError('BatchedNNAllocator: tau is [n, 3]')
+        with np.errstate(all='ignore'):
+            x = tau * self.tau_scale
+        if self.Ws[0].shape[0] == 9:
+            x = np.concatenate([np.broadcast_to(self.in_const, (self.n, 6)), x], 1)
+        return tau, x
+
+    def forward(self, x):
+        """The network on its inputs x [n, in]: (p [n, 6], hs) with hs[l] the input of dense layer l."""
+        h, hs = np.asarray(x, self.dtype), []
+        L = len(self.Ws)
+        with np.errstate(all='ignore'):
+            for l in range(L):
+                hs.append(h)
+                W, b = self.Ws[l], self.bs[l]
+                if self.is32:
+                    y = np.broadcast_to(b, (h.shape[0], b.shape[0])).copy()
+                    for k in range(W.shape[0]):
+                        y = _fma32(W[k][None, :], h[:, k:k + 1], y)
+                else:
+                    y = h @ W + b
+                h = y if l == L - 1 else np.where(y > 0, y, self.leak * y)
+        return h, hs
+
+    def allocate(self, tau, raw=False):
+        tau, x = self.inputs(tau)
+        p, _ = self.forward(x)
+        one = self.dtype.type(1.0)
+        with np.errstate(all='ignore'):
+            thr = np.fmin(np.fmax(p[:, 0:3], -one), one)
+            ang = np.broadcast_to(self.azimuth, (self.n, 2)) if self.mode == 1 else p[:, 3:5] * self.angle_scale
+            s, c = np.sin(ang.astype(np.float64)).astype(self.dtype), np.cos(ang.astype(np.float64)).astype(self.dtype)
+        act = np.stack([thr[:, 2], thr[:, 0], thr[:, 1], s[:, 0], c[:, 0], s[:, 1], c[:, 1]], 1)
+        ok = np.isfinite(tau).all(1) & np.isfinite(p).all(1)
+        act[~ok] = np.asarray(NN_REST_ACTION, self.dtype)
+        return (act, p) if raw else act
+
+
+def thrust_map_host(n_pct, alpha, vessel=None):
+    """tau = B(alpha) F(n) on the host, float64 - SupervisedTau.tau (SupervisedTau.py:42-83) with the hull's numbers, the statement of
+    dpenv_thrust_map without the inflow thrust loss: n_pct, alpha [3, n] in env order (bow, port, star), F_i = K_i n_i |n_i| with K_i =
+    kf_i ahead and kr_i astern; returns [3, n] = Fx, Fy, Mz."""
+    from . import _lib
+    v = np.asarray(_lib.default_vessel() if vessel is None else vessel, np.float64)
+    P = _lib.P
+    n_pct, alpha = np.asarray(n_pct, np.float64), np.asarray(alpha, np.float64)
+    kf, kr = v[P['KF_BOW']:P['KF_BOW'] + 3, None], v[P['KR_BOW']:P['KR_BOW'] + 3, None]
+    lx, ly = v[P['LX_BOW']:P['LX_BOW'] + 3, None], v[P['LY_BOW']:P['LY_BOW'] + 3, None]
+    F = np.where(n_pct >= 0, kf, kr) * n_pct * np.abs(n_pct)
+    c, s = np.cos(alpha), np.sin(alpha)
+    return np.stack([(c * F).sum(0), (s * F).sum(0), ((lx * s - ly * c) * F).sum(0)])
+
+
+def nn_allocator_dataset(rows, seed, vessel=None, angle_range=0.4 * np.pi, tau_min=0.01, tau_max=DP_TAU_MAX, in_dim=9, params=None):
+    """A supervised dataset for the neural allocator by SupervisedTau.generateData's law (SupervisedTau.py:86-197): both stern pods at one
+    angle a0 in [-angle_range, angle_range] (:104,153), the bow thruster at pi / 2 (:110), the three throttles in [-100, 100] % (:111);
+    tau = thrust_map_host(u, a); rows with any |tau_j| < tau_min (:158) or any |tau_j| > tau_max_j (:181; (69, 30, 80), :37) are dropped;
+    labels u / 100 and a / angle_scale (:185-186), inputs the lever-arm constants and tau * tau_scale (:189-193).
+    The DRAW is build-defined: uniform draws from numpy.random.RandomState(seed), drawn in blocks until `rows` rows have passed the
+    filters.  The reference walks a 37 x 21^3 grid whose throttle axis it perturbs with UNSEEDED draws (:114-124) and builds with
+    np.linspace(.., np.floor(..)), which current NumPy refuses - its exact rows cannot be regenerated, its law can.
+    Returns dict(x [rows, in_dim] float32, y [rows, 6] float32 = (u_port, u_star, u_bow, a_port, a_star, a_bow) scaled, and the draws
+    behind them in float64: u [rows, 3] and a [rows, 3] in the NODE's order port, star, bow, tau [rows, 3] unscaled)."""
+    p = nn_allocator_defaults() if params is None else params
+    rng = np.random.RandomState(seed)
+    tmax = np.asarray(tau_max, np.float64)
+    us, as_, taus, have = [], [], [], 0
+    while have < rows:
+        m = max(2 * (rows - have), 256)
+        a0 = rng.uniform(-angle_range, angle_range, size=m)
+        u = rng.uniform(-100.0, 100.0, size=(m, 3))                      # port, star, bow
+        a = np.stack([a0, a0, np.full(m, np.pi / 2)], 1)
+        tau = thrust_map_host(u[:, [2, 0, 1]].T, a[:, [2, 0, 1]].T, vessel).T
+        keep = (np.abs(tau) >= tau_min).all(1) & (np.abs(tau) <= tmax).all(1)
+        us.append(u[keep]); as_.append(a[keep]); taus.append(tau[keep])
+        have += int(keep.sum())
+    u, a, tau = (np.concatenate(v)[:rows] for v in (us, as_, taus))
+    xs = tau * np.asarray(p['tau_scale'], np.float64)
+    x = xs if in_dim == 3 else np.concatenate([np.broadcast_to(np.asarray(p['in_const'], np.float64), (rows, 6)), xs], 1)
+    y = np.concatenate([u / 100.0, a / float(p['angle_scale'])], 1)
+    return dict(x=x.astype(np.float32), y=y.astype(np.float32), u=u, a=a, tau=tau)

@@ -187,6 +187,7 @@ class BatchedRevoltEnv(object):
         self.dp_controller = None            # dict of the parameters while set_dp_controller() has it on
         self.dp_controller_table = None      # the [32, n] tensor while set_dp_controller_table() has per-env numbers in force
         self.qp_allocator = None             # dict of the parameters while set_qp_allocator() has the QP allocation in the closed loop
+        self.nn_allocator = None             # dict of the constants (and 'net') while set_nn_allocator() has the network in the closed loop
         self.qp_allocator_table = None       # the [32, n] tensor while set_qp_allocator_table() has per-env QP numbers in force
         self._qp_table_iterations = 0
 
@@ -448,12 +449,14 @@ class BatchedRevoltEnv(object):
         if off:
             _lib.check(self.lib.dpenv_set_dp_controller(self._h, None, self._stream()), self._h)
             self.dp_controller = self.dp_controller_table = self.qp_allocator = self.qp_allocator_table = None
+            self.nn_allocator = None
             return
         p, c = _dp_controller_struct(params)
         _lib.check(self.lib.dpenv_set_dp_controller(self._h, C.byref(c), self._stream()), self._h)
         self.dp_controller = dict(p)
         self.dp_controller_table = None      # the scalar law again: the library dropped a table in force
         self.qp_allocator = self.qp_allocator_table = None   # ... and a QP allocator, scalar or per-env
+        self.nn_allocator = None                             # ... and a neural allocator
 
     def set_dp_controller_table(self, table, check=True):
         """Per-env numbers for the baseline (dpenv_set_dp_controller_table): table is a float32 tensor [32, n] on the env's device in
@@ -488,6 +491,28 @@ class BatchedRevoltEnv(object):
     def set_dp_controller_state(self, z):
         self._chk(z, (3, self.n_envs), _torch().float32, 'z')
         _lib.check(self.lib.dpenv_set_dp_controller_state(self._h, self._ptr(z), self._stream()), self._h)
+
+    def set_nn_allocator(self, net=None, off=False, **constants):
+        """The neural thrust allocation as the allocation stage of policy.controller_rollout (dpenv_set_nn_allocator; include/dpenv.h has
+        the law): the baseline's PID forms the wrench, the network allocates it in place of the pseudo-inverse.  net: a dict with 'W' and
+        'b' (W[l] [in][out]; inputs 3 or 9, 2..5 dense layers, equal hidden widths <= 96, 6 outputs; train.fit_nn_allocator returns one).
+        Tensors on the env's device are handed over as device pointers - one packing launch on the current stream, capturable in a
+        graph, which then re-packs the tensors' contents at every replay; anything else goes through a host copy and a synchronisation.
+        constants: entries of deploy.nn_allocator_defaults to override (leak, azimuth_mode, azimuth, ...); a net that carries 'leak'
+        supplies it.  off=True (or net=None) returns to the pseudo-inverse.  Needs set_dp_controller on (which drops it again), no per-env
+        controller table and no QP allocator; it flies on every hull the baseline flies, per-env and randomised hulls included."""
+        if off or net is None:
+            _lib.check(self.lib.dpenv_set_nn_allocator(self._h, None, self._stream()), self._h)
+            self.nn_allocator = None
+            return
+        from .deploy import nn_allocator_params
+        from .policy import nn_allocator_struct
+        p = nn_allocator_params(net, **constants)
+        a, keep = nn_allocator_struct(net, p, self.device)
+        with _torch().cuda.device(self.device):
+            _lib.check(self.lib.dpenv_set_nn_allocator(self._h, C.byref(a), self._stream()), self._h)
+        del keep
+        self.nn_allocator = dict(p, net=net)
 
     def set_qp_allocator(self, params=None, off=False):
         """The rate-limited QP thrust allocation as the allocation stage of policy.controller_rollout (dpenv_set_qp_allocator; include/dpenv.h

@@ -508,3 +508,81 @@ def thrust_alloc_qp(tau, state=None, params=None, dt=0.2, out=None, cost=False, 
                                              C.c_void_p(state.data_ptr()) if state is not None else None, C.c_void_p(state_out.data_ptr()),
                                              C.c_void_p(act.data_ptr()), C.c_void_p(J.data_ptr()) if cost else None, n, s))
     return (act, state_out, J) if cost else (act, state_out)
+
+
+def nn_allocator_struct(net, params, device):
+    """(dpenv_nn_allocator, keep) for a net (deploy.nn_net_arrays' forms) and the dict of deploy.nn_allocator_defaults.  If every W and b
+    is a contiguous float32 tensor on `device`, they are handed over as DEVICE pointers (device_pointers = 1: no copy - the optimiser's
+    own tensors, a graph replay reads their contents of that moment); else as host arrays (device_pointers = 0).  keep holds what the
+    struct points to: keep it alive until the call that takes the struct has returned."""
+    torch = _torch()
+    from .deploy import nn_net_arrays, nn_net_sizes
+    Ws, bs = (net['W'], net['b']) if isinstance(net, dict) else net
+    on_dev = all(isinstance(t, torch.Tensor) and t.is_cuda and t.device == device and t.dtype == torch.float32 and t.is_contiguous()
+                 for t in list(Ws) + list(bs))
+    sizes = nn_net_sizes(Ws, bs)
+    hW, hb = (None, None) if on_dev else nn_net_arrays(net)    # (no copy of device tensors: the call stays capturable)
+    m = _lib.Mlp()
+    m.n_layers = len(sizes) - 1
+    for i, sz in enumerate(sizes):
+        m.sizes[i] = int(sz)
+    for i in range(len(sizes) - 1):
+        if on_dev:
+            m.W[i], m.b[i] = Ws[i].data_ptr(), bs[i].data_ptr()
+        else:
+            m.W[i], m.b[i] = hW[i].ctypes.data, hb[i].ctypes.data
+    a = _lib.NNAllocator()
+    a.struct_size = C.sizeof(_lib.NNAllocator)
+    a.net = C.pointer(m)
+    a.leak = float(params['leak'])
+    for name, count in (('in_const', 6), ('tau_scale', 3), ('azimuth', 2)):
+        if len(params[name]) != count:
+            raise ValueError('nn_allocator_struct: %s has %d entries, want %d' % (name, len(params[name]), count))
+        for k in range(count):
+            getattr(a, name)[k] = float(params[name][k])
+    a.angle_scale = float(params['angle_scale'])
+    a.azimuth_mode = int(params['azimuth_mode'])
+    a.device_pointers = 1 if on_dev else 0
+    return a, (m, hW, hb, Ws, bs)
+
+
+def nn_net_to(net, device):
+    """The net's W and b as contiguous float32 tensors on `device` (tensors already there are kept as they are): dict(W, b[, leak])."""
+    torch = _torch()
+    Ws, bs = (net['W'], net['b']) if isinstance(net, dict) else net
+    mv = lambda t: (t if isinstance(t, torch.Tensor) else torch.as_tensor(np.asarray(t, np.float32))).to(device=device, dtype=torch.float32).contiguous()
+    out = dict(W=[mv(w) for w in Ws], b=[mv(b).reshape(-1) for b in bs])
+    if isinstance(net, dict) and 'leak' in net:
+        out['leak'] = net['leak']
+    return out
+
+
+def thrust_alloc_nn(tau, net, out=None, raw=False, **constants):
+    """The neural thrust allocation on the device (dpenv_thrust_alloc_nn), one lane per env: tau float32 [3, n] = Fx, Fy, Mz -> the final
+    variant's continuous-angle action [n, 7] and, with raw=True, the network's six outputs [n, 6] as a second value.  net: a dict with
+    'W' and 'b' (W[l] [in][out]; inputs 3 or 9, 2..5 dense layers, equal hidden widths <= 96, 6 outputs) - tensors on tau's device are
+    read in place, anything else is copied there first; constants: entries of deploy.nn_allocator_defaults to override (leak,
+    azimuth_mode, ...).  out = the action buffer, or (action, raw) with raw=True.  An env whose tau or whose network output is not finite
+    gets the rest action.  Handle-free and stateless; deploy.BatchedNNAllocator is the host statement."""
+    torch = _torch()
+    from .deploy import nn_allocator_params
+    f32 = torch.float32
+    if not isinstance(tau, torch.Tensor) or tau.dim() != 2 or tau.shape[0] != 3 or tau.dtype != f32 or not tau.is_cuda or not tau.is_contiguous():
+        raise ValueError('thrust_alloc_nn: tau is a contiguous float32 device tensor [3, n]')
+    n = int(tau.shape[1])
+    dnet = nn_net_to(net, tau.device)
+    a, keep = nn_allocator_struct(dnet, nn_allocator_params(net, **constants), tau.device)
+    act, p = (out if raw else (out, None)) if out is not None else (None, None)
+    if act is None:
+        act = torch.empty((n, 7), dtype=f32, device=tau.device)
+    if raw and p is None:
+        p = torch.empty((n, 6), dtype=f32, device=tau.device)
+    for t, shape, what in ((act, (n, 7), 'action'), (p, (n, 6), 'raw')):
+        if t is not None and (tuple(t.shape) != shape or t.dtype != f32 or t.device != tau.device or not t.is_contiguous()):
+            raise ValueError('thrust_alloc_nn: the %s buffer is a contiguous float32 tensor %s on tau\'s device' % (what, list(shape)))
+    s = C.c_void_p(torch.cuda.current_stream(tau.device).cuda_stream)
+    with torch.cuda.device(tau.device):
+        _lib.check(_lib.load().dpenv_thrust_alloc_nn(C.byref(a), C.c_void_p(tau.data_ptr()), C.c_void_p(act.data_ptr()),
+                                                     C.c_void_p(p.data_ptr()) if p is not None else None, n, s))
+    del keep
+    return (act, p) if raw else act

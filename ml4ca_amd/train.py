@@ -13,6 +13,7 @@ import math
 import numpy as np
 
 from . import _lib
+from ._num import _fma32          # (the exact host fmaf; deploy.BatchedNNAllocator shares it)
 
 HIDDEN = 80
 NSTAT_ACTOR, NSTAT_CRITIC = 4, 1          # pi_loss, approx_kl, clip_frac, mean_ratio | v_loss
@@ -283,21 +284,6 @@ def value_grad_ref(theta, obs, ret, leak=0.2):
     return _backward64(Ws, hs, zs, (2.0 * e / count)[:, None], leak), np.array([(e * e).mean()])
 
 
-def _fma32(a, b, c):
-    """fmaf on float32 operands, correctly rounded: the product is exact in float64, the sum is rounded to ODD there (TwoSum gives the
-    rounding error), and a round-to-odd float64 rounds to float32 as the exact value would."""
-    a, b, c = (np.asarray(x, np.float32).astype(np.float64) for x in (a, b, c))
-    p = a * b
-    s = p + c
-    bb = s - p
-    err = (p - (s - bb)) + (c - bb)
-    s = np.atleast_1d(s).copy()
-    err = np.broadcast_to(np.atleast_1d(err), s.shape)
-    fix = (err != 0) & ((s.view(np.int64) & 1) == 0) & np.isfinite(s)
-    s[fix] = np.nextafter(s[fix], np.where(err[fix] > 0, np.inf, -np.inf))
-    return s.astype(np.float32)
-
-
 def _powi(b, e):
     p, b = 1.0, float(b)
     while e > 0:
@@ -324,6 +310,51 @@ def adam_step_ref(theta, grad, m, v, step, lr, beta1=0.9, beta2=0.999, eps=1e-8,
     denom = np.sqrt(v2) / bc2s + f(eps)
     theta2 = _fma32(-step_size, m2 / denom, theta)
     return theta2, m2, v2, t, int(stop)
+
+
+# ---- the supervised thrust allocator (src/sl/FFNN.py, train.py): an MSE fit with the imitation gradient and the Adam step above ----------
+def fit_nn_allocator(dataset, in_dim=9, iters=200, lr=1e-3, minibatch=256, seed=0, leak=0.2, device='cuda:0'):
+    """Fit the neural thrust allocator (include/dpenv.h, "the neural thrust allocation") to a dataset of deploy.nn_allocator_dataset:
+    FFNN.py's loss and optimiser - mean squared error, Adam - as `iters` steps of dpenv_imitation_grad(MSE) + dpenv_adam_step on
+    minibatches drawn with a seeded generator, everything on the device, nothing read back inside the loop.  The network is the fused
+    update's shape {in_dim, 80, 80, 80, 6} with the leaky-relu slope `leak` (0 = the reference's relu; the reference's 20-wide shape
+    and every other hidden shape are flown by the allocator but not fitted here); the update sees it as an actor, whose log_std tail
+    is carried and ignored.  in_dim 9: the dataset's inputs as they are; 3: its last three columns (the scaled wrench alone).
+    Returns dict(W, b - views of the flat parameter tensor on the device, what env.set_nn_allocator and policy.thrust_alloc_nn read in
+    place - leak, theta, mse_initial, mse_final: the loss mean_rows(sum_j (out_j - y_j)^2) over the WHOLE dataset before and after)."""
+    torch = _torch()
+    f32 = torch.float32
+    x, y = np.asarray(dataset['x'], np.float32), np.asarray(dataset['y'], np.float32)
+    if in_dim not in (3, 9) or x.shape[1] < in_dim or y.shape != (x.shape[0], 6):
+        raise ValueError('fit_nn_allocator: in_dim is 3 or 9, the dataset has x [rows, >= in_dim] and y [rows, 6]')
+    rows = x.shape[0]
+    x = torch.as_tensor(np.ascontiguousarray(x[:, x.shape[1] - in_dim:])).to(device)
+    y = torch.as_tensor(np.ascontiguousarray(y)).to(device)
+    L = layout(in_dim, 6, True)
+    rng = np.random.RandomState(seed)
+    Ws, bs = [], []
+    for i in range(4):                                           # glorot-uniform, zero biases (tf.layers.dense's default, as policy.ActorCritic)
+        lim = math.sqrt(6.0 / (L['sizes'][i] + L['sizes'][i + 1]))
+        Ws.append(rng.uniform(-lim, lim, size=(L['sizes'][i], L['sizes'][i + 1])).astype(np.float32))
+        bs.append(np.zeros(L['sizes'][i + 1], np.float32))
+    theta = torch.as_tensor(flatten(Ws, bs, np.zeros(6, np.float32))).to(device)
+    P = L['P']
+    m, v = torch.zeros(P, dtype=f32, device=device), torch.zeros(P, dtype=f32, device=device)
+    step = torch.zeros(1, dtype=torch.int32, device=device)
+    sh = make_shape(in_dim, 6, True, leak=leak)
+    count = min(int(minibatch), rows)
+    ws = torch.empty((workspace_bytes(sh, rows) + 3) // 4, dtype=f32, device=device)
+    g = torch.empty(P + NSTAT_ACTOR, dtype=f32, device=device)
+    gen = torch.Generator(device='cpu')
+    gen.manual_seed(int(seed))
+    idx_all = torch.stack([torch.randperm(rows, generator=gen)[:count] for _ in range(int(iters))]).to(torch.int32).to(device)
+    mse0 = float(imitation_grad(theta, x, y, loss='mse', out=g, workspace=ws, leak=leak)[P])
+    for it in range(int(iters)):
+        imitation_grad(theta, x, y, loss='mse', idx=idx_all[it], out=g, workspace=ws, leak=leak, count=count)
+        adam_step(theta, g, m, v, step, lr)
+    mse1 = float(imitation_grad(theta, x, y, loss='mse', out=g, workspace=ws, leak=leak)[P])
+    tW, tb, _ = unflatten(theta, in_dim, 6, True)
+    return dict(W=list(tW), b=list(tb), leak=float(leak), theta=theta, mse_initial=mse0, mse_final=mse1)
 
 
 # ---- the whole update ----------------------------------------------------------------------------------------------------------------

@@ -26,6 +26,8 @@ env.step, critic, trajectory rows), GAE by one scan kernel, advantage statistics
                                                                                       (test_policy.py:97-186) and the box test (IAE, energy) on the NOMINAL hull
     python examples/train_ppo.py --envs 4096 --epochs 30 --eval --nn-allocator 5000   ... with the supervised neural allocator (src/sl) fitted and flown
                                                                                       behind the baseline's PID beside the pseudo-inverse and the QP
+    python examples/train_ppo.py --envs 4096 --epochs 30 --eval --nn-allocator 5000 --nn-loss wrench --nn-w-power 0.05
+                                                                                      ... the same network trained through the force map (the allocation loss)
 """
 import argparse
 import os
@@ -359,6 +361,10 @@ def main():
     ap.add_argument('--nn-allocator', type=int, default=0, metavar='ITERS', help='with --eval: fit the supervised neural allocator (9-80-80-80-6, '
                     'train.fit_nn_allocator: ITERS Adam steps on 16 384 rows of deploy.nn_allocator_dataset for the preset\'s hull) and fly it behind the '
                     'baseline\'s PID on every box test, beside the pseudo-inverse and the QP')
+    ap.add_argument('--nn-loss', choices=('mse', 'wrench'), default='mse', help="with --nn-allocator: 'mse' regresses the network on the dataset's (u, alpha) "
+                    "labels (FFNN.py); 'wrench' trains it through the force map with the allocation loss (train.allocation_grad: the QP's objective at "
+                    'the network\'s output, no labels)')
+    ap.add_argument('--nn-w-power', type=float, default=None, metavar='X', help="with --nn-loss wrench: the loss's w_power (default: the QP's, 1)")
     ap.add_argument('--eval-envs', type=int, default=1024, help='envs per --eval box test; 1024 (the default) scores the resident rows as before, any other '
                                                                 'value flies the test in 50-step launches scored on the device (evaluate.ScoreCard), e.g. 65536')
     ap.add_argument('--eval-presets', default='', help="comma-separated presets to run --eval on (default: the training preset), e.g. 'no_loss,thrust_loss': "
@@ -498,10 +504,14 @@ def main():
                 nn_net = None
                 if args.nn_allocator > 0:
                     from ml4ca_amd.deploy import nn_allocator_dataset
-                    from ml4ca_amd.train import fit_nn_allocator
-                    nn_net = fit_nn_allocator(nn_allocator_dataset(16384, args.seed, vessel=ml4ca_amd.default_vessel(pz)), iters=args.nn_allocator,
-                                              seed=args.seed, device=dev)
-                    print('eval  neural allocator fitted in %d Adam steps: MSE %.4g -> %.4g' % (args.nn_allocator, nn_net['mse_initial'], nn_net['mse_final']))
+                    from ml4ca_amd.train import alloc_loss_params, fit_nn_allocator
+                    hull = ml4ca_amd.default_vessel(pz)
+                    wrench = alloc_loss_params(None if args.nn_w_power is None else dict(w_power=args.nn_w_power), vessel=hull)
+                    nn_net = fit_nn_allocator(nn_allocator_dataset(16384, args.seed, vessel=hull), iters=args.nn_allocator, seed=args.seed, device=dev,
+                                              loss=args.nn_loss, alloc_loss=wrench)
+                    print('eval  neural allocator fitted in %d Adam steps, loss %s%s: label MSE %.4g -> %.4g, mean wrench residual Js %.4g -> %.4g N^2' % (
+                        args.nn_allocator, args.nn_loss, ' (w_power %g)' % wrench['w_power'] if args.nn_loss == 'wrench' else '', nn_net['mse_initial'],
+                        nn_net['mse_final'], nn_net['wrench_ms_initial'], nn_net['wrench_ms_final']))
                 evaluate_actor(ac, dev, pz, 'f32', args.seed, eval_envs=args.eval_envs, nn_net=nn_net)
                 if args.tune_baseline > 0:
                     tune_baseline(ac, dev, pz, 'f32', args.tune_baseline, seed=args.seed)

@@ -1162,6 +1162,59 @@ int dpenv_value_grad(const dpenv_train_shape* shape, const float* theta, const f
 int dpenv_imitation_grad(const dpenv_train_shape* shape, const float* theta, const float* obs, const float* act, const float* weight,
                          const int32_t* idx, int32_t count, int32_t n_rows, int32_t loss, const int32_t* stop_flag, float* grad_out,
                          void* workspace, int64_t workspace_bytes, dpenv_stream s);
+/* ALLOCATION LOSS (additive to ABI 6): the gradient that trains the neural thrust allocator THROUGH THE FORCE MAP instead of on (u, alpha)
+ * labels.  The inverse map tau -> (u, alpha) is one-to-many, so a regression on labels averages over solutions; the wrench a command
+ * produces is a single-valued, differentiable function of the network's output, and the loss is the QP law's own objective evaluated
+ * there: the weighted wrench residual, |F|^3 power and a penalty for thrust commands outside +-1.  It needs no labels, and its w_power is
+ * the knob that turns the QP's point into a front.  No rate terms: the network has no memory of x^-.
+ * The network is the fused update's actor shape {in, 80, 80, 80, 6} with in = 3 or 9 (dpenv_nn_allocator's inputs); its log_std tail is
+ * carried and gets the gradient +0.0, as bits.  Rows: x [n_rows][in] the network's inputs; tau_rows [n_rows][6], columns 0..2 the demanded
+ * wrench tau in N, N, Nm - UNSCALED, the scaled wrench is among the inputs - and columns 3..5 fetched but never entering a result (they
+ * may hold anything, NaN included); weight [n_rows] or NULL = 1.  idx, count, n_rows, stop_flag, the workspace, the first-call rule,
+ * ARITHMETIC and DETERMINISM are dpenv_imitation_grad's: the same kernel body with a fifth per-row stage.
+ * Per row, in f32, in exactly this order (-ffp-contract=off: no product below is fused into a sum; the only fused operations are inside
+ * sincos, which is the library's call-free polynomial sincos_lean - max abs error 9.2e-8 - as in the QP law and the neural allocation;
+ * clip(v, lo, hi) = fminf(fmaxf(v, lo), hi)), with the network's output p = (u_port, u_star, u_bow, a_port, a_star, a_bow), the
+ * allocator's own order, and the env order i = bow, port, star <-> j(i) = 2, 0, 1:
+ *     n_i = 100 * clip(p_j, -1, 1);   K_i = n_i >= 0 ? kf_i : kr_i;   F_i = (K_i * n_i) * |n_i|          (the env's thrust law)
+ *     e_i = fmaxf(|p_j| - 1, 0);      dF_i = |p_j| <= 1 ? (200 * K_i) * |n_i| : 0                          (dF_i/dp_j; 0 outside the clip)
+ *     a_k = azimuth_mode == 0 ? p_{3+k} * angle_scale : azimuth[k]                                         k = port, star
+ *     (s_k, c_k) = sincos(a_k);  b3_k, r_0, r_1, r_2, Js, Jp: the lines of "evaluate(x)" of the QP law above, x = (F_b, F_p, F_s, a_p, a_s) -
+ *                                the bow thruster is pure sway there, column (0, 1, lx_b)
+ *     Jx = (e_b * e_b + e_p * e_p) + e_s * e_s
+ *     J  = 0.5 * ((Js + w_power * Jp) + w_sat * Jx)
+ *     L  = (1/count) sum_rows w_row * J_row
+ * Output gradient, with wr_m = w_slack_m * r_m and Jm the QP law's Jacobian (its step 1):
+ *     gF_i       = ((Jm[0][i] * wr_0 + Jm[1][i] * wr_1) + Jm[2][i] * wr_2) + (1.5 * w_power) * (F_i * |F_i|)
+ *     dL/dp_j(i) = w_row * (gF_i * dF_i + w_sat * copysignf(e_i, p_j)) / count
+ *     ga_k       = (Jm[0][a_k] * wr_0 + Jm[1][a_k] * wr_1) + Jm[2][a_k] * wr_2,   Jm[.][a_k] = (-(F_k * s_k), F_k * c_k, F_k * (lx_k * c_k + ly_k * s_k))
+ *     dL/dp_3+k  = azimuth_mode == 0 ? w_row * (angle_scale * ga_k) / count : +0.0
+ *     dL/dp_5    = +0.0   (a_bow is not used: the tunnel thruster is fixed)
+ * At |p_j| = 1 exactly the thrust's slope is taken (|p_j| <= 1) and e_i = 0.  1/count stays with the reduction, as for the other stages.
+ * STATISTICS, grad_out[P .. P+3]:  L,  (1/count) sum w Js,  (1/count) sum w Jp,  (1/count) sum w Jx.  The buffer is the actor's float[P + 4].
+ * The divisor is count, not sum(w).  A zero-weight row contributes exactly zero; its x and tau must still be finite.
+ * The loss means what the deployed law does: for the p of dpenv_thrust_alloc_nn (raw_out) and azimuth_mode 0, r is the wrench
+ * dpenv_thrust_map's law without inflow loss gives that call's action, minus tau.  ml4ca_amd.train.allocation_grad_ref is the host statement.
+ * Refused with DPENV_EINVAL, launching and touching nothing, the field named in dpenv_last_error(NULL): a wrong struct_size, a critic
+ * shape, sizes[0] outside {3, 9}, an output width other than 6, a number that is not finite, a weight (w_slack, w_power, w_sat) < 0, kf or
+ * kr <= 0, an azimuth_mode other than 0 and 1, and everything dpenv_imitation_grad refuses for the arguments they share. */
+typedef struct dpenv_alloc_loss {
+    uint32_t struct_size;
+    float w_slack[3];        /* >= 0 */
+    float w_power;           /* >= 0 */
+    float w_sat;             /* >= 0: the weight of the commands' excess over +-1 */
+    float lx[3], ly[3];      /* lever arms [m]: bow, port, star, finite (ly[0] is not used) */
+    float kf[3], kr[3];      /* thrust constants ahead / astern, > 0 */
+    float angle_scale;       /* dpenv_nn_allocator's */
+    int32_t azimuth_mode;    /* 0: the network's stern angles; 1: fixed at azimuth[2] (then the angle outputs get no gradient) */
+    float azimuth[2];        /* port, star [rad], read in mode 1 */
+} dpenv_alloc_loss;
+/* The QP's default w_slack (1, 1, 1) and w_power 1, w_sat = 100, the default hull's lever arms and thrust constants
+ * (dpenv_qp_allocator_defaults) and the neural allocator's angle_scale, azimuth_mode and azimuth (dpenv_nn_allocator_defaults). */
+int dpenv_alloc_loss_defaults(dpenv_alloc_loss* q);
+int dpenv_allocation_grad(const dpenv_train_shape* shape, const dpenv_alloc_loss* loss, const float* theta, const float* x,
+                          const float* tau_rows, const float* weight, const int32_t* idx, int32_t count, int32_t n_rows,
+                          const int32_t* stop_flag, float* grad_out, void* workspace, int64_t workspace_bytes, dpenv_stream s);
 /* ADAM, torch.optim.Adam's update (bias correction and eps placement included; not TF's variant).  theta, grad, m, v: device float[P],
  * 16-byte aligned.  step_counter: device int32, the steps taken so far.  With t = *step_counter + 1, every operation in f32 and
  * correctly rounded unless marked f64:

@@ -136,6 +136,12 @@ class TrainShape(C.Structure):
                 ('leak', C.c_float), ('row_dtype', C.c_int32), ('log_std', C.c_int32)]
 
 
+class AllocLoss(C.Structure):
+    _fields_ = [('struct_size', C.c_uint32), ('w_slack', C.c_float * 3), ('w_power', C.c_float), ('w_sat', C.c_float), ('lx', C.c_float * 3),
+                ('ly', C.c_float * 3), ('kf', C.c_float * 3), ('kr', C.c_float * 3), ('angle_scale', C.c_float), ('azimuth_mode', C.c_int32),
+                ('azimuth', C.c_float * 2)]
+
+
 # read slots of the score card (dpenv.h DPENV_SCORE_*)
 SCORE_IAE, SCORE_WORK, SCORE_RET, SCORE_LEN, SCORE_EPISODES, SCORE_EP_IAE, SCORE_EP_WORK, SCORE_EP_RET, SCORE_EP_LEN, SCORE_NOUT = 0, 1, 4, 5, 6, 7, 8, 11, 12, 13
 
@@ -229,6 +235,8 @@ SYMBOLS = {
     'dpenv_ppo_actor_grad': (C.c_int, [C.POINTER(TrainShape), _VP, _VP, _VP, _VP, _VP, _VP, _I32, _I32, _F, _VP, _VP, _VP, _I64, _VP]),
     'dpenv_value_grad': (C.c_int, [C.POINTER(TrainShape), _VP, _VP, _VP, _VP, _I32, _I32, _VP, _VP, _I64, _VP]),
     'dpenv_imitation_grad': (C.c_int, [C.POINTER(TrainShape), _VP, _VP, _VP, _VP, _VP, _I32, _I32, _I32, _VP, _VP, _VP, _I64, _VP]),
+    'dpenv_alloc_loss_defaults': (C.c_int, [C.POINTER(AllocLoss)]),
+    'dpenv_allocation_grad': (C.c_int, [C.POINTER(TrainShape), C.POINTER(AllocLoss), _VP, _VP, _VP, _VP, _VP, _I32, _I32, _VP, _VP, _VP, _I64, _VP]),
     'dpenv_adam_step': (C.c_int, [_VP, _VP, _VP, _VP, _I32, _F, _F, _F, _F, _VP, _VP, _F, _VP, _VP]),
 }
 

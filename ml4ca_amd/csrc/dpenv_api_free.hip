@@ -691,6 +691,76 @@ extern "C" int dpenv_imitation_grad(const dpenv_train_shape* shape, const float*
     return DPENV_OK;
 }
 
+// ---- the allocation loss (dpenv.h, ALLOCATION LOSS): dpenv_imitation_grad's conventions with the loss's numbers in a struct of their own ----
+extern "C" int dpenv_alloc_loss_defaults(dpenv_alloc_loss* q)
+{
+    if (!q) return fail(nullptr, DPENV_EINVAL, "dpenv_alloc_loss_defaults: q is NULL");
+    dpenv_qp_allocator qp;
+    dpenv_nn_allocator nn;
+    if (int rc = dpenv_qp_allocator_defaults(&qp)) return rc;
+    if (int rc = dpenv_nn_allocator_defaults(&nn)) return rc;
+    *q = dpenv_alloc_loss{};
+    q->struct_size = sizeof(dpenv_alloc_loss);
+    for (int k = 0; k < 3; ++k) {
+        q->w_slack[k] = qp.w_slack[k];
+        q->lx[k] = qp.lx[k]; q->ly[k] = qp.ly[k]; q->kf[k] = qp.kf[k]; q->kr[k] = qp.kr[k];
+    }
+    q->w_power = qp.w_power;
+    q->w_sat = 100.0f;
+    q->angle_scale = nn.angle_scale;
+    q->azimuth_mode = nn.azimuth_mode;
+    q->azimuth[0] = nn.azimuth[0]; q->azimuth[1] = nn.azimuth[1];
+    return DPENV_OK;
+}
+
+static const char* alloc_loss_check(const dpenv_alloc_loss* q, AllocLossArgs* out)
+{
+    if (!q) return "loss is NULL";
+    if (q->struct_size != sizeof(dpenv_alloc_loss)) return "dpenv_alloc_loss ABI mismatch (struct_size)";
+    for (int k = 0; k < 3; ++k) {
+        if (!std::isfinite(q->w_slack[k]) || q->w_slack[k] < 0.0f) return "w_slack must be finite and >= 0";
+        if (!std::isfinite(q->lx[k])) return "lx must be finite";
+        if (!std::isfinite(q->ly[k])) return "ly must be finite";
+        if (!std::isfinite(q->kf[k]) || q->kf[k] <= 0.0f) return "kf must be finite and > 0";
+        if (!std::isfinite(q->kr[k]) || q->kr[k] <= 0.0f) return "kr must be finite and > 0";
+    }
+    if (!std::isfinite(q->w_power) || q->w_power < 0.0f) return "w_power must be finite and >= 0";
+    if (!std::isfinite(q->w_sat) || q->w_sat < 0.0f) return "w_sat must be finite and >= 0";
+    if (!std::isfinite(q->angle_scale)) return "angle_scale must be finite";
+    if (q->azimuth_mode != 0 && q->azimuth_mode != 1) return "azimuth_mode must be 0 (the network's stern angles) or 1 (fixed at azimuth)";
+    if (!std::isfinite(q->azimuth[0]) || !std::isfinite(q->azimuth[1])) return "azimuth must be finite";
+    for (int k = 0; k < 3; ++k) {
+        out->ws[k] = q->w_slack[k]; out->lx[k] = q->lx[k]; out->ly[k] = q->ly[k]; out->kf[k] = q->kf[k]; out->kr[k] = q->kr[k];
+    }
+    out->wp = q->w_power; out->wsat = q->w_sat; out->angle_scale = q->angle_scale; out->azimuth_mode = q->azimuth_mode;
+    out->azimuth[0] = q->azimuth[0]; out->azimuth[1] = q->azimuth[1];
+    return nullptr;
+}
+
+extern "C" int dpenv_allocation_grad(const dpenv_train_shape* shape, const dpenv_alloc_loss* loss, const float* theta, const float* x,
+                                     const float* tau_rows, const float* weight, const int32_t* idx, int32_t count, int32_t n_rows,
+                                     const int32_t* stop_flag, float* grad_out, void* workspace, int64_t workspace_bytes, dpenv_stream s)
+{
+    const char* who = "dpenv_allocation_grad";
+    GradArgs a = {};
+    AllocLossArgs q = {};
+    if (const char* why = train_shape_check(shape, &a.L)) return fail(nullptr, DPENV_EINVAL, "%s: %s", who, why);
+    if (!a.L.actor) return fail(nullptr, DPENV_EINVAL, "%s: the shape's log_std = 0 is a critic's; the allocator is fitted as an actor", who);
+    if (a.L.in_dim != 3 && a.L.in_dim != 9)
+        return fail(nullptr, DPENV_EINVAL, "%s: sizes[0] = %d, the allocator's input width must be 3 or 9", who, a.L.in_dim);
+    if (a.L.out_dim != 6) return fail(nullptr, DPENV_EINVAL, "%s: the output width is %d, the allocator's must be 6", who, a.L.out_dim);
+    if (const char* why = alloc_loss_check(loss, &q)) return fail(nullptr, DPENV_EINVAL, "%s: %s", who, why);
+    if (int rc = train_rows_check(who, a.L, idx, count, n_rows, workspace, workspace_bytes)) return rc;
+    if (!theta) return fail(nullptr, DPENV_EINVAL, "%s: theta is NULL", who);
+    if (!x) return fail(nullptr, DPENV_EINVAL, "%s: x is NULL", who);
+    if (!tau_rows) return fail(nullptr, DPENV_EINVAL, "%s: tau_rows is NULL", who);
+    if (!grad_out) return fail(nullptr, DPENV_EINVAL, "%s: grad_out is NULL", who);
+    a.theta = theta; a.obs = x; a.act = tau_rows; a.adv = weight; a.logp_old = nullptr; a.idx = idx; a.stop_flag = stop_flag;
+    a.partial = (float*)workspace; a.grad_out = grad_out; a.count = count; a.leak = shape->leak; a.clip = 0.0f;
+    HIP_TRY(nullptr, dev::launch_alloc_grad(&a, &q, (hipStream_t)s));
+    return DPENV_OK;
+}
+
 extern "C" int dpenv_adam_step(float* theta, const float* grad, float* m, float* v, int32_t P, float lr, float beta1, float beta2, float eps,
                                int32_t* step_counter, const float* gate_kl, float kl_limit, int32_t* stop_flag, dpenv_stream s)
 {

@@ -2,7 +2,8 @@
 // backward and the weight gradients of one in -> 80 -> 80 -> 80 -> out network on the matrix cores, one partial per workgroup),
 // grad_reduce_kernel (the partials summed in a fixed order) and the gated Adam step (adam_step_kernel + adam_commit_kernel).
 // imitation_grad_kernel<LOSS> (dpenv_imitation_grad) is the same body with a third per-row output stage: dpenv_train_grad_body.inc is
-// the one text of all four kernels, the stage chosen at compile time.
+// the one text of all four kernels, the stage chosen at compile time.  allocation_grad_kernel (dpenv_allocation_grad) is the same text
+// with a fifth stage - the QP law's objective at the network's output - and a second argument for that stage's numbers.
 //
 // Arithmetic: the exact-f32 MFMA v_mfma_f32_16x16x4_f32 (bit for bit a k-ordered fmaf chain).  80 = 5 x 16, so the hidden layers tile
 // without padding; the 9- or 6-wide input and the 7- or 1-wide output are padded to one 16-wide tile with zeros.  No operand split, no
@@ -22,6 +23,7 @@
 // of the same blocks, taken by one thread per column in row order.
 #include <mutex>
 
+#include "dpenv_env_dev.h"    // sincos_lean, the allocation stage's sin / cos (the QP law's and the neural allocator's)
 #include "dpenv_train_dev.h"
 
 namespace dpenv {
@@ -170,6 +172,16 @@ __global__ __launch_bounds__(256) void imitation_grad_kernel(GradArgs a)
 #include "dpenv_train_grad_body.inc"
 }
 
+// the allocation loss (dpenv_allocation_grad): the same body with the fifth per-row stage, whose numbers arrive in an argument of its
+// own - the other kernels' argument block, and with it their instruction streams, are what they were without it
+__global__ __launch_bounds__(256) void allocation_grad_kernel(GradArgs a, AllocLossArgs q)
+{
+    constexpr int STAGE = TR_STAGE_ALLOC;
+#define TR_BODY_ALLOC
+#include "dpenv_train_grad_body.inc"
+#undef TR_BODY_ALLOC
+}
+
 // grad_out[p] = (sum over the workgroups' partials, in workgroup order) / count
 __global__ __launch_bounds__(256) void grad_reduce_kernel(const float* partial, int nwg, int total, int count, const int32_t* stop_flag,
                                                           float* grad_out)
@@ -276,6 +288,31 @@ hipError_t dev::launch_mlp_grad(const GradArgs* a, int stage, hipStream_t s)
     case TR_STAGE_IMIT_NLL: hipLaunchKernelGGL(imitation_grad_kernel<0>, dim3(grid), dim3(256), lds_bytes, s, *a); break;
     default: hipLaunchKernelGGL(imitation_grad_kernel<1>, dim3(grid), dim3(256), lds_bytes, s, *a); break;
     }
+    hipLaunchKernelGGL(grad_reduce_kernel, dim3((total + 255) / 256), dim3(256), 0, s, (const float*)a->partial, grid, total, a->count, a->stop_flag,
+                       a->grad_out);
+    return hipGetLastError();
+}
+
+// the fifth stage: launch_mlp_grad's steps for the kernel with the second argument (the same grid, LDS size, first-call rule and reduction)
+hipError_t dev::launch_alloc_grad(const GradArgs* a, const AllocLossArgs* q, hipStream_t s)
+{
+    const int grid = train_grid(a->count);
+    const int total = a->L.P + TR_NSTAT_ACTOR;
+    const size_t lds_bytes = (size_t)LDS_FLOATS * sizeof(float);
+    const void* fn = reinterpret_cast<const void*>(&allocation_grad_kernel);
+    static std::once_flag once[64];
+    int devid = 0;
+    hipError_t e = hipGetDevice(&devid);
+    if (e != hipSuccess) return e;
+    if (devid >= 0 && devid < 64) {
+        hipError_t first = hipSuccess;
+        std::call_once(once[devid], [&] { first = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes); });
+        if (first != hipSuccess) return first;
+    } else {
+        e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
+        if (e != hipSuccess) return e;
+    }
+    hipLaunchKernelGGL(allocation_grad_kernel, dim3(grid), dim3(256), lds_bytes, s, *a, *q);
     hipLaunchKernelGGL(grad_reduce_kernel, dim3((total + 255) / 256), dim3(256), 0, s, (const float*)a->partial, grid, total, a->count, a->stop_flag,
                        a->grad_out);
     return hipGetLastError();

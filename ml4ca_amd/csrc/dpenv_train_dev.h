@@ -46,6 +46,9 @@ inline int train_grid(int count)
 
 // the per-row output stage of the gradient kernel, a template parameter of its body (dpenv_train.hip)
 constexpr int TR_STAGE_VALUE = 0, TR_STAGE_PPO = 1, TR_STAGE_IMIT_NLL = 2, TR_STAGE_IMIT_MSE = 3, TR_NSTAGE = 4;
+// the fifth stage, the allocation loss (dpenv_allocation_grad), has a kernel signature and a launcher of its own: its numbers travel in
+// AllocLossArgs beside GradArgs, so the four stages above keep their argument block and with it their instruction streams
+constexpr int TR_STAGE_ALLOC = 4;
 
 struct GradArgs {
     TrainLayout L;
@@ -62,6 +65,15 @@ struct GradArgs {
     float leak, clip;
 };
 
+// the allocation loss's numbers (dpenv_alloc_loss, validated by the entry point), env order bow, port, star
+struct AllocLossArgs {
+    float ws[3], wp, wsat;
+    float lx[3], ly[3], kf[3], kr[3];
+    float angle_scale;
+    int azimuth_mode;
+    float azimuth[2];        // port, star
+};
+
 struct AdamArgs {
     float* theta; const float* grad; float* m; float* v;
     int P;
@@ -75,6 +87,8 @@ struct AdamArgs {
 namespace __attribute__((visibility("hidden"))) dev {
 // dpenv_train.hip: the gradient (mlp_grad_kernel or imitation_grad_kernel + grad_reduce_kernel) and the gated Adam step (adam_step_kernel + adam_commit_kernel)
 hipError_t launch_mlp_grad(const GradArgs* a, int stage, hipStream_t s);   // stage: TR_STAGE_*
+// allocation_grad_kernel + grad_reduce_kernel: a->act holds the tau rows [n_rows][6], a->adv the row weight or NULL, a->logp_old and a->clip are not read
+hipError_t launch_alloc_grad(const GradArgs* a, const AllocLossArgs* q, hipStream_t s);
 hipError_t launch_adam_step(const AdamArgs* a, hipStream_t s);
 }  // namespace dev
 

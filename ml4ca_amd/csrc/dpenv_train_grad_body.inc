@@ -2,9 +2,15 @@
 // kernel holds the same text directly (a shared device function, even a forced-inline one, changes how the argument block is fetched
 // and with it the schedule of the existing kernels).  Expects in scope: the kernel's argument `GradArgs a` and `constexpr int STAGE`
 // (TR_STAGE_*), which selects the per-row output stage and what it fetches of a row at compile time.
+// The fifth stage, TR_STAGE_ALLOC (dpenv.h, ALLOCATION LOSS), reads numbers of its own, `AllocLossArgs q`, which only its kernel has:
+// everything it adds stands between #ifdef TR_BODY_ALLOC and #endif, so the text the other four kernels compile is the text without it.
     extern __shared__ float lds[];
     constexpr bool ACTOR = STAGE != TR_STAGE_VALUE;           // a policy network: actions and log_std
+#ifdef TR_BODY_ALLOC
+    constexpr bool IMIT = true;                               // a row is fetched as the imitation stages fetch it: the act slot (tau) and the weight or 1
+#else
     constexpr bool IMIT = STAGE == TR_STAGE_IMIT_NLL || STAGE == TR_STAGE_IMIT_MSE;
+#endif
     if (a.stop_flag && *a.stop_flag) return;                  // the gate has closed: the update is over (uniform over the grid)
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int lr = lane & 15, lk = lane >> 4;
@@ -97,6 +103,57 @@
             float* st = lds + O_ST + row * 4;
             if (g < a.count) {
                 const float* ra = lds + O_A + row * 8;
+#ifdef TR_BODY_ALLOC
+                if constexpr (STAGE == TR_STAGE_ALLOC) {
+                    // dpenv.h, ALLOCATION LOSS: the QP law's objective at the network's output p = d[0..5], tau = ra[0..2]; env order i = bow,
+                    // port, star reads p_j with j = 2, 0, 1.  Every index below is a compile-time constant once unrolled: no scratch.
+                    const float w = lds[O_AUX + row * 2];
+                    float F[3], e[3], dFdp[3], pj[3];
+#pragma unroll
+                    for (int i = 0; i < 3; ++i) {
+                        pj[i] = d[i == 0 ? 2 : i - 1];
+                        const float n = 100.0f * fminf(fmaxf(pj[i], -1.0f), 1.0f);
+                        const float K = n >= 0.0f ? q.kf[i] : q.kr[i];
+                        F[i] = (K * n) * fabsf(n);
+                        e[i] = fmaxf(fabsf(pj[i]) - 1.0f, 0.0f);
+                        dFdp[i] = fabsf(pj[i]) <= 1.0f ? (200.0f * K) * fabsf(n) : 0.0f;
+                    }
+                    float sn[2], cs[2], b3[2];
+#pragma unroll
+                    for (int k = 0; k < 2; ++k) {
+                        const float ang = q.azimuth_mode == 0 ? d[3 + k] * q.angle_scale : q.azimuth[k];
+                        sincos_lean(ang, sn[k], cs[k]);
+                        b3[k] = q.lx[1 + k] * sn[k] - q.ly[1 + k] * cs[k];
+                    }
+                    float r[3];
+                    r[0] = (cs[0] * F[1] + cs[1] * F[2]) - ra[0];
+                    r[1] = ((F[0] + sn[0] * F[1]) + sn[1] * F[2]) - ra[1];
+                    r[2] = ((q.lx[0] * F[0] + b3[0] * F[1]) + b3[1] * F[2]) - ra[2];
+                    const float Js = (q.ws[0] * (r[0] * r[0]) + q.ws[1] * (r[1] * r[1])) + q.ws[2] * (r[2] * r[2]);
+                    const float Jp = (fabsf(F[0]) * (F[0] * F[0]) + fabsf(F[1]) * (F[1] * F[1])) + fabsf(F[2]) * (F[2] * F[2]);
+                    const float Jx = (e[0] * e[0] + e[1] * e[1]) + e[2] * e[2];
+                    const float J = 0.5f * ((Js + q.wp * Jp) + q.wsat * Jx);
+                    const float wr[3] = {q.ws[0] * r[0], q.ws[1] * r[1], q.ws[2] * r[2]};
+                    // the Jacobian's force columns: bow (0, 1, lx_b), pods (c_k, s_k, b3_k); its angle columns F_k (-s_k, c_k, lx_k c_k + ly_k s_k)
+                    const float Jf[3][3] = {{0.0f, cs[0], cs[1]}, {1.0f, sn[0], sn[1]}, {q.lx[0], b3[0], b3[1]}};
+#pragma unroll
+                    for (int i = 0; i < 3; ++i) {
+                        const float gF = ((Jf[0][i] * wr[0] + Jf[1][i] * wr[1]) + Jf[2][i] * wr[2]) + (1.5f * q.wp) * (F[i] * fabsf(F[i]));
+                        d[i == 0 ? 2 : i - 1] = w * (gF * dFdp[i] + q.wsat * copysignf(e[i], pj[i]));
+                    }
+#pragma unroll
+                    for (int k = 0; k < 2; ++k) {
+                        const float d3 = q.lx[1 + k] * cs[k] + q.ly[1 + k] * sn[k];
+                        const float ga = (-(F[1 + k] * sn[k]) * wr[0] + (F[1 + k] * cs[k]) * wr[1]) + (F[1 + k] * d3) * wr[2];
+                        d[3 + k] = q.azimuth_mode == 0 ? w * (q.angle_scale * ga) : 0.0f;
+                    }
+                    for (int j = 5; j < TR_PAD; ++j) d[j] = 0.0f;       // a_bow is not used; the log_std part is +0.0
+                    st[0] = w * J;
+                    st[1] = w * Js;
+                    st[2] = w * Jp;
+                    st[3] = w * Jx;
+                } else
+#endif
                 if constexpr (IMIT) {
                     // dpenv.h, IMITATION LOSS: both losses' row statistics, the gradient of the chosen one
                     const float w = lds[O_AUX + row * 2];

@@ -1017,6 +1017,19 @@ def nn_allocator_defaults():
                 azimuth=np.array(NN_FIXED_AZIMUTH))
 
 
+ALLOC_LOSS_W_SAT = 100.0
+
+
+def alloc_loss_defaults(vessel=None):
+    """The allocation loss's default numbers (dpenv_alloc_loss_defaults; include/dpenv.h, ALLOCATION LOSS), env order bow, port, star: the
+    QP's slack and power weights, w_sat = 100 on the thrust commands' excess over +-1, the lever arms and thrust constants of `vessel`
+    (public parameter vector; None = the default hull) and the neural allocator's angle_scale, azimuth_mode and azimuth.  Returns the
+    dict train.allocation_grad, train.allocation_grad_ref and train.fit_nn_allocator(loss='wrench') take."""
+    qp, nn = qp_allocator_defaults(vessel), nn_allocator_defaults()
+    return dict(w_slack=qp['w_slack'], w_power=qp['w_power'], w_sat=ALLOC_LOSS_W_SAT, lx=qp['lx'], ly=qp['ly'], kf=qp['kf'], kr=qp['kr'],
+                angle_scale=nn['angle_scale'], azimuth_mode=nn['azimuth_mode'], azimuth=nn['azimuth'])
+
+
 def nn_allocator_params(net=None, **constants):
     """nn_allocator_defaults with `constants` on top; a net dict that carries 'leak' (train.fit_nn_allocator's does) supplies the leak
     unless constants names one."""

@@ -5,7 +5,9 @@ device-gated Adam step, so that the 80 + 80 gradient steps of an epoch (ppo.py:2
 the tensors of a ``policy.ActorCritic`` as views of two flat parameter vectors and runs the whole update, and - before it - the
 supervised warm start on demonstration rows (``pretrain`` / ``pretrain_critic``).  The host statements of the same law -
 ``ppo_actor_grad_ref`` / ``value_grad_ref`` / ``imitation_grad_ref`` (closed form, float64) and ``adam_step_ref`` (NumPy float32 in
-the header's operation order) - are what the tests hold the kernels to.  There is no fallback: without the library or a GPU the device functions raise.
+the header's operation order) - are what the tests hold the kernels to.  ``allocation_grad`` (host statement ``allocation_grad_ref``) is
+the same gradient kernel with the allocation loss - the QP law's objective at a thrust-allocator network's output, through the force map -
+and ``fit_nn_allocator`` fits that network with it or with the label MSE.  There is no fallback: without the library or a GPU the device functions raise.
 """
 import ctypes as C
 import math
@@ -181,6 +183,73 @@ def imitation_grad(theta, obs, act, loss='nll', weight=None, idx=None, out=None,
     return _grad_call(True, theta, obs, act, weight, None, 0.0, idx, out, workspace, leak, stop_flag, count, loss=_loss_code(loss))
 
 
+ALLOC_LOSS_FIELDS = ('w_slack', 'w_power', 'w_sat', 'lx', 'ly', 'kf', 'kr', 'angle_scale', 'azimuth_mode', 'azimuth')
+
+
+def alloc_loss_params(params=None, vessel=None):
+    """deploy.alloc_loss_defaults(vessel) with the entries of `params` on top (None = the defaults; a partial dict such as
+    dict(w_power=0.05) is enough)."""
+    from .deploy import alloc_loss_defaults
+    p = alloc_loss_defaults(vessel)
+    for k, v in (params or {}).items():
+        if k not in p:
+            raise ValueError('allocation loss: unknown number %r (known: %s)' % (k, sorted(p)))
+        p[k] = v
+    return p
+
+
+def alloc_loss_struct(params=None):
+    """The dpenv_alloc_loss of a dict of deploy.alloc_loss_defaults (None or partial: see alloc_loss_params)."""
+    p = alloc_loss_params(params)
+    q = _lib.AllocLoss()
+    q.struct_size = C.sizeof(_lib.AllocLoss)
+    for name in ('w_slack', 'lx', 'ly', 'kf', 'kr'):
+        v = np.asarray(p[name], np.float64).reshape(-1)
+        if v.shape != (3,):
+            raise ValueError('allocation loss: %s has three entries (bow, port, star)' % name)
+        getattr(q, name)[:] = [float(t) for t in v]
+    az = np.asarray(p['azimuth'], np.float64).reshape(-1)
+    if az.shape != (2,):
+        raise ValueError('allocation loss: azimuth has two entries (port, star)')
+    q.azimuth[:] = [float(t) for t in az]
+    q.w_power, q.w_sat, q.angle_scale, q.azimuth_mode = float(p['w_power']), float(p['w_sat']), float(p['angle_scale']), int(p['azimuth_mode'])
+    return q
+
+
+def allocation_grad(theta, x, tau, params=None, weight=None, idx=None, out=None, workspace=None, leak=0.2, stop_flag=None, count=None):
+    """dpenv_allocation_grad: the gradient of the allocation loss (include/dpenv.h, ALLOCATION LOSS) - the QP law's objective at the
+    network's output, through the force map - of the flat allocator network `theta` ({in, 80, 80, 80, 6} + the carried log_std tail, in =
+    3 or 9) over rows `idx` (int32; None = all rows) of x [n, in] (the network's inputs) and tau [n, 6] (columns 0..2 the demanded wrench
+    in N, N, Nm; 3..5 never enter a result), weight [n] or None = 1.  params: the dict of deploy.alloc_loss_defaults, whole or in part
+    (None = the defaults).  Returns out [P + 4]: the gradient, then L, the weighted mean Js (wrench residual), Jp (power) and Jx
+    (saturation).  Stream-ordered, nothing is read back."""
+    torch = _torch()
+    f32 = torch.float32
+    n_rows, in_dim = x.shape
+    sh = make_shape(in_dim, 6, True, leak=leak)
+    q = alloc_loss_struct(params)
+    P = layout(in_dim, 6, True)['P']
+    _req(theta, (P,), f32, 'theta')
+    _req(x, (n_rows, in_dim), f32, 'x')
+    _req(tau, (n_rows, 6), f32, 'tau')
+    _req(weight, (n_rows,), f32, 'weight')
+    _req(idx, None, torch.int32, 'idx')
+    _req(stop_flag, (1,), torch.int32, 'stop_flag')
+    if count is None:
+        count = int(idx.numel()) if idx is not None else n_rows
+    if idx is not None and int(count) > idx.numel():
+        raise ValueError('count = %d, idx holds %d indices' % (count, idx.numel()))
+    if out is None:
+        out = torch.empty(P + NSTAT_ACTOR, dtype=f32, device=theta.device)
+    _req(out, (P + NSTAT_ACTOR,), f32, 'out')
+    if workspace is None:
+        workspace = torch.empty((workspace_bytes(sh, max(count, 1)) + 3) // 4, dtype=f32, device=theta.device)
+    with torch.cuda.device(theta.device):
+        _lib.check(_lib.load().dpenv_allocation_grad(C.byref(sh), C.byref(q), _p(theta), _p(x), _p(tau), _p(weight), _p(idx), int(count), int(n_rows),
+                                                     _p(stop_flag), _p(out), _p(workspace), workspace.numel() * workspace.element_size(), _s(theta)))
+    return out
+
+
 def adam_step(theta, grad, m, v, step_counter, lr, beta1=0.9, beta2=0.999, eps=1e-8, gate_kl=None, kl_limit=float('inf'), stop_flag=None):
     """dpenv_adam_step: one torch.optim.Adam step of theta [P] with grad[:P] in place; step_counter int32 [1] counts the steps taken.
     gate_kl (float32 [1], e.g. the approx_kl slot of the gradient buffer) with stop_flag (int32 [1]): if the flag is set or
@@ -275,6 +344,54 @@ def imitation_grad_ref(theta, obs, act, loss, weight=None, leak=0.2):
     return grad, np.array([nll if code == _lib.IMITATE_NLL else mse, nll, mse, 0.0])
 
 
+def alloc_loss_terms(p, tau, params=None):
+    """The allocation loss's per-row terms at network outputs p [n, 6] for wrenches tau [n, >= 3] (include/dpenv.h, ALLOCATION LOSS), in
+    float64 on the struct's float32 numbers: dict(r [n, 3] the wrench residual, Js, Jp, Jx, J [n], dp [n, 6] = dJ/dp)."""
+    q = alloc_loss_params(params)
+    t = lambda v: np.asarray(v, np.float64).astype(np.float32).astype(np.float64)    # the struct's f32 numbers
+    ws, lx, ly, kf, kr, az = (t(q[k]) for k in ('w_slack', 'lx', 'ly', 'kf', 'kr', 'azimuth'))
+    wp, wsat, ascale, mode = float(t(q['w_power'])), float(t(q['w_sat'])), float(t(q['angle_scale'])), int(q['azimuth_mode'])
+    if mode not in (0, 1):
+        raise ValueError('allocation loss: azimuth_mode is 0 or 1')
+    p, tau = np.asarray(p, np.float64), np.asarray(tau, np.float64)
+    pj = p[:, [2, 0, 1]]                                                            # env order bow, port, star
+    n = 100.0 * np.clip(pj, -1.0, 1.0)
+    K = np.where(n >= 0, kf, kr)
+    F = (K * n) * np.abs(n)
+    e = np.maximum(np.abs(pj) - 1.0, 0.0)
+    dF = np.where(np.abs(pj) <= 1.0, (200.0 * K) * np.abs(n), 0.0)
+    a = p[:, 3:5] * ascale if mode == 0 else np.broadcast_to(az, (p.shape[0], 2))
+    s, c = np.sin(a), np.cos(a)
+    b3 = lx[1:] * s - ly[1:] * c
+    Fk = F[:, 1:]
+    r = np.stack([(c * Fk).sum(1) - tau[:, 0], (F[:, 0] + (s * Fk).sum(1)) - tau[:, 1], (lx[0] * F[:, 0] + (b3 * Fk).sum(1)) - tau[:, 2]], 1)
+    Js, Jp, Jx = (ws * (r * r)).sum(1), (np.abs(F) * (F * F)).sum(1), (e * e).sum(1)
+    J = 0.5 * ((Js + wp * Jp) + wsat * Jx)
+    wr = ws * r
+    gF = np.empty_like(F)
+    gF[:, 0] = wr[:, 1] + lx[0] * wr[:, 2]                                          # the bow thruster is pure sway: column (0, 1, lx_b)
+    gF[:, 1:] = (c * wr[:, 0:1] + s * wr[:, 1:2]) + b3 * wr[:, 2:3]
+    gF = gF + (1.5 * wp) * (F * np.abs(F))
+    dp = np.zeros_like(p)
+    dp[:, [2, 0, 1]] = gF * dF + wsat * np.copysign(e, pj)
+    if mode == 0:
+        d3 = lx[1:] * c + ly[1:] * s
+        dp[:, 3:5] = ascale * ((-(Fk * s) * wr[:, 0:1] + (Fk * c) * wr[:, 1:2]) + (Fk * d3) * wr[:, 2:3])
+    return dict(r=r, Js=Js, Jp=Jp, Jx=Jx, J=J, dp=dp)
+
+
+def allocation_grad_ref(theta, x, tau, params, weight=None, leak=0.2):
+    """The header's allocation loss in closed form, float64: (grad [P], stats [4] = L, weighted mean Js, Jp, Jx).  x [n, in], tau [n, 3] or
+    [n, 6] (columns 3..5 are not read)."""
+    x = np.asarray(x, np.float64)
+    count, in_dim = x.shape
+    w = np.ones(count) if weight is None else np.asarray(weight, np.float64)
+    Ws, bs, _, hs, zs, p = _forward64(theta, x, in_dim, 6, True, leak)
+    t = alloc_loss_terms(p, tau, params)
+    grad = _backward64(Ws, hs, zs, (w / count)[:, None] * t['dp'], leak, np.zeros(6))
+    return grad, np.array([(w * t[k]).sum() / count for k in ('J', 'Js', 'Jp', 'Jx')])
+
+
 def value_grad_ref(theta, obs, ret, leak=0.2):
     """The critic's law in closed form, float64: (grad [P], stats [1] = v_loss)."""
     obs, ret = np.asarray(obs, np.float64), np.asarray(ret, np.float64)
@@ -312,49 +429,94 @@ def adam_step_ref(theta, grad, m, v, step, lr, beta1=0.9, beta2=0.999, eps=1e-8,
     return theta2, m2, v2, t, int(stop)
 
 
-# ---- the supervised thrust allocator (src/sl/FFNN.py, train.py): an MSE fit with the imitation gradient and the Adam step above ----------
-def fit_nn_allocator(dataset, in_dim=9, iters=200, lr=1e-3, minibatch=256, seed=0, leak=0.2, device='cuda:0'):
+# ---- the supervised thrust allocator (src/sl/FFNN.py, train.py): an MSE fit on (u, alpha) labels with the imitation gradient, or a fit
+# through the force map with the allocation gradient; the Adam step above either way ---------------------------------------------------
+FIT_LOSSES = ('mse', 'wrench')
+
+
+def nn_allocator_init(in_dim, seed):
+    """The flat float32 start of fit_nn_allocator: glorot-uniform kernels from numpy.random.RandomState(seed), zero biases
+    (tf.layers.dense's default, as policy.ActorCritic), a zero log_std tail."""
+    L = layout(in_dim, 6, True)
+    rng = np.random.RandomState(seed)
+    Ws, bs = [], []
+    for i in range(4):
+        lim = math.sqrt(6.0 / (L['sizes'][i] + L['sizes'][i + 1]))
+        Ws.append(rng.uniform(-lim, lim, size=(L['sizes'][i], L['sizes'][i + 1])).astype(np.float32))
+        bs.append(np.zeros(L['sizes'][i + 1], np.float32))
+    return flatten(Ws, bs, np.zeros(6, np.float32))
+
+
+def nn_allocator_minibatches(rows, count, iters, seed):
+    """fit_nn_allocator's minibatches [iters, count] (a CPU int64 tensor): the first `count` of a seeded torch.randperm per step."""
+    torch = _torch()
+    gen = torch.Generator(device='cpu')
+    gen.manual_seed(int(seed))
+    return torch.stack([torch.randperm(rows, generator=gen)[:count] for _ in range(int(iters))])
+
+
+def fit_nn_allocator(dataset, in_dim=9, iters=200, lr=1e-3, minibatch=256, seed=0, leak=0.2, device='cuda:0', loss='mse', alloc_loss=None):
     """Fit the neural thrust allocator (include/dpenv.h, "the neural thrust allocation") to a dataset of deploy.nn_allocator_dataset:
     FFNN.py's loss and optimiser - mean squared error, Adam - as `iters` steps of dpenv_imitation_grad(MSE) + dpenv_adam_step on
     minibatches drawn with a seeded generator, everything on the device, nothing read back inside the loop.  The network is the fused
     update's shape {in_dim, 80, 80, 80, 6} with the leaky-relu slope `leak` (0 = the reference's relu; the reference's 20-wide shape
     and every other hidden shape are flown by the allocator but not fitted here); the update sees it as an actor, whose log_std tail
     is carried and ignored.  in_dim 9: the dataset's inputs as they are; 3: its last three columns (the scaled wrench alone).
+    loss: 'mse' (the above, on the labels dataset['y']) or 'wrench': the same loop, initialisation and minibatches with
+    dpenv_allocation_grad on dataset['x'] and dataset['tau'] - the QP law's objective at the network's output, through the force map, no
+    labels (include/dpenv.h, ALLOCATION LOSS).  alloc_loss: that loss's numbers, the dict of deploy.alloc_loss_defaults whole or in part
+    (e.g. dict(w_power=0.05)); they also define the wrench figures below.
     Returns dict(W, b - views of the flat parameter tensor on the device, what env.set_nn_allocator and policy.thrust_alloc_nn read in
-    place - leak, theta, mse_initial, mse_final: the loss mean_rows(sum_j (out_j - y_j)^2) over the WHOLE dataset before and after)."""
+    place - leak, theta, loss; mse_initial, mse_final: mean_rows(sum_j (out_j - y_j)^2) over the WHOLE dataset before and after (None
+    without dataset['y']); J_initial, J_final, wrench_ms_initial, wrench_ms_final: the allocation loss and its mean Js - the mean squared
+    wrench residual [N^2] with the default w_slack - over the whole dataset before and after (None without dataset['tau']))."""
     torch = _torch()
     f32 = torch.float32
-    x, y = np.asarray(dataset['x'], np.float32), np.asarray(dataset['y'], np.float32)
-    if in_dim not in (3, 9) or x.shape[1] < in_dim or y.shape != (x.shape[0], 6):
-        raise ValueError('fit_nn_allocator: in_dim is 3 or 9, the dataset has x [rows, >= in_dim] and y [rows, 6]')
+    if loss not in FIT_LOSSES:
+        raise ValueError("fit_nn_allocator: loss must be 'mse' or 'wrench' (got %r)" % (loss,))
+    x = np.asarray(dataset['x'], np.float32)
+    y = np.asarray(dataset['y'], np.float32) if dataset.get('y') is not None else None
+    tau = np.asarray(dataset['tau'], np.float32) if dataset.get('tau') is not None else None
+    if in_dim not in (3, 9) or x.ndim != 2 or x.shape[1] < in_dim:
+        raise ValueError('fit_nn_allocator: in_dim is 3 or 9, the dataset has x [rows, >= in_dim]')
+    if (loss == 'mse' or y is not None) and (y is None or y.shape != (x.shape[0], 6)):
+        raise ValueError("fit_nn_allocator: loss='mse' fits the labels y [rows, 6]")
+    if (loss == 'wrench' or tau is not None) and (tau is None or tau.shape != (x.shape[0], 3)):
+        raise ValueError("fit_nn_allocator: loss='wrench' reads the wrenches tau [rows, 3]")
     rows = x.shape[0]
     x = torch.as_tensor(np.ascontiguousarray(x[:, x.shape[1] - in_dim:])).to(device)
-    y = torch.as_tensor(np.ascontiguousarray(y)).to(device)
-    L = layout(in_dim, 6, True)
-    rng = np.random.RandomState(seed)
-    Ws, bs = [], []
-    for i in range(4):                                           # glorot-uniform, zero biases (tf.layers.dense's default, as policy.ActorCritic)
-        lim = math.sqrt(6.0 / (L['sizes'][i] + L['sizes'][i + 1]))
-        Ws.append(rng.uniform(-lim, lim, size=(L['sizes'][i], L['sizes'][i + 1])).astype(np.float32))
-        bs.append(np.zeros(L['sizes'][i + 1], np.float32))
-    theta = torch.as_tensor(flatten(Ws, bs, np.zeros(6, np.float32))).to(device)
-    P = L['P']
+    if y is not None:
+        y = torch.as_tensor(np.ascontiguousarray(y)).to(device)
+    if tau is not None:                                          # the kernel's [rows, 6] target rows: the wrench, then three columns nothing reads
+        tau = torch.as_tensor(np.ascontiguousarray(np.concatenate([tau, np.zeros_like(tau)], 1))).to(device)
+    qp = alloc_loss_params(alloc_loss)
+    theta = torch.as_tensor(nn_allocator_init(in_dim, seed)).to(device)
+    P = layout(in_dim, 6, True)['P']
     m, v = torch.zeros(P, dtype=f32, device=device), torch.zeros(P, dtype=f32, device=device)
     step = torch.zeros(1, dtype=torch.int32, device=device)
     sh = make_shape(in_dim, 6, True, leak=leak)
     count = min(int(minibatch), rows)
     ws = torch.empty((workspace_bytes(sh, rows) + 3) // 4, dtype=f32, device=device)
     g = torch.empty(P + NSTAT_ACTOR, dtype=f32, device=device)
-    gen = torch.Generator(device='cpu')
-    gen.manual_seed(int(seed))
-    idx_all = torch.stack([torch.randperm(rows, generator=gen)[:count] for _ in range(int(iters))]).to(torch.int32).to(device)
-    mse0 = float(imitation_grad(theta, x, y, loss='mse', out=g, workspace=ws, leak=leak)[P])
+    idx_all = nn_allocator_minibatches(rows, count, iters, seed).to(torch.int32).to(device)
+
+    def whole(kind):                                             # a statistic over the whole dataset; `g` is scratch here, read back at once
+        if kind == 'mse':
+            return None if y is None else [float(imitation_grad(theta, x, y, loss='mse', out=g, workspace=ws, leak=leak)[P])]
+        return None if tau is None else [float(t) for t in allocation_grad(theta, x, tau, qp, out=g, workspace=ws, leak=leak)[P:P + 2]]
+
+    mse0, wr0 = whole('mse'), whole('wrench')
     for it in range(int(iters)):
-        imitation_grad(theta, x, y, loss='mse', idx=idx_all[it], out=g, workspace=ws, leak=leak, count=count)
+        if loss == 'mse':
+            imitation_grad(theta, x, y, loss='mse', idx=idx_all[it], out=g, workspace=ws, leak=leak, count=count)
+        else:
+            allocation_grad(theta, x, tau, qp, idx=idx_all[it], out=g, workspace=ws, leak=leak, count=count)
         adam_step(theta, g, m, v, step, lr)
-    mse1 = float(imitation_grad(theta, x, y, loss='mse', out=g, workspace=ws, leak=leak)[P])
+    mse1, wr1 = whole('mse'), whole('wrench')
     tW, tb, _ = unflatten(theta, in_dim, 6, True)
-    return dict(W=list(tW), b=list(tb), leak=float(leak), theta=theta, mse_initial=mse0, mse_final=mse1)
+    first = lambda s, k: None if s is None else s[k]
+    return dict(W=list(tW), b=list(tb), leak=float(leak), theta=theta, loss=loss, mse_initial=first(mse0, 0), mse_final=first(mse1, 0),
+                J_initial=first(wr0, 0), J_final=first(wr1, 0), wrench_ms_initial=first(wr0, 1), wrench_ms_final=first(wr1, 1))
 
 
 # ---- the whole update ----------------------------------------------------------------------------------------------------------------

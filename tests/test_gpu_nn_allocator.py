@@ -38,14 +38,15 @@ def _bits_equal(a, b):
     return bool(((a.view(np.uint32) == b.view(np.uint32)) | (np.isnan(a) & np.isnan(b))).all())
 
 
-def _check_against_host(net, leak, tau, mode=0, want_rest=None, need_heads=True):
+def _check_against_host(net, leak, tau, mode=0, want_rest=None, need_heads=True, **constants):
+    """constants: entries of deploy.nn_allocator_defaults other than leak and azimuth_mode, for both sides"""
     import torch
     from ml4ca_amd.deploy import BatchedNNAllocator, nn_allocator_defaults
     from ml4ca_amd.policy import thrust_alloc_nn
     n = tau.shape[0]
-    params = dict(nn_allocator_defaults(), leak=leak, azimuth_mode=mode)
+    params = dict(nn_allocator_defaults(), leak=leak, azimuth_mode=mode, **constants)
     host_act, host_p = BatchedNNAllocator(n, net, params=params).allocate(tau, raw=True)
-    act, p = thrust_alloc_nn(H.to_dev(np.ascontiguousarray(tau.T)), net, raw=True, leak=leak, azimuth_mode=mode)
+    act, p = thrust_alloc_nn(H.to_dev(np.ascontiguousarray(tau.T)), net, raw=True, leak=leak, azimuth_mode=mode, **constants)
     torch.cuda.synchronize()
     act, p = _np(act), _np(p)
     assert _bits_equal(p, host_p), 'raw_out: %d elements differ' % int((p.view(np.uint32) != host_p.view(np.uint32)).sum())
@@ -56,7 +57,7 @@ def _check_against_host(net, leak, tau, mode=0, want_rest=None, need_heads=True)
     if want_rest is not None:
         assert np.array_equal(rest, want_rest)
     ang32 = np.broadcast_to(np.asarray(params['azimuth'], np.float64).astype(np.float32), (n, 2)) if mode == 1 \
-        else host_p[:, 3:5] * np.float32(np.pi)
+        else host_p[:, 3:5] * np.float32(params['angle_scale'])
     with np.errstate(all='ignore'):
         fine = ~rest & (np.abs(ang32) <= 3.0e4).all(1)            # (beyond 3e4 rad the polynomial folds in f32 first: include/dpenv.h)
         ang = ang32.astype(np.float64)
@@ -132,7 +133,7 @@ def _env(n=NC, **kw):
     return H.make_pair('final_cont', n, **kw)[0]
 
 
-def _start(env, filt=False, nn=True, hulls=None, randomise=None):
+def _start(env, filt=False, nn=True, hulls=None, randomise=None, net=None, constants=None):
     import math
     import torch
     n = env.n_envs
@@ -146,7 +147,12 @@ def _start(env, filt=False, nn=True, hulls=None, randomise=None):
         env.set_reference_filter()
     env.set_dp_controller()
     if nn:                                                       # 'host': NumPy arrays (device_pointers = 0); else tensors on the device
-        env.set_nn_allocator(_net(None if nn == 'host' else env.device))
+        if net is None:                                          # (net: a dict of NumPy arrays in place of the 20-wide one)
+            net = _net()
+        if nn != 'host':
+            from ml4ca_amd.policy import nn_net_to
+            net = nn_net_to(net, env.device)
+        env.set_nn_allocator(net, **(constants or {}))
     env.reset()
     return env
 
@@ -166,8 +172,8 @@ def _refs(dev, n=NC):
 
 
 def _act_rows_are_the_parts(env, out, z0):
-    """act[t] = dpenv_thrust_alloc_nn on the tau the host PID (NumPy float32, bit for bit the kernel's) forms from obs[t], z carried and
-    zeroed behind a done row."""
+    """act[t] = dpenv_thrust_alloc_nn - the env's network with the env's constants - on the tau the host PID (NumPy float32, bit for bit
+    the kernel's) forms from obs[t], z carried and zeroed behind a done row."""
     import torch
     from ml4ca_amd.deploy import BatchedDPController
     from ml4ca_amd.policy import thrust_alloc_nn
@@ -176,11 +182,12 @@ def _act_rows_are_the_parts(env, out, z0):
     ctrl.z = np.ascontiguousarray(_np(z0).T)
     obs, done = _np(out['obs']), _np(out['done'])
     net = env.nn_allocator['net']
+    constants = {k: v for k, v in env.nn_allocator.items() if k != 'net'}
     for t in range(T):
         if t > 0:
             ctrl.reset(done[t - 1] != 0)
         tau = H.to_dev(np.ascontiguousarray(ctrl.wrench(obs[t]).T))
-        act = thrust_alloc_nn(tau, net)
+        act = thrust_alloc_nn(tau, net, **constants)
         assert torch.equal(act, out['act'][t]), (t, int((act != out['act'][t]).sum()))
     ctrl.reset(done[-1] != 0)
     assert np.array_equal(_np(env.get_dp_controller_state()).T.view(np.uint32), ctrl.z.view(np.uint32))

@@ -17,6 +17,8 @@ using namespace dpenv;
 using namespace dpenv::host;
 
 enum { LOSS_OFF = 0, LOSS_ON = 1, LOSS_UNKNOWN = 2 };
+// what allocates the wrench of the baseline's PID in dpenv_controller_rollout: exactly one of these
+enum { ALLOC_PINV = 0, ALLOC_QP, ALLOC_QP_TAB, ALLOC_NN };
 
 // A handle owns what it allocates: the destructor releases all of it, so a failed dpenv_create and dpenv_destroy are the same code.
 #pragma GCC visibility push(hidden)      // its constructor and destructor are no part of the library's symbol table
@@ -82,13 +84,15 @@ struct dpenv_s {
     ControlArgs ctrl = {};  // its numbers and per-env state (float4 [n]: z | pad), allocated by the first dpenv_set_dp_controller
     bool ctrl_tab_on = false;    // dpenv_set_dp_controller_table: env i flies row i of ctrl_tab instead of ctrl's numbers
     float4* ctrl_tab = nullptr;  // the packed per-env controller block (ctrl_tab_float4s(n) float4), allocated by the first dpenv_set_dp_controller_table
-    bool qp_on = false;     // dpenv_set_qp_allocator: dpenv_controller_rollout allocates the PID's wrench with the QP law of `qp`
-    QpRollout qp = {};      // its numbers and per-env thruster state (float [5][n]), allocated by the first dpenv_set_qp_allocator[_table]
+    // The allocation stage, ALLOC_*: the pseudo-inverse of `ctrl` (or of ctrl_tab's rows), the QP law with the numbers of `qp`
+    // (dpenv_set_qp_allocator) or with row i of qp_tab on env i, qp_tab_iters iterations (dpenv_set_qp_allocator_table), or the network of
+    // `nn` (dpenv_set_nn_allocator).  Invariants, kept by the setters (stage_refusal is their one statement) and relied on everywhere else:
+    //   ctrl_tab_on => stage == ALLOC_PINV;   stage != ALLOC_PINV => ctrl_on;   qp_scalar => stage is ALLOC_QP or ALLOC_QP_TAB.
+    int stage = ALLOC_PINV;
+    QpRollout qp = {};      // the QP's numbers and per-env thruster state (float [5][n]), allocated by the first dpenv_set_qp_allocator[_table]
     bool qp_scalar = false; // qp.q holds numbers dpenv_set_qp_allocator set: what dpenv_set_qp_allocator_table(NULL) returns to
-    bool qp_tab_on = false; // dpenv_set_qp_allocator_table (qp_on is set with it): env i flies row i of qp_tab, qp_tab_iters iterations
     float4* qp_tab = nullptr;    // the packed per-env QP block (qp_tab_float4s(n) float4), allocated by the first dpenv_set_qp_allocator_table
     int32_t qp_tab_iters = 0;
-    bool nn_on = false;     // dpenv_set_nn_allocator: dpenv_controller_rollout allocates the PID's wrench with the network of `nn`
     NnRollout nn = {};      // its constants and the layers' addresses inside nn_img
     float* nn_img = nullptr;     // the zero-padded weight image (NN_IMAGE_FLOATS floats: the largest shape), allocated by the first dpenv_set_nn_allocator
     int device = 0;
@@ -447,16 +451,20 @@ static int vessel_source(dpenv_handle h)
     return (h->shared_loss || (h->cur_rand && h->cfg.current_enabled)) ? VES_ARGS_LOSS : VES_ARGS;
 }
 
-// a per-env state block of count x n_envs float4 (integral action, reference filter, DP controller): allocated by the first call that turns
-// the feature on, kept while it is off, released with the handle
-static int ensure_env_state(dpenv_handle h, float4** block, int count, const char* msg)
+// a device block of a feature (integral action, reference filter, DP controller and its table, QP allocator and its table, NN image):
+// allocated by the first call that turns the feature on, kept while it is off, released with the handle
+template <class T>
+static int ensure_block(dpenv_handle h, T** block, size_t bytes, const char* msg)
 {
     if (*block) return DPENV_OK;
     void* p = nullptr;
-    if (hipMalloc(&p, sizeof(float4) * count * (size_t)h->cfg.n_envs) != hipSuccess) return fail(h, DPENV_ENOMEM, "%s", msg);
-    *block = (float4*)p;
+    if (hipMalloc(&p, bytes) != hipSuccess) return fail(h, DPENV_ENOMEM, "%s", msg);
+    *block = (T*)p;
     return DPENV_OK;
 }
+static size_t env_bytes(dpenv_handle h, size_t per_env) { return per_env * (size_t)h->cfg.n_envs; }
+
+static bool qp_flies(dpenv_handle h) { return h->stage == ALLOC_QP || h->stage == ALLOC_QP_TAB; }
 
 static int require_classes(dpenv_handle h)
 {
@@ -592,7 +600,7 @@ extern "C" int dpenv_reset(dpenv_handle h, const uint8_t* mask, const float* ini
     if (h->integ_on) HIP_TRY(h, dev::launch_integ_clear(h->integ.state, mask, h->cfg.n_envs, (hipStream_t)s));   // new episodes start with I = 0
     if (h->reff_on) HIP_TRY(h, dev::launch_reff_rest(a.RF, h->reff.state, mask, h->cfg.n_envs, (hipStream_t)s));   // ... the filter at rest
     if (h->ctrl_on) HIP_TRY(h, dev::launch_control_state(h->ctrl.z, nullptr, mask, h->cfg.n_envs, 2, (hipStream_t)s));   // ... the baseline's z = 0
-    if (h->qp_on) HIP_TRY(h, dev::launch_qp_state_clear(h->qp.state, mask, h->cfg.n_envs, (hipStream_t)s));               // ... and its QP allocator's thrusters at rest
+    if (qp_flies(h)) HIP_TRY(h, dev::launch_qp_state_clear(h->qp.state, mask, h->cfg.n_envs, (hipStream_t)s));               // ... and its QP allocator's thrusters at rest
     // the reset kernel writes the lagged thrust columns (S3) of the envs it re-draws: a full reset makes them valid everywhere, a
     // masked one leaves the validity of the other envs' columns as it was (it used to drop the lag of every env)
     if (!mask) h->lag_valid = true;
@@ -1046,7 +1054,7 @@ extern "C" int dpenv_set_reference_filter(dpenv_handle h, const dpenv_reference_
     float phi[3][9], gam[3][3];
     if (const char* why = reff_coeffs_f32(rf, h->cfg.substep_dt * (float)h->cfg.n_substeps, phi, gam)) return fail(h, DPENV_EINVAL, "%s", why);
     DeviceGuard dev_guard(h->device);
-    if (int rc = ensure_env_state(h, &f.state, 3, "hipMalloc of the reference filter state failed")) return rc;
+    if (int rc = ensure_block(h, &f.state, env_bytes(h, 3 * sizeof(float4)), "hipMalloc of the reference filter state failed")) return rc;
     std::memcpy(f.phi, phi, sizeof phi);
     std::memcpy(f.gam, gam, sizeof gam);
     f.out = nullptr;
@@ -1101,7 +1109,7 @@ extern "C" int dpenv_set_integral_action(dpenv_handle h, const dpenv_integral_ac
     while (D > 0 && (double)(D - 1) * dt > (double)ia->dwell_s) --D;
     while (!((double)D * dt > (double)ia->dwell_s)) ++D;
     DeviceGuard dev_guard(h->device);
-    if (int rc = ensure_env_state(h, &h->integ.state, 1, "hipMalloc of the integral state failed")) return rc;
+    if (int rc = ensure_block(h, &h->integ.state, env_bytes(h, sizeof(float4)), "hipMalloc of the integral state failed")) return rc;
     IntegArgs& g = h->integ;
     for (int j = 0; j < 3; ++j) { g.gain[j] = ia->gain[j]; g.bound[j] = ia->bound[j]; g.box[j] = ia->box[j]; }
     g.step_s = ia->step_s > 0.0f ? ia->step_s : h->cfg.substep_dt * (float)h->cfg.n_substeps;
@@ -1141,29 +1149,29 @@ static bool control_config_ok(dpenv_handle h)
            h->n_classes == 1 && !h->integ_on;
 }
 
+// back to the pseudo-inverse: a QP allocator, scalar or per-env (the held scalar numbers included), and a neural allocator are dropped
+static void allocator_off(dpenv_handle h) { h->stage = ALLOC_PINV; h->qp_scalar = false; }
+
 extern "C" int dpenv_set_dp_controller(dpenv_handle h, const dpenv_dp_controller* c, dpenv_stream s)
 {
     if (!h) return DPENV_EINVAL;
     if (!c) {
-        h->ctrl_on = false;
-        h->ctrl_tab_on = false;
-        h->qp_on = h->qp_scalar = h->qp_tab_on = false;
-        h->nn_on = false;
+        h->ctrl_on = h->ctrl_tab_on = false;
+        allocator_off(h);
         return DPENV_OK;
     }
     ControlArgs g = {};
     if (const char* why = control_check(c, g)) return fail(h, DPENV_EINVAL, "%s", why);
     if (!control_config_ok(h)) return fail(h, DPENV_EINVAL, "dpenv_set_dp_controller: " CONTROL_SET_MSG);
     DeviceGuard dev_guard(h->device);
-    if (int rc = ensure_env_state(h, &h->ctrl.z, 1, "hipMalloc of the DP controller state failed")) return rc;
+    if (int rc = ensure_block(h, &h->ctrl.z, env_bytes(h, sizeof(float4)), "hipMalloc of the DP controller state failed")) return rc;
     HIP_TRY(h, dev::launch_control_state(h->ctrl.z, nullptr, nullptr, h->cfg.n_envs, 2, (hipStream_t)s));   // (the block stays if this fails)
     g.z = h->ctrl.z;
     g.dt = h->cfg.substep_dt * (float)h->cfg.n_substeps;
     h->ctrl = g;
     h->ctrl_on = true;
     h->ctrl_tab_on = false;                                // the scalar law again: a table in force is dropped
-    h->qp_on = h->qp_scalar = h->qp_tab_on = false;        // ... and so is a QP allocator, scalar or per-env: the pseudo-inverse allocates again
-    h->nn_on = false;                                      // ... and a neural allocator
+    allocator_off(h);                                      // ... and so is a QP or a neural allocator: the pseudo-inverse allocates again
     return DPENV_OK;
 }
 
@@ -1179,6 +1187,27 @@ static_assert(CTRL_NPARAM == DPENV_CTRL_NPARAM && CTRL_KP == DPENV_CTRL_KP && CT
                   CTRL_LY == DPENV_CTRL_LY && CTRL_KF == DPENV_CTRL_KF && CTRL_KR_BOW == DPENV_CTRL_KR_BOW && CTRL_F_EPS == DPENV_CTRL_F_EPS,
               "the packing kernel's slots are the header's");
 
+// The rules between the allocation stages, once: may `want` allocate on this handle as it stands - for ALLOC_PINV: from a per-env controller
+// table?  NULL, or the refusal's text for behind "<caller>: ".  The setters ask before they change anything; dpenv_controller_rollout asks
+// again for the stage in force (the hull kind may have changed since the setter).  Where two rules refuse, the first one listed speaks.
+static const char* stage_refusal(dpenv_handle h, int want)
+{
+    switch (want) {
+    case ALLOC_PINV:                                       // (with a controller table: without one nothing stands against it)
+        if (qp_flies(h)) return QP_SET_MSG;
+        if (h->stage == ALLOC_NN) return "a neural allocator is set: " NN_SET_MSG;
+        return nullptr;
+    case ALLOC_QP: case ALLOC_QP_TAB:
+        if (h->stage == ALLOC_NN) return "a neural allocator is set: " NN_SET_MSG;
+        if (h->ctrl_tab_on || h->per_env) return QP_SET_MSG;
+        return nullptr;
+    default:                                               // ALLOC_NN
+        if (h->ctrl_tab_on) return "a per-env controller table is in force: " NN_SET_MSG;
+        if (qp_flies(h)) return "a QP allocator is set: " NN_SET_MSG;
+        return nullptr;
+    }
+}
+
 extern "C" int dpenv_set_dp_controller_table(dpenv_handle h, const float* table, uint8_t* refused_out, dpenv_stream s)
 {
     if (!h) return DPENV_EINVAL;
@@ -1187,15 +1216,10 @@ extern "C" int dpenv_set_dp_controller_table(dpenv_handle h, const float* table,
         h->ctrl_tab_on = false;
         return DPENV_OK;
     }
-    if (h->qp_on) return fail(h, DPENV_EINVAL, "dpenv_set_dp_controller_table: " QP_SET_MSG);
-    if (h->nn_on) return fail(h, DPENV_EINVAL, "dpenv_set_dp_controller_table: a neural allocator is set: " NN_SET_MSG);
+    if (const char* no = stage_refusal(h, ALLOC_PINV)) return fail(h, DPENV_EINVAL, "dpenv_set_dp_controller_table: %s", no);
     DeviceGuard dev_guard(h->device);
-    if (!h->ctrl_tab) {                                    // (whole waves of 64 envs: not ensure_env_state's count x n_envs)
-        void* p = nullptr;
-        if (hipMalloc(&p, sizeof(float4) * (size_t)ctrl_tab_float4s(h->cfg.n_envs)) != hipSuccess)
-            return fail(h, DPENV_ENOMEM, "hipMalloc of the DP controller table failed");
-        h->ctrl_tab = (float4*)p;
-    }
+    if (int rc = ensure_block(h, &h->ctrl_tab, sizeof(float4) * (size_t)ctrl_tab_float4s(h->cfg.n_envs),     // (whole waves of 64 envs)
+                              "hipMalloc of the DP controller table failed")) return rc;
     HIP_TRY(h, dev::launch_pack_controllers(table, h->ctrl_tab, refused_out, h->cfg.n_envs, (hipStream_t)s));
     h->ctrl_tab_on = true;
     return DPENV_OK;
@@ -1242,49 +1266,55 @@ extern "C" int dpenv_controller_rollout(dpenv_handle h, const dpenv_controller_r
     FilterArgs fa = h->reff;
     fa.out = io->ref_out;
     const int ves = rollout_ves(vessel_source(h));
-    // the handle may have changed since dpenv_set_qp_allocator
-    if (h->qp_on && (h->ctrl_tab_on || (ves != VES_ARGS && ves != VES_ARGS_LOSS))) return fail(h, DPENV_EINVAL, "dpenv_controller_rollout: " QP_SET_MSG);
-    if (h->nn_on) {                                        // the neural allocation behind the PID lines: its own kernels (dpenv_control_nn.hip)
-        if (h->ctrl_tab_on || h->qp_on) return fail(h, DPENV_EINVAL, "dpenv_controller_rollout: " NN_SET_MSG);
-        const hipError_t en = dev::launch_controller_rollout_nn(&a, &ca, h->reff_on ? &fa : nullptr, &h->nn, ves, (hipStream_t)s);
-        if (en != hipSuccess) return fail(h, DPENV_EHIP, "controller launch failed: %s", hipGetErrorString(en));
-        h->lag_valid = true;
-        return DPENV_OK;
+    // the handle may have changed since dpenv_set_qp_allocator: per-env hulls (with control_config_ok, the one way ves leaves the shared forms)
+    if (const char* no = stage_refusal(h, h->stage)) return fail(h, DPENV_EINVAL, "dpenv_controller_rollout: %s", no);
+    const FilterArgs* fp = h->reff_on ? &fa : nullptr;
+    hipError_t e;
+    if (h->stage == ALLOC_NN) {                            // the neural allocation behind the PID lines: its own kernels (dpenv_control_nn.hip)
+        e = dev::launch_controller_rollout_nn(&a, &ca, fp, &h->nn, ves, (hipStream_t)s);
+    } else {
+        QpRollout qr = h->qp;
+        if (h->stage == ALLOC_QP_TAB) qr.q.iters = h->qp_tab_iters;     // (of q only iters is read while the table flies)
+        e = dev::launch_controller_rollout(&a, &ca, fp, h->ctrl_tab_on ? h->ctrl_tab : nullptr, qp_flies(h) ? &qr : nullptr,
+                                           h->stage == ALLOC_QP_TAB ? h->qp_tab : nullptr, ves, (hipStream_t)s);
     }
-    QpRollout qr = h->qp;
-    if (h->qp_tab_on) qr.q.iters = h->qp_tab_iters;         // (of q only iters is read while the table flies)
-    const hipError_t e = dev::launch_controller_rollout(&a, &ca, h->reff_on ? &fa : nullptr, h->ctrl_tab_on ? h->ctrl_tab : nullptr,
-                                                        h->qp_on ? &qr : nullptr, h->qp_on && h->qp_tab_on ? h->qp_tab : nullptr, ves,
-                                                        (hipStream_t)s);
     if (e != hipSuccess) return fail(h, DPENV_EHIP, "controller launch failed: %s", hipGetErrorString(e));
     h->lag_valid = true;
     return DPENV_OK;
 }
 
 // ---- the QP allocation as the closed loop's allocation stage (dpenv.h) ----
+// What dpenv_set_qp_allocator and dpenv_set_qp_allocator_table refuse before they look at their numbers ...
+static int qp_setter_before(dpenv_handle h, const char* who)
+{
+    if (!h->ctrl_on) return fail(h, DPENV_EINVAL, "%s: the DP controller is off (dpenv_set_dp_controller first)", who);
+    if (h->stage == ALLOC_NN) return fail(h, DPENV_EINVAL, "%s: %s", who, stage_refusal(h, ALLOC_QP));
+    return DPENV_OK;
+}
+// ... and after them: the handle's configuration, the rest of the stage's rules, and the thruster state's block (on the handle's device)
+static int qp_setter_after(dpenv_handle h, const char* who)
+{
+    if (!control_config_ok(h)) return fail(h, DPENV_EINVAL, "%s: " CONTROL_SET_MSG, who);
+    if (const char* no = stage_refusal(h, ALLOC_QP)) return fail(h, DPENV_EINVAL, "%s: %s", who, no);
+    return ensure_block(h, &h->qp.state, env_bytes(h, 5 * sizeof(float)), "hipMalloc of the QP allocator state failed");
+}
+
 extern "C" int dpenv_set_qp_allocator(dpenv_handle h, const dpenv_qp_allocator* q, dpenv_stream s)
 {
     if (!h) return DPENV_EINVAL;
     if (!q) {
-        h->qp_on = h->qp_scalar = h->qp_tab_on = false;
+        if (qp_flies(h)) allocator_off(h);                 // (a neural allocator stays)
         return DPENV_OK;
     }
-    if (!h->ctrl_on) return fail(h, DPENV_EINVAL, "dpenv_set_qp_allocator: the DP controller is off (dpenv_set_dp_controller first)");
-    if (h->nn_on) return fail(h, DPENV_EINVAL, "dpenv_set_qp_allocator: a neural allocator is set: " NN_SET_MSG);
+    if (int rc = qp_setter_before(h, "dpenv_set_qp_allocator")) return rc;
     QpArgs g = {};
     if (const char* why = qp_check(q, h->ctrl.dt, g)) return fail(h, DPENV_EINVAL, "%s", why);
-    if (!control_config_ok(h)) return fail(h, DPENV_EINVAL, "dpenv_set_qp_allocator: " CONTROL_SET_MSG);
-    if (h->ctrl_tab_on || h->per_env) return fail(h, DPENV_EINVAL, "dpenv_set_qp_allocator: " QP_SET_MSG);
     DeviceGuard dev_guard(h->device);
-    if (!h->qp.state) {
-        void* p = nullptr;
-        if (hipMalloc(&p, sizeof(float) * 5 * (size_t)h->cfg.n_envs) != hipSuccess) return fail(h, DPENV_ENOMEM, "hipMalloc of the QP allocator state failed");
-        h->qp.state = (float*)p;
-    }
+    if (int rc = qp_setter_after(h, "dpenv_set_qp_allocator")) return rc;
     HIP_TRY(h, dev::launch_qp_state_clear(h->qp.state, nullptr, h->cfg.n_envs, (hipStream_t)s));   // (the block stays if this fails)
     h->qp.q = g;
-    h->qp_on = h->qp_scalar = true;
-    h->qp_tab_on = false;                                  // the scalar numbers replace a table in force
+    h->stage = ALLOC_QP;                                   // the scalar numbers replace a table in force
+    h->qp_scalar = true;
     return DPENV_OK;
 }
 
@@ -1298,32 +1328,20 @@ extern "C" int dpenv_set_qp_allocator_table(dpenv_handle h, const float* table, 
 {
     if (!h) return DPENV_EINVAL;
     if (!table) {                                          // back to the scalar numbers last set, or to the pseudo-inverse; z and x stay
-        h->qp_tab_on = false;
-        h->qp_on = h->qp_scalar;
+        if (h->stage == ALLOC_QP_TAB) h->stage = h->qp_scalar ? ALLOC_QP : ALLOC_PINV;
         return DPENV_OK;
     }
-    if (!h->ctrl_on) return fail(h, DPENV_EINVAL, "dpenv_set_qp_allocator_table: the DP controller is off (dpenv_set_dp_controller first)");
-    if (h->nn_on) return fail(h, DPENV_EINVAL, "dpenv_set_qp_allocator_table: a neural allocator is set: " NN_SET_MSG);
+    if (int rc = qp_setter_before(h, "dpenv_set_qp_allocator_table")) return rc;
     if (iterations < 1 || iterations > QP_MAX_ITERS) return fail(h, DPENV_EINVAL, "QP allocator: iterations must be in 1..32");
     if (!std::isfinite(h->ctrl.dt) || !(h->ctrl.dt > 0.0f)) return fail(h, DPENV_EINVAL, "QP allocator: dt must be finite and > 0");
-    if (!control_config_ok(h)) return fail(h, DPENV_EINVAL, "dpenv_set_qp_allocator_table: " CONTROL_SET_MSG);
-    if (h->ctrl_tab_on || h->per_env) return fail(h, DPENV_EINVAL, "dpenv_set_qp_allocator_table: " QP_SET_MSG);
     DeviceGuard dev_guard(h->device);
-    if (!h->qp.state) {
-        void* p = nullptr;
-        if (hipMalloc(&p, sizeof(float) * 5 * (size_t)h->cfg.n_envs) != hipSuccess) return fail(h, DPENV_ENOMEM, "hipMalloc of the QP allocator state failed");
-        h->qp.state = (float*)p;
-    }
-    if (!h->qp_tab) {                                      // (whole waves of 64 envs)
-        void* p = nullptr;
-        if (hipMalloc(&p, sizeof(float4) * (size_t)qp_tab_float4s(h->cfg.n_envs)) != hipSuccess)
-            return fail(h, DPENV_ENOMEM, "hipMalloc of the QP allocator table failed");
-        h->qp_tab = (float4*)p;
-    }
+    if (int rc = qp_setter_after(h, "dpenv_set_qp_allocator_table")) return rc;
+    if (int rc = ensure_block(h, &h->qp_tab, sizeof(float4) * (size_t)qp_tab_float4s(h->cfg.n_envs),          // (whole waves of 64 envs)
+                              "hipMalloc of the QP allocator table failed")) return rc;
     HIP_TRY(h, dev::launch_pack_qp_table(table, h->qp_tab, refused_out, h->ctrl.dt, h->cfg.n_envs, (hipStream_t)s));
     HIP_TRY(h, dev::launch_qp_state_clear(h->qp.state, nullptr, h->cfg.n_envs, (hipStream_t)s));
     h->qp_tab_iters = iterations;
-    h->qp_on = h->qp_tab_on = true;
+    h->stage = ALLOC_QP_TAB;                               // (the scalar numbers, if any are held, stay held)
     return DPENV_OK;
 }
 
@@ -1332,7 +1350,7 @@ extern "C" int dpenv_set_nn_allocator(dpenv_handle h, const dpenv_nn_allocator* 
 {
     if (!h) return DPENV_EINVAL;
     if (!a) {
-        h->nn_on = false;
+        if (h->stage == ALLOC_NN) allocator_off(h);        // (a QP allocator stays)
         return DPENV_OK;
     }
     if (!h->ctrl_on) return fail(h, DPENV_EINVAL, "dpenv_set_nn_allocator: the DP controller is off (dpenv_set_dp_controller first)");
@@ -1340,14 +1358,10 @@ extern "C" int dpenv_set_nn_allocator(dpenv_handle h, const dpenv_nn_allocator* 
     if (const char* why = nn_check(a, g)) return fail(h, DPENV_EINVAL, "%s", why);
     if (a->device_pointers != 0 && a->device_pointers != 1) return fail(h, DPENV_EINVAL, "NN allocator: device_pointers must be 0 or 1");
     if (!control_config_ok(h)) return fail(h, DPENV_EINVAL, "dpenv_set_nn_allocator: " CONTROL_SET_MSG);
-    if (h->ctrl_tab_on) return fail(h, DPENV_EINVAL, "dpenv_set_nn_allocator: a per-env controller table is in force: " NN_SET_MSG);
-    if (h->qp_on) return fail(h, DPENV_EINVAL, "dpenv_set_nn_allocator: a QP allocator is set: " NN_SET_MSG);
+    if (const char* no = stage_refusal(h, ALLOC_NN)) return fail(h, DPENV_EINVAL, "dpenv_set_nn_allocator: %s", no);
     DeviceGuard dev_guard(h->device);
-    if (!h->nn_img) {                                      // the largest shape's image, once: a later call never allocates
-        void* p = nullptr;
-        if (hipMalloc(&p, sizeof(float) * (size_t)NN_IMAGE_FLOATS) != hipSuccess) return fail(h, DPENV_ENOMEM, "hipMalloc of the NN allocator image failed");
-        h->nn_img = (float*)p;
-    }
+    // the largest shape's image, once: a later call never allocates
+    if (int rc = ensure_block(h, &h->nn_img, sizeof(float) * (size_t)NN_IMAGE_FLOATS, "hipMalloc of the NN allocator image failed")) return rc;
     // the image: per layer W [in][nn_pad(out)] then b [nn_pad(out)], zero-padded; a shape's layout is a function of the shape alone
     NnPack pk = {};
     pk.n_layers = g.n_layers; pk.in_dim = g.in_dim; pk.H = g.H;
@@ -1374,27 +1388,40 @@ extern "C" int dpenv_set_nn_allocator(dpenv_handle h, const dpenv_nn_allocator* 
     }
     for (int l = 0; l < g.n_layers; ++l) { g.W[l] = pk.dW[l]; g.b[l] = pk.db[l]; }
     h->nn.a = g;
-    h->nn_on = true;
+    h->stage = ALLOC_NN;
+    return DPENV_OK;
+}
+
+// dpenv_get_qp_allocator_state / dpenv_set_qp_allocator_state: one copy with the direction swapped (as current_io)
+static int qp_state_io(dpenv_handle h, const char* who, float* theirs, bool set, dpenv_stream s)
+{
+    if (!h) return DPENV_EINVAL;
+    if (!qp_flies(h)) return fail(h, DPENV_EINVAL, "%s: no QP allocator is set", who);
+    if (!theirs) return fail(h, DPENV_EINVAL, "%s: NULL argument", who);
+    DeviceGuard dev_guard(h->device);
+    HIP_TRY(h, hipMemcpyAsync(set ? h->qp.state : theirs, set ? theirs : h->qp.state, env_bytes(h, 5 * sizeof(float)), hipMemcpyDeviceToDevice, (hipStream_t)s));
     return DPENV_OK;
 }
 
 extern "C" int dpenv_get_qp_allocator_state(dpenv_handle h, float* state_out, dpenv_stream s)
 {
-    if (!h) return DPENV_EINVAL;
-    if (!h->qp_on) return fail(h, DPENV_EINVAL, "dpenv_get_qp_allocator_state: no QP allocator is set");
-    if (!state_out) return fail(h, DPENV_EINVAL, "dpenv_get_qp_allocator_state: NULL argument");
-    DeviceGuard dev_guard(h->device);
-    HIP_TRY(h, hipMemcpyAsync(state_out, h->qp.state, sizeof(float) * 5 * (size_t)h->cfg.n_envs, hipMemcpyDeviceToDevice, (hipStream_t)s));
-    return DPENV_OK;
+    return qp_state_io(h, "dpenv_get_qp_allocator_state", state_out, false, s);
 }
 
 extern "C" int dpenv_set_qp_allocator_state(dpenv_handle h, const float* state_in, dpenv_stream s)
 {
-    if (!h) return DPENV_EINVAL;
-    if (!h->qp_on) return fail(h, DPENV_EINVAL, "dpenv_set_qp_allocator_state: no QP allocator is set");
-    if (!state_in) return fail(h, DPENV_EINVAL, "dpenv_set_qp_allocator_state: NULL argument");
-    DeviceGuard dev_guard(h->device);
-    HIP_TRY(h, hipMemcpyAsync(h->qp.state, state_in, sizeof(float) * 5 * (size_t)h->cfg.n_envs, hipMemcpyDeviceToDevice, (hipStream_t)s));
+    return qp_state_io(h, "dpenv_set_qp_allocator_state", (float*)state_in, true, s);
+}
+
+// the shared opening of the three label entry points (who: the entry point's name, whose io struct is <who>_io)
+template <class IO>
+static int check_label_io(dpenv_handle h, const char* who, const IO* io)
+{
+    if (!h->ctrl_on) return fail(h, DPENV_EINVAL, "%s: the DP controller is off (dpenv_set_dp_controller)", who);
+    if (!io || io->struct_size != sizeof(IO)) return fail(h, DPENV_EINVAL, "%s_io ABI mismatch", who);
+    if (io->T <= 0) return fail(h, DPENV_EINVAL, "%s: T > 0 is required", who);
+    if (!io->obs || !io->act) return fail(h, DPENV_EINVAL, "%s: the obs and act blocks are required", who);
+    if (io->obs_dtype != DPENV_F32 && io->obs_dtype != DPENV_BF16) return fail(h, DPENV_EINVAL, "%s: obs_dtype must be DPENV_F32 or DPENV_BF16", who);
     return DPENV_OK;
 }
 
@@ -1403,17 +1430,39 @@ extern "C" int dpenv_controller_label(dpenv_handle h, const dpenv_controller_lab
 {
     if (!h) return DPENV_EINVAL;
     DeviceGuard dev_guard(h->device);
-    if (!h->ctrl_on) return fail(h, DPENV_EINVAL, "dpenv_controller_label: the DP controller is off (dpenv_set_dp_controller)");
-    if (!io || io->struct_size != sizeof(dpenv_controller_label_io)) return fail(h, DPENV_EINVAL, "dpenv_controller_label_io ABI mismatch");
-    if (io->T <= 0) return fail(h, DPENV_EINVAL, "dpenv_controller_label: T > 0 is required");
-    if (!io->obs || !io->act) return fail(h, DPENV_EINVAL, "dpenv_controller_label: the obs and act blocks are required");
-    if (io->obs_dtype != DPENV_F32 && io->obs_dtype != DPENV_BF16)
-        return fail(h, DPENV_EINVAL, "dpenv_controller_label: obs_dtype must be DPENV_F32 or DPENV_BF16");
+    if (int rc = check_label_io(h, "dpenv_controller_label", io)) return rc;
     LabelArgs la = {};
     la.obs = io->obs; la.done = io->done; la.z_in = io->z_in; la.z_out = io->z_out; la.act = io->act;
     la.T = io->T; la.n = h->cfg.n_envs;
     const hipError_t e = dev::launch_controller_label(&h->ctrl, &la, h->ctrl_tab_on ? h->ctrl_tab : nullptr, io->obs_dtype == DPENV_BF16, (hipStream_t)s);
     if (e != hipSuccess) return fail(h, DPENV_EHIP, "label launch failed: %s", hipGetErrorString(e));
+    return DPENV_OK;
+}
+
+// the scan's argument block of dpenv_controller_label_qp_io and dpenv_controller_label_qp_ex_io
+template <class IO>
+static LabelQpArgs fill_label_qp_args(const IO* io, int n)
+{
+    LabelQpArgs la = {};
+    la.obs = io->obs; la.done = io->done; la.z_in = io->z_in; la.z_out = io->z_out; la.x_in = io->x_in; la.x_out = io->x_out;
+    la.act = io->act; la.cost = io->cost;
+    la.T = io->T; la.n = n;
+    return la;
+}
+
+// which QP numbers a label call without a table of its own scans with: q's, else the ones dpenv_set_qp_allocator has in force.  takes / pass:
+// the two calls' wordings of what the scan takes and what the caller can pass instead
+static int resolve_label_qp_numbers(dpenv_handle h, const char* who, const dpenv_qp_allocator* q, const char* takes, const char* pass, QpArgs& g)
+{
+    if (q) {
+        if (const char* why = qp_check(q, h->ctrl.dt, g)) return fail(h, DPENV_EINVAL, "%s", why);
+    } else if (h->stage == ALLOC_QP_TAB) {
+        return fail(h, DPENV_EINVAL, "%s: a per-env QP table (dpenv_set_qp_allocator_table) is in force and the scan takes %s: pass %s", who, takes, pass);
+    } else if (h->stage == ALLOC_QP) {
+        g = h->qp.q;
+    } else {
+        return fail(h, DPENV_EINVAL, "%s: no QP allocator (pass %s, or dpenv_set_qp_allocator first)", who, pass);
+    }
     return DPENV_OK;
 }
 
@@ -1423,27 +1472,10 @@ extern "C" int dpenv_controller_label_qp(dpenv_handle h, const dpenv_controller_
 {
     if (!h) return DPENV_EINVAL;
     DeviceGuard dev_guard(h->device);
-    if (!h->ctrl_on) return fail(h, DPENV_EINVAL, "dpenv_controller_label_qp: the DP controller is off (dpenv_set_dp_controller)");
-    if (!io || io->struct_size != sizeof(dpenv_controller_label_qp_io)) return fail(h, DPENV_EINVAL, "dpenv_controller_label_qp_io ABI mismatch");
-    if (io->T <= 0) return fail(h, DPENV_EINVAL, "dpenv_controller_label_qp: T > 0 is required");
-    if (!io->obs || !io->act) return fail(h, DPENV_EINVAL, "dpenv_controller_label_qp: the obs and act blocks are required");
-    if (io->obs_dtype != DPENV_F32 && io->obs_dtype != DPENV_BF16)
-        return fail(h, DPENV_EINVAL, "dpenv_controller_label_qp: obs_dtype must be DPENV_F32 or DPENV_BF16");
+    if (int rc = check_label_io(h, "dpenv_controller_label_qp", io)) return rc;
     QpArgs g = {};
-    if (io->q) {
-        if (const char* why = qp_check(io->q, h->ctrl.dt, g)) return fail(h, DPENV_EINVAL, "%s", why);
-    } else if (h->qp_tab_on) {
-        return fail(h, DPENV_EINVAL, "dpenv_controller_label_qp: a per-env QP table (dpenv_set_qp_allocator_table) is in force and the scan "
-                                     "takes one set of numbers: pass q");
-    } else if (h->qp_on) {
-        g = h->qp.q;
-    } else {
-        return fail(h, DPENV_EINVAL, "dpenv_controller_label_qp: no QP allocator (pass q, or dpenv_set_qp_allocator first)");
-    }
-    LabelQpArgs la = {};
-    la.obs = io->obs; la.done = io->done; la.z_in = io->z_in; la.z_out = io->z_out; la.x_in = io->x_in; la.x_out = io->x_out;
-    la.act = io->act; la.cost = io->cost;
-    la.T = io->T; la.n = h->cfg.n_envs;
+    if (int rc = resolve_label_qp_numbers(h, "dpenv_controller_label_qp", io->q, "one set of numbers", "q", g)) return rc;
+    const LabelQpArgs la = fill_label_qp_args(io, h->cfg.n_envs);
     const hipError_t e = dev::launch_controller_label_qp(&h->ctrl, &g, &la, h->ctrl_tab_on ? h->ctrl_tab : nullptr, io->obs_dtype == DPENV_BF16,
                                                          (hipStream_t)s);
     if (e != hipSuccess) return fail(h, DPENV_EHIP, "QP label launch failed: %s", hipGetErrorString(e));
@@ -1456,32 +1488,17 @@ extern "C" int dpenv_controller_label_qp_ex(dpenv_handle h, const dpenv_controll
 {
     if (!h) return DPENV_EINVAL;
     DeviceGuard dev_guard(h->device);
-    if (!h->ctrl_on) return fail(h, DPENV_EINVAL, "dpenv_controller_label_qp_ex: the DP controller is off (dpenv_set_dp_controller)");
-    if (!io || io->struct_size != sizeof(dpenv_controller_label_qp_ex_io)) return fail(h, DPENV_EINVAL, "dpenv_controller_label_qp_ex_io ABI mismatch");
-    if (io->T <= 0) return fail(h, DPENV_EINVAL, "dpenv_controller_label_qp_ex: T > 0 is required");
-    if (!io->obs || !io->act) return fail(h, DPENV_EINVAL, "dpenv_controller_label_qp_ex: the obs and act blocks are required");
-    if (io->obs_dtype != DPENV_F32 && io->obs_dtype != DPENV_BF16)
-        return fail(h, DPENV_EINVAL, "dpenv_controller_label_qp_ex: obs_dtype must be DPENV_F32 or DPENV_BF16");
+    if (int rc = check_label_io(h, "dpenv_controller_label_qp_ex", io)) return rc;
     if (io->q && io->qp_table) return fail(h, DPENV_EINVAL, "dpenv_controller_label_qp_ex: q or qp_table, not both");
     if (io->refused_out && !io->qp_table) return fail(h, DPENV_EINVAL, "dpenv_controller_label_qp_ex: refused_out goes with qp_table");
     QpArgs g = {};
     if (io->qp_table) {
         if (io->iterations < 1 || io->iterations > QP_MAX_ITERS) return fail(h, DPENV_EINVAL, "QP allocator: iterations must be in 1..32");
         if (!std::isfinite(h->ctrl.dt) || !(h->ctrl.dt > 0.0f)) return fail(h, DPENV_EINVAL, "QP allocator: dt must be finite and > 0");
-    } else if (io->q) {
-        if (const char* why = qp_check(io->q, h->ctrl.dt, g)) return fail(h, DPENV_EINVAL, "%s", why);
-    } else if (h->qp_tab_on) {
-        return fail(h, DPENV_EINVAL, "dpenv_controller_label_qp_ex: a per-env QP table (dpenv_set_qp_allocator_table) is in force and the scan "
-                                     "takes the numbers of the call: pass q or qp_table");
-    } else if (h->qp_on) {
-        g = h->qp.q;
-    } else {
-        return fail(h, DPENV_EINVAL, "dpenv_controller_label_qp_ex: no QP allocator (pass q or qp_table, or dpenv_set_qp_allocator first)");
+    } else if (int rc = resolve_label_qp_numbers(h, "dpenv_controller_label_qp_ex", io->q, "the numbers of the call", "q or qp_table", g)) {
+        return rc;
     }
-    LabelQpArgs la = {};
-    la.obs = io->obs; la.done = io->done; la.z_in = io->z_in; la.z_out = io->z_out; la.x_in = io->x_in; la.x_out = io->x_out;
-    la.act = io->act; la.cost = io->cost;
-    la.T = io->T; la.n = h->cfg.n_envs;
+    const LabelQpArgs la = fill_label_qp_args(io, h->cfg.n_envs);
     const float4* tab = h->ctrl_tab_on ? h->ctrl_tab : nullptr;
     const int bf16 = io->obs_dtype == DPENV_BF16;
     hipError_t e;

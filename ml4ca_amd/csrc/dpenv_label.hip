@@ -13,7 +13,14 @@
 // Two scans: controller_label_kernel allocates the PID's wrench with the pseudo-inverse (dp_control), controller_label_qp_kernel with the
 // rate-limited QP law of dpenv_qp_law.h (dpenv_controller_label_qp), whose thruster state travels beside z and whose objective can go
 // out beside the action (4 B per env-row).  The first is bound by its row traffic, the second by VALU issue.  controller_label_qp_ex_kernel
-// is the second with the thruster state taken from the flown action rows and / or one QP allocator per env (dpenv_controller_label_qp_ex).
+// is the second with the thruster state taken from the flown action rows and / or one QP allocator per env (dpenv_controller_label_qp_ex):
+// the two are one body, dpenv_label_qp_body.inc.  A lane's place in the wave is label_lane for all three.  The rest of the lane prologue
+// (z and x in and out, a row's six columns and done byte) stands once in that body and once in controller_label_kernel, not in shared
+// device functions: tried as __forceinline__ helpers, the z load, the row decode and the z store each re-scheduled controller_label_kernel,
+// and a store helper instantiated for both argument blocks re-scheduled all twenty kernels of the unit (tools/isa_diff.py against the
+// unit before; profiles/controller_family_isa_diff.txt is the record of what stands).
+#include <type_traits>
+
 #include "dpenv_env_dev.h"
 
 namespace dpenv {
@@ -33,6 +40,29 @@ struct LabelRow {
     float o[6];
     uint32_t d;
 };
+// ... and, FLOWN, the action row that was executed on it
+template <bool FLOWN>
+struct LabelRowEx {
+    float o[6];
+    uint32_t d;
+    float f[FLOWN ? 7 : 1];
+};
+
+// one wave per workgroup, one lane per env: dead lanes shadow env n - 1 (il) and store nothing
+struct LabelLane {
+    int lane, wave0, i, il;
+    bool live;
+};
+__device__ __forceinline__ LabelLane label_lane(int n)
+{
+    LabelLane L;
+    L.lane = threadIdx.x;
+    L.wave0 = blockIdx.x * 64;
+    L.i = L.wave0 + L.lane;
+    L.live = L.i < n;
+    L.il = L.live ? L.i : n - 1;
+    return L;
+}
 
 // Forward scan over the T rows of a block, one lane per env, one wave per workgroup.  The law is serial in t, but no load depends on it:
 // rows are fetched LABEL_U at a time into one of two register banks while the other is consumed.  TAB: the env's own row of the packed
@@ -45,11 +75,9 @@ __global__ __launch_bounds__(64) void controller_label_kernel(const ControlArgs 
     __shared__ float lds_row[64 * A];
 
     const int n = la.n, T = la.T;
-    const int lane = threadIdx.x;
-    const int wave0 = blockIdx.x * 64;
-    const int i = wave0 + lane;
-    const bool live = i < n;
-    const int il = live ? i : n - 1;
+    const LabelLane L = label_lane(n);
+    const int lane = L.lane, wave0 = L.wave0, i = L.i, il = L.il;
+    const bool live = L.live;
 
     ControlLane cl;
     if constexpr (TAB) load_control_lane(tab, il, ca.dt, cl);
@@ -109,188 +137,21 @@ __global__ __launch_bounds__(64) void controller_label_kernel(const ControlArgs 
     }
 }
 
-// The same scan with the rate-limited QP allocation behind the PID lines (dpenv_controller_label_qp): per row the closed loop's QP branch
-// (dpenv_control_rollout_body.inc) - dp_wrench on the env's z, qp_allocate on its thruster state x - and both zeroed behind a done row.
-// z[3] and x[5] come in with the opening burst and go out once at the end.  About 620 VALU instructions per LM iteration stand against 7
-// loads per row, so the fetch is one row ahead and no deeper: row t + 1 is in flight under the solve of row t.  The iteration count is
-// a kernel argument, the loop wave-uniform; dead lanes solve env n - 1's rows again and store nothing.
+// dpenv_label_qp_body.inc without the flown rows and the per-env QP table
 template <bool TAB, bool BF16>
 __global__ __launch_bounds__(64) void controller_label_qp_kernel(const ControlArgs ca, const QpArgs qa, const LabelQpArgs la,
                                                                   const float4* __restrict__ tab)
 {
-    constexpr int A = 7, OD = 9;
-    __shared__ float lds_row[64 * A];
-
-    const int n = la.n, T = la.T;
-    const int lane = threadIdx.x;
-    const int wave0 = blockIdx.x * 64;
-    const int i = wave0 + lane;
-    const bool live = i < n;
-    const int il = live ? i : n - 1;
-
-    ControlLane cl;
-    if constexpr (TAB) load_control_lane(tab, il, ca.dt, cl);
-    float z[3] = {0.0f, 0.0f, 0.0f};
-    if (la.z_in) {
-        z[0] = la.z_in[il]; z[1] = la.z_in[(int64_t)n + il]; z[2] = la.z_in[2 * (int64_t)n + il];
-    }
-    float x[5] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
-    if (la.x_in) {
-#pragma unroll
-        for (int k = 0; k < 5; ++k) x[k] = la.x_in[(int64_t)k * n + il];
-    }
-
-    const int64_t stride_a = (int64_t)n * A;
-    const int64_t w_a = (int64_t)wave0 * A;                      // the wave's slice of the [T][n][7] block
-    const int64_t rem_a = stride_a - w_a;
-
-    auto load = [&](LabelRow& row, int t) {
-        t = t < T ? t : T - 1;                                   // past the end: re-read the last row (never consumed)
-        const int64_t k = (int64_t)t * n + il;
-        if (BF16) {
-            const uint16_t* p = (const uint16_t*)la.obs + k * OD;
-#pragma unroll
-            for (int c = 0; c < 6; ++c) row.o[c] = __uint_as_float((uint32_t)p[c] << 16);
-        } else {
-            const float* p = (const float*)la.obs + k * OD;
-#pragma unroll
-            for (int c = 0; c < 6; ++c) row.o[c] = p[c];
-        }
-        row.d = la.done ? (uint32_t)la.done[k] : 0u;
-    };
-    LabelRow cur, nxt;
-    load(cur, 0);
-    for (int t = 0; t < T; ++t) {
-        load(nxt, t + 1);
-        float o[OD], tau[3], act[A], J;
-#pragma unroll
-        for (int c = 0; c < 6; ++c) o[c] = cur.o[c];
-        o[6] = o[7] = o[8] = 0.0f;                               // the thrust columns: the law does not read them
-        if constexpr (TAB) dp_wrench(cl, o, z, tau);
-        else dp_wrench(ca, o, z, tau);
-        qp_allocate(qa, tau, x, act, J);
-        control_store_rows<A>(lds_row, la.act, (int64_t)t * stride_a + w_a, rem_a, act, lane, false);
-        if (live && la.cost) (la.cost + (int64_t)t * n)[(unsigned)i] = J;
-        if (cur.d != 0u) {                                       // the next row is a new episode's first: thrusters at rest
-            z[0] = z[1] = z[2] = 0.0f;
-#pragma unroll
-            for (int k = 0; k < 5; ++k) x[k] = 0.0f;
-        }
-        cur = nxt;
-    }
-    if (live && la.z_out) {
-        la.z_out[i] = z[0]; la.z_out[(int64_t)n + i] = z[1]; la.z_out[2 * (int64_t)n + i] = z[2];
-    }
-    if (live && la.x_out) {
-#pragma unroll
-        for (int k = 0; k < 5; ++k) la.x_out[(int64_t)k * n + i] = x[k];
-    }
+    constexpr bool QTAB = false, FLOWN = false;
+    const LabelQpExArgs xa = {};
+#include "dpenv_label_qp_body.inc"
 }
-
-// controller_label_qp_kernel's scan with the two things dpenv_controller_label_qp_ex adds, same scheme (one wave per workgroup, one lane per
-// env, row t + 1 in flight under the solve of row t, a wave-uniform iteration loop):
-// FLOWN: the thruster state row t + 1 is solved from is S (qp_state_from_action) of the action row t that was EXECUTED, not the law's own
-//   advance of x, which is dropped.  The flown row t is fetched with obs row t - 28 more bytes per lane at the act rows' 28-byte stride (one
-//   16-byte and one 12-byte load), straight into registers like the 36-byte obs rows beside them: they land under the ~620 K VALU
-//   instructions of the previous row's solve, so staging them coalesced through the LDS area would buy nothing the scan can see and cost
-//   a wait the loads do not have (measured: 1.016 x the own recursion at 65 536 envs x 50 rows).
-// QTAB: the lane's own row of the PUBLIC QP table, 26 loads in the opening burst, checked by qp_lane_from_row; QpLane goes through
-//   qp_allocate<QpLane> unedited.  A refused row runs the rest allocator, reports NaN in cost and sets its byte of refused.  qa is not read.
-// Dead lanes shadow env n - 1 and store nothing, refused included.
-template <bool FLOWN>
-struct LabelRowEx {
-    float o[6];
-    uint32_t d;
-    float f[FLOWN ? 7 : 1];
-};
 
 template <bool TAB, bool QTAB, bool FLOWN, bool BF16>
 __global__ __launch_bounds__(64) void controller_label_qp_ex_kernel(const ControlArgs ca, const QpArgs qa, const LabelQpArgs la,
                                                                      const LabelQpExArgs xa, const float4* __restrict__ tab)
 {
-    constexpr int A = 7, OD = 9;
-    __shared__ float lds_row[64 * A];
-
-    const int n = la.n, T = la.T;
-    const int lane = threadIdx.x;
-    const int wave0 = blockIdx.x * 64;
-    const int i = wave0 + lane;
-    const bool live = i < n;
-    const int il = live ? i : n - 1;
-
-    ControlLane cl;
-    if constexpr (TAB) load_control_lane(tab, il, ca.dt, cl);
-    QpLane ql;
-    bool row_ok = true;
-    if constexpr (QTAB) {
-        row_ok = qp_lane_from_row(xa.qp_table, n, il, ca.dt, xa.iters, ql);
-        if (live && xa.refused) xa.refused[i] = row_ok ? 0 : 1;
-    }
-    float z[3] = {0.0f, 0.0f, 0.0f};
-    if (la.z_in) {
-        z[0] = la.z_in[il]; z[1] = la.z_in[(int64_t)n + il]; z[2] = la.z_in[2 * (int64_t)n + il];
-    }
-    float x[5] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
-    if (la.x_in) {
-#pragma unroll
-        for (int k = 0; k < 5; ++k) x[k] = la.x_in[(int64_t)k * n + il];
-    }
-
-    const int64_t stride_a = (int64_t)n * A;
-    const int64_t w_a = (int64_t)wave0 * A;                      // the wave's slice of the [T][n][7] block
-    const int64_t rem_a = stride_a - w_a;
-
-    auto load = [&](LabelRowEx<FLOWN>& row, int t) {
-        t = t < T ? t : T - 1;                                   // past the end: re-read the last row (never consumed)
-        const int64_t k = (int64_t)t * n + il;
-        if (BF16) {
-            const uint16_t* p = (const uint16_t*)la.obs + k * OD;
-#pragma unroll
-            for (int c = 0; c < 6; ++c) row.o[c] = __uint_as_float((uint32_t)p[c] << 16);
-        } else {
-            const float* p = (const float*)la.obs + k * OD;
-#pragma unroll
-            for (int c = 0; c < 6; ++c) row.o[c] = p[c];
-        }
-        row.d = la.done ? (uint32_t)la.done[k] : 0u;
-        if constexpr (FLOWN) {
-            const float* f = xa.flown + k * A;
-#pragma unroll
-            for (int c = 0; c < A; ++c) row.f[c] = f[c];
-        }
-    };
-    LabelRowEx<FLOWN> cur, nxt;
-    load(cur, 0);
-    for (int t = 0; t < T; ++t) {
-        load(nxt, t + 1);
-        float o[OD], tau[3], act[A], J;
-#pragma unroll
-        for (int c = 0; c < 6; ++c) o[c] = cur.o[c];
-        o[6] = o[7] = o[8] = 0.0f;                               // the thrust columns: the law does not read them
-        if constexpr (TAB) dp_wrench(cl, o, z, tau);
-        else dp_wrench(ca, o, z, tau);
-        if constexpr (QTAB) qp_allocate(ql, tau, x, act, J);
-        else qp_allocate(qa, tau, x, act, J);
-        if constexpr (FLOWN) {                                   // the law's own advance of x is dropped: the executed row's state
-            if constexpr (QTAB) qp_state_from_action(ql, cur.f, x);
-            else qp_state_from_action(qa, cur.f, x);
-        }
-        control_store_rows<A>(lds_row, la.act, (int64_t)t * stride_a + w_a, rem_a, act, lane, false);
-        if (live && la.cost) (la.cost + (int64_t)t * n)[(unsigned)i] = row_ok ? J : __builtin_nanf("");
-        if (cur.d != 0u) {                                       // the next row is a new episode's first: thrusters at rest
-            z[0] = z[1] = z[2] = 0.0f;
-#pragma unroll
-            for (int k = 0; k < 5; ++k) x[k] = 0.0f;
-        }
-        cur = nxt;
-    }
-    if (live && la.z_out) {
-        la.z_out[i] = z[0]; la.z_out[(int64_t)n + i] = z[1]; la.z_out[2 * (int64_t)n + i] = z[2];
-    }
-    if (live && la.x_out) {
-#pragma unroll
-        for (int k = 0; k < 5; ++k) la.x_out[(int64_t)k * n + i] = x[k];
-    }
+#include "dpenv_label_qp_body.inc"
 }
 
 }  // namespace
@@ -298,17 +159,30 @@ __global__ __launch_bounds__(64) void controller_label_qp_ex_kernel(const Contro
 
 using namespace dpenv;
 
+// the four instantiations of a scan over (controller table, bf16 rows): launch(tab_c, bf16_c) launches the one its two constants name
+namespace {
+template <class F>
+void label_dispatch(const float4* tab, int obs_bf16, F launch)
+{
+    using std::true_type;
+    using std::false_type;
+    if (tab) {
+        if (obs_bf16) launch(true_type(), true_type());
+        else launch(true_type(), false_type());
+    } else {
+        if (obs_bf16) launch(false_type(), true_type());
+        else launch(false_type(), false_type());
+    }
+}
+}  // namespace
+
 hipError_t dev::launch_controller_label(const ControlArgs* ca, const LabelArgs* la, const float4* tab, int obs_bf16, hipStream_t s)
 {
     if (la->n <= 0 || la->T <= 0 || !la->obs || !la->act) return hipErrorInvalidValue;
     const dim3 grid((la->n + 63) / 64), block(64);
-    if (tab) {
-        if (obs_bf16) hipLaunchKernelGGL((controller_label_kernel<true, true>), grid, block, 0, s, *ca, *la, tab);
-        else hipLaunchKernelGGL((controller_label_kernel<true, false>), grid, block, 0, s, *ca, *la, tab);
-    } else {
-        if (obs_bf16) hipLaunchKernelGGL((controller_label_kernel<false, true>), grid, block, 0, s, *ca, *la, tab);
-        else hipLaunchKernelGGL((controller_label_kernel<false, false>), grid, block, 0, s, *ca, *la, tab);
-    }
+    label_dispatch(tab, obs_bf16, [&](auto t, auto b) {
+        hipLaunchKernelGGL((controller_label_kernel<decltype(t)::value, decltype(b)::value>), grid, block, 0, s, *ca, *la, tab);
+    });
     return hipGetLastError();
 }
 
@@ -317,13 +191,9 @@ hipError_t dev::launch_controller_label_qp(const ControlArgs* ca, const QpArgs* 
 {
     if (la->n <= 0 || la->T <= 0 || !la->obs || !la->act || qa->iters < 1 || qa->iters > QP_MAX_ITERS) return hipErrorInvalidValue;
     const dim3 grid((la->n + 63) / 64), block(64);
-    if (tab) {
-        if (obs_bf16) hipLaunchKernelGGL((controller_label_qp_kernel<true, true>), grid, block, 0, s, *ca, *qa, *la, tab);
-        else hipLaunchKernelGGL((controller_label_qp_kernel<true, false>), grid, block, 0, s, *ca, *qa, *la, tab);
-    } else {
-        if (obs_bf16) hipLaunchKernelGGL((controller_label_qp_kernel<false, true>), grid, block, 0, s, *ca, *qa, *la, tab);
-        else hipLaunchKernelGGL((controller_label_qp_kernel<false, false>), grid, block, 0, s, *ca, *qa, *la, tab);
-    }
+    label_dispatch(tab, obs_bf16, [&](auto t, auto b) {
+        hipLaunchKernelGGL((controller_label_qp_kernel<decltype(t)::value, decltype(b)::value>), grid, block, 0, s, *ca, *qa, *la, tab);
+    });
     return hipGetLastError();
 }
 
@@ -334,13 +204,9 @@ void launch_label_qp_ex(const ControlArgs* ca, const QpArgs* qa, const LabelQpAr
                         hipStream_t s)
 {
     const dim3 grid((la->n + 63) / 64), block(64);
-    if (tab) {
-        if (obs_bf16) hipLaunchKernelGGL((controller_label_qp_ex_kernel<true, QTAB, FLOWN, true>), grid, block, 0, s, *ca, *qa, *la, *xa, tab);
-        else hipLaunchKernelGGL((controller_label_qp_ex_kernel<true, QTAB, FLOWN, false>), grid, block, 0, s, *ca, *qa, *la, *xa, tab);
-    } else {
-        if (obs_bf16) hipLaunchKernelGGL((controller_label_qp_ex_kernel<false, QTAB, FLOWN, true>), grid, block, 0, s, *ca, *qa, *la, *xa, tab);
-        else hipLaunchKernelGGL((controller_label_qp_ex_kernel<false, QTAB, FLOWN, false>), grid, block, 0, s, *ca, *qa, *la, *xa, tab);
-    }
+    label_dispatch(tab, obs_bf16, [&](auto t, auto b) {
+        hipLaunchKernelGGL((controller_label_qp_ex_kernel<decltype(t)::value, QTAB, FLOWN, decltype(b)::value>), grid, block, 0, s, *ca, *qa, *la, *xa, tab);
+    });
 }
 }  // namespace
 

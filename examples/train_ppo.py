@@ -231,14 +231,64 @@ def warm_start(upd, env, args, out=print):
     return h, hv
 
 
+def fit_allocator(args, dev, preset, out=print):
+    """--nn-allocator ITERS: the neural allocator fitted for the preset's hull (train.fit_nn_allocator), with the line that says how."""
+    from ml4ca_amd.deploy import nn_allocator_dataset
+    from ml4ca_amd.train import alloc_loss_params, fit_nn_allocator
+    hull = ml4ca_amd.default_vessel(preset)
+    wrench = alloc_loss_params(None if args.nn_w_power is None else dict(w_power=args.nn_w_power), vessel=hull)
+    base = nn_allocator_dataset(16384, args.seed, vessel=hull)
+    nn_net = fit_nn_allocator(base, iters=args.nn_allocator, seed=args.seed, device=dev, loss=args.nn_loss, alloc_loss=wrench)
+    out('eval  neural allocator fitted in %d Adam steps, loss %s%s: label MSE %.4g -> %.4g, mean wrench residual Js %.4g -> %.4g N^2' % (
+        args.nn_allocator, args.nn_loss, ' (w_power %g)' % wrench['w_power'] if args.nn_loss == 'wrench' else '', nn_net['mse_initial'],
+        nn_net['mse_final'], nn_net['wrench_ms_initial'], nn_net['wrench_ms_final']))
+    return nn_net, base, wrench
+
+
+def nn_score_card(nn_net, dev, preset, seed, nb, tag, out=print):
+    """The score-card line of the PID + neural allocation on the nominal hull, calm and in the thesis' 0.2 m/s current."""
+    from ml4ca_amd import evaluate as EV
+    from ml4ca_amd.deploy import dp_controller_defaults
+    nominal = ml4ca_amd.default_vessel(preset)
+    for name, cur in (('calm', False), ('current 0.2 m/s @ 135 deg', True)):
+        env = ml4ca_amd.BatchedRevoltEnv(nb, device=dev, terminate=False, time_limit=False, seed=seed + 77, vessel_params=nominal, current=cur)
+        if cur:
+            env.set_current(torch.full((nb,), 0.2, device=dev), torch.full((nb,), 2.35619, device=dev))
+        env.set_dp_controller(dp_controller_defaults(nominal))
+        sn = EV.baseline_box_test_streamed(env, T=1250, start=torch.zeros((3, nb), device=dev), chunk=50, allocator='nn', net=nn_net)
+        out('eval  box test (1250 steps, %d envs), %s, %s: baseline PID + neural allocation IAE %.2f (worst env %.2f)  work bow/port/star %s (total %.1f)' % (
+            nb, tag, name, float(sn['iae'].mean()), float(sn['iae'].max()), [round(float(x), 1) for x in sn['work'].mean(0)], float(sn['work'].mean(0).sum())))
+        del env
+
+
+def nn_on_policy(args, dev, preset, base, wrench, out=print):
+    """--nn-on-policy ROUNDS: refit the allocator on the wrenches its own closed loop asks of it (train.fit_nn_allocator_on_policy) - training
+    envs with auto-reset in a 0.2 m/s current from 16 directions, one episode per round, the dataset's rows kept in the pool."""
+    import math
+    from ml4ca_amd.deploy import dp_controller_defaults
+    from ml4ca_amd.train import fit_nn_allocator_on_policy
+    nominal = ml4ca_amd.default_vessel(preset)
+    n = args.eval_envs
+    env = ml4ca_amd.BatchedRevoltEnv(n, auto_reset=True, seed=args.seed + 31, device=dev, current=True, vessel_params=nominal)
+    env.set_current(torch.full((n,), 0.2, device=dev), ((2 * math.pi / 16) * (torch.arange(n, device=dev) % 16).float()).contiguous())
+    env.set_dp_controller(dp_controller_defaults(nominal))
+    env.reset()
+    res = fit_nn_allocator_on_policy(env, args.nn_on_policy, args.steps, args.nn_allocator, base=base, seed=args.seed, alloc_loss=wrench)
+    for r, x in enumerate(res['rounds']):
+        out('eval  on-policy round %2d: %d rows (%d flown)  J %.4g -> %.4g  mean wrench residual Js %.4g -> %.4g N^2' % (
+            r, x['rows'], x['rows'] - res['base']['rows'], x['J_initial'], x['J_final'], x['wrench_ms_initial'], x['wrench_ms_final']))
+    return dict(W=res['W'], b=res['b'], leak=res['leak'])
+
+
 def dagger(upd, env, args, out=print):
     """--dagger: after the warm start (if any) and before PPO, fly the ACTOR on the training envs, label the states it visits with the
     baseline (policy.controller_label: the PID + pseudo-inverse law scanned over the actor's rows in one launch), aggregate the rounds and
     refit (PPOUpdater.dagger).  A clone trained on the expert's states alone has no labels where its own errors take it; these rounds
     supply them.  The labels carry the PID's integral, which the memoryless actor cannot see: it can only fit their mean given o.
     --expert qp labels with the PID + rate-limited QP chain instead (policy.controller_label_qp), whose labels carry its thruster state
-    as well."""
+    as well.  --expert nn labels with the PID + the fitted neural allocator (policy.controller_label_nn; --nn-allocator ITERS fits it first)."""
     from ml4ca_amd.deploy import dp_controller_defaults, qp_allocator_defaults
+    nn_net = fit_allocator(args, env.device, args.preset, out=out)[0] if args.expert == 'nn' else None
     T = args.dagger_steps or args.steps
     nominal = ml4ca_amd.default_vessel(args.preset)
     env.set_dp_controller(dp_controller_defaults(nominal))
@@ -249,7 +299,8 @@ def dagger(upd, env, args, out=print):
     # the scan touches no hull, so it labels the randomised-hull envs the QP closed loop cannot fly
     rec = upd.dagger(env, args.dagger, T, args.dagger_iters, minibatch=mb, loss=args.warm_start_loss, keep=args.dagger_keep or None,
                      average=D.average_flat, upload=dict(precision=args.precision), expert=args.expert,
-                     qp_params=qp_allocator_defaults(nominal) if args.expert == 'qp' else None, thruster_state=args.expert_state)
+                     qp_params=qp_allocator_defaults(nominal) if args.expert == 'qp' else None, thruster_state=args.expert_state,
+                     **(dict(nn_net=nn_net) if nn_net is not None else {}))
     torch.cuda.synchronize()
     D.assert_params_in_step(list(upd.ac.parameters()), what='parameters after DAgger')
     env.set_dp_controller(off=True)
@@ -327,7 +378,7 @@ def main():
     ap.add_argument('--dagger-iters', type=int, default=100, metavar='ITERS', help='gradient steps per DAgger round (loss: --warm-start-loss)')
     ap.add_argument('--dagger-steps', type=int, default=0, metavar='T', help='steps of each DAgger flight (default: one episode, --steps)')
     ap.add_argument('--dagger-keep', type=int, default=0, metavar='K', help='rounds kept in the aggregated dataset, a ring (default 0: all of them)')
-    ap.add_argument('--expert', default='pinv', choices=('pinv', 'qp'),
+    ap.add_argument('--expert', default='pinv', choices=('pinv', 'qp', 'nn'),
                     help="the expert of --warm-start and --dagger: 'pinv' = PID + pseudo-inverse; 'qp' = the same PID with the rate-limited QP allocation "
                          '(55 %% of the pseudo-inverse\'s thruster work on the box test): the warm-start flight flies it (env.set_qp_allocator), --dagger '
                          'labels with it (policy.controller_label_qp)')
@@ -365,6 +416,9 @@ def main():
                     "labels (FFNN.py); 'wrench' trains it through the force map with the allocation loss (train.allocation_grad: the QP's objective at "
                     'the network\'s output, no labels)')
     ap.add_argument('--nn-w-power', type=float, default=None, metavar='X', help="with --nn-loss wrench: the loss's w_power (default: the QP's, 1)")
+    ap.add_argument('--nn-on-policy', type=int, default=0, metavar='ROUNDS', help='with --nn-allocator ITERS --nn-loss wrench: after the fit, ROUNDS rounds of '
+                    'train.fit_nn_allocator_on_policy (fly the PID + network chain, read the PID\'s wrench on every row with the labelling scan, refit '
+                    'ITERS steps on the dataset plus the flown wrenches); the score-card line of the network is printed before and after')
     ap.add_argument('--eval-envs', type=int, default=1024, help='envs per --eval box test; 1024 (the default) scores the resident rows as before, any other '
                                                                 'value flies the test in 50-step launches scored on the device (evaluate.ScoreCard), e.g. 65536')
     ap.add_argument('--eval-presets', default='', help="comma-separated presets to run --eval on (default: the training preset), e.g. 'no_loss,thrust_loss': "
@@ -382,6 +436,10 @@ def main():
     if args.expert == 'qp' and args.randomise > 0 and args.warm_start > 0:
         ap.error('--expert qp with --randomise cannot fly the warm-start demonstration: the QP closed loop runs on a shared hull, not on per-env '
                  'hulls.  Use --dagger without --warm-start: the labelling scan touches no hull')
+    if args.expert == 'nn' and (args.warm_start > 0 or args.nn_allocator <= 0):
+        ap.error("--expert nn labels --dagger rounds with the fitted network: it needs --nn-allocator ITERS, and --warm-start flies 'pinv' or 'qp'")
+    if args.nn_on_policy > 0 and (args.nn_allocator <= 0 or args.nn_loss != 'wrench'):
+        ap.error('--nn-on-policy goes with --nn-allocator ITERS --nn-loss wrench (the wrench loss needs no labels, only wrenches)')
     # one process per GPU under torch.distributed.run (backend nccl = RCCL); envs shard by global id, gradients average
     rank, world, local = int(os.environ.get('RANK', 0)), int(os.environ.get('WORLD_SIZE', 1)), int(os.environ.get('LOCAL_RANK', 0))
     dev = torch.device('cuda', 0 if args.same_device else local)
@@ -503,15 +561,11 @@ def main():
                 print('eval on the %s preset (trained on %s%s)' % (pz, args.preset, ', hulls re-drawn +-%g %%' % (100 * args.randomise) if args.randomise > 0 else ''))
                 nn_net = None
                 if args.nn_allocator > 0:
-                    from ml4ca_amd.deploy import nn_allocator_dataset
-                    from ml4ca_amd.train import alloc_loss_params, fit_nn_allocator
-                    hull = ml4ca_amd.default_vessel(pz)
-                    wrench = alloc_loss_params(None if args.nn_w_power is None else dict(w_power=args.nn_w_power), vessel=hull)
-                    nn_net = fit_nn_allocator(nn_allocator_dataset(16384, args.seed, vessel=hull), iters=args.nn_allocator, seed=args.seed, device=dev,
-                                              loss=args.nn_loss, alloc_loss=wrench)
-                    print('eval  neural allocator fitted in %d Adam steps, loss %s%s: label MSE %.4g -> %.4g, mean wrench residual Js %.4g -> %.4g N^2' % (
-                        args.nn_allocator, args.nn_loss, ' (w_power %g)' % wrench['w_power'] if args.nn_loss == 'wrench' else '', nn_net['mse_initial'],
-                        nn_net['mse_final'], nn_net['wrench_ms_initial'], nn_net['wrench_ms_final']))
+                    nn_net, base, wrench = fit_allocator(args, dev, pz)
+                    if args.nn_on_policy > 0:
+                        nn_score_card(nn_net, dev, pz, args.seed, args.eval_envs, 'before the on-policy rounds')
+                        nn_net = nn_on_policy(args, dev, pz, base, wrench)
+                        nn_score_card(nn_net, dev, pz, args.seed, args.eval_envs, 'after %d on-policy rounds' % args.nn_on_policy)
                 evaluate_actor(ac, dev, pz, 'f32', args.seed, eval_envs=args.eval_envs, nn_net=nn_net)
                 if args.tune_baseline > 0:
                     tune_baseline(ac, dev, pz, 'f32', args.tune_baseline, seed=args.seed)

@@ -937,8 +937,9 @@ int dpenv_thrust_alloc_qp_table(const float* table, int32_t iterations, float dt
  * a_bow is not used: the env's tunnel thruster is fixed.  REST RULE: if any tau_j or any of the six p is not finite, that env's action is
  * the rest action [0, 0, 0, 0, 1, 0, 1]; no other env is affected.  (With leak = 0 a hidden pre-activation of -inf gives 0 * -inf = NaN
  * and so the rest action.)  The law has no state and reads no hull.  ml4ca_amd.deploy.BatchedNNAllocator is its host statement.
- * NOT HERE: a reader for the reference's .h5 models (weights arrive as arrays), a labelling scan with the network, one network per env,
- * and an evaluation on the matrix cores - the network is evaluated on the VALU, one fmaf per weight and env. */
+ * dpenv_controller_label_nn (below) scans the PID + network chain over rows some other flight wrote.
+ * NOT HERE: a reader for the reference's .h5 models (weights arrive as arrays), one network per env, and an evaluation on the matrix
+ * cores - the network is evaluated on the VALU, one fmaf per weight and env. */
 typedef struct dpenv_nn_allocator {
     uint32_t struct_size;
     const dpenv_mlp* net;     /* sizes[0] in {3, 9}; sizes[n_layers] == 6; n_layers 2..5; hidden widths equal, 1..96 */
@@ -978,6 +979,53 @@ int dpenv_thrust_alloc_nn(const dpenv_nn_allocator* a, const float* tau, float* 
  * dpenv_controller_label, dpenv_controller_label_qp and dpenv_controller_label_qp_ex are untouched: they label with the pseudo-inverse
  * and the QP law whatever is set here. */
 int dpenv_set_nn_allocator(dpenv_handle h, const dpenv_nn_allocator* a, dpenv_stream s);
+/* The PID + network chain on rows some other flight wrote (additive to ABI 6): dpenv_controller_label's scan with the neural allocation
+ * in place of the f_m / bow / stern lines, and the PID's clipped wrench per row beside it - the network's labels for the states an actor
+ * visited, and the wrenches a flight asked of its allocator, which the closed loop never writes.  One launch, one lane per env; per row t
+ * and env i, in the order of the closed loop with a network set:
+ *     o   = obs[t][i][0:6]                              (a bf16 value widened exactly)
+ *     tau = the PID lines of the DP controller's law on o with the env's z_i: z_i advanced first, the wrench clipped to tau_max
+ *     tau_j = NaN if o_j or o_{3+j} is NaN              (the law's fminf / fmaxf clip drops a NaN: a closed loop would fly -tau_max on such
+ *                                                        a row, which no flight writes; the scan answers it with the REST RULE, as the host
+ *                                                        statement does, and z_i stays the law's)
+ *     tau_out[t][i][0:3] = tau                          (if tau_out is not NULL: the exact value the allocator is handed)
+ *     act[t][i][0:7], p = the neural law above on tau   (if act is not NULL; the REST RULE included)
+ *     raw[t][i][0:6] = p                                (if raw is not NULL)
+ *     if (done && done[t][i] != 0) z_i = 0              -- the next row is a new episode's first
+ * z_i starts from z_in[:, i] (NULL = 0) and is written to z_out at the end (NULL = not wanted; may be z_in), so a block labelled in pieces
+ * with z handed over gives the rows of one call.  The network has no state: nothing else travels.  The PID's numbers are the handle's
+ * controller in force: row i of dpenv_set_dp_controller_table's table on env i when there is one, else dpenv_set_dp_controller's; dt is
+ * the handle's.  a: the network and its constants, validated with the checks of dpenv_thrust_alloc_nn (device_pointers = 1: W and b are
+ * DEVICE arrays read in place, no packing launch, no allocation); NULL = the network dpenv_set_nn_allocator has in force on h, its image
+ * and its constants.
+ * (A) For f32 rows written by dpenv_controller_rollout with a network set and auto-reset on, labelled with that launch's done block, the z
+ *     it started from and a = NULL, act is that launch's act rows bit for bit and z_out is its final z.
+ * (B) On any block, act and raw are dpenv_thrust_alloc_nn applied row by row to tau_out, bit for bit - with an explicit a and with
+ *     a = NULL alike.
+ * With an explicit a the handle's allocation stage does not matter: a handle with a per-env controller table, a QP allocator or nothing
+ * set is labelled with a network.  dpenv_set_nn_allocator refuses a controller table; the scan does not, and env i takes row i of the
+ * PID's table.  With act = NULL no network is needed at all and a is not looked at: the call is a scan of the PID lines alone, bound by
+ * its row traffic (tau_out and z_out are those of the full scan, bit for bit).
+ * The call reads and writes nothing of the handle's env state, its z, its network image, the lagged thrust columns or the RNG counters.
+ * Stream-ordered, no allocation, no host synchronisation; one kernel node when captured into a graph (a captured call with a = NULL flies
+ * whatever the last upload of that shape wrote, and the constants of capture time).  The scan is serial in T per env.
+ * DPENV_EINVAL with the reason in dpenv_last_error, before anything is launched or written: the controller off, a wrong struct_size,
+ * T <= 0, NULL obs, act and tau_out both NULL, raw without act, an obs_dtype that is neither DPENV_F32 nor DPENV_BF16, act wanted with
+ * a NULL and no network set, and whatever dpenv_thrust_alloc_nn refuses of a.  ml4ca_amd.deploy.label_rows_nn is the host statement. */
+typedef struct dpenv_controller_label_nn_io {
+    uint32_t struct_size;    /* sizeof(dpenv_controller_label_nn_io), ABI check */
+    int32_t T;
+    const void* obs;         /* [T][n][9] rows in dpenv_policy_rollout's conventions; f32 or bf16; columns 0..5 read */
+    int32_t obs_dtype;       /* DPENV_F32 / DPENV_BF16: the block's, independent of the handle's config */
+    const uint8_t* done;     /* [T][n] DPENV_DONE_* bits, or NULL = no episode ends in the block */
+    const float* z_in;       /* [3][n] (dpenv_get_dp_controller_state's layout) or NULL = 0 */
+    float* z_out;            /* [3][n] or NULL; may be z_in */
+    float* act;              /* [T][n][7] the chain's action on obs[t], or NULL = the wrench-only scan */
+    float* raw;              /* [T][n][6] the network's six outputs p, or NULL; needs act */
+    float* tau_out;          /* [T][n][3] the PID's clipped wrench, or NULL */
+    const dpenv_nn_allocator* a;   /* the network; NULL = the one dpenv_set_nn_allocator has in force on h */
+} dpenv_controller_label_nn_io;
+int dpenv_controller_label_nn(dpenv_handle h, const dpenv_controller_label_nn_io* io, dpenv_stream s);
 /* The PID + QP chain on rows some other flight wrote (additive to ABI 6): dpenv_controller_label's scan with the QP law in place of the
  * f_m / bow / stern lines - the low-energy expert's labels for the states an actor visited.  One launch, one lane per env; per row t and
  * env i, in the order of the closed loop with a QP set:

@@ -124,6 +124,12 @@ class ControllerLabelQpExIO(C.Structure):
                                                ('refused_out', C.c_void_p)]
 
 
+class ControllerLabelNnIO(C.Structure):
+    _fields_ = [('struct_size', C.c_uint32), ('T', C.c_int32), ('obs', C.c_void_p), ('obs_dtype', C.c_int32), ('done', C.c_void_p),
+                ('z_in', C.c_void_p), ('z_out', C.c_void_p), ('act', C.c_void_p), ('raw', C.c_void_p), ('tau_out', C.c_void_p),
+                ('a', C.POINTER(NNAllocator))]
+
+
 class ScoreIO(C.Structure):
     _fields_ = [('struct_size', C.c_uint32), ('T', C.c_int32), ('n', C.c_int32), ('obs', C.c_void_p), ('act', C.c_void_p),
                 ('rew', C.c_void_p), ('done', C.c_void_p), ('integ', C.c_void_p), ('obs_dtype', C.c_int32), ('obs_stride', C.c_int32),
@@ -230,6 +236,7 @@ SYMBOLS = {
     'dpenv_nn_allocator_defaults': (C.c_int, [C.POINTER(NNAllocator)]),
     'dpenv_thrust_alloc_nn': (C.c_int, [C.POINTER(NNAllocator), _VP, _VP, _VP, _I32, _VP]),
     'dpenv_set_nn_allocator': (C.c_int, [_VP, C.POINTER(NNAllocator), _VP]),
+    'dpenv_controller_label_nn': (C.c_int, [_VP, C.POINTER(ControllerLabelNnIO), _VP]),
     'dpenv_train_param_count': (C.c_int64, [C.POINTER(TrainShape)]),
     'dpenv_train_workspace_bytes': (C.c_int, [C.POINTER(TrainShape), _I32, C.POINTER(C.c_int64)]),
     'dpenv_ppo_actor_grad': (C.c_int, [C.POINTER(TrainShape), _VP, _VP, _VP, _VP, _VP, _VP, _I32, _I32, _F, _VP, _VP, _VP, _I64, _VP]),

@@ -1413,14 +1413,17 @@ extern "C" int dpenv_set_qp_allocator_state(dpenv_handle h, const float* state_i
     return qp_state_io(h, "dpenv_set_qp_allocator_state", (float*)state_in, true, s);
 }
 
-// the shared opening of the three label entry points (who: the entry point's name, whose io struct is <who>_io)
+// the shared opening of the four label entry points (who: the entry point's name, whose io struct is <who>_io); act_optional: the scan
+// has another output the caller may want instead, and says itself which of them it needs
 template <class IO>
-static int check_label_io(dpenv_handle h, const char* who, const IO* io)
+static int check_label_io(dpenv_handle h, const char* who, const IO* io, bool act_optional = false)
 {
     if (!h->ctrl_on) return fail(h, DPENV_EINVAL, "%s: the DP controller is off (dpenv_set_dp_controller)", who);
     if (!io || io->struct_size != sizeof(IO)) return fail(h, DPENV_EINVAL, "%s_io ABI mismatch", who);
     if (io->T <= 0) return fail(h, DPENV_EINVAL, "%s: T > 0 is required", who);
-    if (!io->obs || !io->act) return fail(h, DPENV_EINVAL, "%s: the obs and act blocks are required", who);
+    if (act_optional) {
+        if (!io->obs) return fail(h, DPENV_EINVAL, "%s: the obs block is required", who);
+    } else if (!io->obs || !io->act) return fail(h, DPENV_EINVAL, "%s: the obs and act blocks are required", who);
     if (io->obs_dtype != DPENV_F32 && io->obs_dtype != DPENV_BF16) return fail(h, DPENV_EINVAL, "%s: obs_dtype must be DPENV_F32 or DPENV_BF16", who);
     return DPENV_OK;
 }
@@ -1510,6 +1513,36 @@ extern "C" int dpenv_controller_label_qp_ex(dpenv_handle h, const dpenv_controll
         e = dev::launch_controller_label_qp_ex(&h->ctrl, &g, &la, &xa, tab, bf16, (hipStream_t)s);
     }
     if (e != hipSuccess) return fail(h, DPENV_EHIP, "QP label launch failed: %s", hipGetErrorString(e));
+    return DPENV_OK;
+}
+
+// ... with the neural allocation behind the PID lines and / or the PID's wrench per row: io->a's network read in place, or the image and
+// constants dpenv_set_nn_allocator has in force.  Of the handle only the controller's numbers (or its table), dt and that image are read.
+extern "C" int dpenv_controller_label_nn(dpenv_handle h, const dpenv_controller_label_nn_io* io, dpenv_stream s)
+{
+    if (!h) return DPENV_EINVAL;
+    DeviceGuard dev_guard(h->device);
+    if (int rc = check_label_io(h, "dpenv_controller_label_nn", io, true)) return rc;
+    if (!io->act && !io->tau_out) return fail(h, DPENV_EINVAL, "dpenv_controller_label_nn: act and tau_out are both NULL (nothing to write)");
+    if (io->raw && !io->act) return fail(h, DPENV_EINVAL, "dpenv_controller_label_nn: raw goes with act");
+    NnArgs g = {};
+    const bool own = io->a != nullptr;
+    if (io->act) {                                         // (the wrench-only scan does not look at a)
+        if (own) {
+            if (const char* why = nn_check_in_place(io->a, g)) return fail(h, DPENV_EINVAL, "%s", why);
+        } else if (h->stage == ALLOC_NN) {
+            g = h->nn.a;
+        } else {
+            return fail(h, DPENV_EINVAL, "dpenv_controller_label_nn: no neural allocator (pass a, or dpenv_set_nn_allocator first)");
+        }
+    }
+    LabelNnArgs la = {};
+    la.obs = io->obs; la.done = io->done; la.z_in = io->z_in; la.z_out = io->z_out;
+    la.act = io->act; la.raw = io->raw; la.tau = io->tau_out;
+    la.T = io->T; la.n = h->cfg.n_envs;
+    const hipError_t e = dev::launch_controller_label_nn(&h->ctrl, io->act ? &g : nullptr, &la, h->ctrl_tab_on ? h->ctrl_tab : nullptr,
+                                                         io->obs_dtype == DPENV_BF16, own ? 0 : 1, (hipStream_t)s);
+    if (e != hipSuccess) return fail(h, DPENV_EHIP, "NN label launch failed: %s", hipGetErrorString(e));
     return DPENV_OK;
 }
 

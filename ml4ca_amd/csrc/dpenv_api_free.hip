@@ -433,14 +433,21 @@ const char* host::nn_check(const dpenv_nn_allocator* a, NnArgs& g)
     return nullptr;
 }
 
+// ... for the calls that read the weights where they are (dpenv_thrust_alloc_nn, dpenv_controller_label_nn with a network of its own)
+const char* host::nn_check_in_place(const dpenv_nn_allocator* a, NnArgs& g)
+{
+    if (const char* why = nn_check(a, g)) return why;
+    if (a->device_pointers != 1) return "NN allocator: device_pointers must be 1 (the weights are read in place)";
+    return nullptr;
+}
+
 extern "C" int dpenv_thrust_alloc_nn(const dpenv_nn_allocator* a, const float* tau, float* action_out, float* raw_out, int32_t n, dpenv_stream s)
 {
     if (!a) return fail(nullptr, DPENV_EINVAL, "dpenv_thrust_alloc_nn: a is NULL");
     if (!tau || !action_out) return fail(nullptr, DPENV_EINVAL, "dpenv_thrust_alloc_nn: tau and action_out must not be NULL");
     if (n <= 0) return fail(nullptr, DPENV_EINVAL, "dpenv_thrust_alloc_nn: n must be > 0");
     NnArgs g;
-    if (const char* why = nn_check(a, g)) return fail(nullptr, DPENV_EINVAL, "%s", why);
-    if (a->device_pointers != 1) return fail(nullptr, DPENV_EINVAL, "dpenv_thrust_alloc_nn: device_pointers must be 1 (the weights are read in place)");
+    if (const char* why = nn_check_in_place(a, g)) return fail(nullptr, DPENV_EINVAL, "%s", why);
     HIP_TRY(nullptr, dev::launch_nn_alloc(&g, tau, action_out, raw_out, n, (hipStream_t)s));
     return DPENV_OK;
 }

@@ -1,7 +1,7 @@
 // dpenv_control_law.h - the baseline DP controller's law (include/dpenv.h states it operation by operation): the numbers of one env, the
 // packed per-env table's index and load, the allocation and one control step.  The ONE text of the law on the device: included inside
-// namespace dpenv by dpenv_control.hip (the closed-loop kernels) and by dpenv_label.hip (the labelling scan), after
-// dpenv_dev.h.  Everything here is plain f32 in the stated order: the build has -ffp-contract=off, `/` and sqrtf are the compiler's
+// namespace dpenv by dpenv_control.hip and dpenv_control_nn.hip (the closed-loop kernels) and by dpenv_label.hip and dpenv_label_nn.hip
+// (the labelling scans), after dpenv_dev.h.  Everything here is plain f32 in the stated order: the build has -ffp-contract=off, `/` and sqrtf are the compiler's
 // correctly rounded forms.
 #ifndef DPENV_CONTROL_LAW_H
 #define DPENV_CONTROL_LAW_H

@@ -77,11 +77,6 @@ __global__ __launch_bounds__(NN_MAX_H) void nn_pack_kernel(const NnPack np)
 
 using namespace dpenv;
 
-static bool nn_shape_ok(int n_layers, int in_dim, int H)
-{
-    return n_layers >= 2 && n_layers <= NN_MAX_LAYERS && (in_dim == 3 || in_dim == 9) && H >= 1 && H <= NN_MAX_H;
-}
-
 hipError_t dev::launch_nn_alloc(const NnArgs* na, const float* tau, float* action, float* raw, int n, hipStream_t s)
 {
     if (!nn_shape_ok(na->n_layers, na->in_dim, na->H) || !tau || !action || n <= 0) return hipErrorInvalidValue;

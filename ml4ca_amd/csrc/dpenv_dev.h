@@ -288,6 +288,11 @@ struct NnArgs {
     int32_t azimuth_mode;
     float azimuth[2];
 };
+// what the launchers of the units that evaluate the network (dpenv_control_nn.hip, dpenv_label_nn.hip) refuse of a shape
+inline bool nn_shape_ok(int n_layers, int in_dim, int H)
+{
+    return n_layers >= 2 && n_layers <= NN_MAX_LAYERS && (in_dim == 3 || in_dim == 9) && H >= 1 && H <= NN_MAX_H;
+}
 // the allocation as the allocation stage of the baseline's closed loop (dpenv_set_nn_allocator): a separate argument of
 // controller_rollout_nn_kernel only; the weights are the handle's padded image
 struct NnRollout {
@@ -490,6 +495,18 @@ struct LabelQpExArgs {
     uint8_t* refused;           // [n] or NULL; with qp_table
     int32_t iters;              // with qp_table: 1 .. QP_MAX_ITERS
 };
+// the scan with the neural allocation behind the PID lines (dpenv_controller_label_nn; the kernel is dpenv_label_nn.hip's): the law has no
+// state, so only z travels.  The network's numbers travel as NnArgs (not read when act is NULL), the PID's as ControlArgs or the table.
+struct LabelNnArgs {
+    const void* obs;            // [T][n][9] f32 or bf16, columns 0..5 read
+    const uint8_t* done;        // [T][n] or NULL
+    const float* z_in;          // [3][n] or NULL = 0
+    float* z_out;               // [3][n] or NULL; may be z_in
+    float* act;                 // [T][n][7], or NULL = the wrench-only scan: the network is not evaluated
+    float* raw;                 // [T][n][6] the network's six outputs, or NULL; with act
+    float* tau;                 // [T][n][3] the PID's clipped wrench, or NULL
+    int T, n;
+};
 
 // ---- launchers: called by the host units (dpenv_api.hip, dpenv_api_free.hip), defined by the translation unit that owns the kernels; not exported from libdpenv.so ----
 namespace __attribute__((visibility("hidden"))) dev {
@@ -572,6 +589,10 @@ hipError_t launch_nn_alloc(const NnArgs* na, const float* tau, float* action, fl
 hipError_t launch_controller_rollout_nn(const StepArgs* a, const ControlArgs* ca, const FilterArgs* fa, const NnRollout* nr, int ves, hipStream_t s);
 // the caller's DEVICE arrays -> the zero-padded image, one launch
 hipError_t launch_nn_pack(const NnPack* np, hipStream_t s);
+// dpenv_label_nn.hip: launch_controller_label's scan with the neural allocation in place of the pseudo-inverse and, if la->tau, the PID's
+// wrench per row; na: NULL exactly when la->act is NULL; padded: na's W and b are the zero-padded image, else arrays read in place
+hipError_t launch_controller_label_nn(const ControlArgs* ca, const NnArgs* na, const LabelNnArgs* la, const float4* tab, int obs_bf16, int padded,
+                                      hipStream_t s);
 // two-wave closed loop, dpenv_policy_ws.h; one arithmetic per translation unit: dpenv_policy_ws.hip PREC_F16, dpenv_policy_xws1.hip
 // PREC_F32, dpenv_policy_xws2.hip PREC_F32_ACTOR
 template <int PREC>

@@ -51,6 +51,8 @@ const char* qp_check(const dpenv_qp_allocator* q, float dt, QpArgs& g);
 // the neural allocation's shape and constants into NnArgs (W and b are the caller's pointers, required non-NULL, not dereferenced), or an
 // error message; device_pointers is not looked at
 const char* nn_check(const dpenv_nn_allocator* a, NnArgs& g);
+// nn_check, then device_pointers == 1: what the calls that read the weights in place demand
+const char* nn_check_in_place(const dpenv_nn_allocator* a, NnArgs& g);
 
 }  // namespace host
 }  // namespace dpenv

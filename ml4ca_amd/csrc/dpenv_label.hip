@@ -30,11 +30,10 @@ namespace dpenv {
 #include "dpenv_qp_law.h"
 // control_store_rows: a wave's 64 action rows staged through the wave-private LDS area, stored coalesced
 #include "dpenv_control_rows.h"
+// LABEL_U and label_lane, shared with the network's scan (dpenv_label_nn.hip)
+#include "dpenv_label_lane.h"
 
 namespace {
-
-// rows fetched ahead per register bank, two banks (score_kernel's scheme and its winner, dpenv_score_dev.h): a row is 7 loads per lane
-constexpr int LABEL_U = 2;
 
 struct LabelRow {
     float o[6];
@@ -47,22 +46,6 @@ struct LabelRowEx {
     uint32_t d;
     float f[FLOWN ? 7 : 1];
 };
-
-// one wave per workgroup, one lane per env: dead lanes shadow env n - 1 (il) and store nothing
-struct LabelLane {
-    int lane, wave0, i, il;
-    bool live;
-};
-__device__ __forceinline__ LabelLane label_lane(int n)
-{
-    LabelLane L;
-    L.lane = threadIdx.x;
-    L.wave0 = blockIdx.x * 64;
-    L.i = L.wave0 + L.lane;
-    L.live = L.i < n;
-    L.il = L.live ? L.i : n - 1;
-    return L;
-}
 
 // Forward scan over the T rows of a block, one lane per env, one wave per workgroup.  The law is serial in t, but no load depends on it:
 // rows are fetched LABEL_U at a time into one of two register banks while the other is consumed.  TAB: the env's own row of the packed

@@ -1130,6 +1130,38 @@ class BatchedNNAllocator(object):
         return (act, p) if raw else act
 
 
+def label_rows_nn(params_or_table, net, obs, done=None, z=None, dt=0.2, dtype=None, nn_params=None):
+    """The PID + network chain's actions on a block of observation rows some other flight wrote - the host statement of
+    dpenv_controller_label_nn (policy.controller_label_nn), NumPy on the CPU.  obs, done, z, params_or_table and dt as label_rows takes
+    them; net and nn_params as BatchedNNAllocator takes them (nn_params None = the defaults with the net's leak).  Per row t, in this order:
+        tau[t] = ctrl.wrench(obs[t]);  act[t], raw[t] = alloc.allocate(tau[t], raw=True);  ctrl.reset(done[t] != 0)
+    - z is advanced before the wrench and zeroed BEHIND a done row; the network has no state.  Returns (act [T, n, 7], z [3, n],
+    raw [T, n, 6], tau [T, n, 3]) in dtype (None = float32: the kernel's bits except for the sin / cos heads, see BatchedNNAllocator);
+    labelling rows [0:k] and [k:T] with z handed over equals one call."""
+    obs = np.asarray(obs)
+    if obs.ndim != 3 or obs.shape[2] < 6:
+        raise ValueError('label_rows_nn: obs is [T, n, >= 6]')
+    T, n = obs.shape[0], obs.shape[1]
+    if done is not None:
+        done = np.asarray(done)
+        if done.shape != (T, n):
+            raise ValueError('label_rows_nn: done is [T, n]')
+    ctrl = BatchedDPController(n, params_or_table, dt=dt, dtype=dtype)
+    alloc = BatchedNNAllocator(n, net, dtype=dtype, params=nn_params)
+    if z is not None:
+        z = np.asarray(z)
+        if z.shape != (3, n):
+            raise ValueError('label_rows_nn: z is [3, n]')
+        ctrl.z = np.ascontiguousarray(z.T).astype(ctrl.dtype)
+    act, raw, tau = np.empty((T, n, 7), ctrl.dtype), np.empty((T, n, 6), ctrl.dtype), np.empty((T, n, 3), ctrl.dtype)
+    for t in range(T):
+        tau[t] = ctrl.wrench(obs[t])
+        act[t], raw[t] = alloc.allocate(tau[t], raw=True)
+        if done is not None:
+            ctrl.reset(done[t] != 0)
+    return act, np.ascontiguousarray(np.asarray(ctrl.z).T), raw, tau
+
+
 def thrust_map_host(n_pct, alpha, vessel=None):
     """tau = B(alpha) F(n) on the host, float64 - SupervisedTau.tau (SupervisedTau.py:42-83) with the hull's numbers, the statement of
     dpenv_thrust_map without the inflow thrust loss: n_pct, alpha [3, n] in env order (bow, port, star), F_i = K_i n_i |n_i| with K_i =

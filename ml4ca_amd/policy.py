@@ -557,6 +557,75 @@ def nn_net_to(net, device):
     return out
 
 
+def controller_label_nn(env, obs, done=None, z=None, net=None, out=None, raw=False, tau=False, act=True, **constants):
+    """The PID + network chain's actions on a block of rows some OTHER flight wrote (dpenv_controller_label_nn), in one launch:
+    controller_label with the neural allocation in place of the pseudo-inverse, and on request the PID's clipped wrench per row - the
+    value the allocator is handed, which the closed loop never writes.  obs [T, n, 9] float32 or bfloat16, done [T, n] uint8 or None,
+    z [3, n] float32 or None = 0 as controller_label takes them.  Per row: the PID lines of env.set_dp_controller (row i of the table
+    while one is in force) on obs[t] with z advanced first, the network on that wrench, z zeroed behind a done row.  net: a dict with
+    'W' and 'b' as thrust_alloc_nn takes it (tensors on the env's device are read in place, anything else is copied there first), with
+    constants on top of deploy.nn_allocator_defaults; None = the network env.set_nn_allocator has in force (an error if none is set;
+    constants are then an error too).  With an explicit net the env's allocation stage does not matter: an env with a controller table
+    or a QP set labels with a network.  Returns (act [T, n, 7], z [3, n]), then raw [T, n, 6] (the network's six outputs) with raw=True,
+    then tau [T, n, 3] with tau=True.  act=False with tau=True is the wrench-only scan: no network is needed or looked at, act is
+    returned as None.  out supplies the buffers in the order of the return value (z may be the input tensor itself).  Nothing of the
+    env changes.  For float32 rows of controller_rollout with a network set and auto-reset on the labels (net=None) are that launch's
+    act rows bit for bit; on any block act and raw are thrust_alloc_nn on tau, row by row, bit for bit.  deploy.label_rows_nn is the
+    host statement."""
+    torch = _torch()
+    n = env.n_envs
+    dev, f32 = env.device, torch.float32
+    if not act and not tau:
+        raise ValueError('controller_label_nn: act=False and tau=False leave nothing to compute')
+    if raw and not act:
+        raise ValueError('controller_label_nn: raw goes with act')
+    if not act and (net is not None or constants):
+        raise ValueError('controller_label_nn: the wrench-only scan (act=False) takes no net and no constants')
+    if net is None and constants:
+        raise ValueError('controller_label_nn: constants go with net (net=None labels with the network and constants the env has in force)')
+    if not isinstance(obs, torch.Tensor) or obs.dim() != 3:
+        raise ValueError('controller_label_nn: obs is a tensor [T, n, 9]')
+    if obs.dtype not in (torch.float32, torch.bfloat16):
+        raise ValueError('controller_label_nn: obs rows are float32 or bfloat16, not %s' % (obs.dtype,))
+    T = int(obs.shape[0])
+    env._chk(obs, (T, n, 9), obs.dtype, 'obs')
+    env._chk(done, (T, n), torch.uint8, 'done')
+    env._chk(z, (3, n), f32, 'z')
+    want = [('act', (T, n, 7), bool(act)), ('z', (3, n), True), ('raw', (T, n, 6), bool(raw)), ('tau', (T, n, 3), bool(tau))]
+    names = [w[0] for w in want if w[2] or w[0] == 'act']
+    if out is not None and len(out) != len(names):
+        raise ValueError('controller_label_nn: out is (%s)' % ', '.join(names))
+    buf = dict(zip(names, out)) if out is not None else {}
+    for name, shape, on in want:
+        if not on:
+            if buf.get(name) is not None:
+                raise ValueError('controller_label_nn: out has a buffer for %s, which is not asked for' % name)
+            buf[name] = None
+            continue
+        if buf.get(name) is None:
+            buf[name] = torch.empty(shape, dtype=f32, device=dev)
+        env._chk(buf[name], shape, f32, "out's %s" % name)
+    a, keep = None, None
+    if net is not None:
+        from .deploy import nn_allocator_params
+        a, keep = nn_allocator_struct(nn_net_to(net, dev), nn_allocator_params(net, **constants), dev)
+    io = _lib.ControllerLabelNnIO()
+    io.struct_size = C.sizeof(_lib.ControllerLabelNnIO)
+    io.T = T
+    io.obs = obs.data_ptr()
+    io.obs_dtype = 1 if obs.dtype == torch.bfloat16 else 0
+    io.done = done.data_ptr() if done is not None else None
+    io.z_in = z.data_ptr() if z is not None else None
+    io.z_out = buf['z'].data_ptr()
+    io.act = buf['act'].data_ptr() if act else None
+    io.raw = buf['raw'].data_ptr() if raw else None
+    io.tau_out = buf['tau'].data_ptr() if tau else None
+    io.a = C.pointer(a) if a is not None else None
+    _lib.check(env.lib.dpenv_controller_label_nn(env._h, C.byref(io), env._stream()), env._h)
+    del keep
+    return tuple(buf[k] for k in names)
+
+
 def thrust_alloc_nn(tau, net, out=None, raw=False, **constants):
     """The neural thrust allocation on the device (dpenv_thrust_alloc_nn), one lane per env: tau float32 [3, n] = Fx, Fy, Mz -> the final
     variant's continuous-angle action [n, 7] and, with raw=True, the network's six outputs [n, 6] as a second value.  net: a dict with

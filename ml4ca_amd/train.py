@@ -455,7 +455,8 @@ def nn_allocator_minibatches(rows, count, iters, seed):
     return torch.stack([torch.randperm(rows, generator=gen)[:count] for _ in range(int(iters))])
 
 
-def fit_nn_allocator(dataset, in_dim=9, iters=200, lr=1e-3, minibatch=256, seed=0, leak=0.2, device='cuda:0', loss='mse', alloc_loss=None):
+def fit_nn_allocator(dataset, in_dim=9, iters=200, lr=1e-3, minibatch=256, seed=0, leak=0.2, device='cuda:0', loss='mse', alloc_loss=None,
+                     init=None):
     """Fit the neural thrust allocator (include/dpenv.h, "the neural thrust allocation") to a dataset of deploy.nn_allocator_dataset:
     FFNN.py's loss and optimiser - mean squared error, Adam - as `iters` steps of dpenv_imitation_grad(MSE) + dpenv_adam_step on
     minibatches drawn with a seeded generator, everything on the device, nothing read back inside the loop.  The network is the fused
@@ -466,6 +467,9 @@ def fit_nn_allocator(dataset, in_dim=9, iters=200, lr=1e-3, minibatch=256, seed=
     dpenv_allocation_grad on dataset['x'] and dataset['tau'] - the QP law's objective at the network's output, through the force map, no
     labels (include/dpenv.h, ALLOCATION LOSS).  alloc_loss: that loss's numbers, the dict of deploy.alloc_loss_defaults whole or in part
     (e.g. dict(w_power=0.05)); they also define the wrench figures below.
+    init: a flat float32 theta [P] (an array, or a tensor on any device; P = layout(in_dim, 6, True)['P'], a fit's 'theta') to start from
+    instead of nn_allocator_init(in_dim, seed); it is copied, not changed.  Adam's state starts at zero either way.  The dataset's x, y
+    and tau may be float32 tensors (nn_wrench_rows' are): they are then used on the device without a host copy.
     Returns dict(W, b - views of the flat parameter tensor on the device, what env.set_nn_allocator and policy.thrust_alloc_nn read in
     place - leak, theta, loss; mse_initial, mse_final: mean_rows(sum_j (out_j - y_j)^2) over the WHOLE dataset before and after (None
     without dataset['y']); J_initial, J_final, wrench_ms_initial, wrench_ms_final: the allocation loss and its mean Js - the mean squared
@@ -474,23 +478,34 @@ def fit_nn_allocator(dataset, in_dim=9, iters=200, lr=1e-3, minibatch=256, seed=
     f32 = torch.float32
     if loss not in FIT_LOSSES:
         raise ValueError("fit_nn_allocator: loss must be 'mse' or 'wrench' (got %r)" % (loss,))
-    x = np.asarray(dataset['x'], np.float32)
-    y = np.asarray(dataset['y'], np.float32) if dataset.get('y') is not None else None
-    tau = np.asarray(dataset['tau'], np.float32) if dataset.get('tau') is not None else None
-    if in_dim not in (3, 9) or x.ndim != 2 or x.shape[1] < in_dim:
+    is_t = lambda a: isinstance(a, torch.Tensor)
+    host = lambda a: a if a is None or is_t(a) else np.asarray(a, np.float32)
+    x, y, tau = host(dataset['x']), host(dataset.get('y')), host(dataset.get('tau'))
+    if in_dim not in (3, 9) or len(x.shape) != 2 or x.shape[1] < in_dim:
         raise ValueError('fit_nn_allocator: in_dim is 3 or 9, the dataset has x [rows, >= in_dim]')
-    if (loss == 'mse' or y is not None) and (y is None or y.shape != (x.shape[0], 6)):
+    if (loss == 'mse' or y is not None) and (y is None or tuple(y.shape) != (x.shape[0], 6)):
         raise ValueError("fit_nn_allocator: loss='mse' fits the labels y [rows, 6]")
-    if (loss == 'wrench' or tau is not None) and (tau is None or tau.shape != (x.shape[0], 3)):
+    if (loss == 'wrench' or tau is not None) and (tau is None or tuple(tau.shape) != (x.shape[0], 3)):
         raise ValueError("fit_nn_allocator: loss='wrench' reads the wrenches tau [rows, 3]")
-    rows = x.shape[0]
-    x = torch.as_tensor(np.ascontiguousarray(x[:, x.shape[1] - in_dim:])).to(device)
+    rows = int(x.shape[0])
+    if rows < 1:
+        raise ValueError('fit_nn_allocator: the dataset has no rows')
+    P = layout(in_dim, 6, True)['P']
+    if init is not None:
+        if not is_t(init):
+            init = torch.as_tensor(np.asarray(init))
+        if init.dim() != 1 or init.numel() != P or init.dtype != f32:
+            raise ValueError('fit_nn_allocator: init is a flat float32 theta of %d entries for in_dim %d (got %s %s)'
+                             % (P, in_dim, init.dtype, list(init.shape)))
+    dev_of = lambda a: a.to(device=device, dtype=f32) if is_t(a) else torch.as_tensor(np.ascontiguousarray(a)).to(device)
+    x = dev_of(x[:, x.shape[1] - in_dim:]).contiguous()
     if y is not None:
-        y = torch.as_tensor(np.ascontiguousarray(y)).to(device)
+        y = dev_of(y).contiguous()
     if tau is not None:                                          # the kernel's [rows, 6] target rows: the wrench, then three columns nothing reads
-        tau = torch.as_tensor(np.ascontiguousarray(np.concatenate([tau, np.zeros_like(tau)], 1))).to(device)
+        tau = dev_of(tau)
+        tau = torch.cat([tau, torch.zeros_like(tau)], 1).contiguous()
     qp = alloc_loss_params(alloc_loss)
-    theta = torch.as_tensor(nn_allocator_init(in_dim, seed)).to(device)
+    theta = torch.as_tensor(nn_allocator_init(in_dim, seed)).to(device) if init is None else init.to(device).clone()
     P = layout(in_dim, 6, True)['P']
     m, v = torch.zeros(P, dtype=f32, device=device), torch.zeros(P, dtype=f32, device=device)
     step = torch.zeros(1, dtype=torch.int32, device=device)
@@ -517,6 +532,93 @@ def fit_nn_allocator(dataset, in_dim=9, iters=200, lr=1e-3, minibatch=256, seed=
     first = lambda s, k: None if s is None else s[k]
     return dict(W=list(tW), b=list(tb), leak=float(leak), theta=theta, loss=loss, mse_initial=first(mse0, 0), mse_final=first(mse1, 0),
                 J_initial=first(wr0, 0), J_final=first(wr1, 0), wrench_ms_initial=first(wr0, 1), wrench_ms_final=first(wr1, 1))
+
+
+def nn_wrench_rows(tau, in_dim=9, params=None):
+    """Wrenches -> the rows fit_nn_allocator(loss='wrench') takes, on the device: tau, a float32 device tensor [R, 3] (N, N, Nm; a
+    policy.controller_label_nn(tau=True) block viewed as rows), -> dict(x [R, in_dim], tau [R, 3]).  x[:, -3:] = tau * tau_scale, one
+    float32 product per entry with tau_scale rounded to float32 first - the bits of the input the kernels form; with in_dim 9 the first
+    six columns are in_const.  params: the dict of deploy.nn_allocator_defaults (None = the defaults)."""
+    torch = _torch()
+    from .deploy import nn_allocator_defaults
+    if not isinstance(tau, torch.Tensor) or tau.dim() != 2 or tau.shape[1] != 3 or tau.dtype != torch.float32:
+        raise ValueError('nn_wrench_rows: tau is a float32 tensor [R, 3]')
+    if in_dim not in (3, 9):
+        raise ValueError('nn_wrench_rows: in_dim is 3 or 9')
+    p = nn_allocator_defaults() if params is None else params
+    f32_of = lambda v: torch.as_tensor(np.asarray(v, np.float64).astype(np.float32)).to(tau.device)
+    x = torch.empty((tau.shape[0], in_dim), dtype=torch.float32, device=tau.device)
+    x[:, in_dim - 3:] = tau * f32_of(p['tau_scale'])
+    if in_dim == 9:
+        x[:, :6] = f32_of(p['in_const'])
+    return dict(x=x, tau=tau)
+
+
+def fit_nn_allocator_on_policy(env, rounds, T, iters, base=None, keep=None, lr=1e-3, minibatch=256, seed=0, leak=0.2, alloc_loss=None, in_dim=9):
+    """Fit the neural allocator to the wrenches its own closed loop asks of it: `rounds` x (fly the PID + network chain, read the PID's
+    clipped wrench on every row flown, refit through the force map).  The wrench loss needs no labels, only wrenches; the closed loop
+    never writes them, the labelling scan does (policy.controller_label_nn(act=False, tau=True)).  env: an env with the baseline on
+    (env.set_dp_controller) that can fly a network (no controller table, no QP allocator); its resets, currents, reference filter and
+    hull randomisation are the caller's and decide which wrenches are flown.  base: an optional deploy.nn_allocator_dataset dict; it is
+    fitted first - fit_nn_allocator(base, loss='wrench', seed=seed) from nn_allocator_init(in_dim, seed) - and its rows stay in the pool
+    of every round.  Without base the first flight is the initial network's.  Per round r:
+      1. env.set_nn_allocator(net) with the network so far (constants: the defaults, the leak `leak`)
+      2. z = env.get_dp_controller_state(), then policy.controller_rollout(env, T)
+      3. controller_label_nn(act=False, tau=True) on the block's obs / done from that z, written into slot `r % keep` of a preallocated
+         wrench pool [keep * T * n, 3] (keep=None: every round has its own slot)
+      4. fit_nn_allocator(loss='wrench', init=theta, seed=seed + 1 + r) on base's rows followed by nn_wrench_rows of the filled slots,
+         rows whose wrench is not finite left out
+    Adam's state starts at zero in every round (fit_nn_allocator owns it).  Returns dict(W, b, leak, theta - the last round's network, as
+    fit_nn_allocator returns it -, rounds = one record per round: dict(rows, J_initial, J_final, wrench_ms_initial, wrench_ms_final) on
+    that round's pool before and after its refit, base = the base fit's record (None without base), pool = the wrench pool
+    [keep * T * n, 3], filled = its rows in use, T, n, keep).  The network is left set on the env; z and the env's state run on through
+    the rounds."""
+    torch = _torch()
+    from .policy import controller_label_nn, controller_rollout
+    rounds, T, iters = int(rounds), int(T), int(iters)
+    if rounds < 1 or T < 1 or iters < 1:
+        raise ValueError('fit_nn_allocator_on_policy: rounds, T and iters are >= 1')
+    if env.dp_controller is None:
+        raise ValueError('fit_nn_allocator_on_policy: the baseline DP controller forms the wrench; env.set_dp_controller() first')
+    keep = rounds if keep is None else int(keep)
+    if keep < 1:
+        raise ValueError('fit_nn_allocator_on_policy: keep >= 1')
+    keep = min(keep, rounds)
+    n, dev, f32 = env.n_envs, env.device, torch.float32
+    R = T * n
+    pool = torch.empty((keep * R, 3), dtype=f32, device=dev)
+    zbuf = torch.empty((3, n), dtype=f32, device=dev)
+    fit_kw = dict(in_dim=in_dim, iters=iters, lr=lr, minibatch=minibatch, leak=leak, device=dev, loss='wrench', alloc_loss=alloc_loss)
+    base_rec, bx, bt = None, None, None
+    if base is not None:
+        fit = fit_nn_allocator(base, seed=seed, **fit_kw)
+        base_rec = {k: fit[k] for k in ('J_initial', 'J_final', 'wrench_ms_initial', 'wrench_ms_final')}
+        base_rec['rows'] = int(np.shape(base['x'])[0])
+        theta = fit['theta']
+        bx = torch.as_tensor(np.ascontiguousarray(np.asarray(base['x'], np.float32)[:, -in_dim:])).to(dev)
+        bt = torch.as_tensor(np.asarray(base['tau'], np.float32)).to(dev)
+    else:
+        theta = torch.as_tensor(nn_allocator_init(in_dim, seed)).to(dev)
+    out, records = None, []
+    for r in range(rounds):
+        tW, tb, _ = unflatten(theta, in_dim, 6, True)
+        env.set_nn_allocator(dict(W=list(tW), b=list(tb), leak=float(leak)))
+        z = env.get_dp_controller_state()
+        out = controller_rollout(env, T, out=out)
+        slot = r % keep
+        controller_label_nn(env, out['obs'], out['done'], z=z, act=False, tau=True, out=(None, zbuf, pool[slot * R:(slot + 1) * R].view(T, n, 3)))
+        filled = min(r + 1, keep) * R
+        flown = pool[:filled]
+        flown = flown[torch.isfinite(flown).all(1)]
+        ds = nn_wrench_rows(flown, in_dim)
+        if bx is not None:
+            ds = dict(x=torch.cat([bx, ds['x']]), tau=torch.cat([bt, ds['tau']]))
+        fit = fit_nn_allocator(ds, seed=seed + 1 + r, init=theta, **fit_kw)
+        theta = fit['theta']
+        rec = {k: fit[k] for k in ('J_initial', 'J_final', 'wrench_ms_initial', 'wrench_ms_final')}
+        rec['rows'] = int(ds['x'].shape[0])
+        records.append(rec)
+    return dict(W=fit['W'], b=fit['b'], leak=float(leak), theta=theta, rounds=records, base=base_rec, pool=pool, filled=filled, T=T, n=n, keep=keep)
 
 
 # ---- the whole update ----------------------------------------------------------------------------------------------------------------
@@ -628,7 +730,7 @@ class PPOUpdater(object):
 
     # ---- DAgger: expert labels on the states the ACTOR visits, aggregated over rounds (Ross et al. 2011) ----
     def dagger(self, env, rounds, T, iters, minibatch=None, loss='mse', keep=None, sample=False, reset_at_end=False, lr=None, average=None,
-               upload=None, expert='pinv', qp_params=None, thruster_state='own', qp_table=None):
+               upload=None, expert='pinv', qp_params=None, thruster_state='own', qp_table=None, nn_net=None, nn_constants=None):
         """`rounds` x (fly the actor, label its states with the baseline DP controller, aggregate, refit).  env: a float32-row env with
         the baseline on (env.set_dp_controller; a table of set_dp_controller_table in force is the one that labels).  Per round:
           1. ac.upload(env, **upload)                       (upload: keyword arguments of ActorCritic.upload, e.g. dict(precision='f32'))
@@ -659,19 +761,25 @@ class PPOUpdater(object):
         row left, is handed from round to round and zeroed by reset_at_end.  qp_table (expert='qp'): a float32 device tensor [32, n]
         (deploy.qp_allocator_table), env i labelled with row i in qp_params['iterations'] solver steps (16 without qp_params) - one
         expert per env; the scalar numbers are then not read.
+        expert='nn': step 3 is policy.controller_label_nn with the explicit network nn_net (a dict with 'W' and 'b', as
+        train.fit_nn_allocator returns one; nn_constants: a dict of deploy.nn_allocator_defaults' entries to override) - the same PID
+        with the neural allocation.  The network has no state: only z is carried.  The env need not fly the network: a controller table
+        or a QP set label like any other.  thruster_state / qp_table are refused as for 'pinv'; nn_net goes with expert='nn' only.
         Not here: beta-mixed flights in which the expert executes some of the steps, an integral-augmented actor, bf16 rows (the gradient
         kernels take float32 rows: a bf16 env raises ValueError)."""
         torch = _torch()
-        from .policy import controller_label, controller_label_qp, policy_rollout
+        from .policy import controller_label, controller_label_nn, controller_label_qp, policy_rollout
         rounds, T, iters = int(rounds), int(T), int(iters)
         if rounds < 1 or T < 1 or iters < 1:
             raise ValueError('dagger: rounds, T and iters are >= 1')
-        if expert not in ('pinv', 'qp'):
-            raise ValueError("dagger: expert is 'pinv' or 'qp', not %r" % (expert,))
+        if expert not in ('pinv', 'qp', 'nn'):
+            raise ValueError("dagger: expert is 'pinv', 'qp' or 'nn', not %r" % (expert,))
         if thruster_state not in ('own', 'flown'):
             raise ValueError("dagger: thruster_state is 'own' or 'flown', not %r" % (thruster_state,))
         if expert != 'qp' and (thruster_state != 'own' or qp_table is not None):
             raise ValueError("dagger: thruster_state and qp_table go with expert='qp' (the pseudo-inverse has no thruster state)")
+        if (expert == 'nn') != (nn_net is not None) or (nn_constants is not None and expert != 'nn'):
+            raise ValueError("dagger: expert='nn' labels with the network nn_net; nn_net and nn_constants go with expert='nn' only")
         if env.obs_torch_dtype != torch.float32:
             raise ValueError('dagger: the gradient kernels take float32 rows; make the env with float32 obs rows (got %s)' % (env.obs_torch_dtype,))
         if env.dp_controller is None:
@@ -704,6 +812,8 @@ class PPOUpdater(object):
                                     iterations=int(qp['iterations']) if qp_table is not None else None)
                 if reset_at_end:
                     x.zero_()
+            elif expert == 'nn':
+                controller_label_nn(env, out['obs'], out['done'], z=z, net=nn_net, out=(labels, z), **(nn_constants or {}))
             else:
                 controller_label(env, out['obs'], out['done'], z=z, out=(labels, z))
             if reset_at_end:

@@ -28,6 +28,8 @@ env.step, critic, trajectory rows), GAE by one scan kernel, advantage statistics
                                                                                       behind the baseline's PID beside the pseudo-inverse and the QP
     python examples/train_ppo.py --envs 4096 --epochs 30 --eval --nn-allocator 5000 --nn-loss wrench --nn-w-power 0.05
                                                                                       ... the same network trained through the force map (the allocation loss)
+    python examples/train_ppo.py --envs 4096 --epochs 1 --eval --tune-nn 8            the neural allocator's IAE / work front in ONE flight: 8 wrench-loss
+                                                                                      fits (w_power 0, 0.01 .. 1), one network per 64 envs
 """
 import argparse
 import os
@@ -195,6 +197,66 @@ def tune_qp(dev, preset, K, seed=0, out=print, directions=16, vc=0.2):
     out('tuneqp  lowest IAE       : ' + row(int(iae.argmin())))
     out('tuneqp  least work       : ' + row(int(tot.argmin())))
     return {'mean_iae': iae.tolist(), 'mean_work': work.tolist(), 'front': [int(k) for k in sw['front']]}
+
+
+def nn_w_power_grid(K):
+    """--tune-nn's power weights: 0 (no power term: the tracking end of the front), then K - 1 values spaced evenly in the logarithm from
+    0.01 to 1 (the QP's own weight: the thrifty end); K = 1 is 0.05, the README's one-at-a-time pick."""
+    import numpy as np
+    if K == 1:
+        return [0.05]
+    return [0.0] + [float(w) for w in np.geomspace(0.01, 1.0, K - 1)]
+
+
+def tune_nn(args, dev, preset, K, seed=0, out=print, directions=16, vc=0.2):
+    """The neural allocator's trade-off curve beside tune_qp's (evaluate.nn_allocator_sweep): K wrench-loss fits, one per w_power of
+    nn_w_power_grid(K) (train.fit_nn_allocator_population; --nn-allocator ITERS Adam steps each, 5000 if not given), flown as ONE
+    population - network k on envs 64 k .. 64 k + 63, four envs per current direction - in one scored box test behind the reference
+    filter; then the same K box tests one network at a time, for the clock and as a check (the per-env scores are equal)."""
+    import math
+    from ml4ca_amd import evaluate as EV
+    from ml4ca_amd.deploy import dp_controller_defaults, nn_allocator_dataset
+    from ml4ca_amd.train import alloc_loss_params, fit_nn_allocator_population
+    nominal = ml4ca_amd.default_vessel(preset)
+    grid = nn_w_power_grid(K)
+    iters = args.nn_allocator or 5000
+    t0 = time.perf_counter()
+    nets = fit_nn_allocator_population(nn_allocator_dataset(16384, seed, vessel=nominal), grid, alloc_loss=alloc_loss_params(None, vessel=nominal),
+                                       iters=iters, seed=seed, device=dev)
+    torch.cuda.synchronize()
+    t_fit = time.perf_counter() - t0
+    mk = lambda n: ml4ca_amd.BatchedRevoltEnv(n, device=dev, terminate=False, time_limit=False, seed=seed + 77, vessel_params=nominal, current=True)
+    env = mk(64 * K)
+    env.set_dp_controller(dp_controller_defaults(nominal))
+    t0 = time.perf_counter()
+    sw = EV.nn_allocator_sweep(env, nets, directions=directions, vc=vc, reference_filter=True)
+    torch.cuda.synchronize()
+    t_sweep = time.perf_counter() - t0
+    one = mk(64)
+    one.set_dp_controller(dp_controller_defaults(nominal))
+    one.set_current(torch.full((64,), float(vc), device=dev), ((2.0 * math.pi / directions) * (torch.arange(64, device=dev) % directions).float()).contiguous())
+    t0 = time.perf_counter()
+    seq = [EV.baseline_box_test_streamed(one, reference_filter=True, chunk=50, allocator='nn', net=net) for net in nets]
+    torch.cuda.synchronize()
+    t_seq = time.perf_counter() - t0
+    same = all(torch.equal(sw['env_iae'][64 * k:64 * k + 64], r['iae']) and torch.equal(sw['env_work'][64 * k:64 * k + 64], r['work'])
+               for k, r in enumerate(seq))
+    iae, work = sw['mean_iae'].cpu().numpy(), sw['mean_work'].cpu().numpy()
+    tot = work.sum(1)
+    row = lambda k: 'net %4d  w_power %-8.4g IAE %.2f  work bow/port/star %s (total %.1f)  wrench residual Js %.4g N^2' % (
+        k, grid[k], iae[k], [round(float(x), 1) for x in work[k]], tot[k], nets[k]['wrench_ms_final'])
+    out('tunenn  %d networks (9-80-80-80-6, wrench loss, %d Adam steps each: %.1f s) x %d directions of %.1f m/s x 4 envs, 1250-step box test behind '
+        'the reference filter' % (K, iters, t_fit, directions, vc))
+    out('tunenn  w_power grid: %s' % ', '.join('%.4g' % w for w in grid))
+    out('tunenn  one flight of the population: %.2f s; the same %d box tests one network at a time: %.2f s (x %.1f); per-env scores %s'
+        % (t_sweep, K, t_seq, t_seq / t_sweep, 'equal' if same else 'DIFFER'))
+    for k in range(K):
+        out('tunenn      ' + row(k))
+    out('tunenn  front (%d of %d networks, by IAE):' % (len(sw['front']), K))
+    for k in sw['front']:
+        out('tunenn      ' + row(int(k)))
+    return {'w_power': grid, 'mean_iae': iae.tolist(), 'mean_work': work.tolist(), 'front': [int(k) for k in sw['front']],
+            'seconds': {'fit': t_fit, 'sweep': t_sweep, 'sequential': t_seq}, 'same': same}
 
 
 def warm_start(upd, env, args, out=print):
@@ -409,6 +471,9 @@ def main():
                     'flight (per-env controller table): the default baseline, the IAE / work front, the best set, and the best at no more than the actor\'s work')
     ap.add_argument('--tune-qp', type=int, default=0, metavar='K', help='with --eval: a scored sweep of K QP weight sets (w_power, w_dalpha, w_dforce) x 16 current '
                     'directions in one flight (per-env QP table): the default QP and its IAE / work front, to read beside --tune-baseline\'s')
+    ap.add_argument('--tune-nn', type=int, default=0, metavar='K', help='with --eval: K neural allocators fitted with the wrench loss, one per w_power of '
+                    'nn_w_power_grid(K) (0, then K - 1 values log-spaced from 0.01 to 1), flown as one population (one network per 64 envs) in one scored '
+                    'box test: every network\'s IAE / work and their front, to read beside --tune-qp\'s; --nn-allocator ITERS sets the Adam steps per fit')
     ap.add_argument('--nn-allocator', type=int, default=0, metavar='ITERS', help='with --eval: fit the supervised neural allocator (9-80-80-80-6, '
                     'train.fit_nn_allocator: ITERS Adam steps on 16 384 rows of deploy.nn_allocator_dataset for the preset\'s hull) and fly it behind the '
                     'baseline\'s PID on every box test, beside the pseudo-inverse and the QP')
@@ -571,6 +636,8 @@ def main():
                     tune_baseline(ac, dev, pz, 'f32', args.tune_baseline, seed=args.seed)
                 if args.tune_qp > 0:
                     tune_qp(dev, pz, args.tune_qp, seed=args.seed)
+                if args.tune_nn > 0:
+                    tune_nn(args, dev, pz, args.tune_nn, seed=args.seed)
     if world > 1:
         torch.distributed.destroy_process_group()
 

@@ -938,8 +938,10 @@ int dpenv_thrust_alloc_qp_table(const float* table, int32_t iterations, float dt
  * the rest action [0, 0, 0, 0, 1, 0, 1]; no other env is affected.  (With leak = 0 a hidden pre-activation of -inf gives 0 * -inf = NaN
  * and so the rest action.)  The law has no state and reads no hull.  ml4ca_amd.deploy.BatchedNNAllocator is its host statement.
  * dpenv_controller_label_nn (below) scans the PID + network chain over rows some other flight wrote.
- * NOT HERE: a reader for the reference's .h5 models (weights arrive as arrays), one network per env, and an evaluation on the matrix
- * cores - the network is evaluated on the VALU, one fmaf per weight and env. */
+ * NOT HERE: a reader for the reference's .h5 models (weights arrive as arrays), one network per single env (the weights reach the
+ * fmaf through scalar loads because every lane of a wave reads the same ones; a network per lane would take them out of the scalar path -
+ * one network per 64 envs is dpenv_set_nn_allocator_population below), and an evaluation on the matrix cores - the network is evaluated
+ * on the VALU, one fmaf per weight and env. */
 typedef struct dpenv_nn_allocator {
     uint32_t struct_size;
     const dpenv_mlp* net;     /* sizes[0] in {3, 9}; sizes[n_layers] == 6; n_layers 2..5; hidden widths equal, 1..96 */
@@ -979,6 +981,40 @@ int dpenv_thrust_alloc_nn(const dpenv_nn_allocator* a, const float* tau, float* 
  * dpenv_controller_label, dpenv_controller_label_qp and dpenv_controller_label_qp_ex are untouched: they label with the pseudo-inverse
  * and the QP law whatever is set here. */
 int dpenv_set_nn_allocator(dpenv_handle h, const dpenv_nn_allocator* a, dpenv_stream s);
+/* ---- a population of neural allocators: one network per envs_per_net envs (additive to ABI 6) -------------------------------------------
+ * K networks of ONE shape and ONE set of constants (leak, in_const, tau_scale, angle_scale, azimuth_mode, azimuth) in one flight: what
+ * dpenv_set_dp_controller_table is to the PID's gains and dpenv_set_qp_allocator_table to the QP's numbers.  a is a dpenv_nn_allocator
+ * whose net arrays carry a leading axis K: W[l] is [K][in][out], b[l] is [K][out] (sizes[] is one network's).  The law:
+ *     net(j) = (j / envs_per_net) % K                   (integer division; j a global env id)
+ *     env i of the handle flies network net(env_id_base + i), with the law above - the REST RULE per env included.
+ * envs_per_net is a multiple of 64 and so is env_id_base: the closed loop runs 64 envs per wave, a wave never straddles two networks, and
+ * the wave's weights stay wave-uniform (scalar loads).  The % K wraps: more envs than K * envs_per_net fly network 0 again behind K - 1,
+ * fewer leave the trailing networks unused.  While a population is set, dpenv_controller_rollout (signature and rows unchanged) allocates
+ * env i's PID wrench with its network; everything else is dpenv_set_nn_allocator's flight, so with K = 1 the rows are that call's bit for
+ * bit, and the rows of env i are those of dpenv_set_nn_allocator with network net(env_id_base + i) on an identically configured handle.
+ * The weights go into a library-owned zero-padded image of K networks (per layer [K][in][pad16(out)], then [K][pad16(out)]), released
+ * with the handle.  device_pointers = 1: ONE packing launch on s with the network index on a grid axis; an upload with the shape and K of
+ * the image in place is stream-ordered, allocation-free and graph-capturable, and a captured launch flies whatever the last such upload
+ * wrote.  An upload with ANOTHER shape or K RE-ALLOCATES the image (hipMalloc, then hipFree of the old one, which synchronises the
+ * device): not capturable, and graphs captured before are void.  device_pointers = 0 (host arrays): the call synchronises s before it
+ * returns.  If the allocation fails the call returns DPENV_ENOMEM and the handle is as it was - the old image, the stage in force.
+ * DPENV_EINVAL with the field named, before anything is launched or allocated: K < 1; envs_per_net < 64 or not a multiple of 64;
+ * K * (envs_per_net / 64) >= 2^31; the handle's env_id_base negative or not a multiple of 64; and everything dpenv_set_nn_allocator
+ * refuses (the controller off, a per-env controller table in force, a QP allocator set, a bad shape, constant or device_pointers).
+ * a = NULL returns the handle to the pseudo-inverse (K and envs_per_net are not looked at).  dpenv_set_nn_allocator replaces a population
+ * by one network, and this call replaces one network by a population; dpenv_set_dp_controller drops it; dpenv_set_qp_allocator,
+ * dpenv_set_qp_allocator_table and dpenv_set_dp_controller_table are refused while it is set, as they are under one network.
+ * dpenv_controller_label_nn under a population: with a = NULL and act wanted the call is refused (the scan takes ONE network: pass a -
+ * the precedent is dpenv_controller_label_qp under a QP table); the wrench-only scan (act = NULL) and the scan with an explicit a work as
+ * on any handle.  A population form of the scan is NOT HERE: dpenv_thrust_alloc_nn_population on the scan's tau_out is that scan's act,
+ * bit for bit. */
+int dpenv_set_nn_allocator_population(dpenv_handle h, const dpenv_nn_allocator* a, int32_t K, int32_t envs_per_net, dpenv_stream s);
+/* dpenv_thrust_alloc_nn with K stacked networks: env i of the call takes network (i / envs_per_net) % K.  a's W[l] [K][in][out] and b[l]
+ * [K][out] are DEVICE arrays (device_pointers = 1) read in place: no packing launch, no allocation, no synchronisation - graph-capturable,
+ * one kernel node.  On network k's lanes the outputs are dpenv_thrust_alloc_nn's with network k, bit for bit.  DPENV_EINVAL before
+ * anything is launched: what dpenv_thrust_alloc_nn refuses, K < 1, envs_per_net < 64 or not a multiple of 64. */
+int dpenv_thrust_alloc_nn_population(const dpenv_nn_allocator* a, int32_t K, int32_t envs_per_net, const float* tau, float* action_out,
+                                     float* raw_out, int32_t n, dpenv_stream s);
 /* The PID + network chain on rows some other flight wrote (additive to ABI 6): dpenv_controller_label's scan with the neural allocation
  * in place of the f_m / bow / stern lines, and the PID's clipped wrench per row beside it - the network's labels for the states an actor
  * visited, and the wrenches a flight asked of its allocator, which the closed loop never writes.  One launch, one lane per env; per row t
@@ -1011,7 +1047,8 @@ int dpenv_set_nn_allocator(dpenv_handle h, const dpenv_nn_allocator* a, dpenv_st
  * whatever the last upload of that shape wrote, and the constants of capture time).  The scan is serial in T per env.
  * DPENV_EINVAL with the reason in dpenv_last_error, before anything is launched or written: the controller off, a wrong struct_size,
  * T <= 0, NULL obs, act and tau_out both NULL, raw without act, an obs_dtype that is neither DPENV_F32 nor DPENV_BF16, act wanted with
- * a NULL and no network set, and whatever dpenv_thrust_alloc_nn refuses of a.  ml4ca_amd.deploy.label_rows_nn is the host statement. */
+ * a NULL and no network set, act wanted with a NULL while a POPULATION is in force (dpenv_set_nn_allocator_population: pass a), and
+ * whatever dpenv_thrust_alloc_nn refuses of a.  ml4ca_amd.deploy.label_rows_nn is the host statement. */
 typedef struct dpenv_controller_label_nn_io {
     uint32_t struct_size;    /* sizeof(dpenv_controller_label_nn_io), ABI check */
     int32_t T;

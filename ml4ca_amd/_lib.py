@@ -236,6 +236,8 @@ SYMBOLS = {
     'dpenv_nn_allocator_defaults': (C.c_int, [C.POINTER(NNAllocator)]),
     'dpenv_thrust_alloc_nn': (C.c_int, [C.POINTER(NNAllocator), _VP, _VP, _VP, _I32, _VP]),
     'dpenv_set_nn_allocator': (C.c_int, [_VP, C.POINTER(NNAllocator), _VP]),
+    'dpenv_set_nn_allocator_population': (C.c_int, [_VP, C.POINTER(NNAllocator), _I32, _I32, _VP]),
+    'dpenv_thrust_alloc_nn_population': (C.c_int, [C.POINTER(NNAllocator), _I32, _I32, _VP, _VP, _VP, _I32, _VP]),
     'dpenv_controller_label_nn': (C.c_int, [_VP, C.POINTER(ControllerLabelNnIO), _VP]),
     'dpenv_train_param_count': (C.c_int64, [C.POINTER(TrainShape)]),
     'dpenv_train_workspace_bytes': (C.c_int, [C.POINTER(TrainShape), _I32, C.POINTER(C.c_int64)]),

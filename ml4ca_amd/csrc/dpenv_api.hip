@@ -95,6 +95,11 @@ struct dpenv_s {
     int32_t qp_tab_iters = 0;
     NnRollout nn = {};      // its constants and the layers' addresses inside nn_img
     float* nn_img = nullptr;     // the zero-padded weight image (NN_IMAGE_FLOATS floats: the largest shape), allocated by the first dpenv_set_nn_allocator
+    // dpenv_set_nn_allocator_population: stage == ALLOC_NN with nn_pop.K >= 1 flies network ((env_id_base + i) / envs_per_net) % K of
+    // nn_pop_img on env i (K == 0: the one network of `nn`).  Every rule about ALLOC_NN holds for both.
+    NnPop nn_pop = {};           // the constants, network 0's layer addresses inside nn_pop_img, K, waves per network and the reduced wave base
+    float* nn_pop_img = nullptr; // the zero-padded image of K networks: re-allocated when the shape or K changes
+    int32_t nn_pop_shape[4] = {0, 0, 0, 0};   // n_layers, in_dim, H, K of the image in place
     int device = 0;
     std::string err;
 
@@ -113,6 +118,7 @@ struct dpenv_s {
         if (qp.state) (void)hipFree(qp.state);
         if (qp_tab) (void)hipFree(qp_tab);
         if (nn_img) (void)hipFree(nn_img);
+        if (nn_pop_img) (void)hipFree(nn_pop_img);
         for (int k = 0; k < 2; ++k) if (pol_read[k]) (void)hipEventDestroy(pol_read[k]);
         if (loss_ev) (void)hipEventDestroy(loss_ev);
         if (loss_host) (void)hipHostFree(loss_host);
@@ -1150,7 +1156,7 @@ static bool control_config_ok(dpenv_handle h)
 }
 
 // back to the pseudo-inverse: a QP allocator, scalar or per-env (the held scalar numbers included), and a neural allocator are dropped
-static void allocator_off(dpenv_handle h) { h->stage = ALLOC_PINV; h->qp_scalar = false; }
+static void allocator_off(dpenv_handle h) { h->stage = ALLOC_PINV; h->qp_scalar = false; h->nn_pop.K = 0; }
 
 extern "C" int dpenv_set_dp_controller(dpenv_handle h, const dpenv_dp_controller* c, dpenv_stream s)
 {
@@ -1270,7 +1276,9 @@ extern "C" int dpenv_controller_rollout(dpenv_handle h, const dpenv_controller_r
     if (const char* no = stage_refusal(h, h->stage)) return fail(h, DPENV_EINVAL, "dpenv_controller_rollout: %s", no);
     const FilterArgs* fp = h->reff_on ? &fa : nullptr;
     hipError_t e;
-    if (h->stage == ALLOC_NN) {                            // the neural allocation behind the PID lines: its own kernels (dpenv_control_nn.hip)
+    if (h->stage == ALLOC_NN && h->nn_pop.K > 0) {         // a population: the wave's network out of K (dpenv_control_nn_pop.hip)
+        e = dev::launch_controller_rollout_nn_pop(&a, &ca, fp, &h->nn_pop, ves, (hipStream_t)s);
+    } else if (h->stage == ALLOC_NN) {                     // the neural allocation behind the PID lines: its own kernels (dpenv_control_nn.hip)
         e = dev::launch_controller_rollout_nn(&a, &ca, fp, &h->nn, ves, (hipStream_t)s);
     } else {
         QpRollout qr = h->qp;
@@ -1388,6 +1396,85 @@ extern "C" int dpenv_set_nn_allocator(dpenv_handle h, const dpenv_nn_allocator* 
     }
     for (int l = 0; l < g.n_layers; ++l) { g.W[l] = pk.dW[l]; g.b[l] = pk.db[l]; }
     h->nn.a = g;
+    h->stage = ALLOC_NN;
+    h->nn_pop.K = 0;                                       // one network: a population in force is replaced
+    return DPENV_OK;
+}
+
+// K networks of one shape, one per envs_per_net envs (dpenv.h).  The image: per layer W [K][in][nn_pad(out)] then b [K][nn_pad(out)], so
+// that network k of a layer lies k strides behind network 0 and the kernel needs one product per layer.
+extern "C" int dpenv_set_nn_allocator_population(dpenv_handle h, const dpenv_nn_allocator* a, int32_t K, int32_t envs_per_net, dpenv_stream s)
+{
+    if (!h) return DPENV_EINVAL;
+    if (!a) {
+        if (h->stage == ALLOC_NN) allocator_off(h);        // (a QP allocator stays)
+        return DPENV_OK;
+    }
+    const char* who = "dpenv_set_nn_allocator_population";
+    if (!h->ctrl_on) return fail(h, DPENV_EINVAL, "%s: the DP controller is off (dpenv_set_dp_controller first)", who);
+    NnArgs g;
+    if (const char* why = nn_check(a, g)) return fail(h, DPENV_EINVAL, "%s", why);
+    if (a->device_pointers != 0 && a->device_pointers != 1) return fail(h, DPENV_EINVAL, "NN allocator: device_pointers must be 0 or 1");
+    if (const char* why = nn_pop_check(K, envs_per_net)) return fail(h, DPENV_EINVAL, "%s: %s", who, why);
+    const int64_t base = h->args.env_id_base;
+    if (base < 0 || base % RBLOCK != 0)
+        return fail(h, DPENV_EINVAL, "%s: env_id_base must be >= 0 and a multiple of 64 (a wave must not straddle two networks)", who);
+    if (!control_config_ok(h)) return fail(h, DPENV_EINVAL, "%s: " CONTROL_SET_MSG, who);
+    if (const char* no = stage_refusal(h, ALLOC_NN)) return fail(h, DPENV_EINVAL, "%s: %s", who, no);
+    DeviceGuard dev_guard(h->device);
+    size_t per_net = 0, w_str[NN_MAX_LAYERS], b_str[NN_MAX_LAYERS];
+    for (int l = 0; l < g.n_layers; ++l) {
+        const size_t in = l == 0 ? g.in_dim : g.H, ld = (size_t)nn_pad(l == g.n_layers - 1 ? 6 : g.H);
+        w_str[l] = in * ld; b_str[l] = ld;
+        per_net += w_str[l] + b_str[l];
+    }
+    const size_t floats = per_net * (size_t)K;
+    const int32_t shape[4] = {g.n_layers, g.in_dim, g.H, K};
+    if (!h->nn_pop_img || std::memcmp(shape, h->nn_pop_shape, sizeof shape) != 0) {   // another shape or K: a new image; the old one goes last
+        void* p = nullptr;
+        if (hipMalloc(&p, sizeof(float) * floats) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(h, DPENV_ENOMEM, "hipMalloc of the NN allocator population image failed (%zu bytes)", sizeof(float) * floats);
+        }
+        if (h->nn_pop_img) {
+            if (h->stage == ALLOC_NN && h->nn_pop.K > 0) allocator_off(h);     // (nothing may fly addresses of the image that goes)
+            (void)hipFree(h->nn_pop_img);
+        }
+        h->nn_pop_img = (float*)p;
+        std::memcpy(h->nn_pop_shape, shape, sizeof shape);
+    }
+    NnPopPack pk = {};
+    pk.K = K;
+    pk.p.n_layers = g.n_layers; pk.p.in_dim = g.in_dim; pk.p.H = g.H;
+    size_t off = 0;
+    for (int l = 0; l < g.n_layers; ++l) {
+        pk.p.W[l] = g.W[l]; pk.p.b[l] = g.b[l];
+        pk.p.dW[l] = h->nn_pop_img + off; off += w_str[l] * (size_t)K;
+        pk.p.db[l] = h->nn_pop_img + off; off += b_str[l] * (size_t)K;
+    }
+    if (a->device_pointers) {
+        HIP_TRY(h, dev::launch_nn_pack_pop(&pk, (hipStream_t)s));
+    } else {                                               // host arrays: the image is formed here and copied; the call waits for the copy
+        std::vector<float> img(floats, 0.0f);
+        for (int l = 0; l < g.n_layers; ++l) {
+            const size_t in = l == 0 ? g.in_dim : g.H, out = l == g.n_layers - 1 ? 6 : g.H, ld = (size_t)nn_pad((int)out);
+            float* dW = img.data() + (pk.p.dW[l] - h->nn_pop_img);
+            float* db = img.data() + (pk.p.db[l] - h->nn_pop_img);
+            for (size_t q = 0; q < (size_t)K; ++q) {
+                for (size_t k = 0; k < in; ++k)
+                    for (size_t j = 0; j < out; ++j) dW[q * in * ld + k * ld + j] = g.W[l][q * in * out + k * out + j];
+                for (size_t j = 0; j < out; ++j) db[q * ld + j] = g.b[l][q * out + j];
+            }
+        }
+        HIP_TRY(h, hipMemcpyAsync(h->nn_pop_img, img.data(), sizeof(float) * floats, hipMemcpyHostToDevice, (hipStream_t)s));
+        HIP_TRY(h, hipStreamSynchronize((hipStream_t)s));
+    }
+    for (int l = 0; l < g.n_layers; ++l) { g.W[l] = pk.p.dW[l]; g.b[l] = pk.p.db[l]; }
+    const int64_t wpn = envs_per_net / RBLOCK;
+    h->nn_pop.a = g;
+    h->nn_pop.waves_per_net = (int32_t)wpn;
+    h->nn_pop.wave_base = (uint32_t)((base / RBLOCK) % (wpn * (int64_t)K));
+    h->nn_pop.K = K;
     h->stage = ALLOC_NN;
     return DPENV_OK;
 }
@@ -1530,6 +1617,8 @@ extern "C" int dpenv_controller_label_nn(dpenv_handle h, const dpenv_controller_
     if (io->act) {                                         // (the wrench-only scan does not look at a)
         if (own) {
             if (const char* why = nn_check_in_place(io->a, g)) return fail(h, DPENV_EINVAL, "%s", why);
+        } else if (h->stage == ALLOC_NN && h->nn_pop.K > 0) {
+            return fail(h, DPENV_EINVAL, "dpenv_controller_label_nn: a population of networks is in force and the scan takes one network (pass a)");
         } else if (h->stage == ALLOC_NN) {
             g = h->nn.a;
         } else {

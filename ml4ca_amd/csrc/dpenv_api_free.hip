@@ -452,6 +452,28 @@ extern "C" int dpenv_thrust_alloc_nn(const dpenv_nn_allocator* a, const float* t
     return DPENV_OK;
 }
 
+const char* host::nn_pop_check(int32_t K, int32_t envs_per_net)
+{
+    if (K < 1) return "K must be >= 1";
+    if (envs_per_net < 64 || envs_per_net % 64 != 0) return "envs_per_net must be a multiple of 64, >= 64 (a wave flies one network)";
+    if ((int64_t)K * (envs_per_net / 64) >= ((int64_t)1 << 31)) return "K * (envs_per_net / 64) must be below 2^31";
+    return nullptr;
+}
+
+extern "C" int dpenv_thrust_alloc_nn_population(const dpenv_nn_allocator* a, int32_t K, int32_t envs_per_net, const float* tau,
+                                                float* action_out, float* raw_out, int32_t n, dpenv_stream s)
+{
+    if (!a) return fail(nullptr, DPENV_EINVAL, "dpenv_thrust_alloc_nn_population: a is NULL");
+    if (!tau || !action_out) return fail(nullptr, DPENV_EINVAL, "dpenv_thrust_alloc_nn_population: tau and action_out must not be NULL");
+    if (n <= 0) return fail(nullptr, DPENV_EINVAL, "dpenv_thrust_alloc_nn_population: n must be > 0");
+    NnPop p = {};
+    if (const char* why = nn_check_in_place(a, p.a)) return fail(nullptr, DPENV_EINVAL, "%s", why);
+    if (const char* why = nn_pop_check(K, envs_per_net)) return fail(nullptr, DPENV_EINVAL, "dpenv_thrust_alloc_nn_population: %s", why);
+    p.K = K; p.waves_per_net = envs_per_net / 64; p.wave_base = 0;
+    HIP_TRY(nullptr, dev::launch_nn_alloc_pop(&p, tau, action_out, raw_out, n, (hipStream_t)s));
+    return DPENV_OK;
+}
+
 extern "C" int dpenv_thrust_map(const float* params, const float* n_pct, const float* alpha, float* tau_out, int32_t n,
                                 dpenv_stream s)
 {

@@ -306,6 +306,21 @@ struct NnPack {
     float* db[NN_MAX_LAYERS];
     int32_t n_layers, in_dim, H;
 };
+// K networks of one shape, one per run of waves (dpenv_set_nn_allocator_population / dpenv_thrust_alloc_nn_population;
+// dpenv_control_nn_pop.hip): a.W[l] is [K][in_l][ld_l] and a.b[l] [K][ld_l] - network 0's addresses, the others behind it layer by layer -
+// and wave w of the launch (workgroup w: 64 envs) takes network ((wave_base + w) / waves_per_net) % K.  The index is a function of
+// blockIdx alone, so the wave's addresses stay wave-uniform and the weights keep arriving by scalar loads.
+struct NnPop {
+    NnArgs a;
+    int32_t K, waves_per_net;       // K >= 1; envs_per_net / 64 >= 1
+    uint32_t wave_base;             // (env_id_base / 64) mod (K waves_per_net), which the host keeps below 2^31; 0 for the handle-free map
+};
+// the packing of K networks (dpenv_set_nn_allocator_population with device_pointers = 1): network k of src layer l at W[l] + k in out
+// and b[l] + k out, of dst at dW[l] + k in ld and db[l] + k ld
+struct NnPopPack {
+    NnPack p;
+    int32_t K;
+};
 
 // device-side weight packing (pack_policy_kernel): one dense network, DEVICE pointers
 struct PackNet {
@@ -589,6 +604,11 @@ hipError_t launch_nn_alloc(const NnArgs* na, const float* tau, float* action, fl
 hipError_t launch_controller_rollout_nn(const StepArgs* a, const ControlArgs* ca, const FilterArgs* fa, const NnRollout* nr, int ves, hipStream_t s);
 // the caller's DEVICE arrays -> the zero-padded image, one launch
 hipError_t launch_nn_pack(const NnPack* np, hipStream_t s);
+// dpenv_control_nn_pop.hip: launch_nn_alloc, launch_controller_rollout_nn and launch_nn_pack with K networks of one shape, one per
+// waves_per_net waves (NnPop)
+hipError_t launch_nn_alloc_pop(const NnPop* np, const float* tau, float* action, float* raw, int n, hipStream_t s);
+hipError_t launch_controller_rollout_nn_pop(const StepArgs* a, const ControlArgs* ca, const FilterArgs* fa, const NnPop* np, int ves, hipStream_t s);
+hipError_t launch_nn_pack_pop(const NnPopPack* pp, hipStream_t s);
 // dpenv_label_nn.hip: launch_controller_label's scan with the neural allocation in place of the pseudo-inverse and, if la->tau, the PID's
 // wrench per row; na: NULL exactly when la->act is NULL; padded: na's W and b are the zero-padded image, else arrays read in place
 hipError_t launch_controller_label_nn(const ControlArgs* ca, const NnArgs* na, const LabelNnArgs* la, const float4* tab, int obs_bf16, int padded,

@@ -53,6 +53,8 @@ const char* qp_check(const dpenv_qp_allocator* q, float dt, QpArgs& g);
 const char* nn_check(const dpenv_nn_allocator* a, NnArgs& g);
 // nn_check, then device_pointers == 1: what the calls that read the weights in place demand
 const char* nn_check_in_place(const dpenv_nn_allocator* a, NnArgs& g);
+// what the population calls refuse of K and envs_per_net, or NULL
+const char* nn_pop_check(int32_t K, int32_t envs_per_net);
 
 }  // namespace host
 }  // namespace dpenv

@@ -1,6 +1,7 @@
 // dpenv_nn_law.h - the neural thrust allocation's law (include/dpenv.h states it operation by operation): a small dense network from the
 // scaled wrench to the thruster command, evaluated per env by the env's own lane.  The ONE text of the law on the device: included inside
-// namespace dpenv after dpenv_env_dev.h by dpenv_control_nn.hip (the handle-free map and the closed-loop kernels), by dpenv_label_nn.hip
+// namespace dpenv after dpenv_env_dev.h by dpenv_control_nn.hip (the handle-free map and the closed-loop kernels), by
+// dpenv_control_nn_pop.hip (the same with a population of networks: it hands nn_allocate the wave's own NnArgs), by dpenv_label_nn.hip
 // (the labelling scan) and by dpenv_control.hip (which only needs the names the shared closed-loop body mentions in its NN branch: nothing
 // of this header is instantiated there).
 // Everything is plain f32 in the stated order: every product-sum of a layer is an explicit fmaf, the build has -ffp-contract=off.

@@ -1130,6 +1130,92 @@ class BatchedNNAllocator(object):
         return (act, p) if raw else act
 
 
+# ---- a population of neural allocators: K networks of one shape, one per envs_per_net envs (dpenv_set_nn_allocator_population) ----------
+def _is_stacked(nets):
+    return isinstance(nets, dict) and len(nets['W']) > 0 and len(nets['W'][0].shape) == 3
+
+
+def nn_population_stack(nets):
+    """K nets of ONE shape -> the stacked dict the population calls take: W[l] [K, in, out], b[l] [K, out], float32.  nets: a list of net
+    dicts (nn_net_arrays' forms; train.fit_nn_allocator_population returns one), or a dict that is already stacked (checked and
+    returned).  If every array of every net is a torch tensor the stack is a torch tensor on their device (so that
+    env.set_nn_allocator_population and policy.thrust_alloc_nn_population read it in place), else float32 NumPy.  A 'leak' the nets
+    carry is kept if they agree on it.  ValueError if the shapes differ, the leaks differ, or the list is empty."""
+    if isinstance(nets, dict):
+        if not _is_stacked(nets):
+            raise ValueError('nn_population_stack: a dict is the stacked form, W[l] [K, in, out] and b[l] [K, out] (for one net pass [net])')
+        K = int(nets['W'][0].shape[0])
+        if K < 1 or any(int(a.shape[0]) != K for a in list(nets['W']) + list(nets['b'])):
+            raise ValueError('nn_population_stack: every W[l] and b[l] has the same leading K >= 1')
+        nn_net_sizes([w[0] for w in nets['W']], [b[0] for b in nets['b']])
+        return nets
+    nets = list(nets)
+    if not nets:
+        raise ValueError('nn_population_stack: no nets')
+    pairs = [((n['W'], n['b']) if isinstance(n, dict) else n) for n in nets]
+    sizes = [nn_net_sizes(Ws, bs) for Ws, bs in pairs]
+    if any(s != sizes[0] for s in sizes):
+        raise ValueError('nn_population_stack: the nets of a population have one shape, got %s' % sorted(set(map(tuple, sizes))))
+    leaks = set(float(n['leak']) for n in nets if isinstance(n, dict) and 'leak' in n)
+    if len(leaks) > 1 or (leaks and not all(isinstance(n, dict) and 'leak' in n for n in nets)):
+        raise ValueError('nn_population_stack: the nets of a population share one leak, got %s' % sorted(leaks))
+    L = len(sizes[0]) - 1
+    if all(hasattr(a, 'detach') for Ws, bs in pairs for a in list(Ws) + list(bs)):
+        import torch
+        out = dict(W=[torch.stack([p[0][l].detach().float() for p in pairs]).contiguous() for l in range(L)],
+                   b=[torch.stack([p[1][l].detach().float().reshape(-1) for p in pairs]).contiguous() for l in range(L)])
+    else:
+        arrs = [nn_net_arrays(p) for p in pairs]
+        out = dict(W=[np.stack([a[0][l] for a in arrs]) for l in range(L)], b=[np.stack([a[1][l] for a in arrs]) for l in range(L)])
+    if leaks:
+        out['leak'] = leaks.pop()
+    return out
+
+
+def nn_population_net(stacked, k):
+    """Network k of a stacked dict (nn_population_stack), as views: dict(W, b[, leak])."""
+    out = dict(W=[w[k] for w in stacked['W']], b=[b[k] for b in stacked['b']])
+    if 'leak' in stacked:
+        out['leak'] = stacked['leak']
+    return out
+
+
+def nn_population_index(n, K, envs_per_net, env_id_base=0):
+    """Which network each env flies (the law of dpenv_set_nn_allocator_population): int64 [n], entry i = ((env_id_base + i) //
+    envs_per_net) % K.  K >= 1; envs_per_net and env_id_base are multiples of 64 (a wave flies one network), env_id_base >= 0."""
+    n, K, E, base = int(n), int(K), int(envs_per_net), int(env_id_base)
+    if n < 1 or K < 1:
+        raise ValueError('nn_population_index: n and K are >= 1')
+    if E < 64 or E % 64:
+        raise ValueError('nn_population_index: envs_per_net is a multiple of 64, >= 64 (got %d)' % E)
+    if base < 0 or base % 64:
+        raise ValueError('nn_population_index: env_id_base is >= 0 and a multiple of 64 (got %d)' % base)
+    return ((base + np.arange(n, dtype=np.int64)) // E) % K
+
+
+class BatchedNNAllocatorPopulation(object):
+    """The population's host statement: env i is allocated by BatchedNNAllocator with network nn_population_index(...)[i] - per env
+    exactly that class's float32 / float64 statement of the env's network, nothing else.  nets: a list of nets or the stacked dict;
+    params, dtype: BatchedNNAllocator's, shared by the K networks.  allocate(tau [n, 3]) -> action [n, 7] (and p [n, 6] with raw=True)."""
+
+    def __init__(self, n, nets, envs_per_net=64, env_id_base=0, dtype=None, params=None):
+        st = nn_population_stack(nets)
+        self.n, self.K = int(n), int(st['W'][0].shape[0])
+        self.index = nn_population_index(n, self.K, envs_per_net, env_id_base)
+        self.dtype = np.dtype(np.float32 if dtype is None else dtype)
+        self.rows = {int(k): np.flatnonzero(self.index == k) for k in np.unique(self.index)}
+        self.allocators = {k: BatchedNNAllocator(len(r), nn_population_net(st, k), dtype=dtype, params=params) for k, r in self.rows.items()}
+
+    def allocate(self, tau, raw=False):
+        tau = np.asarray(tau, self.dtype)
+        if tau.shape != (self.n, 3):
+            raise ValueError('BatchedNNAllocatorPopulation: tau is [n, 3]')
+        act, p = np.empty((self.n, 7), self.dtype), np.empty((self.n, 6), self.dtype)
+        for k, r in self.rows.items():
+            act[r], p[r] = self.allocators[k].allocate(tau[r], raw=True)
+        return (act, p) if raw else act
+
+
 def label_rows_nn(params_or_table, net, obs, done=None, z=None, dt=0.2, dtype=None, nn_params=None):
     """The PID + network chain's actions on a block of observation rows some other flight wrote - the host statement of
     dpenv_controller_label_nn (policy.controller_label_nn), NumPy on the CPU.  obs, done, z, params_or_table and dt as label_rows takes

@@ -514,6 +514,28 @@ class BatchedRevoltEnv(object):
         del keep
         self.nn_allocator = dict(p, net=net)
 
+    def set_nn_allocator_population(self, nets=None, envs_per_net=64, off=False, **constants):
+        """K neural allocators of one shape in one flight (dpenv_set_nn_allocator_population): env i flies network
+        ((env_id_base + i) // envs_per_net) % K behind the baseline's PID, everything else as set_nn_allocator.  nets: a list of K net
+        dicts, or the stacked dict of deploy.nn_population_stack (W[l] [K, in, out], b[l] [K, out]); stacked tensors on the env's device
+        are handed over as device pointers - one packing launch, capturable once an image of that shape and K exists - anything else
+        goes through a host copy.  envs_per_net: a multiple of 64, as is the env's env_id_base (a wave flies one network).  constants:
+        shared by the K networks.  off=True (or nets=None) returns to the pseudo-inverse; set_nn_allocator replaces the population by
+        one network.  While set, self.nn_allocator carries 'net' (the stacked dict), 'K' and 'envs_per_net'."""
+        if off or nets is None:
+            _lib.check(self.lib.dpenv_set_nn_allocator_population(self._h, None, 0, 0, self._stream()), self._h)
+            self.nn_allocator = None
+            return
+        from .deploy import nn_allocator_params, nn_population_stack
+        from .policy import nn_population_struct
+        st = nn_population_stack(nets)
+        p = nn_allocator_params(st, **constants)
+        a, K, keep = nn_population_struct(st, p, self.device)
+        with _torch().cuda.device(self.device):
+            _lib.check(self.lib.dpenv_set_nn_allocator_population(self._h, C.byref(a), K, int(envs_per_net), self._stream()), self._h)
+        del keep
+        self.nn_allocator = dict(p, net=st, K=K, envs_per_net=int(envs_per_net))
+
     def set_qp_allocator(self, params=None, off=False):
         """The rate-limited QP thrust allocation as the allocation stage of policy.controller_rollout (dpenv_set_qp_allocator; include/dpenv.h
         has the law): the baseline's PID forms the wrench, the QP allocates it in place of the pseudo-inverse.  params is the dict of

@@ -546,6 +546,74 @@ def nn_allocator_struct(net, params, device):
     return a, (m, hW, hb, Ws, bs)
 
 
+def nn_population_struct(nets, params, device):
+    """(dpenv_nn_allocator, K, keep) for a population - a list of nets or the stacked dict of deploy.nn_population_stack - and the dict
+    of deploy.nn_allocator_defaults: nn_allocator_struct with W[l] [K, in, out] and b[l] [K, out] behind the pointers (sizes are one
+    network's).  Stacked contiguous float32 tensors on `device` are handed over in place (device_pointers = 1), anything else as host
+    arrays (device_pointers = 0)."""
+    torch = _torch()
+    from .deploy import nn_population_stack
+    st = nn_population_stack(nets)
+    K = int(st['W'][0].shape[0])
+    one = dict(W=[w[0] for w in st['W']], b=[b[0] for b in st['b']])
+    a, keep = nn_allocator_struct(one, params, device)            # the shape, the constants (and network 0's addresses, replaced below)
+    on_dev = all(isinstance(t, torch.Tensor) and t.is_cuda and t.device == device and t.dtype == torch.float32 and t.is_contiguous()
+                 for t in list(st['W']) + list(st['b']))
+    if on_dev:
+        Ws, bs = list(st['W']), list(st['b'])
+        ptr = lambda t: t.data_ptr()
+    else:
+        cv = lambda t: np.ascontiguousarray(t.detach().cpu().numpy() if hasattr(t, 'detach') else np.asarray(t), dtype=np.float32)
+        Ws, bs = [cv(w) for w in st['W']], [cv(b) for b in st['b']]
+        ptr = lambda t: t.ctypes.data
+    m = keep[0]
+    for l in range(len(Ws)):
+        m.W[l], m.b[l] = ptr(Ws[l]), ptr(bs[l])
+    a.device_pointers = 1 if on_dev else 0
+    return a, K, (keep, Ws, bs, st)
+
+
+def nn_population_to(nets, device):
+    """The population's stacked W and b as contiguous float32 tensors on `device` (tensors already there are kept as they are)."""
+    from .deploy import nn_population_stack
+    st = nn_population_stack(nets)
+    out = nn_net_to(dict(W=st['W'], b=st['b']), device)
+    out['b'] = [b.reshape(w.shape[0], -1) for w, b in zip(out['W'], out['b'])]
+    if 'leak' in st:
+        out['leak'] = st['leak']
+    return out
+
+
+def thrust_alloc_nn_population(tau, nets, envs_per_net=64, out=None, raw=False, **constants):
+    """thrust_alloc_nn with K networks of one shape (dpenv_thrust_alloc_nn_population): env i of tau [3, n] takes network
+    (i // envs_per_net) % K.  nets: a list of nets or the stacked dict of deploy.nn_population_stack - stacked tensors on tau's device
+    are read in place, anything else is stacked and copied there first; envs_per_net: a multiple of 64; the rest is thrust_alloc_nn's.
+    On network k's envs the outputs are thrust_alloc_nn's with network k, bit for bit; deploy.BatchedNNAllocatorPopulation is the host
+    statement."""
+    torch = _torch()
+    from .deploy import nn_allocator_params
+    f32 = torch.float32
+    if not isinstance(tau, torch.Tensor) or tau.dim() != 2 or tau.shape[0] != 3 or tau.dtype != f32 or not tau.is_cuda or not tau.is_contiguous():
+        raise ValueError('thrust_alloc_nn_population: tau is a contiguous float32 device tensor [3, n]')
+    n = int(tau.shape[1])
+    dnet = nn_population_to(nets, tau.device)
+    a, K, keep = nn_population_struct(dnet, nn_allocator_params(dnet, **constants), tau.device)
+    act, p = (out if raw else (out, None)) if out is not None else (None, None)
+    if act is None:
+        act = torch.empty((n, 7), dtype=f32, device=tau.device)
+    if raw and p is None:
+        p = torch.empty((n, 6), dtype=f32, device=tau.device)
+    for t, shape, what in ((act, (n, 7), 'action'), (p, (n, 6), 'raw')):
+        if t is not None and (tuple(t.shape) != shape or t.dtype != f32 or t.device != tau.device or not t.is_contiguous()):
+            raise ValueError('thrust_alloc_nn_population: the %s buffer is a contiguous float32 tensor %s on tau\'s device' % (what, list(shape)))
+    s = C.c_void_p(torch.cuda.current_stream(tau.device).cuda_stream)
+    with torch.cuda.device(tau.device):
+        _lib.check(_lib.load().dpenv_thrust_alloc_nn_population(C.byref(a), K, int(envs_per_net), C.c_void_p(tau.data_ptr()),
+                                                                C.c_void_p(act.data_ptr()), C.c_void_p(p.data_ptr()) if p is not None else None, n, s))
+    del keep
+    return (act, p) if raw else act
+
+
 def nn_net_to(net, device):
     """The net's W and b as contiguous float32 tensors on `device` (tensors already there are kept as they are): dict(W, b[, leak])."""
     torch = _torch()

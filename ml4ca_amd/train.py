@@ -534,6 +534,25 @@ def fit_nn_allocator(dataset, in_dim=9, iters=200, lr=1e-3, minibatch=256, seed=
                 J_initial=first(wr0, 0), J_final=first(wr1, 0), wrench_ms_initial=first(wr0, 1), wrench_ms_final=first(wr1, 1))
 
 
+def fit_nn_allocator_population(dataset, w_powers, alloc_loss=None, **fit):
+    """K wrench-loss fits of one shape, one per power weight: for every w in w_powers, fit_nn_allocator(dataset, loss='wrench',
+    alloc_loss=dict(alloc_loss or {}, w_power=w), **fit) - a loop over the existing fused gradient, each fit from the same
+    initialisation and minibatches (fit: in_dim, iters, lr, minibatch, seed, leak, device, init).  Returns the list of the K fits'
+    dicts, each with its 'w_power': what deploy.nn_population_stack, env.set_nn_allocator_population and evaluate.nn_allocator_sweep
+    take."""
+    ws = [float(w) for w in w_powers]
+    if not ws:
+        raise ValueError('fit_nn_allocator_population: w_powers is empty')
+    if 'loss' in fit:
+        raise ValueError("fit_nn_allocator_population: the fits are loss='wrench'")
+    nets = []
+    for w in ws:
+        net = fit_nn_allocator(dataset, loss='wrench', alloc_loss=dict(alloc_loss or {}, w_power=w), **fit)
+        net['w_power'] = w
+        nets.append(net)
+    return nets
+
+
 def nn_wrench_rows(tau, in_dim=9, params=None):
     """Wrenches -> the rows fit_nn_allocator(loss='wrench') takes, on the device: tau, a float32 device tensor [R, 3] (N, N, Nm; a
     policy.controller_label_nn(tau=True) block viewed as rows), -> dict(x [R, in_dim], tau [R, 3]).  x[:, -3:] = tau * tau_scale, one

@@ -13,7 +13,12 @@ batches (tools/time_qp_alloc.py's scheme).  Workload: 65 536 envs; launches of T
   G  train.fit_nn_allocator on 4 096 dataset rows, per count of --fit Adam steps: the loss before and after, and the fitted network on the calm
      250 s box test (64 envs) beside the pseudo-inverse and the QP.
 
-Usage: python tools/time_nn_alloc.py [--out profiles/nn_alloc_timing.txt] [--envs 65536] [--fit 200 5000]"""
+  --population K [K ...]: instead of the legs above, the closed loop with a POPULATION of K networks (dpenv_set_nn_allocator_population,
+     one network per 64 envs, distinct random weights) per K and shape beside the one-network launch of the same build, the handle-free
+     map with K stacked networks, and the K-network packing launch (env.set_nn_allocator_population from device tensors); written to
+     profiles/nn_population_timing.txt unless --out says otherwise.
+
+Usage: python tools/time_nn_alloc.py [--out profiles/nn_alloc_timing.txt] [--envs 65536] [--fit 200 5000] [--population 1 16 256 1024]"""
 import argparse
 import os
 import sys
@@ -26,7 +31,7 @@ import torch
 import ml4ca_amd
 from ml4ca_amd import evaluate
 from ml4ca_amd.deploy import nn_allocator_dataset, qp_allocator_defaults
-from ml4ca_amd.policy import controller_rollout, nn_net_to, thrust_alloc_nn
+from ml4ca_amd.policy import controller_rollout, nn_net_to, nn_population_to, thrust_alloc_nn, thrust_alloc_nn_population
 from ml4ca_amd.train import fit_nn_allocator
 from tools.time_qp_alloc import spacing_us
 
@@ -39,13 +44,63 @@ def glorot(sizes, leak, dev, seed=0):
     return nn_net_to(dict(W=W, b=[np.zeros(b, np.float32) for b in sizes[1:]], leak=leak), dev)
 
 
+def population_leg(args, dev, out):
+    n, T = args.envs, 50
+    rng = np.random.default_rng(0)
+    tau = torch.from_numpy((rng.normal(0.0, 1.0, (3, n)) * np.array([[20.0], [10.0], [15.0]])).astype(np.float32)).to(dev)
+    act = torch.empty((n, 7), device=dev)
+    out('%d envs (%d waves), envs_per_net = 64, T = %d, launch spacing over 20 back-to-back launches, medians of 7 batches, arms alternating:'
+        % (n, (n + 63) // 64, T))
+    for sizes, leak in SHAPES:
+        name = '-'.join(map(str, sizes))
+        one = glorot(sizes, leak, dev)
+        pops = [nn_population_to([glorot(sizes, leak, 'cpu', seed=k) for k in range(K)], dev) for K in args.population]
+        fly, envs = None, []
+        for st in [None] + pops:
+            env = ml4ca_amd.BatchedRevoltEnv(n, device=dev, auto_reset=True, seed=5)
+            env.set_dp_controller()
+            if st is None:
+                env.set_nn_allocator(one)
+            else:
+                env.set_nn_allocator_population(st)
+            env.reset()
+            if fly is None:
+                fly = {k: torch.empty_like(v) for k, v in controller_rollout(env, T).items()}
+            envs.append(env)
+        arms = [lambda env=env: controller_rollout(env, T, out=fly) for env in envs]
+        arms.append(lambda: thrust_alloc_nn(tau, one, out=act))
+        arms += [lambda st=st: thrust_alloc_nn_population(tau, st, out=act) for st in pops]
+        arms.append(lambda: envs[0].set_nn_allocator(one))
+        arms += [lambda env=env, st=st: env.set_nn_allocator_population(st) for env, st in zip(envs[1:], pops)]
+        us = spacing_us(arms)
+        m = len(pops)
+        floats = sum(a * b + b for a, b in zip(sizes[:-1], sizes[1:]))
+        out('  network %s, leak %.1f (%d weights = %.1f KB per network)' % (name, leak, floats, floats * 4 / 1024.0))
+        out('    controller_rollout, one network                 %9.1f us per launch = %.2f us per step' % (us[0], us[0] / T))
+        for K, u in zip(args.population, us[1:1 + m]):
+            out('    controller_rollout, population K = %-5d        %9.1f us per launch = %.2f us per step  x %.3f of one network'
+                % (K, u, u / T, u / us[0]))
+        out('    thrust_alloc_nn, one network                    %9.1f us per call' % us[1 + m])
+        for K, u in zip(args.population, us[2 + m:2 + 2 * m]):
+            out('    thrust_alloc_nn_population, K = %-5d           %9.1f us per call  x %.3f of one network' % (K, u, u / us[1 + m]))
+        out('    set_nn_allocator from device tensors            %9.1f us per call (one packing launch)' % us[2 + 2 * m])
+        for K, u in zip(args.population, us[3 + 2 * m:]):
+            out('    set_nn_allocator_population, K = %-5d          %9.1f us per call (one packing launch, %.1f MB image)'
+                % (K, u, K * sum(a * ((b + 15) // 16 * 16) + (b + 15) // 16 * 16 for a, b in zip(sizes[:-1], sizes[1:])) * 4 / 1e6))
+        del envs, arms, pops
+        torch.cuda.empty_cache()
+
+
 def main():
     here = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     ap = argparse.ArgumentParser()
-    ap.add_argument('--out', default=os.path.join(here, 'profiles', 'nn_alloc_timing.txt'))
+    ap.add_argument('--out', default=None)
+    ap.add_argument('--population', type=int, nargs='+', default=None, help='time populations of K networks instead of the legs A..G')
     ap.add_argument('--envs', type=int, default=65536)
     ap.add_argument('--fit', type=int, nargs='*', default=[200], help='Adam steps of the fit(s) in leg G (none = skip the leg)')
     args = ap.parse_args()
+    if args.out is None:
+        args.out = os.path.join(here, 'profiles', 'nn_population_timing.txt' if args.population else 'nn_alloc_timing.txt')
     dev = torch.device('cuda', 0)
     n, T = args.envs, 50
     lines = []
@@ -55,6 +110,11 @@ def main():
         lines.append(s)
 
     out('tools/time_nn_alloc.py on %s' % torch.cuda.get_device_name(dev))
+    if args.population:
+        population_leg(args, dev, out)
+        with open(args.out, 'w') as f:
+            f.write('\n'.join(lines) + '\n')
+        return
     rng = np.random.default_rng(0)
     tau = torch.from_numpy((rng.normal(0.0, 1.0, (3, n)) * np.array([[20.0], [10.0], [15.0]])).astype(np.float32)).to(dev)
     nets = [glorot(s, leak, dev) for s, leak in SHAPES]

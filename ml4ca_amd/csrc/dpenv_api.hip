@@ -1354,87 +1354,111 @@ extern "C" int dpenv_set_qp_allocator_table(dpenv_handle h, const float* table, 
 }
 
 // ---- the neural allocation as the closed loop's allocation stage (dpenv.h) ----
-extern "C" int dpenv_set_nn_allocator(dpenv_handle h, const dpenv_nn_allocator* a, dpenv_stream s)
+// The zero-padded image of K networks of one shape: per layer W [K][in][nn_pad(out)] then b [K][nn_pad(out)], so that network k of a layer
+// lies k strides behind network 0 and the kernel needs one product per layer.  A function of the shape and K alone; the one network of
+// dpenv_set_nn_allocator is K = 1: per layer W [in][nn_pad(out)] then b [nn_pad(out)].
+struct NnImage {
+    size_t w_off[NN_MAX_LAYERS], b_off[NN_MAX_LAYERS];     // network 0 of the layer, in floats from the image's base
+    size_t floats;
+};
+static NnImage nn_image_layout(const NnArgs& g, size_t K)
+{
+    NnImage im = {};
+    for (int l = 0; l < g.n_layers; ++l) {
+        const size_t in = l == 0 ? g.in_dim : g.H, ld = (size_t)nn_pad(l == g.n_layers - 1 ? 6 : g.H);
+        im.w_off[l] = im.floats; im.floats += K * in * ld;
+        im.b_off[l] = im.floats; im.floats += K * ld;
+    }
+    return im;
+}
+
+// Writes the image of g's K networks at img (room for nn_image_layout(g, K).floats) and points g's W and b into it.  device: g's arrays are
+// DEVICE arrays and one launch packs them; else host arrays: the image is formed here and copied, and the call waits for the copy.
+static int nn_install(dpenv_handle h, NnArgs& g, int32_t K, bool device, float* img, dpenv_stream s)
+{
+    const NnImage im = nn_image_layout(g, (size_t)K);
+    if (device) {
+        NnPack pk = {};
+        pk.n_layers = g.n_layers; pk.in_dim = g.in_dim; pk.H = g.H; pk.K = K;
+        for (int l = 0; l < g.n_layers; ++l) {
+            pk.W[l] = g.W[l]; pk.b[l] = g.b[l];
+            pk.dW[l] = img + im.w_off[l]; pk.db[l] = img + im.b_off[l];
+        }
+        HIP_TRY(h, dev::launch_nn_pack(&pk, (hipStream_t)s));
+    } else {
+        std::vector<float> host(im.floats, 0.0f);
+        for (int l = 0; l < g.n_layers; ++l) {
+            const size_t in = l == 0 ? g.in_dim : g.H, out = l == g.n_layers - 1 ? 6 : g.H, ld = (size_t)nn_pad((int)out);
+            float* dW = host.data() + im.w_off[l];
+            float* db = host.data() + im.b_off[l];
+            for (size_t q = 0; q < (size_t)K; ++q) {
+                for (size_t k = 0; k < in; ++k)
+                    for (size_t j = 0; j < out; ++j) dW[q * in * ld + k * ld + j] = g.W[l][q * in * out + k * out + j];
+                for (size_t j = 0; j < out; ++j) db[q * ld + j] = g.b[l][q * out + j];
+            }
+        }
+        HIP_TRY(h, hipMemcpyAsync(img, host.data(), sizeof(float) * im.floats, hipMemcpyHostToDevice, (hipStream_t)s));
+        HIP_TRY(h, hipStreamSynchronize((hipStream_t)s));
+    }
+    for (int l = 0; l < g.n_layers; ++l) { g.W[l] = img + im.w_off[l]; g.b[l] = img + im.b_off[l]; }
+    return DPENV_OK;
+}
+
+// What dpenv_set_nn_allocator and dpenv_set_nn_allocator_population do before anything of their own: a NULL `a` turns a neural allocator
+// off (a QP allocator stays); else the refusals in their order, `own` (the population's rules about K, envs_per_net and env_id_base; NULL
+// or the text for behind "<who>: ") between those about the struct and those about the handle.  NN_SET_GO: go on with g; else the return.
+enum { NN_SET_GO = 1 };
+template <typename Own>
+static int nn_setter_open(dpenv_handle h, const dpenv_nn_allocator* a, const char* who, NnArgs& g, Own&& own)
 {
     if (!h) return DPENV_EINVAL;
     if (!a) {
-        if (h->stage == ALLOC_NN) allocator_off(h);        // (a QP allocator stays)
+        if (h->stage == ALLOC_NN) allocator_off(h);
         return DPENV_OK;
     }
-    if (!h->ctrl_on) return fail(h, DPENV_EINVAL, "dpenv_set_nn_allocator: the DP controller is off (dpenv_set_dp_controller first)");
-    NnArgs g;
+    if (!h->ctrl_on) return fail(h, DPENV_EINVAL, "%s: the DP controller is off (dpenv_set_dp_controller first)", who);
     if (const char* why = nn_check(a, g)) return fail(h, DPENV_EINVAL, "%s", why);
     if (a->device_pointers != 0 && a->device_pointers != 1) return fail(h, DPENV_EINVAL, "NN allocator: device_pointers must be 0 or 1");
-    if (!control_config_ok(h)) return fail(h, DPENV_EINVAL, "dpenv_set_nn_allocator: " CONTROL_SET_MSG);
-    if (const char* no = stage_refusal(h, ALLOC_NN)) return fail(h, DPENV_EINVAL, "dpenv_set_nn_allocator: %s", no);
+    if (const char* why = own()) return fail(h, DPENV_EINVAL, "%s: %s", who, why);
+    if (!control_config_ok(h)) return fail(h, DPENV_EINVAL, "%s: " CONTROL_SET_MSG, who);
+    if (const char* no = stage_refusal(h, ALLOC_NN)) return fail(h, DPENV_EINVAL, "%s: %s", who, no);
+    return NN_SET_GO;
+}
+
+extern "C" int dpenv_set_nn_allocator(dpenv_handle h, const dpenv_nn_allocator* a, dpenv_stream s)
+{
+    NnArgs g;
+    const int open = nn_setter_open(h, a, "dpenv_set_nn_allocator", g, [] { return (const char*)nullptr; });
+    if (open != NN_SET_GO) return open;
     DeviceGuard dev_guard(h->device);
     // the largest shape's image, once: a later call never allocates
     if (int rc = ensure_block(h, &h->nn_img, sizeof(float) * (size_t)NN_IMAGE_FLOATS, "hipMalloc of the NN allocator image failed")) return rc;
-    // the image: per layer W [in][nn_pad(out)] then b [nn_pad(out)], zero-padded; a shape's layout is a function of the shape alone
-    NnPack pk = {};
-    pk.n_layers = g.n_layers; pk.in_dim = g.in_dim; pk.H = g.H;
-    size_t off = 0, w_off[NN_MAX_LAYERS], b_off[NN_MAX_LAYERS];
-    for (int l = 0; l < g.n_layers; ++l) {
-        const size_t in = l == 0 ? g.in_dim : g.H, ld = (size_t)nn_pad(l == g.n_layers - 1 ? 6 : g.H);
-        w_off[l] = off; off += in * ld;
-        b_off[l] = off; off += ld;
-        pk.W[l] = g.W[l]; pk.b[l] = g.b[l];
-        pk.dW[l] = h->nn_img + w_off[l]; pk.db[l] = h->nn_img + b_off[l];
-    }
-    if (a->device_pointers) {
-        HIP_TRY(h, dev::launch_nn_pack(&pk, (hipStream_t)s));
-    } else {                                               // host arrays: the image is formed here and copied; the call waits for the copy
-        std::vector<float> img(off, 0.0f);
-        for (int l = 0; l < g.n_layers; ++l) {
-            const size_t in = l == 0 ? g.in_dim : g.H, out = l == g.n_layers - 1 ? 6 : g.H, ld = (size_t)nn_pad((int)out);
-            for (size_t k = 0; k < in; ++k)
-                for (size_t j = 0; j < out; ++j) img[w_off[l] + k * ld + j] = g.W[l][k * out + j];
-            for (size_t j = 0; j < out; ++j) img[b_off[l] + j] = g.b[l][j];
-        }
-        HIP_TRY(h, hipMemcpyAsync(h->nn_img, img.data(), sizeof(float) * off, hipMemcpyHostToDevice, (hipStream_t)s));
-        HIP_TRY(h, hipStreamSynchronize((hipStream_t)s));
-    }
-    for (int l = 0; l < g.n_layers; ++l) { g.W[l] = pk.dW[l]; g.b[l] = pk.db[l]; }
+    if (int rc = nn_install(h, g, 1, a->device_pointers != 0, h->nn_img, s)) return rc;
     h->nn.a = g;
     h->stage = ALLOC_NN;
     h->nn_pop.K = 0;                                       // one network: a population in force is replaced
     return DPENV_OK;
 }
 
-// K networks of one shape, one per envs_per_net envs (dpenv.h).  The image: per layer W [K][in][nn_pad(out)] then b [K][nn_pad(out)], so
-// that network k of a layer lies k strides behind network 0 and the kernel needs one product per layer.
+// K networks of one shape, one per envs_per_net envs (dpenv.h)
 extern "C" int dpenv_set_nn_allocator_population(dpenv_handle h, const dpenv_nn_allocator* a, int32_t K, int32_t envs_per_net, dpenv_stream s)
 {
-    if (!h) return DPENV_EINVAL;
-    if (!a) {
-        if (h->stage == ALLOC_NN) allocator_off(h);        // (a QP allocator stays)
-        return DPENV_OK;
-    }
-    const char* who = "dpenv_set_nn_allocator_population";
-    if (!h->ctrl_on) return fail(h, DPENV_EINVAL, "%s: the DP controller is off (dpenv_set_dp_controller first)", who);
     NnArgs g;
-    if (const char* why = nn_check(a, g)) return fail(h, DPENV_EINVAL, "%s", why);
-    if (a->device_pointers != 0 && a->device_pointers != 1) return fail(h, DPENV_EINVAL, "NN allocator: device_pointers must be 0 or 1");
-    if (const char* why = nn_pop_check(K, envs_per_net)) return fail(h, DPENV_EINVAL, "%s: %s", who, why);
-    const int64_t base = h->args.env_id_base;
-    if (base < 0 || base % RBLOCK != 0)
-        return fail(h, DPENV_EINVAL, "%s: env_id_base must be >= 0 and a multiple of 64 (a wave must not straddle two networks)", who);
-    if (!control_config_ok(h)) return fail(h, DPENV_EINVAL, "%s: " CONTROL_SET_MSG, who);
-    if (const char* no = stage_refusal(h, ALLOC_NN)) return fail(h, DPENV_EINVAL, "%s: %s", who, no);
+    const int open = nn_setter_open(h, a, "dpenv_set_nn_allocator_population", g, [&]() -> const char* {
+        if (const char* why = nn_pop_check(K, envs_per_net)) return why;
+        if (h->args.env_id_base < 0 || h->args.env_id_base % RBLOCK != 0)
+            return "env_id_base must be >= 0 and a multiple of 64 (a wave must not straddle two networks)";
+        return nullptr;
+    });
+    if (open != NN_SET_GO) return open;
     DeviceGuard dev_guard(h->device);
-    size_t per_net = 0, w_str[NN_MAX_LAYERS], b_str[NN_MAX_LAYERS];
-    for (int l = 0; l < g.n_layers; ++l) {
-        const size_t in = l == 0 ? g.in_dim : g.H, ld = (size_t)nn_pad(l == g.n_layers - 1 ? 6 : g.H);
-        w_str[l] = in * ld; b_str[l] = ld;
-        per_net += w_str[l] + b_str[l];
-    }
-    const size_t floats = per_net * (size_t)K;
     const int32_t shape[4] = {g.n_layers, g.in_dim, g.H, K};
     if (!h->nn_pop_img || std::memcmp(shape, h->nn_pop_shape, sizeof shape) != 0) {   // another shape or K: a new image; the old one goes last
+        const size_t bytes = sizeof(float) * nn_image_layout(g, (size_t)K).floats;
         void* p = nullptr;
-        if (hipMalloc(&p, sizeof(float) * floats) != hipSuccess) {
+        if (hipMalloc(&p, bytes) != hipSuccess) {
             (void)hipGetLastError();
-            return fail(h, DPENV_ENOMEM, "hipMalloc of the NN allocator population image failed (%zu bytes)", sizeof(float) * floats);
+            return fail(h, DPENV_ENOMEM, "hipMalloc of the NN allocator population image failed (%zu bytes)", bytes);
         }
         if (h->nn_pop_img) {
             if (h->stage == ALLOC_NN && h->nn_pop.K > 0) allocator_off(h);     // (nothing may fly addresses of the image that goes)
@@ -1443,37 +1467,11 @@ extern "C" int dpenv_set_nn_allocator_population(dpenv_handle h, const dpenv_nn_
         h->nn_pop_img = (float*)p;
         std::memcpy(h->nn_pop_shape, shape, sizeof shape);
     }
-    NnPopPack pk = {};
-    pk.K = K;
-    pk.p.n_layers = g.n_layers; pk.p.in_dim = g.in_dim; pk.p.H = g.H;
-    size_t off = 0;
-    for (int l = 0; l < g.n_layers; ++l) {
-        pk.p.W[l] = g.W[l]; pk.p.b[l] = g.b[l];
-        pk.p.dW[l] = h->nn_pop_img + off; off += w_str[l] * (size_t)K;
-        pk.p.db[l] = h->nn_pop_img + off; off += b_str[l] * (size_t)K;
-    }
-    if (a->device_pointers) {
-        HIP_TRY(h, dev::launch_nn_pack_pop(&pk, (hipStream_t)s));
-    } else {                                               // host arrays: the image is formed here and copied; the call waits for the copy
-        std::vector<float> img(floats, 0.0f);
-        for (int l = 0; l < g.n_layers; ++l) {
-            const size_t in = l == 0 ? g.in_dim : g.H, out = l == g.n_layers - 1 ? 6 : g.H, ld = (size_t)nn_pad((int)out);
-            float* dW = img.data() + (pk.p.dW[l] - h->nn_pop_img);
-            float* db = img.data() + (pk.p.db[l] - h->nn_pop_img);
-            for (size_t q = 0; q < (size_t)K; ++q) {
-                for (size_t k = 0; k < in; ++k)
-                    for (size_t j = 0; j < out; ++j) dW[q * in * ld + k * ld + j] = g.W[l][q * in * out + k * out + j];
-                for (size_t j = 0; j < out; ++j) db[q * ld + j] = g.b[l][q * out + j];
-            }
-        }
-        HIP_TRY(h, hipMemcpyAsync(h->nn_pop_img, img.data(), sizeof(float) * floats, hipMemcpyHostToDevice, (hipStream_t)s));
-        HIP_TRY(h, hipStreamSynchronize((hipStream_t)s));
-    }
-    for (int l = 0; l < g.n_layers; ++l) { g.W[l] = pk.p.dW[l]; g.b[l] = pk.p.db[l]; }
+    if (int rc = nn_install(h, g, K, a->device_pointers != 0, h->nn_pop_img, s)) return rc;
     const int64_t wpn = envs_per_net / RBLOCK;
     h->nn_pop.a = g;
     h->nn_pop.waves_per_net = (int32_t)wpn;
-    h->nn_pop.wave_base = (uint32_t)((base / RBLOCK) % (wpn * (int64_t)K));
+    h->nn_pop.wave_base = (uint32_t)((h->args.env_id_base / RBLOCK) % (wpn * (int64_t)K));
     h->nn_pop.K = K;
     h->stage = ALLOC_NN;
     return DPENV_OK;

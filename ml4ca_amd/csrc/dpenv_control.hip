@@ -303,9 +303,7 @@ hipError_t dev::launch_qp_alloc(const QpArgs* qa, const QpAllocIO* io, hipStream
 hipError_t dev::launch_controller_rollout(const StepArgs* a, const ControlArgs* ca, const FilterArgs* fa, const float4* tab, const QpRollout* qr,
                                           const float4* qtab, int ves, hipStream_t s)
 {
-    // the vessel source must match the arguments (as launch_rollout's): a per-env form needs the table, VES_ARGS_LOSS and only it reads StepArgs.kl
-    if ((ves == VES_ENV_VGPR || ves == VES_ENV_RND) && !a->env_tab) return hipErrorInvalidValue;
-    if ((ves == VES_ARGS_LOSS) != (a->loss_on == LOSS_SHARED)) return hipErrorInvalidValue;
+    if (!control_ves_ok(ves, a)) return hipErrorInvalidValue;
     const dim3 grid((a->n + RBLOCK - 1) / RBLOCK), block(RBLOCK);
     if (!qr && qtab) return hipErrorInvalidValue;
     if (qr) {                                                    // the QP allocation: a shared hull only

@@ -4,7 +4,8 @@
 // nn_allocate takes dp_allocate's place.  The law has no state and touches no hull, so the closed loop exists for every vessel source the
 // pseudo-inverse flies (the shared hull, the thrust-loss preset, per-env hulls and their randomisation), with and without the reference
 // filter.  The law exists once, in dpenv_nn_law.h, which also says how it is evaluated (scalar loads of the weights, a wave-private
-// LDS column block for the activations, accumulators in VGPRs).
+// LDS column block for the activations, accumulators in VGPRs).  The handle's zero-padded image is the K = 1 case of the population's:
+// its one packing kernel is in dpenv_control_nn_pop.hip (launch_nn_pack).
 //
 // A unit of its own with the library's CXXFLAGS, for the reason dpenv_label.hip is one: compiled into dpenv_control.hip, new
 // instantiations of the shared body re-schedule the kernels that are there.
@@ -33,43 +34,11 @@ __global__ __launch_bounds__(RBLOCK) void controller_rollout_nn_kernel(const Ste
 #include "dpenv_control_rollout_body.inc"
 }
 
-// the handle-free map (dpenv_thrust_alloc_nn): tau [3][n] -> action [n][7] and, if raw, the network's outputs [n][6]; one lane per env,
-// one wave per workgroup, the caller's weights read in place.  Dead lanes shadow env n - 1 and store nothing.
+// the handle-free map (dpenv_thrust_alloc_nn): the caller's one network on every wave (nn_alloc_lane, dpenv_nn_law.h)
 __global__ __launch_bounds__(64) void nn_alloc_kernel(const NnArgs na, const float* __restrict__ tau, float* __restrict__ action,
                                                        float* __restrict__ raw, int n)
 {
-    const int i = blockIdx.x * 64 + threadIdx.x;
-    const bool live = i < n;
-    const int il = live ? i : n - 1;
-    const float t[3] = {tau[il], tau[(int64_t)n + il], tau[2 * (int64_t)n + il]};
-    float act[7], p[6];
-    nn_allocate<false>(na, nn_lds() + threadIdx.x, t, act, p);
-    if (!live) return;
-    float* q = action + (int64_t)i * 7;
-#pragma unroll
-    for (int k = 0; k < 7; ++k) q[k] = act[k];
-    if (raw) {
-        float* r = raw + (int64_t)i * 6;
-#pragma unroll
-        for (int k = 0; k < 6; ++k) r[k] = p[k];
-    }
-}
-
-// The caller's arrays -> the zero-padded image: block (k, l) copies row k of layer l (row in_l: the bias), thread j column j.
-__global__ __launch_bounds__(NN_MAX_H) void nn_pack_kernel(const NnPack np)
-{
-    const int l = blockIdx.y, k = blockIdx.x, j = threadIdx.x;
-    const float *W = np.W[0], *b = np.b[0];
-    float *dW = np.dW[0], *db = np.db[0];
-#pragma unroll
-    for (int q = 1; q < NN_MAX_LAYERS; ++q)
-        if (l == q) { W = np.W[q]; b = np.b[q]; dW = np.dW[q]; db = np.db[q]; }
-    const int in = l == 0 ? np.in_dim : np.H;
-    const int out = l == np.n_layers - 1 ? 6 : np.H;
-    const int ld = nn_pad(out);
-    if (k > in || j >= ld) return;
-    if (k < in) dW[k * ld + j] = j < out ? W[k * out + j] : 0.0f;
-    else db[j] = j < out ? b[j] : 0.0f;
+    nn_alloc_lane(na, tau, action, raw, n);
 }
 
 }  // namespace
@@ -79,9 +48,7 @@ using namespace dpenv;
 
 hipError_t dev::launch_nn_alloc(const NnArgs* na, const float* tau, float* action, float* raw, int n, hipStream_t s)
 {
-    if (!nn_shape_ok(na->n_layers, na->in_dim, na->H) || !tau || !action || n <= 0) return hipErrorInvalidValue;
-    for (int l = 0; l < na->n_layers; ++l)
-        if (!na->W[l] || !na->b[l]) return hipErrorInvalidValue;
+    if (!nn_args_ok(*na) || !tau || !action || n <= 0) return hipErrorInvalidValue;
     hipLaunchKernelGGL(nn_alloc_kernel, dim3((n + 63) / 64), dim3(64), nn_lds_bytes(na->H), s, *na, tau, action, raw, n);
     return hipGetLastError();
 }
@@ -89,11 +56,7 @@ hipError_t dev::launch_nn_alloc(const NnArgs* na, const float* tau, float* actio
 hipError_t dev::launch_controller_rollout_nn(const StepArgs* a, const ControlArgs* ca, const FilterArgs* fa, const NnRollout* nr, int ves,
                                              hipStream_t s)
 {
-    if ((ves == VES_ENV_VGPR || ves == VES_ENV_RND) && !a->env_tab) return hipErrorInvalidValue;
-    if ((ves == VES_ARGS_LOSS) != (a->loss_on == LOSS_SHARED)) return hipErrorInvalidValue;
-    if (!nn_shape_ok(nr->a.n_layers, nr->a.in_dim, nr->a.H)) return hipErrorInvalidValue;
-    for (int l = 0; l < nr->a.n_layers; ++l)
-        if (!nr->a.W[l] || !nr->a.b[l]) return hipErrorInvalidValue;
+    if (!control_ves_ok(ves, a) || !nn_args_ok(nr->a)) return hipErrorInvalidValue;
     const dim3 grid((a->n + RBLOCK - 1) / RBLOCK), block(RBLOCK);
     const int lds = nn_lds_bytes(nr->a.H);
     return with_control_ves(ves, [&](auto V) {
@@ -101,13 +64,4 @@ hipError_t dev::launch_controller_rollout_nn(const StepArgs* a, const ControlArg
         else hipLaunchKernelGGL((controller_rollout_nn_kernel<V, false>), grid, block, lds, s, *a, *ca, FilterArgs{}, *nr);
         return hipGetLastError();
     });
-}
-
-hipError_t dev::launch_nn_pack(const NnPack* np, hipStream_t s)
-{
-    if (!nn_shape_ok(np->n_layers, np->in_dim, np->H)) return hipErrorInvalidValue;
-    for (int l = 0; l < np->n_layers; ++l)
-        if (!np->W[l] || !np->b[l] || !np->dW[l] || !np->db[l]) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(nn_pack_kernel, dim3(NN_MAX_H + 1, np->n_layers), dim3(NN_MAX_H), 0, s, *np);
-    return hipGetLastError();
 }

@@ -8,6 +8,8 @@
 // flies the `nr` it finds in scope, which here is the wave's), the weights arrive by scalar loads and enter v_fmac_f32 as SGPR operands.
 // The % K keeps every address inside the K networks whatever n and env_id_base are.  A network per single ENV is not here and cannot
 // be had this way: its addresses would differ between lanes, and the weights would leave the scalar path for one vector load per fmaf.
+// The handle-free map's lane after the addresses is dpenv_nn_law.h's nn_alloc_lane, the scalar map's.  The library's ONE packing kernel
+// is here too: the one network of dpenv_set_nn_allocator is packed as a population of K = 1, whose image is the same bytes.
 //
 // A unit of its own with the library's CXXFLAGS, for the reason dpenv_control_nn.hip is one: no kernel of another unit is re-scheduled.
 #include "dpenv_policy_dev.h"
@@ -57,28 +59,13 @@ __global__ __launch_bounds__(RBLOCK) void controller_rollout_nn_pop_kernel(const
 __global__ __launch_bounds__(64) void nn_alloc_pop_kernel(const NnPop pop, const float* __restrict__ tau, float* __restrict__ action,
                                                            float* __restrict__ raw, int n)
 {
-    const NnArgs na = nn_pop_network<false>(pop, pop.wave_base + blockIdx.x);
-    const int i = blockIdx.x * 64 + threadIdx.x;
-    const bool live = i < n;
-    const int il = live ? i : n - 1;
-    const float t[3] = {tau[il], tau[(int64_t)n + il], tau[2 * (int64_t)n + il]};
-    float act[7], p[6];
-    nn_allocate<false>(na, nn_lds() + threadIdx.x, t, act, p);
-    if (!live) return;
-    float* q = action + (int64_t)i * 7;
-#pragma unroll
-    for (int k = 0; k < 7; ++k) q[k] = act[k];
-    if (raw) {
-        float* r = raw + (int64_t)i * 6;
-#pragma unroll
-        for (int k = 0; k < 6; ++k) r[k] = p[k];
-    }
+    nn_alloc_lane(nn_pop_network<false>(pop, pop.wave_base + blockIdx.x), tau, action, raw, n);
 }
 
-// nn_pack_kernel for K networks: block (net, l, k) copies row k of layer l of network net (row in_l: the bias), thread j column j
-__global__ __launch_bounds__(NN_MAX_H) void nn_pack_pop_kernel(const NnPopPack pp)
+// The caller's arrays -> the zero-padded image of K networks (the one network of dpenv_set_nn_allocator: K = 1): block (net, l, k) copies
+// row k of layer l of network net (row in_l: the bias), thread j column j
+__global__ __launch_bounds__(NN_MAX_H) void nn_pack_pop_kernel(const NnPack np)
 {
-    const NnPack& np = pp.p;
     const int net = blockIdx.x, l = blockIdx.y, k = blockIdx.z, j = threadIdx.x;
     const float *W = np.W[0], *b = np.b[0];
     float *dW = np.dW[0], *db = np.db[0];
@@ -88,20 +75,14 @@ __global__ __launch_bounds__(NN_MAX_H) void nn_pack_pop_kernel(const NnPopPack p
     const int in = l == 0 ? np.in_dim : np.H;
     const int out = l == np.n_layers - 1 ? 6 : np.H;
     const int ld = nn_pad(out);
-    if (net >= pp.K || k > in || j >= ld) return;
+    if (net >= np.K || k > in || j >= ld) return;
     W += (int64_t)net * (in * out); b += (int64_t)net * out;
     dW += (int64_t)net * (in * ld); db += (int64_t)net * ld;
     if (k < in) dW[k * ld + j] = j < out ? W[k * out + j] : 0.0f;
     else db[j] = j < out ? b[j] : 0.0f;
 }
 
-bool pop_ok(const NnPop* np)
-{
-    if (!nn_shape_ok(np->a.n_layers, np->a.in_dim, np->a.H) || np->K < 1 || np->waves_per_net < 1) return false;
-    for (int l = 0; l < np->a.n_layers; ++l)
-        if (!np->a.W[l] || !np->a.b[l]) return false;
-    return true;
-}
+bool pop_ok(const NnPop* np) { return nn_args_ok(np->a) && np->K >= 1 && np->waves_per_net >= 1; }
 
 }  // namespace
 }  // namespace dpenv
@@ -118,9 +99,7 @@ hipError_t dev::launch_nn_alloc_pop(const NnPop* np, const float* tau, float* ac
 hipError_t dev::launch_controller_rollout_nn_pop(const StepArgs* a, const ControlArgs* ca, const FilterArgs* fa, const NnPop* np, int ves,
                                                  hipStream_t s)
 {
-    if ((ves == VES_ENV_VGPR || ves == VES_ENV_RND) && !a->env_tab) return hipErrorInvalidValue;
-    if ((ves == VES_ARGS_LOSS) != (a->loss_on == LOSS_SHARED)) return hipErrorInvalidValue;
-    if (!pop_ok(np)) return hipErrorInvalidValue;
+    if (!control_ves_ok(ves, a) || !pop_ok(np)) return hipErrorInvalidValue;
     const dim3 grid((a->n + RBLOCK - 1) / RBLOCK), block(RBLOCK);
     const int lds = nn_lds_bytes(np->a.H);
     return with_control_ves(ves, [&](auto V) {
@@ -130,12 +109,11 @@ hipError_t dev::launch_controller_rollout_nn_pop(const StepArgs* a, const Contro
     });
 }
 
-hipError_t dev::launch_nn_pack_pop(const NnPopPack* pp, hipStream_t s)
+hipError_t dev::launch_nn_pack(const NnPack* np, hipStream_t s)
 {
-    const NnPack* np = &pp->p;
-    if (!nn_shape_ok(np->n_layers, np->in_dim, np->H) || pp->K < 1) return hipErrorInvalidValue;
+    if (!nn_args_ok(*np) || np->K < 1) return hipErrorInvalidValue;
     for (int l = 0; l < np->n_layers; ++l)
-        if (!np->W[l] || !np->b[l] || !np->dW[l] || !np->db[l]) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(nn_pack_pop_kernel, dim3(pp->K, np->n_layers, NN_MAX_H + 1), dim3(NN_MAX_H), 0, s, *pp);
+        if (!np->dW[l] || !np->db[l]) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(nn_pack_pop_kernel, dim3(np->K, np->n_layers, NN_MAX_H + 1), dim3(NN_MAX_H), 0, s, *np);
     return hipGetLastError();
 }

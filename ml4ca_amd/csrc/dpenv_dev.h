@@ -293,18 +293,29 @@ inline bool nn_shape_ok(int n_layers, int in_dim, int H)
 {
     return n_layers >= 2 && n_layers <= NN_MAX_LAYERS && (in_dim == 3 || in_dim == 9) && H >= 1 && H <= NN_MAX_H;
 }
+// ... and of its arrays: every launcher that is handed an NnArgs (or an NnPack, whose source side has the same members) asks this, once
+template <typename A> bool nn_args_ok(const A& a)
+{
+    if (!nn_shape_ok(a.n_layers, a.in_dim, a.H)) return false;
+    for (int l = 0; l < a.n_layers; ++l)
+        if (!a.W[l] || !a.b[l]) return false;
+    return true;
+}
 // the allocation as the allocation stage of the baseline's closed loop (dpenv_set_nn_allocator): a separate argument of
 // controller_rollout_nn_kernel only; the weights are the handle's padded image
 struct NnRollout {
     NnArgs a;
 };
-// the packing of that image from DEVICE arrays (dpenv_set_nn_allocator with device_pointers = 1): src in place, dst the image's layers
+// the packing of the zero-padded image of K networks from DEVICE arrays (dpenv_set_nn_allocator, K = 1, and
+// dpenv_set_nn_allocator_population with device_pointers = 1): network k of src layer l at W[l] + k in out and b[l] + k out, in place; of
+// dst at dW[l] + k in ld and db[l] + k ld, the image's layers
 struct NnPack {
     const float* W[NN_MAX_LAYERS];
     const float* b[NN_MAX_LAYERS];
     float* dW[NN_MAX_LAYERS];
     float* db[NN_MAX_LAYERS];
     int32_t n_layers, in_dim, H;
+    int32_t K;
 };
 // K networks of one shape, one per run of waves (dpenv_set_nn_allocator_population / dpenv_thrust_alloc_nn_population;
 // dpenv_control_nn_pop.hip): a.W[l] is [K][in_l][ld_l] and a.b[l] [K][ld_l] - network 0's addresses, the others behind it layer by layer -
@@ -314,12 +325,6 @@ struct NnPop {
     NnArgs a;
     int32_t K, waves_per_net;       // K >= 1; envs_per_net / 64 >= 1
     uint32_t wave_base;             // (env_id_base / 64) mod (K waves_per_net), which the host keeps below 2^31; 0 for the handle-free map
-};
-// the packing of K networks (dpenv_set_nn_allocator_population with device_pointers = 1): network k of src layer l at W[l] + k in out
-// and b[l] + k out, of dst at dW[l] + k in ld and db[l] + k ld
-struct NnPopPack {
-    NnPack p;
-    int32_t K;
 };
 
 // device-side weight packing (pack_policy_kernel): one dense network, DEVICE pointers
@@ -462,6 +467,14 @@ template <typename F> hipError_t with_control_ves(int ves, F&& f)
     }
     return hipErrorInvalidValue;
 }
+// the vessel source must match the arguments (as launch_rollout's): a per-env form needs the table, VES_ARGS_LOSS and only it reads
+// StepArgs.kl.  What every launcher of that closed loop (dpenv_control.hip, dpenv_control_nn.hip, dpenv_control_nn_pop.hip) asks first.
+inline bool control_ves_ok(int ves, const StepArgs* a)
+{
+    if ((ves == VES_ENV_VGPR || ves == VES_ENV_RND) && !a->env_tab) return false;
+    if ((ves == VES_ARGS_LOSS) != (a->loss_on == LOSS_SHARED)) return false;
+    return true;
+}
 // waves per 64 envs of the two-wave form: an env and a network wave, plus a critic wave of its own (ROLES = 3) in the 128-env geometry
 // for the two split arithmetics, all exact and exact actor - not f16 (dpenv_policy_ws.h has the measurements)
 constexpr int ws_roles(int prec, int groups) { return (groups == 2 && prec != PREC_F16) ? 3 : 2; }
@@ -602,13 +615,11 @@ hipError_t launch_nn_alloc(const NnArgs* na, const float* tau, float* action, fl
 // the baseline's closed loop with the neural allocation behind the PID lines (launch_controller_rollout's a, ca, fa and ves; every
 // vessel source of with_control_ves); nr->a points into the padded image launch_nn_pack or the host wrote
 hipError_t launch_controller_rollout_nn(const StepArgs* a, const ControlArgs* ca, const FilterArgs* fa, const NnRollout* nr, int ves, hipStream_t s);
-// the caller's DEVICE arrays -> the zero-padded image, one launch
-hipError_t launch_nn_pack(const NnPack* np, hipStream_t s);
-// dpenv_control_nn_pop.hip: launch_nn_alloc, launch_controller_rollout_nn and launch_nn_pack with K networks of one shape, one per
-// waves_per_net waves (NnPop)
+// dpenv_control_nn_pop.hip: launch_nn_alloc and launch_controller_rollout_nn with K networks of one shape, one per waves_per_net waves (NnPop)
 hipError_t launch_nn_alloc_pop(const NnPop* np, const float* tau, float* action, float* raw, int n, hipStream_t s);
 hipError_t launch_controller_rollout_nn_pop(const StepArgs* a, const ControlArgs* ca, const FilterArgs* fa, const NnPop* np, int ves, hipStream_t s);
-hipError_t launch_nn_pack_pop(const NnPopPack* pp, hipStream_t s);
+// the caller's DEVICE arrays -> the zero-padded image of np->K networks (one network: K = 1), one launch
+hipError_t launch_nn_pack(const NnPack* np, hipStream_t s);
 // dpenv_label_nn.hip: launch_controller_label's scan with the neural allocation in place of the pseudo-inverse and, if la->tau, the PID's
 // wrench per row; na: NULL exactly when la->act is NULL; padded: na's W and b are the zero-padded image, else arrays read in place
 hipError_t launch_controller_label_nn(const ControlArgs* ca, const NnArgs* na, const LabelNnArgs* la, const float4* tab, int obs_bf16, int padded,

@@ -128,9 +128,7 @@ hipError_t dev::launch_controller_label_nn(const ControlArgs* ca, const NnArgs* 
     NnArgs g = {};
     int lds = 0;
     if (na) {
-        if (!nn_shape_ok(na->n_layers, na->in_dim, na->H)) return hipErrorInvalidValue;
-        for (int l = 0; l < na->n_layers; ++l)
-            if (!na->W[l] || !na->b[l]) return hipErrorInvalidValue;
+        if (!nn_args_ok(*na)) return hipErrorInvalidValue;
         g = *na;
         lds = nn_lds_bytes(na->H);
     }

@@ -122,4 +122,26 @@ __device__ __forceinline__ void nn_allocate(const NnArgs& na, float* hcol, const
     act[6] = ok ? cs[1] : 1.0f;
 }
 
+// The handle-free map's lane (nn_alloc_kernel, nn_alloc_pop_kernel) from "which NnArgs" on: tau [3][n] -> action [n][7] and, if raw, the
+// network's outputs [n][6]; one lane per env, one wave per workgroup, the weights read in place.  Dead lanes shadow env n - 1 and store
+// nothing.  (The kernels' parameters carry __restrict__, these do not: repeated here it re-schedules both kernels.)
+__device__ __forceinline__ void nn_alloc_lane(const NnArgs& na, const float* tau, float* action, float* raw, int n)
+{
+    const int i = blockIdx.x * 64 + threadIdx.x;
+    const bool live = i < n;
+    const int il = live ? i : n - 1;
+    const float t[3] = {tau[il], tau[(int64_t)n + il], tau[2 * (int64_t)n + il]};
+    float act[7], p[6];
+    nn_allocate<false>(na, nn_lds() + threadIdx.x, t, act, p);
+    if (!live) return;
+    float* q = action + (int64_t)i * 7;
+#pragma unroll
+    for (int k = 0; k < 7; ++k) q[k] = act[k];
+    if (raw) {
+        float* r = raw + (int64_t)i * 6;
+#pragma unroll
+        for (int k = 0; k < 6; ++k) r[k] = p[k];
+    }
+}
+
 #endif

@@ -510,16 +510,45 @@ def thrust_alloc_qp(tau, state=None, params=None, dt=0.2, out=None, cost=False, 
     return (act, state_out, J) if cost else (act, state_out)
 
 
+def _in_place(tensors, device):
+    """Every entry is a contiguous float32 tensor on `device`: what the library can read where it is (device_pointers = 1)."""
+    torch = _torch()
+    return all(isinstance(t, torch.Tensor) and t.is_cuda and t.device == device and t.dtype == torch.float32 and t.is_contiguous()
+               for t in tensors)
+
+
+def _nn_alloc_map(who, tau, out, raw, struct, call):
+    """What thrust_alloc_nn and thrust_alloc_nn_population share: the check of tau, the allocator struct (struct(device) -> a tuple the
+    call reads and that keeps the struct's arrays alive), the action and raw buffers, and the launch on tau's device and current stream:
+    call(that tuple, tau, action, raw or None, n, stream) is the one library call."""
+    torch = _torch()
+    f32 = torch.float32
+    if not isinstance(tau, torch.Tensor) or tau.dim() != 2 or tau.shape[0] != 3 or tau.dtype != f32 or not tau.is_cuda or not tau.is_contiguous():
+        raise ValueError('%s: tau is a contiguous float32 device tensor [3, n]' % who)
+    n = int(tau.shape[1])
+    st = struct(tau.device)
+    act, p = (out if raw else (out, None)) if out is not None else (None, None)
+    if act is None:
+        act = torch.empty((n, 7), dtype=f32, device=tau.device)
+    if raw and p is None:
+        p = torch.empty((n, 6), dtype=f32, device=tau.device)
+    for t, shape, what in ((act, (n, 7), 'action'), (p, (n, 6), 'raw')):
+        if t is not None and (tuple(t.shape) != shape or t.dtype != f32 or t.device != tau.device or not t.is_contiguous()):
+            raise ValueError('%s: the %s buffer is a contiguous float32 tensor %s on tau\'s device' % (who, what, list(shape)))
+    s = C.c_void_p(torch.cuda.current_stream(tau.device).cuda_stream)
+    with torch.cuda.device(tau.device):
+        _lib.check(call(st, C.c_void_p(tau.data_ptr()), C.c_void_p(act.data_ptr()), C.c_void_p(p.data_ptr()) if p is not None else None, n, s))
+    return (act, p) if raw else act
+
+
 def nn_allocator_struct(net, params, device):
     """(dpenv_nn_allocator, keep) for a net (deploy.nn_net_arrays' forms) and the dict of deploy.nn_allocator_defaults.  If every W and b
     is a contiguous float32 tensor on `device`, they are handed over as DEVICE pointers (device_pointers = 1: no copy - the optimiser's
     own tensors, a graph replay reads their contents of that moment); else as host arrays (device_pointers = 0).  keep holds what the
     struct points to: keep it alive until the call that takes the struct has returned."""
-    torch = _torch()
     from .deploy import nn_net_arrays, nn_net_sizes
     Ws, bs = (net['W'], net['b']) if isinstance(net, dict) else net
-    on_dev = all(isinstance(t, torch.Tensor) and t.is_cuda and t.device == device and t.dtype == torch.float32 and t.is_contiguous()
-                 for t in list(Ws) + list(bs))
+    on_dev = _in_place(list(Ws) + list(bs), device)
     sizes = nn_net_sizes(Ws, bs)
     hW, hb = (None, None) if on_dev else nn_net_arrays(net)    # (no copy of device tensors: the call stays capturable)
     m = _lib.Mlp()
@@ -551,14 +580,12 @@ def nn_population_struct(nets, params, device):
     of deploy.nn_allocator_defaults: nn_allocator_struct with W[l] [K, in, out] and b[l] [K, out] behind the pointers (sizes are one
     network's).  Stacked contiguous float32 tensors on `device` are handed over in place (device_pointers = 1), anything else as host
     arrays (device_pointers = 0)."""
-    torch = _torch()
     from .deploy import nn_population_stack
     st = nn_population_stack(nets)
     K = int(st['W'][0].shape[0])
     one = dict(W=[w[0] for w in st['W']], b=[b[0] for b in st['b']])
     a, keep = nn_allocator_struct(one, params, device)            # the shape, the constants (and network 0's addresses, replaced below)
-    on_dev = all(isinstance(t, torch.Tensor) and t.is_cuda and t.device == device and t.dtype == torch.float32 and t.is_contiguous()
-                 for t in list(st['W']) + list(st['b']))
+    on_dev = _in_place(list(st['W']) + list(st['b']), device)
     if on_dev:
         Ws, bs = list(st['W']), list(st['b'])
         ptr = lambda t: t.data_ptr()
@@ -590,28 +617,13 @@ def thrust_alloc_nn_population(tau, nets, envs_per_net=64, out=None, raw=False, 
     are read in place, anything else is stacked and copied there first; envs_per_net: a multiple of 64; the rest is thrust_alloc_nn's.
     On network k's envs the outputs are thrust_alloc_nn's with network k, bit for bit; deploy.BatchedNNAllocatorPopulation is the host
     statement."""
-    torch = _torch()
     from .deploy import nn_allocator_params
-    f32 = torch.float32
-    if not isinstance(tau, torch.Tensor) or tau.dim() != 2 or tau.shape[0] != 3 or tau.dtype != f32 or not tau.is_cuda or not tau.is_contiguous():
-        raise ValueError('thrust_alloc_nn_population: tau is a contiguous float32 device tensor [3, n]')
-    n = int(tau.shape[1])
-    dnet = nn_population_to(nets, tau.device)
-    a, K, keep = nn_population_struct(dnet, nn_allocator_params(dnet, **constants), tau.device)
-    act, p = (out if raw else (out, None)) if out is not None else (None, None)
-    if act is None:
-        act = torch.empty((n, 7), dtype=f32, device=tau.device)
-    if raw and p is None:
-        p = torch.empty((n, 6), dtype=f32, device=tau.device)
-    for t, shape, what in ((act, (n, 7), 'action'), (p, (n, 6), 'raw')):
-        if t is not None and (tuple(t.shape) != shape or t.dtype != f32 or t.device != tau.device or not t.is_contiguous()):
-            raise ValueError('thrust_alloc_nn_population: the %s buffer is a contiguous float32 tensor %s on tau\'s device' % (what, list(shape)))
-    s = C.c_void_p(torch.cuda.current_stream(tau.device).cuda_stream)
-    with torch.cuda.device(tau.device):
-        _lib.check(_lib.load().dpenv_thrust_alloc_nn_population(C.byref(a), K, int(envs_per_net), C.c_void_p(tau.data_ptr()),
-                                                                C.c_void_p(act.data_ptr()), C.c_void_p(p.data_ptr()) if p is not None else None, n, s))
-    del keep
-    return (act, p) if raw else act
+
+    def struct(dev):
+        dnet = nn_population_to(nets, dev)
+        return nn_population_struct(dnet, nn_allocator_params(dnet, **constants), dev)
+    return _nn_alloc_map('thrust_alloc_nn_population', tau, out, raw, struct,
+                         lambda st, *io: _lib.load().dpenv_thrust_alloc_nn_population(C.byref(st[0]), st[1], int(envs_per_net), *io))
 
 
 def nn_net_to(net, device):
@@ -701,25 +713,7 @@ def thrust_alloc_nn(tau, net, out=None, raw=False, **constants):
     read in place, anything else is copied there first; constants: entries of deploy.nn_allocator_defaults to override (leak,
     azimuth_mode, ...).  out = the action buffer, or (action, raw) with raw=True.  An env whose tau or whose network output is not finite
     gets the rest action.  Handle-free and stateless; deploy.BatchedNNAllocator is the host statement."""
-    torch = _torch()
     from .deploy import nn_allocator_params
-    f32 = torch.float32
-    if not isinstance(tau, torch.Tensor) or tau.dim() != 2 or tau.shape[0] != 3 or tau.dtype != f32 or not tau.is_cuda or not tau.is_contiguous():
-        raise ValueError('thrust_alloc_nn: tau is a contiguous float32 device tensor [3, n]')
-    n = int(tau.shape[1])
-    dnet = nn_net_to(net, tau.device)
-    a, keep = nn_allocator_struct(dnet, nn_allocator_params(net, **constants), tau.device)
-    act, p = (out if raw else (out, None)) if out is not None else (None, None)
-    if act is None:
-        act = torch.empty((n, 7), dtype=f32, device=tau.device)
-    if raw and p is None:
-        p = torch.empty((n, 6), dtype=f32, device=tau.device)
-    for t, shape, what in ((act, (n, 7), 'action'), (p, (n, 6), 'raw')):
-        if t is not None and (tuple(t.shape) != shape or t.dtype != f32 or t.device != tau.device or not t.is_contiguous()):
-            raise ValueError('thrust_alloc_nn: the %s buffer is a contiguous float32 tensor %s on tau\'s device' % (what, list(shape)))
-    s = C.c_void_p(torch.cuda.current_stream(tau.device).cuda_stream)
-    with torch.cuda.device(tau.device):
-        _lib.check(_lib.load().dpenv_thrust_alloc_nn(C.byref(a), C.c_void_p(tau.data_ptr()), C.c_void_p(act.data_ptr()),
-                                                     C.c_void_p(p.data_ptr()) if p is not None else None, n, s))
-    del keep
-    return (act, p) if raw else act
+    return _nn_alloc_map('thrust_alloc_nn', tau, out, raw,
+                         lambda dev: nn_allocator_struct(nn_net_to(net, dev), nn_allocator_params(net, **constants), dev),
+                         lambda st, *io: _lib.load().dpenv_thrust_alloc_nn(C.byref(st[0]), *io))

@@ -410,3 +410,44 @@ def test_sweep_equals_one_box_test_per_network():
     assert torch.equal(res['mean_iae'], res['iae'].mean(1)) and torch.equal(res['mean_work'], res['work'].mean(1))
     assert np.array_equal(res['front'], pareto_front(_np(res['mean_iae']), _np(res['mean_work'].sum(1))))
     assert not torch.equal(res['iae'][0], res['iae'][1])
+
+
+# ---- 11. one handle through both setters ------------------------------------------------------------------------------------------------
+def test_one_handle_walked_through_both_setters_flies_each_setting_alone():
+    """The two setters share one image layout and one installer; what that can get wrong is an address or a stride that survives from
+    the call before.  One handle of n = 192 (three waves), T = 4, walked through: one network from host arrays; a population of K = 3 of
+    the largest shape from device tensors; one network (3, 1, 6) from device tensors; K = 2 of (9, 17, 17, 6) from host arrays (another
+    shape and K: the image is re-allocated); K = 2 of that shape with other weights (the image in place); off.  Every flight starts
+    from the same saved state, and after every setter the rows are, bit for bit, those of a fresh handle given that setting alone -
+    after "off" the pseudo-inverse's."""
+    import torch
+    from ml4ca_amd.policy import controller_rollout
+    n, T, E = 192, 4, 64
+    pad_edge, largest = (9, 17, 17, 6), (9, 96, 96, 96, 96, 6)
+    walk = [
+        ('one network, host arrays', lambda e: e.set_nn_allocator(_nets(1, pad_edge, seed=70)[0])),
+        ('K = 3 of the largest shape, device tensors', lambda e: e.set_nn_allocator_population(_dev(_nets(3, largest, seed=71)), envs_per_net=E)),
+        ('one network (3, 1, 6), device tensors', lambda e: e.set_nn_allocator(_one(_nets(1, (3, 1, 6), seed=74)[0]))),
+        ('K = 2, host arrays, a new image', lambda e: e.set_nn_allocator_population(_nets(2, pad_edge, seed=75), envs_per_net=E)),
+        ('K = 2, other weights, the image in place', lambda e: e.set_nn_allocator_population(_nets(2, pad_edge, seed=77), envs_per_net=E)),
+        ('off', lambda e: e.set_nn_allocator_population(off=True)),
+    ]
+    env = _start(_env(n), nn=False)
+    st0, ctr0 = env.get_state()
+    z0 = torch.zeros((3, n), device=env.device)
+
+    def fly(e, setting):
+        setting(e)
+        e.set_state(st0, ctr0)
+        e.set_dp_controller_state(z0)
+        return {k: v.clone() for k, v in controller_rollout(e, T).items()}
+
+    pinv = fly(_start(_env(n), nn=False), lambda e: None)
+    before = pinv
+    for what, setting in walk:
+        rows = fly(env, setting)
+        alone = pinv if what == 'off' else fly(_start(_env(n), nn=False), setting)
+        _same(rows, alone, what=what)
+        assert bool(torch.isfinite(rows['act']).all())
+        assert not torch.equal(rows['act'], before['act']), '%s: the rows of the setting before' % what
+        before = rows

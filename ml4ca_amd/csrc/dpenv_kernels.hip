@@ -1062,8 +1062,8 @@ __global__ __launch_bounds__(BLOCK) void thrust_map_kernel(const VesselDev vd, c
 }
 
 // ---- GAE-lambda reverse scan (ppo.py:65-91, core.py:48-63) + advantage statistics (ppo.py:99-103, mpi_tools.py:71-92) ----
-// A lane owns V adjacent env columns (V = 4: every row access is a 16-byte load / store, 1 KiB per wave-instruction) and walks
-// them from t = T-1 down to 0.  The recurrence is serial in t, but none of the LOADS depends on it: rows are fetched GAE_U at a
+// A lane owns V adjacent env columns (V = 2: every row access is an 8-byte load / store, 512 B per wave-instruction; V = 1, the
+// scalar form, when n is odd or a block is off its alignment: launch_gae chooses) and walks them from t = T-1 down to 0.  The recurrence is serial in t, but none of the LOADS depends on it: rows are fetched GAE_U at a
 // time into one of two register buffers while the other is being consumed, so 2 GAE_U rows of every column are in flight and
 // the scan runs at memory speed instead of one HBM latency per row (round 1: 0.13 of the HBM roof).  The same pass sums adv and
 // adv^2 per lane in double; a fixed-order wave reduction leaves one partial pair per workgroup and gae_finalize_kernel adds

@@ -45,10 +45,20 @@ from ml4ca_amd import rollout
 from ml4ca_amd.policy import ActorCritic
 
 
+def iadc_text(s):
+    """'  IADC total (rps part + angle part)' of a box-test result scored with wear=True: the thesis' wear axis, means over the envs."""
+    return '  IADC %.2f (rps %.2f + angle %.2f)' % (float(s['iadc'].mean()), float(s['iadc_rps'].mean()), float(s['iadc_angle'].mean()))
+
+
+def iadc_entries(s):
+    return {'IADC': float(s['iadc'].mean()), 'IADC_rps': float(s['iadc_rps'].mean()), 'IADC_angle': float(s['iadc_angle'].mean())}
+
+
 def evaluate_actor(ac, dev, preset, precision, seed, out=print, eval_envs=1024, only=None, nn_net=None):
     """The trained actor on the NOMINAL hull (and on a spread of hulls): the reference's run_RL_policy (spinup/utils/test_policy.py:97-186: six
-    fixed starts, deterministic policy) and the thesis' 4-corner box test with its two metrics - IAE (results/all_plots/common.py:60-74) and
-    the energy-equivalent work of the thruster power model (box_test/plot_act.py:128-135,184-211)."""
+    fixed starts, deterministic policy) and the thesis' 4-corner box test with its three metrics - IAE (results/all_plots/common.py:60-74),
+    the energy-equivalent work of the thruster power model (box_test/plot_act.py:128-135,184-211) and IADC, the wear of the commands
+    (box_test/plot_act.py:320-391), on every contender's line."""
     from ml4ca_amd import evaluate as EV
     from ml4ca_amd.deploy import dp_controller_defaults, qp_allocator_defaults
     from ml4ca_amd.policy import policy_rollout
@@ -81,28 +91,30 @@ def evaluate_actor(ac, dev, preset, precision, seed, out=print, eval_envs=1024, 
             # with the pole-placement defaults of the NOMINAL hull (deploy.dp_controller_defaults), flown in 50-step launches
             envb = make_env()
             envb.set_dp_controller(dp_controller_defaults(nominal))
-            sb = EV.baseline_box_test_streamed(envb, T=T, start=torch.zeros((3, nb), device=dev), chunk=50)
-            out('eval  box test (1250 steps, %d envs), %-13s: baseline PID + pseudo-inverse IAE %.2f (worst env %.2f)  work bow/port/star %s' % (
-                nb, tag, float(sb['iae'].mean()), float(sb['iae'].max()), [round(float(x), 1) for x in sb['work'].mean(0)]))
-            rb = {'IAE': float(sb['iae'].mean()), 'IAE_worst': float(sb['iae'].max()), 'work': [float(x) for x in sb['work'].mean(0)]}
+            sb = EV.baseline_box_test_streamed(envb, T=T, start=torch.zeros((3, nb), device=dev), chunk=50, wear=True)
+            out('eval  box test (1250 steps, %d envs), %-13s: baseline PID + pseudo-inverse IAE %.2f (worst env %.2f)  work bow/port/star %s%s' % (
+                nb, tag, float(sb['iae'].mean()), float(sb['iae'].max()), [round(float(x), 1) for x in sb['work'].mean(0)], iadc_text(sb)))
+            rb = {'IAE': float(sb['iae'].mean()), 'IAE_worst': float(sb['iae'].max()), 'work': [float(x) for x in sb['work'].mean(0)], **iadc_entries(sb)}
             if nn_net is not None:
                 # the supervised contender (--nn-allocator): the same PID with the fitted network in place of the pseudo-inverse; it touches
                 # no hull, so it flies the spreads of hulls too - on a handle made the same way, which draws the same hulls and currents
                 envn = make_env()
                 envn.set_dp_controller(dp_controller_defaults(nominal))
-                sn = EV.baseline_box_test_streamed(envn, T=T, start=torch.zeros((3, nb), device=dev), chunk=50, allocator='nn', net=nn_net)
-                out('eval  box test (1250 steps, %d envs), %-13s: baseline PID + neural allocation IAE %.2f (worst env %.2f)  work bow/port/star %s' % (
-                    nb, tag, float(sn['iae'].mean()), float(sn['iae'].max()), [round(float(x), 1) for x in sn['work'].mean(0)]))
-                rb['nn'] = {'IAE': float(sn['iae'].mean()), 'IAE_worst': float(sn['iae'].max()), 'work': [float(x) for x in sn['work'].mean(0)]}
+                sn = EV.baseline_box_test_streamed(envn, T=T, start=torch.zeros((3, nb), device=dev), chunk=50, allocator='nn', net=nn_net, wear=True)
+                out('eval  box test (1250 steps, %d envs), %-13s: baseline PID + neural allocation IAE %.2f (worst env %.2f)  work bow/port/star %s%s' % (
+                    nb, tag, float(sn['iae'].mean()), float(sn['iae'].max()), [round(float(x), 1) for x in sn['work'].mean(0)], iadc_text(sn)))
+                rb['nn'] = {'IAE': float(sn['iae'].mean()), 'IAE_worst': float(sn['iae'].max()), 'work': [float(x) for x in sn['work'].mean(0)],
+                            **iadc_entries(sn)}
                 del envn
             if spread > 0:
                 return rb                                                  # (the QP allocation flies the shared hull only: no per-env hull blocks)
             # the thesis' third contender: the same PID with the rate-limited QP allocation in place of the pseudo-inverse
             envb.set_qp_allocator(qp_allocator_defaults(nominal))
-            sq = EV.baseline_box_test_streamed(envb, T=T, start=torch.zeros((3, nb), device=dev), chunk=50, allocator='qp')
-            out('eval  box test (1250 steps, %d envs), %-13s: baseline PID + QP allocation IAE %.2f (worst env %.2f)  work bow/port/star %s' % (
-                nb, tag, float(sq['iae'].mean()), float(sq['iae'].max()), [round(float(x), 1) for x in sq['work'].mean(0)]))
-            rb['qp'] = {'IAE': float(sq['iae'].mean()), 'IAE_worst': float(sq['iae'].max()), 'work': [float(x) for x in sq['work'].mean(0)]}
+            sq = EV.baseline_box_test_streamed(envb, T=T, start=torch.zeros((3, nb), device=dev), chunk=50, allocator='qp', wear=True)
+            out('eval  box test (1250 steps, %d envs), %-13s: baseline PID + QP allocation IAE %.2f (worst env %.2f)  work bow/port/star %s%s' % (
+                nb, tag, float(sq['iae'].mean()), float(sq['iae'].max()), [round(float(x), 1) for x in sq['work'].mean(0)], iadc_text(sq)))
+            rb['qp'] = {'IAE': float(sq['iae'].mean()), 'IAE_worst': float(sq['iae'].max()), 'work': [float(x) for x in sq['work'].mean(0)],
+                        **iadc_entries(sq)}
             return rb
 
         env = make_env()
@@ -111,11 +123,12 @@ def evaluate_actor(ac, dev, preset, precision, seed, out=print, eval_envs=1024, 
         if nb != 1024:
             # any other batch: the same flight in 50-step launches through one re-used set of row blocks, scored on the device as it flies
             # (evaluate.ScoreCard: O(n) memory - 65 536 envs fit); the corner errors need the rows and are not reported
-            st = EV.deployment_box_test_streamed(env, T=T, chunk=50, integral=False, start=start)
+            st = EV.deployment_box_test_streamed(env, T=T, chunk=50, integral=False, start=start, wear=True)
             iae_tot, w, rps = st['iae'], st['work'], float(st['ret'].mean()) / T
-            out('eval  box test (1250 steps, %d envs, streamed), %-13s: IAE %.2f (worst env %.2f)  work bow/port/star %s  reward/step %.3f' % (
-                nb, tag, float(iae_tot.mean()), float(iae_tot.max()), [round(float(x), 1) for x in w.mean(0)], rps))
-            res[tag] = {'IAE': float(iae_tot.mean()), 'IAE_worst': float(iae_tot.max()), 'work': [float(x) for x in w.mean(0)], 'reward_per_step': rps}
+            out('eval  box test (1250 steps, %d envs, streamed), %-13s: IAE %.2f (worst env %.2f)  work bow/port/star %s%s  reward/step %.3f' % (
+                nb, tag, float(iae_tot.mean()), float(iae_tot.max()), [round(float(x), 1) for x in w.mean(0)], iadc_text(st), rps))
+            res[tag] = {'IAE': float(iae_tot.mean()), 'IAE_worst': float(iae_tot.max()), 'work': [float(x) for x in w.mean(0)], 'reward_per_step': rps,
+                        **iadc_entries(st)}
             del env
             res[tag]['baseline'] = baseline()
             continue
@@ -124,14 +137,15 @@ def evaluate_actor(ac, dev, preset, precision, seed, out=print, eval_envs=1024, 
         o = policy_rollout(env, T, noise=None, switch_steps=steps, refs=refs)
         iae_tot, _ = EV.iae(o['obs'])
         w = EV.work(EV.commanded_thrust(o['act']))
+        wear = EV.iadc(o['act'], env.variant, env.cont_ang)
         e = o['obs'][:, :, :3]
         k = [max(t - 1, 0) for t in list(steps)[1:] + [T - 1]]             # just before each switch: how close to the corner
         pos = torch.sqrt(e[k, :, 0] ** 2 + e[k, :, 1] ** 2)
-        out('eval  box test (1250 steps, %d envs), %-13s: IAE %.2f (worst env %.2f)  work bow/port/star %s  corner error %.2f m / %.1f deg (worst %.2f m)  reward/step %.3f' % (
-            nb, tag, float(iae_tot.mean()), float(iae_tot.max()), [round(float(x), 1) for x in w.mean(0)], float(pos.mean()),
+        out('eval  box test (1250 steps, %d envs), %-13s: IAE %.2f (worst env %.2f)  work bow/port/star %s%s  corner error %.2f m / %.1f deg (worst %.2f m)  reward/step %.3f' % (
+            nb, tag, float(iae_tot.mean()), float(iae_tot.max()), [round(float(x), 1) for x in w.mean(0)], iadc_text(wear), float(pos.mean()),
             float(torch.rad2deg(e[k, :, 2].abs().mean())), float(pos.max()), float(o['rew'].mean())))
         res[tag] = {'IAE': float(iae_tot.mean()), 'IAE_worst': float(iae_tot.max()), 'work': [float(x) for x in w.mean(0)],
-                    'corner_error_m': float(pos.mean()), 'reward_per_step': float(o['rew'].mean())}
+                    'corner_error_m': float(pos.mean()), 'reward_per_step': float(o['rew'].mean()), **iadc_entries(wear)}
         del env
         res[tag]['baseline'] = baseline()
     return res
@@ -148,16 +162,16 @@ def tune_baseline(ac, dev, preset, precision, K, seed=0, out=print, directions=1
     env = ml4ca_amd.BatchedRevoltEnv(n, device=dev, terminate=False, time_limit=False, seed=seed + 77, vessel_params=nominal, current=True)
     pop = gain_population(K, dp_controller_defaults(nominal), seed=seed)
     env.set_dp_controller(dp_controller_defaults(nominal))
-    sw = EV.baseline_gain_sweep(env, pop, directions=directions, vc=vc, reference_filter=True)
-    iae, work = sw['mean_iae'].cpu().numpy(), sw['mean_work'].cpu().numpy()
+    sw = EV.baseline_gain_sweep(env, pop, directions=directions, vc=vc, reference_filter=True, wear=True)
+    iae, work, wear = sw['mean_iae'].cpu().numpy(), sw['mean_work'].cpu().numpy(), sw['mean_iadc'].cpu().numpy()
     tot = work.sum(1)
     ac.upload(env, precision=precision)
-    sa = EV.deployment_box_test_streamed(env, chunk=50, integral=False, reference_filter=True)       # (the sweep left the currents set)
+    sa = EV.deployment_box_test_streamed(env, chunk=50, integral=False, reference_filter=True, wear=True)       # (the sweep left the currents set)
     a_iae, a_work = float(sa['iae'].mean()), sa['work'].mean(0).cpu().numpy()
-    row = lambda k: 'set %4d  IAE %.2f  work bow/port/star %s (total %.1f)  kp x %s  kd x %s  ki x %s' % (
-        k, iae[k], [round(float(x), 1) for x in work[k]], tot[k], *([round(float(x), 2) for x in pop['factors'][g][k]] for g in ('kp', 'kd', 'ki')))
+    row = lambda k: 'set %4d  IAE %.2f  work bow/port/star %s (total %.1f)  IADC %.2f  kp x %s  kd x %s  ki x %s' % (
+        k, iae[k], [round(float(x), 1) for x in work[k]], tot[k], wear[k], *([round(float(x), 2) for x in pop['factors'][g][k]] for g in ('kp', 'kd', 'ki')))
     out('tune  %d gain sets x %d directions of %.1f m/s, 1250-step box test behind the reference filter' % (K, directions, vc))
-    out('tune  actor (no integral action): IAE %.2f  work bow/port/star %s (total %.1f)' % (a_iae, [round(float(x), 1) for x in a_work], a_work.sum()))
+    out('tune  actor (no integral action): IAE %.2f  work bow/port/star %s (total %.1f)%s' % (a_iae, [round(float(x), 1) for x in a_work], a_work.sum(), iadc_text(sa)))
     out('tune  default baseline : ' + row(0))
     out('tune  front (%d of %d sets, by IAE):' % (len(sw['front']), K))
     for k in sw['front']:
@@ -169,7 +183,9 @@ def tune_baseline(ac, dev, preset, precision, K, seed=0, out=print, directions=1
         out('tune  lowest IAE at no more than the actor\'s work: ' + row(min(fair, key=lambda k: iae[k])))
     else:
         out('tune  no gain set spends as little work as the actor (the least: ' + row(int(tot.argmin())) + ')')
-    return {'mean_iae': iae.tolist(), 'mean_work': work.tolist(), 'front': [int(k) for k in sw['front']], 'actor': {'IAE': a_iae, 'work': a_work.tolist()}}
+    out('tune  front on IAE, work and IADC: %d of %d sets' % (len(sw['front3']), K))
+    return {'mean_iae': iae.tolist(), 'mean_work': work.tolist(), 'mean_iadc': wear.tolist(), 'front': [int(k) for k in sw['front']],
+            'front3': [int(k) for k in sw['front3']], 'actor': {'IAE': a_iae, 'work': a_work.tolist(), **iadc_entries(sa)}}
 
 
 def tune_qp(dev, preset, K, seed=0, out=print, directions=16, vc=0.2):
@@ -183,12 +199,12 @@ def tune_qp(dev, preset, K, seed=0, out=print, directions=16, vc=0.2):
     env = ml4ca_amd.BatchedRevoltEnv(n, device=dev, terminate=False, time_limit=False, seed=seed + 77, vessel_params=nominal, current=True)
     pop = qp_weight_population(K, qp_allocator_defaults(nominal), seed=seed)
     env.set_dp_controller(dp_controller_defaults(nominal))
-    sw = EV.qp_weight_sweep(env, pop, directions=directions, vc=vc, reference_filter=True)
-    iae, work = sw['mean_iae'].cpu().numpy(), sw['mean_work'].cpu().numpy()
+    sw = EV.qp_weight_sweep(env, pop, directions=directions, vc=vc, reference_filter=True, wear=True)
+    iae, work, wear = sw['mean_iae'].cpu().numpy(), sw['mean_work'].cpu().numpy(), sw['mean_iadc'].cpu().numpy()
     tot = work.sum(1)
     names = ('w_power', 'w_dalpha', 'w_dforce')
-    row = lambda k: 'set %4d  IAE %.2f  work bow/port/star %s (total %.1f)  %s' % (
-        k, iae[k], [round(float(x), 1) for x in work[k]], tot[k], '  '.join('%s x %.2f' % (g, float(pop['factors'][g][k])) for g in names))
+    row = lambda k: 'set %4d  IAE %.2f  work bow/port/star %s (total %.1f)  IADC %.2f  %s' % (
+        k, iae[k], [round(float(x), 1) for x in work[k]], tot[k], wear[k], '  '.join('%s x %.2f' % (g, float(pop['factors'][g][k])) for g in names))
     out('tuneqp  %d QP weight sets x %d directions of %.1f m/s, 1250-step box test behind the reference filter' % (K, directions, vc))
     out('tuneqp  default QP       : ' + row(0))
     out('tuneqp  front (%d of %d sets, by IAE):' % (len(sw['front']), K))
@@ -196,7 +212,10 @@ def tune_qp(dev, preset, K, seed=0, out=print, directions=16, vc=0.2):
         out('tuneqp      ' + row(int(k)))
     out('tuneqp  lowest IAE       : ' + row(int(iae.argmin())))
     out('tuneqp  least work       : ' + row(int(tot.argmin())))
-    return {'mean_iae': iae.tolist(), 'mean_work': work.tolist(), 'front': [int(k) for k in sw['front']]}
+    out('tuneqp  least wear       : ' + row(int(wear.argmin())))
+    out('tuneqp  front on IAE, work and IADC: %d of %d sets' % (len(sw['front3']), K))
+    return {'mean_iae': iae.tolist(), 'mean_work': work.tolist(), 'mean_iadc': wear.tolist(), 'front': [int(k) for k in sw['front']],
+            'front3': [int(k) for k in sw['front3']]}
 
 
 def nn_w_power_grid(K):
@@ -229,7 +248,7 @@ def tune_nn(args, dev, preset, K, seed=0, out=print, directions=16, vc=0.2):
     env = mk(64 * K)
     env.set_dp_controller(dp_controller_defaults(nominal))
     t0 = time.perf_counter()
-    sw = EV.nn_allocator_sweep(env, nets, directions=directions, vc=vc, reference_filter=True)
+    sw = EV.nn_allocator_sweep(env, nets, directions=directions, vc=vc, reference_filter=True, wear=True)
     torch.cuda.synchronize()
     t_sweep = time.perf_counter() - t0
     one = mk(64)
@@ -241,10 +260,10 @@ def tune_nn(args, dev, preset, K, seed=0, out=print, directions=16, vc=0.2):
     t_seq = time.perf_counter() - t0
     same = all(torch.equal(sw['env_iae'][64 * k:64 * k + 64], r['iae']) and torch.equal(sw['env_work'][64 * k:64 * k + 64], r['work'])
                for k, r in enumerate(seq))
-    iae, work = sw['mean_iae'].cpu().numpy(), sw['mean_work'].cpu().numpy()
+    iae, work, wear = sw['mean_iae'].cpu().numpy(), sw['mean_work'].cpu().numpy(), sw['mean_iadc'].cpu().numpy()
     tot = work.sum(1)
-    row = lambda k: 'net %4d  w_power %-8.4g IAE %.2f  work bow/port/star %s (total %.1f)  wrench residual Js %.4g N^2' % (
-        k, grid[k], iae[k], [round(float(x), 1) for x in work[k]], tot[k], nets[k]['wrench_ms_final'])
+    row = lambda k: 'net %4d  w_power %-8.4g IAE %.2f  work bow/port/star %s (total %.1f)  IADC %.2f  wrench residual Js %.4g N^2' % (
+        k, grid[k], iae[k], [round(float(x), 1) for x in work[k]], tot[k], wear[k], nets[k]['wrench_ms_final'])
     out('tunenn  %d networks (9-80-80-80-6, wrench loss, %d Adam steps each: %.1f s) x %d directions of %.1f m/s x 4 envs, 1250-step box test behind '
         'the reference filter' % (K, iters, t_fit, directions, vc))
     out('tunenn  w_power grid: %s' % ', '.join('%.4g' % w for w in grid))
@@ -255,8 +274,9 @@ def tune_nn(args, dev, preset, K, seed=0, out=print, directions=16, vc=0.2):
     out('tunenn  front (%d of %d networks, by IAE):' % (len(sw['front']), K))
     for k in sw['front']:
         out('tunenn      ' + row(int(k)))
-    return {'w_power': grid, 'mean_iae': iae.tolist(), 'mean_work': work.tolist(), 'front': [int(k) for k in sw['front']],
-            'seconds': {'fit': t_fit, 'sweep': t_sweep, 'sequential': t_seq}, 'same': same}
+    out('tunenn  front on IAE, work and IADC: %d of %d networks' % (len(sw['front3']), K))
+    return {'w_power': grid, 'mean_iae': iae.tolist(), 'mean_work': work.tolist(), 'mean_iadc': wear.tolist(), 'front': [int(k) for k in sw['front']],
+            'front3': [int(k) for k in sw['front3']], 'seconds': {'fit': t_fit, 'sweep': t_sweep, 'sequential': t_seq}, 'same': same}
 
 
 def warm_start(upd, env, args, out=print):
@@ -317,9 +337,10 @@ def nn_score_card(nn_net, dev, preset, seed, nb, tag, out=print):
         if cur:
             env.set_current(torch.full((nb,), 0.2, device=dev), torch.full((nb,), 2.35619, device=dev))
         env.set_dp_controller(dp_controller_defaults(nominal))
-        sn = EV.baseline_box_test_streamed(env, T=1250, start=torch.zeros((3, nb), device=dev), chunk=50, allocator='nn', net=nn_net)
-        out('eval  box test (1250 steps, %d envs), %s, %s: baseline PID + neural allocation IAE %.2f (worst env %.2f)  work bow/port/star %s (total %.1f)' % (
-            nb, tag, name, float(sn['iae'].mean()), float(sn['iae'].max()), [round(float(x), 1) for x in sn['work'].mean(0)], float(sn['work'].mean(0).sum())))
+        sn = EV.baseline_box_test_streamed(env, T=1250, start=torch.zeros((3, nb), device=dev), chunk=50, allocator='nn', net=nn_net, wear=True)
+        out('eval  box test (1250 steps, %d envs), %s, %s: baseline PID + neural allocation IAE %.2f (worst env %.2f)  work bow/port/star %s (total %.1f)%s' % (
+            nb, tag, name, float(sn['iae'].mean()), float(sn['iae'].max()), [round(float(x), 1) for x in sn['work'].mean(0)], float(sn['work'].mean(0).sum()),
+            iadc_text(sn)))
         del env
 
 

@@ -637,6 +637,67 @@ int dpenv_score_read(const void* state, int32_t n, double* out, dpenv_stream s);
 int64_t dpenv_score_summary_workspace_bytes(int32_t n);
 int dpenv_score_summary(const void* state, int32_t n, double* out, void* workspace, dpenv_stream s);
 
+/* ---- the score card's wear axis: IADC, the integral absolute derivative of the commands (additive to ABI 6) -----------------------------
+ * The thesis' third axis beside IAE and W* (results/all_plots/box_test/plot_act.py:320-391): how much the thrust and azimuth commands
+ * move.  dpenv_score_accumulate_wear is dpenv_score_accumulate - the score state ends up the same, bit for bit - with a second
+ * caller-owned state beside it, in ONE pass over the rows: a scored flight reads its act rows once.
+ *
+ * The commands.  Per env i and row t, the commands the env itself decodes from the action row:
+ *     n_j, j = bow, port, star, in percent:  fminf(fmaxf(act[t][i][j]*100, -100), 100)                  (the score card's own expression)
+ *     alpha_k, k = port, star, in radians:  the variant's command decode (customEnv.py:104-122, 215-244; the step kernels' own function):
+ *         FULL                    act[4], act[5] times pi_f, clipped to +-pi_f                           (pi_f = (float)pi)
+ *         LIMITED                 act[3], act[4] times pi_f/2, clipped to +-pi_f/2
+ *         FINAL without cont_ang  w = a - 2 floorf((a + 1) * 0.5f) for a = act[3], act[4]; w * pi_f, clipped to +-pi_f     (the wrap form)
+ *         FINAL with cont_ang     atan2(act[3], act[4]), atan2(act[5], act[6]), clipped to +-pi_f; atan2 is the kernels' own, max abs
+ *                                 error 2.6e-7, signed zeros kept ((+-0, -x) gives +-pi)
+ *         SIMPLE                  commands no azimuth: alpha_k = 0, its angle term is 0
+ *     The bow azimuth is not counted, as in the reference (plot_act.py:334, "no action from the angle of the bow thruster").
+ *
+ * Per-row update.  With a previous sample (n', alpha') of the same episode, in f32, in exactly this order (the build has -ffp-contract=off;
+ * / is correctly rounded):
+ *     d_n = ((|n_0 - n_0'| + |n_1 - n_1'|) + |n_2 - n_2'|) / 100
+ *     w_k = fminf(|alpha_k - alpha_k'|, 2pi_f - |alpha_k - alpha_k'|)      (2pi_f = 2 * (float)pi; both angles are clipped to +-pi_f, so w_k >= 0)
+ *     d_a = (w_1 + w_2) / pi_f
+ *     iadc_rps += (double)d_n ;  iadc_angle += (double)d_a
+ * then (n', alpha') = (n, alpha), has_prev = 1, and behind a row that ends the episode (dpenv_score_accumulate's rule: any non-zero done
+ * byte, or cut_at_end on row T-1) closed += open, open = 0, has_prev = 0.  IADC = iadc_rps + iadc_angle, added in f64 at read time.
+ * The first sample of an episode contributes nothing - the reset's own command is not a previous sample - and nothing bridges an episode
+ * end.  On the env's uniform grid the reference's (|delta|/dt/scale)*dt is |delta|/scale: the law has no dt.  The reference's per-interval
+ * clip to [0, 400] (plot_act.py:385) cannot act - an interval is at most 3*2 + 2*1 = 8 - and is not built; its re-use of the previous entry
+ * for intervals under 0.1 s (:336-339, :358-363) never fires on a 0.2 s grid and lives in the host's series function only
+ * (evaluate.iadc_series).
+ *
+ * Non-finite actions.  The law is stated for finite actions.  fmaxf / fminf return their other operand when one is NaN, so every clip above
+ * returns a bound for a NaN: a NaN thrust entry reads as -100 %, +-Inf as +-100 %; a NaN or Inf azimuth entry (or head: atan2 of a NaN or
+ * of two infinities is a NaN or some finite angle) reads as some angle within the clip, -pi_f (-pi_f/2 for LIMITED) where the decode's
+ * result is a NaN.  The commands, and so both sums, stay finite whatever the row holds; lanes never read one another's rows, so a
+ * non-finite row changes nothing of any other env.
+ *
+ * Wear state.  One per env, caller-owned, dpenv_score_wear_state_bytes(n) bytes (64 per env; 0 for n < 1), 16-byte aligned, all-zero bytes
+ * = fresh (a memset resets it, like the score state): open and closed iadc_rps / iadc_angle in f64, the previous n[3] and alpha[2] in f32,
+ * and a has_prev flag of its own - a fresh wear state joined to a score state in mid-episode counts nothing for its first row instead of
+ * differencing against zeros.  dpenv_score_state_bytes and the 128-byte score state are what they were. */
+enum { DPENV_SCORE_WEAR_RPS = 0, DPENV_SCORE_WEAR_ANGLE = 1,             /* the open episode */
+       DPENV_SCORE_WEAR_EP_RPS = 2, DPENV_SCORE_WEAR_EP_ANGLE = 3,       /* closed episodes, summed */
+       DPENV_SCORE_WEAR_NOUT = 4 };
+typedef struct dpenv_score_wear_io {
+    uint32_t struct_size;    /* sizeof(dpenv_score_wear_io), ABI check */
+    int32_t variant;         /* DPENV_FULL .. DPENV_FINAL: whose command decode the azimuths take */
+    int32_t cont_ang;        /* FINAL only: the rows carry sin / cos heads (7 columns) */
+} dpenv_score_wear_io;
+int64_t dpenv_score_wear_state_bytes(int32_t n);     /* 0 for n < 1 */
+/* One pass over the block: the score state as dpenv_score_accumulate leaves it, the wear state by the law above.  Refused on the host,
+ * before any device call, with the field named: everything dpenv_score_accumulate refuses; wear NULL or not 16-byte aligned; wio NULL or
+ * of another struct_size; a variant outside the enum; cont_ang on a variant other than FINAL; io->act NULL; io->act_stride below the
+ * variant's dpenv_act_dim (6 / 3 / 5 / 5, 7 with cont_ang). */
+int dpenv_score_accumulate_wear(void* state, void* wear, const dpenv_score_io* io, const dpenv_score_wear_io* wio, dpenv_stream s);
+/* out: device double[DPENV_SCORE_WEAR_NOUT][n], slot DPENV_SCORE_WEAR_* of every env. */
+int dpenv_score_wear_read(const void* wear, int32_t n, double* out, dpenv_stream s);
+/* out: device double[DPENV_SCORE_WEAR_NOUT][3] = sum, min, max over the envs of each wear slot, with dpenv_score_summary's fixed two-stage
+ * pairing.  workspace: dpenv_score_wear_summary_workspace_bytes(n) bytes of device memory. */
+int64_t dpenv_score_wear_summary_workspace_bytes(int32_t n);
+int dpenv_score_wear_summary(const void* wear, int32_t n, double* out, void* workspace, dpenv_stream s);
+
 /* ---- the classical baseline in the closed loop: a PID motion controller feeding a pseudo-inverse thrust allocation (additive to ABI 6) --
  * The thesis compares the RL allocator with the classical chain; the reference tree has neither its PID nor its pseudo-inverse node, so the
  * law is build-defined, like the plant.  While it is on, dpenv_controller_rollout flies it per env and per control step on the observation

@@ -137,6 +137,10 @@ class ScoreIO(C.Structure):
                 ('rps_max', C.c_float * 3), ('cut_at_end', C.c_int32)]
 
 
+class ScoreWearIO(C.Structure):
+    _fields_ = [('struct_size', C.c_uint32), ('variant', C.c_int32), ('cont_ang', C.c_int32)]
+
+
 class TrainShape(C.Structure):
     _fields_ = [('struct_size', C.c_uint32), ('n_layers', C.c_int32), ('sizes', C.c_int32 * 6), ('activation', C.c_int32),
                 ('leak', C.c_float), ('row_dtype', C.c_int32), ('log_std', C.c_int32)]
@@ -150,6 +154,9 @@ class AllocLoss(C.Structure):
 
 # read slots of the score card (dpenv.h DPENV_SCORE_*)
 SCORE_IAE, SCORE_WORK, SCORE_RET, SCORE_LEN, SCORE_EPISODES, SCORE_EP_IAE, SCORE_EP_WORK, SCORE_EP_RET, SCORE_EP_LEN, SCORE_NOUT = 0, 1, 4, 5, 6, 7, 8, 11, 12, 13
+
+# read slots of its wear axis (dpenv.h DPENV_SCORE_WEAR_*)
+SCORE_WEAR_RPS, SCORE_WEAR_ANGLE, SCORE_WEAR_EP_RPS, SCORE_WEAR_EP_ANGLE, SCORE_WEAR_NOUT = 0, 1, 2, 3, 4
 
 
 # every symbol include/dpenv.h declares: name -> (restype, argtypes)
@@ -216,6 +223,11 @@ SYMBOLS = {
     'dpenv_score_read': (C.c_int, [_VP, _I32, _VP, _VP]),
     'dpenv_score_summary_workspace_bytes': (C.c_int64, [_I32]),
     'dpenv_score_summary': (C.c_int, [_VP, _I32, _VP, _VP, _VP]),
+    'dpenv_score_wear_state_bytes': (C.c_int64, [_I32]),
+    'dpenv_score_accumulate_wear': (C.c_int, [_VP, _VP, C.POINTER(ScoreIO), C.POINTER(ScoreWearIO), _VP]),
+    'dpenv_score_wear_read': (C.c_int, [_VP, _I32, _VP, _VP]),
+    'dpenv_score_wear_summary_workspace_bytes': (C.c_int64, [_I32]),
+    'dpenv_score_wear_summary': (C.c_int, [_VP, _I32, _VP, _VP, _VP]),
     'dpenv_dp_allocation_matrix': (C.c_int, [C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float * 3 * 5)]),
     'dpenv_set_dp_controller': (C.c_int, [_VP, C.POINTER(DPController), _VP]),
     'dpenv_get_dp_controller_state': (C.c_int, [_VP, _VP, _VP]),

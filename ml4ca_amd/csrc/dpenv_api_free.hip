@@ -532,34 +532,90 @@ extern "C" int dpenv_score_default_io(dpenv_score_io* io)
     return DPENV_OK;
 }
 
-extern "C" int dpenv_score_accumulate(void* state, const dpenv_score_io* io, dpenv_stream s)
+// what dpenv_score_accumulate and dpenv_score_accumulate_wear both refuse (who: the entry point named in the message), then the kernel's arguments
+static int score_check(const char* who, void* state, const dpenv_score_io* io, ScoreArgs* a)
 {
-    if (!io) return fail(nullptr, DPENV_EINVAL, "dpenv_score_accumulate: io is NULL");
+    if (!io) return fail(nullptr, DPENV_EINVAL, "%s: io is NULL", who);
     if (io->struct_size != sizeof(dpenv_score_io))
-        return fail(nullptr, DPENV_EINVAL, "dpenv_score_accumulate: struct_size %u != %zu", io->struct_size, sizeof(dpenv_score_io));
-    if (io->T < 1) return fail(nullptr, DPENV_EINVAL, "dpenv_score_accumulate: T = %d, must be >= 1", io->T);
-    if (io->n < 1) return fail(nullptr, DPENV_EINVAL, "dpenv_score_accumulate: n = %d, must be >= 1", io->n);
-    if (!state) return fail(nullptr, DPENV_EINVAL, "dpenv_score_accumulate: state is NULL");
-    if (reinterpret_cast<uintptr_t>(state) & 15u) return fail(nullptr, DPENV_EINVAL, "dpenv_score_accumulate: state must be 16-byte aligned");
+        return fail(nullptr, DPENV_EINVAL, "%s: struct_size %u != %zu", who, io->struct_size, sizeof(dpenv_score_io));
+    if (io->T < 1) return fail(nullptr, DPENV_EINVAL, "%s: T = %d, must be >= 1", who, io->T);
+    if (io->n < 1) return fail(nullptr, DPENV_EINVAL, "%s: n = %d, must be >= 1", who, io->n);
+    if (!state) return fail(nullptr, DPENV_EINVAL, "%s: state is NULL", who);
+    if (reinterpret_cast<uintptr_t>(state) & 15u) return fail(nullptr, DPENV_EINVAL, "%s: state must be 16-byte aligned", who);
     if (io->obs_dtype != DPENV_F32 && io->obs_dtype != DPENV_BF16)
-        return fail(nullptr, DPENV_EINVAL, "dpenv_score_accumulate: obs_dtype %d is neither DPENV_F32 nor DPENV_BF16", io->obs_dtype);
-    if (io->obs && io->obs_stride < 3) return fail(nullptr, DPENV_EINVAL, "dpenv_score_accumulate: obs_stride = %d, must be >= 3", io->obs_stride);
-    if (io->act && io->act_stride < 3) return fail(nullptr, DPENV_EINVAL, "dpenv_score_accumulate: act_stride = %d, must be >= 3", io->act_stride);
-    if (io->integ && !io->obs) return fail(nullptr, DPENV_EINVAL, "dpenv_score_accumulate: integ needs obs");
-    if (!std::isfinite(io->dt) || !(io->dt > 0.0f)) return fail(nullptr, DPENV_EINVAL, "dpenv_score_accumulate: dt must be finite and > 0");
+        return fail(nullptr, DPENV_EINVAL, "%s: obs_dtype %d is neither DPENV_F32 nor DPENV_BF16", who, io->obs_dtype);
+    if (io->obs && io->obs_stride < 3) return fail(nullptr, DPENV_EINVAL, "%s: obs_stride = %d, must be >= 3", who, io->obs_stride);
+    if (io->act && io->act_stride < 3) return fail(nullptr, DPENV_EINVAL, "%s: act_stride = %d, must be >= 3", who, io->act_stride);
+    if (io->integ && !io->obs) return fail(nullptr, DPENV_EINVAL, "%s: integ needs obs", who);
+    if (!std::isfinite(io->dt) || !(io->dt > 0.0f)) return fail(nullptr, DPENV_EINVAL, "%s: dt must be finite and > 0", who);
     for (int j = 0; j < 3; ++j) {
         if (!std::isfinite(io->norm[j]) || !(io->norm[j] > 0.0f))
-            return fail(nullptr, DPENV_EINVAL, "dpenv_score_accumulate: norm[%d] must be finite and > 0", j);
-        if (!std::isfinite(io->power_coeff[j])) return fail(nullptr, DPENV_EINVAL, "dpenv_score_accumulate: power_coeff[%d] is not finite", j);
-        if (!std::isfinite(io->rps_max[j])) return fail(nullptr, DPENV_EINVAL, "dpenv_score_accumulate: rps_max[%d] is not finite", j);
+            return fail(nullptr, DPENV_EINVAL, "%s: norm[%d] must be finite and > 0", who, j);
+        if (!std::isfinite(io->power_coeff[j])) return fail(nullptr, DPENV_EINVAL, "%s: power_coeff[%d] is not finite", who, j);
+        if (!std::isfinite(io->rps_max[j])) return fail(nullptr, DPENV_EINVAL, "%s: rps_max[%d] is not finite", who, j);
     }
+    a->state = (uint4*)state;
+    a->obs = io->obs; a->act = io->act; a->rew = io->rew; a->done = io->done; a->integ = io->integ;
+    a->T = io->T; a->n = io->n; a->obs_stride = io->obs_stride; a->act_stride = io->act_stride; a->cut_at_end = io->cut_at_end ? 1 : 0;
+    a->dt = io->dt;
+    for (int j = 0; j < 3; ++j) { a->norm[j] = io->norm[j]; a->coeff[j] = io->power_coeff[j]; a->rps[j] = io->rps_max[j]; }
+    return DPENV_OK;
+}
+
+extern "C" int dpenv_score_accumulate(void* state, const dpenv_score_io* io, dpenv_stream s)
+{
     ScoreArgs a;
-    a.state = (uint4*)state;
-    a.obs = io->obs; a.act = io->act; a.rew = io->rew; a.done = io->done; a.integ = io->integ;
-    a.T = io->T; a.n = io->n; a.obs_stride = io->obs_stride; a.act_stride = io->act_stride; a.cut_at_end = io->cut_at_end ? 1 : 0;
-    a.dt = io->dt;
-    for (int j = 0; j < 3; ++j) { a.norm[j] = io->norm[j]; a.coeff[j] = io->power_coeff[j]; a.rps[j] = io->rps_max[j]; }
+    if (int rc = score_check("dpenv_score_accumulate", state, io, &a)) return rc;
     HIP_TRY(nullptr, dev::launch_score(&a, io->obs_dtype == DPENV_BF16, (hipStream_t)s));
+    return DPENV_OK;
+}
+
+// ---- the wear axis (dpenv.h: dpenv_score_accumulate_wear, dpenv_score_wear_*): IADC beside the score state, one pass over the rows ----
+extern "C" int64_t dpenv_score_wear_state_bytes(int32_t n) { return n > 0 ? dev::score_wear_state_bytes(n) : 0; }
+
+extern "C" int64_t dpenv_score_wear_summary_workspace_bytes(int32_t n) { return n > 0 ? dev::score_wear_summary_workspace_bytes(n) : 0; }
+
+extern "C" int dpenv_score_accumulate_wear(void* state, void* wear, const dpenv_score_io* io, const dpenv_score_wear_io* wio, dpenv_stream s)
+{
+    static const char* who = "dpenv_score_accumulate_wear";
+    ScoreArgs a;
+    if (int rc = score_check(who, state, io, &a)) return rc;
+    if (!wear) return fail(nullptr, DPENV_EINVAL, "%s: wear is NULL", who);
+    if (reinterpret_cast<uintptr_t>(wear) & 15u) return fail(nullptr, DPENV_EINVAL, "%s: wear must be 16-byte aligned", who);
+    if (!wio) return fail(nullptr, DPENV_EINVAL, "%s: wio is NULL", who);
+    if (wio->struct_size != sizeof(dpenv_score_wear_io))
+        return fail(nullptr, DPENV_EINVAL, "%s: wio struct_size %u != %zu", who, wio->struct_size, sizeof(dpenv_score_wear_io));
+    dpenv_config cfg;
+    std::memset(&cfg, 0, sizeof cfg);
+    cfg.variant = wio->variant; cfg.cont_ang = wio->cont_ang;
+    const int mode = mode_of(&cfg);
+    if (mode < 0) return fail(nullptr, DPENV_EINVAL, "%s: variant %d is none of DPENV_FULL .. DPENV_FINAL", who, wio->variant);
+    if (wio->cont_ang && wio->variant != DPENV_FINAL)
+        return fail(nullptr, DPENV_EINVAL, "%s: cont_ang is only defined for the final variant", who);
+    if (!io->act) return fail(nullptr, DPENV_EINVAL, "%s: act is NULL (the wear axis is taken on the action rows)", who);
+    const int ad = dpenv_act_dim(&cfg);
+    if (io->act_stride < ad)
+        return fail(nullptr, DPENV_EINVAL, "%s: act_stride = %d, must be >= %d (the variant's dpenv_act_dim)", who, io->act_stride, ad);
+    HIP_TRY(nullptr, dev::launch_score_wear(&a, wear, io->obs_dtype == DPENV_BF16, mode, (hipStream_t)s));
+    return DPENV_OK;
+}
+
+extern "C" int dpenv_score_wear_read(const void* wear, int32_t n, double* out, dpenv_stream s)
+{
+    if (n < 1) return fail(nullptr, DPENV_EINVAL, "dpenv_score_wear_read: n = %d, must be >= 1", n);
+    if (!wear || (reinterpret_cast<uintptr_t>(wear) & 15u)) return fail(nullptr, DPENV_EINVAL, "dpenv_score_wear_read: wear is NULL or not 16-byte aligned");
+    if (!out) return fail(nullptr, DPENV_EINVAL, "dpenv_score_wear_read: out is NULL");
+    HIP_TRY(nullptr, dev::launch_score_wear_read(wear, n, out, (hipStream_t)s));
+    return DPENV_OK;
+}
+
+extern "C" int dpenv_score_wear_summary(const void* wear, int32_t n, double* out, void* workspace, dpenv_stream s)
+{
+    if (n < 1) return fail(nullptr, DPENV_EINVAL, "dpenv_score_wear_summary: n = %d, must be >= 1", n);
+    if (!wear || (reinterpret_cast<uintptr_t>(wear) & 15u)) return fail(nullptr, DPENV_EINVAL, "dpenv_score_wear_summary: wear is NULL or not 16-byte aligned");
+    if (!out) return fail(nullptr, DPENV_EINVAL, "dpenv_score_wear_summary: out is NULL");
+    if (!workspace) return fail(nullptr, DPENV_EINVAL, "dpenv_score_wear_summary: workspace is NULL (dpenv_score_wear_summary_workspace_bytes)");
+    HIP_TRY(nullptr, dev::launch_score_wear_summary(wear, n, out, (double*)workspace, (hipStream_t)s));
     return DPENV_OK;
 }
 

@@ -479,7 +479,7 @@ inline bool control_ves_ok(int ves, const StepArgs* a)
 // for the two split arithmetics, all exact and exact actor - not f16 (dpenv_policy_ws.h has the measurements)
 constexpr int ws_roles(int prec, int groups) { return (groups == 2 && prec != PREC_F16) ? 3 : 2; }
 
-// ---- the streaming score card (dpenv_score_*; kernels in dpenv_score_dev.h): the arguments of one accumulate call ----
+// ---- the streaming score card (dpenv_score_*; kernels in dpenv_score_dev.h and dpenv_score_wear.hip): the arguments of one accumulate call ----
 struct ScoreArgs {
     uint4* state;
     const void* obs;            // [T][n][obs_stride] f32 or bf16, columns 0..2 read
@@ -561,6 +561,13 @@ int64_t score_summary_workspace_bytes(int n);
 hipError_t launch_score(const ScoreArgs* a, int obs_bf16, hipStream_t s);
 hipError_t launch_score_read(const void* state, int n, double* out, hipStream_t s);
 hipError_t launch_score_summary(const void* state, int n, double* out, double* workspace, hipStream_t s);
+// dpenv_score_wear.hip: the score scan with the wear state (IADC) beside the score state, one pass over the rows (mode: MODE_* of the
+// variant whose command decode the azimuths take; a->act must not be NULL), the [4][n] read-out and the two-stage summary of the wear slots
+int64_t score_wear_state_bytes(int n);
+int64_t score_wear_summary_workspace_bytes(int n);
+hipError_t launch_score_wear(const ScoreArgs* a, void* wear, int obs_bf16, int mode, hipStream_t s);
+hipError_t launch_score_wear_read(const void* wear, int n, double* out, hipStream_t s);
+hipError_t launch_score_wear_summary(const void* wear, int n, double* out, double* workspace, hipStream_t s);
 hipError_t launch_sum(const float* x, int64_t count, const float* mean, float* out, hipStream_t s);
 hipError_t launch_adv_apply(float* x, int64_t count, const float* mean, const float* std, const double* stats, double total_count,
                             hipStream_t s);

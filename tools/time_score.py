@@ -3,12 +3,13 @@
 launch by launch, medians of 20.
 
   block   65 536 envs x 50-row blocks, resident (f32 obs 9, act 7, integ, rew, done): A = ScoreCard.add, B = the host-composed way to the
-          same numbers from the same blocks: evaluate.iae(obs - integ) + evaluate.work(commanded_thrust(act)) + rew.sum(0).
+          same numbers from the same blocks: evaluate.iae(obs - integ) + evaluate.work(commanded_thrust(act)) + rew.sum(0); then the
+          one-pass score + wear call (ScoreCard(wear=).add) for three variants beside A, and A on the act rows alone.
   flight  the 1 250-step box test at 16 384 envs (f16 actor, integral action + reference filter): streamed in 50-step launches against the
           one-piece deployment_box_test - wall time including the scoring, peak allocated memory, and the adds' share of the streamed flight;
           then the streamed flight alone at 65 536 envs (one piece there is the 8.6 GB of rows the card exists to avoid: not run).
 
-Usage: python tools/time_score.py [--out profiles/score_card_timing.txt] [--envs 65536] [--flight-envs 16384]"""
+Usage: python tools/time_score.py [--out profiles/score_card_timing.txt] [--envs 65536] [--flight-envs 16384] [--block-only]"""
 import argparse
 import os
 import statistics
@@ -68,6 +69,16 @@ def block_cost(n, T, dev, out):
     blk_bf = dict(blk, obs=blk['obs'].to(torch.bfloat16))
     c, d = median_us([lambda: sc.add(blk_bf), lambda: sc.add(dict(obs=blk['obs'], rew=blk['rew']))])
     out('  A with bf16 obs rows: %.1f us;  A with obs and rew alone: %.1f us' % (c, d))
+    # the one-pass call (dpenv_score_accumulate_wear: score + IADC, the act fetch widened to the variant's columns) beside A, from the same run
+    wear_row = {'final cont_ang (7 columns)': ROW_BYTES + 16, 'final (5 columns)': ROW_BYTES + 8, 'simple (3 columns)': ROW_BYTES}
+    cards = [EV.ScoreCard(n, dev, wear=w) for w in (dict(variant='final', cont_ang=True), dict(variant='final', cont_ang=False), dict(variant='simple'))]
+    t = median_us([arm_a] + [lambda c=c: c.add(blk) for c in cards])
+    out('  one pass, score + wear (score_wear_kernel; 64 B of wear state per env beside the 128 B), against A = %.1f us in the same alternation:' % t[0])
+    for (name, rb), us in zip(wear_row.items(), t[1:]):
+        out('    %-28s %8.1f us  x %.3f of A  %7.1f GB/s at %d B per env-step' % (name, us, us / t[0], rows * rb / us / 1e3, rb))
+    # the alternative: A, then a second full pass over the act rows (here: A on the act rows alone, what a separate wear kernel would at least read)
+    e, = median_us([lambda: sc.add(dict(act=blk['act']))])
+    out('  A on the act rows alone (the least a separate wear pass would cost): %.1f us; A + that = %.1f us' % (e, t[0] + e))
     return a
 
 
@@ -123,6 +134,7 @@ def main():
     ap.add_argument('--out', default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'profiles', 'score_card_timing.txt'))
     ap.add_argument('--envs', type=int, default=65536)
     ap.add_argument('--flight-envs', type=int, default=16384)
+    ap.add_argument('--block-only', action='store_true', help='the block costs alone, no flights')
     args = ap.parse_args()
     dev = torch.device('cuda', 0)
     lines = []
@@ -133,8 +145,9 @@ def main():
 
     out('tools/time_score.py on %s' % torch.cuda.get_device_name(dev))
     block_cost(args.envs, 50, dev, out)
-    flight(args.flight_envs, dev, out, one_piece=True)
-    flight(args.envs, dev, out, one_piece=False)
+    if not args.block_only:
+        flight(args.flight_envs, dev, out, one_piece=True)
+        flight(args.envs, dev, out, one_piece=False)
     with open(args.out, 'w') as f:
         f.write('\n'.join(lines) + '\n')
 

@@ -1247,6 +1247,9 @@ int dpenv_controller_label_qp_ex(dpenv_handle h, const dpenv_controller_label_qp
  * GRADIENT RULE.  dL/dlogp = -A ratio / count  if  s1 <= s2,  else 0.  s1 < s2 is the unclipped term being the minimum (also with the
  * ratio outside the bounds, when the advantage pulls it back); s1 == s2 happens where A == 0 or 1 - clip <= ratio <= 1 + clip, bounds
  * INCLUDED, and there torch.minimum's half-and-half tie split and torch.clamp's inclusive bounds add up to the same -A ratio / count.
+ * A ratio outside float32's range is taken as float32 forms it: exp underflows to 0 (the row's gradient is zero for either sign of A)
+ * or overflows to +inf, where A > 0 is cut (zero gradient, the row's loss -(1 + clip) A, mean_ratio +inf) and A < 0 is non-finite by
+ * the law itself, as it is in torch float32 - such rows are the caller's to keep out.
  *     dlogp/dmu_j = q_j / sd_j        dlogp/dlog_std_j = q_j^2 exp(log_std_j) / sd_j - 1
  * STATISTICS behind the gradient, grad_out[P .. P+3] (so a multi-rank caller averages gradient and KL in the one all-reduce):
  *     pi_loss = L,  approx_kl = mean(logp_old - logp),  clip_frac = mean(ratio > 1 + clip or ratio < 1 - clip),  mean_ratio = mean(ratio).

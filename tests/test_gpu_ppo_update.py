@@ -202,7 +202,7 @@ def test_workgroup_partition(leak):
     """The same 64 rows as ONE workgroup (count 64) and, each three times in a shuffled order, as THREE (count 192): the mean gradient is
     the same number, so both must sit within the parity bound of the float64 reference of the 64 rows, with whatever the partition, the
     per-workgroup partials and the reduction add.  (There is no test-only grid override; the cap of 256 workgroups, where one workgroup
-    takes several tiles, is exercised by tools/time_ppo_update.py's sizes only.)"""
+    takes several tiles, is exercised by test_gradient_parity_several_tiles_per_workgroup.)"""
     torch = torch_()
     fx, d, _ = fixture(leak)
     rng = np.random.RandomState(9)

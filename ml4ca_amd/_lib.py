@@ -293,6 +293,35 @@ def check(code, handle=None):
         raise DpenvError('libdpenv error %d: %s' % (code, msg.decode() if msg else '?'))
 
 
+# ---- what every module of the host layer shares: torch on demand, pointers, streams, tensor checks ----
+def _torch():
+    import torch
+    return torch
+
+
+def _p(t):
+    return None if t is None else C.c_void_p(t.data_ptr())
+
+
+def _s(t):
+    """The current stream of t's device."""
+    return C.c_void_p(_torch().cuda.current_stream(t.device).cuda_stream)
+
+
+def _req(t, shape, dtype, what):
+    """None, or a contiguous cuda tensor of that dtype (and shape, unless shape is None)."""
+    if t is None:
+        return
+    if (shape is not None and tuple(t.shape) != tuple(shape)) or t.dtype != dtype or not t.is_contiguous() or not t.is_cuda:
+        raise ValueError('%s must be a contiguous cuda %s tensor%s' % (what, dtype, '' if shape is None else ' of shape %s' % (tuple(shape),)))
+
+
+def _is_on(t, shape, dtype, device):
+    """t is a contiguous tensor of this shape and dtype on that device."""
+    return (isinstance(t, _torch().Tensor) and tuple(t.shape) == tuple(shape) and t.dtype == dtype and t.device == device
+            and t.is_contiguous())
+
+
 def default_config():
     cfg = Config()
     check(load().dpenv_default_config(C.byref(cfg)))

@@ -506,26 +506,46 @@ def label_rows(params_or_table, obs, done=None, z=None, dt=0.2, dtype=None):
     of dp_controller_defaults (None = the defaults) or a public table [32, n], as BatchedDPController takes them; dt the control period.
     Returns (act [T, n, 7], z [3, n]) in dtype (None = float32, which reproduces the kernel's bits); labelling rows [0:k] and [k:T] with z
     handed over equals one call."""
+    obs, done, T, n = _label_block('label_rows', obs, done)
+    ctrl = BatchedDPController(n, params_or_table, dt=dt, dtype=dtype)
+    (act,), z = _label_scan('label_rows', ctrl, obs, done, z, (7,), lambda t, tau, ended: (ctrl.allocate(tau),))
+    return act, z
+
+
+def _label_block(who, obs, done):
+    """The block a host labelling scan reads, checked under the caller's name: (obs [T, n, >= 6], done [T, n] or None, T, n) as arrays."""
     obs = np.asarray(obs)
     if obs.ndim != 3 or obs.shape[2] < 6:
-        raise ValueError('label_rows: obs is [T, n, >= 6]')
+        raise ValueError('%s: obs is [T, n, >= 6]' % who)
     T, n = obs.shape[0], obs.shape[1]
     if done is not None:
         done = np.asarray(done)
         if done.shape != (T, n):
-            raise ValueError('label_rows: done is [T, n]')
-    ctrl = BatchedDPController(n, params_or_table, dt=dt, dtype=dtype)
+            raise ValueError('%s: done is [T, n]' % who)
+    return obs, done, T, n
+
+
+def _label_scan(who, ctrl, obs, done, z, widths, stage):
+    """The host labelling scan of label_rows, label_rows_qp and label_rows_nn on a block of _label_block: ctrl, the PID
+    (BatchedDPController), starts from z [3, n] (None = where it is), and per row t, in this order:
+        tau = ctrl.wrench(obs[t]);  outputs[t] = stage(t, tau, ended);  ctrl.reset(ended)
+    with ended = (done[t] != 0), or None where done is None (nothing is reset then).  stage is the allocation stage: it returns one row
+    [n, w] per width w in `widths` and resets its OWN state behind an ended row.  Returns (one [T, n, w] array per width in ctrl's
+    dtype, z [3, n])."""
+    T, n = obs.shape[0], obs.shape[1]
     if z is not None:
         z = np.asarray(z)
         if z.shape != (3, n):
-            raise ValueError('label_rows: z is [3, n]')
+            raise ValueError('%s: z is [3, n]' % who)
         ctrl.z = np.ascontiguousarray(z.T).astype(ctrl.dtype)
-    act = np.empty((T, n, 7), ctrl.dtype)
+    outs = tuple(np.empty((T, n, w), ctrl.dtype) for w in widths)
     for t in range(T):
-        act[t] = ctrl.allocate(ctrl.wrench(obs[t]))
-        if done is not None:
-            ctrl.reset(done[t] != 0)
-    return act, np.ascontiguousarray(np.asarray(ctrl.z).T)
+        ended = None if done is None else done[t] != 0
+        for o, row in zip(outs, stage(t, ctrl.wrench(obs[t]), ended)):
+            o[t] = row
+        if ended is not None:
+            ctrl.reset(ended)
+    return outs, np.ascontiguousarray(np.asarray(ctrl.z).T)
 
 
 QP_MAX_ITERATIONS = 32
@@ -903,14 +923,7 @@ def label_rows_qp(params_or_table, qp_params, obs, done=None, z=None, x=None, dt
     of row t, qp.x = S(flown[t]), then the resets; the label of row t does not depend on flown[t:], and x out is the last such state.
     qp_params may be a public QP table [32, n] (env i labelled with row i, in `iterations` solver steps, None = 16): rows the library
     refuses (qp_table_refused) run the rest allocator here too - zero thrust, azimuths held."""
-    obs = np.asarray(obs)
-    if obs.ndim != 3 or obs.shape[2] < 6:
-        raise ValueError('label_rows_qp: obs is [T, n, >= 6]')
-    T, n = obs.shape[0], obs.shape[1]
-    if done is not None:
-        done = np.asarray(done)
-        if done.shape != (T, n):
-            raise ValueError('label_rows_qp: done is [T, n]')
+    obs, done, T, n = _label_block('label_rows_qp', obs, done)
     if flown is not None:
         flown = np.asarray(flown)
         if flown.shape != (T, n, 7):
@@ -927,25 +940,22 @@ def label_rows_qp(params_or_table, qp_params, obs, done=None, z=None, x=None, dt
         raise ValueError('label_rows_qp: iterations goes with a QP table (the dict carries its own)')
     ctrl = BatchedDPController(n, params_or_table, dt=dt, dtype=dtype)
     qp = BatchedQPAllocator(n, qp_params, dt=dt, dtype=dtype)
-    if z is not None:
-        z = np.asarray(z)
-        if z.shape != (3, n):
-            raise ValueError('label_rows_qp: z is [3, n]')
-        ctrl.z = np.ascontiguousarray(z.T).astype(ctrl.dtype)
     if x is not None:
         x = np.asarray(x)
         if x.shape != (5, n):
             raise ValueError('label_rows_qp: x is [5, n]')
         qp.x = np.ascontiguousarray(x.T).astype(qp.dtype)
-    act = np.empty((T, n, 7), ctrl.dtype)
-    for t in range(T):
-        act[t] = qp.allocate(ctrl.wrench(obs[t]))
+
+    def stage(t, tau, ended):
+        act = qp.allocate(tau)
         if flown is not None:                                                          # the law's own advance of x is dropped
             qp.x = _qp_state(qp.kf, qp.kr, qp.fmax, flown[t], qp.dtype)
-        if done is not None:
-            ctrl.reset(done[t] != 0)
-            qp.reset(done[t] != 0)
-    return act, np.ascontiguousarray(np.asarray(ctrl.z).T), np.ascontiguousarray(np.asarray(qp.x).T)
+        if ended is not None:
+            qp.reset(ended)
+        return (act,)
+
+    (act,), z = _label_scan('label_rows_qp', ctrl, obs, done, z, (7,), stage)
+    return act, z, np.ascontiguousarray(np.asarray(qp.x).T)
 
 
 class RLAllocatorNode(object):
@@ -1224,28 +1234,12 @@ def label_rows_nn(params_or_table, net, obs, done=None, z=None, dt=0.2, dtype=No
     - z is advanced before the wrench and zeroed BEHIND a done row; the network has no state.  Returns (act [T, n, 7], z [3, n],
     raw [T, n, 6], tau [T, n, 3]) in dtype (None = float32: the kernel's bits except for the sin / cos heads, see BatchedNNAllocator);
     labelling rows [0:k] and [k:T] with z handed over equals one call."""
-    obs = np.asarray(obs)
-    if obs.ndim != 3 or obs.shape[2] < 6:
-        raise ValueError('label_rows_nn: obs is [T, n, >= 6]')
-    T, n = obs.shape[0], obs.shape[1]
-    if done is not None:
-        done = np.asarray(done)
-        if done.shape != (T, n):
-            raise ValueError('label_rows_nn: done is [T, n]')
+    obs, done, T, n = _label_block('label_rows_nn', obs, done)
     ctrl = BatchedDPController(n, params_or_table, dt=dt, dtype=dtype)
     alloc = BatchedNNAllocator(n, net, dtype=dtype, params=nn_params)
-    if z is not None:
-        z = np.asarray(z)
-        if z.shape != (3, n):
-            raise ValueError('label_rows_nn: z is [3, n]')
-        ctrl.z = np.ascontiguousarray(z.T).astype(ctrl.dtype)
-    act, raw, tau = np.empty((T, n, 7), ctrl.dtype), np.empty((T, n, 6), ctrl.dtype), np.empty((T, n, 3), ctrl.dtype)
-    for t in range(T):
-        tau[t] = ctrl.wrench(obs[t])
-        act[t], raw[t] = alloc.allocate(tau[t], raw=True)
-        if done is not None:
-            ctrl.reset(done[t] != 0)
-    return act, np.ascontiguousarray(np.asarray(ctrl.z).T), raw, tau
+    (tau, act, raw), z = _label_scan('label_rows_nn', ctrl, obs, done, z, (3, 7, 6),
+                                     lambda t, tau, ended: (tau,) + tuple(alloc.allocate(tau, raw=True)))
+    return act, z, raw, tau
 
 
 def thrust_map_host(n_pct, alpha, vessel=None):

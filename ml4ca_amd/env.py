@@ -21,6 +21,7 @@ import weakref
 import numpy as np
 
 from . import _lib
+from ._lib import _torch
 from .deploy import REFERENCE_FILTER_OMEGA, REFERENCE_FILTER_ZETA
 from . import reset_samplers as simtools
 
@@ -66,9 +67,7 @@ class Box(object):
         return np.random.uniform(self.low, self.high).astype(self.dtype)
 
 
-def _torch():
-    import torch
-    return torch
+_OUT_NAMES = {}                          # 'out[%r]' % key, formatted once per key: the block checks run on every launch
 
 
 class BatchedRevoltEnv(object):
@@ -169,7 +168,7 @@ class BatchedRevoltEnv(object):
         oshape = (n, od) if layout == 'aos' else (od, n)
         self._obs = [torch.empty(oshape, dtype=self.obs_torch_dtype, device=self.device) for _ in range(2)]
         self._flip = 0
-        self._f32, self._u8 = torch.float32, torch.uint8
+        self._f32, self._u8, self._i32 = torch.float32, torch.uint8, torch.int32
         self._rew = torch.empty(n, dtype=torch.float32, device=self.device)
         self._done = torch.empty(n, dtype=torch.uint8, device=self.device)
         self._final_obs = None
@@ -229,6 +228,47 @@ class BatchedRevoltEnv(object):
     @staticmethod
     def _ptr(t):
         return None if t is None else C.c_void_p(t.data_ptr())
+
+    def _get(self, fn, *specs, or_none=False):
+        """A getter of the C ABI: one new tensor per (shape, dtype), fn(handle, their pointers..., stream), the tensors (one: itself).
+        or_none: a refusal returns None instead of raising."""
+        torch = _torch()
+        ts = [torch.empty(shape, dtype=dtype, device=self.device) for shape, dtype in specs]
+        rc = fn(self._h, *[self._ptr(t) for t in ts], self._stream())
+        if or_none and rc != _lib.OK:
+            return None
+        _lib.check(rc, self._h)
+        return ts[0] if len(ts) == 1 else tuple(ts)
+
+    def _set(self, fn, *args):
+        """A setter of the C ABI: _chk of every (tensor, shape, dtype, what) - None passes, and reaches the library as NULL - then
+        fn(handle, their pointers..., stream)."""
+        _lib.check(fn(self._h, *[self._ptr(self._chk(*a)) for a in args], self._stream()), self._h)
+
+    def _blocks(self, spec, out=None, fill=False):
+        """The blocks a launch writes, spec = (key, shape, dtype) each: out None makes them (a dict by key); else out[key] - a dict's or
+        a tuple's - is checked (_chk, named out[key]), a block the dict lacks being made first if fill."""
+        torch = _torch()
+        if out is None:
+            return {key: torch.empty(shape, dtype=dtype, device=self.device) for key, shape, dtype in spec}
+        for key, shape, dtype in spec:
+            if fill and out.get(key) is None:
+                out[key] = torch.empty(shape, dtype=dtype, device=self.device)
+            self._chk(out[key], shape, dtype, _OUT_NAMES.get(key) or _OUT_NAMES.setdefault(key, 'out[%r]' % (key,)))
+        return out
+
+    def _schedule(self, io, switch_steps, refs):
+        """The setpoint schedule of a rollout launch into its io struct (n_switch, switch_step[], refs): refs[k] float32 [3, n] is the
+        new_ref of step switch_steps[k]."""
+        k = len(switch_steps)
+        if k > 8:
+            raise ValueError('at most 8 setpoint switches per rollout launch')
+        if k:
+            self._chk(refs, (k, 3, self.n_envs), self._f32, 'refs')
+        io.n_switch = k
+        for j, st in enumerate(switch_steps):
+            io.switch_step[j] = int(st)
+        io.refs = refs.data_ptr() if k else None
 
     def close(self):
         if getattr(self, '_h', None) is not None and self._h.value:
@@ -324,47 +364,26 @@ class BatchedRevoltEnv(object):
         T = int(actions.shape[0])
         n = self.n_envs
         self._chk(actions, (T,) + self.action_shape, torch.float32, 'actions')
-        k = len(switch_steps)
-        if k > 8:
-            raise ValueError('at most 8 setpoint switches per rollout launch')
-        if k:
-            self._chk(refs, (k, 3, n), torch.float32, 'refs')
-        if out is None:
-            obs = torch.empty((T,) + self.obs_shape, dtype=self.obs_torch_dtype, device=self.device)
-            rew = torch.empty((T, n), dtype=torch.float32, device=self.device)
-            done = torch.empty((T, n), dtype=torch.uint8, device=self.device)
-        else:
-            obs, rew, done = out
-            self._chk(obs, (T,) + self.obs_shape, self.obs_torch_dtype, 'out[0]')
-            self._chk(rew, (T, n), torch.float32, 'out[1]')
-            self._chk(done, (T, n), torch.uint8, 'out[2]')
         io = _lib.RolloutIO()
         io.struct_size = C.sizeof(_lib.RolloutIO)
+        self._schedule(io, switch_steps, refs)
+        blk = self._blocks(((0, (T,) + self.obs_shape, self.obs_torch_dtype), (1, (T, n), torch.float32), (2, (T, n), torch.uint8)), out)
+        obs, rew, done = blk[0], blk[1], blk[2]
         io.T = T
         io.actions = actions.data_ptr()
         io.obs = obs.data_ptr()
         io.reward = rew.data_ptr()
         io.done = done.data_ptr()
-        io.n_switch = k
-        for j, st in enumerate(switch_steps):
-            io.switch_step[j] = int(st)
-        io.refs = refs.data_ptr() if k else None
         _lib.check(self.lib.dpenv_rollout(self._h, C.byref(io), self._stream()), self._h)
         return obs, rew, done
 
     # -- state access (parity tests, checkpoints) ----------------------------------------------
     def get_state(self):
-        torch = _torch()
-        st = torch.empty((_lib.NSTATE, self.n_envs), dtype=torch.float32, device=self.device)
-        ctr = torch.empty((2, self.n_envs), dtype=torch.int32, device=self.device)
-        _lib.check(self.lib.dpenv_get_state(self._h, self._ptr(st), self._ptr(ctr), self._stream()), self._h)
-        return st, ctr
+        return self._get(self.lib.dpenv_get_state, ((_lib.NSTATE, self.n_envs), self._f32), ((2, self.n_envs), self._i32))
 
     def set_state(self, state=None, counters=None):
-        torch = _torch()
-        state = self._chk(state, (_lib.NSTATE, self.n_envs), torch.float32, 'state')
-        counters = self._chk(counters, (2, self.n_envs), torch.int32, 'counters')
-        _lib.check(self.lib.dpenv_set_state(self._h, self._ptr(state), self._ptr(counters), self._stream()), self._h)
+        self._set(self.lib.dpenv_set_state, (state, (_lib.NSTATE, self.n_envs), self._f32, 'state'),
+                  (counters, (2, self.n_envs), self._i32, 'counters'))
 
     # -- the deployed controller's integral action (dpenv.h dpenv_set_integral_action) ----------------------------------------------
     @property
@@ -397,17 +416,10 @@ class BatchedRevoltEnv(object):
     def get_integral_state(self):
         """(I float32 [3, n], count int32 [n]): the integrator and the control steps since the last (re)arrival.  Checkpoint with
         get_state() / get_rng_counters()."""
-        torch = _torch()
-        I = torch.empty((3, self.n_envs), dtype=torch.float32, device=self.device)
-        c = torch.empty(self.n_envs, dtype=torch.int32, device=self.device)
-        _lib.check(self.lib.dpenv_get_integral_state(self._h, self._ptr(I), self._ptr(c), self._stream()), self._h)
-        return I, c
+        return self._get(self.lib.dpenv_get_integral_state, (self._r3, self._f32), (self._n1, self._i32))
 
     def set_integral_state(self, I=None, count=None):
-        torch = _torch()
-        I = self._chk(I, (3, self.n_envs), torch.float32, 'I')
-        count = self._chk(count, (self.n_envs,), torch.int32, 'count')
-        _lib.check(self.lib.dpenv_set_integral_state(self._h, self._ptr(I), self._ptr(count), self._stream()), self._h)
+        self._set(self.lib.dpenv_set_integral_state, (I, self._r3, self._f32, 'I'), (count, self._n1, self._i32, 'count'))
 
     # -- the deployed controller's setpoint reference filter (dpenv.h dpenv_set_reference_filter) ------------------------------------
     def set_reference_filter(self, omega=REFERENCE_FILTER_OMEGA, zeta=REFERENCE_FILTER_ZETA):
@@ -429,17 +441,10 @@ class BatchedRevoltEnv(object):
     def get_reference_filter_state(self):
         """(x float32 [9, n], r float32 [3, n]): row 3 k + j of x is (pos, vel, acc)[k] of axis (N, E, psi)[j]; r the targets.  Checkpoint
         with get_state() / get_rng_counters()."""
-        torch = _torch()
-        x = torch.empty((9, self.n_envs), dtype=torch.float32, device=self.device)
-        r = torch.empty((3, self.n_envs), dtype=torch.float32, device=self.device)
-        _lib.check(self.lib.dpenv_get_reference_filter_state(self._h, self._ptr(x), self._ptr(r), self._stream()), self._h)
-        return x, r
+        return self._get(self.lib.dpenv_get_reference_filter_state, ((9, self.n_envs), self._f32), (self._r3, self._f32))
 
     def set_reference_filter_state(self, x=None, r=None):
-        torch = _torch()
-        x = self._chk(x, (9, self.n_envs), torch.float32, 'x')
-        r = self._chk(r, (3, self.n_envs), torch.float32, 'r')
-        _lib.check(self.lib.dpenv_set_reference_filter_state(self._h, self._ptr(x), self._ptr(r), self._stream()), self._h)
+        self._set(self.lib.dpenv_set_reference_filter_state, (x, (9, self.n_envs), self._f32, 'x'), (r, self._r3, self._f32, 'r'))
 
     # -- the classical baseline: PID + pseudo-inverse allocation in the closed loop (dpenv.h dpenv_set_dp_controller) ------------------
     def set_dp_controller(self, params=None, off=False):
@@ -483,14 +488,10 @@ class BatchedRevoltEnv(object):
 
     def get_dp_controller_state(self):
         """z float32 [3, n]: the baseline's error integral.  Checkpoint with get_state()."""
-        torch = _torch()
-        z = torch.empty((3, self.n_envs), dtype=torch.float32, device=self.device)
-        _lib.check(self.lib.dpenv_get_dp_controller_state(self._h, self._ptr(z), self._stream()), self._h)
-        return z
+        return self._get(self.lib.dpenv_get_dp_controller_state, (self._r3, self._f32))
 
     def set_dp_controller_state(self, z):
-        self._chk(z, (3, self.n_envs), _torch().float32, 'z')
-        _lib.check(self.lib.dpenv_set_dp_controller_state(self._h, self._ptr(z), self._stream()), self._h)
+        self._set(self.lib.dpenv_set_dp_controller_state, (z, self._r3, self._f32, 'z'))
 
     def set_nn_allocator(self, net=None, off=False, **constants):
         """The neural thrust allocation as the allocation stage of policy.controller_rollout (dpenv_set_nn_allocator; include/dpenv.h has
@@ -591,29 +592,18 @@ class BatchedRevoltEnv(object):
 
     def get_qp_allocator_state(self):
         """float32 [5, n]: the QP allocator's thruster state F_bow, F_port, F_star, a_port, a_star.  Checkpoint with get_dp_controller_state()."""
-        torch = _torch()
-        x = torch.empty((5, self.n_envs), dtype=torch.float32, device=self.device)
-        _lib.check(self.lib.dpenv_get_qp_allocator_state(self._h, self._ptr(x), self._stream()), self._h)
-        return x
+        return self._get(self.lib.dpenv_get_qp_allocator_state, ((5, self.n_envs), self._f32))
 
     def set_qp_allocator_state(self, x):
-        self._chk(x, (5, self.n_envs), _torch().float32, 'x')
-        _lib.check(self.lib.dpenv_set_qp_allocator_state(self._h, self._ptr(x), self._stream()), self._h)
+        self._set(self.lib.dpenv_set_qp_allocator_state, (x, (5, self.n_envs), self._f32, 'x'))
 
     def get_rng_counters(self):
         """(noise_ctr, drift_ctr): int32 [n] draws made so far of the in-kernel exploration noise and of the current drift (uint32
         bits).  With get_state() and get_current() a complete checkpoint: restoring all of them reproduces sampled rollouts."""
-        torch = _torch()
-        nc = torch.empty(self.n_envs, dtype=torch.int32, device=self.device)
-        dc = torch.empty(self.n_envs, dtype=torch.int32, device=self.device)
-        _lib.check(self.lib.dpenv_get_rng_counters(self._h, self._ptr(nc), self._ptr(dc), self._stream()), self._h)
-        return nc, dc
+        return self._get(self.lib.dpenv_get_rng_counters, (self._n1, self._i32), (self._n1, self._i32))
 
     def set_rng_counters(self, noise_ctr=None, drift_ctr=None):
-        torch = _torch()
-        self._chk(noise_ctr, (self.n_envs,), torch.int32, 'noise_ctr')
-        self._chk(drift_ctr, (self.n_envs,), torch.int32, 'drift_ctr')
-        _lib.check(self.lib.dpenv_set_rng_counters(self._h, self._ptr(noise_ctr), self._ptr(drift_ctr), self._stream()), self._h)
+        self._set(self.lib.dpenv_set_rng_counters, (noise_ctr, self._n1, self._i32, 'noise_ctr'), (drift_ctr, self._n1, self._i32, 'drift_ctr'))
 
     def get_obs_thrust(self):
         """float32 [n, 4]: thrust columns of the observation the last closed-loop launch ended with (a mid-episode checkpoint needs
@@ -622,40 +612,25 @@ class BatchedRevoltEnv(object):
         (previous thrust / 100), a reset those of the envs it re-draws, step() those of the observation it returns while a policy is in
         force.  None only while they are stale: after a step() WITHOUT a policy uploaded, or after a masked reset of a handle whose
         columns were already stale - the next closed-loop launch then starts from the state block alone."""
-        torch = _torch()
-        t = torch.empty((self.n_envs, 4), dtype=torch.float32, device=self.device)
-        rc = self.lib.dpenv_get_obs_thrust(self._h, self._ptr(t), self._stream())
-        return t if rc == _lib.OK else None
+        return self._get(self.lib.dpenv_get_obs_thrust, ((self.n_envs, 4), self._f32), or_none=True)
 
     def set_obs_thrust(self, t):
-        self._chk(t, (self.n_envs, 4), _torch().float32, 'obs_thrust')
-        _lib.check(self.lib.dpenv_set_obs_thrust(self._h, self._ptr(t), self._stream()), self._h)
+        self._set(self.lib.dpenv_set_obs_thrust, (t, (self.n_envs, 4), self._f32, 'obs_thrust'))
 
     def set_current(self, vc, beta, present_only=False):
         """Per-env constant current: speed [m/s] and NED direction [rad] (results/.../current_box_test/plot_pos.py:78).  They are
         both the present value and the mean a drifting current reverts to; present_only=True restores only the present values
         (what get_current returned: checkpoints of a drifting current)."""
-        torch = _torch()
-        self._chk(vc, (self.n_envs,), torch.float32, 'vc')
-        self._chk(beta, (self.n_envs,), torch.float32, 'beta')
-        fn = self.lib.dpenv_set_current_present if present_only else self.lib.dpenv_set_current
-        _lib.check(fn(self._h, self._ptr(vc), self._ptr(beta), self._stream()), self._h)
+        self._set(self.lib.dpenv_set_current_present if present_only else self.lib.dpenv_set_current,
+                  (vc, self._n1, self._f32, 'vc'), (beta, self._n1, self._f32, 'beta'))
 
     def get_current(self):
         """Present (vc, beta) of every env; differs from what set_current gave only with current_drift."""
-        torch = _torch()
-        vc = torch.empty(self.n_envs, dtype=torch.float32, device=self.device)
-        beta = torch.empty(self.n_envs, dtype=torch.float32, device=self.device)
-        _lib.check(self.lib.dpenv_get_current(self._h, self._ptr(vc), self._ptr(beta), self._stream()), self._h)
-        return vc, beta
+        return self._get(self.lib.dpenv_get_current, (self._n1, self._f32), (self._n1, self._f32))
 
     def get_current_mean(self):
         """(vc, beta) the drift reverts to: what set_current gave, or what the last randomised reset drew (set_current_randomisation)."""
-        torch = _torch()
-        vc = torch.empty(self.n_envs, dtype=torch.float32, device=self.device)
-        beta = torch.empty(self.n_envs, dtype=torch.float32, device=self.device)
-        _lib.check(self.lib.dpenv_get_current_mean(self._h, self._ptr(vc), self._ptr(beta), self._stream()), self._h)
-        return vc, beta
+        return self._get(self.lib.dpenv_get_current_mean, (self._n1, self._f32), (self._n1, self._f32))
 
     def set_current_randomisation(self, vc_range, beta_range, vc_nominal=None, beta_nominal=None):
         """Per-episode randomisation of the current through the reset path (dpenv_set_current_randomisation): every reset starts its
@@ -692,10 +667,7 @@ class BatchedRevoltEnv(object):
 
     def get_vessel_params(self):
         """float32 [NPARAM, n]: the per-env parameter vectors in force (set explicitly, or drawn by the randomisation)."""
-        torch = _torch()
-        out = torch.empty((_lib.NPARAM, self.n_envs), dtype=torch.float32, device=self.device)
-        _lib.check(self.lib.dpenv_get_vessel_params(self._h, self._ptr(out), self._stream()), self._h)
-        return out
+        return self._get(self.lib.dpenv_get_vessel_params, ((_lib.NPARAM, self.n_envs), self._f32))
 
     def set_vessel_randomisation(self, rel_range, nominal=None):
         """Domain randomisation through the reset path (dpenv_set_vessel_randomisation): every reset starts its episode on a hull with
@@ -733,10 +705,8 @@ def thrust_map(n_pct, alpha, params=None):
         pa = np.ascontiguousarray(params, dtype=np.float32)
         assert pa.shape == (_lib.NPARAM,)
         p = pa.ctypes.data_as(C.POINTER(C.c_float))
-    s = C.c_void_p(torch.cuda.current_stream(n_pct.device).cuda_stream)
     with torch.cuda.device(n_pct.device):
-        _lib.check(lib.dpenv_thrust_map(p, C.c_void_p(n_pct.data_ptr()), C.c_void_p(alpha.data_ptr()),
-                                        C.c_void_p(tau.data_ptr()), n_pct.shape[1], s))
+        _lib.check(lib.dpenv_thrust_map(p, _lib._p(n_pct), _lib._p(alpha), _lib._p(tau), n_pct.shape[1], _lib._s(n_pct)))
     return tau
 
 
@@ -764,9 +734,8 @@ def thrust_alloc(tau, params=None):
     assert tau.dim() == 2 and tau.shape[0] == 3 and tau.is_contiguous() and tau.dtype == torch.float32 and tau.is_cuda
     _, c = _dp_controller_struct(params)
     act = torch.empty((tau.shape[1], 7), dtype=torch.float32, device=tau.device)
-    s = C.c_void_p(torch.cuda.current_stream(tau.device).cuda_stream)
     with torch.cuda.device(tau.device):
-        _lib.check(lib.dpenv_thrust_alloc(C.byref(c), C.c_void_p(tau.data_ptr()), C.c_void_p(act.data_ptr()), tau.shape[1], s))
+        _lib.check(lib.dpenv_thrust_alloc(C.byref(c), _lib._p(tau), _lib._p(act), tau.shape[1], _lib._s(tau)))
     return act
 
 

@@ -12,11 +12,7 @@ import math
 import numpy as np
 
 from . import _lib
-
-
-def _torch():
-    import torch
-    return torch
+from ._lib import _is_on, _torch
 
 
 class ActorCritic(object):
@@ -242,50 +238,33 @@ def policy_rollout(env, T, noise=None, switch_steps=(), refs=None, out=None, sam
     targets, every step's new_ref is its position, and out['ref'] [T,n,3] holds the eta_d that obs[t] was formed against."""
     torch = _torch()
     n, od, ad = env.n_envs, env.num_states, env.num_actions
-    dev = env.device
+    f32, odt = torch.float32, env.obs_torch_dtype
     if noise is not None:
-        env._chk(noise, (T, n, ad), torch.float32, 'noise')
-    k = len(switch_steps)
-    if k:
-        env._chk(refs, (k, 3, n), torch.float32, 'refs')
-    f32 = torch.float32
-    if out is None:
-        out = dict(obs=torch.empty((T, n, od), dtype=env.obs_torch_dtype, device=dev), act=torch.empty((T, n, ad), dtype=f32, device=dev),
-                   rew=torch.empty((T, n), dtype=f32, device=dev), val=torch.empty((T, n), dtype=f32, device=dev),
-                   logp=torch.empty((T, n), dtype=f32, device=dev), boot=torch.empty((T, n), dtype=f32, device=dev),
-                   done=torch.empty((T, n), dtype=torch.uint8, device=dev),
-                   last_obs=torch.empty((n, od), dtype=env.obs_torch_dtype, device=dev), last_val=torch.empty(n, dtype=f32, device=dev))
+        env._chk(noise, (T, n, ad), f32, 'noise')
     io = _lib.PolicyRolloutIO()
     io.struct_size = C.sizeof(_lib.PolicyRolloutIO)
+    env._schedule(io, switch_steps, refs)
+    out = env._blocks((('obs', (T, n, od), odt), ('act', (T, n, ad), f32), ('rew', (T, n), f32), ('val', (T, n), f32), ('logp', (T, n), f32),
+                       ('boot', (T, n), f32), ('done', (T, n), torch.uint8), ('last_obs', (n, od), odt), ('last_val', (n,), f32)), out)
+    filt, integ = env.reference_filter is not None, env.integral_action is not None
+    for key, on in (('ref', filt), ('integ', integ)):
+        if on:
+            env._blocks(((key, (T, n, 3), f32),), out, fill=True)
     io.T = int(T)
     io.noise = noise.data_ptr() if noise is not None else None
     io.obs, io.act, io.reward = out['obs'].data_ptr(), out['act'].data_ptr(), out['rew'].data_ptr()
     io.value, io.logp, io.done = out['val'].data_ptr(), out['logp'].data_ptr(), out['done'].data_ptr()
     io.boot, io.last_obs, io.last_value = out['boot'].data_ptr(), out['last_obs'].data_ptr(), out['last_val'].data_ptr()
-    io.n_switch = k
-    for j, st in enumerate(switch_steps):
-        io.switch_step[j] = int(st)
-    io.refs = refs.data_ptr() if k else None
     io.sample = 1 if (sample and noise is None) else 0
     io.reset_at_end = 1 if reset_at_end else 0
-    if env.reference_filter is not None:
-        if out.get('ref') is None:
-            out['ref'] = torch.empty((T, n, 3), dtype=f32, device=dev)
-        env._chk(out['ref'], (T, n, 3), f32, "out['ref']")
-        integ = None
-        if env.integral_action is not None:
-            if out.get('integ') is None:
-                out['integ'] = torch.empty((T, n, 3), dtype=f32, device=dev)
-            env._chk(out['integ'], (T, n, 3), f32, "out['integ']")
-            integ = out['integ'].data_ptr()
-        _lib.check(env.lib.dpenv_policy_rollout_deployed(env._h, C.byref(io), out['ref'].data_ptr(), integ, env._stream()), env._h)
-    elif env.integral_action is not None:
-        if out.get('integ') is None:
-            out['integ'] = torch.empty((T, n, 3), dtype=f32, device=dev)
-        env._chk(out['integ'], (T, n, 3), f32, "out['integ']")
-        _lib.check(env.lib.dpenv_policy_rollout_integral(env._h, C.byref(io), out['integ'].data_ptr(), env._stream()), env._h)
+    ipt = out['integ'].data_ptr() if integ else None
+    if filt:
+        rc = env.lib.dpenv_policy_rollout_deployed(env._h, C.byref(io), out['ref'].data_ptr(), ipt, env._stream())
+    elif integ:
+        rc = env.lib.dpenv_policy_rollout_integral(env._h, C.byref(io), ipt, env._stream())
     else:
-        _lib.check(env.lib.dpenv_policy_rollout(env._h, C.byref(io), env._stream()), env._h)
+        rc = env.lib.dpenv_policy_rollout(env._h, C.byref(io), env._stream())
+    _lib.check(rc, env._h)
     return out
 
 
@@ -297,34 +276,18 @@ def controller_rollout(env, T, switch_steps=(), refs=None, out=None):
     obs[t] was formed against.  ScoreCard.add consumes the dict unchanged."""
     torch = _torch()
     n, od, ad = env.n_envs, env.num_states, env.num_actions
-    dev, f32 = env.device, torch.float32
-    k = len(switch_steps)
-    if k:
-        env._chk(refs, (k, 3, n), f32, 'refs')
-    if out is None:
-        out = dict(obs=torch.empty((T, n, od), dtype=env.obs_torch_dtype, device=dev), act=torch.empty((T, n, ad), dtype=f32, device=dev),
-                   rew=torch.empty((T, n), dtype=f32, device=dev), done=torch.empty((T, n), dtype=torch.uint8, device=dev),
-                   last_obs=torch.empty((n, od), dtype=env.obs_torch_dtype, device=dev))
-    env._chk(out['obs'], (T, n, od), env.obs_torch_dtype, "out['obs']")
-    env._chk(out['act'], (T, n, ad), f32, "out['act']")
-    env._chk(out['rew'], (T, n), f32, "out['rew']")
-    env._chk(out['done'], (T, n), torch.uint8, "out['done']")
-    env._chk(out['last_obs'], (n, od), env.obs_torch_dtype, "out['last_obs']")
+    f32, odt = torch.float32, env.obs_torch_dtype
     io = _lib.ControllerRolloutIO()
     io.struct_size = C.sizeof(_lib.ControllerRolloutIO)
+    env._schedule(io, switch_steps, refs)
+    out = env._blocks((('obs', (T, n, od), odt), ('act', (T, n, ad), f32), ('rew', (T, n), f32), ('done', (T, n), torch.uint8),
+                       ('last_obs', (n, od), odt)), out)
     io.T = int(T)
     io.obs, io.act, io.reward, io.done = out['obs'].data_ptr(), out['act'].data_ptr(), out['rew'].data_ptr(), out['done'].data_ptr()
     io.last_obs = out['last_obs'].data_ptr()
-    io.n_switch = k
-    for j, st in enumerate(switch_steps):
-        io.switch_step[j] = int(st)
-    io.refs = refs.data_ptr() if k else None
     io.ref_out = None
     if env.reference_filter is not None:
-        if out.get('ref') is None:
-            out['ref'] = torch.empty((T, n, 3), dtype=f32, device=dev)
-        env._chk(out['ref'], (T, n, 3), f32, "out['ref']")
-        io.ref_out = out['ref'].data_ptr()
+        io.ref_out = env._blocks((('ref', (T, n, 3), f32),), out, fill=True)['ref'].data_ptr()
     _lib.check(env.lib.dpenv_controller_rollout(env._h, C.byref(io), env._stream()), env._h)
     return out
 
@@ -339,32 +302,47 @@ def controller_label(env, obs, done=None, z=None, out=None):
     buffers (z may be the input tensor itself).  Nothing of the env changes: not its state, not its own z, not a counter.  For float32
     rows of controller_rollout with auto-reset on the labels are that launch's act rows bit for bit.  deploy.label_rows is the host
     statement."""
+    T, (act, z_out) = _label_front('controller_label', env, obs, done, z, out, more=())
+    io = _label_io(_lib.ControllerLabelIO(), T, obs, done, z, z_out, act)
+    _lib.check(env.lib.dpenv_controller_label(env._h, C.byref(io), env._stream()), env._h)
+    return act, z_out
+
+
+def _label_front(who, env, obs, done, z, out=None, more=None):
+    """The opening of the controller_label* scans: obs is a [T, n, 9] float32 or bfloat16 block (refused under the caller's name `who`),
+    done [T, n] uint8 or None, z [3, n] float32 or None.  Returns T and the float32 out buffers - act [T, n, 7], z [3, n], then one per
+    shape in `more` - as a tuple: the caller's out tuple checked (_chk, named out[j]), or new tensors when out is None.  more=None
+    leaves the buffers to the caller (None is returned for them)."""
     torch = _torch()
-    n, ad = env.n_envs, env.num_actions
-    dev, f32 = env.device, torch.float32
+    n, f32 = env.n_envs, torch.float32
     if not isinstance(obs, torch.Tensor) or obs.dim() != 3:
-        raise ValueError('controller_label: obs is a tensor [T, n, 9]')
+        raise ValueError('%s: obs is a tensor [T, n, 9]' % who)
     if obs.dtype not in (torch.float32, torch.bfloat16):
-        raise ValueError('controller_label: obs rows are float32 or bfloat16, not %s' % (obs.dtype,))
+        raise ValueError('%s: obs rows are float32 or bfloat16, not %s' % (who, obs.dtype))
     T = int(obs.shape[0])
     env._chk(obs, (T, n, 9), obs.dtype, 'obs')
     env._chk(done, (T, n), torch.uint8, 'done')
     env._chk(z, (3, n), f32, 'z')
-    if out is None:
-        out = (torch.empty((T, n, ad), dtype=f32, device=dev), torch.empty((3, n), dtype=f32, device=dev))
-    act, z_out = out
-    env._chk(act, (T, n, 7), f32, 'out[0]')
-    env._chk(z_out, (3, n), f32, 'out[1]')
-    io = _lib.ControllerLabelIO()
-    io.struct_size = C.sizeof(_lib.ControllerLabelIO)
+    if more is None:
+        return T, None
+    shapes = ((T, n, 7), (3, n)) + tuple(more)
+    if out is not None and len(out) != len(shapes):
+        raise ValueError('%s: out holds %d buffers' % (who, len(shapes)))
+    blk = env._blocks(tuple((j, shape, f32) for j, shape in enumerate(shapes)), out)
+    return T, tuple(blk[j] for j in range(len(shapes)))
+
+
+def _label_io(io, T, obs, done, z, z_out, act):
+    """The fields the four label io structs share, into a new one of them."""
+    io.struct_size = C.sizeof(io)
     io.T = T
     io.obs = obs.data_ptr()
-    io.obs_dtype = 1 if obs.dtype == torch.bfloat16 else 0
+    io.obs_dtype = 1 if obs.dtype == _torch().bfloat16 else 0
     io.done = done.data_ptr() if done is not None else None
     io.z_in = z.data_ptr() if z is not None else None
-    io.z_out, io.act = z_out.data_ptr(), act.data_ptr()
-    _lib.check(env.lib.dpenv_controller_label(env._h, C.byref(io), env._stream()), env._h)
-    return act, z_out
+    io.z_out = z_out.data_ptr()
+    io.act = act.data_ptr() if act is not None else None
+    return io
 
 
 def qp_allocator_struct(params=None):
@@ -405,54 +383,32 @@ def controller_label_qp(env, obs, done=None, z=None, x=None, params=None, out=No
     Each lane checks its own row: a refused one runs the rest allocator (zero thrust, azimuths held), reports a NaN objective and sets
     its byte of refused (a uint8 tensor [n], or None).  With neither flown nor table the call is dpenv_controller_label_qp itself."""
     torch = _torch()
-    n, ad = env.n_envs, env.num_actions
-    dev, f32 = env.device, torch.float32
+    n, f32 = env.n_envs, torch.float32
     if table is not None and params is not None:
         raise ValueError('controller_label_qp: params or table, not both')
     if table is None and (iterations is not None or refused is not None):
         raise ValueError('controller_label_qp: iterations and refused go with table (params carries its own iterations)')
-    if not isinstance(obs, torch.Tensor) or obs.dim() != 3:
-        raise ValueError('controller_label_qp: obs is a tensor [T, n, 9]')
-    if obs.dtype not in (torch.float32, torch.bfloat16):
-        raise ValueError('controller_label_qp: obs rows are float32 or bfloat16, not %s' % (obs.dtype,))
-    T = int(obs.shape[0])
-    env._chk(obs, (T, n, 9), obs.dtype, 'obs')
-    env._chk(done, (T, n), torch.uint8, 'done')
-    env._chk(z, (3, n), f32, 'z')
+    T, (act, z_out, x_out) = _label_front('controller_label_qp', env, obs, done, z, out, more=((5, n),))
     env._chk(x, (5, n), f32, 'x')
-    if out is None:
-        out = (torch.empty((T, n, ad), dtype=f32, device=dev), torch.empty((3, n), dtype=f32, device=dev),
-               torch.empty((5, n), dtype=f32, device=dev))
-    act, z_out, x_out = out
-    env._chk(act, (T, n, 7), f32, 'out[0]')
-    env._chk(z_out, (3, n), f32, 'out[1]')
-    env._chk(x_out, (5, n), f32, 'out[2]')
-    J = torch.empty((T, n), dtype=f32, device=dev) if cost else None
+    J = torch.empty((T, n), dtype=f32, device=env.device) if cost else None
     q = qp_allocator_struct(params) if params is not None else None
     ex = flown is not None or table is not None
+    io = _label_io(_lib.ControllerLabelQpExIO() if ex else _lib.ControllerLabelQpIO(), T, obs, done, z, z_out, act)
+    io.x_in = x.data_ptr() if x is not None else None
+    io.x_out = x_out.data_ptr()
+    io.cost = J.data_ptr() if cost else None
+    io.q = C.pointer(q) if q is not None else None
+    call = env.lib.dpenv_controller_label_qp
     if ex:
         env._chk(flown, (T, n, 7), f32, 'flown')
         env._chk(table, (32, n), f32, 'table')
         env._chk(refused, (n,), torch.uint8, 'refused')
-    io = _lib.ControllerLabelQpExIO() if ex else _lib.ControllerLabelQpIO()
-    io.struct_size = C.sizeof(io)
-    io.T = T
-    io.obs = obs.data_ptr()
-    io.obs_dtype = 1 if obs.dtype == torch.bfloat16 else 0
-    io.done = done.data_ptr() if done is not None else None
-    io.z_in = z.data_ptr() if z is not None else None
-    io.x_in = x.data_ptr() if x is not None else None
-    io.z_out, io.x_out, io.act = z_out.data_ptr(), x_out.data_ptr(), act.data_ptr()
-    io.cost = J.data_ptr() if cost else None
-    io.q = C.pointer(q) if q is not None else None
-    if ex:
         io.flown = flown.data_ptr() if flown is not None else None
         io.qp_table = table.data_ptr() if table is not None else None
         io.iterations = (16 if iterations is None else int(iterations)) if table is not None else 0
         io.refused_out = refused.data_ptr() if refused is not None else None
-        _lib.check(env.lib.dpenv_controller_label_qp_ex(env._h, C.byref(io), env._stream()), env._h)
-        return (act, z_out, x_out, J) if cost else (act, z_out, x_out)
-    _lib.check(env.lib.dpenv_controller_label_qp(env._h, C.byref(io), env._stream()), env._h)
+        call = env.lib.dpenv_controller_label_qp_ex
+    _lib.check(call(env._h, C.byref(io), env._stream()), env._h)
     return (act, z_out, x_out, J) if cost else (act, z_out, x_out)
 
 
@@ -474,7 +430,7 @@ def thrust_alloc_qp(tau, state=None, params=None, dt=0.2, out=None, cost=False, 
     n = int(tau.shape[1])
 
     def chk(t, shape, what):
-        if not isinstance(t, torch.Tensor) or tuple(t.shape) != shape or t.dtype != f32 or t.device != tau.device or not t.is_contiguous():
+        if not _is_on(t, shape, f32, tau.device):
             raise ValueError('thrust_alloc_qp: %s is a contiguous float32 tensor %s on tau\'s device' % (what, list(shape)))
 
     if state is not None:
@@ -485,13 +441,12 @@ def thrust_alloc_qp(tau, state=None, params=None, dt=0.2, out=None, cost=False, 
     chk(act, (n, 7), 'out[0]')
     chk(state_out, (5, n), 'out[1]')
     J = torch.empty((n,), dtype=f32, device=tau.device) if cost else None
-    s = C.c_void_p(torch.cuda.current_stream(tau.device).cuda_stream)
+    s = _lib._s(tau)
     if table is not None:
         if params is not None:
             raise ValueError('thrust_alloc_qp: params or table, not both')
         chk(table, (32, n), 'table')
-        if refused is not None and (not isinstance(refused, torch.Tensor) or tuple(refused.shape) != (n,) or refused.dtype != torch.uint8
-                                    or refused.device != tau.device or not refused.is_contiguous()):
+        if refused is not None and not _is_on(refused, (n,), torch.uint8, tau.device):
             raise ValueError('thrust_alloc_qp: refused is a contiguous uint8 tensor [%d] on tau\'s device' % n)
         with torch.cuda.device(tau.device):
             _lib.check(lib.dpenv_thrust_alloc_qp_table(C.c_void_p(table.data_ptr()), 16 if iterations is None else int(iterations), float(dt),
@@ -533,9 +488,9 @@ def _nn_alloc_map(who, tau, out, raw, struct, call):
     if raw and p is None:
         p = torch.empty((n, 6), dtype=f32, device=tau.device)
     for t, shape, what in ((act, (n, 7), 'action'), (p, (n, 6), 'raw')):
-        if t is not None and (tuple(t.shape) != shape or t.dtype != f32 or t.device != tau.device or not t.is_contiguous()):
+        if t is not None and not _is_on(t, shape, f32, tau.device):
             raise ValueError('%s: the %s buffer is a contiguous float32 tensor %s on tau\'s device' % (who, what, list(shape)))
-    s = C.c_void_p(torch.cuda.current_stream(tau.device).cuda_stream)
+    s = _lib._s(tau)
     with torch.cuda.device(tau.device):
         _lib.check(call(st, C.c_void_p(tau.data_ptr()), C.c_void_p(act.data_ptr()), C.c_void_p(p.data_ptr()) if p is not None else None, n, s))
     return (act, p) if raw else act
@@ -663,14 +618,7 @@ def controller_label_nn(env, obs, done=None, z=None, net=None, out=None, raw=Fal
         raise ValueError('controller_label_nn: the wrench-only scan (act=False) takes no net and no constants')
     if net is None and constants:
         raise ValueError('controller_label_nn: constants go with net (net=None labels with the network and constants the env has in force)')
-    if not isinstance(obs, torch.Tensor) or obs.dim() != 3:
-        raise ValueError('controller_label_nn: obs is a tensor [T, n, 9]')
-    if obs.dtype not in (torch.float32, torch.bfloat16):
-        raise ValueError('controller_label_nn: obs rows are float32 or bfloat16, not %s' % (obs.dtype,))
-    T = int(obs.shape[0])
-    env._chk(obs, (T, n, 9), obs.dtype, 'obs')
-    env._chk(done, (T, n), torch.uint8, 'done')
-    env._chk(z, (3, n), f32, 'z')
+    T, _ = _label_front('controller_label_nn', env, obs, done, z)
     want = [('act', (T, n, 7), bool(act)), ('z', (3, n), True), ('raw', (T, n, 6), bool(raw)), ('tau', (T, n, 3), bool(tau))]
     names = [w[0] for w in want if w[2] or w[0] == 'act']
     if out is not None and len(out) != len(names):
@@ -689,15 +637,7 @@ def controller_label_nn(env, obs, done=None, z=None, net=None, out=None, raw=Fal
     if net is not None:
         from .deploy import nn_allocator_params
         a, keep = nn_allocator_struct(nn_net_to(net, dev), nn_allocator_params(net, **constants), dev)
-    io = _lib.ControllerLabelNnIO()
-    io.struct_size = C.sizeof(_lib.ControllerLabelNnIO)
-    io.T = T
-    io.obs = obs.data_ptr()
-    io.obs_dtype = 1 if obs.dtype == torch.bfloat16 else 0
-    io.done = done.data_ptr() if done is not None else None
-    io.z_in = z.data_ptr() if z is not None else None
-    io.z_out = buf['z'].data_ptr()
-    io.act = buf['act'].data_ptr() if act else None
+    io = _label_io(_lib.ControllerLabelNnIO(), T, obs, done, z, buf['z'], buf['act'])
     io.raw = buf['raw'].data_ptr() if raw else None
     io.tau_out = buf['tau'].data_ptr() if tau else None
     io.a = C.pointer(a) if a is not None else None

@@ -7,30 +7,8 @@ one trajectory in host NumPy arrays; here the env kernel writes observation / re
 env column, and the advantage statistics are two device reductions with an optional all-reduce in between
 (the two MPI all-reduces of mpi_statistics_scalar).
 """
-import ctypes as C
-
 from . import _lib
-
-
-def _torch():
-    import torch
-    return torch
-
-
-def _s(t):
-    return C.c_void_p(_torch().cuda.current_stream(t.device).cuda_stream)
-
-
-def _p(t):
-    return None if t is None else C.c_void_p(t.data_ptr())
-
-
-def _req(t, shape, dtype, what):
-    if t is None:
-        return
-    if tuple(t.shape) != tuple(shape) or t.dtype != dtype or not t.is_contiguous() or not t.is_cuda:
-        raise ValueError('%s must be a contiguous cuda %s tensor of shape %s' % (what, dtype, tuple(shape)))
-
+from ._lib import _p, _req, _s, _torch
 
 _ws_cache = {}
 

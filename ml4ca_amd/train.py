@@ -15,16 +15,12 @@ import math
 import numpy as np
 
 from . import _lib
+from ._lib import _p, _req, _s, _torch
 from ._num import _fma32          # (the exact host fmaf; deploy.BatchedNNAllocator shares it)
 
 HIDDEN = 80
 NSTAT_ACTOR, NSTAT_CRITIC = 4, 1          # pi_loss, approx_kl, clip_frac, mean_ratio | v_loss
 ROWS_PER_TILE, MAX_WORKGROUPS = 64, 256   # the gradient kernel's grid: min(ceil(count / 64), 256) workgroups
-
-
-def _torch():
-    import torch
-    return torch
 
 
 def grid(count):
@@ -95,21 +91,6 @@ def workspace_bytes(shape, max_count):
     out = C.c_int64(0)
     _lib.check(_lib.load().dpenv_train_workspace_bytes(C.byref(shape), int(max_count), C.byref(out)))
     return int(out.value)
-
-
-def _p(t):
-    return None if t is None else C.c_void_p(t.data_ptr())
-
-
-def _s(t):
-    return C.c_void_p(_torch().cuda.current_stream(t.device).cuda_stream)
-
-
-def _req(t, shape, dtype, what):
-    if t is None:
-        return
-    if (shape is not None and tuple(t.shape) != tuple(shape)) or t.dtype != dtype or not t.is_contiguous() or not t.is_cuda:
-        raise ValueError('%s must be a contiguous cuda %s tensor%s' % (what, dtype, '' if shape is None else ' of shape %s' % (tuple(shape),)))
 
 
 def _grad_call(actor, theta, obs, act, adv, logp_old, clip, idx, out, workspace, leak, stop_flag, count, loss=None):
@@ -434,6 +415,42 @@ def adam_step_ref(theta, grad, m, v, step, lr, beta1=0.9, beta2=0.999, eps=1e-8,
 FIT_LOSSES = ('mse', 'wrench')
 
 
+def _steps(iters, draw, grad, buf, adam, average=None, hist=None, stat0=0):
+    """The one step loop of every fit here, `iters` times: idx = draw(k) (an int32 index tensor, or None = every row), grad(idx) writes
+    the gradient and its statistics into buf, average(buf) in place if given (a multi-rank caller's all-reduce), hist[k] = buf[stat0:] if
+    a history is kept (stream-ordered, device to device: the statistics are those BEFORE the step), adam() takes the step."""
+    for k in range(iters):
+        grad(draw(k))
+        if average is not None:
+            average(buf)
+        if hist is not None:
+            hist[k].copy_(buf[stat0:])
+        adam()
+
+
+class _RoundPool(object):
+    """The aggregation pool of the round drivers (PPOUpdater.dagger, fit_nn_allocator_on_policy): `rounds` flights of T x n rows each, of
+    which the last `keep` stay (None: all).  Checks the counts under the caller's name; round r writes slot r % keep of a preallocated
+    [keep * T * n, w] block, and the first filled(r) rows of the block are then in use."""
+
+    def __init__(self, who, rounds, T, iters, keep, n):
+        rounds, T, iters = int(rounds), int(T), int(iters)
+        if rounds < 1 or T < 1 or iters < 1:
+            raise ValueError('%s: rounds, T and iters are >= 1' % who)
+        keep = rounds if keep is None else int(keep)
+        if keep < 1:
+            raise ValueError('%s: keep >= 1' % who)
+        self.rounds, self.T, self.iters, self.keep, self.n, self.R = rounds, T, iters, min(keep, rounds), n, T * n
+
+    def slot(self, block, r):
+        """Round r's rows of block [keep * T * n, w] as [T, n, w]."""
+        s = r % self.keep
+        return block[s * self.R:(s + 1) * self.R].view(self.T, self.n, -1)
+
+    def filled(self, r):
+        return min(r + 1, self.keep) * self.R
+
+
 def nn_allocator_init(in_dim, seed):
     """The flat float32 start of fit_nn_allocator: glorot-uniform kernels from numpy.random.RandomState(seed), zero biases
     (tf.layers.dense's default, as policy.ActorCritic), a zero log_std tail."""
@@ -506,7 +523,6 @@ def fit_nn_allocator(dataset, in_dim=9, iters=200, lr=1e-3, minibatch=256, seed=
         tau = torch.cat([tau, torch.zeros_like(tau)], 1).contiguous()
     qp = alloc_loss_params(alloc_loss)
     theta = torch.as_tensor(nn_allocator_init(in_dim, seed)).to(device) if init is None else init.to(device).clone()
-    P = layout(in_dim, 6, True)['P']
     m, v = torch.zeros(P, dtype=f32, device=device), torch.zeros(P, dtype=f32, device=device)
     step = torch.zeros(1, dtype=torch.int32, device=device)
     sh = make_shape(in_dim, 6, True, leak=leak)
@@ -521,12 +537,11 @@ def fit_nn_allocator(dataset, in_dim=9, iters=200, lr=1e-3, minibatch=256, seed=
         return None if tau is None else [float(t) for t in allocation_grad(theta, x, tau, qp, out=g, workspace=ws, leak=leak)[P:P + 2]]
 
     mse0, wr0 = whole('mse'), whole('wrench')
-    for it in range(int(iters)):
-        if loss == 'mse':
-            imitation_grad(theta, x, y, loss='mse', idx=idx_all[it], out=g, workspace=ws, leak=leak, count=count)
-        else:
-            allocation_grad(theta, x, tau, qp, idx=idx_all[it], out=g, workspace=ws, leak=leak, count=count)
-        adam_step(theta, g, m, v, step, lr)
+    if loss == 'mse':
+        grad = lambda idx: imitation_grad(theta, x, y, loss='mse', idx=idx, out=g, workspace=ws, leak=leak, count=count)
+    else:
+        grad = lambda idx: allocation_grad(theta, x, tau, qp, idx=idx, out=g, workspace=ws, leak=leak, count=count)
+    _steps(int(iters), lambda k: idx_all[k], grad, g, lambda: adam_step(theta, g, m, v, step, lr))
     mse1, wr1 = whole('mse'), whole('wrench')
     tW, tb, _ = unflatten(theta, in_dim, 6, True)
     first = lambda s, k: None if s is None else s[k]
@@ -594,18 +609,12 @@ def fit_nn_allocator_on_policy(env, rounds, T, iters, base=None, keep=None, lr=1
     the rounds."""
     torch = _torch()
     from .policy import controller_label_nn, controller_rollout
-    rounds, T, iters = int(rounds), int(T), int(iters)
-    if rounds < 1 or T < 1 or iters < 1:
-        raise ValueError('fit_nn_allocator_on_policy: rounds, T and iters are >= 1')
+    n, dev, f32 = env.n_envs, env.device, torch.float32
+    rp = _RoundPool('fit_nn_allocator_on_policy', rounds, T, iters, keep, n)
     if env.dp_controller is None:
         raise ValueError('fit_nn_allocator_on_policy: the baseline DP controller forms the wrench; env.set_dp_controller() first')
-    keep = rounds if keep is None else int(keep)
-    if keep < 1:
-        raise ValueError('fit_nn_allocator_on_policy: keep >= 1')
-    keep = min(keep, rounds)
-    n, dev, f32 = env.n_envs, env.device, torch.float32
-    R = T * n
-    pool = torch.empty((keep * R, 3), dtype=f32, device=dev)
+    rounds, T, iters, keep = rp.rounds, rp.T, rp.iters, rp.keep
+    pool = torch.empty((keep * rp.R, 3), dtype=f32, device=dev)
     zbuf = torch.empty((3, n), dtype=f32, device=dev)
     fit_kw = dict(in_dim=in_dim, iters=iters, lr=lr, minibatch=minibatch, leak=leak, device=dev, loss='wrench', alloc_loss=alloc_loss)
     base_rec, bx, bt = None, None, None
@@ -624,9 +633,8 @@ def fit_nn_allocator_on_policy(env, rounds, T, iters, base=None, keep=None, lr=1
         env.set_nn_allocator(dict(W=list(tW), b=list(tb), leak=float(leak)))
         z = env.get_dp_controller_state()
         out = controller_rollout(env, T, out=out)
-        slot = r % keep
-        controller_label_nn(env, out['obs'], out['done'], z=z, act=False, tau=True, out=(None, zbuf, pool[slot * R:(slot + 1) * R].view(T, n, 3)))
-        filled = min(r + 1, keep) * R
+        controller_label_nn(env, out['obs'], out['done'], z=z, act=False, tau=True, out=(None, zbuf, rp.slot(pool, r)))
+        filled = rp.filled(r)
         flown = pool[:filled]
         flown = flown[torch.isfinite(flown).all(1)]
         ds = nn_wrench_rows(flown, in_dim)
@@ -682,33 +690,54 @@ class PPOUpdater(object):
             self._ws = _torch().empty((need + 3) // 4, dtype=_torch().float32, device=self.device)
         return self._ws
 
+    def _batch(self, obs, minibatch):
+        """(rows N, rows per gradient step, the workspace for them)."""
+        N = obs.shape[0]
+        mb = N if minibatch is None else min(int(minibatch), N)
+        return N, mb, self._workspace(mb)
+
+    def _net(self, actor):
+        if actor:
+            return self.pi_theta, self.pi_grad, self.pi_m, self.pi_v, self.pi_steps, self.P_pi
+        return self.v_theta, self.v_grad, self.v_m, self.v_v, self.v_steps, self.P_v
+
+    def _loop(self, actor, grad, iters, N, mb, lr, average, hist=None, **gate):
+        """_steps on the actor's or the critic's flat vector: indices drawn with torch.randint as the torch loop draws them (only when
+        mb < N), grad(idx) into that net's gradient buffer, Adam at lr with this updater's betas and eps (gate: adam_step's gate)."""
+        torch = _torch()
+        theta, g, m, v, steps, P = self._net(actor)
+        b1, b2 = self.betas
+        _steps(iters, lambda k: torch.randint(0, N, (mb,), device=self.device).to(torch.int32) if mb < N else None, grad, g,
+               lambda: adam_step(theta, g, m, v, steps, lr, b1, b2, self.eps, **gate), average, hist, P)
+
+    def _read(self, actor, hist, iters, keep_optimizer_state):
+        """A warm start's tail: the one read of its history, then that net's Adam m, v and step counter are zeroed, so PPO starts with
+        a fresh optimiser - or, kept, the host's count of the actor's steps is advanced (ungated: every queued step was taken)."""
+        out = hist.cpu()
+        _, _, m, v, steps, _ = self._net(actor)
+        if not keep_optimizer_state:
+            m.zero_()
+            v.zero_()
+            steps.zero_()
+        if actor:
+            self._pi_steps_host = self._pi_steps_host + iters if keep_optimizer_state else 0
+        return out
+
     def update(self, obs, act, adv, ret, logp_old, iters=80, minibatch=None, average=None):
         """Queue `iters` actor steps (gated on approx_kl > 1.5 target_kl, ppo.py:267-270) and `iters` critic steps, then read
         (pi_iters, kl, v_loss) back ONCE.  obs [N, od], act [N, ad], adv / ret / logp_old [N], float32 on the device.
         minibatch: rows per gradient step, drawn with torch.randint as the torch loop draws them (None or >= N: every row).
         average: callable applied in place to the flat [P + nstat] gradient-and-statistics buffer between gradient and Adam
         (a multi-rank caller's all-reduce)."""
-        torch = _torch()
-        N = obs.shape[0]
-        mb = N if minibatch is None else min(int(minibatch), N)
-        ws = self._workspace(mb)
-        b1, b2 = self.betas
-        kl_slot = self.pi_grad[self.P_pi + 1:self.P_pi + 2]
+        N, mb, ws = self._batch(obs, minibatch)
+        leak = self.ac.leak
         self.stop.zero_()
-        for _ in range(iters):
-            idx = torch.randint(0, N, (mb,), device=self.device).to(torch.int32) if mb < N else None
-            ppo_actor_grad(self.pi_theta, obs, act, adv, logp_old, self.clip, idx=idx, out=self.pi_grad, workspace=ws, leak=self.ac.leak,
-                           stop_flag=self.stop, count=mb)
-            if average is not None:
-                average(self.pi_grad)
-            adam_step(self.pi_theta, self.pi_grad, self.pi_m, self.pi_v, self.pi_steps, self.pi_lr, b1, b2, self.eps, gate_kl=kl_slot,
-                      kl_limit=1.5 * self.target_kl, stop_flag=self.stop)
-        for _ in range(iters):
-            idx = torch.randint(0, N, (mb,), device=self.device).to(torch.int32) if mb < N else None
-            value_grad(self.v_theta, obs, ret, idx=idx, out=self.v_grad, workspace=ws, leak=self.ac.leak, count=mb)
-            if average is not None:
-                average(self.v_grad)
-            adam_step(self.v_theta, self.v_grad, self.v_m, self.v_v, self.v_steps, self.v_lr, b1, b2, self.eps)
+        self._loop(True, lambda idx: ppo_actor_grad(self.pi_theta, obs, act, adv, logp_old, self.clip, idx=idx, out=self.pi_grad, workspace=ws,
+                                                    leak=leak, stop_flag=self.stop, count=mb),
+                   iters, N, mb, self.pi_lr, average, gate_kl=self.pi_grad[self.P_pi + 1:self.P_pi + 2], kl_limit=1.5 * self.target_kl,
+                   stop_flag=self.stop)
+        self._loop(False, lambda idx: value_grad(self.v_theta, obs, ret, idx=idx, out=self.v_grad, workspace=ws, leak=leak, count=mb),
+                   iters, N, mb, self.v_lr, average)
         self._out[0] = self.pi_steps[0]
         self._out[1] = self.pi_grad[self.P_pi + 1]
         self._out[2] = self.v_grad[self.P_v]
@@ -723,29 +752,12 @@ class PPOUpdater(object):
         the device; indices drawn as `update` draws them.  Returns the [iters, 4] history (chosen loss, weighted NLL, weighted MSE, 0 per
         step, each measured BEFORE that step's Adam), read back once.  Unless keep_optimizer_state, the actor's Adam m, v and step counter
         are then zeroed, so PPO starts with a fresh optimiser."""
-        torch = _torch()
-        N = obs.shape[0]
-        mb = N if minibatch is None else min(int(minibatch), N)
-        ws = self._workspace(mb)
-        b1, b2 = self.betas
-        lr = self.pi_lr if lr is None else float(lr)
-        hist = torch.zeros((iters, NSTAT_ACTOR), dtype=torch.float32, device=self.device)
-        for k in range(iters):
-            idx = torch.randint(0, N, (mb,), device=self.device).to(torch.int32) if mb < N else None
-            imitation_grad(self.pi_theta, obs, act, loss=loss, weight=weight, idx=idx, out=self.pi_grad, workspace=ws, leak=self.ac.leak, count=mb)
-            if average is not None:
-                average(self.pi_grad)
-            hist[k].copy_(self.pi_grad[self.P_pi:])                    # stream-ordered, device to device
-            adam_step(self.pi_theta, self.pi_grad, self.pi_m, self.pi_v, self.pi_steps, lr, b1, b2, self.eps)
-        out = hist.cpu()                                               # the one read
-        if not keep_optimizer_state:
-            self.pi_m.zero_()
-            self.pi_v.zero_()
-            self.pi_steps.zero_()
-            self._pi_steps_host = 0
-        else:
-            self._pi_steps_host += iters                               # ungated: every queued step was taken
-        return out
+        N, mb, ws = self._batch(obs, minibatch)
+        hist = _torch().zeros((iters, NSTAT_ACTOR), dtype=_torch().float32, device=self.device)
+        self._loop(True, lambda idx: imitation_grad(self.pi_theta, obs, act, loss=loss, weight=weight, idx=idx, out=self.pi_grad, workspace=ws,
+                                                    leak=self.ac.leak, count=mb),
+                   iters, N, mb, self.pi_lr if lr is None else float(lr), average, hist)
+        return self._read(True, hist, iters, keep_optimizer_state)
 
     # ---- DAgger: expert labels on the states the ACTOR visits, aggregated over rounds (Ross et al. 2011) ----
     def dagger(self, env, rounds, T, iters, minibatch=None, loss='mse', keep=None, sample=False, reset_at_end=False, lr=None, average=None,
@@ -788,9 +800,8 @@ class PPOUpdater(object):
         kernels take float32 rows: a bf16 env raises ValueError)."""
         torch = _torch()
         from .policy import controller_label, controller_label_nn, controller_label_qp, policy_rollout
-        rounds, T, iters = int(rounds), int(T), int(iters)
-        if rounds < 1 or T < 1 or iters < 1:
-            raise ValueError('dagger: rounds, T and iters are >= 1')
+        rp = _RoundPool('dagger', rounds, T, iters, keep, env.n_envs)
+        rounds, T, iters, keep = rp.rounds, rp.T, rp.iters, rp.keep
         if expert not in ('pinv', 'qp', 'nn'):
             raise ValueError("dagger: expert is 'pinv', 'qp' or 'nn', not %r" % (expert,))
         if thruster_state not in ('own', 'flown'):
@@ -803,15 +814,10 @@ class PPOUpdater(object):
             raise ValueError('dagger: the gradient kernels take float32 rows; make the env with float32 obs rows (got %s)' % (env.obs_torch_dtype,))
         if env.dp_controller is None:
             raise ValueError('dagger: the baseline DP controller labels the rows; env.set_dp_controller() first')
-        keep = rounds if keep is None else int(keep)
-        if keep < 1:
-            raise ValueError('dagger: keep >= 1')
-        keep = min(keep, rounds)
         n, od, ad = env.n_envs, env.num_states, env.num_actions
         dev, f32 = self.device, torch.float32
-        R = T * n
-        data_obs = torch.empty((keep * R, od), dtype=f32, device=dev)
-        data_act = torch.empty((keep * R, ad), dtype=f32, device=dev)
+        data_obs = torch.empty((keep * rp.R, od), dtype=f32, device=dev)
+        data_act = torch.empty((keep * rp.R, ad), dtype=f32, device=dev)
         self.dagger_data = dict(obs=data_obs, act=data_act, filled=0, T=T, n=n, keep=keep)
         z = torch.zeros((3, n), dtype=f32, device=dev)
         if expert == 'qp':
@@ -823,8 +829,7 @@ class PPOUpdater(object):
         for r in range(rounds):
             self.ac.upload(env, **(upload or {}))
             out = policy_rollout(env, T, out=out, sample=sample, reset_at_end=reset_at_end)
-            slot = r % keep
-            labels = data_act[slot * R:(slot + 1) * R].view(T, n, ad)
+            labels = rp.slot(data_act, r)
             if expert == 'qp':                                         # neither flown nor a table: the call of the driver before them
                 controller_label_qp(env, out['obs'], out['done'], z=z, x=x, params=qp if qp_table is None else None, out=(labels, z, x),
                                     flown=out['act'] if thruster_state == 'flown' else None, table=qp_table,
@@ -837,8 +842,8 @@ class PPOUpdater(object):
                 controller_label(env, out['obs'], out['done'], z=z, out=(labels, z))
             if reset_at_end:
                 z.zero_()
-            data_obs[slot * R:(slot + 1) * R].copy_(out['obs'].view(R, od))
-            filled = min(r + 1, keep) * R
+            rp.slot(data_obs, r).copy_(out['obs'])
+            filled = rp.filled(r)
             self.dagger_data['filled'] = filled
             flight[r, 0] = out['rew'].mean()
             flight[r, 1] = ((out['act'] - labels) ** 2).mean()
@@ -852,23 +857,8 @@ class PPOUpdater(object):
     def pretrain_critic(self, obs, ret, iters, minibatch=None, lr=None, average=None, keep_optimizer_state=False):
         """The critic's half of the warm start: `iters` x (value_grad -> adam_step) on ret [N] (the demonstration's discounted returns).
         Returns the [iters, 1] history of v_loss, read back once; the critic's Adam state is then zeroed unless keep_optimizer_state."""
-        torch = _torch()
-        N = obs.shape[0]
-        mb = N if minibatch is None else min(int(minibatch), N)
-        ws = self._workspace(mb)
-        b1, b2 = self.betas
-        lr = self.v_lr if lr is None else float(lr)
-        hist = torch.zeros((iters, NSTAT_CRITIC), dtype=torch.float32, device=self.device)
-        for k in range(iters):
-            idx = torch.randint(0, N, (mb,), device=self.device).to(torch.int32) if mb < N else None
-            value_grad(self.v_theta, obs, ret, idx=idx, out=self.v_grad, workspace=ws, leak=self.ac.leak, count=mb)
-            if average is not None:
-                average(self.v_grad)
-            hist[k].copy_(self.v_grad[self.P_v:])
-            adam_step(self.v_theta, self.v_grad, self.v_m, self.v_v, self.v_steps, lr, b1, b2, self.eps)
-        out = hist.cpu()
-        if not keep_optimizer_state:
-            self.v_m.zero_()
-            self.v_v.zero_()
-            self.v_steps.zero_()
-        return out
+        N, mb, ws = self._batch(obs, minibatch)
+        hist = _torch().zeros((iters, NSTAT_CRITIC), dtype=_torch().float32, device=self.device)
+        self._loop(False, lambda idx: value_grad(self.v_theta, obs, ret, idx=idx, out=self.v_grad, workspace=ws, leak=self.ac.leak, count=mb),
+                   iters, N, mb, self.v_lr if lr is None else float(lr), average, hist)
+        return self._read(False, hist, iters, keep_optimizer_state)

@@ -516,7 +516,11 @@ typedef struct dpenv_integral_action {
  * NaN, negative bounds or box, a negative dwell, and the simple variant (the node refuses it too, rl_allocator.py:126). */
 int dpenv_set_integral_action(dpenv_handle h, const dpenv_integral_action* ia, dpenv_stream s);
 /* The checkpoint path of the action's state, next to dpenv_get_state / dpenv_get_rng_counters: I_out / I_in device float[3][n_envs],
- * count device int32[n_envs]; either pointer may be NULL.  DPENV_EINVAL while the action is off. */
+ * count device int32[n_envs]; either pointer may be NULL.  DPENV_EINVAL while the action is off.  The library produces counts in
+ * [0, D] only; count_in is copied as it is (a device block: nothing is read back to check it), and the law's c = min(c + 1, D) then
+ * does this: a count above D acts as D from the next update on; a negative count -k waits k updates longer before I integrates (the
+ * dwell is D + k); I_in is taken as it is and clipped to the bound at the next integrating update.  count_in must not be INT32_MAX:
+ * c + 1 would overflow, which C leaves undefined.  tests/test_gpu_control_edges.py pins -3, D + 1, 1000 and INT32_MAX - 1. */
 int dpenv_get_integral_state(dpenv_handle h, float* I_out, int32_t* count_out, dpenv_stream s);
 int dpenv_set_integral_state(dpenv_handle h, const float* I_in, const int32_t* count_in, dpenv_stream s);
 /* dpenv_policy_rollout with the action on (required), plus integ_out: device float[T][n][3], the I added to obs[t] (NULL = not written),
@@ -564,7 +568,11 @@ int dpenv_set_reference_filter(dpenv_handle h, const dpenv_reference_filter* rf,
  * float[3][n_envs], the targets.  Either pointer may be NULL.  DPENV_EINVAL while the filter is off. */
 int dpenv_get_reference_filter_state(dpenv_handle h, float* x_out, float* r_out, dpenv_stream s);
 int dpenv_set_reference_filter_state(dpenv_handle h, const float* x_in, const float* r_in, dpenv_stream s);
-/* Pure host function: the f32 coefficients the kernels use for control period dt: phi_out[j] = Phi_j row-major, gam_out[j] = Gamma_j. */
+/* Pure host function: the f32 coefficients the kernels use for control period dt: phi_out[j] = Phi_j row-major, gam_out[j] = Gamma_j.
+ * No upper limit is put on omega.  Each coefficient is within 2^-24 |c| + a of the exact matrix exponential, a the f64 recipe's own
+ * absolute error (tests/control_edges.py measures it against 60 digits: below 3e-14 for omega <= 1.51, 2e-12 at omega = 10, 2e-9 at
+ * omega = 50 with zeta = 1e-3, dt = 0.2).  From omega dt of about 40 on, the entries that decay like exp(-omega dt) are smaller than a:
+ * they carry an absolute meaning only, and only that form is tested there. */
 int dpenv_reference_filter_coeffs(const dpenv_reference_filter* rf, float dt, float phi_out[3][9], float gam_out[3][3]);
 /* dpenv_policy_rollout with the filter on (required), plus ref_out: device float[T][n][3], the eta_d that obs[t] was formed against (the
  * env's reference when obs[t] was formed), and integ_out as in dpenv_policy_rollout_integral (needs the integral action on).  Either may
@@ -722,7 +730,24 @@ int dpenv_score_wear_summary(const void* wear, int32_t n, double* out, void* wor
  * the shared hull, the thrust-loss preset, per-env hulls and their randomisation, constant, drifting and per-episode currents, auto-reset,
  * with or without the reference filter.  Vessel classes (n_classes > 1), any other variant and a handle with the integral action on:
  * DPENV_EINVAL with the set named.  The controller is a launch form, not a mode: dpenv_step, dpenv_rollout and dpenv_policy_rollout keep
- * working while it is on (they leave z alone).  ml4ca_amd.deploy.BatchedDPController is the host statement of the law. */
+ * working while it is on (they leave z alone).  ml4ca_amd.deploy.BatchedDPController is the host statement of the law.
+ * AT THE EDGES of the numbers (tests/control_edges.py flies them).  The allocation's domain: every f_m finite and, per stern pod,
+ * Fx Fx + Fy Fy inside f32's normal range or exactly 0 - |f| below about 1.3e19 and, unless both components are 0, above 2^-63 = 1.1e-19.
+ * Inside it the action is the float64 law's to a few roundings (the bounds are derived in tests/control_edges.py).  Outside it the law
+ * is the f32 text above and nothing more: from |f| = 1.3e19 on the sum of squares overflows, F = inf, n_i saturates at 1 and the heads
+ * are (+-0, +-0) - not a unit vector - or NaN where a component is itself inf; below 2^-63 the squares round as subnormals and from
+ * 2^-75 = 2.6e-23 down to 0, F = 0 and the heads are (0, 1) whatever f_eps is (with f_eps = 0 a force that small keeps the direction
+ * ahead).  At tau = 0 and f_eps = 0, F = 0 is not > f_eps: the heads are (0, 1), never 0 / 0.  tau_max_j = +inf is accepted (only NaN
+ * and negative bounds are refused): that axis is not clipped, and dpenv_thrust_alloc takes any tau, so the domain is the caller's to
+ * keep.  Every clip is fminf(fmaxf(v, -b), b), which DROPS a NaN: an observation with a NaN in e_j gives z_j = -z_bound_j and
+ * tau_j = -tau_max_j on that row, a NaN in nu_j gives tau_j = -tau_max_j and leaves z_j alone, and the rows behind it are finite again;
+ * a NaN wrench handed to the allocation commands [-1, 1, 1, 0, 1, 0, 1].  e_j = +-inf puts z_j on +-z_bound_j and, for kp_j > 0, tau_j
+ * on -+tau_max_j (kp_j < 0: the other sign; kp_j = 0: 0 * inf is NaN and tau_j = -tau_max_j).  The integral action's counts outside
+ * [0, D] and the reference filter's omega are treated at dpenv_set_integral_state and dpenv_reference_filter_coeffs.
+ * No row of the law's own flights is non-finite; these are the answers for rows some other flight wrote.  With a bound of exactly 0
+ * the clip returns a zero whose sign is not defined (fminf and fmaxf may return either of two equal zeros): z_j and tau_j are 0 in value.
+ * The host statement clips with fmin / fmax in the same nesting and agrees with the device on all of this bit for bit, such a zero's
+ * sign apart. */
 typedef struct dpenv_dp_controller {
     uint32_t struct_size;
     float kp[3], kd[3], ki[3];   /* finite */
@@ -768,7 +793,8 @@ int dpenv_set_dp_controller_state(dpenv_handle h, const float* z_in, dpenv_strea
  * Refused rows: a row is refused if it breaks any condition dpenv_set_dp_controller refuses (non-finite gains, NaN or negative bounds and
  * f_eps, kf <= 0, kr_bow <= 0), has a weight <= 0 or non-finite, a non-finite lever arm, a det that is non-finite or zero, or a non-finite
  * G.  A refused row is packed as the ZERO CONTROLLER - gains, bounds and G all 0, kf = kr_bow = 1, f_eps = 0 - with which the law commands
- * the action [0, 0, 0, 0, 1, 0, 1] at every step; the other rows are not affected.  refused_out: NULL, or a device uint8[n_envs] that
+ * the action [0, 0, 0, 0, 1, 0, 1] at every step, whatever the observation holds, non-finite entries included (equal in VALUE: the
+ * law forms tau = -(0 + 0), so n_bow may be -0.0); the other rows are not affected.  refused_out: NULL, or a device uint8[n_envs] that
  * gets 1 for a refused env and 0 for the others.  The library reads nothing back, does not synchronise and uses no atomics: the caller
  * decides whether to look.
  * While a table is in force dpenv_controller_rollout flies row i on env i: the law above, read with per-env operands (dt stays the

@@ -133,7 +133,7 @@ class BatchedBodyFrameIntegrator(object):
         outside = (e.abs() > self.box).any(dim=1)
         self.count = torch.where(outside, torch.zeros_like(self.count), torch.clamp(self.count + 1, max=self.dwell))
         grow = (~outside) & (self.count >= self.dwell)
-        new = torch.minimum(torch.maximum(self.I + self.step_s * (self.gain * e), -self.bound), self.bound)
+        new = torch.fmin(torch.fmax(self.I + self.step_s * (self.gain * e), -self.bound), self.bound)    # fminf(fmaxf()): a NaN is dropped
         self.I = torch.where(outside[:, None], torch.zeros_like(self.I), torch.where(grow[:, None], new, self.I))
         return e + self.I
 
@@ -463,14 +463,14 @@ class BatchedDPController(object):
         f = [(G[..., m, 0] * tau[:, 0] + G[..., m, 1] * tau[:, 1]) + G[..., m, 2] * tau[:, 2] for m in range(5)]
         kb = xp.where(f[0] >= self.zero, self.kf[..., 0], self.kr_bow)
         nb = xp.copysign(xp.sqrt(xp.abs(f[0]) / kb), f[0])
-        cols = [xp.minimum(xp.maximum(nb / self.hundred, -self.one), self.one)]
+        cols = [xp.fmin(xp.fmax(nb / self.hundred, -self.one), self.one)]       # every clip is the stated fminf(fmaxf()): a NaN is dropped
         sc = []
         with np.errstate(invalid='ignore', divide='ignore'):
             for k in range(2):
                 Fx, Fy = f[1 + 2 * k], f[2 + 2 * k]
                 F = xp.sqrt(Fx * Fx + Fy * Fy)
                 ns = xp.sqrt(F / self.kf[..., 1 + k])
-                cols.append(xp.minimum(ns / self.hundred, self.one))
+                cols.append(xp.fmin(ns / self.hundred, self.one))
                 dirn = F > self.f_eps
                 sc += [xp.where(dirn, Fy / F, self.zero), xp.where(dirn, Fx / F, self.one)]
         return xp.stack(cols + sc, 1)
@@ -483,9 +483,9 @@ class BatchedDPController(object):
             e, nu = e.to(self.dtype), nu.to(self.dtype)
         else:
             e, nu = np.asarray(e, self.dtype), np.asarray(nu, self.dtype)
-        self.z = xp.minimum(xp.maximum(self.z + self.dt * e, -self.zb), self.zb)
+        self.z = xp.fmin(xp.fmax(self.z + self.dt * e, -self.zb), self.zb)
         tau = -((self.kp * e + self.kd * nu) + self.ki * self.z)
-        return xp.minimum(xp.maximum(tau, -self.tmax), self.tmax)
+        return xp.fmin(xp.fmax(tau, -self.tmax), self.tmax)
 
     def act(self, obs):
         return self.allocate(self.wrench(obs))
@@ -1237,8 +1237,14 @@ def label_rows_nn(params_or_table, net, obs, done=None, z=None, dt=0.2, dtype=No
     obs, done, T, n = _label_block('label_rows_nn', obs, done)
     ctrl = BatchedDPController(n, params_or_table, dt=dt, dtype=dtype)
     alloc = BatchedNNAllocator(n, net, dtype=dtype, params=nn_params)
-    (tau, act, raw), z = _label_scan('label_rows_nn', ctrl, obs, done, z, (3, 7, 6),
-                                     lambda t, tau, ended: (tau,) + tuple(alloc.allocate(tau, raw=True)))
+    def stage(t, tau, ended):
+        # the law's clip drops a NaN (z_j = -z_bound_j, tau_j = -tau_max_j); the scan says it again: tau_j = NaN if o_j or o_{3+j} is,
+        # so the rest rule answers such a row.  z_j stays the law's.
+        o = np.asarray(obs[t], ctrl.dtype)
+        tau = np.where(np.isnan(o[:, 0:3]) | np.isnan(o[:, 3:6]), ctrl.dtype.type(np.nan), tau)
+        return (tau,) + tuple(alloc.allocate(tau, raw=True))
+
+    (tau, act, raw), z = _label_scan('label_rows_nn', ctrl, obs, done, z, (3, 7, 6), stage)
     return act, z, raw, tau
 
 
